@@ -13,9 +13,14 @@ GPU; the parent never touches a GPU) unless it already runs under a launcher (WO
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`).  RCCL is mandatory
 for N > 1: if the communicator cannot be created the run fails, it never falls back.
 
-Before anything is timed the GPU result is checked against the CPU oracle (parity gate); a
-mismatch ends the run with a non-zero exit code.  One JSON line on rank 0; `value` = GB/s
-scanned by the whole job (queries/sec beside it).
+A plain run sets up, warms up, times --steps steps and prints one JSON line on rank 0; `value` =
+GB/s scanned by the whole job (queries/sec and `ms_per_step` beside it).  --dump-outputs DIR
+writes the hits of the last timed step as DIR/{index,score,query}.npy (float64 / float32 /
+float64); the inputs depend on the arguments only, so two builds can be compared output for
+output.  --full adds everything else the line used to carry: before anything is timed the GPU
+result is checked against the CPU oracle (parity gate; a mismatch ends the run with a non-zero
+exit code), the live PMC traffic child runs (--traffic), the CPU baselines and the extras
+(config 2 on one GPU; config 4 and the strong-scaling split for N > 1).
 """
 import argparse
 import csv
@@ -291,16 +296,27 @@ def main() -> int:
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--seed", type=int, default=0x07735)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational measurements beside the headline (N = 1: config 2; N > 1: config 4's shape and the strong-scaling split)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity gate against the CPU oracle, live PMC traffic (--traffic), the CPU "
+                         "baselines and the extras.  Without it a run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's hits as DIR/index.npy (float64), DIR/score.npy (float32), "
+                         "DIR/query.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the informational measurements beside the headline (N = 1: config 2; N > 1: config 4's shape and the strong-scaling split)")
     ap.add_argument("--c4-queries", type=int, default=1024, help="N > 1 extras: queries per batch of the config-4 shape")
     ap.add_argument("--inprocess", action="store_true",
                     help="N GPUs inside THIS one process: one store over all of them (ott_store_create_multi; VecStore(devices=[0..N-1])), "
                          "the reference's own single-process shape.  Default for N > 1 (what the driver launches): one process per GPU")
-    ap.add_argument("--traffic", choices=("live", "profile", "off"), default="live",
+    ap.add_argument("--traffic", choices=("live", "profile", "off"), default=None,
                     help="roofline.traffic: 'live' = PMC child runs of this command under rocprofv3 (N = 1 only; falls back to "
-                         "'profile'), 'profile' = the newest committed profiles/roundN/bench_n1_pmc_*.csv, 'off' = null")
+                         "'profile'), 'profile' = the newest committed profiles/roundN/bench_n1_pmc_*.csv, 'off' = null.  "
+                         "Default: 'live' with --full, 'off' without")
     args = ap.parse_args()
+    if args.traffic is None:
+        args.traffic = "live" if args.full else "off"
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -422,29 +438,31 @@ def main() -> int:
         N.check(N.lib().ott_store_sync(store._handle()))
 
     # ---- parity gate: nothing is timed before the GPU result has been checked on this run ----------
+    # (the first query and its count in every run; the comparisons with the oracle with --full)
     parity = {}
     t_par = time.perf_counter()
     hits0 = run(queries[0])
     if hits0.size != args.k:
         raise SystemExit(f"[bench] PARITY FAILED: {hits0.size} hits, expected {args.k}")
-    parity_rescore(hits0, queries[0], args.dim, args.seed)  # (a) every returned score, bit for bit, from regenerated rows
-    parity["rescored_by_oracle"] = int(hits0.size)
     sample = None
-    if world == 1 and not args.inprocess and not args.no_cpu_baseline and args.rows >= SAMPLE_ROWS:
-        # (b) the same query restricted (zonemap-style chunk mask) to the rows the CPU baseline scores anyway: the whole
-        # top-k — indices, order and score bits — against the oracle's answer over those rows
-        import oracle as O
-        sample = cpu_sample(args.dim, args.seed)
-        n_s = sample[0].shape[0]
-        n_chunks = (args.rows + 1023) // 1024
-        cmask = np.zeros(n_chunks, dtype=bool)
-        cmask[: n_s // 1024] = True
-        rq = store.query(queries[0], Metric.Cosine).take(args.k).with_path(Path.Exact).resolve()
-        got, _, _ = store._run(rq, chunk_mask=cmask)
-        ref = O.vec_query(sample[0], queries[0], O.METRIC_COSINE, O.TAKE_MAX, args.k, inv=sample[1], ties=O.TIES_CANONICAL)
-        if not (np.array_equal(got["index"], ref["index"]) and np.array_equal(bits(got["score"]), bits(ref["score"]))):
-            raise SystemExit(f"[bench] PARITY FAILED: top-{args.k} over the first {n_s} rows differs from the oracle\n got {got}\n ref {ref}")
-        parity["topk_vs_oracle_rows"] = int(n_s)
+    if args.full:
+        parity_rescore(hits0, queries[0], args.dim, args.seed)  # (a) every returned score, bit for bit, from regenerated rows
+        parity["rescored_by_oracle"] = int(hits0.size)
+        if world == 1 and not args.inprocess and not args.no_cpu_baseline and args.rows >= SAMPLE_ROWS:
+            # (b) the same query restricted (zonemap-style chunk mask) to the rows the CPU baseline scores anyway: the whole
+            # top-k — indices, order and score bits — against the oracle's answer over those rows
+            import oracle as O
+            sample = cpu_sample(args.dim, args.seed)
+            n_s = sample[0].shape[0]
+            n_chunks = (args.rows + 1023) // 1024
+            cmask = np.zeros(n_chunks, dtype=bool)
+            cmask[: n_s // 1024] = True
+            rq = store.query(queries[0], Metric.Cosine).take(args.k).with_path(Path.Exact).resolve()
+            got, _, _ = store._run(rq, chunk_mask=cmask)
+            ref = O.vec_query(sample[0], queries[0], O.METRIC_COSINE, O.TAKE_MAX, args.k, inv=sample[1], ties=O.TIES_CANONICAL)
+            if not (np.array_equal(got["index"], ref["index"]) and np.array_equal(bits(got["score"]), bits(ref["score"]))):
+                raise SystemExit(f"[bench] PARITY FAILED: top-{args.k} over the first {n_s} rows differs from the oracle\n got {got}\n ref {ref}")
+            parity["topk_vs_oracle_rows"] = int(n_s)
     parity["seconds"] = round(time.perf_counter() - t_par, 2)
 
     for i in range(args.warmup):
@@ -469,6 +487,8 @@ def main() -> int:
         raise SystemExit(f"[bench] {res.size} hits in the timed loop, expected {args.k}")
     if store.last_stats["path_used"] != int(Path.Exact):  # the headline is the exact-order f32 kernel, never the bf16 cascade
         raise SystemExit(f"[bench] the timed loop ran on path {store.last_stats['path_used']}, not on the exact-order kernel")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     rank_kernel_ms = [float(np.mean(kernel_ns)) / 1e6]
     if dist is not None:
@@ -486,7 +506,7 @@ def main() -> int:
     # N > 1 (either launcher): what the 8-GPU node must answer BESIDE the weak-scaling headline — config 4's shape and the metric's
     # own corpus split N ways.  Collective: every rank runs it, rank 0 reports it.  Never inside the timed region above.
     multi_extras = None
-    if (world > 1 or args.inprocess or comm is not None) and not args.no_extras:
+    if (world > 1 or args.inprocess or comm is not None) and args.full and not args.no_extras:
         try:
             multi_extras = multi_gpu_extras(args, store, sharded, comm, world, n_shards, rng, Metric, Path, barrier, dist, torch)
         except SystemExit:
@@ -543,7 +563,7 @@ def main() -> int:
             "value": round(gbs, 2), "unit": "GB/s", "queries_per_sec": round(qps, 2),
             "n_gpus": world * n_shards, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "parity_checked": True, "parity": parity,
+            "parity_checked": args.full, "parity": parity,
             "config": {"workload": f"{args.rows}x{args.dim} f32 VecStore per GPU, single query, Metric::Cosine, take({args.k})",
                        "rows_per_gpu": args.rows, "dim": args.dim, "k": args.k, "nq": 1,
                        "sharding": sharding, "processes": world,
@@ -564,14 +584,14 @@ def main() -> int:
             }
         if multi_extras is not None:
             line["extras"] = multi_extras
-        if world == 1 and comm is None and not args.no_extras and not args.inprocess:
+        if world == 1 and comm is None and args.full and not args.no_extras and not args.inprocess:
             try:
                 line["extras"] = config2_extras(store, rng, args, queries, Metric, Path)
             except SystemExit:
                 raise
             except Exception as e:  # noqa: BLE001 -- never let the informational part break the contract line
                 line["extras"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1 and not args.inprocess:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.inprocess:
             if sample is None:
                 sample = cpu_sample(args.dim, args.seed)
             line["cpu_baseline"] = cpu_baseline(sample[0], sample[1], queries[:1], args.k)
@@ -587,6 +607,15 @@ def main() -> int:
     if dist is not None:
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(out_dir: str, hits) -> None:
+    """--dump-outputs: the hits the timed path returned in its last step, one array per field (k values each).  Row indices and
+    query ids as float64 (exact below 2**53), scores as float32 (the bits the path returned)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "index.npy"), hits["index"].astype(np.float64))
+    np.save(os.path.join(out_dir, "score.npy"), hits["score"].astype(np.float32))
+    np.save(os.path.join(out_dir, "query.npy"), hits["query"].astype(np.float64))
 
 
 def C_int_device_count(N) -> int:

@@ -7,14 +7,14 @@ rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 cd "$R"
 # 1. the driver's command under kernel trace + stats, then FETCH_SIZE / WRITE_SIZE in their own passes
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$O/bench_stats.log" 2>&1
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras > "$O/bench_fetch.log" 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/write" -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras > "$O/bench_write.log" 2>&1
-python3 bench.py --steps 50 --warmup 5 > "$O/bench_plain.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$O/bench_stats.log" 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-extras > "$O/bench_fetch.log" 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/write" -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-extras > "$O/bench_write.log" 2>&1
+python3 bench.py --full --steps 50 --warmup 5 > "$O/bench_plain.log" 2>&1
 # 2. the sharded path at one rank (RCCL communicator of one rank): kernel trace shows what the exchange adds
-OTT_BENCH_FORCE_DIST=1 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/dist1_stats" -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > "$O/bench_dist1_stats.log" 2>&1
-OTT_BENCH_FORCE_DIST=1 python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras > "$O/bench_dist1_plain.log" 2>&1
-python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras > "$O/bench_nodist_plain.log" 2>&1
+OTT_BENCH_FORCE_DIST=1 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/dist1_stats" -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras > "$O/bench_dist1_stats.log" 2>&1
+OTT_BENCH_FORCE_DIST=1 python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras > "$O/bench_dist1_plain.log" 2>&1
+python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras > "$O/bench_nodist_plain.log" 2>&1
 # 3. config-2 batch (256 queries): PMC triple of the hi pass, both kernels
 for HI in 0 1; do
   OTT_HI256=$HI rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVES --output-format csv -d "$O/c2_hi${HI}_mfma" -- python3 benchmarks/mfma_batch.py 256 > "$O/c2_hi${HI}_mfma.log" 2>&1

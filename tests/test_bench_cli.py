@@ -1,9 +1,11 @@
 """CPU: bench.py's launch contract.  `--gpus N` must never quietly run fewer ranks than asked for: a mismatch with the
 launcher's WORLD_SIZE is an error, and on a box that cannot host N ranks the self-launched run fails loudly (non-zero
-exit, no JSON line) instead of printing an n_gpus=1 line."""
+exit, no JSON line) instead of printing an n_gpus=1 line.  GPU (marked): a plain run's line and its --dump-outputs."""
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -65,3 +67,31 @@ def test_parity_gate_rejects_a_wrong_result(oracle):
     bad["index"][5] = (int(bad["index"][5]) + 1) % n  # a different row under the same score
     with pytest.raises(SystemExit):
         bench.parity_rescore(bad, q, dim, seed)
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dumped_outputs(oracle, tmp_path):
+    """A plain run (no --full) prints the headline line with `ms_per_step` over exactly --steps timed steps and none of what
+    --full adds; --dump-outputs writes the last timed step's hits, which are the oracle's top-k of that step's query over the
+    regenerated rows, index for index and bit for bit."""
+    import json
+    import numpy as np
+    rows, dim, k, seed, steps, warmup = 20480, 96, 10, 0x07735, 3, 2
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--rows", str(rows), "--dim", str(dim), "--k", str(k), "--steps", str(steps),
+                        "--warmup", str(warmup), "--dump-outputs", str(out)], env=_env(), capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0 and d["n_gpus"] == 1, d
+    assert d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "f32", d
+    assert abs(d["value"] - rows * (dim * 4 + 4) / (d["ms_per_step"] * 1e-3) / 1e9) <= 0.02 * d["value"], d
+    assert d["parity_checked"] is False and "extras" not in d and "cpu_baseline" not in d and d["roofline"]["traffic"] is None, d
+    got = {name: np.load(out / f"{name}.npy") for name in ("index", "score", "query")}
+    assert got["index"].dtype == np.float64 and got["score"].dtype == np.float32 and got["query"].dtype == np.float64
+    q = np.random.default_rng(seed + 1).uniform(-1, 1, (steps + warmup, dim)).astype(np.float32)[-1]
+    ref = oracle.vec_query(oracle.rand_rows(0, rows, dim, seed), q, oracle.METRIC_COSINE, oracle.TAKE_MAX, k, ties=oracle.TIES_CANONICAL)
+    assert np.array_equal(got["index"], ref["index"].astype(np.float64)), (got["index"], ref["index"])
+    assert np.array_equal(got["score"].view(np.uint32), np.asarray(ref["score"], np.float32).view(np.uint32))
+    assert np.array_equal(got["query"], np.zeros(k))

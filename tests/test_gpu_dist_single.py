@@ -586,7 +586,7 @@ def test_bench_two_ranks_through_both_launchers():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     bench = os.path.join(root, "bench.py")
-    args = ["--gpus", "2", "--rows", "1000448", "--steps", "3", "--warmup", "1"]
+    args = ["--gpus", "2", "--rows", "1000448", "--steps", "3", "--warmup", "1", "--full"]
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
@@ -665,7 +665,8 @@ def test_bench_eight_ranks_one_gpu():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--rows", "200704", "--steps", "3", "--warmup", "1", "--c4-queries", "64"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--rows", "200704", "--steps", "3", "--warmup", "1", "--c4-queries", "64",
+                        "--full"],
                        env=_clean_env(OTT_BENCH_SINGLE_DEVICE="1"), capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -692,7 +693,7 @@ def test_bench_inprocess_n_shards_one_gpu(shards):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(shards), "--inprocess", "--rows", "200704", "--steps", "3", "--warmup", "1",
-                        "--c4-queries", "64"],
+                        "--c4-queries", "64", "--full"],
                        env=_clean_env(OTT_BENCH_SINGLE_DEVICE="1"), capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -738,7 +739,8 @@ def test_bench_two_ranks_one_gpu_over_rccl():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--rows", "1000448", "--steps", "3", "--warmup", "1", "--c4-queries", "64"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--rows", "1000448", "--steps", "3", "--warmup", "1", "--c4-queries", "64",
+           "--full"]
     r = subprocess.run(cmd, env=_clean_env(OTT_BENCH_SINGLE_DEVICE="rccl"), capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -761,7 +763,8 @@ def test_bench_eight_ranks_one_gpu_over_rccl():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--rows", "200704", "--steps", "3", "--warmup", "1", "--c4-queries", "64"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--rows", "200704", "--steps", "3", "--warmup", "1", "--c4-queries", "64",
+                        "--full"],
                        env=_clean_env(OTT_BENCH_SINGLE_DEVICE="rccl"), capture_output=True, text=True, timeout=1200, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
