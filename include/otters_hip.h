@@ -242,7 +242,8 @@ int ott_store_batch_ready(const ott_store* s);
  *   "tie_order"  0 (default): canonical total order — better score, lower row, lower query.  1: the reference's own outcome at
  *                exact score ties, ONE TopKCollector over the store (VecStore, src/vec.rs:217-310, src/vec_compute.rs:236-277).
  *                2: one collector per chunk, then concat-sort-truncate (MetaStore, src/meta.rs:678-709), for any chunk size
- *                (src/meta.rs:86-89).  See INTEGRATION.md 6a.
+ *                (src/meta.rs:86-89).  Signed zeros follow the collector too: a pair is admitted by IEEE comparison with the
+ *                k-th score (-0.0 == +0.0) and placed by total order (+0.0 above -0.0).  See INTEGRATION.md 6a.
  *   "hi_fmt"     which compact copies of the corpus the cascade keeps: -1 (default) / 2: an INT8 plane as its first level (one f32
  *                scale per row, a quarter of the f32 bytes; k <= 128) with an IEEE-half plane behind it that is built
  *                only once a query needs it (k > 128, or what the int8 level could not certify); 1: the half plane

@@ -448,6 +448,7 @@ int sharded_ref_ties(ott_store* s, ott_store* ctx, ott_comm* c, const ott_query_
     env.tmax = d->take == OTT_TAKE_MAX;
     env.base = base0;
     env.chunk_size = L.all[2];  // the TABLE's chunk size (tie order 2: one on every rank, judge_layout), never a rank-local value
+    env.rows = total_rows;
     env.dim = s->dim;
     const auto run_off = [ctx, c, total_rows](const ott_query_desc& dd, uint64_t k, bool flat, uint32_t tie_off, std::vector<ott_hit>& o, std::vector<uint64_t>& per,
                                               ott_stats* st) -> int {

@@ -583,6 +583,7 @@ struct TieEnv {
     bool tmax = true;
     uint64_t base = 0;        // global index of the (whole) store's first row: 8-row blocks and chunks are counted from here
     uint64_t chunk_size = 1024;
+    uint64_t rows = 0;        // the whole store's rows (tie order 2 walks its chunks when the cut runs through the zeros)
     uint32_t dim = 0;
     Runner run;
     std::function<int(uint64_t chunk, const ott_query_desc& d, uint64_t k, bool flat, std::vector<ott_hit>& out, std::vector<uint64_t>& per, ott_stats* st)> run_chunk;

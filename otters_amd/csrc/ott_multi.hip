@@ -1120,6 +1120,7 @@ int multi_query(ott_store* ms, const ott_query_desc* d, ott_hit* out, uint64_t c
         env.tmax = d->take == OTT_TAKE_MAX;
         env.base = ms->base_offset;
         env.chunk_size = ms->chunk_size;
+        env.rows = ms->n;
         env.dim = ms->dim;
         const auto run_off = [&mc, ms](const ott_query_desc& dd, uint64_t k, bool flat, uint32_t tie_off, std::vector<ott_hit>& o, std::vector<uint64_t>& per,
                                        ott_stats* st2) -> int {

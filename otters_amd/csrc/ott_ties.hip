@@ -33,6 +33,13 @@
 // beyond, the order std's ipnsort leaves inside a run of equal scores is an implementation detail this file — like the
 // oracle's OTTO_TIES_LITERAL, which it is tested against — replaces by the stable one.)
 //
+// Signed zeros: the collector ADMITS a pair by IEEE comparison with the k-th score (-0.0 == +0.0) but POSITIONS it by
+// total_cmp (+0.0 above -0.0), so a cut through the scores +-0 is no single group of the key order above.  When the cut runs
+// through zeros of both signs, the collector is replayed on the host (replay_literal) over the only pairs that can matter: those
+// strictly better than zero (all of them in L), the fill phase, and the first 2k zero-scoring pairs in visit order (one more
+// flat pass, filter == 0) — the zeros it admits are a prefix of that order no longer than the fill phase's zeros plus the k
+// entries it can displace.  O(k log k) on the host; cuts without both zeros take the derivation above.
+//
 // tie_order = 1: ONE collector over the store (VecStore).  tie_order = 2: one collector per chunk, the per-chunk lists
 // concatenated in chunk order, stably sorted by score and truncated (MetaStore, src/meta.rs:678-709 / process_chunk), for any
 // chunk size (src/meta.rs:86-89).  When the cut is ambiguous, the chunks that hold candidates are re-queried one by one as
@@ -42,6 +49,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
+#include <map>
 #include <set>
 #include <utility>
 
@@ -70,6 +79,44 @@ inline bool visited_before(const Ctx& c, const ott_hit& a, const ott_hit& b) {
 
 uint64_t k_plus_one(uint64_t k) { return k == ~0ull ? k : k + 1; }
 
+inline bool is_zero(float x) { return x == 0.0f; }
+
+// position of x in the collector's buffer (sorted by total_cmp, best first): find_insert_position, src/vec_compute.rs:270-277,
+// with the loop shape of std's binary_search_by (>= 1.82).  Ok(i) and Err(i) both give i.
+size_t literal_insert_pos(const Ctx& c, const std::vector<ott_hit>& buf, const ott_hit& x) {
+    size_t size = buf.size(), base = 0;
+    if (size == 0) return 0;
+    const uint32_t kx = ord(c, x);  // larger ord = better, for either take
+    while (size > 1) {
+        const size_t half = size / 2, mid = base + half;
+        base = ord(c, buf[mid]) < kx ? base : mid;  // cmp == Greater: the probe ranks below x
+        size -= half;
+    }
+    const uint32_t kp = ord(c, buf[base]);
+    if (kp == kx) return base;
+    return base + (kp > kx ? 1 : 0);
+}
+
+// The collector itself (push_single, src/vec_compute.rs:236-268) over `pairs`, which must be in visit order: IEEE admission
+// against the k-th score, total-order position, pop of the last entry; the fill-phase sort is stable (as in the oracle).
+void replay_literal(const Ctx& c, const std::vector<ott_hit>& pairs, uint64_t k, std::vector<ott_hit>& buf) {
+    buf.clear();
+    for (const ott_hit& x : pairs) {
+        if (std::isnan(x.score)) continue;
+        if (buf.size() == k) {
+            const float thr = buf.back().score;
+            if (!(c.tmax ? x.score > thr : x.score < thr)) continue;
+            buf.insert(buf.begin() + literal_insert_pos(c, buf, x), x);
+            buf.pop_back();
+        } else {
+            buf.push_back(x);
+            if (buf.size() == k)
+                std::stable_sort(buf.begin(), buf.end(), [&c](const ott_hit& a, const ott_hit& b) { return ord(c, a) > ord(c, b); });
+        }
+    }
+    if (buf.size() < k) std::stable_sort(buf.begin(), buf.end(), [&c](const ott_hit& a, const ott_hit& b) { return ord(c, a) > ord(c, b); });
+}
+
 // one plain query into host vectors through the environment's runner.  per: per-query counts (PER_QUERY), lists concatenated
 // in query order
 int run_core(const Runner& run, const ott_query_desc& d, uint64_t k, bool flat, std::vector<ott_hit>& out, std::vector<uint64_t>& per, ott_stats* st) {
@@ -79,24 +126,68 @@ int run_core(const Runner& run, const ott_query_desc& d, uint64_t k, bool flat, 
 }
 
 // The collector's result for ONE candidate list.  L: up to k + 1 candidates, best first, equal scores in visit order.
-// get_F: fills the fill-phase set on demand (returns a status).  want_order: arrange every run of equal scores the way the
-// collector's buffer holds it (needed when the list is merged further by position: tie_order = 2); otherwise runs stay in
-// visit order and the fill-phase pass is only made when the cut is ambiguous.
-template <typename GetF>
-int collector_result(const Ctx& c, const std::vector<ott_hit>& L, uint64_t k, GetF&& get_F, bool want_order, std::vector<ott_hit>& out) {
+// get_F: the fill-phase pairs on demand (returns a status).  get_Z: the first 2k zero-scoring passing pairs in visit order, asked
+// for only when the cut runs through zeros.  want_order: arrange every run of equal scores the way the collector's buffer holds it
+// (needed when the list is merged further by position: tie_order = 2); otherwise runs stay in visit order and the fill-phase
+// pass is only made when the cut is ambiguous.
+template <typename GetF, typename GetZ>
+int collector_result(const Ctx& c, const std::vector<ott_hit>& L, uint64_t k, GetF&& get_F, GetZ&& get_Z, bool want_order,
+                     std::vector<ott_hit>& out) {
     out.clear();
     const size_t m = L.size();
     if (m == 0 || k == 0) return OTT_OK;
     const bool over = m > k;  // a (k+1)-th candidate exists
     const size_t kk = over ? (size_t)k : m;
-    const bool ambiguous = over && ord(c, L[kk]) == ord(c, L[kk - 1]);
+    std::vector<ott_hit> Fh;
     PairSet F;
     bool have_F = false;
     auto need_F = [&]() -> int {
         if (have_F) return OTT_OK;
         have_F = true;
-        return get_F(F);
+        const int rc = get_F(Fh);
+        for (const ott_hit& h : Fh) F.insert(std::make_pair(h.index, h.query));
+        return rc;
     };
+    if (over && is_zero(L[kk].score) && is_zero(L[kk - 1].score)) {
+        // the cut runs through zeros: if both signs take part, IEEE admission and total-order position part ways
+        std::vector<ott_hit> Z;
+        int rc = get_Z(Z);
+        if (rc) return rc;
+        bool pos = false, neg = false;
+        for (const ott_hit& h : Z) (std::signbit(h.score) ? neg : pos) = true;
+        for (const ott_hit& h : L)
+            if (is_zero(h.score)) (std::signbit(h.score) ? neg : pos) = true;
+        if (pos && neg) {
+            if ((rc = need_F())) return rc;
+            std::vector<ott_hit> pairs;
+            std::map<std::pair<uint64_t, uint32_t>, float> known;  // true scores: a flat pass reports every score as +0.0
+            for (const ott_hit& h : L)
+                if (!is_zero(h.score) && (c.tmax ? h.score > 0.0f : h.score < 0.0f)) {  // strictly better than zero: all in L
+                    pairs.push_back(h);
+                    known[std::make_pair(h.index, h.query)] = h.score;
+                }
+            for (const ott_hit& h : Z) known[std::make_pair(h.index, h.query)] = h.score;
+            pairs.insert(pairs.end(), Z.begin(), Z.end());
+            // the fill phase's zeros are a prefix of Z and its better pairs are in L; the rest scores worse than zero, and which
+            // worse score it has changes nothing above zero: it only holds a slot until a zero or a better pair takes it
+            for (ott_hit h : Fh) {
+                const auto it = known.find(std::make_pair(h.index, h.query));
+                h.score = it != known.end() ? it->second : (c.tmax ? -__builtin_inff() : __builtin_inff());
+                pairs.push_back(h);
+            }
+            std::sort(pairs.begin(), pairs.end(), [&c](const ott_hit& a, const ott_hit& b) { return visited_before(c, a, b); });
+            pairs.erase(std::unique(pairs.begin(), pairs.end(),
+                                    [](const ott_hit& a, const ott_hit& b) { return a.index == b.index && a.query == b.query; }),
+                        pairs.end());
+            replay_literal(c, pairs, k, out);
+            if (!want_order)  // runs in visit order, as below
+                std::stable_sort(out.begin(), out.end(), [&c](const ott_hit& a, const ott_hit& b) {
+                    return ord(c, a) != ord(c, b) ? ord(c, a) > ord(c, b) : visited_before(c, a, b);
+                });
+            return OTT_OK;
+        }
+    }
+    const bool ambiguous = over && ord(c, L[kk]) == ord(c, L[kk - 1]);
     auto in_F = [&](const ott_hit& h) { return F.count(std::make_pair(h.index, h.query)) != 0; };
 
     // the cut group
@@ -186,34 +277,74 @@ int collect_vecstore(const Ctx& c, const Runner& run, const ott_query_desc& d, b
     } else {
         cand[0] = std::move(all);
     }
-    // the fill phase of every group's collector: ONE flat pass (first k passing pairs in visit order), made on first demand
-    std::vector<PairSet> fill(ng);
-    bool filled = false;
-    auto ensure_fill = [&]() -> int {
-        if (filled) return OTT_OK;
-        filled = true;
+    // one flat pass over d, split into the groups' lists (in visit order)
+    auto flat_pass = [&](const ott_query_desc& df, uint64_t k, std::vector<std::vector<ott_hit>>& lists) -> int {
         std::vector<ott_hit> f;
         std::vector<uint64_t> fper;
-        int rc2 = run_core(run, d, d.k, true, f, fper, nullptr);
+        int rc2 = run_core(run, df, k, true, f, fper, nullptr);
         if (rc2) return rc2;
+        lists.assign(ng, {});
         if (perq) {
             size_t o = 0;
             for (uint32_t g = 0; g < ng; g++) {
-                for (size_t i = 0; i < (size_t)fper[g]; i++) fill[g].insert(std::make_pair(f[o + i].index, f[o + i].query));
+                lists[g].assign(f.begin() + o, f.begin() + o + (size_t)fper[g]);
                 o += (size_t)fper[g];
             }
         } else {
-            for (const ott_hit& h : f) fill[0].insert(std::make_pair(h.index, h.query));
+            lists[0] = std::move(f);
         }
         return OTT_OK;
     };
+    // the fill phase of every group's collector: ONE flat pass (first k passing pairs in visit order), made on first demand
+    std::vector<std::vector<ott_hit>> fill, zeros;
+    bool filled = false, zeroed = false;
     groups.assign(ng, {});
     for (uint32_t g = 0; g < ng; g++) {
         rc = collector_result(c, cand[g], d.k,
-                              [&](PairSet& F) -> int {
-                                  int rc2 = ensure_fill();
-                                  if (rc2) return rc2;
+                              [&](std::vector<ott_hit>& F) -> int {
+                                  if (!filled) {
+                                      filled = true;
+                                      const int rc2 = flat_pass(d, d.k, fill);
+                                      if (rc2) return rc2;
+                                  }
                                   F = fill[g];
+                                  return OTT_OK;
+                              },
+                              [&](std::vector<ott_hit>& Z) -> int {
+                                  // the first 2k zero-scoring pairs in visit order, signs included (a flat pass reports every score
+                                  // as +0.0): the first 2k of each sign — filter == 0 ranked by take_max (+0.0 first) and by
+                                  // take_min (-0.0 first), each run in visit order — merged and cut at 2k.  A pair that passes the
+                                  // user's filter with score +-0 passes == 0 too, and every zero passes it alike.
+                                  if (!zeroed) {
+                                      zeroed = true;
+                                      const uint64_t k2 = d.k > ~0ull / 2 ? ~0ull : 2 * d.k;
+                                      zeros.assign(ng, {});
+                                      for (uint32_t t : {(uint32_t)OTT_TAKE_MAX, (uint32_t)OTT_TAKE_MIN}) {
+                                          ott_query_desc dz = d;
+                                          dz.filter_cmp = OTT_CMP_EQ;
+                                          dz.filter_thr = 0.0f;
+                                          dz.take = t;
+                                          dz.path = OTT_PATH_EXACT;
+                                          std::vector<ott_hit> z;
+                                          std::vector<uint64_t> zper;
+                                          const int rc2 = run_core(run, dz, k2, false, z, zper, nullptr);
+                                          if (rc2) return rc2;
+                                          size_t o = 0;
+                                          for (uint32_t g2 = 0; g2 < ng; g2++) {
+                                              const size_t cnt = perq ? (size_t)zper[g2] : z.size();
+                                              zeros[g2].insert(zeros[g2].end(), z.begin() + o, z.begin() + o + cnt);
+                                              o += cnt;
+                                          }
+                                      }
+                                      for (auto& zl : zeros) {
+                                          std::sort(zl.begin(), zl.end(), [&c](const ott_hit& a, const ott_hit& b) { return visited_before(c, a, b); });
+                                          zl.erase(std::unique(zl.begin(), zl.end(),
+                                                               [](const ott_hit& a, const ott_hit& b) { return a.index == b.index && a.query == b.query; }),
+                                                   zl.end());
+                                          if (zl.size() > k2) zl.resize((size_t)k2);
+                                      }
+                                  }
+                                  Z = zeros[g];
                                   return OTT_OK;
                               },
                               want_order, groups[g]);
@@ -229,16 +360,15 @@ int collect_metastore_merged(const Ctx& c, const ott_query_desc& d, std::vector<
     int rc = run_core(c.run, d, k_plus_one(d.k), false, L, per, st);
     if (rc) return rc;
     const size_t k = (size_t)(d.k < L.size() ? d.k : L.size());
-    if (L.size() <= d.k || ord(c, L[k]) != ord(c, L[k - 1])) {
+    if (L.size() <= d.k || !(L[k].score == L[k - 1].score)) {  // (IEEE: +0.0 and -0.0 are one group of the final sort below)
         out.assign(L.begin(), L.begin() + k);  // the set is unambiguous (equal scores stay in visit order)
         return OTT_OK;
     }
     // ambiguous cut: the chunks that hold candidates, each as a store of its own (src/meta_compute.rs:153-192)
     const uint64_t cs = c.chunk_size;
-    std::set<uint64_t> chunks;
-    for (const ott_hit& h : L) chunks.insert((h.index - c.base) / cs);
-    std::vector<ott_hit> concat;
-    for (uint64_t ch : chunks) {
+    std::map<uint64_t, std::vector<ott_hit>> lists;  // chunk -> its collector's list, in chunk order
+    auto chunk_list = [&](uint64_t ch) -> int {
+        if (lists.count(ch)) return OTT_OK;
         ott_query_desc d3 = d;
         d3.mode = OTT_MODE_MERGED;
         const Runner one_chunk = [&c, ch](const ott_query_desc& dd, uint64_t k, bool flat, std::vector<ott_hit>& out, std::vector<uint64_t>& per,
@@ -246,9 +376,26 @@ int collect_metastore_merged(const Ctx& c, const ott_query_desc& d, std::vector<
         std::vector<std::vector<ott_hit>> one;
         Ctx cc = c;
         cc.base = c.base + ch * cs;  // the chunk is a VecStore of its own: its collector's 8-row blocks start at its first row
-        if ((rc = collect_vecstore(cc, one_chunk, d3, true, one, nullptr))) return rc;
-        concat.insert(concat.end(), one[0].begin(), one[0].end());
+        const int rc2 = collect_vecstore(cc, one_chunk, d3, true, one, nullptr);
+        if (rc2) return rc2;
+        lists[ch] = std::move(one[0]);
+        return OTT_OK;
+    };
+    for (const ott_hit& h : L)
+        if ((rc = chunk_list((h.index - c.base) / cs))) return rc;
+    if (is_zero(L[k].score)) {
+        // a cut through the zeros: the final sort keeps +0.0 and -0.0 in chunk order, so a chunk whose collector kept only zeros
+        // of the other sign — none of them in L — can still take slots.  Every chunk in front of the k-th zero counts.
+        const uint64_t n_chunks = (c.rows + cs - 1) / cs;
+        uint64_t zeros = 0;
+        for (uint64_t ch = 0; ch < n_chunks && zeros < d.k; ch++) {
+            if (d.chunk_mask && !((d.chunk_mask[ch >> 6] >> (ch & 63)) & 1)) continue;
+            if ((rc = chunk_list(ch))) return rc;
+            for (const ott_hit& h : lists[ch]) zeros += is_zero(h.score) ? 1 : 0;
+        }
     }
+    std::vector<ott_hit> concat;
+    for (const auto& kv : lists) concat.insert(concat.end(), kv.second.begin(), kv.second.end());
     // src/meta.rs:702-705: sort by partial_cmp (IEEE order: -0.0 == +0.0), stable here as in the oracle's restatement
     if (c.tmax) std::stable_sort(concat.begin(), concat.end(), [](const ott_hit& a, const ott_hit& b) { return a.score > b.score; });
     else std::stable_sort(concat.begin(), concat.end(), [](const ott_hit& a, const ott_hit& b) { return a.score < b.score; });
@@ -273,10 +420,13 @@ int ties_resolve(ott_store* s, bool tmax, uint64_t base, const std::vector<ott_h
     c.tmax = tmax;
     c.base = base;
     return collector_result(c, L, k,
-                            [&](PairSet& F) -> int {
+                            [&](std::vector<ott_hit>& F) -> int {
                                 if (!fill) return fail(OTT_ERR_INVALID, "ties_resolve: the fill phase is needed but was not supplied");
-                                for (const ott_hit& h : *fill) F.insert(std::make_pair(h.index, h.query));
+                                F = *fill;
                                 return OTT_OK;
+                            },
+                            [&](std::vector<ott_hit>&) -> int {
+                                return fail(OTT_ERR_INVALID, "ties_resolve: a cut through the zeros needs the store (ref_ties_collect)");
                             },
                             false, out);
 }
@@ -337,6 +487,7 @@ int query_ref_ties(ott_store* s, const ott_query_desc* d, ott_hit* out_host, uin
     env.tmax = d->take == OTT_TAKE_MAX;
     env.base = s->base_offset;
     env.chunk_size = s->chunk_size;
+    env.rows = s->n;
     env.dim = s->dim;
     const auto run_off = [s](const ott_query_desc& dd, uint64_t k, bool flat, uint32_t tie_off, std::vector<ott_hit>& out, std::vector<uint64_t>& per, ott_stats* st) -> int {
         ott_query_desc d2 = dd;

@@ -408,8 +408,10 @@ class VecStore:
         """Which of several EQUAL-scoring (row, query) pairs survives the cut at take(k).  "canonical" (default): the
         library's total order — better score, lower row, lower query.  "reference": what the reference's TopKCollector
         keeps (strict-improvement inserts in visit order — 8-row block, query, row — at the position its binary search
-        returns, src/vec_compute.rs:236-277; one collector over the store, src/vec.rs:217-219).  Scores and every hit
-        strictly better than the k-th score are the same either way."""
+        returns, src/vec_compute.rs:236-277; one collector over the store, src/vec.rs:217-219).  Signed zeros: the
+        collector admits a pair by IEEE comparison (-0.0 == +0.0) but places it by total order (+0.0 above -0.0), so at a
+        cut through the zeros the two orders may keep zeros of different signs.  Otherwise scores and every hit strictly
+        better than the k-th score are the same either way."""
         self.set_option("tie_order", {"canonical": 0, "reference": 1, "reference_chunked": 2}[order])
 
     def set_reduce_order(self, order: int) -> None:

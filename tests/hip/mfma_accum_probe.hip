@@ -11,7 +11,10 @@
 //     ratio = |mfma - exact| / (2^-24 * sum |a_i b_i|)   in units of "one f32 rounding of the sum's magnitude".
 // Same-sign operands (every product positive: errors cannot cancel), mixed signs, and operands spread over many binades.
 // Prints one line per case; exit code 1 if any ratio exceeds K (the plain recursive-summation bound the model's constants sit
-// above).  tests/test_gpu_mfma.py builds and runs it on the GPU box.
+// above).  Then one line per 16-bit format on whether the unit keeps or flushes SUBNORMAL A operands (the half plane's loss
+// measurement assumes gradual underflow): "f16 subnormal inputs: kept|flushed", the same for bf16.  Measured on the MI355X
+// (gfx950): both KEPT — every output of the 16-bit instructions equals the exact sum of subnormal-operand products, so the half
+// plane's loss measurement (v_cvt_f16_f32 with gradual underflow) matches what the unit computes and no row needs flagging.  tests/test_gpu_mfma.py builds and runs it on the GPU box.
 //   hipcc -O2 --offload-arch=gfx950 mfma_accum_probe.hip -o mfma_accum_probe
 #include <hip/hip_runtime.h>
 
@@ -127,6 +130,41 @@ int main() {
                 CK(hipFree(dC));
             }
         }
+    }
+    // Subnormal A operands in the 16-bit formats: f16 multiples of 2^-24 below 2^-14, bf16 multiples of 2^-133 below 2^-126, each
+    // against a power-of-two B that makes every product a normal f32 (the f32 sum is exact).  "kept": every output equals that sum;
+    // "flushed": every output is 0 (the inputs were read as zero); anything else is a finding of its own and fails the probe.
+    for (int mode = 1; mode <= 2; mode++) {
+        const int K = 64;
+        const int sub_exp = mode == 2 ? -24 : -133, max_m = mode == 2 ? 1023 : 127;
+        const float bval = std::ldexp(1.0f, mode == 2 ? 10 : 100);
+        std::vector<float> A(32 * K), B(32 * K, mode == 2 ? bval : to_fmt(bval, 1)), C(32 * 32);
+        for (int m = 0; m < 32; m++)
+            for (int k = 0; k < K; k++) A[m * K + k] = to_fmt(std::ldexp((float)(1 + (37 * m + 11 * k) % max_m), sub_exp), mode);
+        float *dA, *dB, *dC;
+        CK(hipMalloc(&dA, A.size() * 4));
+        CK(hipMalloc(&dB, B.size() * 4));
+        CK(hipMalloc(&dC, C.size() * 4));
+        CK(hipMemcpy(dA, A.data(), A.size() * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dB, B.data(), B.size() * 4, hipMemcpyHostToDevice));
+        if (mode == 1) hipLaunchKernelGGL(probe<1>, dim3(1), dim3(64), 0, 0, dA, dB, dC, K);
+        else hipLaunchKernelGGL(probe<2>, dim3(1), dim3(64), 0, 0, dA, dB, dC, K);
+        CK(hipDeviceSynchronize());
+        CK(hipMemcpy(C.data(), dC, C.size() * 4, hipMemcpyDeviceToHost));
+        int kept = 0, zero = 0;
+        for (int m = 0; m < 32; m++)
+            for (int n = 0; n < 32; n++) {
+                double s = 0.0;
+                for (int k = 0; k < K; k++) s += (double)A[m * K + k] * (double)B[n * K + k];
+                kept += (double)C[m * 32 + n] == s;
+                zero += C[m * 32 + n] == 0.0f;
+            }
+        const char* verdict = kept == 32 * 32 ? "kept" : zero == 32 * 32 ? "flushed" : "neither";
+        printf("%s subnormal inputs: %s   (%s, %d of 1024 outputs exact, %d zero)\n", mode == 2 ? "f16" : "bf16", verdict, names[mode], kept, zero);
+        if (verdict[0] == 'n') bad++;
+        CK(hipFree(dA));
+        CK(hipFree(dB));
+        CK(hipFree(dC));
     }
     printf(bad ? "FAILED: %d case(s) above the recursive-summation bound\n" : "ALL WITHIN BOUND\n", bad);
     return bad ? 1 : 0;

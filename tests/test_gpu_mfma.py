@@ -529,6 +529,10 @@ def test_mfma_accumulation_error_probe():
     print(r.stdout)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert "ALL WITHIN BOUND" in r.stdout and r.stdout.count("max |mfma - exact|") == 27
+    # subnormal operands of the 16-bit instructions: one verdict line per format, and the unit either keeps or flushes them
+    import re
+    for fmt in ("f16", "bf16"):
+        assert len(re.findall(r"^%s subnormal inputs: (kept|flushed) " % fmt, r.stdout, re.M)) == 1, (fmt, r.stdout[-1500:])
 
 
 def test_single_query_int8_sweep(oracle):
