@@ -27,6 +27,8 @@ pub const OTT_ERR_UNSUPPORTED: c_int = -4;
 pub const OTT_METRIC_COSINE: u32 = 0;
 pub const OTT_METRIC_EUCLIDEAN: u32 = 1;
 pub const OTT_METRIC_DOT: u32 = 2;
+// extension (L1, EXACT path only); upstream otters has no such variant yet
+pub const OTT_METRIC_MANHATTAN: u32 = 3;
 // ott_take (src/vec.rs:18-22)
 pub const OTT_TAKE_MIN: u32 = 0;
 pub const OTT_TAKE_MAX: u32 = 1;

@@ -23,7 +23,7 @@ struct Error : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
 
-enum class Metric { Cosine = 0, Euclidean = 1, DotProduct = 2 };  // src/vec.rs:11-16
+enum class Metric { Cosine = 0, Euclidean = 1, DotProduct = 2, Manhattan = 3 };  // src/vec.rs:11-16; Manhattan (L1, EXACT only): extension
 enum class TakeType { Min = 0, Max = 1 };                          // src/vec.rs:18-22
 enum class Cmp { Lt = 1, Gt = 2, Lte = 3, Gte = 4, Eq = 5 };       // src/vec.rs:24-31
 
@@ -75,7 +75,7 @@ class VecQueryPlan {  // src/vec.rs:55-312
         if (error_) return *this;
         take_count_ = count;
         if (tt) take_type_ = tt;
-        else if (!take_type_ && metric_) take_type_ = (*metric_ == Metric::Euclidean) ? TakeType::Min : TakeType::Max;
+        else if (!take_type_ && metric_) take_type_ = (*metric_ == Metric::Euclidean || *metric_ == Metric::Manhattan) ? TakeType::Min : TakeType::Max;
         return *this;
     }
     void validate() const;

@@ -54,8 +54,9 @@ typedef enum {
     OTT_ERR_UNSUPPORTED = -4
 } ott_status;
 
-/* src/vec.rs:11-16 */
-typedef enum { OTT_METRIC_COSINE = 0, OTT_METRIC_EUCLIDEAN = 1, OTT_METRIC_DOT = 2 } ott_metric;
+/* src/vec.rs:11-16.  MANHATTAN (L1: the sum of |q[i] - v[i]|, default take MIN) is an extension on the EXACT path only; its
+ * summation order is the other metrics' (eight chains over chunks_exact(8), reduce_add, then the sequential remainder). */
+typedef enum { OTT_METRIC_COSINE = 0, OTT_METRIC_EUCLIDEAN = 1, OTT_METRIC_DOT = 2, OTT_METRIC_MANHATTAN = 3 } ott_metric;
 /* src/vec.rs:18-22 */
 typedef enum { OTT_TAKE_MIN = 0, OTT_TAKE_MAX = 1 } ott_take;
 /* src/vec.rs:24-31; NONE = no filter_criteria */
@@ -70,7 +71,7 @@ typedef enum { OTT_DT_INT32 = 0, OTT_DT_INT64 = 1, OTT_DT_FLOAT32 = 2, OTT_DT_FL
 typedef enum { OTT_MODE_MERGED = 0, OTT_MODE_PER_QUERY = 1 } ott_mode;
 
 /* Which scoring kernel family runs.  EXACT scores every row in the reference's summation order (one pass over the f32 rows
- * per 4 queries).  MFMA is the certified cascade, all three metrics, k <= 484: candidate passes over compact copies of the corpus
+ * per 4 queries).  MFMA is the certified cascade, cosine / Euclidean / dot, k <= 484: candidate passes over compact copies of the corpus
  * — an int8 plane first (k <= 128: a quarter of the f32 bytes; batches on the matrix cores, a single cosine / dot query as a
  * streaming sweep), a 16-bit hi plane for what that cannot certify, split bf16 behind it — every candidate
  * re-scored in the reference's order, the top-k CERTIFIED against a measured error bound, uncertifiable queries recomputed on
@@ -79,7 +80,8 @@ typedef enum { OTT_MODE_MERGED = 0, OTT_MODE_PER_QUERY = 1 } ott_mode;
  * background build after appends, a batch query or ott_store_prepare_batch made it) and the store is large enough for a quarter
  * of the bytes to pay (~200k x 768 rows): then it takes the cascade, same bits.  Batches: 2+ queries on large stores, 5+
  * elsewhere — except small batches (up to 16 queries) on small stores (up to ~65k rows), which stay on EXACT while its
- * small-store kernel (8 queries per pass) is cheaper than the cascade's fixed cost. */
+ * small-store kernel (8 queries per pass) is cheaper than the cascade's fixed cost.  MANHATTAN is EXACT only: AUTO sends it
+ * there before the cost model runs (it never builds, extends or waits for a plane) and MFMA refuses it (OTT_ERR_UNSUPPORTED). */
 typedef enum { OTT_PATH_AUTO = 0, OTT_PATH_EXACT = 1, OTT_PATH_MFMA = 2 } ott_path;
 
 /* Horizontal-sum order of wide::f32x8::reduce_add (third-party, unpinned by the reference's tests; see

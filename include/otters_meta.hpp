@@ -797,7 +797,7 @@ class MetaQueryPlan {  // src/meta.rs:579-830
     }
     MetaQueryPlan& take(std::size_t k) {  // src/meta.rs:623-630
         take_count_ = k;
-        take_type_ = metric_ == Metric::Euclidean ? TakeType::Min : TakeType::Max;
+        take_type_ = (metric_ == Metric::Euclidean || metric_ == Metric::Manhattan) ? TakeType::Min : TakeType::Max;
         return *this;
     }
     MetaQueryResults collect() const {  // src/meta.rs:632-829
@@ -805,7 +805,7 @@ class MetaQueryPlan {  // src/meta.rs:579-830
         const MetaStore& st = *store_;
         if (queries_.empty()) throw Error("No queries provided");
         const std::size_t k = take_count_.value_or(st.n_rows_);
-        const TakeType tt = take_type_.value_or(metric_ == Metric::Euclidean ? TakeType::Min : TakeType::Max);
+        const TakeType tt = take_type_.value_or((metric_ == Metric::Euclidean || metric_ == Metric::Manhattan) ? TakeType::Min : TakeType::Max);
         MetaQueryStats stats;
         stats.total_chunks = st.n_chunks_;
         std::vector<ott_hit> hits;

@@ -143,11 +143,13 @@ int validate_query(const ott_store* s, const ott_query_desc* d) {
     if (!d) return fail(OTT_ERR_INVALID, "ott_query: desc is NULL");
     if (d->nq == 0) return fail(OTT_ERR_INVALID, "No queries provided");  // src/vec.rs:188-190
     if (!d->queries) return fail(OTT_ERR_INVALID, "ott_query: queries is NULL");
-    if (d->metric > OTT_METRIC_DOT) return fail(OTT_ERR_INVALID, "ott_query: unknown metric");
+    if (d->metric > OTT_METRIC_MANHATTAN) return fail(OTT_ERR_INVALID, "ott_query: unknown metric");
     if (d->take > OTT_TAKE_MAX) return fail(OTT_ERR_INVALID, "ott_query: unknown take type");
     if (d->filter_cmp > OTT_CMP_EQ) return fail(OTT_ERR_INVALID, "ott_query: unknown filter comparator");
     if (d->mode > OTT_MODE_PER_QUERY) return fail(OTT_ERR_INVALID, "ott_query: unknown mode");
     if (d->path > OTT_PATH_MFMA) return fail(OTT_ERR_INVALID, "ott_query: unknown path");
+    if (d->path == OTT_PATH_MFMA && d->metric == OTT_METRIC_MANHATTAN)  // |q - v| is not a dot product: no candidate pass bounds it
+        return fail(OTT_ERR_UNSUPPORTED, "ott_query: the MFMA path does not score the Manhattan metric; use path AUTO or EXACT");
     if (d->use_device_row_mask && s->evalmask_bits == 0 && s->n)
         return fail(OTT_ERR_INVALID, "ott_query: use_device_row_mask set but ott_store_eval_row_mask was not called");
     return OTT_OK;
@@ -383,6 +385,7 @@ int ott::query_core(ott_store* s, const ott_query_desc* d, ott_hit* out_host, vo
     const bool mfma_ok = k_q + 28 <= 512 && s->dim >= 8;
     bool use_mfma;
     if (co.flat) use_mfma = false;  // (the flat pass exists on the exact-order kernel only)
+    else if (d->metric == OTT_METRIC_MANHATTAN) use_mfma = false;  // EXACT only, decided before the cost model looks at the planes (img_mu)
     else if (d->path == OTT_PATH_MFMA) {
         if (!mfma_ok) return fail(OTT_ERR_UNSUPPORTED, "ott_query: the MFMA path needs dim >= 8 and k <= 484");
         use_mfma = true;

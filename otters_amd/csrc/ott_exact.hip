@@ -273,6 +273,31 @@ __device__ __forceinline__ bool cmp_holds(float s, uint32_t cmp, float thr) {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
+// Metric kind of the exact family (template parameter MK of exact_kernel / exact_rows8_kernel): the per-element term that the
+// eight chains and the remainder add up.  Dot and cosine share MK_DOT (cosine scales the sum by the inverse norms afterwards).
+// MK_L1 is the Manhattan metric, an extension whose contract the project defines in the reference's style:
+//     manhattan(q, v) = reduce_add(acc) + tail
+//       acc[l] = 0;  for each chunk j of chunks_exact(8), in order:  acc[l] = acc[l] + |q[8j+l] - v[8j+l]|
+//       tail   = 0;  for each remainder element i, in order:          tail   = tail + |q[i] - v[i]|
+// IEEE f32 round-to-nearest-even throughout (the subtraction rounds, abs is exact, the add rounds), nothing fused, no flush;
+// reduce_add is reduce8 in the store's order and the final add __fadd_rn(reduce8(acc), tail), as for dot and L2.  inf - inf
+// gives NaN (the pair is dropped), an infinite difference or an overflowing sum +inf (a valid score).
+constexpr int MK_DOT = 0, MK_L2 = 1, MK_L1 = 2;
+static inline int metric_kind(uint32_t metric) {
+    return metric == OTT_METRIC_EUCLIDEAN ? MK_L2 : metric == OTT_METRIC_MANHATTAN ? MK_L1 : MK_DOT;
+}
+template <int MK>
+__device__ __forceinline__ float exact_term(float qv, float x) {
+    if constexpr (MK == MK_L2) {
+        const float d = __fsub_rn(qv, x);  // vec_compute.rs:39-42
+        return __fmul_rn(d, d);
+    } else if constexpr (MK == MK_L1) {
+        return fabsf(__fsub_rn(qv, x));    // |q - v|: the subtraction rounds, abs is exact, so |q - v| == |v - q| bit for bit
+    } else {
+        return __fmul_rn(qv, x);           // vec_compute.rs:12-13
+    }
+}
+
 // wide::f32x8::reduce_add (see oracle/otters_oracle.h for the two orders)
 __device__ __forceinline__ float reduce8(const float* l, uint32_t mode) {
     if (mode == OTT_REDUCE_SEQ4) {
@@ -296,9 +321,9 @@ __device__ __forceinline__ float reduce8(const float* l, uint32_t mode) {
 // copy rides in the kernel arguments, a lane accumulates its row with v_dot4 (exact i32), and the "score" offered to the wave
 // list is the APPROXIMATE (float)(q~ . v~) x row factor: the list's T best go to the exact re-score (run_i8_single).  Rows
 // outside the pass's error model (flag bits 0 / 2) are always listed, ranked first.
-template <bool L2, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false>
+template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false>
 __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) {
-    static_assert(!I8 || (NQ == 1 && !L2 && !PERQ && !DUMP && !SMALL), "the int8 sweep takes one query, cosine / dot, merged");
+    static_assert(!I8 || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL), "the int8 sweep takes one query, cosine / dot, merged");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -538,14 +563,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                                 float qv;
                                 if constexpr (SMALL) qv = sQ[col + l];  // NQ == 1: broadcast LDS read
                                 else qv = qp[l];
-                                float pr;
-                                if (L2) {
-                                    const float d = __fsub_rn(qv, x[l]);
-                                    pr = __fmul_rn(d, d);
-                                } else {
-                                    pr = __fmul_rn(qv, x[l]);
-                                }
-                                acc[q][l] = __fadd_rn(acc[q][l], pr);
+                                acc[q][l] = __fadd_rn(acc[q][l], exact_term<MK>(qv, x[l]));
                             }
                         }
                     } else {
@@ -560,14 +578,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                                     float qv;
                                     if constexpr (SMALL) qv = sQ[col + l];  // NQ == 1: broadcast LDS read
                                     else qv = qp[l];
-                                    float pr;
-                                    if (L2) {
-                                        const float d = __fsub_rn(qv, x[l]);
-                                        pr = __fmul_rn(d, d);
-                                    } else {
-                                        pr = __fmul_rn(qv, x[l]);
-                                    }
-                                    tail[q] = __fadd_rn(tail[q], pr);
+                                    tail[q] = __fadd_rn(tail[q], exact_term<MK>(qv, x[l]));
                                 }
                             }
                         }
@@ -708,7 +719,7 @@ constexpr int R8_SMEM_MAX = (8 * (int)SMALL_QMAX + 8 * 64 + 64) * 4;  // 8 queri
 
 // NQ queries share a pass (1, 2, 4 or 8: small batches on small stores; each lane then carries NQ accumulators for its chain),
 // PERQ = one list per query instead of one merged list.  Dynamic LDS: [NQ x dimq query floats | NQ x 64 scores | 64 validity words].
-template <bool L2, int E, int NQ, bool PERQ>
+template <int MK, int E, int NQ, bool PERQ>
 __global__ __launch_bounds__(64 * R8_WAVES) void exact_rows8_kernel(ExactParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* sQ = smem;                                 // [NQ][dimq]
@@ -762,14 +773,7 @@ __global__ __launch_bounds__(64 * R8_WAVES) void exact_rows8_kernel(ExactParams 
 #pragma unroll
         for (int q = 0; q < NQ; q++) {
             const float qv = sQ[(uint32_t)q * p.dimq + 8 * jj + c];
-            float pr;
-            if (L2) {
-                const float d = __fsub_rn(qv, xv);
-                pr = __fmul_rn(d, d);
-            } else {
-                pr = __fmul_rn(qv, xv);
-            }
-            acc[q] = __fadd_rn(acc[q], pr);
+            acc[q] = __fadd_rn(acc[q], exact_term<MK>(qv, xv));
         }
     };
     uint32_t j = 0;
@@ -791,14 +795,7 @@ __global__ __launch_bounds__(64 * R8_WAVES) void exact_rows8_kernel(ExactParams 
 #pragma unroll
         for (int q = 0; q < NQ; q++) {
             const float qv = sQ[(uint32_t)q * p.dimq + 8 * full + l];
-            float pr;
-            if (L2) {
-                const float d = __fsub_rn(qv, xv);
-                pr = __fmul_rn(d, d);
-            } else {
-                pr = __fmul_rn(qv, xv);
-            }
-            tail[q] = __fadd_rn(tail[q], pr);
+            tail[q] = __fadd_rn(tail[q], exact_term<MK>(qv, xv));
         }
     }
 #pragma unroll
@@ -1478,13 +1475,13 @@ int exact_grid(const ott_store* s, uint32_t n_tiles) {
     return (int)(want < cap ? want : cap);
 }
 
-template <bool L2, int NQ, int E, bool PERQ>
+template <int MK, int NQ, int E, bool PERQ>
 static int launch_one(ott_store* s, const ExactParams& p, int grid) {
 #ifdef OTT_MFMA_DEBUG_BUILD  // round 2's one-wave LDS-DMA variant (SMALL): retired in round 5 (31 us against rows8's 10 on 10k x 768), instantiated in the diagnostic build only
     if constexpr (NQ == 1 && E <= 2 && !PERQ) {
         if (p.small == 1) {
             static std::atomic<uint64_t> attr_set{0};  // > 64 KB of dynamic LDS needs the opt-in, once per DEVICE (idempotent: a race only repeats it)
-            auto kern = exact_kernel<L2, NQ, E, PERQ, false, true>;
+            auto kern = exact_kernel<MK, NQ, E, PERQ, false, true>;
             if (ott::attr_needed(attr_set, s->device)) {
                 OTT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, EXACT_SMEM_SMALL));
                 ott::attr_done(attr_set, s->device);
@@ -1499,21 +1496,21 @@ static int launch_one(ott_store* s, const ExactParams& p, int grid) {
 #endif
     if constexpr (E == 1) {
         if (p.k > 16) {  // (see BLK)
-            hipLaunchKernelGGL((exact_kernel<L2, NQ, E, PERQ, false, false, true>), dim3(grid), dim3(256), EXACT_SMEM, s->stream, p);
+            hipLaunchKernelGGL((exact_kernel<MK, NQ, E, PERQ, false, false, true>), dim3(grid), dim3(256), EXACT_SMEM, s->stream, p);
             OTT_HIP(hipGetLastError());
             return OTT_OK;
         }
     }
-    hipLaunchKernelGGL((exact_kernel<L2, NQ, E, PERQ>), dim3(grid), dim3(256), EXACT_SMEM, s->stream, p);
+    hipLaunchKernelGGL((exact_kernel<MK, NQ, E, PERQ>), dim3(grid), dim3(256), EXACT_SMEM, s->stream, p);
     OTT_HIP(hipGetLastError());
     return OTT_OK;
 }
 
-template <bool L2>
-static int launch_l2(ott_store* s, const ExactParams& p, int nq_tile, int E, int grid) {
+template <int MK>
+static int launch_pass(ott_store* s, const ExactParams& p, int nq_tile, int E, int grid) {
     const bool perq = p.perq != 0 && nq_tile > 1;
 #define OTT_CASE(NQv, Ev, PQ) \
-    if (nq_tile == NQv && E == Ev && perq == PQ) return launch_one<L2, NQv, Ev, PQ>(s, p, grid);
+    if (nq_tile == NQv && E == Ev && perq == PQ) return launch_one<MK, NQv, Ev, PQ>(s, p, grid);
     OTT_CASE(1, 1, false) OTT_CASE(2, 1, false) OTT_CASE(4, 1, false)
     OTT_CASE(1, 2, false) OTT_CASE(2, 2, false) OTT_CASE(4, 2, false)
     OTT_CASE(1, 4, false) OTT_CASE(1, 8, false)
@@ -1524,26 +1521,27 @@ static int launch_l2(ott_store* s, const ExactParams& p, int nq_tile, int E, int
 }
 
 int launch_exact_dump(ott_store* s, const ExactParams& p, int nq_tile, int grid) {
-    const bool l2 = p.metric == OTT_METRIC_EUCLIDEAN;
-    if (nq_tile == 1) {
-        if (l2) hipLaunchKernelGGL((exact_kernel<true, 1, 1, false, true>), dim3(grid), dim3(256), EXACT_SMEM_DUMP, s->stream, p);
-        else hipLaunchKernelGGL((exact_kernel<false, 1, 1, false, true>), dim3(grid), dim3(256), EXACT_SMEM_DUMP, s->stream, p);
-    } else {
-        if (l2) hipLaunchKernelGGL((exact_kernel<true, 4, 1, false, true>), dim3(grid), dim3(256), EXACT_SMEM_DUMP, s->stream, p);
-        else hipLaunchKernelGGL((exact_kernel<false, 4, 1, false, true>), dim3(grid), dim3(256), EXACT_SMEM_DUMP, s->stream, p);
+#define OTT_DUMP(MKv)                                                                                                                     \
+    if (nq_tile == 1) hipLaunchKernelGGL((exact_kernel<MKv, 1, 1, false, true>), dim3(grid), dim3(256), EXACT_SMEM_DUMP, s->stream, p); \
+    else hipLaunchKernelGGL((exact_kernel<MKv, 4, 1, false, true>), dim3(grid), dim3(256), EXACT_SMEM_DUMP, s->stream, p);
+    switch (metric_kind(p.metric)) {
+        case MK_L2: OTT_DUMP(MK_L2) break;
+        case MK_L1: OTT_DUMP(MK_L1) break;
+        default: OTT_DUMP(MK_DOT) break;
     }
+#undef OTT_DUMP
     OTT_HIP(hipGetLastError());
     return OTT_OK;
 }
 
 // rows8 (p.small == 2): eight lanes per row, one 8-wave workgroup per 64-row tile, 1 / 2 / 4 / 8 queries per pass
-template <bool L2>
+template <int MK>
 static int launch_rows8(ott_store* s, const ExactParams& p, int nq_tile, int E, int grid) {
     const bool perq = p.perq != 0 && nq_tile > 1;
     const size_t smem = ((size_t)nq_tile * p.dimq + (size_t)nq_tile * 64 + 64) * 4;
 #define OTT_R8(NQv, Ev, PQ)                                                                                           \
     if (nq_tile == NQv && E == Ev && perq == PQ) {                                                                    \
-        auto kern = exact_rows8_kernel<L2, Ev, NQv, PQ>;                                                              \
+        auto kern = exact_rows8_kernel<MK, Ev, NQv, PQ>;                                                              \
         if (smem > 48 * 1024) {                                                                                       \
             static std::atomic<uint64_t> attr_set{0};                                                                 \
             if (ott::attr_needed(attr_set, s->device)) {                                                          \
@@ -1565,9 +1563,9 @@ static int launch_rows8(ott_store* s, const ExactParams& p, int nq_tile, int E, 
 
 int launch_exact_i8(ott_store* s, const ExactParams& p, int E, int grid) {
     switch (E) {
-        case 2: hipLaunchKernelGGL((exact_kernel<false, 1, 2, false, false, false, true, true>), dim3(grid), dim3(256), EXACT_SMEM, s->stream, p); break;
-        case 4: hipLaunchKernelGGL((exact_kernel<false, 1, 4, false, false, false, true, true>), dim3(grid), dim3(256), EXACT_SMEM, s->stream, p); break;
-        case 8: hipLaunchKernelGGL((exact_kernel<false, 1, 8, false, false, false, true, true>), dim3(grid), dim3(256), EXACT_SMEM, s->stream, p); break;
+        case 2: hipLaunchKernelGGL((exact_kernel<MK_DOT, 1, 2, false, false, false, true, true>), dim3(grid), dim3(256), EXACT_SMEM, s->stream, p); break;
+        case 4: hipLaunchKernelGGL((exact_kernel<MK_DOT, 1, 4, false, false, false, true, true>), dim3(grid), dim3(256), EXACT_SMEM, s->stream, p); break;
+        case 8: hipLaunchKernelGGL((exact_kernel<MK_DOT, 1, 8, false, false, false, true, true>), dim3(grid), dim3(256), EXACT_SMEM, s->stream, p); break;
         default: return fail(OTT_ERR_INVALID, "launch_exact_i8: the candidate list holds 128, 256 or 512 entries");
     }
     OTT_HIP(hipGetLastError());
@@ -1575,9 +1573,11 @@ int launch_exact_i8(ott_store* s, const ExactParams& p, int E, int grid) {
 }
 
 int launch_exact(ott_store* s, const ExactParams& p, int nq_tile, int E, int grid) {
-    if (p.small == 2) return p.metric == OTT_METRIC_EUCLIDEAN ? launch_rows8<true>(s, p, nq_tile, E, grid) : launch_rows8<false>(s, p, nq_tile, E, grid);
-    if (p.metric == OTT_METRIC_EUCLIDEAN) return launch_l2<true>(s, p, nq_tile, E, grid);
-    return launch_l2<false>(s, p, nq_tile, E, grid);
+    switch (metric_kind(p.metric)) {
+        case MK_L2: return p.small == 2 ? launch_rows8<MK_L2>(s, p, nq_tile, E, grid) : launch_pass<MK_L2>(s, p, nq_tile, E, grid);
+        case MK_L1: return p.small == 2 ? launch_rows8<MK_L1>(s, p, nq_tile, E, grid) : launch_pass<MK_L1>(s, p, nq_tile, E, grid);
+        default: return p.small == 2 ? launch_rows8<MK_DOT>(s, p, nq_tile, E, grid) : launch_pass<MK_DOT>(s, p, nq_tile, E, grid);
+    }
 }
 
 int launch_merge(ott_store* s, const Cand* lists, uint32_t n_lists, uint32_t list_stride, uint64_t group_stride,

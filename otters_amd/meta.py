@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import Cmp, Metric, Mode, Path, ResolvedQuery, TakeType, VecStore
+from .vec import Cmp, Metric, Mode, Path, ResolvedQuery, TakeType, VecStore, infer_default_take_type
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -702,7 +702,7 @@ class MetaQueryPlan:  # src/meta.rs:579-830
 
     def take(self, k: int) -> "MetaQueryPlan":  # src/meta.rs:623-630
         self.take_count = int(k)
-        self.take_type = TakeType.Min if self.metric == Metric.Euclidean else TakeType.Max
+        self.take_type = infer_default_take_type(self.metric)
         return self
 
     def with_path(self, path: Path) -> "MetaQueryPlan":
@@ -716,7 +716,7 @@ class MetaQueryPlan:  # src/meta.rs:579-830
             raise OttersError(self.meta_error)
         st = self.store
         k = self.take_count if self.take_count is not None else st._n_rows  # src/meta.rs:638-640
-        take = self.take_type if self.take_type is not None else (TakeType.Min if self.metric == Metric.Euclidean else TakeType.Max)
+        take = self.take_type if self.take_type is not None else (infer_default_take_type(self.metric))
         for q in self.queries:
             if st._n_rows and q.size != st._dim:
                 raise OttersError(f"Query vector length {q.size} does not match expected dimension {st._dim}")

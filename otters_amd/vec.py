@@ -28,6 +28,7 @@ class Metric(enum.IntEnum):  # src/vec.rs:11-16
     Cosine = 0
     Euclidean = 1
     DotProduct = 2
+    Manhattan = 3   # extension: L1, sum of |q[i] - v[i]| in the other metrics' order; Path.Exact only (Path.Auto sends it there)
 
 
 class TakeType(enum.IntEnum):  # src/vec.rs:18-22
@@ -101,7 +102,7 @@ class ResolvedQuery:
 
 
 def infer_default_take_type(metric: Metric) -> TakeType:  # src/vec.rs:92-98
-    return TakeType.Min if metric == Metric.Euclidean else TakeType.Max
+    return TakeType.Min if metric in (Metric.Euclidean, Metric.Manhattan) else TakeType.Max
 
 
 class VecQueryPlan:
