@@ -70,8 +70,9 @@ typedef enum { OTT_DT_INT32 = 0, OTT_DT_INT64 = 1, OTT_DT_FLOAT32 = 2, OTT_DT_FL
  * (src/vec.rs:217-219).  PER_QUERY is an extension: k hits for each query. */
 typedef enum { OTT_MODE_MERGED = 0, OTT_MODE_PER_QUERY = 1 } ott_mode;
 
-/* Which scoring kernel family runs.  EXACT scores every row in the reference's summation order (one pass over the f32 rows
- * per 4 queries).  MFMA is the certified cascade, cosine / Euclidean / dot, k <= 484: candidate passes over compact copies of the corpus
+/* Which scoring kernel family runs.  EXACT returns exactly what scoring every row in the reference's summation order returns
+ * (one pass over the f32 rows per 4 queries); a single query may skip the last dims of rows that provably miss the top-k
+ * (option "exact_prune": a bound on the rest of the dot product against a seed's k-th best; no copy of the corpus).  MFMA is the certified cascade, cosine / Euclidean / dot, k <= 484: candidate passes over compact copies of the corpus
  * — an int8 plane first (k <= 128: a quarter of the f32 bytes; batches on the matrix cores, a single cosine / dot query as a
  * streaming sweep), a 16-bit hi plane for what that cannot certify, split bf16 behind it — every candidate
  * re-scored in the reference's order, the top-k CERTIFIED against a measured error bound, uncertifiable queries recomputed on
@@ -239,7 +240,7 @@ int ott_store_batch_ready(const ott_store* s);
 
 /* Behaviour switches of one store.  The library reads the environment exactly once per store, in ott_store_create
  * (OTT_<NAME>=<int> presets the option of the same name); after that only this call changes them — the query path never calls
- * getenv.  Sixteen options (round 5 retired the rest: experiment switches whose measurements are in DESIGN.md 3.4 and profiles/dead_ends_rounds_2_4.md).
+ * getenv.  Seventeen options (round 5 retired the rest: experiment switches whose measurements are in DESIGN.md 3.4 and profiles/dead_ends_rounds_2_4.md).
  * Behaviour a host may want:
  *   "tie_order"  0 (default): canonical total order — better score, lower row, lower query.  1: the reference's own outcome at
  *                exact score ties, ONE TopKCollector over the store (VecStore, src/vec.rs:217-310, src/vec_compute.rs:236-277).
@@ -256,6 +257,8 @@ int ott_store_batch_ready(const ott_store* s);
  *   "multi_transport", "multi_rebalance", "multi_min_shard_rows": the multi-GPU store, see ott_store_create_multi.
  * Which of several equivalent paths runs (results never depend on them; the tests hold each to the oracle):
  *   "exact_small" (-1 auto / 0 streaming kernel / 2 rows8, eight lanes per row: which kernel answers on a small store),
+ *   "exact_prune" (-1 auto, from 2^20 rows and dim 225 / 0 off / 1 forced: a single cosine / dot query on EXACT scores a tenth of
+ *   the rows first, then skips the last eighth of the dims of rows whose score bound misses that seed's k-th best),
  *   "large_k_from" (k above which host-output queries take the sort path; 0 = default: 512 for one query or a small store,
  *   128 for several queries on a large one), "small_sort" (0: results of up to 16384 (row, query) pairs with k > 512 through
  *   the radix sort instead of the rank sort), "mfma_f32" (batch path: one candidate pass on the f32 matrix pipe),

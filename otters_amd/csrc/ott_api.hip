@@ -7,6 +7,7 @@
 #include <chrono>
 
 #include "ott_internal.h"
+#include "ott_prune.h"
 
 using namespace ott;
 
@@ -223,9 +224,38 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
 
     // single query, at most two runs: everything the kernel needs rides in its arguments (no H2D copy, no staging)
     const bool lean = nq == 1 && s->dimq <= OTT_QEMB_MAX && pl.runs.size() <= 2;
+    // Pruned sweep (store option exact_prune): one query, merged, cosine / dot, the streaming kernel.  A seed of a
+    // tenth of the rows is scored in full and merged; its k-th best gates the second launch over the rest, which skips the last
+    // stages (from c, 7/8 of them) of every row whose score bound misses it.  Automatic from 2^20 rows and 8 stages (dim >= 225).
+    uint32_t prune_c = 0;
+    RunPlan plA, plB;
+    double prune_qt = 0.0, prune_qn = 0.0;
+    if (lean && !perq && small == 0 && !s->cur_flat && s->opt.exact_prune != 0 &&
+        (d->metric == OTT_METRIC_COSINE || d->metric == OTT_METRIC_DOT)) {
+        const uint32_t nst = (s->ld + 31) / 32;
+        uint32_t c = nst * 7 / 8;
+        while (c > 0 && c * 32 > s->dim - s->dim % 8) c--;  // the prefix holds whole chunks of eight only (no remainder term yet)
+        const bool worth = s->opt.exact_prune == 1 || (nst >= 8 && pl.rows_scored >= (1ull << 20));
+        if (worth && c >= 1 && c < nst) {
+            uint64_t seed = (pl.rows_scored / 10 + 63) & ~63ull;
+            if (seed < 64) seed = 64;
+            split_plan(pl, seed, plA, plB);
+            if (plA.runs.size() <= 2 && plB.runs.size() <= 2 && plB.rows_scored > 0 &&
+                prune_query_bounds(queries, s->dim, c * 32, &prune_qt, &prune_qn))
+                prune_c = c;
+        }
+    }
+    std::vector<uint32_t> preA, preB;
+    int gridA = 0, gridB = 0;
+    if (prune_c) {
+        preA = tile_prefix(plA, 64);
+        preB = tile_prefix(plB, 64);
+        gridA = exact_grid(s, preA.back());
+        gridB = exact_grid(s, preB.back());
+    }
     int rc;
     if (!lean && (rc = upload_exact_inputs(s, queries, nq, pl, prefix))) return rc;
-    const size_t n_lists_total = perq ? (size_t)nq * grid : (size_t)passes * grid;
+    const size_t n_lists_total = prune_c ? (size_t)(gridA + gridB) : perq ? (size_t)nq * grid : (size_t)passes * grid;
     if ((rc = s->d_lists.ensure(n_lists_total * KS * sizeof(Cand)))) return rc;
     const uint32_t groups = perq ? nq : 1;
     // results block: [counts (groups x u64, padded to 64 B) | hits (groups x KS)].  Host output: the merge kernel
@@ -266,15 +296,46 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
     }
 
     if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
-    for (uint32_t ps = 0; ps < passes; ps++) {
-        p.q0 = ps * tile;
-        // merged: one list group per pass.  per-query: list (query, block) lives at (query*grid + block)*KS; a
-        // 1-query pass runs the single-list kernel, so it is pointed at its query's slot (q0 == ps there)
-        p.lists = (Cand*)s->d_lists.p + ((perq && tile > 1) ? 0 : (size_t)ps * grid * KS);
-        if ((rc = launch_exact(s, p, (int)tile, E, grid))) return rc;
+    if (prune_c) {
+        // [count (u64, 64 B) | KS hits]: the seed's merged result, read by the second launch
+        if ((rc = s->d_prune.ensure(64 + (size_t)KS * sizeof(ott_hit)))) return rc;
+        uint64_t* seed_res = (uint64_t*)s->d_prune.p;
+        auto part = [&](const RunPlan& sub, const std::vector<uint32_t>& pre, Cand* dst) {
+            ExactParams q = p;
+            q.n_runs = (uint32_t)sub.runs.size();
+            q.n_tiles = pre.back();
+            memset(q.eruns, 0, sizeof(q.eruns));
+            memset(q.eprefix, 0, sizeof(q.eprefix));
+            for (size_t i = 0; i < sub.runs.size(); i++) q.eruns[i] = sub.runs[i];
+            for (size_t i = 0; i < pre.size(); i++) q.eprefix[i] = pre[i];
+            q.lists = dst;
+            return q;
+        };
+        const ExactParams pa = part(plA, preA, (Cand*)s->d_lists.p);
+        if ((rc = launch_exact(s, pa, 1, E, gridA))) return rc;
+        if ((rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)gridA, KS, 0, 1, (uint32_t)k_eff, E, p.take_max != 0, tie_base(s),
+                               (ott_hit*)(seed_res + 8), KS, seed_res, s->cur_tie_sh)))
+            return rc;
+        ExactParams pb = part(plB, preB, (Cand*)s->d_lists.p + (size_t)gridA * KS);
+        pb.prune_stage = prune_c;
+        pb.prune_seed = seed_res;
+        pb.prune_qt = prune_qt;
+        pb.prune_qn = prune_qn;
+        if ((rc = launch_exact(s, pb, 1, E, gridB))) return rc;
+    } else {
+        for (uint32_t ps = 0; ps < passes; ps++) {
+            p.q0 = ps * tile;
+            // merged: one list group per pass.  per-query: list (query, block) lives at (query*grid + block)*KS; a
+            // 1-query pass runs the single-list kernel, so it is pointed at its query's slot (q0 == ps there)
+            p.lists = (Cand*)s->d_lists.p + ((perq && tile > 1) ? 0 : (size_t)ps * grid * KS);
+            if ((rc = launch_exact(s, p, (int)tile, E, grid))) return rc;
+        }
     }
     if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
-    if (perq)
+    if (prune_c)  // the block lists of both launches
+        rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)(gridA + gridB), KS, 0, 1, (uint32_t)k_eff, E, p.take_max != 0,
+                          tie_base(s), d_hits, KS, d_counts, s->cur_tie_sh);
+    else if (perq)
         rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)grid, KS, (uint64_t)grid * KS, nq, (uint32_t)k_eff, E,
                           p.take_max != 0, tie_base(s), d_hits, KS, d_counts, s->cur_tie_sh);
     else

@@ -24,6 +24,7 @@
 #include <atomic>
 
 #include "ott_internal.h"
+#include "ott_prune.h"
 
 namespace ott {
 
@@ -33,6 +34,12 @@ constexpr int STAGE_FLOATS = 64 * KC;  // per wave: 8 KB
 constexpr int EXACT_SMEM = WAVES * STAGE_FLOATS * 4;
 constexpr int DUMP_QCAP = 128;  // large-k dump: survivors queued per wave between two appends (8 B key + 4 B query each)
 constexpr int EXACT_SMEM_DUMP = EXACT_SMEM + WAVES * DUMP_QCAP * 12;
+// pruned sweep (PRUNE): a wave's deferred-tail queue, a ring of rows that passed the checkpoint — 8 partial accumulators, the
+// inverse norm and the row, one array each.  64 are finished together as one dense tile; the ring holds the 63 that may wait
+// plus a whole tile's 64 more
+constexpr int PQ_CAP = 128;
+constexpr int PQ_WORDS = 10;
+constexpr int EXACT_SMEM_PRUNE = EXACT_SMEM + WAVES * PQ_CAP * PQ_WORDS * 4;  // 52 KB: two workgroups per CU
 // Workgroups per CU of the persistent grid.  TWO since round 6 (8 waves per CU, 64 KB of row stages in flight per CU, 512 block lists for
 // the merge): measured against 3, 4 (rounds 2-5), 5 and 8 on every instantiation — 1M x 128 dot top-10 89.4 + 11.8 -> 86.3 + 9.7 us
 // (scoring + merge), 2M / 4M x 128 5 % / 3 % faster, 3M x 768 2 %, the 10M x 768 headline 4403 -> 4374 us, four queries per pass 4799
@@ -321,9 +328,16 @@ __device__ __forceinline__ float reduce8(const float* l, uint32_t mode) {
 // copy rides in the kernel arguments, a lane accumulates its row with v_dot4 (exact i32), and the "score" offered to the wave
 // list is the APPROXIMATE (float)(q~ . v~) x row factor: the list's T best go to the exact re-score (run_i8_single).  Rows
 // outside the pass's error model (flag bits 0 / 2) are always listed, ranked first.
-template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false>
+// PRUNE: the pruned sweep of ONE query, cosine / dot, merged.  A tile runs stages 0 .. c-1 (c = p.prune_stage),
+// summing each row's prefix squares beside the eight chains; then every row whose score bound (ott_prune.h) ranks strictly below
+// the gate — the seed launch's k-th best, or the wave's own k-th once that is higher — is dropped, and the others (the
+// accumulators, the inverse norm, the row) go to the wave's deferred-tail queue in LDS.  The next tile starts at once; whenever
+// 64 rows wait they are finished as one dense tile — stages c .. n-1, the same loads and the same additions in the same order,
+// so the same bits — and offered to the list (the list orders by key: when a row is offered changes nothing).
+template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false>
 __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) {
     static_assert(!I8 || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL), "the int8 sweep takes one query, cosine / dot, merged");
+    static_assert(!PRUNE || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL && !I8), "the pruned sweep takes one query, cosine / dot, merged");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -405,6 +419,89 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
     // end must not make the LAST row of the store read past the allocation
     const uint32_t lsl4 = ((uint32_t)lslot * 4 < p.ld) ? (uint32_t)lslot * 4 : 0u;
 
+    // PRUNE: the gate (the seed's k-th best score ordinal, 0 = open while the seed listed fewer than k rows), the stages a tile
+    // runs in the sweep, the wave's queue, and how queued rows are finished
+    const uint32_t s_end = PRUNE ? p.prune_stage : nstages;
+    uint32_t theta = 0;
+    if constexpr (PRUNE) {
+        if (p.prune_seed[0] >= p.k) theta = ord_of(reinterpret_cast<const ott_hit*>(p.prune_seed + 8)[p.k - 1].score, take_max);
+    }
+    float* pq = smem + WAVES * STAGE_FLOATS + wave * (PQ_CAP * PQ_WORDS);  // [acc 0..7 | vinv | row] x PQ_CAP
+    uint32_t* pq_row = reinterpret_cast<uint32_t*>(pq + 9 * PQ_CAP);
+    uint32_t pq_head = 0, pq_n = 0;  // wave-uniform
+    auto pq_finish = [&](uint32_t n) {  // the first n <= 64 queued rows: stages c .. n-1 as one tile, then the list
+        wave_sync();
+        const bool valid = (uint32_t)lane < n;
+        const uint32_t e = (pq_head + (valid ? (uint32_t)lane : 0u)) & (PQ_CAP - 1);
+        float acc[8];
+#pragma unroll
+        for (int l = 0; l < 8; l++) acc[l] = pq[l * PQ_CAP + e];
+        const float vinv = pq[8 * PQ_CAP + e];
+        const uint32_t my_row = pq_row[e];
+        float tail = 0.0f;
+        const float* rp[8];
+        bool rok[8];
+#pragma unroll
+        for (int m = 0; m < 8; m++) {  // rows past n re-read the first queued row (never offered)
+            const uint32_t i = 8 * m + lrow;
+            rok[m] = i < n;
+            rp[m] = p.rows + (uint64_t)pq_row[(pq_head + (rok[m] ? i : 0u)) & (PQ_CAP - 1)] * p.ld + lsl4;
+        }
+        v4f R[8];
+        auto load_stage = [&](uint32_t s) {
+            const uint32_t soff = (s * KC + lslot * 4 < p.ld) ? s * KC : 0u;
+#pragma unroll
+            for (int m = 0; m < 8; m++) R[m] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(rp[m] + soff));
+        };
+        load_stage(p.prune_stage);
+        for (uint32_t s = p.prune_stage; s < nstages; s++) {
+            const bool cok = s * KC + lslot * 4 < p.ld;
+#pragma unroll
+            for (int m = 0; m < 8; m++) {
+                const int row = 8 * m + lrow;
+                const bool ok = rok[m] & cok;
+                const v4f v = R[m];
+                *reinterpret_cast<float4*>(st + row * KC + ((lslot ^ ((row >> 1) & 7)) << 2)) =
+                    make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
+            }
+            wave_sync();
+            if (s + 1 < nstages) load_stage(s + 1);
+#pragma unroll
+            for (int j = 0; j < KC / 8; j++) {
+                const uint32_t col = s * KC + 8 * j;
+                if (col < p.dim) {
+                    const float4 a = *reinterpret_cast<const float4*>(st + lane * KC + (((2 * j) ^ sw) << 2));
+                    const float4 b = *reinterpret_cast<const float4*>(st + lane * KC + (((2 * j + 1) ^ sw) << 2));
+                    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+                    if (col + 8 <= p.dim) {
+#pragma unroll
+                        for (int l = 0; l < 8; l++) acc[l] = __fadd_rn(acc[l], exact_term<MK>(Q[col + l], x[l]));
+                    } else {
+                        const uint32_t nt = p.dim - col;
+#pragma unroll
+                        for (int l = 0; l < 7; l++)
+                            if ((uint32_t)l < nt) tail = __fadd_rn(tail, exact_term<MK>(Q[col + l], x[l]));
+                    }
+                }
+            }
+            wave_sync();
+        }
+        float sc = __fadd_rn(reduce8(acc, p.reduce), tail);
+        if (p.metric == OTT_METRIC_COSINE) sc = __fmul_rn(__fmul_rn(sc, qinv[0]), vinv);
+        const bool pass = valid && !(sc != sc) && cmp_holds(sc, p.cmp, p.thr);
+        const uint64_t key = ((uint64_t)ord_of(sc, take_max) << 32) | (uint32_t)(~(my_row + p.tie_off));
+        if (fresh[0]) {
+            wl_fill_sorted(L[0], tk[0], tq[0], p.k, pass, key, p.q0, lane, p.tie_sh);
+            fresh[0] = false;
+        } else if constexpr (!BLK) {
+            wl_offer(L[0], tk[0], tq[0], p.k, pass, key, p.q0, lane, p.tie_sh);
+        } else {
+            wl_offer_block(L[0], tk[0], tq[0], p.k, pass, key, p.q0, lane, p.tie_sh);
+        }
+        pq_head = (pq_head + n) & (PQ_CAP - 1);
+        pq_n -= n;
+    };
+
     for (uint32_t t = gw; t < p.n_tiles; t += nw) {
         // tile -> run of surviving chunks (wave-uniform scalar search)
         uint32_t lo = 0, hi = p.n_runs;
@@ -428,7 +525,8 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
         // the row's inverse norm is fetched now and used after the K loop: its latency hides behind the stages (after the
         // loop it was a ~2 us bubble per tile, which shows at small dims where a tile is only a few stages long)
         float vinv = 0.0f;
-        if (p.metric == OTT_METRIC_COSINE && valid) vinv = p.inv[my_row];
+        if ((PRUNE || p.metric == OTT_METRIC_COSINE) && valid) vinv = p.inv[my_row];  // (PRUNE: the bound needs ||v||, dot too)
+        float vsq = 0.0f;  // PRUNE: the prefix's sum of squares
         float i8_rf = 0.0f;     // I8: the row factor s_v [x 1/||v||] x s_Q
         bool i8_forced = false; // I8: a row outside the error model
         if constexpr (I8) {
@@ -498,7 +596,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
         } else {
             load_stage(0);
         }
-        for (uint32_t s = 0; s < nstages; s++) {
+        for (uint32_t s = 0; s < s_end; s++) {
             const float* sst = st;
             if constexpr (SMALL) {
                 // issued so far: stages 0 .. s+RING-2.  Stage s has landed when at most the later stages' pieces (8 each,
@@ -526,7 +624,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                         make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
                 }
                 wave_sync();
-                if (s + 1 < nstages) load_stage(s + 1);
+                if (s + 1 < s_end) load_stage(s + 1);
             }
 
             if constexpr (I8) {
@@ -566,6 +664,10 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                                 acc[q][l] = __fadd_rn(acc[q][l], exact_term<MK>(qv, x[l]));
                             }
                         }
+                        if constexpr (PRUNE) {
+#pragma unroll
+                            for (int l = 0; l < 8; l++) vsq = fmaf(x[l], x[l], vsq);
+                        }
                     } else {
                         // remainder: sequential sum of the last dim%8 products (vec_compute.rs:15-21, 44-53)
                         const uint32_t nt = p.dim - col;
@@ -587,6 +689,31 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             }
             }
             wave_sync();
+        }
+
+        if constexpr (PRUNE) {
+            // the checkpoint: a row whose bound ranks strictly below the gate is done; the others wait in the queue for stages c ..
+            // n-1.  The gate is the seed's k-th best or, once higher, the wave's own (0 while its list holds fewer than k)
+            uint32_t gate = theta;
+            const uint32_t own = (uint32_t)(tk[0] >> 32);
+            if (own > gate) gate = own;
+            bool keep = valid;
+            if (valid && gate != 0) {
+                const float b = prune_score_bound(acc[0], vsq, vinv, p.prune_stage * KC, p.dim, p.prune_qt, p.prune_qn, qinv[0],
+                                                  p.metric == OTT_METRIC_COSINE, take_max);
+                keep = !(b == b && ord_of(b, take_max) < gate);  // (NaN: no bound, the row is finished)
+            }
+            const uint64_t km = __ballot(keep);
+            if (keep) {
+                const uint32_t at = (pq_head + pq_n + (uint32_t)__popcll(km & ((1ull << lane) - 1ull))) & (PQ_CAP - 1);
+#pragma unroll
+                for (int l = 0; l < 8; l++) pq[l * PQ_CAP + at] = acc[0][l];
+                pq[8 * PQ_CAP + at] = vinv;
+                pq_row[at] = (uint32_t)my_row;
+            }
+            pq_n += (uint32_t)__popcll(km);
+            if (pq_n >= 64) pq_finish(64);
+            continue;
         }
 
         // scores -> filter -> top-k gate
@@ -640,6 +767,9 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
         }
     }
 
+    if constexpr (PRUNE) {
+        if (pq_n) pq_finish(pq_n);  // (< 64 left)
+    }
     if (DUMP) {
         dq_flush();
         return;
@@ -1475,8 +1605,31 @@ int exact_grid(const ott_store* s, uint32_t n_tiles) {
     return (int)(want < cap ? want : cap);
 }
 
+// the pruned sweep (p.prune_stage != 0): its queue takes the dynamic LDS past 48 KB
+template <int E, bool BLK>
+static int launch_prune(ott_store* s, const ExactParams& p, int grid) {
+    auto kern = exact_kernel<MK_DOT, 1, E, false, false, false, BLK, false, true>;
+    static std::atomic<uint64_t> attr_set{0};
+    if (ott::attr_needed(attr_set, s->device)) {
+        OTT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, EXACT_SMEM_PRUNE));
+        ott::attr_done(attr_set, s->device);
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), EXACT_SMEM_PRUNE, s->stream, p);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+
 template <int MK, int NQ, int E, bool PERQ>
 static int launch_one(ott_store* s, const ExactParams& p, int grid) {
+    if constexpr (MK == MK_DOT && NQ == 1 && !PERQ) {
+        if (p.prune_stage != 0) {
+            if constexpr (E == 1) {
+                if (p.k > 16) return launch_prune<1, true>(s, p, grid);  // (see BLK)
+            }
+            return launch_prune<E, (E > 1)>(s, p, grid);
+        }
+    }
+    if (p.prune_stage != 0) return fail(OTT_ERR_INVALID, "launch_exact: the pruned sweep takes one query, cosine / dot, merged");
 #ifdef OTT_MFMA_DEBUG_BUILD  // round 2's one-wave LDS-DMA variant (SMALL): retired in round 5 (31 us against rows8's 10 on 10k x 768), instantiated in the diagnostic build only
     if constexpr (NQ == 1 && E <= 2 && !PERQ) {
         if (p.small == 1) {

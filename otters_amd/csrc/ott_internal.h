@@ -73,15 +73,17 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  SIXTEEN of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  SEVENTEEN of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
 struct Options {
     int exact_small = -1;         // single-query small-store kernel: -1 = automatic, 0 = streaming kernel, 2 = rows8 (eight lanes per row)
                                   // (1, round 2's one-wave LDS-DMA variant, is retired: 31 us against rows8's 10)
+    int exact_prune = -1;         // single-query exact sweep: score a seed of the rows first, then skip the last stages of rows whose score
+                                  // bound misses the seed's k-th best: -1 = automatic (stores of 2^20 rows and more), 0 = off, 1 = forced
     int force_fallback = 0;       // TESTS: bit mask of code paths the library otherwise takes only in rare conditions, forced on so that the
                                   // suite and the option fuzz hold them to the oracle: 1 = block lists merged by insertion (merge_kernel: the
                                   // rank merge's own fallback when a plateau overflows its buffer or there are > 4096 lists), 2 = k <= 64
@@ -248,6 +250,7 @@ struct ott_store {
 
     // per-query scratch
     ott::DevBuf d_queries, d_qinv, d_rowmask, d_runs, d_prefix, d_lists, d_lists2, d_hits, d_count, d_cand, d_misc;  // d_lists2: first stage of the two-stage merge
+    ott::DevBuf d_prune;     // pruned exact sweep: the seed's merged result (the gate of the second launch)
     ott::DevBuf d_minpos;    // device word behind min_pos_inv
     // MFMA path scratch
     ott::DevBuf m_Q, m_qinv, m_qnorm, m_tau, m_cntA, m_cntB, m_candA, m_candB, m_over, m_out, m_outcnt, m_uncert, m_prefix;
@@ -447,6 +450,12 @@ struct ExactParams {
     float i8_qscale;        // s_Q: the query's quantisation scale
     const float* i8_scale;  // [n] s_v
     const uint8_t* flag;    // [n] rows outside the pass's error model (bits 0, 2): always listed, ranked first
+    // pruned sweep of a SINGLE query (exact_kernel<..., PRUNE>): at stage prune_stage (0 = off) a row whose
+    // score bound (ott_prune.h) ranks strictly below the seed's k-th best is not finished.  prune_seed: the seed launch's merged
+    // result block, [count (u64, 64 B) | hits]; prune_qt / prune_qn: upper bounds of ||q[prune_stage * 32:]|| and ||q||
+    uint32_t prune_stage;
+    const uint64_t* prune_seed;
+    double prune_qt, prune_qn;
     float qemb[896];  // last: the embedded query (kernel arguments are limited to 4 KB)
 };
 constexpr uint32_t OTT_QEMB_MAX = 896;
@@ -477,6 +486,7 @@ struct RunPlan {
     uint64_t rows_scored = 0, total_chunks = 0, evaluated = 0;
 };
 std::vector<uint32_t> tile_prefix(const RunPlan& pl, uint32_t tile_rows);
+void split_plan(const RunPlan& pl, uint64_t m_rows, RunPlan& a, RunPlan& b);  // the first m_rows rows of a plan and the rest
 
 // large-k path (k > 512): score dump + device radix sort.  Entries [0, *n_entries) of (l_keysA|B, l_qA|B) are left sorted in
 // canonical order (merged) or grouped by query (per-query); results are copied to `lists`.

@@ -563,7 +563,7 @@ __global__ void gate_from_sorted_kernel(const uint64_t* keys, const uint32_t* st
 }
 
 // the first `m_rows` rows of a plan and the rest
-static void split_plan(const RunPlan& pl, uint64_t m_rows, RunPlan& a, RunPlan& b) {
+void split_plan(const RunPlan& pl, uint64_t m_rows, RunPlan& a, RunPlan& b) {
     a = RunPlan();
     b = RunPlan();
     uint64_t left = m_rows;
