@@ -72,7 +72,11 @@ typedef enum { OTT_MODE_MERGED = 0, OTT_MODE_PER_QUERY = 1 } ott_mode;
 
 /* Which scoring kernel family runs.  EXACT returns exactly what scoring every row in the reference's summation order returns
  * (one pass over the f32 rows per 4 queries); a single query may skip the last dims of rows that provably miss the top-k
- * (option "exact_prune": a bound on the rest of the dot product against a seed's k-th best; no copy of the corpus).  MFMA is the certified cascade, cosine / Euclidean / dot, k <= 484: candidate passes over compact copies of the corpus
+ * (option "exact_prune": a bound on the rest of the dot product against a seed's k-th best).  That bound may use a per-row
+ * sketch of the row's last quarter (option "exact_sketch": one sign bit per dim, a mean magnitude and a remainder norm — 32 B
+ * beside a 3072-B row at dim 768, about 1 % of the store's HBM, made once when rows are appended and valid for every later
+ * query): per-row metadata of the same kind as the inverse norm, not a plane a query could be answered from — every returned row
+ * is still finished over all of its f32 dims in the reference's summation order.  MFMA is the certified cascade, cosine / Euclidean / dot, k <= 484: candidate passes over compact copies of the corpus
  * — an int8 plane first (k <= 128: a quarter of the f32 bytes; batches on the matrix cores, a single cosine / dot query as a
  * streaming sweep), a 16-bit hi plane for what that cannot certify, split bf16 behind it — every candidate
  * re-scored in the reference's order, the top-k CERTIFIED against a measured error bound, uncertifiable queries recomputed on
@@ -125,7 +129,9 @@ typedef struct {
     uint64_t bytes_scanned;     /* algorithmic: 4*dim*rows_scored (+4*rows_scored for cosine), per pass */
     uint32_t path_used;         /* ott_path */
     uint32_t passes;            /* corpus passes (EXACT path: ceil(nq / queries per pass)) */
-    uint64_t rescored;          /* MFMA path: candidates re-scored in reference order */
+    uint64_t rescored;          /* MFMA path: candidates re-scored in reference order.  EXACT path, pruned sweep of one query (host
+                                   output): rows that passed the checkpoint and had their last stages read (of the rows behind the
+                                   seed; 0 when the sweep was not pruned) */
     uint32_t retries;           /* MFMA path: queries no candidate pass could certify, recomputed on the exact path */
     uint32_t refined;           /* MFMA path: queries the hi pass (bf16 hi plane) could not certify, re-run through the split pass */
     float err_ratio_max;        /* MFMA path: max over the re-scored candidates of |approximate - exact score| / eps, eps the error bound
@@ -240,7 +246,7 @@ int ott_store_batch_ready(const ott_store* s);
 
 /* Behaviour switches of one store.  The library reads the environment exactly once per store, in ott_store_create
  * (OTT_<NAME>=<int> presets the option of the same name); after that only this call changes them — the query path never calls
- * getenv.  Seventeen options (round 5 retired the rest: experiment switches whose measurements are in DESIGN.md 3.4 and profiles/dead_ends_rounds_2_4.md).
+ * getenv.  Eighteen options (round 5 retired the rest: experiment switches whose measurements are in DESIGN.md 3.4 and profiles/dead_ends_rounds_2_4.md).
  * Behaviour a host may want:
  *   "tie_order"  0 (default): canonical total order — better score, lower row, lower query.  1: the reference's own outcome at
  *                exact score ties, ONE TopKCollector over the store (VecStore, src/vec.rs:217-310, src/vec_compute.rs:236-277).
@@ -259,6 +265,11 @@ int ott_store_batch_ready(const ott_store* s);
  *   "exact_small" (-1 auto / 0 streaming kernel / 2 rows8, eight lanes per row: which kernel answers on a small store),
  *   "exact_prune" (-1 auto, from 2^20 rows and dim 225 / 0 off / 1 forced: a single cosine / dot query on EXACT scores a tenth of
  *   the rows first, then skips the last eighth of the dims of rows whose score bound misses that seed's k-th best),
+ *   "exact_sketch" (-1 auto: stores of dim >= 225 / 0 never / 1 always: the store keeps the pruned sweep's tail sign sketch — per
+ *   row the sign bits of the last quarter of its 32-dim stages, the mean of their magnitudes and an upper bound of the norm of
+ *   what the two leave out; 32 B per row at dim 768, computed behind the inverse norms on every append — and the sweep then
+ *   stops a row after three quarters of its dims instead of seven eighths.  Set it before rows are appended: switched on later,
+ *   the sketch is made at the next append; a store without one takes the 7/8 form),
  *   "large_k_from" (k above which host-output queries take the sort path; 0 = default: 512 for one query or a small store,
  *   128 for several queries on a large one), "small_sort" (0: results of up to 16384 (row, query) pairs with k > 512 through
  *   the radix sort instead of the rank sort), "mfma_f32" (batch path: one candidate pass on the f32 matrix pipe),

@@ -227,22 +227,34 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
     // Pruned sweep (store option exact_prune): one query, merged, cosine / dot, the streaming kernel.  A seed of a
     // tenth of the rows is scored in full and merged; its k-th best gates the second launch over the rest, which skips the last
     // stages (from c, 7/8 of them) of every row whose score bound misses it.  Automatic from 2^20 rows and 8 stages (dim >= 225).
+    // A store that keeps a tail sign sketch for every row (option exact_sketch) takes the sketch form: the checkpoint is the sketch's
+    // first stage, 3/4 of the stages.
     uint32_t prune_c = 0;
+    bool prune_sk = false;
     RunPlan plA, plB;
-    double prune_qt = 0.0, prune_qn = 0.0;
+    double prune_qt = 0.0, prune_qn = 0.0, prune_q1 = 0.0;
     if (lean && !perq && small == 0 && !s->cur_flat && s->opt.exact_prune != 0 &&
         (d->metric == OTT_METRIC_COSINE || d->metric == OTT_METRIC_DOT)) {
         const uint32_t nst = (s->ld + 31) / 32;
         uint32_t c = nst * 7 / 8;
         while (c > 0 && c * 32 > s->dim - s->dim % 8) c--;  // the prefix holds whole chunks of eight only (no remainder term yet)
+        if (s->opt.exact_sketch != 0 && s->d_sketch != nullptr && s->sk_n >= s->n && s->sk_words <= OTT_SKETCH_MAX_WORDS) {
+            const uint32_t cs = s->sk_stage0;
+            if (cs >= 1 && cs < nst && cs * 32 <= s->dim - s->dim % 8) {
+                c = cs;
+                prune_sk = true;
+            }
+        }
         const bool worth = s->opt.exact_prune == 1 || (nst >= 8 && pl.rows_scored >= (1ull << 20));
         if (worth && c >= 1 && c < nst) {
             uint64_t seed = (pl.rows_scored / 10 + 63) & ~63ull;
             if (seed < 64) seed = 64;
             split_plan(pl, seed, plA, plB);
             if (plA.runs.size() <= 2 && plB.runs.size() <= 2 && plB.rows_scored > 0 &&
-                prune_query_bounds(queries, s->dim, c * 32, &prune_qt, &prune_qn))
+                prune_query_bounds(queries, s->dim, c * 32, &prune_qt, &prune_qn)) {
                 prune_c = c;
+                prune_q1 = prune_query_l1(queries, s->dim, c * 32);
+            }
         }
     }
     std::vector<uint32_t> preA, preB;
@@ -264,7 +276,7 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
     const size_t res_bytes = cnt_pad + (size_t)groups * KS * sizeof(ott_hit);
     char* res_dev = nullptr;
     if (fetch) {
-        if ((rc = s->h_hits.ensure(res_bytes))) return rc;
+        if ((rc = s->h_hits.ensure(res_bytes + 8))) return rc;  // (+ 8: the pruned sweep's tail counter)
         void* mapped = nullptr;
         OTT_HIP(hipHostGetDevicePointer(&mapped, s->h_hits.p, 0));
         res_dev = (char*)mapped;
@@ -300,6 +312,16 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
         // [count (u64, 64 B) | KS hits]: the seed's merged result, read by the second launch
         if ((rc = s->d_prune.ensure(64 + (size_t)KS * sizeof(ott_hit)))) return rc;
         uint64_t* seed_res = (uint64_t*)s->d_prune.p;
+        // the kernel's count of finished tails: a running total in device memory, read back with the result (host output only)
+        unsigned long long* tails_dev = nullptr;
+        if (fetch) {
+            if (!s->d_tails.p) {
+                if ((rc = s->d_tails.ensure(8))) return rc;
+                OTT_HIP(hipMemsetAsync(s->d_tails.p, 0, 8, s->stream));
+                s->tails_seen = 0;
+            }
+            tails_dev = (unsigned long long*)s->d_tails.p;
+        }
         auto part = [&](const RunPlan& sub, const std::vector<uint32_t>& pre, Cand* dst) {
             ExactParams q = p;
             q.n_runs = (uint32_t)sub.runs.size();
@@ -321,6 +343,13 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
         pb.prune_seed = seed_res;
         pb.prune_qt = prune_qt;
         pb.prune_qn = prune_qn;
+        pb.prune_tails = tails_dev;
+        if (prune_sk) {
+            pb.prune_sketch = s->d_sketch;
+            pb.sk_pitch = s->sk_pitch;
+            pb.sk_stage0 = s->sk_stage0;
+            pb.prune_q1 = prune_q1;
+        }
         if ((rc = launch_exact(s, pb, 1, E, gridB))) return rc;
     } else {
         for (uint32_t ps = 0; ps < passes; ps++) {
@@ -348,7 +377,14 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
     if (!fetch) return OTT_OK;
 
     char* hh = (char*)s->h_hits.p;
+    if (prune_c) OTT_HIP(hipMemcpyAsync(hh + res_bytes, s->d_tails.p, 8, hipMemcpyDeviceToHost, s->stream));
     OTT_HIP(hipStreamSynchronize(s->stream));
+    if (prune_c) {  // rows whose last stages were read after the checkpoint (the seed's rows are not counted: they have no checkpoint)
+        uint64_t total;
+        memcpy(&total, hh + res_bytes, 8);
+        st.rescored += total - s->tails_seen;
+        s->tails_seen = total;
+    }
     const uint64_t* counts = (const uint64_t*)hh;
     const ott_hit* hits = (const ott_hit*)(hh + cnt_pad);
     lists.assign(groups, {});

@@ -40,6 +40,9 @@ constexpr int EXACT_SMEM_DUMP = EXACT_SMEM + WAVES * DUMP_QCAP * 12;
 constexpr int PQ_CAP = 128;
 constexpr int PQ_WORDS = 10;
 constexpr int EXACT_SMEM_PRUNE = EXACT_SMEM + WAVES * PQ_CAP * PQ_WORDS * 4;  // 52 KB: two workgroups per CU
+// sketch form of the pruned sweep (SK): the sign words of a row's sketch line a lane keeps in registers — with a and rho at most
+// three 16-B loads (OTT_SKETCH_MAX_WORDS, ott_internal.h)
+constexpr int SK_MAXW = (int)OTT_SKETCH_MAX_WORDS;
 // Workgroups per CU of the persistent grid.  TWO since round 6 (8 waves per CU, 64 KB of row stages in flight per CU, 512 block lists for
 // the merge): measured against 3, 4 (rounds 2-5), 5 and 8 on every instantiation — 1M x 128 dot top-10 89.4 + 11.8 -> 86.3 + 9.7 us
 // (scoring + merge), 2M / 4M x 128 5 % / 3 % faster, 3M x 768 2 %, the 10M x 768 headline 4403 -> 4374 us, four queries per pass 4799
@@ -334,10 +337,15 @@ __device__ __forceinline__ float reduce8(const float* l, uint32_t mode) {
 // accumulators, the inverse norm, the row) go to the wave's deferred-tail queue in LDS.  The next tile starts at once; whenever
 // 64 rows wait they are finished as one dense tile — stages c .. n-1, the same loads and the same additions in the same order,
 // so the same bits — and offered to the list (the list orders by key: when a row is offered changes nothing).
-template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false>
+// SK (with PRUNE): the store keeps a tail sign sketch (ott_prune.h), so the checkpoint moves from 7/8 to 3/4 of the stages.  Each lane
+// fetches its row's line (lane = row: 64 contiguous lines) with the inverse norm, at the checkpoint forms q_t . s from the sign
+// words and the query's tail (scalar loads; one shift, one and-or and one fma per dim) and asks prune_score_bound_sketch; no prefix
+// sum of squares is kept.  The queue and the finishing of survivors are the same code.
+template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false, bool SK = false>
 __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) {
     static_assert(!I8 || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL), "the int8 sweep takes one query, cosine / dot, merged");
     static_assert(!PRUNE || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL && !I8), "the pruned sweep takes one query, cosine / dot, merged");
+    static_assert(!SK || PRUNE, "the sketch is the pruned sweep's");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -429,6 +437,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
     float* pq = smem + WAVES * STAGE_FLOATS + wave * (PQ_CAP * PQ_WORDS);  // [acc 0..7 | vinv | row] x PQ_CAP
     uint32_t* pq_row = reinterpret_cast<uint32_t*>(pq + 9 * PQ_CAP);
     uint32_t pq_head = 0, pq_n = 0;  // wave-uniform
+    uint32_t tails_done = 0;         // rows this wave finished (wave-uniform; added to p.prune_tails at the end)
     auto pq_finish = [&](uint32_t n) {  // the first n <= 64 queued rows: stages c .. n-1 as one tile, then the list
         wave_sync();
         const bool valid = (uint32_t)lane < n;
@@ -500,6 +509,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
         }
         pq_head = (pq_head + n) & (PQ_CAP - 1);
         pq_n -= n;
+        tails_done += n;
     };
 
     for (uint32_t t = gw; t < p.n_tiles; t += nw) {
@@ -526,7 +536,26 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
         // loop it was a ~2 us bubble per tile, which shows at small dims where a tile is only a few stages long)
         float vinv = 0.0f;
         if ((PRUNE || p.metric == OTT_METRIC_COSINE) && valid) vinv = p.inv[my_row];  // (PRUNE: the bound needs ||v||, dot too)
-        float vsq = 0.0f;  // PRUNE: the prefix's sum of squares
+        float vsq = 0.0f;  // PRUNE without a sketch: the prefix's sum of squares
+        // SK: the row's sketch line [a | rho | sign words], fetched now like the inverse norm (non-temporal: read once per sweep)
+        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+        uint32_t skl[2 + SK_MAXW];
+        if constexpr (SK) {
+#pragma unroll
+            for (int i = 0; i < 2 + SK_MAXW; i++) skl[i] = 0u;
+            skl[1] = 0x7F800000u;  // (rho = +inf: no bound)
+            if (valid) {
+                const v4u* sp = reinterpret_cast<const v4u*>(p.prune_sketch + my_row * (uint64_t)p.sk_pitch);
+                // (a line is sk_pitch words, 4, 8 or 12: a load past it would leave the buffer behind the store's last row)
+                const v4u l0 = __builtin_nontemporal_load(sp);
+                v4u l1 = {0u, 0u, 0u, 0u}, l2 = {0u, 0u, 0u, 0u};
+                if (p.sk_pitch > 4) l1 = __builtin_nontemporal_load(sp + 1);
+                if (p.sk_pitch > 8) l2 = __builtin_nontemporal_load(sp + 2);
+                skl[0] = l0.x; skl[1] = l0.y; skl[2] = l0.z; skl[3] = l0.w;
+                skl[4] = l1.x; skl[5] = l1.y; skl[6] = l1.z; skl[7] = l1.w;
+                skl[8] = l2.x; skl[9] = l2.y; skl[10] = l2.z; skl[11] = l2.w;
+            }
+        }
         float i8_rf = 0.0f;     // I8: the row factor s_v [x 1/||v||] x s_Q
         bool i8_forced = false; // I8: a row outside the error model
         if constexpr (I8) {
@@ -664,7 +693,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                                 acc[q][l] = __fadd_rn(acc[q][l], exact_term<MK>(qv, x[l]));
                             }
                         }
-                        if constexpr (PRUNE) {
+                        if constexpr (PRUNE && !SK) {
 #pragma unroll
                             for (int l = 0; l < 8; l++) vsq = fmaf(x[l], x[l], vsq);
                         }
@@ -698,7 +727,29 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             const uint32_t own = (uint32_t)(tk[0] >> 32);
             if (own > gate) gate = own;
             bool keep = valid;
-            if (valid && gate != 0) {
+            if constexpr (SK) {
+                if (gate != 0) {  // (wave-uniform)
+                    // D = q_t . s in f32: the sign bit of dim 32 s + b moves to bit 31 and makes +-1.0, one fma per dim (exact product)
+                    float D = 0.0f;
+#pragma unroll
+                    for (int j = 0; j < SK_MAXW; j++) {
+                        const uint32_t sj = p.sk_stage0 + (uint32_t)j;
+                        if (sj >= p.prune_stage && sj < nstages) {
+                            const uint32_t w = skl[2 + j];
+#pragma unroll
+                            for (int b = 0; b < 32; b++) {
+                                const float sg = __uint_as_float(((w << (31 - b)) & 0x80000000u) | 0x3F800000u);
+                                D = fmaf(sg, Q[sj * KC + b], D);
+                            }
+                        }
+                    }
+                    if (valid) {
+                        const float b = prune_score_bound_sketch(acc[0], vinv, __uint_as_float(skl[0]), __uint_as_float(skl[1]), D, p.prune_stage * KC,
+                                                                 p.dim, p.prune_qt, p.prune_q1, p.prune_qn, qinv[0], p.metric == OTT_METRIC_COSINE, take_max);
+                        keep = !(b == b && ord_of(b, take_max) < gate);  // (NaN: no bound, the row is finished)
+                    }
+                }
+            } else if (valid && gate != 0) {
                 const float b = prune_score_bound(acc[0], vsq, vinv, p.prune_stage * KC, p.dim, p.prune_qt, p.prune_qn, qinv[0],
                                                   p.metric == OTT_METRIC_COSINE, take_max);
                 keep = !(b == b && ord_of(b, take_max) < gate);  // (NaN: no bound, the row is finished)
@@ -769,6 +820,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
 
     if constexpr (PRUNE) {
         if (pq_n) pq_finish(pq_n);  // (< 64 left)
+        if (p.prune_tails != nullptr && tails_done != 0 && lane == 0) atomicAdd(p.prune_tails, (unsigned long long)tails_done);
     }
     if (DUMP) {
         dq_flush();
@@ -1606,9 +1658,9 @@ int exact_grid(const ott_store* s, uint32_t n_tiles) {
 }
 
 // the pruned sweep (p.prune_stage != 0): its queue takes the dynamic LDS past 48 KB
-template <int E, bool BLK>
+template <int E, bool BLK, bool SK>
 static int launch_prune(ott_store* s, const ExactParams& p, int grid) {
-    auto kern = exact_kernel<MK_DOT, 1, E, false, false, false, BLK, false, true>;
+    auto kern = exact_kernel<MK_DOT, 1, E, false, false, false, BLK, false, true, SK>;
     static std::atomic<uint64_t> attr_set{0};
     if (ott::attr_needed(attr_set, s->device)) {
         OTT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, EXACT_SMEM_PRUNE));
@@ -1623,10 +1675,11 @@ template <int MK, int NQ, int E, bool PERQ>
 static int launch_one(ott_store* s, const ExactParams& p, int grid) {
     if constexpr (MK == MK_DOT && NQ == 1 && !PERQ) {
         if (p.prune_stage != 0) {
+            const bool sk = p.prune_sketch != nullptr;  // the sketch form: the store keeps a tail sign sketch
             if constexpr (E == 1) {
-                if (p.k > 16) return launch_prune<1, true>(s, p, grid);  // (see BLK)
+                if (p.k > 16) return sk ? launch_prune<1, true, true>(s, p, grid) : launch_prune<1, true, false>(s, p, grid);  // (see BLK)
             }
-            return launch_prune<E, (E > 1)>(s, p, grid);
+            return sk ? launch_prune<E, (E > 1), true>(s, p, grid) : launch_prune<E, (E > 1), false>(s, p, grid);
         }
     }
     if (p.prune_stage != 0) return fail(OTT_ERR_INVALID, "launch_exact: the pruned sweep takes one query, cosine / dot, merged");

@@ -73,9 +73,9 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  SEVENTEEN of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  EIGHTEEN of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, exact_prune, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, exact_sketch, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
@@ -84,6 +84,10 @@ struct Options {
                                   // (1, round 2's one-wave LDS-DMA variant, is retired: 31 us against rows8's 10)
     int exact_prune = -1;         // single-query exact sweep: score a seed of the rows first, then skip the last stages of rows whose score
                                   // bound misses the seed's k-th best: -1 = automatic (stores of 2^20 rows and more), 0 = off, 1 = forced
+    int exact_sketch = -1;        // the pruned sweep's per-row tail sign sketch (one sign bit per dim of the last quarter of the
+                                  // stages, a mean magnitude and a remainder norm, ~1 % of the row bytes, made when rows are appended): -1 =
+                                  // automatic (stores of 8 stages and more, dim >= 225), 0 = never, 1 = always.  A store that keeps one
+                                  // stops rows at 3/4 of the stages instead of 7/8
     int force_fallback = 0;       // TESTS: bit mask of code paths the library otherwise takes only in rare conditions, forced on so that the
                                   // suite and the option fuzz hold them to the oracle: 1 = block lists merged by insertion (merge_kernel: the
                                   // rank merge's own fallback when a plateau overflows its buffer or there are > 4096 lists), 2 = k <= 64
@@ -194,6 +198,11 @@ struct ott_store {
 
     float* d_rows = nullptr;  // [cap * ld]
     float* d_inv = nullptr;   // [cap]
+    // tail sign sketch of the pruned exact sweep (ott_prune.h: prune_sketch_row): [cap * sk_pitch] words, made beside the inverse
+    // norms for the same rows (launch_inv_norms).  sk_n: rows [0, sk_n) hold one — the sweep uses it only when that covers the store
+    uint32_t* d_sketch = nullptr;
+    uint64_t sk_n = 0;
+    uint32_t sk_words = 0, sk_pitch = 0, sk_stage0 = 0;  // sign words per row, line pitch in words, first sketched stage
     uint8_t* d_flag = nullptr;  // [cap] 1 = row norm is inf / NaN / > 1e18 / tiny but non-zero / underflowed (always re-scored exactly by the MFMA path)
     // Batch-path image of the corpus: every row pre-split into bf16 hi + bf16 lo, per 32-k stage [32 hi | 32 lo] (the same
     // 128 B a stage of f32 takes; row pitch = dim rounded up to 32 floats).  Built lazily by the first batch query, extended
@@ -251,6 +260,8 @@ struct ott_store {
     // per-query scratch
     ott::DevBuf d_queries, d_qinv, d_rowmask, d_runs, d_prefix, d_lists, d_lists2, d_hits, d_count, d_cand, d_misc;  // d_lists2: first stage of the two-stage merge
     ott::DevBuf d_prune;     // pruned exact sweep: the seed's merged result (the gate of the second launch)
+    ott::DevBuf d_tails;     // pruned exact sweep: running count of the rows whose tails the kernel finished (u64)
+    uint64_t tails_seen = 0; // ... and what of it earlier queries have reported
     ott::DevBuf d_minpos;    // device word behind min_pos_inv
     // MFMA path scratch
     ott::DevBuf m_Q, m_qinv, m_qnorm, m_tau, m_cntA, m_cntB, m_candA, m_candB, m_over, m_out, m_outcnt, m_uncert, m_prefix;
@@ -330,7 +341,7 @@ inline uint64_t store_rows(const ott_store* s) { return s->n + s->pend.count(); 
 int store_flush(ott_store* s);
 int store_flush_locked(ott_store* s);  // the caller holds `rw` exclusively and `mu`
 // ott_store.hip: a shard takes over freshly filled buffers (rows moved between the GPUs of a multi-GPU store)
-int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint64_t n, uint64_t cap);
+int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* sketch, uint64_t n, uint64_t cap);
 
 constexpr size_t OTT_MAX_WORKERS = 15;
 ott_store* ctx_acquire(ott_store* s);  // returns s or a worker, with its `mu` held
@@ -453,12 +464,21 @@ struct ExactParams {
     // pruned sweep of a SINGLE query (exact_kernel<..., PRUNE>): at stage prune_stage (0 = off) a row whose
     // score bound (ott_prune.h) ranks strictly below the seed's k-th best is not finished.  prune_seed: the seed launch's merged
     // result block, [count (u64, 64 B) | hits]; prune_qt / prune_qn: upper bounds of ||q[prune_stage * 32:]|| and ||q||
+    // Sketch form (prune_sketch != nullptr): the store's tail sign sketch, lines of sk_pitch words whose sign words start at stage
+    // sk_stage0 <= prune_stage; prune_q1: an upper bound of the 1-norm of q[prune_stage * 32:].  prune_tails: device counter, += the
+    // rows whose tails were finished (both forms)
     uint32_t prune_stage;
+    uint32_t sk_pitch, sk_stage0;
     const uint64_t* prune_seed;
-    double prune_qt, prune_qn;
+    const uint32_t* prune_sketch;
+    unsigned long long* prune_tails;
+    double prune_qt, prune_qn, prune_q1;
     float qemb[896];  // last: the embedded query (kernel arguments are limited to 4 KB)
 };
 constexpr uint32_t OTT_QEMB_MAX = 896;
+// Sign words of a sketch line that the sketch form's kernel keeps in registers: with a and rho, three 16-B loads.  The embedded
+// query holds at most 28 stages, so a sketch of the last quarter has at most 7; a store with more takes the 7/8 form.
+constexpr uint32_t OTT_SKETCH_MAX_WORDS = 10;
 static_assert(sizeof(ExactParams) <= 4096, "kernel arguments are limited to 4 KB");
 
 int launch_exact(ott_store* s, const ExactParams& p, int nq_tile, int E, int grid);
@@ -477,7 +497,8 @@ int launch_merge(ott_store* s, const Cand* lists, uint32_t n_lists, uint32_t lis
 int launch_merge_hits(ott_store* s, const ott_hit* lists, uint32_t n_lists, uint32_t n_groups, uint32_t list_len, uint32_t k, int E,
                       bool take_max, ott_hit* out, uint64_t* count, uint32_t hdr_slots = 0, ott_hit* hdr_out = nullptr);
 
-int launch_inv_norms(ott_store* s, uint64_t first_row, uint64_t n_rows);
+int launch_inv_norms(ott_store* s, uint64_t first_row, uint64_t n_rows);  // + the tail sign sketch of the same rows where the store keeps one
+bool store_wants_sketch(const ott_store* s);
 int update_min_pos_inv(ott_store* s, uint64_t first_row, uint64_t n_rows);  // call after launch_inv_norms; syncs
 
 // surviving chunk runs of one query (candidate_chunks, src/meta.rs:648-659)

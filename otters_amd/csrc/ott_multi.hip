@@ -204,9 +204,21 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
         float* rows = nullptr;
         float* inv = nullptr;
         uint8_t* flag = nullptr;
+        uint32_t* sketch = nullptr;
         uint64_t cap = 0;
         bool changed = false;
     };
+    // the tail sign sketches move with the inverse norms — when every shard that holds rows has one for all of them (same dim, so
+    // the same line pitch everywhere); otherwise the receiving shards start without and make theirs at the next append
+    bool move_sk = true;
+    uint32_t sk_pitch = 0;
+    for (size_t g = 0; g < G; g++) {
+        const ott_store* sh = m->shards[g];
+        if (!store_rows(sh)) continue;
+        if (!sh->d_sketch || sh->sk_n < sh->n || !store_wants_sketch(sh)) move_sk = false;
+        else sk_pitch = sh->sk_pitch;
+    }
+    if (!sk_pitch) move_sk = false;
     std::vector<Fresh> fr(G);
     auto drop_fresh = [&]() {
         for (size_t g = 0; g < G; g++) {
@@ -214,6 +226,7 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
             if (fr[g].rows) (void)hipFree(fr[g].rows);
             if (fr[g].inv) (void)hipFree(fr[g].inv);
             if (fr[g].flag) (void)hipFree(fr[g].flag);
+            if (fr[g].sketch) (void)hipFree(fr[g].sketch);
         }
     };
     if (moves) {
@@ -235,6 +248,7 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
             if (e == hipSuccess) e = hipMalloc((void**)&fr[g].rows, cap * s->ld * sizeof(float));
             if (e == hipSuccess) e = hipMalloc((void**)&fr[g].inv, cap * sizeof(float));
             if (e == hipSuccess) e = hipMalloc((void**)&fr[g].flag, cap);
+            if (e == hipSuccess && move_sk) e = hipMalloc((void**)&fr[g].sketch, cap * (size_t)sk_pitch * 4);
             if (e == hipSuccess && s->ld != s->dim && cap > cnt)  // padding columns of rows still to come must be zero
                 e = hipMemsetAsync(fr[g].rows + cnt * s->ld, 0, (cap - cnt) * s->ld * sizeof(float), s->stream);
             if (e != hipSuccess) {
@@ -257,6 +271,8 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
                 hipError_t e = hipMemcpyPeerAsync(fr[g].rows + d0 * s->ld, m->devs[g], src->d_rows + s0 * src->ld, m->devs[h], cnt * s->ld * sizeof(float), s->stream);
                 if (e == hipSuccess) e = hipMemcpyPeerAsync(fr[g].inv + d0, m->devs[g], src->d_inv + s0, m->devs[h], cnt * sizeof(float), s->stream);
                 if (e == hipSuccess) e = hipMemcpyPeerAsync(fr[g].flag + d0, m->devs[g], src->d_flag + s0, m->devs[h], cnt, s->stream);
+                if (e == hipSuccess && move_sk)
+                    e = hipMemcpyPeerAsync(fr[g].sketch + d0 * sk_pitch, m->devs[g], src->d_sketch + s0 * sk_pitch, m->devs[h], cnt * (size_t)sk_pitch * 4, s->stream);
                 if (e != hipSuccess) {
                     (void)hipGetLastError();
                     for (size_t x = 0; x < G; x++) {
@@ -275,7 +291,8 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
         // phase C: the shards take the fresh buffers over (the old ones are freed)
         for (size_t g = 0; g < G; g++) {
             if (!fr[g].changed) continue;
-            const int rc = store_adopt(m->shards[g], fr[g].rows, fr[g].inv, fr[g].flag, new_r[g].hi - new_r[g].lo, fr[g].cap);
+            const int rc = store_adopt(m->shards[g], fr[g].rows, fr[g].inv, fr[g].flag, fr[g].sketch, new_r[g].hi - new_r[g].lo, fr[g].cap);
+            fr[g].sketch = nullptr;
             fr[g].rows = nullptr;
             fr[g].inv = nullptr;
             fr[g].flag = nullptr;

@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "ott_internal.h"
+#include "ott_prune.h"
 
 namespace ott {
 
@@ -28,11 +29,11 @@ struct OptName {
     const char* name;
     int kind;  // 0 = bool, 1 = tri-state (-1 automatic / 0 / 1), 2 = non-negative int
 };
-// the seventeen options of the product library (see struct Options) ...
+// the eighteen options of the product library (see struct Options) ...
 const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"hi_prebuild", 1},          {"stage_appends", 1},       {"multi_transport", 2},
                              {"multi_rebalance", 0}, {"multi_min_shard_rows", 2}, {"exact_small", 1},     {"large_k_from", 2},        {"small_sort", 1},
                              {"mfma_f32", 0},        {"no_hi_pass", 0},      {"no_batch_image", 0},       {"force_fallback", 2},      {"eps_scale_ppm", 2},
-                             {"multi_fake_distinct", 0}, {"exact_prune", 1},
+                             {"multi_fake_distinct", 0}, {"exact_prune", 1},            {"exact_sketch", 1},
 #ifdef OTT_MFMA_DEBUG_BUILD
                              // ... and, in the diagnostic build only, kernel tuning, timing ablations and every fallback bit by its own name
                              {"mfma_wg", 2},         {"mfma_growth", 2},     {"mfma_debug", 0},           {"mfma_abl", 2},            {"hi_tmin", 2},
@@ -40,11 +41,11 @@ const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"h
                              {"merge_rank1", 1},
 #endif
 };
-static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 17
+static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 18
 #ifdef OTT_MFMA_DEBUG_BUILD
                                                             + 11
 #endif
-              , "the product library's option table stays at seventeen entries");
+              , "the product library's option table stays at eighteen entries");
 }  // namespace
 
 int option_set(Options& o, const char* name, long long v) {
@@ -78,6 +79,7 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "hi_fmt") { if (v < -1 || v > 2) return -1; o.hi_fmt = (int)v; return 0; }
     if (n == "small_sort") return tri(o.small_sort);
     if (n == "exact_prune") return tri(o.exact_prune);
+    if (n == "exact_sketch") return tri(o.exact_sketch);
 #ifdef OTT_MFMA_DEBUG_BUILD
     if (n == "mfma_coop") return tri(o.mfma_coop);
     if (n == "mfma_spec") return tri(o.mfma_spec);
@@ -321,6 +323,130 @@ int update_min_pos_inv(ott_store* s, uint64_t first_row, uint64_t n_rows) {
     return OTT_OK;
 }
 
+// The pruned sweep's tail sign sketch (ott_prune.h: prune_sketch_row, the same sums in the same order).  Runs right behind
+// inv_norm_kernel for the same rows and reads their last stages only (a quarter of the row), staged as there: a wave stages 64
+// rows x 128 B per step, coalesced, then lane = row walks its 32 dims out of LDS.  A lane writes its line in 16-B pieces: the
+// groups of four sign words as they fill, [a | rho | word 0 | word 1] at the end.
+__global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restrict__ rows, uint32_t ld, uint32_t dim, uint64_t first, uint64_t n,
+                                                           uint32_t stage0, uint32_t n_words, uint32_t pitch, uint32_t* __restrict__ sketch) {
+    __shared__ __attribute__((aligned(16))) float smem[4 * 64 * NKC];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float* st = smem + wave * 64 * NKC;
+    const uint64_t n_tiles = (n + 63) / 64;
+    const int lrow = lane >> 3, lslot = lane & 7, sw = (lane >> 1) & 7;
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    for (uint64_t t = (uint64_t)blockIdx.x * 4 + wave; t < n_tiles; t += (uint64_t)gridDim.x * 4) {
+        const uint64_t row0 = first + t * 64;
+        const uint32_t cnt = (n - t * 64) < 64 ? (uint32_t)(n - t * 64) : 64u;
+        // branch-free staging as in inv_norm_kernel: rows past a short tile's end clamped to its last row, a column group past
+        // `ld` re-reads column 0; lanes past `cnt` sum a copy of the last row and write nothing
+        const float* rp[8];
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            const uint32_t row = 8 * m + lrow;
+            rp[m] = rows + (row0 + (row < cnt ? row : cnt - 1)) * (uint64_t)ld;
+        }
+        v4f R[8];
+        auto load_stage = [&](uint32_t sg) {
+            const uint32_t col = sg * NKC + lslot * 4;
+            const uint32_t c = col < ld ? col : 0u;
+#pragma unroll
+            for (int m = 0; m < 8; m++) R[m] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(rp[m] + c));
+        };
+        const bool mine = (uint32_t)lane < cnt;
+        v4u* line = reinterpret_cast<v4u*>(sketch + (row0 + (mine ? lane : 0)) * (uint64_t)pitch);
+        PruneSketchSums sums;
+        uint32_t w01[2] = {0u, 0u};          // sign words 0 and 1: they share the first 16 B with a and rho
+        v4u grp = {0u, 0u, 0u, 0u};          // the 16-B piece that is filling (line words 4 g .. 4 g + 3)
+        load_stage(stage0);
+        for (uint32_t j = 0; j < n_words; j++) {
+            const uint32_t sg = stage0 + j;
+#pragma unroll
+            for (int m = 0; m < 8; m++)
+                *reinterpret_cast<v4f*>(st + (8 * m + lrow) * NKC + ((lslot ^ (((8 * m + lrow) >> 1) & 7)) << 2)) = R[m];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (j + 1 < n_words) load_stage(sg + 1);
+            uint32_t w = 0;
+#pragma unroll
+            for (int c = 0; c < NKC / 4; c++) {
+                const v4u x = *reinterpret_cast<const v4u*>(st + lane * NKC + ((c ^ sw) << 2));
+                const uint32_t bits[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                for (int l = 0; l < 4; l++)
+                    if (sg * NKC + 4 * c + l < dim) {  // (dims past `dim` count as zero and are excluded)
+                        w |= (bits[l] >> 31) << (4 * c + l);
+                        prune_sketch_add(sums, bits[l]);
+                    }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (j < 2) {
+                w01[0] = j == 0 ? w : w01[0];
+                w01[1] = j == 1 ? w : w01[1];
+            } else {
+                const uint32_t k = j + 2, slot = k & 3;
+                grp.x = slot == 0 ? w : grp.x;
+                grp.y = slot == 1 ? w : grp.y;
+                grp.z = slot == 2 ? w : grp.z;
+                grp.w = slot == 3 ? w : grp.w;
+                if (slot == 3 || j + 1 == n_words) {  // (4 (k / 4) + 3 < pitch: the pitch is a multiple of four words)
+                    if (mine) line[k >> 2] = grp;
+                    grp = v4u{0u, 0u, 0u, 0u};
+                }
+            }
+        }
+        float a, rho;
+        prune_sketch_finish(sums, dim > stage0 * NKC ? dim - stage0 * NKC : 0u, &a, &rho);
+        if (mine) line[0] = v4u{__float_as_uint(a), __float_as_uint(rho), w01[0], w01[1]};
+    }
+}
+
+bool store_wants_sketch(const ott_store* s) {
+    const uint32_t nst = (s->ld + 31) / 32;
+    if (s->opt.exact_sketch == 0 || nst < 2 || prune_sketch_stage0(nst) < 1) return false;
+    return s->opt.exact_sketch == 1 || nst >= 8;
+}
+
+// rows [first_row, first_row + n_rows) have new values: their sketch lines, and those of every earlier row that has none yet (the
+// option was switched on, or a move between shards dropped the buffer).  A store that does not want one drops what it has.
+static int update_sketch(ott_store* s, uint64_t first_row, uint64_t n_rows) {
+    if (!store_wants_sketch(s)) {
+        if (s->d_sketch) {
+            OTT_HIP(hipStreamSynchronize(s->stream));
+            (void)hipFree(s->d_sketch);
+            s->d_sketch = nullptr;
+        }
+        s->sk_n = 0;
+        return OTT_OK;
+    }
+    const uint32_t nst = (s->ld + 31) / 32;
+    if (!s->d_sketch) {
+        s->sk_stage0 = prune_sketch_stage0(nst);
+        s->sk_words = nst - s->sk_stage0;
+        s->sk_pitch = prune_sketch_pitch(s->sk_words);
+        s->sk_n = 0;
+        const hipError_t e = hipMalloc((void**)&s->d_sketch, s->cap * (size_t)s->sk_pitch * 4);
+        if (e != hipSuccess) {  // no room: the store stays without one (the sweep then stops rows at 7/8 of the stages)
+            (void)hipGetLastError();
+            s->d_sketch = nullptr;
+            return OTT_OK;
+        }
+    }
+    const uint64_t lo = first_row < s->sk_n ? first_row : s->sk_n, hi = first_row + n_rows;
+    uint64_t blocks = ((hi - lo + 63) / 64 + 3) / 4;  // a wave per 64 rows, as launch_inv_norms
+    if (blocks > (uint64_t)s->n_cu * 8) blocks = (uint64_t)s->n_cu * 8;
+    hipLaunchKernelGGL(tail_sketch_kernel, dim3((uint32_t)blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
+                       s->sk_words, s->sk_pitch, s->d_sketch);
+    OTT_HIP(hipGetLastError());
+    if (hi > s->sk_n) s->sk_n = hi;
+    return OTT_OK;
+}
+
 int launch_inv_norms(ott_store* s, uint64_t first_row, uint64_t n_rows) {
     if (!n_rows) return OTT_OK;
     uint64_t tiles = (n_rows + 63) / 64;
@@ -330,7 +456,7 @@ int launch_inv_norms(ott_store* s, uint64_t first_row, uint64_t n_rows) {
     hipLaunchKernelGGL(inv_norm_kernel, dim3((uint32_t)blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, first_row,
                        n_rows, s->d_inv, s->d_flag);
     OTT_HIP(hipGetLastError());
-    return OTT_OK;
+    return update_sketch(s, first_row, n_rows);
 }
 
 int launch_rand_fill(ott_store* s, uint64_t first_row, uint64_t n_rows, uint64_t seed) {
@@ -349,17 +475,22 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
     float* nrows = nullptr;
     float* ninv = nullptr;
     uint8_t* nflag = nullptr;
+    uint32_t* nsk = nullptr;  // the tail sign sketch is allocated, grown and copied exactly as the inverse norms are
+    const bool keep_sk = s->d_sketch != nullptr && store_wants_sketch(s);
     hipError_t e = hipSuccess;
     for (int attempt = 0; attempt < 2; attempt++) {
         e = hipMalloc((void**)&nrows, ncap * s->ld * sizeof(float));
         if (e == hipSuccess) e = hipMalloc((void**)&ninv, ncap * sizeof(float));
         if (e == hipSuccess) e = hipMalloc((void**)&nflag, ncap);
+        if (e == hipSuccess && keep_sk) e = hipMalloc((void**)&nsk, ncap * (size_t)s->sk_pitch * 4);
         if (e == hipSuccess) break;
         if (nrows) (void)hipFree(nrows);
         if (ninv) (void)hipFree(ninv);
         if (nflag) (void)hipFree(nflag);
+        if (nsk) (void)hipFree(nsk);
         nrows = ninv = nullptr;
         nflag = nullptr;
+        nsk = nullptr;
         (void)hipGetLastError();  // reported here: the store stays as it was, and the next launch check must not see this again
         // The store's own copies of the corpus for the batch path (int8 plane, 16-bit plane, split image) are dropped by a
         // reallocation anyway: when the new buffers do not fit NEXT TO them, they go first and the allocation is tried once more
@@ -384,6 +515,10 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
         OTT_HIP(hipMemcpyAsync(nrows, s->d_rows, s->n * s->ld * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
         OTT_HIP(hipMemcpyAsync(ninv, s->d_inv, s->n * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
         OTT_HIP(hipMemcpyAsync(nflag, s->d_flag, s->n, hipMemcpyDeviceToDevice, s->stream));
+        if (nsk && s->sk_n) {
+            const uint64_t have = s->sk_n < s->n ? s->sk_n : s->n;
+            OTT_HIP(hipMemcpyAsync(nsk, s->d_sketch, have * (size_t)s->sk_pitch * 4, hipMemcpyDeviceToDevice, s->stream));
+        }
     }
     if (s->ld != s->dim)  // padding columns must be zero
         OTT_HIP(hipMemsetAsync(nrows + s->n * s->ld, 0, (ncap - s->n) * s->ld * sizeof(float), s->stream));
@@ -391,9 +526,12 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
     if (s->d_rows) (void)hipFree(s->d_rows);
     if (s->d_inv) (void)hipFree(s->d_inv);
     if (s->d_flag) (void)hipFree(s->d_flag);
+    if (s->d_sketch) (void)hipFree(s->d_sketch);
     s->d_rows = nrows;
     s->d_inv = ninv;
     s->d_flag = nflag;
+    s->d_sketch = nsk;
+    if (!nsk) s->sk_n = 0;
     s->cap = ncap;
     if (s->d_img) (void)hipFree(s->d_img);  // the batch image is rebuilt lazily at the new capacity
     s->d_img = nullptr;
@@ -412,7 +550,7 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
 // A shard of a multi-GPU store takes over buffers the relayout filled (rows [0, n) valid, capacity `cap`): the old ones are
 // freed, the 16-bit copies of the corpus are dropped (rebuilt lazily), the hi plane's per-row marks are cleared, the smallest
 // inverse norm is measured again, the evaluated row mask is forgotten.  The caller holds the multi store exclusively.
-int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint64_t n, uint64_t cap) {
+int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* sketch, uint64_t n, uint64_t cap) {
     // the shard's own lock too: its background plane builder reads the rows under it (shared) and must be out before they go
     ott::host::ExclusiveLock wr(s->rw);
     std::lock_guard<std::mutex> g(s->mu);
@@ -421,9 +559,18 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint64_t n
     if (s->d_rows) (void)hipFree(s->d_rows);
     if (s->d_inv) (void)hipFree(s->d_inv);
     if (s->d_flag) (void)hipFree(s->d_flag);
+    if (s->d_sketch) (void)hipFree(s->d_sketch);
     s->d_rows = rows;
     s->d_inv = inv;
     s->d_flag = flag;
+    s->d_sketch = sketch;  // (nullptr: the rows came without sketch lines — the next append makes them for the whole shard)
+    if (sketch) {
+        const uint32_t nst = (s->ld + 31) / 32;
+        s->sk_stage0 = prune_sketch_stage0(nst);
+        s->sk_words = nst - s->sk_stage0;
+        s->sk_pitch = prune_sketch_pitch(s->sk_words);
+    }
+    s->sk_n = sketch ? n : 0;
     s->n = n;
     s->cap = cap;
     {
@@ -537,6 +684,11 @@ static void alias_corpus(ott_store* w, const ott_store* s) {
     w->d_rows = s->d_rows;
     w->d_inv = s->d_inv;
     w->d_flag = s->d_flag;
+    w->d_sketch = s->d_sketch;
+    w->sk_n = s->sk_n;
+    w->sk_words = s->sk_words;
+    w->sk_pitch = s->sk_pitch;
+    w->sk_stage0 = s->sk_stage0;
     w->d_evalmask.p = s->d_evalmask.p;
     w->d_evalmask.cap = 0;
     w->evalmask_bits = s->evalmask_bits;
@@ -1143,12 +1295,14 @@ int ott_store_destroy(ott_store* s) {
         s->d_rows = nullptr;
         s->d_inv = nullptr;
         s->d_flag = nullptr;
+        s->d_sketch = nullptr;
         s->d_evalmask.p = nullptr;
         s->d_evalmask.cap = 0;
     }
     if (s->d_rows) (void)hipFree(s->d_rows);
     if (s->d_inv) (void)hipFree(s->d_inv);
     if (s->d_flag) (void)hipFree(s->d_flag);
+    if (s->d_sketch) (void)hipFree(s->d_sketch);
     if (s->d_img && !s->is_worker) (void)hipFree(s->d_img);
     if (s->d_imgh && !s->is_worker) (void)hipFree(s->d_imgh);
     if (s->d_imgh_rel && !s->is_worker) (void)hipFree(s->d_imgh_rel);
@@ -1158,7 +1312,7 @@ int ott_store_destroy(ott_store* s) {
         if (s->d_img8_rel) (void)hipFree(s->d_img8_rel);
     }
     for (ott::DevBuf* b : {&s->d_queries, &s->d_qinv, &s->d_rowmask, &s->d_runs, &s->d_prefix, &s->d_lists, &s->d_lists2, &s->d_hits,
-                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_evalmask, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
+                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
                            &s->m_tau, &s->m_cntA, &s->m_cntB, &s->m_candA, &s->m_candB, &s->m_over, &s->m_out, &s->m_outcnt,
                            &s->m_uncert, &s->m_prefix, &s->x_send, &s->x_recv, &s->l_keysA, &s->l_keysB, &s->l_qA, &s->l_qB, &s->l_tmp, &s->l_cursor, &s->l_hist, &s->l_gate, &s->l_ctl})
         b->release();
