@@ -158,6 +158,11 @@ extern "C" {
     pub fn ott_store_append_clustered(s: *mut ott_store, n_rows: u64, seed: u64, n_clusters: u32, spread: f32, aniso: f32) -> c_int;
     pub fn ott_store_write_rows(s: *mut ott_store, first_row: u64, rows_host: *const f32, n_rows: u64) -> c_int;
     pub fn ott_store_len(s: *const ott_store) -> u64;
+    pub fn ott_store_delete_rows(s: *mut ott_store, rows_host: *const u64, n: u64, n_changed: *mut u64) -> c_int;
+    pub fn ott_store_restore_rows(s: *mut ott_store, rows_host: *const u64, n: u64, n_changed: *mut u64) -> c_int;
+    pub fn ott_store_live_len(s: *const ott_store) -> u64;
+    pub fn ott_store_read_live_mask(s: *const ott_store, out_host: *mut u64) -> c_int;
+    pub fn ott_store_compact(s: *mut ott_store, out_new_index: *mut u64) -> c_int;
     pub fn ott_store_dim(s: *const ott_store) -> u32;
     pub fn ott_store_device(s: *const ott_store) -> c_int;
     pub fn ott_store_set_chunk_size(s: *mut ott_store, chunk_size: u64) -> c_int;

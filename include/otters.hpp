@@ -179,6 +179,19 @@ class VecStore {  // src/vec.rs:338-412
     // Pre-size the store (a multi-GPU store also plans the even split of n rows over its shards with it)
     void reserve(std::size_t n_rows) { check(ott_store_reserve(handle(), n_rows)); }
     int shard_count() const { return ott_store_shard_count(handle()); }
+    // Deleted rows (include/otters_hip.h: ott_store_delete_rows): indices stay stable, len() keeps counting every slot, no result
+    // holds a deleted row.  Both return how many rows changed state.
+    std::size_t delete_rows(const std::vector<uint64_t>& ids) {
+        uint64_t changed = 0;
+        check(ott_store_delete_rows(handle(), ids.data(), ids.size(), &changed));
+        return static_cast<std::size_t>(changed);
+    }
+    std::size_t restore_rows(const std::vector<uint64_t>& ids) {
+        uint64_t changed = 0;
+        check(ott_store_restore_rows(handle(), ids.data(), ids.size(), &changed));
+        return static_cast<std::size_t>(changed);
+    }
+    std::size_t live_len() const { return h_ ? static_cast<std::size_t>(ott_store_live_len(h_)) : n_; }
 
   private:
     std::size_t dim_;

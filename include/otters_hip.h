@@ -224,6 +224,32 @@ int ott_store_write_rows(ott_store* s, uint64_t first_row, const float* rows_hos
 uint64_t ott_store_len(const ott_store* s);  /* VecStore::len, src/vec.rs:378 */
 uint32_t ott_store_dim(const ott_store* s);
 int ott_store_device(const ott_store* s);
+/* Deleting rows (an extension: the reference's stores only grow).  A deleted row keeps its slot: row indices are stable, and
+ * ott_store_len keeps counting every slot (cap and k arithmetic do not change); ott_store_live_len counts the rest.  A deleted
+ * row is never scored into a result, on any path, mode, metric, k or tie order: a query returns exactly the hits it would
+ * return with nothing deleted and a row mask that ALSO clears the deleted rows — ANDed with the caller's own row_mask or with
+ * what ott_store_eval_row_mask left (which is not modified).  Stats fields may differ, hits may not.  The deleted set is a live
+ * mask in HBM that belongs to the store (allocated by the first delete; a store that never had one runs exactly what it ran
+ * before) and joins every query at the one place the row mask reaches the kernels; the exact kernel never reads a tile whose
+ * rows are all masked.  Appended rows are live; ott_store_write_rows on a deleted row writes the data and leaves it deleted;
+ * restore brings a row back exactly as it was (data, inverse norm and sketch line are kept while it is deleted).
+ * rows_host: n indices counted from the store's first row (like row_mask: not base_offset-shifted).  Listing a row twice, or
+ * one already in that state, is not an error: *n_changed (may be NULL) = rows whose state changed.  An index >= ott_store_len
+ * fails with OTT_ERR_INVALID before anything changes.  Both take the store exclusively, like append (staged appends go first).
+ * Multi-GPU store: routed by row range, like ott_store_write_rows. */
+int ott_store_delete_rows(ott_store* s, const uint64_t* rows_host, uint64_t n, uint64_t* n_changed);
+int ott_store_restore_rows(ott_store* s, const uint64_t* rows_host, uint64_t n, uint64_t* n_changed);
+uint64_t ott_store_live_len(const ott_store* s);
+/* (len+63)/64 words, bit = 1: live; bits past len are 0.  For tests / hosts that mirror the state. */
+int ott_store_read_live_mask(const ott_store* s, uint64_t* out_host);
+/* Physically removes the deleted rows, order preserved: len becomes live_len, and HBM behind it is free for appends again.
+ * out_new_index (may be NULL): old-len entries, the row's new index or UINT64_MAX for a removed row.  Rows, inverse norms and
+ * flags move in place through a bounded bounce buffer (no second copy of the store); sketch lines are made again (the same bits
+ * a fresh store of the surviving rows has), the cascade's planes are dropped and rebuilt on demand, the evaluated row mask is
+ * forgotten, the live mask is freed.  With nothing deleted it does nothing.  Takes the store exclusively.
+ * OTT_ERR_UNSUPPORTED on a multi-GPU store (the shards' row ranges are pinned to chunk multiples) and while metadata columns
+ * are resident (they would have to move with the rows: the restriction of ott_store_create_multi's rebalancing). */
+int ott_store_compact(ott_store* s, uint64_t* out_new_index);
 /* MetaStore chunking: chunk c = local rows [c*chunk_size, ...) (src/meta.rs:203-281).  Default 1024. */
 int ott_store_set_chunk_size(ott_store* s, uint64_t chunk_size);
 /* The certified cascade (query batches; single queries once its first plane is resident) keeps compact copies of the corpus in

@@ -607,6 +607,12 @@ class MetaStore {  // src/meta.rs:48-60, 308-577
         if (store_) store_->set_tie_order(on ? 2 : 0);
     }
 
+    // deleted rows: forwarded to the vector store, whose live mask joins every query's row mask on the device (zonemaps stay
+    // conservative, materialisation only ever sees returned rows)
+    std::size_t delete_rows(const std::vector<uint64_t>& ids) { return store_ ? store_->delete_rows(ids) : 0; }
+    std::size_t restore_rows(const std::vector<uint64_t>& ids) { return store_ ? store_->restore_rows(ids) : 0; }
+    std::size_t live_len() const { return store_ ? store_->live_len() : n_rows_; }
+
     MetaQueryPlan query(std::vector<float> q, Metric m) const;
     MetaQueryPlan query_batch(std::vector<std::vector<float>> qs, Metric m) const;
 

@@ -131,6 +131,11 @@ def lib() -> C.CDLL:
         "ott_store_append_random": (i32, [vp, u64, u64]),
         "ott_store_append_clustered": (i32, [vp, u64, u64, u32, C.c_float, C.c_float]),
         "ott_store_write_rows": (i32, [vp, u64, vp, u64]),
+        "ott_store_delete_rows": (i32, [vp, vp, u64, vp]),
+        "ott_store_restore_rows": (i32, [vp, vp, u64, vp]),
+        "ott_store_live_len": (u64, [vp]),
+        "ott_store_read_live_mask": (i32, [vp, vp]),
+        "ott_store_compact": (i32, [vp, vp]),
         "ott_store_len": (u64, [vp]),
         "ott_store_dim": (u32, [vp]),
         "ott_store_device": (i32, [vp]),

@@ -475,6 +475,9 @@ int ott::query_core(ott_store* s, const ott_query_desc* d, ott_hit* out_host, vo
         d_mask = (const uint64_t*)s->d_rowmask.p;
         mask_bits = d->row_mask_bits;
     }
+    // deleted rows (ott_tomb.hip): the store's live mask joins here — as the mask itself when the query brought none, else ANDed
+    // with it into this context's scratch.  A store without deletions has no live mask and takes neither branch.
+    if (s->n_dead && (rc = live_compose(s, &d_mask, &mask_bits))) return rc;
 
     // ---- path choice --------------------------------------------------------------------------------
     // per-query k for the batch path: the merged top-k is contained in the union of per-query top-k

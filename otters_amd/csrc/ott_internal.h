@@ -277,6 +277,15 @@ struct ott_store {
     ott::DevBuf x_send, x_recv;  // sharded queries: this shard's candidate block, the gathered blocks of all shards
     ott::DevBuf d_evalmask;  // mask built by ott_store_eval_row_mask
     uint64_t evalmask_bits = 0;
+    // Deleted rows (ott_tomb.hip): the LIVE mask, one bit per row slot, 1 = live — [(cap + 63) / 64] words,
+    // allocated by the first ott_store_delete_rows and freed again by ott_store_compact; nullptr = no row was ever deleted (and
+    // the query path is then exactly what it was).  Every bit at and past `n` is 1 in every word, so appended rows are live
+    // without a launch; a reallocation copies the words and fills the new ones with ones.  Owned by the store (workers alias
+    // it), changed only under `rw` exclusive.  n_dead: cleared bits below n.  d_livefx: THIS context's scratch for
+    // caller mask & live mask (one small kernel per query that carries a row mask of its own).
+    uint64_t* d_live = nullptr;
+    uint64_t n_dead = 0;
+    ott::DevBuf d_livefx;
     // Small appends are STAGED: rows of appends below 256 KB (VecStore::add_vector is one row per call, src/vec.rs:357-371)
     // collect in pinned host memory and go to the GPU together — when 4 MB are full, and before anything looks at the rows
     // (queries, reads, columns, other kinds of append).  A single-row append costs a memcpy instead of a copy + a kernel + a
@@ -320,6 +329,9 @@ int multi_destroy(ott_store* ms);
 int multi_reserve(ott_store* ms, uint64_t n_rows);
 int multi_append(ott_store* ms, const AppendArgs& a, uint64_t n_rows);
 int multi_write_rows(ott_store* ms, uint64_t first_row, const float* rows_host, uint64_t n_rows);
+int multi_set_live(ott_store* ms, bool live, const uint64_t* rows_host, uint64_t n, uint64_t* n_changed);  // delete (live = false) / restore
+uint64_t multi_live_len(const ott_store* ms);
+int multi_read_live_mask(const ott_store* ms, uint64_t* out_host);
 int multi_read(const ott_store* ms, bool inv_norms, uint64_t first_row, uint64_t n_rows, float* out_host);
 int multi_set_chunk_size(ott_store* ms, uint64_t chunk_size);
 int multi_set_base_offset(ott_store* ms, uint64_t base);
@@ -497,6 +509,18 @@ int launch_merge(ott_store* s, const Cand* lists, uint32_t n_lists, uint32_t lis
 int launch_merge_hits(ott_store* s, const ott_hit* lists, uint32_t n_lists, uint32_t n_groups, uint32_t list_len, uint32_t k, int E,
                       bool take_max, ott_hit* out, uint64_t* count, uint32_t hdr_slots = 0, ott_hit* hdr_out = nullptr);
 
+// ott_tomb.hip: the live mask of deleted rows.  live_grow: the rows were reallocated to ncap slots (realloc_store); live_drop: the
+// mask goes (every row counts as live again: store_adopt, compact); live_load: the mask of rows [0, s->n) from host words (a
+// multi-GPU store moves its rows between shards: the bits travel through the host); live_compose: the row mask a query's
+// kernels get — the caller's (device words or nullptr) ANDed with the live mask over s->n bits, in the context's scratch; a
+// store without deletions gets its arguments back untouched.  All but live_compose need the store exclusively.
+int live_grow(ott_store* s, uint64_t ncap);
+void live_drop(ott_store* s);
+int live_load(ott_store* s, const uint64_t* words_host);
+int live_read(const ott_store* s, uint64_t* out_host);  // (n + 63) / 64 words, bits past n zero; the caller holds the store (shared)
+int live_compose(ott_store* ctx, const uint64_t** d_mask, uint64_t* mask_bits);
+// ott_store.hip: rows [0, new_n) are what ott_store_compact left — sketch lines again, planes and evaluated mask dropped
+int store_after_compact(ott_store* s, uint64_t new_n);
 int launch_inv_norms(ott_store* s, uint64_t first_row, uint64_t n_rows);  // + the tail sign sketch of the same rows where the store keeps one
 bool store_wants_sketch(const ott_store* s);
 int update_min_pos_inv(ott_store* s, uint64_t first_row, uint64_t n_rows);  // call after launch_inv_norms; syncs

@@ -173,6 +173,8 @@ bool layout_aligned(const ott_store* ms, uint64_t granule) {
     return true;
 }
 
+void slice_bits_any(const uint64_t* words, uint64_t first, uint64_t count, std::vector<uint64_t>& out);  // below
+
 // Moves rows so that shard g holds [target[g], min(target[g + 1], n)).  Every shard whose range changes gets fresh buffers on
 // its device (transiently old + new: when that does not fit, nothing has moved and OTT_ERR_OOM is returned), filled by peer
 // copies from the old buffers of whichever shards hold its rows.  The caller holds the store exclusively.
@@ -219,6 +221,26 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
         else sk_pitch = sh->sk_pitch;
     }
     if (!sk_pitch) move_sk = false;
+    // deleted rows: the live bits of rows that move travel through the host — read from every shard now, loaded into the shards
+    // that took fresh buffers once they have adopted them (a relayout is a rare, heavy step: 1.25 MB per 10M rows does not show)
+    std::vector<uint64_t> live_all;
+    if (moves) {
+        bool any_dead = false;
+        for (const ott_store* sh : m->shards) any_dead = any_dead || sh->n_dead;
+        if (any_dead) {
+            live_all.assign((size_t)((n + 63) / 64) + 1, 0);
+            std::vector<uint64_t> part;
+            for (size_t g = 0; g < G; g++) {
+                const ott_store* sh = m->shards[g];
+                if (!sh->n) continue;
+                part.assign((size_t)((sh->n + 63) / 64), 0);
+                const int rcl = live_read(sh, part.data());
+                if (rcl) return rcl;
+                for (uint64_t i = 0; i < sh->n; i++)
+                    if ((part[(size_t)(i >> 6)] >> (i & 63)) & 1) live_all[(size_t)((old_r[g].lo + i) >> 6)] |= 1ull << ((old_r[g].lo + i) & 63);
+            }
+        }
+    }
     std::vector<Fresh> fr(G);
     auto drop_fresh = [&]() {
         for (size_t g = 0; g < G; g++) {
@@ -297,6 +319,13 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
             fr[g].inv = nullptr;
             fr[g].flag = nullptr;
             if (rc) return rc;
+            if (!live_all.empty() && new_r[g].hi > new_r[g].lo) {
+                std::vector<uint64_t> part;
+                slice_bits_any(live_all.data(), new_r[g].lo, new_r[g].hi - new_r[g].lo, part);
+                OTT_HIP(use_device(m->shards[g]));
+                const int rcl = live_load(m->shards[g], part.data());
+                if (rcl) return rcl;
+            }
         }
     }
     m->start = target;
@@ -923,6 +952,72 @@ int multi_write_rows(ott_store* ms, uint64_t first_row, const float* rows_host, 
     for (const Piece& pc : pieces_of(ms, first_row, n_rows)) {
         const int rc = ott_store_write_rows(ms->multi->shards[pc.g], pc.first_local, rows_host + (pc.first_global - first_row) * ms->dim, pc.count);
         if (rc) return rc;
+    }
+    return OTT_OK;
+}
+
+// delete / restore: the indices are cut by row range into every shard's own (counted from its first row), and each shard
+// changes the live mask of its rows (ott_tomb.hip).  Checked against the whole store's length before any shard is touched.
+int multi_set_live(ott_store* ms, bool live, const uint64_t* rows_host, uint64_t n, uint64_t* n_changed) {
+    ott::host::ExclusiveLock wr(ms->rw);
+    ott_multi* m = ms->multi;
+    const size_t G = m->shards.size();
+    const char* who = live ? "ott_store_restore_rows" : "ott_store_delete_rows";
+    for (uint64_t i = 0; i < n; i++)
+        if (rows_host[i] >= ms->n)
+            return fail(OTT_ERR_INVALID, std::string(who) + ": row " + std::to_string(rows_host[i]) + " is out of range (the store holds " +
+                                             std::to_string(ms->n) + " rows)");
+    std::vector<std::vector<uint64_t>> local(G);
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t r = rows_host[i];
+        for (size_t g = 0; g < G; g++) {
+            const uint64_t s0 = start_of(ms, g), n_g = store_rows(m->shards[g]);
+            if (n_g && r >= s0 && r < s0 + n_g) {
+                local[g].push_back(r - s0);
+                break;
+            }
+        }
+    }
+    uint64_t total = 0;
+    int rc = OTT_OK;
+    for (size_t g = 0; g < G && !rc; g++) {
+        if (local[g].empty()) continue;
+        uint64_t ch = 0;
+        rc = live ? ott_store_restore_rows(m->shards[g], local[g].data(), local[g].size(), &ch)
+                  : ott_store_delete_rows(m->shards[g], local[g].data(), local[g].size(), &ch);
+        total += ch;
+    }
+    if (n_changed) *n_changed = total;
+    return rc;
+}
+
+uint64_t multi_live_len(const ott_store* ms) {
+    uint64_t live = 0;
+    for (const ott_store* s : ms->multi->shards) live += ott_store_live_len(s);
+    return live;
+}
+
+int multi_read_live_mask(const ott_store* cms, uint64_t* out_host) {
+    ott_store* ms = const_cast<ott_store*>(cms);
+    ott::host::SharedLock rd;
+    const int rcl = lock_clean(ms, rd);
+    if (rcl) return rcl;
+    const uint64_t words = (ms->n + 63) / 64;
+    for (uint64_t w = 0; w < words; w++) out_host[w] = 0;
+    std::vector<uint64_t> part;
+    for (size_t g = 0; g < ms->multi->shards.size(); g++) {
+        const ott_store* s = ms->multi->shards[g];
+        if (!s->n) continue;
+        part.assign((size_t)((s->n + 63) / 64), 0);
+        const int rc = live_read(s, part.data());
+        if (rc) return rc;
+        const uint64_t s0 = start_of(ms, g);
+        if ((s0 & 63) == 0) {  // (shards start on multiples of lcm(chunk size, 8) rows: usually whole words)
+            for (size_t w = 0; w < part.size(); w++) out_host[(size_t)(s0 >> 6) + w] |= part[w];
+        } else {
+            for (uint64_t i = 0; i < s->n; i++)
+                if ((part[(size_t)(i >> 6)] >> (i & 63)) & 1) out_host[(size_t)((s0 + i) >> 6)] |= 1ull << ((s0 + i) & 63);
+        }
     }
     return OTT_OK;
 }

@@ -472,6 +472,10 @@ __global__ void clear_flag_bit_kernel(uint8_t* flag, uint64_t n, uint8_t mask); 
 // (re)allocate rows / inv_norms / row flags for `ncap` rows, keeping the first s->n rows
 static int realloc_store(ott_store* s, uint64_t ncap) {
     if (ncap > 0xFFFFFFF0ull) return fail(OTT_ERR_UNSUPPORTED, "a store holds at most 2^32-16 rows per GPU");
+    {
+        const int rcl = live_grow(s, ncap);  // the live mask of deleted rows (ott_tomb.hip) is sized with the row capacity
+        if (rcl) return rcl;
+    }
     float* nrows = nullptr;
     float* ninv = nullptr;
     uint8_t* nflag = nullptr;
@@ -560,6 +564,7 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
     if (s->d_inv) (void)hipFree(s->d_inv);
     if (s->d_flag) (void)hipFree(s->d_flag);
     if (s->d_sketch) (void)hipFree(s->d_sketch);
+    live_drop(s);  // (the rows are other rows now: whoever moved them loads their live bits afterwards, live_load)
     s->d_rows = rows;
     s->d_inv = inv;
     s->d_flag = flag;
@@ -594,6 +599,41 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
     hipLaunchKernelGGL(clear_flag_bit_kernel, dim3(grid), dim3(256), 0, s->stream, s->d_flag, n, (uint8_t)0xF9);  // the planes' marks (bits 1, 2)
     OTT_HIP(hipGetLastError());
     const int rc = update_min_pos_inv(s, 0, n);
+    kick_plane_build(s);
+    return rc;
+}
+
+// ott_store_compact (ott_tomb.hip) moved the surviving rows, their inverse norms and flag bytes to the front: the store is
+// `new_n` rows long now.  What is derived from the rows follows: sketch lines are made again by the ingest kernel (deterministic
+// per row: the bits a fresh store of these rows has), the cascade's planes are dropped as by a reallocation and rebuilt on
+// demand, their marks in the flag bytes cleared, the smallest inverse norm measured again, the evaluated row mask forgotten.
+// The caller holds the store exclusively and `mu`.
+int store_after_compact(ott_store* s, uint64_t new_n) {
+    s->n = new_n;
+    {
+        std::lock_guard<std::mutex> g(s->img_mu);
+        if (s->d_img) (void)hipFree(s->d_img);
+        s->d_img = nullptr;
+        s->img_rows = s->img_cap = 0;
+        if (s->d_imgh) (void)hipFree(s->d_imgh);
+        s->d_imgh = nullptr;
+        s->imgh_rows = 0;
+        if (s->d_img8) (void)hipFree(s->d_img8);
+        if (s->d_img8_scale) (void)hipFree(s->d_img8_scale);
+        s->d_img8 = nullptr;
+        s->d_img8_scale = nullptr;
+        s->img8_rows = 0;
+    }
+    s->evalmask_bits = 0;
+    s->sk_n = 0;
+    s->min_pos_inv = __builtin_inff();
+    if (!new_n) return OTT_OK;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((new_n + 255) / 256, (uint64_t)s->n_cu * 8);
+    hipLaunchKernelGGL(clear_flag_bit_kernel, dim3(grid), dim3(256), 0, s->stream, s->d_flag, new_n, (uint8_t)0xF9);  // the planes' marks (bits 1, 2)
+    OTT_HIP(hipGetLastError());
+    int rc = update_sketch(s, 0, new_n);
+    if (rc) return rc;
+    rc = update_min_pos_inv(s, 0, new_n);
     kick_plane_build(s);
     return rc;
 }
@@ -692,6 +732,8 @@ static void alias_corpus(ott_store* w, const ott_store* s) {
     w->d_evalmask.p = s->d_evalmask.p;
     w->d_evalmask.cap = 0;
     w->evalmask_bits = s->evalmask_bits;
+    w->d_live = s->d_live;
+    w->n_dead = s->n_dead;
 }
 
 // rows [first, first + n) -> batch image: one thread per (row, 4 floats)
@@ -1298,7 +1340,9 @@ int ott_store_destroy(ott_store* s) {
         s->d_sketch = nullptr;
         s->d_evalmask.p = nullptr;
         s->d_evalmask.cap = 0;
+        s->d_live = nullptr;
     }
+    if (s->d_live) (void)hipFree(s->d_live);
     if (s->d_rows) (void)hipFree(s->d_rows);
     if (s->d_inv) (void)hipFree(s->d_inv);
     if (s->d_flag) (void)hipFree(s->d_flag);
@@ -1312,7 +1356,7 @@ int ott_store_destroy(ott_store* s) {
         if (s->d_img8_rel) (void)hipFree(s->d_img8_rel);
     }
     for (ott::DevBuf* b : {&s->d_queries, &s->d_qinv, &s->d_rowmask, &s->d_runs, &s->d_prefix, &s->d_lists, &s->d_lists2, &s->d_hits,
-                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
+                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
                            &s->m_tau, &s->m_cntA, &s->m_cntB, &s->m_candA, &s->m_candB, &s->m_over, &s->m_out, &s->m_outcnt,
                            &s->m_uncert, &s->m_prefix, &s->x_send, &s->x_recv, &s->l_keysA, &s->l_keysB, &s->l_qA, &s->l_qB, &s->l_tmp, &s->l_cursor, &s->l_hist, &s->l_gate, &s->l_ctl})
         b->release();

@@ -427,6 +427,17 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
         if self._store is not None:
             self._store.set_tie_order({"canonical": "canonical", "reference": "reference_chunked"}[order])
 
+    # deleted rows: the vector store's live mask joins every query's row mask on the device (VecStore.delete_rows); zonemaps
+    # stay conservative and materialisation only ever sees returned rows, so nothing else changes here
+    def delete_rows(self, ids) -> int:
+        return self._store.delete_rows(ids) if self._store is not None else 0
+
+    def restore_rows(self, ids) -> int:
+        return self._store.restore_rows(ids) if self._store is not None else 0
+
+    def live_len(self) -> int:
+        return self._store.live_len() if self._store is not None else self._n_rows
+
     def last_query_stats(self) -> Optional[MetaQueryStats]:
         return self._last_stats
 

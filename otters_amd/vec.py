@@ -359,6 +359,45 @@ class VecStore:
         rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, self.dim)
         N.check(N.lib().ott_store_write_rows(self._handle(), int(first_row), N.ptr(rows), rows.shape[0]))
 
+    # -- deleted rows (include/otters_hip.h: ott_store_delete_rows) ------------------------------------
+    def _set_live(self, fn, ids) -> int:
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).ravel())
+        if ids.size and int(ids.min()) < 0:
+            raise OttersError(f"row {int(ids.min())} is out of range (the store holds {self._n} rows)")
+        ids = ids.astype(np.uint64)
+        changed = C.c_uint64(0)
+        N.check(fn(self._handle(), N.ptr(ids), ids.size, C.byref(changed)))
+        return int(changed.value)
+
+    def delete_rows(self, ids) -> int:
+        """Rows `ids` (counted from the store's first row) no longer appear in any result; indices stay stable and `len()`
+        keeps counting them.  Returns how many rows changed state (duplicates and repeats are not errors)."""
+        return self._set_live(N.lib().ott_store_delete_rows, ids)
+
+    def restore_rows(self, ids) -> int:
+        """Brings deleted rows back exactly as they were.  Returns how many rows changed state."""
+        return self._set_live(N.lib().ott_store_restore_rows, ids)
+
+    def live_len(self) -> int:
+        """`len()` minus the deleted rows."""
+        return int(N.lib().ott_store_live_len(self._handle())) if self._h is not None else self._n
+
+    def live_mask(self) -> np.ndarray:
+        """bool[len()]: True = live."""
+        if self._n == 0:
+            return np.zeros(0, dtype=bool)
+        words = np.zeros((self._n + 63) // 64, dtype="<u8")
+        N.check(N.lib().ott_store_read_live_mask(self._handle(), N.ptr(words)))
+        return N.unpack_bits(words, self._n)
+
+    def compact(self) -> np.ndarray:
+        """Physically removes the deleted rows (order preserved): `len()` becomes `live_len()`.  Returns int64[old len]:
+        every row's new index, -1 for a removed row.  Not on a multi-GPU store, nor while metadata columns are resident."""
+        new_index = np.empty(self._n, dtype="<u8")
+        N.check(N.lib().ott_store_compact(self._handle(), N.ptr(new_index)))
+        self._n = int(N.lib().ott_store_len(self._handle()))
+        return new_index.view(np.int64)  # (UINT64_MAX reads as -1)
+
     def shards(self):
         """[(device, first_row, n_rows)] of the store's shards (one entry for a single-GPU store)."""
         h = self._handle()
