@@ -272,7 +272,7 @@ int ott_store_batch_ready(const ott_store* s);
 
 /* Behaviour switches of one store.  The library reads the environment exactly once per store, in ott_store_create
  * (OTT_<NAME>=<int> presets the option of the same name); after that only this call changes them — the query path never calls
- * getenv.  Eighteen options (round 5 retired the rest: experiment switches whose measurements are in DESIGN.md 3.4 and profiles/dead_ends_rounds_2_4.md).
+ * getenv.  Nineteen options (round 5 retired the rest: experiment switches whose measurements are in DESIGN.md 3.4 and profiles/dead_ends_rounds_2_4.md).
  * Behaviour a host may want:
  *   "tie_order"  0 (default): canonical total order — better score, lower row, lower query.  1: the reference's own outcome at
  *                exact score ties, ONE TopKCollector over the store (VecStore, src/vec.rs:217-310, src/vec_compute.rs:236-277).
@@ -296,6 +296,8 @@ int ott_store_batch_ready(const ott_store* s);
  *   what the two leave out; 32 B per row at dim 768, computed behind the inverse norms on every append — and the sweep then
  *   stops a row after three quarters of its dims instead of seven eighths.  Set it before rows are appended: switched on later,
  *   the sketch is made at the next append; a store without one takes the 7/8 form),
+ *   "id_gather" (-1 auto: lists of up to 10000 ids / 0 never / 1 wherever eligible: whether ott_query_ids scores the listed rows with the gather kernel or
+ *   turns the list into a row mask and takes ott_query's paths),
  *   "large_k_from" (k above which host-output queries take the sort path; 0 = default: 512 for one query or a small store,
  *   128 for several queries on a large one), "small_sort" (0: results of up to 16384 (row, query) pairs with k > 512 through
  *   the radix sort instead of the rank sort), "mfma_f32" (batch path: one candidate pass on the f32 matrix pipe),
@@ -344,6 +346,28 @@ int ott_store_eval_row_mask(ott_store* s, const ott_leaf* leaves, uint32_t n_lea
  * query, each group best first, *n_out = total, per-query counts in n_per_query if non-NULL). */
 int ott_query(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64_t cap, uint64_t* n_out,
               uint64_t* n_per_query, ott_stats* stats);
+
+/* Candidate id lists (an extension; FAISS has IDSelectorArray, Qdrant has_id): rank only the listed rows.  ids: n_ids row indices
+ * counted from the store's first row (like row_mask and ott_store_delete_rows: not base_offset-shifted), in any order, duplicates
+ * allowed.  The query returns exactly the hits — index, score bits, order, per-query counts — that ott_query returns with a row
+ * mask that keeps only the listed rows, ANDed with the caller's row_mask or the evaluated device mask, with the live mask of
+ * deleted rows and with chunk_mask: every metric, mode, take, filter, k and tie order.  Stats fields may differ, hits may not.
+ * cap need only be min(k, n_unique * nq) (MERGED) or nq * min(k, n_unique) (PER_QUERY).  An id >= ott_store_len, or ids == NULL
+ * with n_ids > 0, fails with OTT_ERR_INVALID before any device work; n_ids == 0 is a valid query with no hits.
+ * The work follows the list, not the store: a gather kernel scores the listed rows (eight lanes per row, the reference's summation
+ * order) where it is eligible — canonical tie order, k <= 128, at most 65536 distinct ids, at most 16 queries of at most 2048
+ * floats, path AUTO or EXACT, a single-GPU store; stats: path_used = EXACT, vectors_compared = listed rows after unique, chunk mask
+ * and row mask (x nq), bytes_scanned = their bytes per pass.  Everything else turns the list into a row mask on the device (a
+ * multi-GPU store: on the host) and runs ott_query's own paths with it.  Option "id_gather" chooses.  Takes the store shared,
+ * like ott_query (staged appends go first). */
+int ott_query_ids(ott_store* s, const ott_query_desc* d, const uint64_t* ids, uint64_t n_ids, ott_hit* out, uint64_t cap,
+                  uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats);
+/* Raw scores of given rows: out_scores[q * n_ids + i] = the f32 score of query q against row ids[i] — the exact path's and the
+ * oracle's bits, entries in the list's order, duplicates allowed, no filter, no top-k, a NaN score returned as NaN.  It reads stored
+ * data, as ott_store_read_rows does: a DELETED row's score is returned like any other.  Any number of ids (launches of 65536);
+ * rows of at most 2048 floats.  Errors as ott_query_ids.  Takes the store shared. */
+int ott_store_score_rows(ott_store* s, const float* queries, uint32_t nq, uint32_t metric, const uint64_t* ids, uint64_t n_ids,
+                         float* out_scores);
 
 /* Same, but the result stays on the GPU: out_dev holds `cap` ott_hit slots in device memory
  * of the store's GPU, padded with sentinel hits (index = UINT64_MAX); *n_out_dev (device

@@ -151,6 +151,8 @@ def lib() -> C.CDLL:
         "ott_store_eval_row_mask": (i32, [vp, vp, u32, u32, vp]),
         "ott_store_zone_stats": (i32, [vp, u32, u64, vp, vp, vp]),
         "ott_query": (i32, [vp, vp, vp, u64, vp, vp, vp]),
+        "ott_query_ids": (i32, [vp, vp, vp, u64, vp, u64, vp, vp, vp]),
+        "ott_store_score_rows": (i32, [vp, vp, u32, u32, vp, u64, vp]),
         "ott_query_device": (i32, [vp, vp, vp, u64, vp, vp]),
         "ott_store_sync": (i32, [vp]),
         "ott_store_stream": (vp, [vp]),

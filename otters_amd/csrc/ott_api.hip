@@ -397,6 +397,42 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
 
 }  // namespace
 
+// The row mask a query's kernels get, on the context's stream: the caller's host mask (uploaded) or the evaluated device mask,
+// ANDed with the mask of an id list that takes the mask route (ott_gather.hip: cur_idmask) and with the live mask of deleted
+// rows (ott_tomb.hip).  A query that brings none of them gets nullptr and takes neither branch.
+int ott::compose_row_mask(ott_store* s, const ott_query_desc* d, const uint64_t** d_mask_out, uint64_t* mask_bits_out) {
+    int rc;
+    const uint64_t* d_mask = nullptr;
+    uint64_t mask_bits = 0;
+    if (d->use_device_row_mask) {
+        d_mask = (const uint64_t*)s->d_evalmask.p;
+        mask_bits = s->evalmask_bits;
+    } else if (d->row_mask && d->row_mask_bits) {
+        const size_t words = (size_t)((d->row_mask_bits + 63) / 64);
+        if ((rc = s->d_rowmask.ensure(words * 8))) return rc;
+        OTT_HIP(hipMemcpyAsync(s->d_rowmask.p, d->row_mask, words * 8, hipMemcpyHostToDevice, s->stream));
+        d_mask = (const uint64_t*)s->d_rowmask.p;
+        mask_bits = d->row_mask_bits;
+    }
+    // an id list on the mask route: its bits over the store's rows, ANDed with the caller's mask into the words behind them
+    if (s->cur_idmask) {
+        if (d_mask) {
+            uint64_t* both = s->cur_idmask + (s->n + 63) / 64;
+            if ((rc = mask_and(s, s->cur_idmask, d_mask, mask_bits, s->n, both))) return rc;
+            d_mask = both;
+        } else {
+            d_mask = s->cur_idmask;
+        }
+        mask_bits = s->n;
+    }
+    // deleted rows (ott_tomb.hip): the store's live mask joins here — as the mask itself when the query brought none, else ANDed
+    // with it into this context's scratch.  A store without deletions has no live mask and takes neither branch.
+    if (s->n_dead && (rc = live_compose(s, &d_mask, &mask_bits))) return rc;
+    *d_mask_out = d_mask;
+    *mask_bits_out = mask_bits;
+    return OTT_OK;
+}
+
 // runs on a query context `s` (the store itself or one of its workers) whose `mu` the caller holds
 int ott::query_on(ott_store* s, const ott_query_desc* d, ott_hit* out_host, void* out_dev, uint64_t cap, uint64_t* n_out,
                   uint64_t* n_per_query, void* n_out_dev, ott_stats* stats_out, bool nosync, bool* events_pending) {
@@ -462,22 +498,10 @@ int ott::query_core(ott_store* s, const ott_query_desc* d, ott_hit* out_host, vo
         return OTT_OK;
     }
 
-    // row mask -> device
+    // row mask -> device: the ONE place every mask joins (the caller's or the evaluated one, an id list's, the live mask)
     const uint64_t* d_mask = nullptr;
     uint64_t mask_bits = 0;
-    if (d->use_device_row_mask) {
-        d_mask = (const uint64_t*)s->d_evalmask.p;
-        mask_bits = s->evalmask_bits;
-    } else if (d->row_mask && d->row_mask_bits) {
-        const size_t words = (size_t)((d->row_mask_bits + 63) / 64);
-        if ((rc = s->d_rowmask.ensure(words * 8))) return rc;
-        OTT_HIP(hipMemcpyAsync(s->d_rowmask.p, d->row_mask, words * 8, hipMemcpyHostToDevice, s->stream));
-        d_mask = (const uint64_t*)s->d_rowmask.p;
-        mask_bits = d->row_mask_bits;
-    }
-    // deleted rows (ott_tomb.hip): the store's live mask joins here — as the mask itself when the query brought none, else ANDed
-    // with it into this context's scratch.  A store without deletions has no live mask and takes neither branch.
-    if (s->n_dead && (rc = live_compose(s, &d_mask, &mask_bits))) return rc;
+    if ((rc = compose_row_mask(s, d, &d_mask, &mask_bits))) return rc;
 
     // ---- path choice --------------------------------------------------------------------------------
     // per-query k for the batch path: the merged top-k is contained in the union of per-query top-k

@@ -73,9 +73,9 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  EIGHTEEN of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  NINETEEN of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, exact_prune, exact_sketch, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, exact_sketch, id_gather, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
@@ -135,6 +135,8 @@ struct Options {
                                   // store counts as a device of its own although the ordinals repeat — the exchange, the row moves and
                                   // device appends then take the code paths of distinct GPUs (send buffer + hipMemcpyPeerAsync + event
                                   // wait, or the grouped all-gather) on a one-GPU box.  Results never depend on it.
+    int id_gather = -1;           // candidate id lists (ott_query_ids): -1 = automatic, 0 = never (the list becomes a row mask and
+                                  // takes the mask's paths), 1 = the gather kernel wherever it is eligible
     int multi_min_shard_rows = 32768;  // multi-GPU store: a shard is only brought in for this many rows (a store of fewer than twice as many stays
                                   // on its first GPU and is answered by that shard alone: the fan-out over N GPUs costs 50-150 us per query,
                                   // more than a small store's whole query); 0 = always split evenly over all shards
@@ -286,6 +288,12 @@ struct ott_store {
     uint64_t* d_live = nullptr;
     uint64_t n_dead = 0;
     ott::DevBuf d_livefx;
+    // Candidate id lists (ott_gather.hip), THIS context's scratch.  d_idmask: the list as a row mask when a query
+    // takes the mask route — [its bits over the store's rows | those & the caller's mask | the ids]; cur_idmask points at it for
+    // the duration of that query (compose_row_mask reads it, like cur_tie_sh).  d_gather: [rows the gather kernel scored (u64,
+    // 64 B) | raw scores of ott_store_score_rows]
+    ott::DevBuf d_idmask, d_gather;
+    uint64_t* cur_idmask = nullptr;
     // Small appends are STAGED: rows of appends below 256 KB (VecStore::add_vector is one row per call, src/vec.rs:357-371)
     // collect in pinned host memory and go to the GPU together — when 4 MB are full, and before anything looks at the rows
     // (queries, reads, columns, other kinds of append).  A single-row append costs a memcpy instead of a copy + a kernel + a
@@ -519,6 +527,8 @@ void live_drop(ott_store* s);
 int live_load(ott_store* s, const uint64_t* words_host);
 int live_read(const ott_store* s, uint64_t* out_host);  // (n + 63) / 64 words, bits past n zero; the caller holds the store (shared)
 int live_compose(ott_store* ctx, const uint64_t** d_mask, uint64_t* mask_bits);
+// out[w] = keep[w] & caller[w] over the words of n_bits rows, on the context's stream; caller bits at and past caller_bits count as keep
+int mask_and(ott_store* ctx, const uint64_t* keep, const uint64_t* caller, uint64_t caller_bits, uint64_t n_bits, uint64_t* out);
 // ott_store.hip: rows [0, new_n) are what ott_store_compact left — sketch lines again, planes and evaluated mask dropped
 int store_after_compact(ott_store* s, uint64_t new_n);
 int launch_inv_norms(ott_store* s, uint64_t first_row, uint64_t n_rows);  // + the tail sign sketch of the same rows where the store keeps one
@@ -627,6 +637,12 @@ struct CoreOpts {
 inline uint64_t tie_base(const ott_store* s) { return s->base_offset - s->cur_tie_off; }
 int query_core(ott_store* s, const ott_query_desc* d, ott_hit* out_host, void* out_dev, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query,
                void* n_out_dev, ott_stats* stats_out, bool nosync, bool* events_pending, const CoreOpts& co);
+// ott_api.hip: the row mask the kernels of a query get (caller's or evaluated mask & id list on the mask route & live mask), nullptr = none
+int compose_row_mask(ott_store* s, const ott_query_desc* d, const uint64_t** d_mask, uint64_t* mask_bits);
+// ott_multi.hip: candidate id lists on a multi-GPU store (ott_gather.hip).  ids: ascending, duplicate-free, every id < the store's length
+int multi_query_ids(ott_store* ms, const ott_query_desc* d, const std::vector<uint64_t>& ids, ott_hit* out, uint64_t cap, uint64_t* n_out,
+                    uint64_t* n_per_query, ott_stats* stats);
+int multi_score_rows(ott_store* ms, const float* queries, uint32_t nq, uint32_t metric, const uint64_t* ids, uint64_t n_ids, float* out_scores);
 // ott_ties.hip is written against this: where the candidate lists of a store come from.  `run`: one plain query over what `d`
 // selects with take count k, candidates ranked (score, visit order: tie_sh = 3), `flat` = every passing score ranks the same
 // (EXACT path); host vectors, PER_QUERY lists concatenated in query order with their counts in `per`.  `run_chunk`: the same

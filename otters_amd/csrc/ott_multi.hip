@@ -1276,6 +1276,71 @@ int multi_query(ott_store* ms, const ott_query_desc* d, ott_hit* out, uint64_t c
     return OTT_OK;
 }
 
+// Candidate id lists on a multi-GPU store (ott_gather.hip): the list becomes a HOST row mask over the store's rows — its bits
+// ANDed with the caller's mask (host words, or what ott_store_eval_row_mask left on every shard, read back) — and the query is
+// multi_query with it: the ids are few, and the shards slice the mask like any other.
+int multi_query_ids(ott_store* ms, const ott_query_desc* d, const std::vector<uint64_t>& ids, ott_hit* out, uint64_t cap, uint64_t* n_out,
+                    uint64_t* n_per_query, ott_stats* stats) {
+    ott_multi* m = ms->multi;
+    std::vector<uint64_t> mask;
+    {
+        ott::host::SharedLock rd;
+        int rc = lock_clean(ms, rd);
+        if (rc) return rc;
+        mask.assign((size_t)((ms->n + 63) / 64) + 1, 0);
+        std::vector<std::vector<uint64_t>> ev(m->shards.size());  // the shards' evaluated masks (use_device_row_mask)
+        if (d->use_device_row_mask)
+            for (size_t g = 0; g < m->shards.size(); g++) {
+                const ott_store* sh = m->shards[g];
+                if (!sh->evalmask_bits) continue;
+                ev[g].resize((size_t)((sh->evalmask_bits + 63) / 64));
+                OTT_HIP(use_device(sh));
+                OTT_HIP(hipMemcpy(ev[g].data(), sh->d_evalmask.p, ev[g].size() * 8, hipMemcpyDeviceToHost));
+            }
+        size_t g = 0;
+        for (const uint64_t r : ids) {  // ascending
+            while (g + 1 < m->shards.size() && r >= start_of(ms, g + 1)) g++;
+            bool keep = true;
+            if (d->use_device_row_mask) {
+                const uint64_t l = r - start_of(ms, g);
+                if (l < m->shards[g]->evalmask_bits) keep = (ev[g][(size_t)(l >> 6)] >> (l & 63)) & 1;
+            } else if (d->row_mask && r < d->row_mask_bits) {  // rows at and beyond row_mask_bits are kept (src/vec.rs:234)
+                keep = (d->row_mask[r >> 6] >> (r & 63)) & 1;
+            }
+            if (keep) mask[(size_t)(r >> 6)] |= 1ull << (r & 63);
+        }
+    }
+    ott_query_desc d2 = *d;
+    d2.use_device_row_mask = 0;
+    d2.row_mask = mask.data();
+    d2.row_mask_bits = ms->n;
+    return multi_query(ms, &d2, out, cap, n_out, n_per_query, stats);
+}
+
+// ott_store_score_rows, routed by row range: every shard scores the listed rows it holds
+int multi_score_rows(ott_store* ms, const float* queries, uint32_t nq, uint32_t metric, const uint64_t* ids, uint64_t n_ids, float* out_scores) {
+    ott_multi* m = ms->multi;
+    ott::host::SharedLock rd;
+    int rc = lock_clean(ms, rd);
+    if (rc) return rc;
+    for (size_t g = 0; g < m->shards.size(); g++) {
+        ott_store* sh = m->shards[g];
+        const uint64_t s0 = start_of(ms, g), n_g = store_rows(sh);
+        std::vector<uint64_t> local, at;
+        for (uint64_t i = 0; i < n_ids; i++)
+            if (ids[i] >= s0 && ids[i] - s0 < n_g) {
+                local.push_back(ids[i] - s0);
+                at.push_back(i);
+            }
+        if (local.empty()) continue;
+        std::vector<float> part((size_t)nq * local.size());
+        if ((rc = ott_store_score_rows(sh, queries, nq, metric, local.data(), local.size(), part.data()))) return rc;
+        for (uint32_t q = 0; q < nq; q++)
+            for (size_t i = 0; i < local.size(); i++) out_scores[(size_t)q * n_ids + at[i]] = part[(size_t)q * local.size() + i];
+    }
+    return OTT_OK;
+}
+
 }  // namespace ott
 
 extern "C" {

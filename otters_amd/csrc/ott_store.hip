@@ -29,11 +29,12 @@ struct OptName {
     const char* name;
     int kind;  // 0 = bool, 1 = tri-state (-1 automatic / 0 / 1), 2 = non-negative int
 };
-// the eighteen options of the product library (see struct Options) ...
+// the nineteen options of the product library (see struct Options) ...
 const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"hi_prebuild", 1},          {"stage_appends", 1},       {"multi_transport", 2},
                              {"multi_rebalance", 0}, {"multi_min_shard_rows", 2}, {"exact_small", 1},     {"large_k_from", 2},        {"small_sort", 1},
                              {"mfma_f32", 0},        {"no_hi_pass", 0},      {"no_batch_image", 0},       {"force_fallback", 2},      {"eps_scale_ppm", 2},
                              {"multi_fake_distinct", 0}, {"exact_prune", 1},            {"exact_sketch", 1},
+                             {"id_gather", 1},
 #ifdef OTT_MFMA_DEBUG_BUILD
                              // ... and, in the diagnostic build only, kernel tuning, timing ablations and every fallback bit by its own name
                              {"mfma_wg", 2},         {"mfma_growth", 2},     {"mfma_debug", 0},           {"mfma_abl", 2},            {"hi_tmin", 2},
@@ -41,11 +42,11 @@ const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"h
                              {"merge_rank1", 1},
 #endif
 };
-static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 18
+static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 19
 #ifdef OTT_MFMA_DEBUG_BUILD
                                                             + 11
 #endif
-              , "the product library's option table stays at eighteen entries");
+              , "the product library's option table stays at nineteen entries");
 }  // namespace
 
 int option_set(Options& o, const char* name, long long v) {
@@ -80,6 +81,7 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "small_sort") return tri(o.small_sort);
     if (n == "exact_prune") return tri(o.exact_prune);
     if (n == "exact_sketch") return tri(o.exact_sketch);
+    if (n == "id_gather") return tri(o.id_gather);
 #ifdef OTT_MFMA_DEBUG_BUILD
     if (n == "mfma_coop") return tri(o.mfma_coop);
     if (n == "mfma_spec") return tri(o.mfma_spec);
@@ -1356,7 +1358,7 @@ int ott_store_destroy(ott_store* s) {
         if (s->d_img8_rel) (void)hipFree(s->d_img8_rel);
     }
     for (ott::DevBuf* b : {&s->d_queries, &s->d_qinv, &s->d_rowmask, &s->d_runs, &s->d_prefix, &s->d_lists, &s->d_lists2, &s->d_hits,
-                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
+                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_gather, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
                            &s->m_tau, &s->m_cntA, &s->m_cntB, &s->m_candA, &s->m_candB, &s->m_over, &s->m_out, &s->m_outcnt,
                            &s->m_uncert, &s->m_prefix, &s->x_send, &s->x_recv, &s->l_keysA, &s->l_keysB, &s->l_qA, &s->l_qB, &s->l_tmp, &s->l_cursor, &s->l_hist, &s->l_gate, &s->l_ctl})
         b->release();

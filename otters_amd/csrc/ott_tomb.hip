@@ -220,6 +220,16 @@ int live_read(const ott_store* s, uint64_t* out_host) {
     return OTT_OK;
 }
 
+int mask_and(ott_store* ctx, const uint64_t* keep, const uint64_t* caller, uint64_t caller_bits, uint64_t n_bits, uint64_t* out) {
+    const uint64_t words = live_words(n_bits);
+    uint64_t blocks = (words + 255) / 256;
+    if (blocks > (uint64_t)ctx->n_cu * 4) blocks = (uint64_t)ctx->n_cu * 4;
+    if (!blocks) return OTT_OK;
+    hipLaunchKernelGGL(and_live_kernel, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, keep, caller, caller_bits, n_bits, out);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+
 int live_compose(ott_store* ctx, const uint64_t** d_mask, uint64_t* mask_bits) {
     if (!ctx->d_live || !ctx->n_dead) return OTT_OK;
     if (!*d_mask) {  // the kernels read the live mask itself
@@ -230,10 +240,7 @@ int live_compose(ott_store* ctx, const uint64_t** d_mask, uint64_t* mask_bits) {
     const uint64_t words = live_words(ctx->n);
     int rc = ctx->d_livefx.ensure((size_t)words * 8);
     if (rc) return rc;
-    uint64_t blocks = (words + 255) / 256;
-    if (blocks > (uint64_t)ctx->n_cu * 4) blocks = (uint64_t)ctx->n_cu * 4;
-    hipLaunchKernelGGL(and_live_kernel, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, ctx->d_live, *d_mask, *mask_bits, ctx->n, (uint64_t*)ctx->d_livefx.p);
-    OTT_HIP(hipGetLastError());
+    if ((rc = mask_and(ctx, ctx->d_live, *d_mask, *mask_bits, ctx->n, (uint64_t*)ctx->d_livefx.p))) return rc;
     *d_mask = (const uint64_t*)ctx->d_livefx.p;
     *mask_bits = ctx->n;
     return OTT_OK;

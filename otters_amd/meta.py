@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import Cmp, Metric, Mode, Path, ResolvedQuery, TakeType, VecStore, infer_default_take_type
+from .vec import Cmp, Metric, Mode, Path, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -698,6 +698,7 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         self.take_type: Optional[TakeType] = None
         self.take_count: Optional[int] = None
         self._path = Path.Auto
+        self._row_ids = None
 
     def meta_filter(self, expr: Expr) -> "MetaQueryPlan":  # src/meta.rs:605-616 (error deferred to collect)
         try:
@@ -720,6 +721,12 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         self._path = Path(path)
         return self
 
+    def with_row_ids(self, ids) -> "MetaQueryPlan":
+        """Rank only the rows `ids` (VecQueryPlan.with_row_ids): ANDed with meta_filter and vec_filter.  Ids of chunks the zone
+        maps prune are dropped on the host before the call."""
+        self._row_ids = ids
+        return self
+
     def resolve(self):
         """Host-side part of collect (src/meta.rs:632-669): k / take defaults, zonemap prune.
         Returns (ResolvedQuery, chunk_mask or None, compiled filter or None)."""
@@ -736,6 +743,14 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         q = np.ascontiguousarray(np.stack(self.queries)) if self.queries else np.zeros((0, st._dim), np.float32)
         rq = ResolvedQuery(queries=q, metric=int(self.metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft,
                            row_mask=None, mode=int(Mode.Merged), path=int(self._path))
+        if self._row_ids is not None:
+            ids = as_row_ids(self._row_ids)
+            if chunk_mask is not None and ids.size:  # (an id past the store's end stays: the library names it)
+                inside = ids < np.uint64(st._n_rows)
+                keep = np.ones(ids.size, dtype=bool)
+                keep[inside] = chunk_mask[(ids[inside] // np.uint64(st._chunk_size)).astype(np.int64)]
+                ids = np.ascontiguousarray(ids[keep])
+            rq.row_ids = ids
         return rq, chunk_mask, self._meta_filter
 
     def collect(self) -> MetaQueryResults:  # src/meta.rs:632-829

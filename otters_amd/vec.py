@@ -99,6 +99,28 @@ class ResolvedQuery:
     row_mask: Optional[np.ndarray]  # bool[<=n] or None
     mode: int = Mode.Merged
     path: int = Path.Auto
+    row_ids: Optional[np.ndarray] = None  # uint64[n_ids] (with_row_ids): only these rows are ranked, or None
+
+
+def as_row_ids(ids) -> np.ndarray:
+    """A candidate id list as uint64[n]: any integer sequence or array; a negative or non-integer id raises OttersError."""
+    a = np.asarray(ids)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.uint64)
+    a = a.ravel()
+    if a.dtype == bool or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise OttersError(f"row ids must be integers, not {a.dtype}")
+    if np.issubdtype(a.dtype, np.floating):
+        if not np.all(np.isfinite(a)) or np.any(a != np.floor(a)):
+            raise OttersError("row ids must be integers")
+        if a.min() < 0:
+            raise OttersError(f"row id {int(a.min())} is negative")
+        if a.max() >= 2.0 ** 64:
+            raise OttersError("row ids must fit 64 bits")
+        return np.ascontiguousarray(a.astype(np.uint64))
+    if np.issubdtype(a.dtype, np.signedinteger) and int(a.min()) < 0:
+        raise OttersError(f"row id {int(a.min())} is negative")
+    return np.ascontiguousarray(a.astype(np.uint64))
 
 
 def infer_default_take_type(metric: Metric) -> TakeType:  # src/vec.rs:92-98
@@ -117,6 +139,7 @@ class VecQueryPlan:
         self.vector_store: Optional["VecStore"] = None
         self.error: Optional[str] = None
         self.row_mask: Optional[np.ndarray] = None
+        self.row_ids = None  # with_row_ids: the list as the caller gave it (checked at validate())
         self._mode = Mode.Merged
         self._path = Path.Auto
 
@@ -179,6 +202,15 @@ class VecQueryPlan:
         self._path = Path(path)
         return self
 
+    def with_row_ids(self, ids) -> "VecQueryPlan":
+        """Rank only the rows `ids` (counted from the store's first row; any integer sequence or array, any order, duplicates
+        allowed): the hits of the same plan with a row mask that keeps just these rows, ANDed with with_row_mask and the
+        deleted rows (ott_query_ids).  The work follows the list, not the store.  A negative or non-integer id raises at
+        validate(), an id >= len() when the query runs."""
+        if self.error is None:
+            self.row_ids = ids
+        return self
+
     # -- execution -----------------------------------------------------------------------------
     def validate(self) -> None:  # src/vec.rs:170-203
         if self.error is not None:
@@ -191,6 +223,8 @@ class VecQueryPlan:
             raise OttersError("Vector store is not set")
         if len(self.query_vectors) == 0:
             raise OttersError("No queries provided")
+        if self.row_ids is not None:
+            as_row_ids(self.row_ids)
         dim = self.vector_store.dim
         if isinstance(self.query_vectors, np.ndarray):  # a matrix: every row has the same length
             if self.query_vectors.shape[1] != dim:
@@ -212,7 +246,8 @@ class VecQueryPlan:
         take = self.take_type if self.take_type is not None else TakeType.Max  # src/vec.rs:214
         fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
         return ResolvedQuery(queries=queries, metric=int(self.search_metric), take=int(take), k=max(int(k), 0),
-                             filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, mode=int(self._mode), path=int(self._path))
+                             filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, mode=int(self._mode), path=int(self._path),
+                             row_ids=None if self.row_ids is None else as_row_ids(self.row_ids))
 
     def collect(self):  # src/vec.rs:205-311
         hits, counts = self.collect_arrays()
@@ -438,7 +473,7 @@ class VecStore:
         return bool(self._n) and bool(N.lib().ott_store_batch_ready(self._handle()))
 
     def set_option(self, name: str, value: int) -> None:
-        """Behaviour switch of this store (ott_store_set_option; the eighteen names are listed in include/otters_hip.h:
+        """Behaviour switch of this store (ott_store_set_option; the nineteen names are listed in include/otters_hip.h:
         "tie_order", "hi_fmt", "hi_prebuild", ..., "force_fallback").  Results never depend on any but "tie_order"."""
         self._options[name] = int(value)
         if self._h is not None:
@@ -492,12 +527,14 @@ class VecStore:
 
     # -- execution -----------------------------------------------------------------------------
     def _run(self, rq: ResolvedQuery, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
-        """ott_query.  Returns (hits HIT_DTYPE array, per-query counts, stats dict)."""
+        """ott_query (ott_query_ids when the plan carries an id list).  Returns (hits HIT_DTYPE array, per-query counts, stats dict)."""
         nq = rq.queries.shape[0]
-        if self._n == 0:  # nothing resident: VecQueryPlan::collect yields an empty Vec (src/vec.rs:222, 270)
+        ids = rq.row_ids
+        if self._n == 0 and (ids is None or ids.size == 0):  # nothing resident: VecQueryPlan::collect yields an empty Vec (src/vec.rs:222, 270)
             return np.zeros(0, dtype=N.HIT_DTYPE), [0] * nq, None
         perq = rq.mode == Mode.PerQuery
-        pool = self._n if perq else self._n * nq
+        rows = self._n if ids is None else int(np.unique(ids).size)  # the buffer is sized by the list, not by the store
+        pool = rows if perq else rows * nq
         k_eff = min(rq.k, pool)
         cap = max(k_eff * (nq if perq else 1), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)  # ott_query writes n_out entries; only those are returned
@@ -521,6 +558,24 @@ class VecStore:
         n_out = C.c_uint64(0)
         per = (C.c_uint64 * nq)()
         st = N.Stats()
-        N.check(N.lib().ott_query(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        if ids is None:
+            N.check(N.lib().ott_query(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        else:
+            N.check(N.lib().ott_query_ids(self._handle(), C.byref(d), N.ptr(ids), ids.size, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         hits = out if n_out.value == cap else out[: n_out.value].copy()
         return hits, list(per), st.as_dict()
+
+    def score_rows(self, queries, metric: Metric, ids) -> np.ndarray:
+        """float32[nq, n_ids]: the score of every query against every row of `ids` (ott_store_score_rows) -- the exact path's bits,
+        in the list's order, duplicates allowed, no filter and no top-k; a NaN score comes back as NaN.  Reads stored data: a
+        deleted row is scored like any other."""
+        qv = QueryBatch(queries).queries
+        if len(qv) == 0:
+            raise OttersError("No queries provided")
+        q = qv if isinstance(qv, np.ndarray) else np.ascontiguousarray(np.stack(qv).astype(np.float32, copy=False))
+        if q.shape[1] != self.dim:
+            raise OttersError(f"Query vector length {q.shape[1]} does not match expected dimension {self.dim}")
+        ids = as_row_ids(ids)
+        out = np.empty((q.shape[0], ids.size), dtype=np.float32)
+        N.check(N.lib().ott_store_score_rows(self._handle(), N.ptr(q), q.shape[0], int(Metric(metric)), N.ptr(ids), ids.size, N.ptr(out)))
+        return out
