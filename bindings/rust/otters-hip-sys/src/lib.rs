@@ -181,6 +181,10 @@ extern "C" {
     pub fn ott_query(s: *mut ott_store, d: *const ott_query_desc, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int;
     pub fn ott_query_ids(s: *mut ott_store, d: *const ott_query_desc, ids: *const u64, n_ids: u64, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int;
     pub fn ott_store_score_rows(s: *mut ott_store, queries: *const f32, nq: u32, metric: u32, ids: *const u64, n_ids: u64, out_scores: *mut f32) -> c_int;
+    pub fn ott_store_set_groups(s: *mut ott_store, gid_host: *const c_void, n: u64, n_groups: u32) -> c_int; // gid_host: n u32
+    pub fn ott_store_clear_groups(s: *mut ott_store) -> c_int;
+    pub fn ott_store_group_count(s: *const ott_store) -> u32;
+    pub fn ott_query_groups(s: *mut ott_store, d: *const ott_query_desc, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int;
     pub fn ott_query_device(s: *mut ott_store, d: *const ott_query_desc, out_dev: *mut c_void, cap: u64, n_out_dev: *mut c_void, stats: *mut ott_stats) -> c_int;
     pub fn ott_store_sync(s: *mut ott_store) -> c_int;
     pub fn ott_store_stream(s: *mut ott_store) -> *mut c_void;

@@ -369,6 +369,37 @@ int ott_query_ids(ott_store* s, const ott_query_desc* d, const uint64_t* ids, ui
 int ott_store_score_rows(ott_store* s, const float* queries, uint32_t nq, uint32_t metric, const uint64_t* ids, uint64_t n_ids,
                          float* out_scores);
 
+/* Grouped search (an extension; Elasticsearch field collapse, Qdrant search_groups, Milvus group_by_field): one best hit per group,
+ * top-k over the groups — top-10 DOCUMENTS of a store of chunks.  A store may carry one dense group id per row (uint32, < n_groups,
+ * resident in HBM at 4 B per row).  ott_query_groups returns exactly the hits — index, score bits, order, per-query counts — of the
+ * same query with the default take (every passing pair in the canonical order: better score, lower row, lower query) after dropping
+ * every hit whose group occurred earlier in that list, cut at k; per query in PER_QUERY mode.  chunk_mask, the caller's row_mask or
+ * the evaluated device mask, the live mask of deleted rows and the score filter all apply BEFORE grouping: a masked, deleted or
+ * filtered row never represents its group, the group's best surviving row does; NaN scores are dropped as everywhere.  All four
+ * metrics, both takes, every comparator.  The order among equal scores is ALWAYS the canonical one, whatever option "tie_order"
+ * says: the reference has no grouped query whose tie outcome could be reproduced.
+ * k_eff = min(k, n_groups); cap >= k_eff (MERGED) or nq * k_eff (PER_QUERY).
+ * One sweep over the rows keeps, per (query, group), the best candidate key in a table of n_groups 8-byte slots (scratch of the
+ * query context); the top-k is taken over the slots (k_eff <= 512: register lists + the block-list merge; above: the radix sort).
+ * Refused: OTT_MODE_MERGED with nq > 1 (OTT_ERR_UNSUPPORTED: one winner per group ACROSS queries is left out; use PER_QUERY) and
+ * OTT_PATH_MFMA (OTT_ERR_UNSUPPORTED; AUTO takes the exact sweep and never builds, extends or waits for a plane).  OTT_ERR_INVALID,
+ * checked on the host before any device work: no group ids are set, or they cover a different number of rows than ott_store_len
+ * (rows were appended since: set them again).  Takes the store shared, like ott_query (staged appends go first).
+ *
+ * ott_store_set_groups: gid_host points at n uint32_t (declared const void*, as ott_store_add_column's values), [i] = group of row i, n must equal ott_store_len, every id < n_groups (else OTT_ERR_INVALID, checked
+ * on the host before any device work); a second call replaces the first.  ott_store_clear_groups drops them.  Both take the store
+ * exclusively, like ott_store_add_column, and flush staged appends first.  Group ids count as a resident metadata column: while they
+ * are set ott_store_compact is refused (OTT_ERR_UNSUPPORTED) and a multi-GPU store no longer moves rows between its shards;
+ * clear_groups lifts both.  A reallocation on append keeps the ids that are there.  A store without groups runs exactly what it ran
+ * before: nothing is allocated, no launch is added.  ott_store_group_count: n_groups, 0 = none set.
+ * Multi-GPU store: ids are global and routed by row range; every shard answers for its rows, the host merges the shards' lists by the
+ * canonical order and keeps each group's first hit (a group in the global top-k is in its own shard's top-k). */
+int ott_store_set_groups(ott_store* s, const void* gid_host /* uint32_t[n] */, uint64_t n, uint32_t n_groups);
+int ott_store_clear_groups(ott_store* s);
+uint32_t ott_store_group_count(const ott_store* s);
+int ott_query_groups(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query,
+                     ott_stats* stats);
+
 /* Same, but the result stays on the GPU: out_dev holds `cap` ott_hit slots in device memory
  * of the store's GPU, padded with sentinel hits (index = UINT64_MAX); *n_out_dev (device
  * uint64) receives the count.  PER_QUERY mode: cap must be a multiple of nq; query q's hits

@@ -139,6 +139,8 @@ void build_plan(const ott_store* s, const uint64_t* chunk_mask, RunPlan& pl) {
 }  // namespace
 
 namespace ott {
+void make_run_plan(const ott_store* s, const uint64_t* chunk_mask, RunPlan& pl) { build_plan(s, chunk_mask, pl); }
+
 int validate_query(const ott_store* s, const ott_query_desc* d) {
     if (!s) return fail(OTT_ERR_INVALID, "ott_query: store is NULL");
     if (!d) return fail(OTT_ERR_INVALID, "ott_query: desc is NULL");

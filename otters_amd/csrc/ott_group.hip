@@ -1,0 +1,602 @@
+// ott_group.hip — grouped search: one best hit per group, top-k over the groups.  ott_query_groups returns the
+// hits of the same query with the default take (every passing pair in the canonical order) after dropping every hit whose group
+// occurred earlier in that list, cut at k — per query.  One sweep and one small table give that answer on the GPU:
+//
+//   group_sweep_kernel    exact_kernel's streaming geometry with every variant stripped (lane = row, 64-row tiles per wave, 128-B
+//                         stages through the swizzled LDS tile, queries through the constant address space, a persistent grid over
+//                         the run lists of surviving chunks), the scoring terms of ott_exact_dev.h, so the bits are the oracle's.
+//                         Epilogue per (row, query of the pass): composed row mask, NaN drop, cmp_holds, key = ord(score) << 32 |
+//                         ~row; if the key beats a load of table[q][gid[row]], a vector atomicMax on that 64-bit slot.  The load
+//                         in front keeps the atomics at the number of IMPROVEMENTS, not the number of rows.  0 = empty slot (no
+//                         key is 0: rows stay below 2^32 - 16, so ~row >= 15).  The largest key of a group is its best score and,
+//                         among equal scores, its lowest row: the group's first hit in the canonical list.
+//   group_select_kernel   k_eff <= 512: one-wave workgroups sweep the table and offer every non-empty slot to a register wave list
+//                         (WaveList<E>); block lists in the layout launch_merge takes.  Leaves the slots it read zeroed.
+//   group_compact_kernel  k_eff > 512 (what a plan without take() gives): the non-empty slots become (key, query) pairs in the
+//                         arrays of ott_sort.hip; its radix sort and hits_from_sorted order them (sort_group_pairs).  Zeroes too.
+//
+// Tie order: ALWAYS the canonical one (better score, lower row, lower query), whatever option tie_order says — the reference has
+// no grouped query whose tie outcome could be reproduced.  MERGED with nq > 1 is refused (one winner per group ACROSS queries is
+// left out: use PER_QUERY), Path.Mfma too (AUTO takes this sweep and never builds, extends or waits for a plane, as for Manhattan).
+//
+// Queries per pass: 4 (one for a single query).  A lane keeps 8 accumulators and a tail per query beside the 32 staging registers
+// of the next stage: 4 queries are 36 + 32 live floats, which exact_kernel measured as the sweet spot of this geometry (an 8-wide
+// pass needs 233 VGPRs and ran slower than two 4-wide ones); the epilogue here adds a key and a slot address, not a list.
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#include "ott_internal.h"
+#include "ott_exact_dev.h"
+
+namespace ott {
+
+constexpr int GS_KC = 32;                   // floats per row per stage: one 128-B line
+constexpr int GS_WAVES = 4;
+constexpr int GS_STAGE_FLOATS = 64 * GS_KC;  // per wave: 8 KB
+constexpr int GS_SMEM = GS_WAVES * GS_STAGE_FLOATS * 4;
+constexpr int GS_BLOCKS_PER_CU = 2;         // the persistent grid of exact_kernel
+constexpr uint32_t GS_NQ = 4;               // queries per pass of a batch
+constexpr uint32_t GS_MAX_LISTS = 1024;     // block lists per query the select kernel writes (merge_rank_kernel takes up to 4096)
+
+struct GroupParams {
+    const float* rows;
+    const float* inv;
+    const float* queries;  // [nq_pad * dimq], zero padded
+    const float* qinv;     // [nq_pad]
+    const uint64_t* row_mask;
+    uint64_t row_mask_bits;
+    const ott_run* runs;
+    const uint32_t* tile_prefix;  // [n_runs + 1]
+    const uint32_t* gid;          // [n] dense group ids, every one < n_groups (checked on the host when they were set)
+    unsigned long long* table;    // [NQ][n_groups] best key per (query of the pass, group); 0 = empty
+    uint32_t n_groups;
+    uint32_t ld, dim, dimq;
+    uint32_t n_runs, n_tiles;
+    uint32_t q0, nq_total;
+    uint32_t metric, take_max, cmp, reduce;
+    float thr;
+};
+
+template <int MK, int NQ>
+__global__ __launch_bounds__(64 * GS_WAVES) void group_sweep_kernel(GroupParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float* st = smem + wave * GS_STAGE_FLOATS;
+    const bool take_max = p.take_max != 0;
+    const uint32_t nq_here = (p.nq_total - p.q0) < (uint32_t)NQ ? (p.nq_total - p.q0) : (uint32_t)NQ;
+    // wave-uniform, read-only inputs through the CONSTANT address space: always scalar loads (see exact_kernel)
+    typedef __attribute__((address_space(4))) const float* CF32;
+    typedef __attribute__((address_space(4))) const uint32_t* CU32;
+    typedef __attribute__((address_space(4))) const ott_run* CRUN;
+    const CF32 Q = (CF32)(p.queries + (size_t)p.q0 * p.dimq);
+    const CU32 tile_prefix = (CU32)p.tile_prefix;
+    const CRUN runs = (CRUN)p.runs;
+    float qinv[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) qinv[q] = (uint32_t)q < nq_here ? p.qinv[p.q0 + q] : 0.0f;
+
+    const uint32_t gw = blockIdx.x * GS_WAVES + wave, nw = gridDim.x * GS_WAVES;
+    const int sw = (lane >> 1) & 7;
+    const uint32_t nstages = (p.ld + GS_KC - 1) / GS_KC;
+    const int lrow = lane >> 3;  // row within an 8-row load group
+    const int lslot = lane & 7;  // 16-B slot within the 128-B line
+    // its float offset, kept inside a short row (dim < 29): the staging loads are unconditional, so a slot past the row's end must
+    // not make the LAST row of the store read past the allocation
+    const uint32_t lsl4 = ((uint32_t)lslot * 4 < p.ld) ? (uint32_t)lslot * 4 : 0u;
+
+    for (uint32_t t = gw; t < p.n_tiles; t += nw) {
+        // tile -> run of surviving chunks (wave-uniform scalar search)
+        uint32_t lo = 0, hi = p.n_runs;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (tile_prefix[mid] <= t) lo = mid;
+            else hi = mid;
+        }
+        const uint64_t run_start = runs[lo].start, run_count = runs[lo].count;
+        const uint64_t off = (uint64_t)(t - tile_prefix[lo]) * 64;
+        const uint64_t row0 = run_start + off;
+        const uint32_t cnt = (run_count - off) < 64 ? (uint32_t)(run_count - off) : 64u;
+        const uint64_t my_row = row0 + lane;
+        bool valid = (uint32_t)lane < cnt;
+        if (p.row_mask != nullptr && valid && my_row < p.row_mask_bits)
+            valid = (p.row_mask[my_row >> 6] >> (my_row & 63)) & 1;  // src/vec.rs:231-237
+        if (__ballot(valid) == 0) continue;  // whole tile masked: its rows are never read
+
+        // the row's group and inverse norm are fetched now and used after the K loop: their latency hides behind the stages
+        float vinv = 0.0f;
+        uint32_t g = 0;
+        if (valid) {
+            g = p.gid[my_row];
+            if (p.metric == OTT_METRIC_COSINE) vinv = p.inv[my_row];
+        }
+        float acc[NQ][8];
+        float tail[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            tail[q] = 0.0f;
+#pragma unroll
+            for (int l = 0; l < 8; l++) acc[q][l] = 0.0f;
+        }
+        // Branch-free staging: every load is always issued (rows past a short tile's end are clamped to its last row, a column
+        // group past `ld` in the last stage re-reads stage 0) and the out-of-range values are zeroed when they go to LDS
+        v4f R[8];
+        const float* rp[8];
+        bool rok[8];
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            const uint32_t row = 8 * m + lrow;
+            rok[m] = row < cnt;
+            rp[m] = p.rows + (row0 + (rok[m] ? row : cnt - 1)) * (uint64_t)p.ld + lsl4;
+        }
+        auto load_stage = [&](uint32_t s) {
+            const uint32_t soff = (s * GS_KC + lslot * 4 < p.ld) ? s * GS_KC : 0u;
+#pragma unroll
+            for (int m = 0; m < 8; m++) R[m] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(rp[m] + soff));  // streamed once per pass
+        };
+        load_stage(0);
+        for (uint32_t s = 0; s < nstages; s++) {
+            const bool cok = s * GS_KC + lslot * 4 < p.ld;
+#pragma unroll
+            for (int m = 0; m < 8; m++) {
+                const int row = 8 * m + lrow;
+                const bool ok = rok[m] & cok;
+                const v4f v = R[m];
+                *reinterpret_cast<float4*>(st + row * GS_KC + ((lslot ^ ((row >> 1) & 7)) << 2)) =
+                    make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
+            }
+            wave_sync();
+            if (s + 1 < nstages) load_stage(s + 1);
+#pragma unroll
+            for (int j = 0; j < GS_KC / 8; j++) {
+                const uint32_t col = s * GS_KC + 8 * j;
+                if (col < p.dim) {
+                    const float4 a = *reinterpret_cast<const float4*>(st + lane * GS_KC + (((2 * j) ^ sw) << 2));
+                    const float4 b = *reinterpret_cast<const float4*>(st + lane * GS_KC + (((2 * j + 1) ^ sw) << 2));
+                    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+                    if (col + 8 <= p.dim) {
+                        // one chunks_exact(8) step: acc = acc + term(q, v)   (vec_compute.rs:12-13, 39-42); every slot of the
+                        // pass is computed (the query block is zero padded): no per-query branch
+#pragma unroll
+                        for (int q = 0; q < NQ; q++) {
+                            const CF32 qp = Q + (size_t)q * p.dimq + col;
+#pragma unroll
+                            for (int l = 0; l < 8; l++) acc[q][l] = __fadd_rn(acc[q][l], exact_term<MK>(qp[l], x[l]));
+                        }
+                    } else {
+                        // remainder: sequential sum of the last dim % 8 terms (vec_compute.rs:15-21, 44-53)
+                        const uint32_t nt = p.dim - col;
+#pragma unroll
+                        for (int q = 0; q < NQ; q++) {
+                            const CF32 qp = Q + (size_t)q * p.dimq + col;
+#pragma unroll
+                            for (int l = 0; l < 7; l++)
+                                if ((uint32_t)l < nt) tail[q] = __fadd_rn(tail[q], exact_term<MK>(qp[l], x[l]));
+                        }
+                    }
+                }
+            }
+            wave_sync();
+        }
+
+        // score -> filter -> key -> the group's slot
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            if ((uint32_t)q < nq_here) {
+                float s = __fadd_rn(reduce8(acc[q], p.reduce), tail[q]);
+                if (p.metric == OTT_METRIC_COSINE) s = __fmul_rn(__fmul_rn(s, qinv[q]), vinv);  // vec_compute.rs:31
+                const bool pass = valid && !(s != s) && cmp_holds(s, p.cmp, p.thr);             // NaN dropped: vec_compute.rs:237
+                if (pass) {
+                    const unsigned long long key = ((unsigned long long)ord_of(s, take_max) << 32) | (uint32_t)(~(uint32_t)my_row);
+                    unsigned long long* slot = p.table + (size_t)q * p.n_groups + g;
+                    // the load goes past this CU's vector L1 (agent scope), so it sees what other CUs' atomics left; a value that
+                    // is stale all the same is a smaller one (slots only rise) and costs an atomic, never a result
+                    if (key > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, key);
+                }
+            }
+        }
+    }
+}
+
+// One wave per workgroup; blockIdx.x = list, blockIdx.y = query of the pass.  The wave walks tiles of 64 slots, list by list
+// strided, and offers the non-empty ones; the slots it read are left zeroed (the next query's sweep needs no memset).
+template <int E>
+__global__ __launch_bounds__(64) void group_select_kernel(unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t k, Cand* lists,
+                                                          uint32_t n_lists, uint32_t list_stride) {
+    const int lane = threadIdx.x;
+    const uint32_t qy = blockIdx.y;
+    unsigned long long* tab = table + (size_t)qy * n_groups;
+    const uint32_t n_tiles = (n_groups + 63) / 64;
+    WaveList<E> L;
+    wl_init(L);
+    uint64_t tk = 0;
+    uint32_t tq = 0xFFFFFFFFu;
+    bool fresh = true;
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint32_t i = t * 64 + (uint32_t)lane;
+        uint64_t key = 0;
+        if (i < n_groups) {
+            key = tab[i];
+            if (key != 0) tab[i] = 0ull;
+        }
+        const bool pass = key != 0;
+        if (__ballot(pass) == 0) continue;
+        if (fresh) {
+            wl_fill_sorted(L, tk, tq, k, pass, key, q0 + qy, lane, 0u);
+            fresh = false;
+        } else {
+            wl_offer_block(L, tk, tq, k, pass, key, q0 + qy, lane, 0u);
+        }
+    }
+    Cand* dst = lists + ((size_t)(q0 + qy) * n_lists + blockIdx.x) * list_stride;
+#pragma unroll
+    for (int e = 0; e < E; e++) {
+        Cand c;
+        c.key = L.key[e];
+        c.q = L.q[e];
+        c.pad = 0;
+        dst[e * 64 + lane] = c;
+    }
+}
+
+// k_eff > 512: every non-empty slot of the pass's table becomes a (key, query) pair behind the cursor — one returning atomic
+// per wave and tile that holds any — and is zeroed.  blockIdx.y = query of the pass.
+__global__ __launch_bounds__(256) void group_compact_kernel(unsigned long long* table, uint32_t n_groups, uint32_t q0, uint64_t* keys, uint32_t* qs,
+                                                            unsigned long long* cursor, uint64_t cap) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t qy = blockIdx.y;
+    unsigned long long* tab = table + (size_t)qy * n_groups;
+    const uint32_t n_round = (n_groups + 63) & ~63u;  // whole waves stay together for the ballot
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t key = 0;
+        if (i < n_groups) {
+            key = tab[i];
+            if (key != 0) tab[i] = 0ull;
+        }
+        const uint64_t m = __ballot(key != 0);
+        if (m == 0) continue;
+        unsigned long long base = 0;
+        if (lane == (int)__builtin_ctzll(m)) base = atomicAdd(cursor, (unsigned long long)__popcll(m));
+        base = rl64(base, (int)__builtin_ctzll(m));
+        if (key != 0) {
+            const uint64_t at = base + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (at < cap) {
+                keys[at] = key;
+                qs[at] = q0 + qy;
+            }
+        }
+    }
+}
+
+// out[i] = gid[rows[i]], rows[i] < the rows the ids cover (checked on the host)
+__global__ __launch_bounds__(256) void group_gather_kernel(const uint32_t* __restrict__ gid, const uint64_t* __restrict__ rows, uint64_t n, uint32_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = gid[rows[i]];
+}
+
+namespace {
+
+uint64_t now_ns() {
+    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+template <int MK>
+int launch_sweep_mk(ott_store* s, const GroupParams& p, uint32_t nq_tile, uint32_t grid) {
+    if (nq_tile == 1) hipLaunchKernelGGL((group_sweep_kernel<MK, 1>), dim3(grid), dim3(64 * GS_WAVES), GS_SMEM, s->stream, p);
+    else hipLaunchKernelGGL((group_sweep_kernel<MK, (int)GS_NQ>), dim3(grid), dim3(64 * GS_WAVES), GS_SMEM, s->stream, p);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+
+int launch_sweep(ott_store* s, const GroupParams& p, uint32_t nq_tile, uint32_t grid) {
+    switch (metric_kind(p.metric)) {
+        case MK_L2: return launch_sweep_mk<MK_L2>(s, p, nq_tile, grid);
+        case MK_L1: return launch_sweep_mk<MK_L1>(s, p, nq_tile, grid);
+        default: return launch_sweep_mk<MK_DOT>(s, p, nq_tile, grid);
+    }
+}
+
+int launch_select(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint32_t k, int E, Cand* lists, uint32_t n_lists) {
+#define OTT_GSEL(Ev)                                                                                                                       \
+    if (E == Ev) {                                                                                                                         \
+        hipLaunchKernelGGL((group_select_kernel<Ev>), dim3(n_lists, nq_here), dim3(64), 0, s->stream, table, n_groups, q0, k, lists, n_lists, \
+                           (uint32_t)(64 * Ev));                                                                                           \
+        OTT_HIP(hipGetLastError());                                                                                                        \
+        return OTT_OK;                                                                                                                     \
+    }
+    OTT_GSEL(1) OTT_GSEL(2) OTT_GSEL(4) OTT_GSEL(8)
+#undef OTT_GSEL
+    return fail(OTT_ERR_INVALID, "group select: bad E");
+}
+
+// The grouped query on a context whose `mu` the caller holds (and the owner's `rw`, shared).  k_eff = min(k, n_groups) >= 1.
+int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats_out) {
+    int rc;
+    OTT_HIP(use_device(s));
+    const uint64_t t0 = now_ns();
+    ott_stats st;
+    memset(&st, 0, sizeof(st));
+    const uint32_t nq = d->nq, ng = s->n_groups;
+    RunPlan pl;
+    make_run_plan(s, d->chunk_mask, pl);
+    st.path_used = OTT_PATH_EXACT;
+    st.total_chunks = pl.total_chunks;
+    st.evaluated_chunks = pl.evaluated;
+    st.pruned_chunks = pl.total_chunks - pl.evaluated;
+    st.vectors_compared = pl.rows_scored * nq;
+    if (pl.rows_scored == 0) {
+        st.total_ns = now_ns() - t0;
+        if (stats_out) *stats_out = st;
+        return OTT_OK;
+    }
+    const uint64_t* d_mask = nullptr;
+    uint64_t mask_bits = 0;
+    if ((rc = compose_row_mask(s, d, &d_mask, &mask_bits))) return rc;
+    const std::vector<uint32_t> prefix = tile_prefix(pl, 64);
+    const uint32_t n_tiles = prefix.back();
+    if ((rc = upload_exact_inputs(s, d->queries, nq, pl, prefix))) return rc;
+
+    const uint32_t tile = nq == 1 ? 1u : GS_NQ;
+    const uint32_t passes = (nq + tile - 1) / tile;
+    // the table: zero when a query finds it — zeroed when it is (re)allocated or a query failed half way, and left zeroed by every
+    // query's select / compact kernel
+    const size_t tab_bytes = (size_t)tile * ng * 8;
+    if (s->d_gtable.cap < tab_bytes || !s->gtable_clean) {
+        if ((rc = s->d_gtable.ensure(tab_bytes))) return rc;
+        OTT_HIP(hipMemsetAsync(s->d_gtable.p, 0, s->d_gtable.cap, s->stream));
+    }
+    s->gtable_clean = false;
+    unsigned long long* table = (unsigned long long*)s->d_gtable.p;
+
+    GroupParams p;
+    memset(&p, 0, sizeof(p));
+    p.rows = s->d_rows;
+    p.inv = s->d_inv;
+    p.queries = (const float*)s->d_queries.p;
+    p.qinv = (const float*)((const char*)s->d_queries.p + s->in_off_qinv);
+    p.row_mask = d_mask;
+    p.row_mask_bits = mask_bits;
+    p.runs = (const ott_run*)((const char*)s->d_queries.p + s->in_off_runs);
+    p.tile_prefix = (const uint32_t*)((const char*)s->d_queries.p + s->in_off_prefix);
+    p.gid = s->d_gid;
+    p.table = table;
+    p.n_groups = ng;
+    p.ld = s->ld;
+    p.dim = s->dim;
+    p.dimq = s->dimq;
+    p.n_runs = (uint32_t)pl.runs.size();
+    p.n_tiles = n_tiles;
+    p.nq_total = nq;
+    p.metric = d->metric;
+    p.take_max = d->take == OTT_TAKE_MAX;
+    p.cmp = d->filter_cmp;
+    p.thr = d->filter_thr;
+    p.reduce = s->reduce;
+    // the persistent grid: a workgroup of four waves per four tiles, at most GS_BLOCKS_PER_CU per CU — from
+    // 4 x GS_BLOCKS_PER_CU x n_cu tiles (2048 tiles = 131072 rows on 256 CUs) a wave takes a second tile
+    uint32_t grid = (n_tiles + GS_WAVES - 1) / GS_WAVES;
+    const uint32_t grid_cap = (uint32_t)s->n_cu * GS_BLOCKS_PER_CU;
+    if (grid > grid_cap) grid = grid_cap;
+    if (grid < 1) grid = 1;
+
+    const bool lists_path = k_eff <= 512;
+    const int E = lists_path ? list_E(k_eff) : 1;
+    const uint32_t KS = 64u * (uint32_t)E;
+    uint32_t n_lists = (ng + 63) / 64;
+    if (n_lists > GS_MAX_LISTS) n_lists = GS_MAX_LISTS;
+    const uint64_t pair_cap = (uint64_t)nq * ng;
+    if (lists_path) {
+        if ((rc = s->d_lists.ensure((size_t)nq * n_lists * KS * sizeof(Cand)))) return rc;
+    } else {
+        if (pair_cap > 0xFFFFFFF0ull) return fail(OTT_ERR_UNSUPPORTED, "ott_query_groups: more than 2^32 - 16 (query, group) pairs; use take(k) with k <= 512 or fewer queries");
+        if ((rc = ensure_group_pairs(s, pair_cap))) return rc;
+        if ((rc = s->d_gctl.ensure(64))) return rc;
+        OTT_HIP(hipMemsetAsync(s->d_gctl.p, 0, 8, s->stream));
+    }
+    const bool timing = stats_out != nullptr;
+    if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
+    for (uint32_t ps = 0; ps < passes; ps++) {
+        p.q0 = ps * tile;
+        const uint32_t nq_here = (nq - p.q0) < tile ? (nq - p.q0) : tile;
+        if ((rc = launch_sweep(s, p, tile, grid))) return rc;
+        if (lists_path) {
+            if ((rc = launch_select(s, table, ng, p.q0, nq_here, (uint32_t)k_eff, E, (Cand*)s->d_lists.p, n_lists))) return rc;
+        } else {
+            uint32_t blocks = (ng + 255) / 256;
+            if (blocks > (uint32_t)s->n_cu * 8) blocks = (uint32_t)s->n_cu * 8;
+            hipLaunchKernelGGL(group_compact_kernel, dim3(blocks, nq_here), dim3(256), 0, s->stream, table, ng, p.q0, (uint64_t*)s->l_keysA.p, (uint32_t*)s->l_qA.p,
+                               (unsigned long long*)s->d_gctl.p, pair_cap);
+            OTT_HIP(hipGetLastError());
+        }
+    }
+    if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
+    st.passes = passes;
+    st.bytes_scanned = (uint64_t)passes * pl.rows_scored * ((uint64_t)s->dim * 4 + 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));  // (+ 4: the group id)
+
+    uint64_t total = 0;
+    if (lists_path) {
+        // results block in pinned host memory, as run_exact lays it out: [counts (nq x u64, padded to 64 B) | hits (nq x KS)]
+        const size_t cnt_pad = (((size_t)nq * sizeof(uint64_t)) + 63) & ~(size_t)63;
+        const size_t res_bytes = cnt_pad + (size_t)nq * KS * sizeof(ott_hit);
+        if ((rc = s->h_hits.ensure(res_bytes))) return rc;
+        void* mapped = nullptr;
+        OTT_HIP(hipHostGetDevicePointer(&mapped, s->h_hits.p, 0));
+        if ((rc = launch_merge(s, (const Cand*)s->d_lists.p, n_lists, KS, (uint64_t)n_lists * KS, nq, (uint32_t)k_eff, E, p.take_max != 0, s->base_offset,
+                               (ott_hit*)((char*)mapped + cnt_pad), KS, (uint64_t*)mapped, 0)))
+            return rc;
+        if (timing) OTT_HIP(hipEventRecord(s->ev[5], s->stream));
+        OTT_HIP(hipStreamSynchronize(s->stream));
+        s->gtable_clean = true;
+        const char* hh = (const char*)s->h_hits.p;
+        const uint64_t* counts = (const uint64_t*)hh;
+        const ott_hit* hits = (const ott_hit*)(hh + cnt_pad);
+        for (uint32_t q = 0; q < nq; q++) {
+            const uint64_t cq = counts[q];
+            if (cq) memcpy(out + total, hits + (size_t)q * KS, (size_t)cq * sizeof(ott_hit));
+            if (n_per_query) n_per_query[q] = cq;
+            total += cq;
+        }
+    } else {
+        unsigned long long n_pairs = 0;
+        OTT_HIP(hipMemcpyAsync(&n_pairs, s->d_gctl.p, 8, hipMemcpyDeviceToHost, s->stream));
+        OTT_HIP(hipStreamSynchronize(s->stream));
+        s->gtable_clean = true;
+        if (n_pairs > pair_cap) n_pairs = pair_cap;
+        std::vector<std::vector<ott_hit>> lists;
+        if ((rc = sort_group_pairs(s, n_pairs, nq, p.take_max != 0, k_eff, lists))) return rc;
+        if (timing) {
+            OTT_HIP(hipEventRecord(s->ev[5], s->stream));
+            OTT_HIP(hipStreamSynchronize(s->stream));
+        }
+        for (uint32_t q = 0; q < nq; q++) {
+            const std::vector<ott_hit>& l = lists[q];
+            if (!l.empty()) memcpy(out + total, l.data(), l.size() * sizeof(ott_hit));
+            if (n_per_query) n_per_query[q] = l.size();
+            total += l.size();
+        }
+    }
+    if (n_out) *n_out = total;
+    if (timing) read_exact_events(s, &st);
+    st.total_ns = now_ns() - t0;
+    if (stats_out) *stats_out = st;
+    return OTT_OK;
+}
+
+}  // namespace
+
+int group_grow(ott_store* s, uint64_t ncap) {
+    if (!s->d_gid || ncap <= s->cap) return OTT_OK;
+    uint32_t* ng = nullptr;
+    OTT_HIP(hipMalloc((void**)&ng, (size_t)ncap * 4));
+    OTT_HIP(hipMemcpyAsync(ng, s->d_gid, (size_t)s->gid_n * 4, hipMemcpyDeviceToDevice, s->stream));
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    (void)hipFree(s->d_gid);
+    s->d_gid = ng;
+    return OTT_OK;
+}
+
+// The groups of `n` hits of this store (a shard of a multi-GPU store hands them to the merging host with its hits): a gather of n
+// values from the resident ids.  The caller holds the store shared (or the multi-GPU front that owns it).
+int group_ids_of_hits(ott_store* s, const ott_hit* hits, uint64_t n, uint32_t* out) {
+    if (n == 0) return OTT_OK;
+    if (!s->d_gid) return fail(OTT_ERR_INVALID, "group_ids_of_hits: no group ids are set");
+    ott_store* ctx = ctx_acquire(s);
+    const int rc = [&]() -> int {
+        int r;
+        OTT_HIP(use_device(ctx));
+        if ((r = ctx->h_stage.ensure((size_t)n * 8))) return r;
+        uint64_t* hr = (uint64_t*)ctx->h_stage.p;
+        for (uint64_t i = 0; i < n; i++) {
+            hr[i] = hits[i].index - ctx->base_offset;
+            if (hr[i] >= ctx->gid_n) return fail(OTT_ERR_INVALID, "group_ids_of_hits: a hit outside the store's rows");
+        }
+        if ((r = ctx->d_gather.ensure(64 + (size_t)n * 12))) return r;
+        uint64_t* d_rows = (uint64_t*)((char*)ctx->d_gather.p + 64);
+        uint32_t* d_out = (uint32_t*)(d_rows + n);
+        OTT_HIP(hipMemcpyAsync(d_rows, hr, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(group_gather_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_gid, (const uint64_t*)d_rows, n, d_out);
+        OTT_HIP(hipGetLastError());
+        OTT_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        OTT_HIP(hipStreamSynchronize(ctx->stream));
+        return OTT_OK;
+    }();
+    ctx_release(ctx);
+    return rc;
+}
+
+void group_drop(ott_store* s) {
+    if (s->d_gid) (void)hipFree(s->d_gid);
+    s->d_gid = nullptr;
+    s->gid_n = 0;
+    s->n_groups = 0;
+}
+
+}  // namespace ott
+
+using namespace ott;
+
+extern "C" {
+
+int ott_store_set_groups(ott_store* s, const void* gid_void, uint64_t n, uint32_t n_groups) {
+    const uint32_t* gid_host = (const uint32_t*)gid_void;
+    if (!s) return fail(OTT_ERR_INVALID, "ott_store_set_groups: store is NULL");
+    if (n && !gid_host) return fail(OTT_ERR_INVALID, "ott_store_set_groups: gid is NULL");
+    if (n != ott_store_len(s))
+        return fail(OTT_ERR_INVALID, "ott_store_set_groups: " + std::to_string(n) + " group ids for a store of " + std::to_string(ott_store_len(s)) + " rows");
+    if (n && n_groups == 0) return fail(OTT_ERR_INVALID, "ott_store_set_groups: n_groups is 0");
+    for (uint64_t i = 0; i < n; i++)  // before any device work
+        if (gid_host[i] >= n_groups)
+            return fail(OTT_ERR_INVALID, "ott_store_set_groups: group id " + std::to_string(gid_host[i]) + " of row " + std::to_string(i) + " is not below n_groups = " +
+                                             std::to_string(n_groups));
+    if (s->multi) return multi_set_groups(s, gid_host, n, n_groups);
+    ott::host::ExclusiveLock wr(s->rw);  // no query is running on any context
+    std::lock_guard<std::mutex> g(s->mu);
+    int rc = store_flush_locked(s);
+    if (rc) return rc;
+    if (n != s->n) return fail(OTT_ERR_INVALID, "ott_store_set_groups: the store's length changed during the call");
+    OTT_HIP(use_device(s));
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    group_drop(s);
+    if (n == 0) return OTT_OK;
+    const uint64_t slots = s->cap > n ? s->cap : n;
+    OTT_HIP(hipMalloc((void**)&s->d_gid, (size_t)slots * 4));
+    const hipError_t e = hipMemcpy(s->d_gid, gid_host, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        group_drop(s);
+        return fail(OTT_ERR_HIP, std::string("ott_store_set_groups: ") + hipGetErrorString(e));
+    }
+    s->gid_n = n;
+    s->n_groups = n_groups;
+    return OTT_OK;
+}
+
+int ott_store_clear_groups(ott_store* s) {
+    if (!s) return fail(OTT_ERR_INVALID, "ott_store_clear_groups: store is NULL");
+    if (s->multi) return multi_clear_groups(s);
+    ott::host::ExclusiveLock wr(s->rw);  // no query is running on any context
+    std::lock_guard<std::mutex> g(s->mu);
+    int rc = store_flush_locked(s);
+    if (rc) return rc;
+    if (!s->d_gid) return OTT_OK;
+    OTT_HIP(use_device(s));
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    group_drop(s);
+    return OTT_OK;
+}
+
+uint32_t ott_store_group_count(const ott_store* s) { return s ? s->n_groups : 0u; }
+
+int ott_query_groups(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats) {
+    int rc = validate_query(s, d);
+    if (rc) return rc;
+    if (d->mode == OTT_MODE_MERGED && d->nq > 1)
+        return fail(OTT_ERR_UNSUPPORTED, "ott_query_groups: a merged list over several queries is not served (one winner per group across queries); use PER_QUERY");
+    if (d->path == OTT_PATH_MFMA) return fail(OTT_ERR_UNSUPPORTED, "ott_query_groups: the MFMA path does not serve grouped queries; use path AUTO or EXACT");
+    if (s->n_groups == 0) return fail(OTT_ERR_INVALID, "ott_query_groups: no group ids are set (ott_store_set_groups)");
+    if (n_out) *n_out = 0;
+    if (n_per_query)
+        for (uint32_t i = 0; i < d->nq; i++) n_per_query[i] = 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (s->multi) return multi_query_groups(s, d, out, cap, n_out, n_per_query, stats);
+    if (s->gid_n != ott_store_len(s))  // staged rows count: they were appended
+        return fail(OTT_ERR_INVALID, "ott_query_groups: the group ids cover " + std::to_string(s->gid_n) + " rows, the store holds " + std::to_string(ott_store_len(s)) +
+                                         " (rows were appended since ott_store_set_groups: set them again)");
+    ott::host::SharedLock rd;  // the corpus and the group ids cannot change while this query runs
+    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
+    // what the checks above read without the lock is read again, and k_eff only here: a set_groups may have come in between
+    if (s->n_groups == 0) return fail(OTT_ERR_INVALID, "ott_query_groups: no group ids are set (ott_store_set_groups)");
+    if (s->gid_n != s->n) return fail(OTT_ERR_INVALID, "ott_query_groups: the group ids no longer cover the store's rows (set them again)");
+    const uint64_t k_eff = d->k < s->n_groups ? d->k : s->n_groups;
+    if (cap < k_eff * d->nq) return fail(OTT_ERR_INVALID, "ott_query_groups: output capacity is smaller than nq * min(k, n_groups)");
+    if (!out && cap) return fail(OTT_ERR_INVALID, "ott_query_groups: out is NULL");
+    if (k_eff == 0) return OTT_OK;
+    ott_store* ctx = ctx_acquire(s);
+    rc = run_groups(ctx, d, k_eff, out, n_out, n_per_query, stats);
+    ctx_release(ctx);
+    return rc;
+}
+
+}  // extern "C"

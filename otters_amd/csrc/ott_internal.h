@@ -294,6 +294,16 @@ struct ott_store {
     // 64 B) | raw scores of ott_store_score_rows]
     ott::DevBuf d_idmask, d_gather;
     uint64_t* cur_idmask = nullptr;
+    // Grouped search (ott_group.hip).  d_gid: one dense group id per row slot, [cap] words, allocated by
+    // ott_store_set_groups and freed by ott_store_clear_groups; nullptr = no groups (and nothing else below exists).  gid_n: the
+    // rows the ids cover (a query needs gid_n == n).  Owned by the store (workers alias it), changed only under `rw` exclusive; a
+    // reallocation copies the ids (group_grow).  d_gtable: THIS context's table of best keys, [queries per pass][n_groups] x 8 B,
+    // left zeroed by every query's select / compact kernel (gtable_clean); d_gctl: the compact kernel's cursor
+    uint32_t* d_gid = nullptr;
+    uint64_t gid_n = 0;
+    uint32_t n_groups = 0;
+    ott::DevBuf d_gtable, d_gctl;
+    bool gtable_clean = false;
     // Small appends are STAGED: rows of appends below 256 KB (VecStore::add_vector is one row per call, src/vec.rs:357-371)
     // collect in pinned host memory and go to the GPU together — when 4 MB are full, and before anything looks at the rows
     // (queries, reads, columns, other kinds of append).  A single-row append costs a memcpy instead of a copy + a kernel + a
@@ -643,6 +653,20 @@ int compose_row_mask(ott_store* s, const ott_query_desc* d, const uint64_t** d_m
 int multi_query_ids(ott_store* ms, const ott_query_desc* d, const std::vector<uint64_t>& ids, ott_hit* out, uint64_t cap, uint64_t* n_out,
                     uint64_t* n_per_query, ott_stats* stats);
 int multi_score_rows(ott_store* ms, const float* queries, uint32_t nq, uint32_t metric, const uint64_t* ids, uint64_t n_ids, float* out_scores);
+// Grouped search (ott_group.hip).  group_grow: the rows were reallocated to ncap slots (realloc_store keeps the ids that are there);
+// group_drop: the ids go.  make_run_plan (ott_api.hip): chunk mask -> runs of surviving chunks, as every query builds them.
+// sort_group_pairs (ott_sort.hip): the n (key, query) pairs a grouped query compacted into (l_keysA, l_qA) through the radix sort,
+// grouped by query and best first; lists[q] = the first k of query q's pairs as hits.
+int group_grow(ott_store* s, uint64_t ncap);
+int group_ids_of_hits(ott_store* s, const ott_hit* hits, uint64_t n, uint32_t* out);  // the groups of hits of this store: a gather from the resident ids
+void group_drop(ott_store* s);
+void make_run_plan(const ott_store* s, const uint64_t* chunk_mask, RunPlan& pl);
+int sort_group_pairs(ott_store* s, uint64_t n, uint32_t nq, bool take_max, uint64_t k, std::vector<std::vector<ott_hit>>& lists);
+int ensure_group_pairs(ott_store* s, uint64_t cap);  // the pair arrays for up to `cap` pairs
+// ott_multi.hip: grouped search on a multi-GPU store
+int multi_set_groups(ott_store* ms, const uint32_t* gid_host, uint64_t n, uint32_t n_groups);
+int multi_clear_groups(ott_store* ms);
+int multi_query_groups(ott_store* ms, const ott_query_desc* d, ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats);
 // ott_ties.hip is written against this: where the candidate lists of a store come from.  `run`: one plain query over what `d`
 // selects with take count k, candidates ranked (score, visit order: tie_sh = 3), `flat` = every passing score ranks the same
 // (EXACT path); host vectors, PER_QUERY lists concatenated in query order with their counts in `per`.  `run_chunk`: the same

@@ -160,6 +160,7 @@ int run_on_shards(ott_store* ms, const std::function<int(size_t)>& fn) {
 // ---- layout -----------------------------------------------------------------------------------------------------------------
 
 bool any_columns(const ott_store* ms) {
+    if (ms->n_groups) return true;  // group ids count as a resident column (ott_group.hip): the rows stay where they are
     for (ott_store* s : ms->multi->shards)
         if (!s->columns.empty()) return true;
     return false;
@@ -1337,6 +1338,141 @@ int multi_score_rows(ott_store* ms, const float* queries, uint32_t nq, uint32_t 
         if ((rc = ott_store_score_rows(sh, queries, nq, metric, local.data(), local.size(), part.data()))) return rc;
         for (uint32_t q = 0; q < nq; q++)
             for (size_t i = 0; i < local.size(); i++) out_scores[(size_t)q * n_ids + at[i]] = part[(size_t)q * local.size() + i];
+    }
+    return OTT_OK;
+}
+
+// ---- grouped search (ott_group.hip) -------------------------------------------------------------------------------------------------
+// Group ids are GLOBAL and routed by row range, like write_rows: every shard holds the ids of its rows over the same n_groups; the
+// front keeps only their count and the rows they cover.  From here on the rows stay where they are (any_columns), until clear_groups.
+namespace {
+// every shard's ids and the front's counts go: the state a store is in before its first set_groups (the caller holds it exclusively)
+int drop_all_groups(ott_store* ms) {
+    int rc = OTT_OK;
+    for (ott_store* sh : ms->multi->shards) {
+        const int r = ott_store_clear_groups(sh);
+        if (r && !rc) rc = r;
+    }
+    ms->n_groups = 0;
+    ms->gid_n = 0;
+    return rc;
+}
+}  // namespace
+
+// A call that fails after its argument checks leaves the store WITHOUT groups (front and every shard alike), never half set.
+int multi_set_groups(ott_store* ms, const uint32_t* gid_host, uint64_t n, uint32_t n_groups) {
+    ott::host::ExclusiveLock wr(ms->rw);
+    ott_multi* m = ms->multi;
+    int rc;
+    if (m->layout_dirty) {  // staged rows go to their GPUs; last chance to balance: group ids pin the rows
+        // a second set_groups replaces the first: the old ids go first, on the front AND the shards, so that they neither hold the
+        // rows back nor outlive a move that fails
+        if ((rc = drop_all_groups(ms))) return rc;
+        if ((rc = ensure_layout(ms, false))) return rc;
+        m->layout_dirty = false;
+    }
+    if (n != ms->n) return fail(OTT_ERR_INVALID, "ott_store_set_groups: the store's length changed during the call");
+    for (size_t g = 0; g < m->shards.size(); g++) {
+        ott_store* sh = m->shards[g];
+        const uint64_t s0 = start_of(ms, g), n_g = store_rows(sh);
+        if ((rc = n_g ? ott_store_set_groups(sh, gid_host + s0, n_g, n_groups) : ott_store_clear_groups(sh))) {
+            const std::string msg = ott_last_error();
+            (void)drop_all_groups(ms);
+            return fail(rc, msg);
+        }
+    }
+    ms->n_groups = n ? n_groups : 0;
+    ms->gid_n = n;
+    return OTT_OK;
+}
+
+int multi_clear_groups(ott_store* ms) {
+    ott::host::ExclusiveLock wr(ms->rw);
+    const int rc = drop_all_groups(ms);
+    ms->multi->layout_dirty.store(true, std::memory_order_release);  // the rows may move again: the next query looks at the balance
+    return rc;
+}
+
+// Every shard runs ott_query_groups over its rows (masks cut to its range, as for any query) and returns its hits together with
+// their group ids (group_ids_of_hits: a gather of at most nq x k_eff values from its resident ids); the host concatenates the
+// shards' lists, orders them by the canonical key, keeps each group's first hit and cuts at k.  A group in the global top-k is in
+// its own shard's top-k (fewer than k groups beat it anywhere), so shard lists of k_eff suffice.  While one shard holds every row
+// the query is that shard's own.
+int multi_query_groups(ott_store* ms, const ott_query_desc* d, ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats) {
+    ott_multi* m = ms->multi;
+    const uint64_t t0 = now_ns();
+    ott::host::SharedLock rd;
+    int rc = lock_clean(ms, rd);
+    if (rc) return rc;
+    if (ms->n_groups == 0) return fail(OTT_ERR_INVALID, "ott_query_groups: no group ids are set (ott_store_set_groups)");
+    if (ms->gid_n != ms->n)
+        return fail(OTT_ERR_INVALID, "ott_query_groups: the group ids cover " + std::to_string(ms->gid_n) + " rows, the store holds " + std::to_string(ms->n) +
+                                         " (rows were appended since ott_store_set_groups: set them again)");
+    const uint32_t nq = d->nq;
+    const uint64_t k_eff = d->k < ms->n_groups ? d->k : ms->n_groups;
+    if (cap < k_eff * nq) return fail(OTT_ERR_INVALID, "ott_query_groups: output capacity is smaller than nq * min(k, n_groups)");
+    if (!out && cap) return fail(OTT_ERR_INVALID, "ott_query_groups: out is NULL");
+    if (k_eff == 0 || ms->n == 0) return OTT_OK;
+    for (ott_store* sh : m->shards)
+        if (store_rows(sh) == ms->n) return ott_query_groups(sh, d, out, cap, n_out, n_per_query, stats);
+    const size_t G = m->shards.size();
+    std::vector<ShardSlice> sl;
+    {
+        MultiCall mc(ms);  // (only for its slicing of the masks; the contexts go back before the shards take their own)
+        mc.slice(*d, k_eff, sl);
+    }
+    std::vector<std::vector<ott_hit>> part(G);
+    std::vector<std::vector<uint32_t>> part_gid(G);
+    std::vector<std::vector<uint64_t>> per(G, std::vector<uint64_t>(nq, 0));
+    std::vector<ott_stats> sst(G);
+    rc = run_on_shards(ms, [&](size_t g) -> int {
+        memset(&sst[g], 0, sizeof(ott_stats));
+        if (sl[g].idle) return OTT_OK;
+        part[g].resize((size_t)(k_eff * nq));
+        uint64_t n_g = 0;
+        int r = ott_query_groups(m->shards[g], &sl[g].d, part[g].data(), part[g].size(), &n_g, per[g].data(), stats ? &sst[g] : nullptr);
+        if (r) return r;
+        part[g].resize((size_t)n_g);
+        part_gid[g].resize((size_t)n_g);
+        return group_ids_of_hits(m->shards[g], part[g].data(), n_g, part_gid[g].data());
+    });
+    if (rc) return rc;
+    const CanonLess less{d->take == OTT_TAKE_MAX, 0, ms->base_offset};
+    struct Tagged {
+        ott_hit h;
+        uint32_t grp;
+    };
+    std::vector<uint8_t> seen(ms->n_groups, 0);
+    std::vector<size_t> at(G, 0);
+    std::vector<Tagged> cat;
+    uint64_t total = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        cat.clear();
+        for (size_t g = 0; g < G; g++) {
+            for (size_t i = at[g]; i < at[g] + (size_t)per[g][q]; i++) cat.push_back(Tagged{part[g][i], part_gid[g][i]});
+            at[g] += (size_t)per[g][q];
+        }
+        std::sort(cat.begin(), cat.end(), [&less](const Tagged& a, const Tagged& b) { return less(a.h, b.h); });
+        uint64_t kept = 0;
+        for (const Tagged& t : cat) {
+            if (kept == k_eff) break;
+            if (t.grp >= ms->n_groups) return fail(OTT_ERR_INVALID, "multi-GPU store: internal error (a shard returned a group id out of range)");
+            if (seen[t.grp]) continue;
+            seen[t.grp] = 1;
+            out[total + kept++] = t.h;
+        }
+        for (const Tagged& t : cat)
+            if (t.grp < ms->n_groups) seen[t.grp] = 0;
+        if (n_per_query) n_per_query[q] = kept;
+        total += kept;
+    }
+    if (n_out) *n_out = total;
+    if (stats) {
+        ott_stats st;
+        memset(&st, 0, sizeof(st));
+        for (size_t g = 0; g < G; g++) MultiCall::add_stats(st, sst[g]);
+        st.total_ns = now_ns() - t0;
+        *stats = st;
     }
     return OTT_OK;
 }

@@ -1050,4 +1050,77 @@ int run_large_k(ott_store* s, const float* queries, uint32_t nq, const ott_query
     return OTT_OK;
 }
 
+// Grouped search above the register lists (ott_group.hip: k_eff > 512, which is what a plan without take() gives).  The compact
+// kernel left the non-empty table slots of every query as (key, query) pairs in (l_keysA, l_qA), in no order; this is the sort
+// path's own last step on them — the same radix sort, plan of a per-query result (key descending, then the query), the groups'
+// extents without atomics, hits_from_sorted*.  Canonical order only (a grouped query has no other).
+int ensure_group_pairs(ott_store* s, uint64_t cap) {
+    int rc;
+    if ((rc = s->l_keysA.ensure(cap * 8))) return rc;
+    if ((rc = s->l_keysB.ensure(cap * 8))) return rc;
+    if ((rc = s->l_qA.ensure(cap * 4))) return rc;
+    if ((rc = s->l_qB.ensure(cap * 4))) return rc;
+    return s->l_tmp.ensure(rs_tmp_bytes(cap));
+}
+
+int sort_group_pairs(ott_store* s, uint64_t n, uint32_t nq, bool take_max, uint64_t k, std::vector<std::vector<ott_hit>>& lists) {
+    int rc;
+    lists.assign(nq, {});
+    if (n == 0) return OTT_OK;
+    uint64_t* kA = (uint64_t*)s->l_keysA.p;
+    uint64_t* kB = (uint64_t*)s->l_keysB.p;
+    uint32_t* qA = (uint32_t*)s->l_qA.p;
+    uint32_t* qB = (uint32_t*)s->l_qB.p;
+    uint32_t qbits = 0, rbits = 1;
+    while (nq > 1 && qbits < 32 && ((uint64_t)(nq - 1) >> qbits) != 0) qbits++;
+    while (rbits < 32 && ((s->n - 1) >> rbits) != 0) rbits++;
+    RsPlan plan;
+    memset(&plan, 0, sizeof(plan));
+    rs_add_digits(plan, 0, 0, rbits, true);   // ~row: the lower row first among equal scores
+    rs_add_digits(plan, 0, 32, 64, true);     // the score ordinal
+    rs_add_digits(plan, 1, 0, qbits, false);  // grouped by query
+    bool in_A = true;
+    if ((rc = radix_sort_plan(s->stream, kA, qA, kB, qB, n, plan, s->l_tmp.p, s->n_cu, &in_A))) return rc;
+    if (!in_A) {
+        std::swap(kA, kB);
+        std::swap(qA, qB);
+    }
+    // extents of the query groups
+    std::vector<uint32_t> start(nq, 0u);
+    if (nq > 1) {
+        if ((rc = s->l_hist.ensure((size_t)nq * 4))) return rc;
+        OTT_HIP(hipMemsetAsync(s->l_hist.p, 0xFF, (size_t)nq * 4, s->stream));
+        hipLaunchKernelGGL(group_start_kernel, dim3((uint32_t)s->n_cu * 4), dim3(256), 0, s->stream, (const uint32_t*)qA, n, (uint32_t*)s->l_hist.p);
+        OTT_HIP(hipGetLastError());
+        OTT_HIP(hipMemcpyAsync(start.data(), s->l_hist.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
+        OTT_HIP(hipStreamSynchronize(s->stream));
+    }
+    std::vector<uint64_t> first(nq, 0), count(nq, 0);
+    uint64_t next = n, total = 0;
+    for (uint32_t q = nq; q-- > 0;) {
+        if (start[q] == 0xFFFFFFFFu) continue;
+        first[q] = start[q];
+        count[q] = std::min<uint64_t>(next - start[q], k);
+        next = start[q];
+        total += count[q];
+    }
+    if ((rc = s->d_hits.ensure((size_t)(total ? total : 1) * sizeof(ott_hit)))) return rc;
+    uint64_t o = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        if (!count[q]) continue;
+        hipLaunchKernelGGL(hits_from_sorted_kernel, dim3((uint32_t)((count[q] + 255) / 256)), dim3(256), 0, s->stream, (const uint64_t*)kA, (const uint32_t*)qA, first[q],
+                           count[q], take_max ? 1u : 0u, s->base_offset, (ott_hit*)s->d_hits.p + o);
+        OTT_HIP(hipGetLastError());
+        o += count[q];
+    }
+    o = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        lists[q].resize((size_t)count[q]);
+        if (count[q]) OTT_HIP(hipMemcpyAsync(lists[q].data(), (ott_hit*)s->d_hits.p + o, (size_t)count[q] * sizeof(ott_hit), hipMemcpyDeviceToHost, s->stream));
+        o += count[q];
+    }
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    return OTT_OK;
+}
+
 }  // namespace ott

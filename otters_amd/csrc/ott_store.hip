@@ -477,6 +477,8 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
     {
         const int rcl = live_grow(s, ncap);  // the live mask of deleted rows (ott_tomb.hip) is sized with the row capacity
         if (rcl) return rcl;
+        const int rcg = group_grow(s, ncap);  // the group ids of a grouped store (ott_group.hip) likewise: the ids that are there are kept
+        if (rcg) return rcg;
     }
     float* nrows = nullptr;
     float* ninv = nullptr;
@@ -567,6 +569,7 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
     if (s->d_flag) (void)hipFree(s->d_flag);
     if (s->d_sketch) (void)hipFree(s->d_sketch);
     live_drop(s);  // (the rows are other rows now: whoever moved them loads their live bits afterwards, live_load)
+    group_drop(s); // (a store with group ids moves no rows: nothing to drop unless a caller forced the move)
     s->d_rows = rows;
     s->d_inv = inv;
     s->d_flag = flag;
@@ -736,6 +739,9 @@ static void alias_corpus(ott_store* w, const ott_store* s) {
     w->evalmask_bits = s->evalmask_bits;
     w->d_live = s->d_live;
     w->n_dead = s->n_dead;
+    w->d_gid = s->d_gid;
+    w->gid_n = s->gid_n;
+    w->n_groups = s->n_groups;
 }
 
 // rows [first, first + n) -> batch image: one thread per (row, 4 floats)
@@ -1343,8 +1349,10 @@ int ott_store_destroy(ott_store* s) {
         s->d_evalmask.p = nullptr;
         s->d_evalmask.cap = 0;
         s->d_live = nullptr;
+        s->d_gid = nullptr;
     }
     if (s->d_live) (void)hipFree(s->d_live);
+    if (s->d_gid) (void)hipFree(s->d_gid);
     if (s->d_rows) (void)hipFree(s->d_rows);
     if (s->d_inv) (void)hipFree(s->d_inv);
     if (s->d_flag) (void)hipFree(s->d_flag);
@@ -1358,7 +1366,7 @@ int ott_store_destroy(ott_store* s) {
         if (s->d_img8_rel) (void)hipFree(s->d_img8_rel);
     }
     for (ott::DevBuf* b : {&s->d_queries, &s->d_qinv, &s->d_rowmask, &s->d_runs, &s->d_prefix, &s->d_lists, &s->d_lists2, &s->d_hits,
-                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_gather, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
+                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_gather, &s->d_gtable, &s->d_gctl, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
                            &s->m_tau, &s->m_cntA, &s->m_cntB, &s->m_candA, &s->m_candB, &s->m_over, &s->m_out, &s->m_outcnt,
                            &s->m_uncert, &s->m_prefix, &s->x_send, &s->x_recv, &s->l_keysA, &s->l_keysB, &s->l_qA, &s->l_qB, &s->l_tmp, &s->l_cursor, &s->l_hist, &s->l_gate, &s->l_ctl})
         b->release();

@@ -277,6 +277,8 @@ int ott_store_compact(ott_store* s, uint64_t* out_new_index) {
     std::lock_guard<std::mutex> g(s->mu);
     if (!s->columns.empty())
         return fail(OTT_ERR_UNSUPPORTED, "ott_store_compact: rows cannot move once metadata columns are resident");
+    if (s->d_gid)  // group ids count as a resident column (ott_group.hip)
+        return fail(OTT_ERR_UNSUPPORTED, "ott_store_compact: rows cannot move while group ids are set (ott_store_clear_groups first, set them again afterwards)");
     int rc = store_flush_locked(s);
     if (rc) return rc;
     const uint64_t n = s->n;

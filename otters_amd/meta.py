@@ -396,6 +396,8 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
         self._build_stats: Optional[MetaBuildStats] = None
         self._dev_cols: Dict[str, int] = {}
         self._str_codes: Dict[str, tuple] = {}
+        self._group_ids: Dict[str, tuple] = {}   # distinct_by: column name -> (dense uint32 ids, n_groups), built once
+        self._groups_on_device: Optional[tuple] = None  # (column, the vector store's group generation) of the ids this store uploaded last
         self._mask_lock = threading.RLock()  # build_row_mask_device + the query that reads the mask: one critical section
 
     # -- constructors --------------------------------------------------------------------------------
@@ -616,6 +618,40 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
             self._str_codes[name] = ({u: i for i, u in enumerate(uniq.tolist())}, inv.astype(np.int32))
         return self._str_codes[name]
 
+    def _distinct_ids(self, name: str):
+        """Dense group ids of a column for distinct_by, built once per column name: (uint32[n_rows], n_groups).  Int32, Int64
+        and DateTime columns group by value, String columns through _string_codes; every NULL row is a group of its own (a
+        fresh id behind the values' ids).  Pure host logic."""
+        if name not in self._group_ids:
+            c = self._columns.get(name)
+            if c is None:
+                raise OttersError(f"distinct_by: unknown column '{name}'")
+            dt = c.dtype()
+            if dt in (DataType.Float32, DataType.Float64):
+                raise OttersError(f"distinct_by: column '{name}' is a Float column; group by an Int32, Int64, DateTime or String column")
+            vals = self._string_codes(name)[1] if dt == DataType.String else np.asarray(c.values())
+            nulls = np.asarray(c.null_mask(), dtype=bool)
+            ids = np.zeros(self._n_rows, dtype=np.int64)
+            live = ~nulls
+            n_val = 0
+            if live.any():
+                uniq, inv = np.unique(np.asarray(vals)[live], return_inverse=True)
+                ids[live] = inv.reshape(-1)
+                n_val = int(uniq.size)
+            n_null = int(nulls.sum())
+            ids[nulls] = n_val + np.arange(n_null, dtype=np.int64)
+            self._group_ids[name] = (np.ascontiguousarray(ids.astype(np.uint32)), n_val + n_null)
+        return self._group_ids[name]
+
+    def _ensure_groups(self, name: str) -> int:
+        """The vector store holds the ids of column `name`: uploaded once per column name and reused while they are still what
+        the store holds (its group generation tells: a set_groups / clear_groups on the VecStore in between, or another
+        column's distinct_by, makes this upload them again)."""
+        ids, n_groups = self._distinct_ids(name)
+        if self._groups_on_device != (name, self._store._groups_gen):
+            self._groups_on_device = (name, self._store._set_dense_groups(ids, n_groups))
+        return n_groups
+
     def _device_column(self, name: str) -> int:
         if name not in self._dev_cols:
             c = self._columns[name]
@@ -699,6 +735,7 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         self.take_count: Optional[int] = None
         self._path = Path.Auto
         self._row_ids = None
+        self._distinct: Optional[str] = None
 
     def meta_filter(self, expr: Expr) -> "MetaQueryPlan":  # src/meta.rs:605-616 (error deferred to collect)
         try:
@@ -727,13 +764,28 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         self._row_ids = ids
         return self
 
+    def distinct_by(self, name: str) -> "MetaQueryPlan":
+        """One best row per distinct value of column `name`, top-k over the values (VecQueryPlan.one_per_group): Int32, Int64
+        and DateTime columns by value, String columns by string; every NULL row is a group of its own.  meta_filter, vec_filter
+        and deleted rows apply before grouping; the default take becomes the number of groups.  Float columns, unknown
+        columns, a batch of queries and with_row_ids raise OttersError at collect()."""
+        self._distinct = str(name)
+        return self
+
     def resolve(self):
         """Host-side part of collect (src/meta.rs:632-669): k / take defaults, zonemap prune.
         Returns (ResolvedQuery, chunk_mask or None, compiled filter or None)."""
         if self.meta_error is not None:
             raise OttersError(self.meta_error)
         st = self.store
-        k = self.take_count if self.take_count is not None else st._n_rows  # src/meta.rs:638-640
+        n_groups = 0
+        if self._distinct is not None:
+            if len(self.queries) > 1:
+                raise OttersError("distinct_by takes one query, not a batch (a merged list over several queries would need one winner per group across queries)")
+            if self._row_ids is not None:
+                raise OttersError("distinct_by cannot be combined with with_row_ids in this version")
+            n_groups = st._distinct_ids(self._distinct)[1]
+        k = self.take_count if self.take_count is not None else (n_groups if self._distinct is not None else st._n_rows)  # src/meta.rs:638-640
         take = self.take_type if self.take_type is not None else (infer_default_take_type(self.metric))
         for q in self.queries:
             if st._n_rows and q.size != st._dim:
@@ -742,7 +794,7 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         fc, ft = (0, 0.0) if self._vec_filter is None else (int(self._vec_filter[1]), self._vec_filter[0])
         q = np.ascontiguousarray(np.stack(self.queries)) if self.queries else np.zeros((0, st._dim), np.float32)
         rq = ResolvedQuery(queries=q, metric=int(self.metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft,
-                           row_mask=None, mode=int(Mode.Merged), path=int(self._path))
+                           row_mask=None, mode=int(Mode.Merged), path=int(self._path), grouped=self._distinct is not None)
         if self._row_ids is not None:
             ids = as_row_ids(self._row_ids)
             if chunk_mask is not None and ids.size:  # (an id past the store's end stays: the library names it)
@@ -769,6 +821,8 @@ class MetaQueryPlan:  # src/meta.rs:579-830
             # querying with it are one critical section per MetaStore, so two threads filtering one store cannot score with
             # each other's mask (the reference's MetaStore is !Sync, src/meta.rs:54: there the compiler forbids the race)
             with st._mask_lock:
+                if self._distinct is not None:
+                    st._ensure_groups(self._distinct)
                 if compiled is not None and st.row_mask_is_all_true(compiled, chunk_mask):
                     pass  # the zone statistics already decide every row of every surviving chunk: no row mask needed
                 elif compiled is not None:

@@ -100,6 +100,7 @@ class ResolvedQuery:
     mode: int = Mode.Merged
     path: int = Path.Auto
     row_ids: Optional[np.ndarray] = None  # uint64[n_ids] (with_row_ids): only these rows are ranked, or None
+    grouped: bool = False                 # one_per_group: one best hit per group, top-k over the groups (ott_query_groups)
 
 
 def as_row_ids(ids) -> np.ndarray:
@@ -123,6 +124,22 @@ def as_row_ids(ids) -> np.ndarray:
     return np.ascontiguousarray(a.astype(np.uint64))
 
 
+def dense_group_ids(ids):
+    """Group labels -> (uint32[n] dense ids, n_groups): any integer array; equal labels share an id, ids are 0 .. n_groups - 1 in
+    the labels' sorted order (np.unique).  Pure host logic."""
+    a = np.asarray(ids)
+    if a.ndim != 1:
+        a = a.ravel()
+    if a.size == 0:
+        return np.zeros(0, dtype=np.uint32), 0
+    if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+        raise OttersError(f"group ids must be integers, not {a.dtype}")
+    uniq, inv = np.unique(a, return_inverse=True)
+    if uniq.size >= 2 ** 32:
+        raise OttersError("more than 2^32 - 1 groups")
+    return np.ascontiguousarray(inv.reshape(-1).astype(np.uint32)), int(uniq.size)
+
+
 def infer_default_take_type(metric: Metric) -> TakeType:  # src/vec.rs:92-98
     return TakeType.Min if metric in (Metric.Euclidean, Metric.Manhattan) else TakeType.Max
 
@@ -142,6 +159,7 @@ class VecQueryPlan:
         self.row_ids = None  # with_row_ids: the list as the caller gave it (checked at validate())
         self._mode = Mode.Merged
         self._path = Path.Auto
+        self._grouped = False
 
     @staticmethod
     def new() -> "VecQueryPlan":
@@ -211,6 +229,15 @@ class VecQueryPlan:
             self.row_ids = ids
         return self
 
+    def one_per_group(self) -> "VecQueryPlan":
+        """One best hit per group, top-k over the groups (VecStore.set_groups; ott_query_groups): the hits of the same plan with
+        the default take after dropping every hit whose group occurred earlier, cut at take(k); the default take becomes
+        group_count().  Row mask, deleted rows and filter apply before grouping; ties are always in the canonical order.  A
+        batch needs per_query().  Not together with with_row_ids in this version."""
+        if self.error is None:
+            self._grouped = True
+        return self
+
     # -- execution -----------------------------------------------------------------------------
     def validate(self) -> None:  # src/vec.rs:170-203
         if self.error is not None:
@@ -225,6 +252,8 @@ class VecQueryPlan:
             raise OttersError("No queries provided")
         if self.row_ids is not None:
             as_row_ids(self.row_ids)
+        if self._grouped and self.row_ids is not None:
+            raise OttersError("one_per_group cannot be combined with with_row_ids in this version; use with_row_mask")
         dim = self.vector_store.dim
         if isinstance(self.query_vectors, np.ndarray):  # a matrix: every row has the same length
             if self.query_vectors.shape[1] != dim:
@@ -242,12 +271,12 @@ class VecQueryPlan:
             queries = self.query_vectors
         else:
             queries = np.ascontiguousarray(np.stack(self.query_vectors).astype(np.float32, copy=False))
-        k = self.take_count if self.take_count is not None else store.len()  # src/vec.rs:213
+        k = self.take_count if self.take_count is not None else (store.group_count() if self._grouped else store.len())  # src/vec.rs:213
         take = self.take_type if self.take_type is not None else TakeType.Max  # src/vec.rs:214
         fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
         return ResolvedQuery(queries=queries, metric=int(self.search_metric), take=int(take), k=max(int(k), 0),
                              filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, mode=int(self._mode), path=int(self._path),
-                             row_ids=None if self.row_ids is None else as_row_ids(self.row_ids))
+                             row_ids=None if self.row_ids is None else as_row_ids(self.row_ids), grouped=self._grouped)
 
     def collect(self):  # src/vec.rs:205-311
         hits, counts = self.collect_arrays()
@@ -297,6 +326,8 @@ class VecStore:
         self._base_offset = 0
         self._reduce = None
         self._options: dict = {}
+        self._n_groups = 0
+        self._groups_gen = 0  # changes with every set_groups / clear_groups
         self.last_stats: Optional[dict] = None
         # OTTERS_TIE_ORDER=reference: this mirror then returns, like the Rust patch and the C++ mirror do by default, the
         # reference's own outcome at exact score ties (one TopKCollector over the store); default here: the canonical order
@@ -433,6 +464,35 @@ class VecStore:
         self._n = int(N.lib().ott_store_len(self._handle()))
         return new_index.view(np.int64)  # (UINT64_MAX reads as -1)
 
+    # -- grouped search (include/otters_hip.h: ott_query_groups) ---------------------------------------
+    def set_groups(self, ids) -> None:
+        """One group label per row (any integer array of length len()); the host makes them dense (dense_group_ids) and the
+        store keeps them in HBM at 4 B per row.  A second call replaces the first; rows appended afterwards need a new call.
+        While groups are set, compact() is refused and a multi-GPU store moves no rows."""
+        a = np.asarray(ids)
+        if a.size != self._n:
+            raise OttersError(f"{a.size} group ids for a store of {self._n} rows")
+        self._set_dense_groups(*dense_group_ids(a))
+
+    def _set_dense_groups(self, dense: np.ndarray, n_groups: int) -> int:
+        """uint32 ids that are dense already (MetaStore.distinct_by builds them per column).  Returns the store's group
+        generation: it changes with every set_groups / clear_groups, so a caller that remembers it knows whether the ids
+        it uploaded are still the ones the store holds."""
+        N.check(N.lib().ott_store_set_groups(self._handle(), N.ptr(dense), dense.size, n_groups))
+        self._n_groups = n_groups
+        self._groups_gen += 1
+        return self._groups_gen
+
+    def clear_groups(self) -> None:
+        if self._h is not None:
+            N.check(N.lib().ott_store_clear_groups(self._h))
+        self._n_groups = 0
+        self._groups_gen += 1
+
+    def group_count(self) -> int:
+        """Number of groups set_groups left (0 = none)."""
+        return self._n_groups
+
     def shards(self):
         """[(device, first_row, n_rows)] of the store's shards (one entry for a single-GPU store)."""
         h = self._handle()
@@ -537,6 +597,8 @@ class VecStore:
         pool = rows if perq else rows * nq
         k_eff = min(rq.k, pool)
         cap = max(k_eff * (nq if perq else 1), 1)
+        if rq.grouped:  # at most one hit per group and query
+            cap = max(min(rq.k, self._n_groups) * nq, 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)  # ott_query writes n_out entries; only those are returned
         d = N.QueryDesc()
         d.queries = rq.queries.ctypes.data
@@ -558,7 +620,9 @@ class VecStore:
         n_out = C.c_uint64(0)
         per = (C.c_uint64 * nq)()
         st = N.Stats()
-        if ids is None:
+        if rq.grouped:
+            N.check(N.lib().ott_query_groups(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        elif ids is None:
             N.check(N.lib().ott_query(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         else:
             N.check(N.lib().ott_query_ids(self._handle(), C.byref(d), N.ptr(ids), ids.size, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
