@@ -229,8 +229,8 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
     // Pruned sweep (store option exact_prune): one query, merged, cosine / dot, the streaming kernel.  A seed of a
     // tenth of the rows is scored in full and merged; its k-th best gates the second launch over the rest, which skips the last
     // stages (from c, 7/8 of them) of every row whose score bound misses it.  Automatic from 2^20 rows and 8 stages (dim >= 225).
-    // A store that keeps a tail sign sketch for every row (option exact_sketch) takes the sketch form: the checkpoint is the sketch's
-    // first stage, 3/4 of the stages.
+    // A store that keeps a tail sketch for every row (option exact_sketch) takes the sketch form in the store's own width (option
+    // exact_sketch_bits): the checkpoint is the sketch's first stage, 3/8 of the stages at three bits per dim, 3/4 at one.
     uint32_t prune_c = 0;
     bool prune_sk = false;
     RunPlan plA, plB;
@@ -240,7 +240,8 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
         const uint32_t nst = (s->ld + 31) / 32;
         uint32_t c = nst * 7 / 8;
         while (c > 0 && c * 32 > s->dim - s->dim % 8) c--;  // the prefix holds whole chunks of eight only (no remainder term yet)
-        if (s->opt.exact_sketch != 0 && s->d_sketch != nullptr && s->sk_n >= s->n && s->sk_words <= OTT_SKETCH_MAX_WORDS) {
+        if (s->opt.exact_sketch != 0 && s->d_sketch != nullptr && s->sk_n >= s->n &&
+            s->sk_words <= (s->sk_bits == 3 ? OTT_SKETCH_MAX_WORDS : OTT_SKETCH1_MAX_WORDS)) {
             const uint32_t cs = s->sk_stage0;
             if (cs >= 1 && cs < nst && cs * 32 <= s->dim - s->dim % 8) {
                 c = cs;
@@ -350,6 +351,7 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
             pb.prune_sketch = s->d_sketch;
             pb.sk_pitch = s->sk_pitch;
             pb.sk_stage0 = s->sk_stage0;
+            pb.sk_bits = s->sk_bits;
             pb.prune_q1 = prune_q1;
         }
         if ((rc = launch_exact(s, pb, 1, E, gridB))) return rc;

@@ -41,9 +41,13 @@ constexpr int EXACT_SMEM_DUMP = EXACT_SMEM + WAVES * DUMP_QCAP * 12;
 constexpr int PQ_CAP = 128;
 constexpr int PQ_WORDS = 10;
 constexpr int EXACT_SMEM_PRUNE = EXACT_SMEM + WAVES * PQ_CAP * PQ_WORDS * 4;  // 52 KB: two workgroups per CU
-// sketch form of the pruned sweep (SK): the sign words of a row's sketch line a lane keeps in registers — with a and rho at most
-// three 16-B loads (OTT_SKETCH_MAX_WORDS, ott_internal.h)
-constexpr int SK_MAXW = (int)OTT_SKETCH_MAX_WORDS;
+// sketch form of the pruned sweep (SK = 1): the sign words of a row's sketch line a lane keeps in registers — with a and rho at most
+// three 16-B loads (OTT_SKETCH1_MAX_WORDS, ott_internal.h)
+constexpr int SK_MAXW = (int)OTT_SKETCH1_MAX_WORDS;
+// three-bit form (SK = 3): the stages a line can hold codes for (three words each), and its 16-B pieces beyond the eight that
+// arrive in the row staging registers (OTT_SKETCH_MAX_WORDS)
+constexpr int SK3_MAXST = (int)OTT_SKETCH_MAX_WORDS / 3;
+constexpr int SK3_XP = ((int)OTT_SKETCH_MAX_WORDS + 2 + 3) / 4 - 8;
 // Workgroups per CU of the persistent grid.  TWO since round 6 (8 waves per CU, 64 KB of row stages in flight per CU, 512 block lists for
 // the merge): measured against 3, 4 (rounds 2-5), 5 and 8 on every instantiation — 1M x 128 dot top-10 89.4 + 11.8 -> 86.3 + 9.7 us
 // (scoring + merge), 2M / 4M x 128 5 % / 3 % faster, 3M x 768 2 %, the 10M x 768 headline 4403 -> 4374 us, four queries per pass 4799
@@ -101,11 +105,16 @@ __device__ __forceinline__ void exact_glds16(const char* sbase, uint32_t voff, u
 // fetches its row's line (lane = row: 64 contiguous lines) with the inverse norm, at the checkpoint forms q_t . s from the sign
 // words and the query's tail (scalar loads; one shift, one and-or and one fma per dim) and asks prune_score_bound_sketch; no prefix
 // sum of squares is kept.  The queue and the finishing of survivors are the same code.
-template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false, bool SK = false>
+// SK = 3: the three-bit sketch of the last 5/8 of the stages, so the checkpoint is at 3/8 of them.  A line is up to fourteen 16-B
+// pieces, too many to hold across the stages: the lane fetches them while the LAST prefix stage is consumed — no row stage is in
+// flight then, so the first eight pieces land in the row staging registers, the others are asked for behind the loop and arrive
+// while the first are decoded (lane = row: the 64 lines of a tile are one contiguous block).  Per dim: a signed field extract,
+// kappa = 2 code + 1, a convert and one fma into D; then prune_score_bound_sketchb with kmax = 7.
+template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false, int SK = 0>
 __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) {
     static_assert(!I8 || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL), "the int8 sweep takes one query, cosine / dot, merged");
     static_assert(!PRUNE || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL && !I8), "the pruned sweep takes one query, cosine / dot, merged");
-    static_assert(!SK || PRUNE, "the sketch is the pruned sweep's");
+    static_assert((SK == 0 || PRUNE) && (SK == 0 || SK == 1 || SK == 3), "the sketch is the pruned sweep's: none, one bit or three bits per dim");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -299,8 +308,16 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
         float vsq = 0.0f;  // PRUNE without a sketch: the prefix's sum of squares
         // SK: the row's sketch line [a | rho | sign words], fetched now like the inverse norm (non-temporal: read once per sweep)
         typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-        uint32_t skl[2 + SK_MAXW];
-        if constexpr (SK) {
+        [[maybe_unused]] uint32_t skl[2 + SK_MAXW];
+        // SK = 3: the gate is known before the stages (the wave's list changes only when queued rows are finished): no line is fetched
+        // while it is open
+        [[maybe_unused]] uint32_t gate3 = 0;
+        if constexpr (SK == 3) {
+            gate3 = theta;
+            const uint32_t own = (uint32_t)(tk[0] >> 32);
+            if (own > gate3) gate3 = own;
+        }
+        if constexpr (SK == 1) {
 #pragma unroll
             for (int i = 0; i < 2 + SK_MAXW; i++) skl[i] = 0u;
             skl[1] = 0x7F800000u;  // (rho = +inf: no bound)
@@ -413,7 +430,19 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                         make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
                 }
                 wave_sync();
-                if (s + 1 < s_end) load_stage(s + 1);
+                if (s + 1 < s_end) {
+                    load_stage(s + 1);
+                } else if constexpr (SK == 3) {
+                    // the row's sketch line into the idle staging registers: pieces 0 .. 7, clamped to the line's last piece (a load
+                    // past it would leave the buffer behind the store's last row); lanes past the tile's end read its last row's
+                    if (gate3 != 0) {
+                        const uint64_t lr = row0 + ((uint32_t)lane < cnt ? (uint32_t)lane : cnt - 1);
+                        const v4f* sp = reinterpret_cast<const v4f*>(p.prune_sketch + lr * (uint64_t)p.sk_pitch);
+                        const uint32_t np = p.sk_pitch >> 2;
+#pragma unroll
+                        for (int m = 0; m < 8; m++) R[m] = __builtin_nontemporal_load(sp + ((uint32_t)m < np ? (uint32_t)m : np - 1));
+                    }
+                }
             }
 
             if constexpr (I8) {
@@ -453,7 +482,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                                 acc[q][l] = __fadd_rn(acc[q][l], exact_term<MK>(qv, x[l]));
                             }
                         }
-                        if constexpr (PRUNE && !SK) {
+                        if constexpr (PRUNE && SK == 0) {
 #pragma unroll
                             for (int l = 0; l < 8; l++) vsq = fmaf(x[l], x[l], vsq);
                         }
@@ -486,8 +515,47 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             uint32_t gate = theta;
             const uint32_t own = (uint32_t)(tk[0] >> 32);
             if (own > gate) gate = own;
+            if constexpr (SK == 3) gate = gate3;  // the gate the line was fetched for: the staging registers hold a line only then
             bool keep = valid;
-            if constexpr (SK) {
+            if constexpr (SK == 3) {
+                if (gate != 0) {  // (wave-uniform; the line is in R)
+                    v4f X[SK3_XP];
+#pragma unroll
+                    for (int i = 0; i < SK3_XP; i++) X[i] = R[7];
+                    const uint32_t np = p.sk_pitch >> 2;
+                    if (np > 8) {  // the pieces beyond the eight: they arrive while the first stages are decoded
+                        const uint64_t lr = row0 + ((uint32_t)lane < cnt ? (uint32_t)lane : cnt - 1);
+                        const v4f* sp = reinterpret_cast<const v4f*>(p.prune_sketch + lr * (uint64_t)p.sk_pitch);
+#pragma unroll
+                        for (int i = 0; i < SK3_XP; i++) X[i] = __builtin_nontemporal_load(sp + ((uint32_t)(8 + i) < np ? (uint32_t)(8 + i) : np - 1));
+                    }
+                    auto word = [&](int k) -> uint32_t {  // line word k (a constant once unrolled)
+                        const v4f v = (k >> 2) < 8 ? R[(k >> 2) & 7] : X[((k >> 2) - 8) % SK3_XP];
+                        return __float_as_uint(v[k & 3]);
+                    };
+                    float D = 0.0f;
+#pragma unroll
+                    for (int j = 0; j < SK3_MAXST; j++) {
+                        const uint32_t sj = p.sk_stage0 + (uint32_t)j;
+                        if (sj >= p.prune_stage && sj < nstages) {
+                            const uint32_t w[3] = {word(2 + 3 * j), word(3 + 3 * j), word(4 + 3 * j)};
+#pragma unroll
+                            for (int b = 0; b < 32; b++) {
+                                const int pos = 3 * b, lo = pos & 31;
+                                uint32_t x = w[pos >> 5] >> lo;
+                                if (lo + 3 > 32) x |= w[(pos >> 5) + 1] << (32 - lo);
+                                const int code = (int)(x << 29) >> 29;
+                                D = fmaf((float)(2 * code + 1), Q[sj * KC + b], D);
+                            }
+                        }
+                    }
+                    if (valid) {
+                        const float b = prune_score_bound_sketchb(acc[0], vinv, __uint_as_float(word(0)), __uint_as_float(word(1)), D, 7.0, p.prune_stage * KC,
+                                                                  p.dim, p.prune_qt, p.prune_q1, p.prune_qn, qinv[0], p.metric == OTT_METRIC_COSINE, take_max);
+                        keep = !(b == b && ord_of(b, take_max) < gate);  // (NaN: no bound, the row is finished)
+                    }
+                }
+            } else if constexpr (SK == 1) {
                 if (gate != 0) {  // (wave-uniform)
                     // D = q_t . s in f32: the sign bit of dim 32 s + b moves to bit 31 and makes +-1.0, one fma per dim (exact product)
                     float D = 0.0f;
@@ -1418,7 +1486,7 @@ int exact_grid(const ott_store* s, uint32_t n_tiles) {
 }
 
 // the pruned sweep (p.prune_stage != 0): its queue takes the dynamic LDS past 48 KB
-template <int E, bool BLK, bool SK>
+template <int E, bool BLK, int SK>
 static int launch_prune(ott_store* s, const ExactParams& p, int grid) {
     auto kern = exact_kernel<MK_DOT, 1, E, false, false, false, BLK, false, true, SK>;
     static std::atomic<uint64_t> attr_set{0};
@@ -1435,11 +1503,13 @@ template <int MK, int NQ, int E, bool PERQ>
 static int launch_one(ott_store* s, const ExactParams& p, int grid) {
     if constexpr (MK == MK_DOT && NQ == 1 && !PERQ) {
         if (p.prune_stage != 0) {
-            const bool sk = p.prune_sketch != nullptr;  // the sketch form: the store keeps a tail sign sketch
+            const uint32_t sk = p.prune_sketch != nullptr ? p.sk_bits : 0u;  // the sketch form: the store keeps a tail sketch of 1 or 3 bits per dim
+            if (sk != 0 && sk != 1 && sk != 3) return fail(OTT_ERR_INVALID, "launch_exact: a tail sketch has one or three bits per dim");
             if constexpr (E == 1) {
-                if (p.k > 16) return sk ? launch_prune<1, true, true>(s, p, grid) : launch_prune<1, true, false>(s, p, grid);  // (see BLK)
+                if (p.k > 16)  // (see BLK)
+                    return sk == 3 ? launch_prune<1, true, 3>(s, p, grid) : sk == 1 ? launch_prune<1, true, 1>(s, p, grid) : launch_prune<1, true, 0>(s, p, grid);
             }
-            return sk ? launch_prune<E, (E > 1), true>(s, p, grid) : launch_prune<E, (E > 1), false>(s, p, grid);
+            return sk == 3 ? launch_prune<E, (E > 1), 3>(s, p, grid) : sk == 1 ? launch_prune<E, (E > 1), 1>(s, p, grid) : launch_prune<E, (E > 1), 0>(s, p, grid);
         }
     }
     if (p.prune_stage != 0) return fail(OTT_ERR_INVALID, "launch_exact: the pruned sweep takes one query, cosine / dot, merged");

@@ -73,9 +73,9 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  NINETEEN of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  TWENTY of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, exact_prune, exact_sketch, id_gather, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
@@ -88,6 +88,9 @@ struct Options {
                                   // stages, a mean magnitude and a remainder norm, ~1 % of the row bytes, made when rows are appended): -1 =
                                   // automatic (stores of 8 stages and more, dim >= 225), 0 = never, 1 = always.  A store that keeps one
                                   // stops rows at 3/4 of the stages instead of 7/8
+    int exact_sketch_bits = 3;    // the sketch's form, read when the store makes its first line: 3 = a three-bit code per dim of the last 5/8 of
+                                  // the stages (192 B per row at dim 768, 1/16 of the row bytes; rows stop at 3/8 of the stages), 1 = the sign
+                                  // sketch described above
     int force_fallback = 0;       // TESTS: bit mask of code paths the library otherwise takes only in rare conditions, forced on so that the
                                   // suite and the option fuzz hold them to the oracle: 1 = block lists merged by insertion (merge_kernel: the
                                   // rank merge's own fallback when a plateau overflows its buffer or there are > 4096 lists), 2 = k <= 64
@@ -204,7 +207,8 @@ struct ott_store {
     // norms for the same rows (launch_inv_norms).  sk_n: rows [0, sk_n) hold one — the sweep uses it only when that covers the store
     uint32_t* d_sketch = nullptr;
     uint64_t sk_n = 0;
-    uint32_t sk_words = 0, sk_pitch = 0, sk_stage0 = 0;  // sign words per row, line pitch in words, first sketched stage
+    uint32_t sk_words = 0, sk_pitch = 0, sk_stage0 = 0;  // code words per row, line pitch in words, first sketched stage
+    uint32_t sk_bits = 0;                                // bits per sketched dim of the lines that are there (1 or 3)
     uint8_t* d_flag = nullptr;  // [cap] 1 = row norm is inf / NaN / > 1e18 / tiny but non-zero / underflowed (always re-scored exactly by the MFMA path)
     // Batch-path image of the corpus: every row pre-split into bf16 hi + bf16 lo, per 32-k stage [32 hi | 32 lo] (the same
     // 128 B a stage of f32 takes; row pitch = dim rounded up to 32 floats).  Built lazily by the first batch query, extended
@@ -371,7 +375,7 @@ inline uint64_t store_rows(const ott_store* s) { return s->n + s->pend.count(); 
 int store_flush(ott_store* s);
 int store_flush_locked(ott_store* s);  // the caller holds `rw` exclusively and `mu`
 // ott_store.hip: a shard takes over freshly filled buffers (rows moved between the GPUs of a multi-GPU store)
-int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* sketch, uint64_t n, uint64_t cap);
+int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* sketch, uint32_t sketch_bits, uint64_t n, uint64_t cap);
 
 constexpr size_t OTT_MAX_WORKERS = 15;
 ott_store* ctx_acquire(ott_store* s);  // returns s or a worker, with its `mu` held
@@ -498,7 +502,7 @@ struct ExactParams {
     // sk_stage0 <= prune_stage; prune_q1: an upper bound of the 1-norm of q[prune_stage * 32:].  prune_tails: device counter, += the
     // rows whose tails were finished (both forms)
     uint32_t prune_stage;
-    uint32_t sk_pitch, sk_stage0;
+    uint32_t sk_pitch, sk_stage0, sk_bits;
     const uint64_t* prune_seed;
     const uint32_t* prune_sketch;
     unsigned long long* prune_tails;
@@ -506,9 +510,11 @@ struct ExactParams {
     float qemb[896];  // last: the embedded query (kernel arguments are limited to 4 KB)
 };
 constexpr uint32_t OTT_QEMB_MAX = 896;
-// Sign words of a sketch line that the sketch form's kernel keeps in registers: with a and rho, three 16-B loads.  The embedded
-// query holds at most 28 stages, so a sketch of the last quarter has at most 7; a store with more takes the 7/8 form.
-constexpr uint32_t OTT_SKETCH_MAX_WORDS = 10;
+// Code words of a sketch line that the sketch form's kernel decodes.  The embedded query holds at most 28 stages, so a three-bit
+// sketch of the last 5/8 has at most 18 stages of three words (with a and rho fourteen 16-B pieces), a sign sketch of the last
+// quarter at most 7 words; a store with more takes the 7/8 form.
+constexpr uint32_t OTT_SKETCH_MAX_WORDS = 54;
+constexpr uint32_t OTT_SKETCH1_MAX_WORDS = 10;  // the sign form keeps its words in registers across the stages: three 16-B loads
 static_assert(sizeof(ExactParams) <= 4096, "kernel arguments are limited to 4 KB");
 
 int launch_exact(ott_store* s, const ExactParams& p, int nq_tile, int E, int grid);

@@ -214,12 +214,12 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
     // the tail sign sketches move with the inverse norms — when every shard that holds rows has one for all of them (same dim, so
     // the same line pitch everywhere); otherwise the receiving shards start without and make theirs at the next append
     bool move_sk = true;
-    uint32_t sk_pitch = 0;
+    uint32_t sk_pitch = 0, sk_bits = 0;
     for (size_t g = 0; g < G; g++) {
         const ott_store* sh = m->shards[g];
         if (!store_rows(sh)) continue;
-        if (!sh->d_sketch || sh->sk_n < sh->n || !store_wants_sketch(sh)) move_sk = false;
-        else sk_pitch = sh->sk_pitch;
+        if (!sh->d_sketch || sh->sk_n < sh->n || !store_wants_sketch(sh) || (sk_bits && sh->sk_bits != sk_bits)) move_sk = false;  // (one form on every shard)
+        else sk_pitch = sh->sk_pitch, sk_bits = sh->sk_bits;
     }
     if (!sk_pitch) move_sk = false;
     // deleted rows: the live bits of rows that move travel through the host — read from every shard now, loaded into the shards
@@ -314,7 +314,7 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
         // phase C: the shards take the fresh buffers over (the old ones are freed)
         for (size_t g = 0; g < G; g++) {
             if (!fr[g].changed) continue;
-            const int rc = store_adopt(m->shards[g], fr[g].rows, fr[g].inv, fr[g].flag, fr[g].sketch, new_r[g].hi - new_r[g].lo, fr[g].cap);
+            const int rc = store_adopt(m->shards[g], fr[g].rows, fr[g].inv, fr[g].flag, fr[g].sketch, sk_bits, new_r[g].hi - new_r[g].lo, fr[g].cap);
             fr[g].sketch = nullptr;
             fr[g].rows = nullptr;
             fr[g].inv = nullptr;

@@ -125,55 +125,6 @@ OTT_PRUNE_HD inline float prune_score_bound(const float acc[8], float vsq, float
 OTT_PRUNE_HD inline uint32_t prune_sketch_stage0(uint32_t nst) { return nst - (nst + 3) / 4; }
 OTT_PRUNE_HD inline uint32_t prune_sketch_pitch(uint32_t n_words) { return (n_words + 2 + 3) & ~3u; }
 
-// The sketch's running sums over the tail dims, taken in dim order: one element (its f32 bits), then the end.
-struct PruneSketchSums {
-    double s1 = 0.0, s2 = 0.0;  // sum |v_i|, sum v_i^2
-    bool finite = true;
-};
-OTT_PRUNE_HD inline void prune_sketch_add(PruneSketchSums& t, uint32_t bits) {
-    if ((bits & 0x7F800000u) == 0x7F800000u) t.finite = false;
-    const double x = (double)prune_u2f(bits & 0x7FFFFFFFu);
-    t.s1 += x;
-    t.s2 += x * x;
-}
-// n: the tail's real dims.  Writes a and rho.
-OTT_PRUNE_HD inline void prune_sketch_finish(const PruneSketchSums& t, uint32_t n, float* a_out, float* rho_out) {
-    float a = 0.0f, rho = prune_u2f(0x7F800000u);
-    if (t.finite) {
-        a = n ? (float)(t.s1 / (double)n) : 0.0f;  // (any non-negative finite a gives a valid sketch: rho is taken for THIS a)
-        const double ad = (double)a;
-        const double mag = t.s2 + 2.0 * ad * t.s1 + (double)n * ad * ad;
-        double r2 = t.s2 - 2.0 * ad * t.s1 + (double)n * ad * ad;
-        r2 = (r2 > 0.0 ? r2 : 0.0) + mag * 0x1p-34;
-        const double r = sqrt(r2) * (1.0 + 0x1p-30);
-        if (r <= 3.4028234e38) rho = prune_f32_up(r);
-        else a = 0.0f;
-    }
-    *a_out = a;
-    *rho_out = rho;
-}
-
-// v: the row (at least `dim` floats), first: the sketch's first dim (a multiple of 32).  Writes pitch words to `line`.
-OTT_PRUNE_HD inline void prune_sketch_row(const float* v, uint32_t dim, uint32_t first, uint32_t n_words, uint32_t* line) {
-    PruneSketchSums t;
-    for (uint32_t j = 0; j < n_words; j++) {
-        uint32_t w = 0;
-        for (uint32_t b = 0; b < 32; b++) {
-            const uint32_t i = first + 32 * j + b;
-            if (i >= dim) break;
-            const uint32_t bits = prune_f2u(v[i]);
-            w |= (bits >> 31) << b;
-            prune_sketch_add(t, bits);
-        }
-        line[2 + j] = w;
-    }
-    float a, rho;
-    prune_sketch_finish(t, dim > first ? dim - first : 0u, &a, &rho);
-    line[0] = prune_f2u(a);
-    line[1] = prune_f2u(rho);
-    for (uint32_t j = 2 + n_words; j < prune_sketch_pitch(n_words); j++) line[j] = 0u;
-}
-
 // Host: an upper bound of sum |q[m:dim]| (double, inflated like the norms), m a multiple of 32
 inline double prune_query_l1(const float* q, uint32_t dim, uint32_t m) {
     double t = 0.0;
@@ -188,8 +139,13 @@ inline double prune_query_l1(const float* q, uint32_t dim, uint32_t m) {
 //   final dot S <= sum(acc) + q_t . v_t + 2 N u ||q|| ||v|| + dim 2^-148                   (as in prune_score_bound)
 // (a D is exact in double: two 24-bit significands.)  q1 >= ||q[m:]||_1 (prune_query_l1), qt, qn as for prune_score_bound.
 // The same evaluation in double with slack, the same outward rounding, cosine scaling and zero rule.
-OTT_PRUNE_HD inline float prune_score_bound_sketch(const float acc[8], float vinv, float a, float rho, float D, uint32_t m, uint32_t dim,
-                                                   double qt, double q1, double qn, float qinv, bool cosine, bool upper) {
+// The b-bit form (prune_score_bound_sketchb): s is replaced by the odd integers kappa_i, |kappa_i| <= kmax = 2^b - 1, and D = the
+// kernel's fmaf chain D <- fl(D + q_i kappa_i), one rounding per dim (the product is no longer a float, the fused sum still rounds
+// once; no step underflows: D and q_i kappa_i are multiples of 2^-149).  The standard bound of a recursive sum of n_t terms gives
+// |D - q_t . kappa| <= n_t u' sum |q_i kappa_i| <= n_t u' kmax ||q_t||_1, so only that term of the half width grows by kmax; kmax = 1
+// is the sign form bit for bit.
+OTT_PRUNE_HD inline float prune_score_bound_sketchb(const float acc[8], float vinv, float a, float rho, float D, double kmax, uint32_t m,
+                                                    uint32_t dim, double qt, double q1, double qn, float qinv, bool cosine, bool upper) {
     const float nan = prune_u2f(0x7FC00000u);
     if (!(vinv >= 0x1p-50f && vinv <= 3.4028234e38f)) return nan;  // zero, tiny, huge, inf or NaN norm: no bound
     if (!(rho >= 0.0f && rho <= 3.4028234e38f)) return nan;        // no sketch of this tail
@@ -208,7 +164,7 @@ OTT_PRUNE_HD inline float prune_score_bound_sketch(const float acc[8], float vin
     const double vn2 = iv * iv * (1.0 + 2.0 * ((double)dim + 8.0) * u) + (double)dim * 0x1p-148;
     const double nt = (double)(dim > m ? dim - m : 0u);
     const double C = (double)a * (double)D;                                     // the centre of the tail: exact
-    const double W = (double)a * (nt * u * (1.0 + 0x1p-6) * q1) + qt * (double)rho;  // its half width
+    const double W = (double)a * (nt * u * (1.0 + 0x1p-6) * kmax * q1) + qt * (double)rho;  // its half width (x 1.0 is exact: b = 1)
     const double G = 2.0 * ((double)(dim / 8) + 9.0) * u * qn * sqrt(vn2);
     const double r = W + G + (Pa + fabs(C) + W + G) * 0x1p-40 + (double)dim * 0x1p-147;
     float S = upper ? prune_f32_up(P + C + r) : prune_f32_down(P + C - r);
@@ -222,6 +178,130 @@ OTT_PRUNE_HD inline float prune_score_bound_sketch(const float acc[8], float vin
     }
     if (S == 0.0f) S = upper ? 0.0f : -0.0f;
     return S;
+}
+
+OTT_PRUNE_HD inline float prune_score_bound_sketch(const float acc[8], float vinv, float a, float rho, float D, uint32_t m, uint32_t dim,
+                                                   double qt, double q1, double qn, float qinv, bool cosine, bool upper) {
+    return prune_score_bound_sketchb(acc, vinv, a, rho, D, 1.0, m, dim, qt, q1, qn, qinv, cosine, upper);
+}
+
+// ---- the b-bit tail sketch ("three bits per dim") ---------------------------------------------------------------
+// The sign sketch generalised to a signed mid-rise code of b bits per dim: kappa_i = 2 code_i + 1, code_i a two's-complement field
+// of b bits, so kappa_i is an odd integer in [-(2^b - 1), 2^b - 1], and the row's tail is v_t = a kappa + r with ||r|| <= rho.
+//   b = 1: the sign sketch itself — code = -1 where the sign bit is set, a = the mean of |v_i|, the same line bit for bit.
+//   b > 1: Delta = max |v_i| / 2^(b-1) over the sketched dims, code_i = floor(v_i / Delta) clamped to [-2^(b-1), 2^(b-1) - 1],
+//          a = Delta / 2: the mid points of 2^b cells of width Delta that cover [-max, max].
+// rho is taken for the a and the codes that are stored, whatever rule chose them: ||v_t - a kappa||^2 = sum v_i^2 - 2 a sum v_i kappa_i
+// + a^2 sum kappa_i^2, the three sums in double (every term exact), the cancellation paid for with 2^-34 of the magnitudes, the root
+// inflated and rounded up exactly as in the sign form.  So a code on a cell boundary, or of a -0, may fall either way (host and
+// device need not agree), and any a >= 0 is a valid sketch.  A tail that holds a NaN or an inf, or whose rho leaves the f32 range:
+// a = 0, rho = +inf.
+// Layout of a line (u32 words): [a | rho | b words per sketched stage], the field of dim 32 s + i at bits b i .. b i + b - 1 of the
+// stage's b words taken as one little-endian string of 32 b bits; dims past `dim` hold code 0.  Pitch: whole 16-B lines.
+// The first sketched stage: the last quarter of the stages at b = 1, the last 5/8 (rounded up) at b > 1 — at least one stage stays
+// in front (the prefix then holds whole chunks of eight: 32 c < dim for every c below the stage count).
+OTT_PRUNE_HD inline uint32_t prune_sketchb_stage0(uint32_t nst, uint32_t bits) {
+    if (bits <= 1) return prune_sketch_stage0(nst);
+    const uint32_t c = nst - (5 * nst + 7) / 8;
+    return (c < 1 && nst >= 2) ? 1u : c;
+}
+OTT_PRUNE_HD inline uint32_t prune_sketchb_pitch(uint32_t n_stages, uint32_t bits) { return prune_sketch_pitch(n_stages * bits); }
+
+// the code of dim i (0 .. 31) of a stage whose b words start at w
+OTT_PRUNE_HD inline int32_t prune_sketchb_code(const uint32_t* w, uint32_t i, uint32_t bits) {
+    const uint32_t pos = bits * i, lo = pos & 31u;
+    uint32_t x = w[pos >> 5] >> lo;
+    if (lo + bits > 32u) x |= w[(pos >> 5) + 1] << (32u - lo);
+    return (int32_t)(x << (32u - bits)) >> (32u - bits);
+}
+// the code of a value for the cell width 1 / inv_delta, b > 1 (inv_delta = 0: every code is 0)
+OTT_PRUNE_HD inline int32_t prune_sketchb_quant(float v, float inv_delta, uint32_t bits) {
+    const float t = floorf(v * inv_delta), hi = (float)((1 << (bits - 1)) - 1), lo = -(float)(1 << (bits - 1));
+    if (!(t == t)) return 0;
+    return (int32_t)(t > hi ? hi : t < lo ? lo : t);
+}
+// the cell width's reciprocal and a from the largest magnitude of the tail (finite), b > 1
+OTT_PRUNE_HD inline void prune_sketchb_scale(float vmax, uint32_t bits, float* inv_delta, float* a) {
+    const float delta = vmax / (float)(1 << (bits - 1));
+    float r = delta > 0.0f ? 1.0f / delta : 0.0f;
+    if (!(r <= 3.4028234e38f)) r = 3.4028234e38f;  // (a subnormal Delta: the products saturate, the clamp sorts them)
+    *inv_delta = r;
+    *a = delta * 0.5f;
+}
+
+struct PruneSketchSumsB {
+    double s1 = 0.0, s1a = 0.0, s2 = 0.0, sk = 0.0;  // sum v_i kappa_i, sum |v_i kappa_i|, sum v_i^2, sum kappa_i^2
+    bool finite = true;
+};
+OTT_PRUNE_HD inline void prune_sketchb_add(PruneSketchSumsB& t, uint32_t vbits, int32_t kappa) {
+    if ((vbits & 0x7F800000u) == 0x7F800000u) t.finite = false;
+    const double x = (double)prune_u2f(vbits), kd = (double)kappa, p = x * kd;
+    t.s1 += p;
+    t.s1a += fabs(p);
+    t.s2 += x * x;
+    t.sk += kd * kd;
+}
+// a_in: the a the codes were made for (any non-negative finite value).  Writes a and rho.
+OTT_PRUNE_HD inline void prune_sketchb_finish(const PruneSketchSumsB& t, float a_in, float* a_out, float* rho_out) {
+    float a = 0.0f, rho = prune_u2f(0x7F800000u);
+    if (t.finite && a_in >= 0.0f && a_in <= 3.4028234e38f) {
+        a = a_in;
+        const double ad = (double)a;
+        const double mag = t.s2 + 2.0 * ad * t.s1a + t.sk * ad * ad;
+        double r2 = t.s2 - 2.0 * ad * t.s1 + t.sk * ad * ad;
+        r2 = (r2 > 0.0 ? r2 : 0.0) + mag * 0x1p-34;
+        const double r = sqrt(r2) * (1.0 + 0x1p-30);
+        if (r <= 3.4028234e38) rho = prune_f32_up(r);
+        else a = 0.0f;
+    }
+    *a_out = a;
+    *rho_out = rho;
+}
+// the sign form's a from the b = 1 sums (sum v_i kappa_i = sum |v_i| there)
+OTT_PRUNE_HD inline float prune_sketchb_mean(const PruneSketchSumsB& t, uint32_t n) { return (t.finite && n) ? (float)(t.s1 / (double)n) : 0.0f; }
+
+// v: the row (at least `dim` floats), first: the sketch's first dim (a multiple of 32).  Writes prune_sketchb_pitch words to `line`.
+OTT_PRUNE_HD inline void prune_sketchb_row(const float* v, uint32_t dim, uint32_t first, uint32_t n_stages, uint32_t bits, uint32_t* line) {
+    const uint32_t pitch = prune_sketchb_pitch(n_stages, bits);
+    for (uint32_t j = 2; j < pitch; j++) line[j] = 0u;
+    float inv_delta = 0.0f, a_in = 0.0f;
+    if (bits > 1) {
+        float vmax = 0.0f;
+        for (uint32_t i = first; i < dim; i++) {
+            const float x = prune_u2f(prune_f2u(v[i]) & 0x7FFFFFFFu);
+            if (x > vmax && x <= 3.4028234e38f) vmax = x;
+        }
+        prune_sketchb_scale(vmax, bits, &inv_delta, &a_in);
+    }
+    PruneSketchSumsB t;
+    for (uint32_t i = first; i < dim && i < first + 32 * n_stages; i++) {
+        const uint32_t vb = prune_f2u(v[i]);
+        const int32_t code = bits > 1 ? prune_sketchb_quant(v[i], inv_delta, bits) : -(int32_t)(vb >> 31);
+        const uint32_t pos = bits * ((i - first) & 31u), lo = pos & 31u;
+        uint32_t* w = line + 2 + bits * ((i - first) >> 5) + (pos >> 5);
+        const uint32_t f = (uint32_t)code & ((1u << bits) - 1u);
+        w[0] |= f << lo;
+        if (lo + bits > 32u) w[1] |= f >> (32u - lo);
+        prune_sketchb_add(t, vb, 2 * code + 1);
+    }
+    if (bits <= 1) a_in = prune_sketchb_mean(t, dim > first ? dim - first : 0u);
+    float a, rho;
+    prune_sketchb_finish(t, a_in, &a, &rho);
+    line[0] = prune_f2u(a);
+    line[1] = prune_f2u(rho);
+}
+
+// The sign sketch's own names: the b = 1 case of the functions above (sum v_i kappa_i = sum |v_i| there, sum kappa_i^2 = n, the same
+// operations in the same order: the same bits).
+typedef PruneSketchSumsB PruneSketchSums;
+OTT_PRUNE_HD inline void prune_sketch_add(PruneSketchSums& t, uint32_t bits) { prune_sketchb_add(t, bits, (bits >> 31) ? -1 : 1); }
+// n: the tail's real dims (every one of them added).  Writes a and rho.
+OTT_PRUNE_HD inline void prune_sketch_finish(const PruneSketchSums& t, uint32_t n, float* a_out, float* rho_out) {
+    prune_sketchb_finish(t, prune_sketchb_mean(t, n), a_out, rho_out);
+}
+// v: the row (at least `dim` floats), first: the sketch's first dim (a multiple of 32).  Writes pitch words to `line`.
+OTT_PRUNE_HD inline void prune_sketch_row(const float* v, uint32_t dim, uint32_t first, uint32_t n_words, uint32_t* line) {
+    prune_sketchb_row(v, dim, first, n_words, 1, line);
 }
 
 }  // namespace ott

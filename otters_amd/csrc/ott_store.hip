@@ -29,12 +29,12 @@ struct OptName {
     const char* name;
     int kind;  // 0 = bool, 1 = tri-state (-1 automatic / 0 / 1), 2 = non-negative int
 };
-// the nineteen options of the product library (see struct Options) ...
+// the twenty options of the product library (see struct Options) ...
 const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"hi_prebuild", 1},          {"stage_appends", 1},       {"multi_transport", 2},
                              {"multi_rebalance", 0}, {"multi_min_shard_rows", 2}, {"exact_small", 1},     {"large_k_from", 2},        {"small_sort", 1},
                              {"mfma_f32", 0},        {"no_hi_pass", 0},      {"no_batch_image", 0},       {"force_fallback", 2},      {"eps_scale_ppm", 2},
                              {"multi_fake_distinct", 0}, {"exact_prune", 1},            {"exact_sketch", 1},
-                             {"id_gather", 1},
+                             {"id_gather", 1},       {"exact_sketch_bits", 2},
 #ifdef OTT_MFMA_DEBUG_BUILD
                              // ... and, in the diagnostic build only, kernel tuning, timing ablations and every fallback bit by its own name
                              {"mfma_wg", 2},         {"mfma_growth", 2},     {"mfma_debug", 0},           {"mfma_abl", 2},            {"hi_tmin", 2},
@@ -42,11 +42,11 @@ const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"h
                              {"merge_rank1", 1},
 #endif
 };
-static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 19
+static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 20
 #ifdef OTT_MFMA_DEBUG_BUILD
                                                             + 11
 #endif
-              , "the product library's option table stays at nineteen entries");
+              , "the product library's option table stays at twenty entries");
 }  // namespace
 
 int option_set(Options& o, const char* name, long long v) {
@@ -81,6 +81,7 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "small_sort") return tri(o.small_sort);
     if (n == "exact_prune") return tri(o.exact_prune);
     if (n == "exact_sketch") return tri(o.exact_sketch);
+    if (n == "exact_sketch_bits") { if (v != 1 && v != 3) return -1; o.exact_sketch_bits = (int)v; return 0; }
     if (n == "id_gather") return tri(o.id_gather);
 #ifdef OTT_MFMA_DEBUG_BUILD
     if (n == "mfma_coop") return tri(o.mfma_coop);
@@ -325,12 +326,15 @@ int update_min_pos_inv(ott_store* s, uint64_t first_row, uint64_t n_rows) {
     return OTT_OK;
 }
 
-// The pruned sweep's tail sign sketch (ott_prune.h: prune_sketch_row, the same sums in the same order).  Runs right behind
-// inv_norm_kernel for the same rows and reads their last stages only (a quarter of the row), staged as there: a wave stages 64
-// rows x 128 B per step, coalesced, then lane = row walks its 32 dims out of LDS.  A lane writes its line in 16-B pieces: the
-// groups of four sign words as they fill, [a | rho | word 0 | word 1] at the end.
+// The pruned sweep's tail sketch (ott_prune.h: prune_sketchb_row, the same sums in the same order).  Runs right behind
+// inv_norm_kernel for the same rows and reads their sketched stages only (the last quarter of the row at one bit per dim, the last
+// 5/8 at three), staged as there: a wave stages 64 rows x 128 B per step, coalesced, then lane = row walks its 32 dims out of LDS.
+// BITS > 1: the cell width comes from the tail's largest magnitude, so the stages are walked twice — the maximum first, the codes
+// and the sums after it (a rule that needs one walk, the width from the row norm, clips an eighth of the dims of Gaussian rows).
+// A lane writes its line in 16-B pieces: the groups of four code words as they fill, [a | rho | word 0 | word 1] at the end.
+template <int BITS>
 __global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restrict__ rows, uint32_t ld, uint32_t dim, uint64_t first, uint64_t n,
-                                                           uint32_t stage0, uint32_t n_words, uint32_t pitch, uint32_t* __restrict__ sketch) {
+                                                           uint32_t stage0, uint32_t n_stages, uint32_t pitch, uint32_t* __restrict__ sketch) {
     __shared__ __attribute__((aligned(16))) float smem[4 * 64 * NKC];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -339,6 +343,11 @@ __global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restric
     const int lrow = lane >> 3, lslot = lane & 7, sw = (lane >> 1) & 7;
     typedef float v4f __attribute__((ext_vector_type(4)));
     typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    auto wave_fence = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
     for (uint64_t t = (uint64_t)blockIdx.x * 4 + wave; t < n_tiles; t += (uint64_t)gridDim.x * 4) {
         const uint64_t row0 = first + t * 64;
         const uint32_t cnt = (n - t * 64) < 64 ? (uint32_t)(n - t * 64) : 64u;
@@ -357,60 +366,95 @@ __global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restric
 #pragma unroll
             for (int m = 0; m < 8; m++) R[m] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(rp[m] + c));
         };
-        const bool mine = (uint32_t)lane < cnt;
-        v4u* line = reinterpret_cast<v4u*>(sketch + (row0 + (mine ? lane : 0)) * (uint64_t)pitch);
-        PruneSketchSums sums;
-        uint32_t w01[2] = {0u, 0u};          // sign words 0 and 1: they share the first 16 B with a and rho
-        v4u grp = {0u, 0u, 0u, 0u};          // the 16-B piece that is filling (line words 4 g .. 4 g + 3)
-        load_stage(stage0);
-        for (uint32_t j = 0; j < n_words; j++) {
-            const uint32_t sg = stage0 + j;
+        auto to_lds = [&]() {
 #pragma unroll
             for (int m = 0; m < 8; m++)
                 *reinterpret_cast<v4f*>(st + (8 * m + lrow) * NKC + ((lslot ^ (((8 * m + lrow) >> 1) & 7)) << 2)) = R[m];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (j + 1 < n_words) load_stage(sg + 1);
-            uint32_t w = 0;
+            wave_fence();
+        };
+        const bool mine = (uint32_t)lane < cnt;
+        v4u* line = reinterpret_cast<v4u*>(sketch + (row0 + (mine ? lane : 0)) * (uint64_t)pitch);
+        float inv_delta = 0.0f, a_in = 0.0f;
+        if constexpr (BITS > 1) {  // first walk: the largest finite magnitude
+            uint32_t vmax = 0u;    // (magnitudes of floats order like their bit patterns)
+            load_stage(stage0);
+            for (uint32_t j = 0; j < n_stages; j++) {
+                const uint32_t sg = stage0 + j;
+                to_lds();
+                if (j + 1 < n_stages) load_stage(sg + 1);
+#pragma unroll
+                for (int c = 0; c < NKC / 4; c++) {
+                    const v4u x = *reinterpret_cast<const v4u*>(st + lane * NKC + ((c ^ sw) << 2));
+                    const uint32_t bits[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                    for (int l = 0; l < 4; l++) {
+                        const uint32_t m = bits[l] & 0x7FFFFFFFu;
+                        if (sg * NKC + 4 * c + l < dim && m < 0x7F800000u && m > vmax) vmax = m;
+                    }
+                }
+                wave_fence();
+            }
+            prune_sketchb_scale(__uint_as_float(vmax), BITS, &inv_delta, &a_in);
+        }
+        PruneSketchSumsB sums;
+        uint32_t w01[2] = {0u, 0u};          // code words 0 and 1: they share the first 16 B with a and rho
+        v4u grp = {0u, 0u, 0u, 0u};          // the 16-B piece that is filling (line words 4 g .. 4 g + 3)
+        load_stage(stage0);
+        for (uint32_t j = 0; j < n_stages; j++) {
+            const uint32_t sg = stage0 + j;
+            to_lds();
+            if (j + 1 < n_stages) load_stage(sg + 1);
+            uint32_t w[BITS];
+#pragma unroll
+            for (int b = 0; b < BITS; b++) w[b] = 0u;
 #pragma unroll
             for (int c = 0; c < NKC / 4; c++) {
                 const v4u x = *reinterpret_cast<const v4u*>(st + lane * NKC + ((c ^ sw) << 2));
                 const uint32_t bits[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
                 for (int l = 0; l < 4; l++)
-                    if (sg * NKC + 4 * c + l < dim) {  // (dims past `dim` count as zero and are excluded)
-                        w |= (bits[l] >> 31) << (4 * c + l);
-                        prune_sketch_add(sums, bits[l]);
+                    if (sg * NKC + 4 * c + l < dim) {  // (dims past `dim` count as zero and are excluded: code 0)
+                        int32_t code;
+                        if constexpr (BITS > 1) code = prune_sketchb_quant(__uint_as_float(bits[l]), inv_delta, BITS);
+                        else code = -(int32_t)(bits[l] >> 31);
+                        constexpr uint32_t fmask = (1u << BITS) - 1u;
+                        const uint32_t pos = BITS * (4 * c + l), lo = pos & 31u;  // (constants once unrolled)
+                        const uint32_t f = (uint32_t)code & fmask;
+                        w[pos >> 5] |= f << lo;
+                        if (lo + BITS > 32u) w[(pos >> 5) + 1] |= f >> (32u - lo);
+                        prune_sketchb_add(sums, bits[l], 2 * code + 1);
                     }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (j < 2) {
-                w01[0] = j == 0 ? w : w01[0];
-                w01[1] = j == 1 ? w : w01[1];
-            } else {
-                const uint32_t k = j + 2, slot = k & 3;
-                grp.x = slot == 0 ? w : grp.x;
-                grp.y = slot == 1 ? w : grp.y;
-                grp.z = slot == 2 ? w : grp.z;
-                grp.w = slot == 3 ? w : grp.w;
-                if (slot == 3 || j + 1 == n_words) {  // (4 (k / 4) + 3 < pitch: the pitch is a multiple of four words)
-                    if (mine) line[k >> 2] = grp;
-                    grp = v4u{0u, 0u, 0u, 0u};
+            wave_fence();
+#pragma unroll
+            for (int b = 0; b < BITS; b++) {
+                const uint32_t k = 2 + BITS * j + b, slot = k & 3;  // the word's place in the line
+                if (k < 4) {
+                    w01[0] = k == 2 ? w[b] : w01[0];
+                    w01[1] = k == 3 ? w[b] : w01[1];
+                } else {
+                    grp.x = slot == 0 ? w[b] : grp.x;
+                    grp.y = slot == 1 ? w[b] : grp.y;
+                    grp.z = slot == 2 ? w[b] : grp.z;
+                    grp.w = slot == 3 ? w[b] : grp.w;
+                    if (slot == 3 || (j + 1 == n_stages && b == BITS - 1)) {  // (4 (k / 4) + 3 < pitch: the pitch is a multiple of four words)
+                        if (mine) line[k >> 2] = grp;
+                        grp = v4u{0u, 0u, 0u, 0u};
+                    }
                 }
             }
         }
+        if constexpr (BITS == 1) a_in = prune_sketchb_mean(sums, dim > stage0 * NKC ? dim - stage0 * NKC : 0u);
         float a, rho;
-        prune_sketch_finish(sums, dim > stage0 * NKC ? dim - stage0 * NKC : 0u, &a, &rho);
+        prune_sketchb_finish(sums, a_in, &a, &rho);
         if (mine) line[0] = v4u{__float_as_uint(a), __float_as_uint(rho), w01[0], w01[1]};
     }
 }
 
 bool store_wants_sketch(const ott_store* s) {
     const uint32_t nst = (s->ld + 31) / 32;
-    if (s->opt.exact_sketch == 0 || nst < 2 || prune_sketch_stage0(nst) < 1) return false;
+    const uint32_t bits = s->d_sketch ? s->sk_bits : (uint32_t)s->opt.exact_sketch_bits;  // (read when the store makes its first line)
+    if (s->opt.exact_sketch == 0 || nst < 2 || prune_sketchb_stage0(nst, bits) < 1) return false;
     return s->opt.exact_sketch == 1 || nst >= 8;
 }
 
@@ -428,8 +472,9 @@ static int update_sketch(ott_store* s, uint64_t first_row, uint64_t n_rows) {
     }
     const uint32_t nst = (s->ld + 31) / 32;
     if (!s->d_sketch) {
-        s->sk_stage0 = prune_sketch_stage0(nst);
-        s->sk_words = nst - s->sk_stage0;
+        s->sk_bits = (uint32_t)s->opt.exact_sketch_bits;
+        s->sk_stage0 = prune_sketchb_stage0(nst, s->sk_bits);
+        s->sk_words = (nst - s->sk_stage0) * s->sk_bits;
         s->sk_pitch = prune_sketch_pitch(s->sk_words);
         s->sk_n = 0;
         const hipError_t e = hipMalloc((void**)&s->d_sketch, s->cap * (size_t)s->sk_pitch * 4);
@@ -442,8 +487,12 @@ static int update_sketch(ott_store* s, uint64_t first_row, uint64_t n_rows) {
     const uint64_t lo = first_row < s->sk_n ? first_row : s->sk_n, hi = first_row + n_rows;
     uint64_t blocks = ((hi - lo + 63) / 64 + 3) / 4;  // a wave per 64 rows, as launch_inv_norms
     if (blocks > (uint64_t)s->n_cu * 8) blocks = (uint64_t)s->n_cu * 8;
-    hipLaunchKernelGGL(tail_sketch_kernel, dim3((uint32_t)blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
-                       s->sk_words, s->sk_pitch, s->d_sketch);
+    if (s->sk_bits == 3)
+        hipLaunchKernelGGL(tail_sketch_kernel<3>, dim3((uint32_t)blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
+                           nst - s->sk_stage0, s->sk_pitch, s->d_sketch);
+    else
+        hipLaunchKernelGGL(tail_sketch_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
+                           nst - s->sk_stage0, s->sk_pitch, s->d_sketch);
     OTT_HIP(hipGetLastError());
     if (hi > s->sk_n) s->sk_n = hi;
     return OTT_OK;
@@ -558,7 +607,7 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
 // A shard of a multi-GPU store takes over buffers the relayout filled (rows [0, n) valid, capacity `cap`): the old ones are
 // freed, the 16-bit copies of the corpus are dropped (rebuilt lazily), the hi plane's per-row marks are cleared, the smallest
 // inverse norm is measured again, the evaluated row mask is forgotten.  The caller holds the multi store exclusively.
-int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* sketch, uint64_t n, uint64_t cap) {
+int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* sketch, uint32_t sketch_bits, uint64_t n, uint64_t cap) {
     // the shard's own lock too: its background plane builder reads the rows under it (shared) and must be out before they go
     ott::host::ExclusiveLock wr(s->rw);
     std::lock_guard<std::mutex> g(s->mu);
@@ -576,8 +625,9 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
     s->d_sketch = sketch;  // (nullptr: the rows came without sketch lines — the next append makes them for the whole shard)
     if (sketch) {
         const uint32_t nst = (s->ld + 31) / 32;
-        s->sk_stage0 = prune_sketch_stage0(nst);
-        s->sk_words = nst - s->sk_stage0;
+        s->sk_bits = sketch_bits;  // (the form the lines were made in, on whichever shard)
+        s->sk_stage0 = prune_sketchb_stage0(nst, s->sk_bits);
+        s->sk_words = (nst - s->sk_stage0) * s->sk_bits;
         s->sk_pitch = prune_sketch_pitch(s->sk_words);
     }
     s->sk_n = sketch ? n : 0;
@@ -732,6 +782,7 @@ static void alias_corpus(ott_store* w, const ott_store* s) {
     w->d_sketch = s->d_sketch;
     w->sk_n = s->sk_n;
     w->sk_words = s->sk_words;
+    w->sk_bits = s->sk_bits;
     w->sk_pitch = s->sk_pitch;
     w->sk_stage0 = s->sk_stage0;
     w->d_evalmask.p = s->d_evalmask.p;
