@@ -226,9 +226,10 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
 
     // single query, at most two runs: everything the kernel needs rides in its arguments (no H2D copy, no staging)
     const bool lean = nq == 1 && s->dimq <= OTT_QEMB_MAX && pl.runs.size() <= 2;
-    // Pruned sweep (store option exact_prune): one query, merged, cosine / dot, the streaming kernel.  A seed of a
-    // tenth of the rows is scored in full and merged; its k-th best gates the second launch over the rest, which skips the last
-    // stages (from c, 7/8 of them) of every row whose score bound misses it.  Automatic from 2^20 rows and 8 stages (dim >= 225).
+    // Pruned sweep (store option exact_prune): one query, merged, cosine / dot, the streaming kernel.  A seed of the
+    // first rows (how many: where `seed` is set below) is scored in full and merged; its k-th best gates the second launch over the
+    // rest, which skips the last stages (from c, 7/8 of them) of every row whose score bound misses it.  Automatic from 2^20 rows
+    // and 8 stages (dim >= 225).
     // A store that keeps a tail sketch for every row (option exact_sketch) takes the sketch form in the store's own width (option
     // exact_sketch_bits): the checkpoint is the sketch's first stage, 3/8 of the stages at three bits per dim, 3/4 at one.
     uint32_t prune_c = 0;
@@ -250,7 +251,14 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
         }
         const bool worth = s->opt.exact_prune == 1 || (nst >= 8 && pl.rows_scored >= (1ull << 20));
         if (worth && c >= 1 && c < nst) {
-            uint64_t seed = (pl.rows_scored / 10 + 63) & ~63ull;
+            // The seed: a tenth of the rows.  With the three-bit sketch and k <= 64, once that is more than 131072 rows: a
+            // thirty-second of them, never fewer than 131072 (continuous at 1.31M rows; 10M rows: 312 512 rows read in full instead of
+            // 1M, 10M x 768 top-10 2.862 -> 2.753 ms).  A smaller seed gives a lower gate; the wide sketch loses few rows to that, but a
+            // longer list's k-th best sits deeper in the seed (k = 500 at 10M x 768: 3.54 -> 3.78 ms with the small seed), and the
+            // other forms save less per seed row (their checkpoint is at 3/4 or 7/8 of the row): those keep the tenth
+            uint64_t seed = pl.rows_scored / 10;
+            if (prune_sk && s->sk_bits == 3 && E == 1 && seed > 131072) seed = pl.rows_scored / 32 > 131072 ? pl.rows_scored / 32 : 131072;
+            seed = (seed + 63) & ~63ull;
             if (seed < 64) seed = 64;
             split_plan(pl, seed, plA, plB);
             if (plA.runs.size() <= 2 && plB.runs.size() <= 2 && plB.rows_scored > 0 &&

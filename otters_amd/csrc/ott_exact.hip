@@ -51,7 +51,9 @@ constexpr int SK3_XP = ((int)OTT_SKETCH_MAX_WORDS + 2 + 3) / 4 - 8;
 // Workgroups per CU of the persistent grid.  TWO since round 6 (8 waves per CU, 64 KB of row stages in flight per CU, 512 block lists for
 // the merge): measured against 3, 4 (rounds 2-5), 5 and 8 on every instantiation — 1M x 128 dot top-10 89.4 + 11.8 -> 86.3 + 9.7 us
 // (scoring + merge), 2M / 4M x 128 5 % / 3 % faster, 3M x 768 2 %, the 10M x 768 headline 4403 -> 4374 us, four queries per pass 4799
-// -> 4552, top-500 on 1M x 128 294 -> 247, the single-query int8 sweep 1161 -> 1134 (profiles/round6/c1_latency.md).  Experiment
+// -> 4552, top-500 on 1M x 128 294 -> 247, the single-query int8 sweep 1161 -> 1134 (profiles/round6/c1_latency.md).  The pruned
+// launch with the three-bit sketch was measured on its own later, three against two for k <= 128 where registers and LDS allow
+// it: 2.815 against 2.753 ms on the 10M x 768 headline (profiles/exact_overlap/README.md), so it keeps two as well.  Experiment
 // builds override it: variants/build_exact.sh name "-DOTT_X_BLOCKS_PER_CU=4".
 #ifndef OTT_X_BLOCKS_PER_CU
 #define OTT_X_BLOCKS_PER_CU 2
