@@ -404,6 +404,32 @@ uint32_t ott_store_group_count(const ott_store* s);
 int ott_query_groups(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query,
                      ott_stats* stats);
 
+/* Late-interaction (MaxSim) search over grouped rows (an extension; ColBERT / ColPali scoring as Qdrant's multivector MaxSim, Vespa
+ * and Milvus serve it): the d->nq query vectors are the TOKENS of ONE query, the rows are token or passage embeddings, the store's
+ * group ids (ott_store_set_groups) say which document a row belongs to, and the answer is the top-k DOCUMENTS by
+ *     score(g) = best[0][g] + best[1][g] + ... + best[nq-1][g],   best[t][g] = the best score of token t among the rows of g
+ * that survive chunk_mask, the caller's row_mask or the evaluated device mask, and the live mask of deleted rows.  "Best" follows
+ * d->take (largest for OTT_TAKE_MAX, smallest for OTT_TAKE_MIN: with Euclidean or Manhattan the sum of minimum distances) in the
+ * library's total order (+0.0 beats -0.0 under Max); NaN pair scores are dropped as everywhere; pair scores are the exact path's
+ * bits for all four metrics.  A group is a candidate only if EVERY token has a best (it has a surviving row, and no token for which
+ * all of them scored NaN).  The sum is f32, round to nearest, in token order, started from best[0] (a -0.0 stays -0.0); a NaN sum
+ * (+inf + -inf) drops the group.  filter_cmp / filter_thr apply to the SUM: every returned score satisfies the filter (a filter on
+ * the single pair scores is not offered).  Candidates are ranked by the sum (total order, by d->take), then the lower group id, and
+ * cut at k_eff = min(k, n_groups): always this canonical order, whatever option "tie_order" says.  Hits: index = the dense group id
+ * (NOT shifted by base_offset), score = the sum, query = 0.  With nq = 1 the hits are ott_query_groups' for that query without a
+ * score filter, each row replaced by its group (between groups of EQUAL score that call prefers the lower row, this one the lower group).  cap >= k_eff.
+ * One sweep per four tokens keeps the best score ordinal of every (token, group) in a table of nq x n_groups 4-byte slots (scratch
+ * of the query context), a reduce kernel sums every group's slots into an 8-byte key, and the top-k over the keys is grouped
+ * search's.  Stats: path_used = EXACT, passes = corpus passes (ceil(nq / 4); 1 for one token), vectors_compared = rows scored x nq,
+ * bytes_scanned and score_ns / merge_ns as ott_query_groups counts them.
+ * Refused on the host before any device work: OTT_MODE_PER_QUERY (OTT_ERR_UNSUPPORTED: a batch of token sets is left out),
+ * OTT_PATH_MFMA (OTT_ERR_UNSUPPORTED; AUTO takes the sweep and never builds, extends or waits for a plane), a multi-GPU store
+ * (OTT_ERR_UNSUPPORTED: a group may span shards, the maxima would have to be joined before the sum), no group ids set or ids that
+ * cover a different number of rows than ott_store_len (OTT_ERR_INVALID, as ott_query_groups), nq x n_groups x 4 bytes above 2 GiB
+ * (OTT_ERR_UNSUPPORTED: the table holds all tokens at once), cap < k_eff (OTT_ERR_INVALID).  Takes the store shared, like
+ * ott_query_groups (staged appends go first). */
+int ott_query_maxsim(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64_t cap, uint64_t* n_out, ott_stats* stats);
+
 /* Same, but the result stays on the GPU: out_dev holds `cap` ott_hit slots in device memory
  * of the store's GPU, padded with sentinel hits (index = UINT64_MAX); *n_out_dev (device
  * uint64) receives the count.  PER_QUERY mode: cap must be a multiple of nq; query q's hits

@@ -467,6 +467,25 @@ int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* o
 
 }  // namespace
 
+// the table's top-k for ott_maxsim.hip (ott_internal.h): the launches run_groups makes, under names other files can call
+uint32_t group_select_lists(uint32_t n_groups) {
+    const uint32_t n_lists = (n_groups + 63) / 64;
+    return n_lists > GS_MAX_LISTS ? GS_MAX_LISTS : n_lists;
+}
+
+int launch_group_select(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint32_t k, int E, Cand* lists, uint32_t n_lists) {
+    return launch_select(s, table, n_groups, q0, nq_here, k, E, lists, n_lists);
+}
+
+int launch_group_compact(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint64_t* keys, uint32_t* qs,
+                         unsigned long long* cursor, uint64_t cap) {
+    uint32_t blocks = (n_groups + 255) / 256;
+    if (blocks > (uint32_t)s->n_cu * 8) blocks = (uint32_t)s->n_cu * 8;
+    hipLaunchKernelGGL(group_compact_kernel, dim3(blocks, nq_here), dim3(256), 0, s->stream, table, n_groups, q0, keys, qs, cursor, cap);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+
 int group_grow(ott_store* s, uint64_t ncap) {
     if (!s->d_gid || ncap <= s->cap) return OTT_OK;
     uint32_t* ng = nullptr;

@@ -140,6 +140,8 @@ struct Options {
                                   // wait, or the grouped all-gather) on a one-GPU box.  Results never depend on it.
     int id_gather = -1;           // candidate id lists (ott_query_ids): -1 = automatic, 0 = never (the list becomes a row mask and
                                   // takes the mask's paths), 1 = the gather kernel wherever it is eligible
+    int maxsim_fold = -1;         // [debug build] late-interaction sweep (ott_maxsim.hip): -1 = the product's epilogue, 0 = one atomic per lane,
+                                  // 1 = folded over runs of adjacent lanes of one group first (the A/B of profiles/maxsim)
     int multi_min_shard_rows = 32768;  // multi-GPU store: a shard is only brought in for this many rows (a store of fewer than twice as many stays
                                   // on its first GPU and is answered by that shard alone: the fan-out over N GPUs costs 50-150 us per query,
                                   // more than a small store's whole query); 0 = always split evenly over all shards
@@ -308,6 +310,11 @@ struct ott_store {
     uint32_t n_groups = 0;
     ott::DevBuf d_gtable, d_gctl;
     bool gtable_clean = false;
+    // Late-interaction search (ott_maxsim.hip), THIS context's scratch: the best score ordinal of every (token,
+    // group), [nq][n_groups] x 4 B, 0 = empty; zeroed when it is (re)allocated or after a failed query and left zeroed by every
+    // query's reduce kernel (mstable_clean).  The groups' 8-byte keys the reduce makes go through d_gtable, under its own protocol
+    ott::DevBuf d_mstable;
+    bool mstable_clean = false;
     // Small appends are STAGED: rows of appends below 256 KB (VecStore::add_vector is one row per call, src/vec.rs:357-371)
     // collect in pinned host memory and go to the GPU together — when 4 MB are full, and before anything looks at the rows
     // (queries, reads, columns, other kinds of append).  A single-row append costs a memcpy instead of a copy + a kernel + a
@@ -667,8 +674,17 @@ int group_grow(ott_store* s, uint64_t ncap);
 int group_ids_of_hits(ott_store* s, const ott_hit* hits, uint64_t n, uint32_t* out);  // the groups of hits of this store: a gather from the resident ids
 void group_drop(ott_store* s);
 void make_run_plan(const ott_store* s, const uint64_t* chunk_mask, RunPlan& pl);
-int sort_group_pairs(ott_store* s, uint64_t n, uint32_t nq, bool take_max, uint64_t k, std::vector<std::vector<ott_hit>>& lists);
+// id_span: the low key words are ~id with id < id_span (0 = the store's rows, what a grouped query's keys hold; a late-interaction
+// query's hold group ids)
+int sort_group_pairs(ott_store* s, uint64_t n, uint32_t nq, bool take_max, uint64_t k, std::vector<std::vector<ott_hit>>& lists, uint64_t id_span = 0);
 int ensure_group_pairs(ott_store* s, uint64_t cap);  // the pair arrays for up to `cap` pairs
+// ott_group.hip's top-k over a table of [nq_here][n_groups] 8-byte keys (0 = empty), for ott_maxsim.hip: the select kernel's block
+// lists (k <= 512, E = list_E(k); at most group_select_lists(n_groups) lists of 64 E entries per query) or the compact kernel's
+// (key, query) pairs behind `cursor`.  Both leave the slots they read zeroed.
+uint32_t group_select_lists(uint32_t n_groups);
+int launch_group_select(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint32_t k, int E, Cand* lists, uint32_t n_lists);
+int launch_group_compact(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint64_t* keys, uint32_t* qs,
+                         unsigned long long* cursor, uint64_t cap);
 // ott_multi.hip: grouped search on a multi-GPU store
 int multi_set_groups(ott_store* ms, const uint32_t* gid_host, uint64_t n, uint32_t n_groups);
 int multi_clear_groups(ott_store* ms);

@@ -1063,7 +1063,7 @@ int ensure_group_pairs(ott_store* s, uint64_t cap) {
     return s->l_tmp.ensure(rs_tmp_bytes(cap));
 }
 
-int sort_group_pairs(ott_store* s, uint64_t n, uint32_t nq, bool take_max, uint64_t k, std::vector<std::vector<ott_hit>>& lists) {
+int sort_group_pairs(ott_store* s, uint64_t n, uint32_t nq, bool take_max, uint64_t k, std::vector<std::vector<ott_hit>>& lists, uint64_t id_span) {
     int rc;
     lists.assign(nq, {});
     if (n == 0) return OTT_OK;
@@ -1073,7 +1073,8 @@ int sort_group_pairs(ott_store* s, uint64_t n, uint32_t nq, bool take_max, uint6
     uint32_t* qB = (uint32_t*)s->l_qB.p;
     uint32_t qbits = 0, rbits = 1;
     while (nq > 1 && qbits < 32 && ((uint64_t)(nq - 1) >> qbits) != 0) qbits++;
-    while (rbits < 32 && ((s->n - 1) >> rbits) != 0) rbits++;
+    const uint64_t span = id_span ? id_span : s->n;
+    while (rbits < 32 && ((span - 1) >> rbits) != 0) rbits++;
     RsPlan plan;
     memset(&plan, 0, sizeof(plan));
     rs_add_digits(plan, 0, 0, rbits, true);   // ~row: the lower row first among equal scores

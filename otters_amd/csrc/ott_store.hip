@@ -39,12 +39,12 @@ const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"h
                              // ... and, in the diagnostic build only, kernel tuning, timing ablations and every fallback bit by its own name
                              {"mfma_wg", 2},         {"mfma_growth", 2},     {"mfma_debug", 0},           {"mfma_abl", 2},            {"hi_tmin", 2},
                              {"mfma_no_dense", 0},   {"mfma_coop", 1},       {"mfma_spec", 1},            {"large_k_pre", 1},         {"merge_walk", 0},
-                             {"merge_rank1", 1},
+                             {"merge_rank1", 1},     {"maxsim_fold", 1},
 #endif
 };
 static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 20
 #ifdef OTT_MFMA_DEBUG_BUILD
-                                                            + 11
+                                                            + 12
 #endif
               , "the product library's option table stays at twenty entries");
 }  // namespace
@@ -84,6 +84,7 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "exact_sketch_bits") { if (v != 1 && v != 3) return -1; o.exact_sketch_bits = (int)v; return 0; }
     if (n == "id_gather") return tri(o.id_gather);
 #ifdef OTT_MFMA_DEBUG_BUILD
+    if (n == "maxsim_fold") return tri(o.maxsim_fold);
     if (n == "mfma_coop") return tri(o.mfma_coop);
     if (n == "mfma_spec") return tri(o.mfma_spec);
     if (n == "mfma_no_dense") return flag(o.mfma_no_dense);
@@ -1417,7 +1418,7 @@ int ott_store_destroy(ott_store* s) {
         if (s->d_img8_rel) (void)hipFree(s->d_img8_rel);
     }
     for (ott::DevBuf* b : {&s->d_queries, &s->d_qinv, &s->d_rowmask, &s->d_runs, &s->d_prefix, &s->d_lists, &s->d_lists2, &s->d_hits,
-                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_gather, &s->d_gtable, &s->d_gctl, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
+                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_gather, &s->d_gtable, &s->d_gctl, &s->d_mstable, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
                            &s->m_tau, &s->m_cntA, &s->m_cntB, &s->m_candA, &s->m_candB, &s->m_over, &s->m_out, &s->m_outcnt,
                            &s->m_uncert, &s->m_prefix, &s->x_send, &s->x_recv, &s->l_keysA, &s->l_keysB, &s->l_qA, &s->l_qB, &s->l_tmp, &s->l_cursor, &s->l_hist, &s->l_gate, &s->l_ctl})
         b->release();

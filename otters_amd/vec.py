@@ -101,6 +101,7 @@ class ResolvedQuery:
     path: int = Path.Auto
     row_ids: Optional[np.ndarray] = None  # uint64[n_ids] (with_row_ids): only these rows are ranked, or None
     grouped: bool = False                 # one_per_group: one best hit per group, top-k over the groups (ott_query_groups)
+    max_sim: bool = False                 # max_sim: the query vectors are one query's tokens, top-k groups by the sum of their best scores (ott_query_maxsim)
 
 
 def as_row_ids(ids) -> np.ndarray:
@@ -160,6 +161,7 @@ class VecQueryPlan:
         self._mode = Mode.Merged
         self._path = Path.Auto
         self._grouped = False
+        self._max_sim = False
 
     @staticmethod
     def new() -> "VecQueryPlan":
@@ -238,6 +240,18 @@ class VecQueryPlan:
             self._grouped = True
         return self
 
+    def max_sim(self) -> "VecQueryPlan":
+        """Late-interaction (MaxSim) search (VecStore.set_groups; ott_query_maxsim): the plan's query vectors are the TOKENS of one
+        query; a group's score is the sum over the tokens, in token order, of the token's best score among the group's surviving
+        rows, and the hits are the top groups by that sum (then lower group id).  take(k) infers Min / Max from the metric as
+        usual (Euclidean / Manhattan: the sum of minimum distances); a plan without take ranks by Max and returns every group
+        (the default take becomes group_count()).  filter() applies to the sum.  collect_arrays() returns hits whose `index` is
+        the dense group id; collect() returns SearchResult(label, score) with the caller's own group label.  Not together with
+        with_row_ids, one_per_group or per_query; not on a multi-GPU store."""
+        if self.error is None:
+            self._max_sim = True
+        return self
+
     # -- execution -----------------------------------------------------------------------------
     def validate(self) -> None:  # src/vec.rs:170-203
         if self.error is not None:
@@ -254,6 +268,12 @@ class VecQueryPlan:
             as_row_ids(self.row_ids)
         if self._grouped and self.row_ids is not None:
             raise OttersError("one_per_group cannot be combined with with_row_ids in this version; use with_row_mask")
+        if self._max_sim and self.row_ids is not None:
+            raise OttersError("max_sim cannot be combined with with_row_ids in this version; use with_row_mask")
+        if self._max_sim and self._grouped:
+            raise OttersError("max_sim cannot be combined with one_per_group: a hit of max_sim is a group already")
+        if self._max_sim and self._mode == Mode.PerQuery:
+            raise OttersError("max_sim cannot be combined with per_query: the query vectors are the tokens of one query")
         dim = self.vector_store.dim
         if isinstance(self.query_vectors, np.ndarray):  # a matrix: every row has the same length
             if self.query_vectors.shape[1] != dim:
@@ -271,15 +291,20 @@ class VecQueryPlan:
             queries = self.query_vectors
         else:
             queries = np.ascontiguousarray(np.stack(self.query_vectors).astype(np.float32, copy=False))
-        k = self.take_count if self.take_count is not None else (store.group_count() if self._grouped else store.len())  # src/vec.rs:213
+        k = self.take_count if self.take_count is not None else (store.group_count() if self._grouped or self._max_sim else store.len())  # src/vec.rs:213
         take = self.take_type if self.take_type is not None else TakeType.Max  # src/vec.rs:214
         fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
         return ResolvedQuery(queries=queries, metric=int(self.search_metric), take=int(take), k=max(int(k), 0),
                              filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, mode=int(self._mode), path=int(self._path),
-                             row_ids=None if self.row_ids is None else as_row_ids(self.row_ids), grouped=self._grouped)
+                             row_ids=None if self.row_ids is None else as_row_ids(self.row_ids), grouped=self._grouped,
+                             max_sim=self._max_sim)
 
     def collect(self):  # src/vec.rs:205-311
         hits, counts = self.collect_arrays()
+        if self._max_sim:  # a hit is a group: the caller's own label where set_groups made the ids dense
+            labels = self.vector_store.group_labels()
+            idx = hits["index"].astype(np.int64)
+            return [SearchResult(i, x) for i, x in zip((idx if labels is None else labels[idx]).tolist(), hits["score"].tolist())]
         # .tolist() first: building the objects from Python scalars is several times faster than indexing a record array
         idx, sc = hits["index"].tolist(), hits["score"].tolist()
         if self._mode == Mode.PerQuery:
@@ -298,6 +323,8 @@ class VecQueryPlan:
         store = self.vector_store
         hits, counts, stats = store._run(rq)
         store.last_stats = stats
+        if rq.max_sim:  # one list of groups; the tokens have no hits of their own
+            return hits, [int(hits.size)]
         if rq.mode != Mode.PerQuery:  # merged: how many of the k hits each query of the batch contributed
             counts = np.bincount(hits["query"], minlength=rq.queries.shape[0]).tolist()
         return hits, counts
@@ -328,6 +355,7 @@ class VecStore:
         self._options: dict = {}
         self._n_groups = 0
         self._groups_gen = 0  # changes with every set_groups / clear_groups
+        self._group_labels: Optional[np.ndarray] = None  # set_groups: np.unique's sorted labels, [dense id] = label
         self.last_stats: Optional[dict] = None
         # OTTERS_TIE_ORDER=reference: this mirror then returns, like the Rust patch and the C++ mirror do by default, the
         # reference's own outcome at exact score ties (one TopKCollector over the store); default here: the canonical order
@@ -473,6 +501,7 @@ class VecStore:
         if a.size != self._n:
             raise OttersError(f"{a.size} group ids for a store of {self._n} rows")
         self._set_dense_groups(*dense_group_ids(a))
+        self._group_labels = np.unique(a) if a.size else None
 
     def _set_dense_groups(self, dense: np.ndarray, n_groups: int) -> int:
         """uint32 ids that are dense already (MetaStore.distinct_by builds them per column).  Returns the store's group
@@ -480,6 +509,7 @@ class VecStore:
         it uploaded are still the ones the store holds."""
         N.check(N.lib().ott_store_set_groups(self._handle(), N.ptr(dense), dense.size, n_groups))
         self._n_groups = n_groups
+        self._group_labels = None
         self._groups_gen += 1
         return self._groups_gen
 
@@ -487,7 +517,13 @@ class VecStore:
         if self._h is not None:
             N.check(N.lib().ott_store_clear_groups(self._h))
         self._n_groups = 0
+        self._group_labels = None
         self._groups_gen += 1
+
+    def group_labels(self) -> Optional[np.ndarray]:
+        """The labels set_groups was given, sorted and duplicate-free: [dense group id] = label (what max_sim().collect() reports).
+        None when no groups are set or the ids came dense already (_set_dense_groups)."""
+        return self._group_labels
 
     def group_count(self) -> int:
         """Number of groups set_groups left (0 = none)."""
@@ -599,6 +635,8 @@ class VecStore:
         cap = max(k_eff * (nq if perq else 1), 1)
         if rq.grouped:  # at most one hit per group and query
             cap = max(min(rq.k, self._n_groups) * nq, 1)
+        if rq.max_sim:  # at most one hit per group
+            cap = max(min(rq.k, self._n_groups), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)  # ott_query writes n_out entries; only those are returned
         d = N.QueryDesc()
         d.queries = rq.queries.ctypes.data
@@ -620,7 +658,10 @@ class VecStore:
         n_out = C.c_uint64(0)
         per = (C.c_uint64 * nq)()
         st = N.Stats()
-        if rq.grouped:
+        if rq.max_sim:
+            N.check(N.lib().ott_query_maxsim(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), C.byref(st)))
+            per[0] = n_out.value
+        elif rq.grouped:
             N.check(N.lib().ott_query_groups(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         elif ids is None:
             N.check(N.lib().ott_query(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
