@@ -4,7 +4,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 
 #include "ott_internal.h"
 #include "ott_prune.h"
@@ -97,10 +96,6 @@ void fill_exact_params(ott_store* s, const ott_query_desc* d, const RunPlan& pl,
 }  // namespace ott
 
 namespace {
-
-uint64_t now_ns() {
-    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 uint32_t pow2ceil(uint32_t v) {
     uint32_t p = 1;

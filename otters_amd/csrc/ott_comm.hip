@@ -87,10 +87,6 @@ int nccl_fail(const char* what, int code) {
     return fail(OTT_ERR_HIP, std::string(what) + ": " + msg);
 }
 
-uint64_t now_ns() {
-    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
 
 struct ott_comm {

@@ -14,7 +14,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <numeric>
 #include <vector>
 
@@ -224,10 +223,6 @@ __global__ __launch_bounds__(256) void set_bits_kernel(uint64_t* __restrict__ wo
 }
 
 namespace {
-
-uint64_t now_ns() {
-    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 uint32_t pow2ceil(uint32_t v) {
     uint32_t p = 1;

@@ -2,10 +2,8 @@
 // hits of the same query with the default take (every passing pair in the canonical order) after dropping every hit whose group
 // occurred earlier in that list, cut at k — per query.  One sweep and one small table give that answer on the GPU:
 //
-//   group_sweep_kernel    exact_kernel's streaming geometry with every variant stripped (lane = row, 64-row tiles per wave, 128-B
-//                         stages through the swizzled LDS tile, queries through the constant address space, a persistent grid over
-//                         the run lists of surviving chunks), the scoring terms of ott_exact_dev.h, so the bits are the oracle's.
-//                         Epilogue per (row, query of the pass): composed row mask, NaN drop, cmp_holds, key = ord(score) << 32 |
+//   group_sweep_kernel    sweep_tiles (ott_sweep_dev.h: the streaming tile loop this sweep shares with maxsim_sweep_kernel) and this
+//                         epilogue per (row, query of the pass): composed row mask, NaN drop, cmp_holds, key = ord(score) << 32 |
 //                         ~row; if the key beats a load of table[q][gid[row]], a vector atomicMax on that 64-bit slot.  The load
 //                         in front keeps the atomics at the number of IMPROVEMENTS, not the number of rows.  0 = empty slot (no
 //                         key is 0: rows stay below 2^32 - 16, so ~row >= 15).  The largest key of a group is its best score and,
@@ -19,176 +17,38 @@
 // no grouped query whose tie outcome could be reproduced.  MERGED with nq > 1 is refused (one winner per group ACROSS queries is
 // left out: use PER_QUERY), Path.Mfma too (AUTO takes this sweep and never builds, extends or waits for a plane, as for Manhattan).
 //
-// Queries per pass: 4 (one for a single query).  A lane keeps 8 accumulators and a tail per query beside the 32 staging registers
-// of the next stage: 4 queries are 36 + 32 live floats, which exact_kernel measured as the sweet spot of this geometry (an 8-wide
-// pass needs 233 VGPRs and ran slower than two 4-wide ones); the epilogue here adds a key and a slot address, not a list.
+// The host half of a sweep over grouped rows is shared with ott_maxsim.hip too (declared in ott_internal.h): sweep_prologue (plan,
+// mask, upload, SweepParams, grid), ensure_zeroed (the "zero when found" table protocol), GroupTopK (key table -> host hits) and
+// check_group_ids.  Queries per pass: ott_sweep_dev.h; the epilogue here adds a key and a slot address, not a list.
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 #include <vector>
 
 #include "ott_internal.h"
-#include "ott_exact_dev.h"
+#include "ott_sweep_dev.h"
 
 namespace ott {
 
-constexpr int GS_KC = 32;                   // floats per row per stage: one 128-B line
-constexpr int GS_WAVES = 4;
-constexpr int GS_STAGE_FLOATS = 64 * GS_KC;  // per wave: 8 KB
-constexpr int GS_SMEM = GS_WAVES * GS_STAGE_FLOATS * 4;
-constexpr int GS_BLOCKS_PER_CU = 2;         // the persistent grid of exact_kernel
-constexpr uint32_t GS_NQ = 4;               // queries per pass of a batch
-constexpr uint32_t GS_MAX_LISTS = 1024;     // block lists per query the select kernel writes (merge_rank_kernel takes up to 4096)
+constexpr uint32_t GS_MAX_LISTS = 1024;  // block lists per query the select kernel writes (merge_rank_kernel takes up to 4096)
 
-struct GroupParams {
-    const float* rows;
-    const float* inv;
-    const float* queries;  // [nq_pad * dimq], zero padded
-    const float* qinv;     // [nq_pad]
-    const uint64_t* row_mask;
-    uint64_t row_mask_bits;
-    const ott_run* runs;
-    const uint32_t* tile_prefix;  // [n_runs + 1]
-    const uint32_t* gid;          // [n] dense group ids, every one < n_groups (checked on the host when they were set)
-    unsigned long long* table;    // [NQ][n_groups] best key per (query of the pass, group); 0 = empty
+struct GroupParams : SweepParams {
+    unsigned long long* table;  // [NQ][n_groups] best key per (query of the pass, group); 0 = empty
     uint32_t n_groups;
-    uint32_t ld, dim, dimq;
-    uint32_t n_runs, n_tiles;
-    uint32_t q0, nq_total;
-    uint32_t metric, take_max, cmp, reduce;
+    uint32_t cmp;
     float thr;
 };
 
 template <int MK, int NQ>
-__global__ __launch_bounds__(64 * GS_WAVES) void group_sweep_kernel(GroupParams p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* st = smem + wave * GS_STAGE_FLOATS;
+__global__ __launch_bounds__(64 * SW_WAVES) void group_sweep_kernel(GroupParams p) {
     const bool take_max = p.take_max != 0;
-    const uint32_t nq_here = (p.nq_total - p.q0) < (uint32_t)NQ ? (p.nq_total - p.q0) : (uint32_t)NQ;
-    // wave-uniform, read-only inputs through the CONSTANT address space: always scalar loads (see exact_kernel)
-    typedef __attribute__((address_space(4))) const float* CF32;
-    typedef __attribute__((address_space(4))) const uint32_t* CU32;
-    typedef __attribute__((address_space(4))) const ott_run* CRUN;
-    const CF32 Q = (CF32)(p.queries + (size_t)p.q0 * p.dimq);
-    const CU32 tile_prefix = (CU32)p.tile_prefix;
-    const CRUN runs = (CRUN)p.runs;
-    float qinv[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) qinv[q] = (uint32_t)q < nq_here ? p.qinv[p.q0 + q] : 0.0f;
-
-    const uint32_t gw = blockIdx.x * GS_WAVES + wave, nw = gridDim.x * GS_WAVES;
-    const int sw = (lane >> 1) & 7;
-    const uint32_t nstages = (p.ld + GS_KC - 1) / GS_KC;
-    const int lrow = lane >> 3;  // row within an 8-row load group
-    const int lslot = lane & 7;  // 16-B slot within the 128-B line
-    // its float offset, kept inside a short row (dim < 29): the staging loads are unconditional, so a slot past the row's end must
-    // not make the LAST row of the store read past the allocation
-    const uint32_t lsl4 = ((uint32_t)lslot * 4 < p.ld) ? (uint32_t)lslot * 4 : 0u;
-
-    for (uint32_t t = gw; t < p.n_tiles; t += nw) {
-        // tile -> run of surviving chunks (wave-uniform scalar search)
-        uint32_t lo = 0, hi = p.n_runs;
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (tile_prefix[mid] <= t) lo = mid;
-            else hi = mid;
-        }
-        const uint64_t run_start = runs[lo].start, run_count = runs[lo].count;
-        const uint64_t off = (uint64_t)(t - tile_prefix[lo]) * 64;
-        const uint64_t row0 = run_start + off;
-        const uint32_t cnt = (run_count - off) < 64 ? (uint32_t)(run_count - off) : 64u;
-        const uint64_t my_row = row0 + lane;
-        bool valid = (uint32_t)lane < cnt;
-        if (p.row_mask != nullptr && valid && my_row < p.row_mask_bits)
-            valid = (p.row_mask[my_row >> 6] >> (my_row & 63)) & 1;  // src/vec.rs:231-237
-        if (__ballot(valid) == 0) continue;  // whole tile masked: its rows are never read
-
-        // the row's group and inverse norm are fetched now and used after the K loop: their latency hides behind the stages
-        float vinv = 0.0f;
-        uint32_t g = 0;
-        if (valid) {
-            g = p.gid[my_row];
-            if (p.metric == OTT_METRIC_COSINE) vinv = p.inv[my_row];
-        }
-        float acc[NQ][8];
-        float tail[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            tail[q] = 0.0f;
-#pragma unroll
-            for (int l = 0; l < 8; l++) acc[q][l] = 0.0f;
-        }
-        // Branch-free staging: every load is always issued (rows past a short tile's end are clamped to its last row, a column
-        // group past `ld` in the last stage re-reads stage 0) and the out-of-range values are zeroed when they go to LDS
-        v4f R[8];
-        const float* rp[8];
-        bool rok[8];
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-            const uint32_t row = 8 * m + lrow;
-            rok[m] = row < cnt;
-            rp[m] = p.rows + (row0 + (rok[m] ? row : cnt - 1)) * (uint64_t)p.ld + lsl4;
-        }
-        auto load_stage = [&](uint32_t s) {
-            const uint32_t soff = (s * GS_KC + lslot * 4 < p.ld) ? s * GS_KC : 0u;
-#pragma unroll
-            for (int m = 0; m < 8; m++) R[m] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(rp[m] + soff));  // streamed once per pass
-        };
-        load_stage(0);
-        for (uint32_t s = 0; s < nstages; s++) {
-            const bool cok = s * GS_KC + lslot * 4 < p.ld;
-#pragma unroll
-            for (int m = 0; m < 8; m++) {
-                const int row = 8 * m + lrow;
-                const bool ok = rok[m] & cok;
-                const v4f v = R[m];
-                *reinterpret_cast<float4*>(st + row * GS_KC + ((lslot ^ ((row >> 1) & 7)) << 2)) =
-                    make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
-            }
-            wave_sync();
-            if (s + 1 < nstages) load_stage(s + 1);
-#pragma unroll
-            for (int j = 0; j < GS_KC / 8; j++) {
-                const uint32_t col = s * GS_KC + 8 * j;
-                if (col < p.dim) {
-                    const float4 a = *reinterpret_cast<const float4*>(st + lane * GS_KC + (((2 * j) ^ sw) << 2));
-                    const float4 b = *reinterpret_cast<const float4*>(st + lane * GS_KC + (((2 * j + 1) ^ sw) << 2));
-                    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-                    if (col + 8 <= p.dim) {
-                        // one chunks_exact(8) step: acc = acc + term(q, v)   (vec_compute.rs:12-13, 39-42); every slot of the
-                        // pass is computed (the query block is zero padded): no per-query branch
-#pragma unroll
-                        for (int q = 0; q < NQ; q++) {
-                            const CF32 qp = Q + (size_t)q * p.dimq + col;
-#pragma unroll
-                            for (int l = 0; l < 8; l++) acc[q][l] = __fadd_rn(acc[q][l], exact_term<MK>(qp[l], x[l]));
-                        }
-                    } else {
-                        // remainder: sequential sum of the last dim % 8 terms (vec_compute.rs:15-21, 44-53)
-                        const uint32_t nt = p.dim - col;
-#pragma unroll
-                        for (int q = 0; q < NQ; q++) {
-                            const CF32 qp = Q + (size_t)q * p.dimq + col;
-#pragma unroll
-                            for (int l = 0; l < 7; l++)
-                                if ((uint32_t)l < nt) tail[q] = __fadd_rn(tail[q], exact_term<MK>(qp[l], x[l]));
-                        }
-                    }
-                }
-            }
-            wave_sync();
-        }
-
-        // score -> filter -> key -> the group's slot
+    // score -> filter -> key -> the group's slot
+    sweep_tiles<MK, NQ>(p, [&](uint64_t my_row, bool valid, uint32_t g, const float (&sc)[NQ], uint32_t nq_here) {
 #pragma unroll
         for (int q = 0; q < NQ; q++) {
             if ((uint32_t)q < nq_here) {
-                float s = __fadd_rn(reduce8(acc[q], p.reduce), tail[q]);
-                if (p.metric == OTT_METRIC_COSINE) s = __fmul_rn(__fmul_rn(s, qinv[q]), vinv);  // vec_compute.rs:31
-                const bool pass = valid && !(s != s) && cmp_holds(s, p.cmp, p.thr);             // NaN dropped: vec_compute.rs:237
+                const float s = sc[q];
+                const bool pass = valid && !(s != s) && cmp_holds(s, p.cmp, p.thr);  // NaN dropped: vec_compute.rs:237
                 if (pass) {
                     const unsigned long long key = ((unsigned long long)ord_of(s, take_max) << 32) | (uint32_t)(~(uint32_t)my_row);
                     unsigned long long* slot = p.table + (size_t)q * p.n_groups + g;
@@ -198,7 +58,7 @@ __global__ __launch_bounds__(64 * GS_WAVES) void group_sweep_kernel(GroupParams 
                 }
             }
         }
-    }
+    });
 }
 
 // One wave per workgroup; blockIdx.x = list, blockIdx.y = query of the pass.  The wave walks tiles of 64 slots, list by list
@@ -279,14 +139,10 @@ __global__ __launch_bounds__(256) void group_gather_kernel(const uint32_t* __res
 
 namespace {
 
-uint64_t now_ns() {
-    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 template <int MK>
 int launch_sweep_mk(ott_store* s, const GroupParams& p, uint32_t nq_tile, uint32_t grid) {
-    if (nq_tile == 1) hipLaunchKernelGGL((group_sweep_kernel<MK, 1>), dim3(grid), dim3(64 * GS_WAVES), GS_SMEM, s->stream, p);
-    else hipLaunchKernelGGL((group_sweep_kernel<MK, (int)GS_NQ>), dim3(grid), dim3(64 * GS_WAVES), GS_SMEM, s->stream, p);
+    if (nq_tile == 1) hipLaunchKernelGGL((group_sweep_kernel<MK, 1>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
+    else hipLaunchKernelGGL((group_sweep_kernel<MK, (int)SW_NQ>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
     OTT_HIP(hipGetLastError());
     return OTT_OK;
 }
@@ -299,7 +155,7 @@ int launch_sweep(ott_store* s, const GroupParams& p, uint32_t nq_tile, uint32_t 
     }
 }
 
-int launch_select(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint32_t k, int E, Cand* lists, uint32_t n_lists) {
+int launch_group_select(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint32_t k, int E, Cand* lists, uint32_t n_lists) {
 #define OTT_GSEL(Ev)                                                                                                                       \
     if (E == Ev) {                                                                                                                         \
         hipLaunchKernelGGL((group_select_kernel<Ev>), dim3(n_lists, nq_here), dim3(64), 0, s->stream, table, n_groups, q0, k, lists, n_lists, \
@@ -312,129 +168,154 @@ int launch_select(ott_store* s, unsigned long long* table, uint32_t n_groups, ui
     return fail(OTT_ERR_INVALID, "group select: bad E");
 }
 
+int launch_group_compact(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint64_t* keys, uint32_t* qs,
+                         unsigned long long* cursor, uint64_t cap) {
+    uint32_t blocks = (n_groups + 255) / 256;
+    if (blocks > (uint32_t)s->n_cu * 8) blocks = (uint32_t)s->n_cu * 8;
+    hipLaunchKernelGGL(group_compact_kernel, dim3(blocks, nq_here), dim3(256), 0, s->stream, table, n_groups, q0, keys, qs, cursor, cap);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+
 // The grouped query on a context whose `mu` the caller holds (and the owner's `rw`, shared).  k_eff = min(k, n_groups) >= 1.
 int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats_out) {
     int rc;
     OTT_HIP(use_device(s));
     const uint64_t t0 = now_ns();
     ott_stats st;
-    memset(&st, 0, sizeof(st));
     const uint32_t nq = d->nq, ng = s->n_groups;
+    GroupParams p{};
+    uint32_t grid = 0;
+    if ((rc = sweep_prologue(s, d, &st, &p, &grid))) return rc;
+    if (grid != 0) {
+        const uint32_t tile = nq == 1 ? 1u : SW_NQ;
+        if ((rc = ensure_zeroed(s, s->d_gtable, s->gtable_clean, (size_t)tile * ng * 8))) return rc;
+        p.table = (unsigned long long*)s->d_gtable.p;
+        p.n_groups = ng;
+        p.cmp = d->filter_cmp;
+        p.thr = d->filter_thr;
+
+        GroupTopK tk;
+        tk.n_groups = ng;
+        tk.nq = nq;
+        tk.k = k_eff;
+        tk.take_max = p.take_max != 0;
+        if ((rc = tk.prepare(s, "ott_query_groups: more than 2^32 - 16 (query, group) pairs; use take(k) with k <= 512 or fewer queries"))) return rc;
+        const bool timing = stats_out != nullptr;
+        if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
+        for (uint32_t ps = 0; ps < st.passes; ps++) {
+            p.q0 = ps * tile;
+            if ((rc = launch_sweep(s, p, tile, grid))) return rc;
+            if ((rc = tk.pass(s, p.table, p.q0, (nq - p.q0) < tile ? (nq - p.q0) : tile))) return rc;
+        }
+        if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
+        if ((rc = tk.finish(s, timing, out, n_out, n_per_query))) return rc;
+        if (timing) read_exact_events(s, &st);
+    }
+    st.total_ns = now_ns() - t0;
+    if (stats_out) *stats_out = st;
+    return OTT_OK;
+}
+
+}  // namespace
+
+// Stats, run plan, composed row mask, tile prefix and the upload of a sweep over grouped rows; `p` gets what the store, the
+// descriptor and the plan decide (q0 and whatever the kernel's own struct adds are the caller's).  *grid: the persistent grid — a
+// workgroup of four waves per four tiles, at most SW_BLOCKS_PER_CU per CU: from 4 x SW_BLOCKS_PER_CU x n_cu tiles (2048 tiles =
+// 131072 rows on 256 CUs) a wave takes a second tile — or 0: no row survives the chunk mask, `st` is complete and nothing was uploaded.
+int sweep_prologue(ott_store* s, const ott_query_desc* d, ott_stats* st, SweepParams* p, uint32_t* grid) {
+    int rc;
+    memset(st, 0, sizeof(*st));
+    const uint32_t nq = d->nq;
     RunPlan pl;
     make_run_plan(s, d->chunk_mask, pl);
-    st.path_used = OTT_PATH_EXACT;
-    st.total_chunks = pl.total_chunks;
-    st.evaluated_chunks = pl.evaluated;
-    st.pruned_chunks = pl.total_chunks - pl.evaluated;
-    st.vectors_compared = pl.rows_scored * nq;
-    if (pl.rows_scored == 0) {
-        st.total_ns = now_ns() - t0;
-        if (stats_out) *stats_out = st;
-        return OTT_OK;
-    }
-    const uint64_t* d_mask = nullptr;
-    uint64_t mask_bits = 0;
-    if ((rc = compose_row_mask(s, d, &d_mask, &mask_bits))) return rc;
+    st->path_used = OTT_PATH_EXACT;
+    st->total_chunks = pl.total_chunks;
+    st->evaluated_chunks = pl.evaluated;
+    st->pruned_chunks = pl.total_chunks - pl.evaluated;
+    st->vectors_compared = pl.rows_scored * nq;
+    *grid = 0;
+    if (pl.rows_scored == 0) return OTT_OK;
+    if ((rc = compose_row_mask(s, d, &p->row_mask, &p->row_mask_bits))) return rc;
     const std::vector<uint32_t> prefix = tile_prefix(pl, 64);
-    const uint32_t n_tiles = prefix.back();
     if ((rc = upload_exact_inputs(s, d->queries, nq, pl, prefix))) return rc;
+    st->passes = nq == 1 ? 1u : (nq + SW_NQ - 1) / SW_NQ;
+    st->bytes_scanned = (uint64_t)st->passes * pl.rows_scored * ((uint64_t)s->dim * 4 + 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));  // (+ 4: the group id)
+    p->rows = s->d_rows;
+    p->inv = s->d_inv;
+    p->queries = (const float*)s->d_queries.p;
+    p->qinv = (const float*)((const char*)s->d_queries.p + s->in_off_qinv);
+    p->runs = (const ott_run*)((const char*)s->d_queries.p + s->in_off_runs);
+    p->tile_prefix = (const uint32_t*)((const char*)s->d_queries.p + s->in_off_prefix);
+    p->gid = s->d_gid;
+    p->ld = s->ld;
+    p->dim = s->dim;
+    p->dimq = s->dimq;
+    p->n_runs = (uint32_t)pl.runs.size();
+    p->n_tiles = prefix.back();
+    p->nq_total = nq;
+    p->metric = d->metric;
+    p->take_max = d->take == OTT_TAKE_MAX;
+    p->reduce = s->reduce;
+    *grid = std::min((p->n_tiles + SW_WAVES - 1) / SW_WAVES, (uint32_t)s->n_cu * SW_BLOCKS_PER_CU);
+    if (*grid < 1) *grid = 1;
+    return OTT_OK;
+}
 
-    const uint32_t tile = nq == 1 ? 1u : GS_NQ;
-    const uint32_t passes = (nq + tile - 1) / tile;
-    // the table: zero when a query finds it — zeroed when it is (re)allocated or a query failed half way, and left zeroed by every
-    // query's select / compact kernel
-    const size_t tab_bytes = (size_t)tile * ng * 8;
-    if (s->d_gtable.cap < tab_bytes || !s->gtable_clean) {
-        if ((rc = s->d_gtable.ensure(tab_bytes))) return rc;
-        OTT_HIP(hipMemsetAsync(s->d_gtable.p, 0, s->d_gtable.cap, s->stream));
+// A table that is zero when a query finds it: zeroed here when it is (re)allocated or a query failed half way (`clean` is false),
+// left zeroed by the kernel that reads it; the caller sets `clean` again once the stream has drained.
+int ensure_zeroed(ott_store* s, DevBuf& b, bool& clean, size_t bytes) {
+    int rc;
+    if (b.cap < bytes || !clean) {
+        if ((rc = b.ensure(bytes))) return rc;
+        OTT_HIP(hipMemsetAsync(b.p, 0, b.cap, s->stream));
     }
-    s->gtable_clean = false;
-    unsigned long long* table = (unsigned long long*)s->d_gtable.p;
+    clean = false;
+    return OTT_OK;
+}
 
-    GroupParams p;
-    memset(&p, 0, sizeof(p));
-    p.rows = s->d_rows;
-    p.inv = s->d_inv;
-    p.queries = (const float*)s->d_queries.p;
-    p.qinv = (const float*)((const char*)s->d_queries.p + s->in_off_qinv);
-    p.row_mask = d_mask;
-    p.row_mask_bits = mask_bits;
-    p.runs = (const ott_run*)((const char*)s->d_queries.p + s->in_off_runs);
-    p.tile_prefix = (const uint32_t*)((const char*)s->d_queries.p + s->in_off_prefix);
-    p.gid = s->d_gid;
-    p.table = table;
-    p.n_groups = ng;
-    p.ld = s->ld;
-    p.dim = s->dim;
-    p.dimq = s->dimq;
-    p.n_runs = (uint32_t)pl.runs.size();
-    p.n_tiles = n_tiles;
-    p.nq_total = nq;
-    p.metric = d->metric;
-    p.take_max = d->take == OTT_TAKE_MAX;
-    p.cmp = d->filter_cmp;
-    p.thr = d->filter_thr;
-    p.reduce = s->reduce;
-    // the persistent grid: a workgroup of four waves per four tiles, at most GS_BLOCKS_PER_CU per CU — from
-    // 4 x GS_BLOCKS_PER_CU x n_cu tiles (2048 tiles = 131072 rows on 256 CUs) a wave takes a second tile
-    uint32_t grid = (n_tiles + GS_WAVES - 1) / GS_WAVES;
-    const uint32_t grid_cap = (uint32_t)s->n_cu * GS_BLOCKS_PER_CU;
-    if (grid > grid_cap) grid = grid_cap;
-    if (grid < 1) grid = 1;
+int GroupTopK::prepare(ott_store* s, const char* too_many_pairs) {
+    int rc;
+    lists_path = k <= 512;
+    E = lists_path ? list_E(k) : 1;
+    KS = 64u * (uint32_t)E;
+    n_lists = std::min((n_groups + 63) / 64, GS_MAX_LISTS);
+    pair_cap = (uint64_t)nq * n_groups;
+    if (lists_path) return s->d_lists.ensure((size_t)nq * n_lists * KS * sizeof(Cand));
+    if (too_many_pairs && pair_cap > 0xFFFFFFF0ull) return fail(OTT_ERR_UNSUPPORTED, too_many_pairs);
+    if ((rc = ensure_group_pairs(s, pair_cap))) return rc;
+    if ((rc = s->d_gctl.ensure(64))) return rc;
+    OTT_HIP(hipMemsetAsync(s->d_gctl.p, 0, 8, s->stream));
+    return OTT_OK;
+}
 
-    const bool lists_path = k_eff <= 512;
-    const int E = lists_path ? list_E(k_eff) : 1;
-    const uint32_t KS = 64u * (uint32_t)E;
-    uint32_t n_lists = (ng + 63) / 64;
-    if (n_lists > GS_MAX_LISTS) n_lists = GS_MAX_LISTS;
-    const uint64_t pair_cap = (uint64_t)nq * ng;
-    if (lists_path) {
-        if ((rc = s->d_lists.ensure((size_t)nq * n_lists * KS * sizeof(Cand)))) return rc;
-    } else {
-        if (pair_cap > 0xFFFFFFF0ull) return fail(OTT_ERR_UNSUPPORTED, "ott_query_groups: more than 2^32 - 16 (query, group) pairs; use take(k) with k <= 512 or fewer queries");
-        if ((rc = ensure_group_pairs(s, pair_cap))) return rc;
-        if ((rc = s->d_gctl.ensure(64))) return rc;
-        OTT_HIP(hipMemsetAsync(s->d_gctl.p, 0, 8, s->stream));
-    }
-    const bool timing = stats_out != nullptr;
-    if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
-    for (uint32_t ps = 0; ps < passes; ps++) {
-        p.q0 = ps * tile;
-        const uint32_t nq_here = (nq - p.q0) < tile ? (nq - p.q0) : tile;
-        if ((rc = launch_sweep(s, p, tile, grid))) return rc;
-        if (lists_path) {
-            if ((rc = launch_select(s, table, ng, p.q0, nq_here, (uint32_t)k_eff, E, (Cand*)s->d_lists.p, n_lists))) return rc;
-        } else {
-            uint32_t blocks = (ng + 255) / 256;
-            if (blocks > (uint32_t)s->n_cu * 8) blocks = (uint32_t)s->n_cu * 8;
-            hipLaunchKernelGGL(group_compact_kernel, dim3(blocks, nq_here), dim3(256), 0, s->stream, table, ng, p.q0, (uint64_t*)s->l_keysA.p, (uint32_t*)s->l_qA.p,
-                               (unsigned long long*)s->d_gctl.p, pair_cap);
-            OTT_HIP(hipGetLastError());
-        }
-    }
-    if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
-    st.passes = passes;
-    st.bytes_scanned = (uint64_t)passes * pl.rows_scored * ((uint64_t)s->dim * 4 + 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));  // (+ 4: the group id)
+int GroupTopK::pass(ott_store* s, unsigned long long* table, uint32_t q0, uint32_t nq_here) {
+    if (lists_path) return launch_group_select(s, table, n_groups, q0, nq_here, (uint32_t)k, E, (Cand*)s->d_lists.p, n_lists);
+    return launch_group_compact(s, table, n_groups, q0, nq_here, (uint64_t*)s->l_keysA.p, (uint32_t*)s->l_qA.p, (unsigned long long*)s->d_gctl.p, pair_cap);
+}
 
+int GroupTopK::finish(ott_store* s, bool timing, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query) {
+    int rc;
     uint64_t total = 0;
     if (lists_path) {
         // results block in pinned host memory, as run_exact lays it out: [counts (nq x u64, padded to 64 B) | hits (nq x KS)]
         const size_t cnt_pad = (((size_t)nq * sizeof(uint64_t)) + 63) & ~(size_t)63;
-        const size_t res_bytes = cnt_pad + (size_t)nq * KS * sizeof(ott_hit);
-        if ((rc = s->h_hits.ensure(res_bytes))) return rc;
+        if ((rc = s->h_hits.ensure(cnt_pad + (size_t)nq * KS * sizeof(ott_hit)))) return rc;
         void* mapped = nullptr;
         OTT_HIP(hipHostGetDevicePointer(&mapped, s->h_hits.p, 0));
-        if ((rc = launch_merge(s, (const Cand*)s->d_lists.p, n_lists, KS, (uint64_t)n_lists * KS, nq, (uint32_t)k_eff, E, p.take_max != 0, s->base_offset,
+        if ((rc = launch_merge(s, (const Cand*)s->d_lists.p, n_lists, KS, (uint64_t)n_lists * KS, nq, (uint32_t)k, E, take_max, index_is_group ? 0 : s->base_offset,
                                (ott_hit*)((char*)mapped + cnt_pad), KS, (uint64_t*)mapped, 0)))
             return rc;
         if (timing) OTT_HIP(hipEventRecord(s->ev[5], s->stream));
         OTT_HIP(hipStreamSynchronize(s->stream));
         s->gtable_clean = true;
+        if (also_clean) *also_clean = true;
         const char* hh = (const char*)s->h_hits.p;
         const uint64_t* counts = (const uint64_t*)hh;
         const ott_hit* hits = (const ott_hit*)(hh + cnt_pad);
         for (uint32_t q = 0; q < nq; q++) {
-            const uint64_t cq = counts[q];
+            uint64_t cq = counts[q];
+            if (index_is_group && cq > k) cq = k;
             if (cq) memcpy(out + total, hits + (size_t)q * KS, (size_t)cq * sizeof(ott_hit));
             if (n_per_query) n_per_query[q] = cq;
             total += cq;
@@ -444,45 +325,38 @@ int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* o
         OTT_HIP(hipMemcpyAsync(&n_pairs, s->d_gctl.p, 8, hipMemcpyDeviceToHost, s->stream));
         OTT_HIP(hipStreamSynchronize(s->stream));
         s->gtable_clean = true;
+        if (also_clean) *also_clean = true;
         if (n_pairs > pair_cap) n_pairs = pair_cap;
         std::vector<std::vector<ott_hit>> lists;
-        if ((rc = sort_group_pairs(s, n_pairs, nq, p.take_max != 0, k_eff, lists))) return rc;
+        if ((rc = sort_group_pairs(s, n_pairs, nq, take_max, k, lists, index_is_group ? n_groups : 0))) return rc;
         if (timing) {
             OTT_HIP(hipEventRecord(s->ev[5], s->stream));
             OTT_HIP(hipStreamSynchronize(s->stream));
         }
         for (uint32_t q = 0; q < nq; q++) {
-            const std::vector<ott_hit>& l = lists[q];
+            std::vector<ott_hit>& l = lists[q];
+            if (index_is_group)
+                for (ott_hit& h : l) h.index -= s->base_offset;  // the sort path's hits are rows of the store; these are groups
             if (!l.empty()) memcpy(out + total, l.data(), l.size() * sizeof(ott_hit));
             if (n_per_query) n_per_query[q] = l.size();
             total += l.size();
         }
     }
     if (n_out) *n_out = total;
-    if (timing) read_exact_events(s, &st);
-    st.total_ns = now_ns() - t0;
-    if (stats_out) *stats_out = st;
     return OTT_OK;
 }
 
-}  // namespace
-
-// the table's top-k for ott_maxsim.hip (ott_internal.h): the launches run_groups makes, under names other files can call
-uint32_t group_select_lists(uint32_t n_groups) {
-    const uint32_t n_lists = (n_groups + 63) / 64;
-    return n_lists > GS_MAX_LISTS ? GS_MAX_LISTS : n_lists;
-}
-
-int launch_group_select(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint32_t k, int E, Cand* lists, uint32_t n_lists) {
-    return launch_select(s, table, n_groups, q0, nq_here, k, E, lists, n_lists);
-}
-
-int launch_group_compact(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint64_t* keys, uint32_t* qs,
-                         unsigned long long* cursor, uint64_t cap) {
-    uint32_t blocks = (n_groups + 255) / 256;
-    if (blocks > (uint32_t)s->n_cu * 8) blocks = (uint32_t)s->n_cu * 8;
-    hipLaunchKernelGGL(group_compact_kernel, dim3(blocks, nq_here), dim3(256), 0, s->stream, table, n_groups, q0, keys, qs, cursor, cap);
-    OTT_HIP(hipGetLastError());
+// What ott_query_groups and ott_query_maxsim (`fn`) ask of the group ids: they are set and cover the store's rows.  Asked before
+// the lock, and again under it (`locked`): a set_groups may have come in between.  A multi-GPU store's ids live on its shards.
+int check_group_ids(const ott_store* s, const char* fn, bool locked) {
+    const std::string name(fn);
+    if (s->n_groups == 0) return fail(OTT_ERR_INVALID, name + ": no group ids are set (ott_store_set_groups)");
+    if (locked) {
+        if (s->gid_n != s->n) return fail(OTT_ERR_INVALID, name + ": the group ids no longer cover the store's rows (set them again)");
+    } else if (!s->multi && s->gid_n != ott_store_len(s)) {  // staged rows count: they were appended
+        return fail(OTT_ERR_INVALID, name + ": the group ids cover " + std::to_string(s->gid_n) + " rows, the store holds " + std::to_string(ott_store_len(s)) +
+                                         " (rows were appended since ott_store_set_groups: set them again)");
+    }
     return OTT_OK;
 }
 
@@ -594,20 +468,16 @@ int ott_query_groups(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64
     if (d->mode == OTT_MODE_MERGED && d->nq > 1)
         return fail(OTT_ERR_UNSUPPORTED, "ott_query_groups: a merged list over several queries is not served (one winner per group across queries); use PER_QUERY");
     if (d->path == OTT_PATH_MFMA) return fail(OTT_ERR_UNSUPPORTED, "ott_query_groups: the MFMA path does not serve grouped queries; use path AUTO or EXACT");
-    if (s->n_groups == 0) return fail(OTT_ERR_INVALID, "ott_query_groups: no group ids are set (ott_store_set_groups)");
     if (n_out) *n_out = 0;
     if (n_per_query)
         for (uint32_t i = 0; i < d->nq; i++) n_per_query[i] = 0;
     if (stats) memset(stats, 0, sizeof(*stats));
+    if ((rc = check_group_ids(s, "ott_query_groups", false))) return rc;
     if (s->multi) return multi_query_groups(s, d, out, cap, n_out, n_per_query, stats);
-    if (s->gid_n != ott_store_len(s))  // staged rows count: they were appended
-        return fail(OTT_ERR_INVALID, "ott_query_groups: the group ids cover " + std::to_string(s->gid_n) + " rows, the store holds " + std::to_string(ott_store_len(s)) +
-                                         " (rows were appended since ott_store_set_groups: set them again)");
     ott::host::SharedLock rd;  // the corpus and the group ids cannot change while this query runs
     if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
     // what the checks above read without the lock is read again, and k_eff only here: a set_groups may have come in between
-    if (s->n_groups == 0) return fail(OTT_ERR_INVALID, "ott_query_groups: no group ids are set (ott_store_set_groups)");
-    if (s->gid_n != s->n) return fail(OTT_ERR_INVALID, "ott_query_groups: the group ids no longer cover the store's rows (set them again)");
+    if ((rc = check_group_ids(s, "ott_query_groups", true))) return rc;
     const uint64_t k_eff = d->k < s->n_groups ? d->k : s->n_groups;
     if (cap < k_eff * d->nq) return fail(OTT_ERR_INVALID, "ott_query_groups: output capacity is smaller than nq * min(k, n_groups)");
     if (!out && cap) return fail(OTT_ERR_INVALID, "ott_query_groups: out is NULL");

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -55,6 +56,10 @@ inline bool attr_needed(const std::atomic<uint64_t>& seen, int device) {
 }
 inline void attr_done(std::atomic<uint64_t>& seen, int device) {
     if (device <= 63) seen.fetch_or(1ull << (device & 63), std::memory_order_release);
+}
+
+inline uint64_t now_ns() {
+    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 // ---- device buffers that grow on demand -----------------------------------------------------
@@ -678,13 +683,30 @@ void make_run_plan(const ott_store* s, const uint64_t* chunk_mask, RunPlan& pl);
 // query's hold group ids)
 int sort_group_pairs(ott_store* s, uint64_t n, uint32_t nq, bool take_max, uint64_t k, std::vector<std::vector<ott_hit>>& lists, uint64_t id_span = 0);
 int ensure_group_pairs(ott_store* s, uint64_t cap);  // the pair arrays for up to `cap` pairs
-// ott_group.hip's top-k over a table of [nq_here][n_groups] 8-byte keys (0 = empty), for ott_maxsim.hip: the select kernel's block
-// lists (k <= 512, E = list_E(k); at most group_select_lists(n_groups) lists of 64 E entries per query) or the compact kernel's
-// (key, query) pairs behind `cursor`.  Both leave the slots they read zeroed.
-uint32_t group_select_lists(uint32_t n_groups);
-int launch_group_select(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint32_t k, int E, Cand* lists, uint32_t n_lists);
-int launch_group_compact(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint64_t* keys, uint32_t* qs,
-                         unsigned long long* cursor, uint64_t cap);
+// The host half of a sweep over grouped rows (ott_group.hip; ott_maxsim.hip uses it too).  sweep_prologue: stats, run plan, mask,
+// upload, the kernel parameters of ott_sweep_dev.h and the grid (0 = no rows).  ensure_zeroed: a table that is zero when a query
+// finds it.  check_group_ids: the ids are set and cover the store, for entry point `fn`, before and under the lock.
+struct SweepParams;
+int sweep_prologue(ott_store* s, const ott_query_desc* d, ott_stats* st, SweepParams* p, uint32_t* grid);
+int ensure_zeroed(ott_store* s, DevBuf& b, bool& clean, size_t bytes);
+int check_group_ids(const ott_store* s, const char* fn, bool locked);
+// The top-k over a table of [queries of a pass][n_groups] 8-byte keys in d_gtable (0 = empty): prepare, pass() after every sweep
+// (k <= 512: the select kernel's block lists; above: the compact kernel's (key, query) pairs; both leave the slots zeroed), finish
+// (launch_merge into the pinned block or sort_group_pairs, hits and counts out, gtable_clean — and *also_clean — after the sync).
+struct GroupTopK {
+    uint32_t n_groups = 0, nq = 0;  // nq: the queries whose lists come out
+    uint64_t k = 0;
+    bool take_max = false;
+    bool index_is_group = false;    // the keys' low words are ~group, not ~row: a hit's index is the group, the count is cut at k
+    bool* also_clean = nullptr;
+    bool lists_path = false;        // from here on: prepare's
+    int E = 1;
+    uint32_t KS = 0, n_lists = 0;
+    uint64_t pair_cap = 0;
+    int prepare(ott_store* s, const char* too_many_pairs);  // the refusal's text for more than 2^32 - 16 pairs (nullptr: cannot happen)
+    int pass(ott_store* s, unsigned long long* table, uint32_t q0, uint32_t nq_here);
+    int finish(ott_store* s, bool timing, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query);
+};
 // ott_multi.hip: grouped search on a multi-GPU store
 int multi_set_groups(ott_store* ms, const uint32_t* gid_host, uint64_t n, uint32_t n_groups);
 int multi_clear_groups(ott_store* ms);

@@ -23,7 +23,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -39,10 +38,6 @@ using namespace ott;
 namespace {
 
 constexpr uint64_t NOT_YET = ~0ull;  // start[] of a shard the appends have not reached
-
-uint64_t now_ns() {
-    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 using ott::host::ShardPool;  // one persistent host thread per shard (ott_host.h: the rayon pool of src/meta.rs:678, sized to the GPUs)
 
