@@ -15,6 +15,7 @@ use std::os::raw::{c_char, c_int, c_void};
 
 pub const OTT_ABI_VERSION: c_int = 4;
 pub const OTT_COMM_ID_BYTES: usize = 128;
+pub const OTT_GROUP_SIZE_MAX: u32 = 16; // ott_query_groups_top: the largest group_size
 
 // ott_status
 pub const OTT_OK: c_int = 0;
@@ -185,6 +186,7 @@ extern "C" {
     pub fn ott_store_clear_groups(s: *mut ott_store) -> c_int;
     pub fn ott_store_group_count(s: *const ott_store) -> u32;
     pub fn ott_query_groups(s: *mut ott_store, d: *const ott_query_desc, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int;
+    pub fn ott_query_groups_top(s: *mut ott_store, d: *const ott_query_desc, group_size: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, group_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // group_of_hit may be null
     pub fn ott_query_maxsim(s: *mut ott_store, d: *const ott_query_desc, out: *mut ott_hit, cap: u64, n_out: *mut u64, stats: *mut ott_stats) -> c_int;
     pub fn ott_query_device(s: *mut ott_store, d: *const ott_query_desc, out_dev: *mut c_void, cap: u64, n_out_dev: *mut c_void, stats: *mut ott_stats) -> c_int;
     pub fn ott_store_sync(s: *mut ott_store) -> c_int;

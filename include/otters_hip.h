@@ -404,6 +404,32 @@ uint32_t ott_store_group_count(const ott_store* s);
 int ott_query_groups(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query,
                      ott_stats* stats);
 
+/* Grouped search with up to group_size hits per group (Qdrant search_groups' and Milvus group_by_field's group_size, Elasticsearch
+ * collapse with inner_hits): the top-10 documents and the best 3 passages of each, from one call.  Let L be the hits of the same
+ * query with the default take (every passing pair in the canonical order: better score, then lower row), after chunk_mask, the
+ * caller's row_mask or the evaluated device mask, the live mask of deleted rows, the score filter and the NaN drop — exactly as in
+ * ott_query_groups.  With group_size = m: (1) a hit of L is kept iff fewer than m earlier hits of L have its group; (2) groups are
+ * ranked by the position of their first kept hit, which is ott_query_groups' ranking of the groups; (3) the first k_eff = min(k,
+ * n_groups) groups are kept; (4) they come out in that rank order, each group's hits (1 .. m of them) contiguous and in their order
+ * in L.  Per query in PER_QUERY mode.  Four metrics, both takes, every comparator; always the canonical tie order, whatever option
+ * "tie_order" says.  A group with fewer than m surviving rows returns what it has.  With m = 1 the output is ott_query_groups' on
+ * every field (and it IS that query: no kernel and no launch is added; group_of_hit then comes from one small gather).
+ * cap >= nq * k_eff * group_size, and group_of_hit — if given — holds as many uint32: [i] = the dense group id of out[i].
+ * n_per_query[q] = the number of HITS of query q.  Stats as ott_query_groups counts them.
+ * m >= 2: the sweep keeps, per (query, group), the m best candidate keys in a table of nq x m x n_groups 8-byte slots (scratch of the
+ * query context, all queries at once) by a cascade of vector atomicMax — a key that takes slot j sends the slot's old key on to slot
+ * j + 1 — the groups are ranked over the first slots by ott_query_groups' own top-k, and the winners' other slots are read back.
+ * Refused on the host before any device work: group_size == 0 or > OTT_GROUP_SIZE_MAX (OTT_ERR_INVALID); OTT_MODE_MERGED with nq > 1
+ * and OTT_PATH_MFMA (OTT_ERR_UNSUPPORTED, as ott_query_groups; AUTO takes the sweep); no group ids set, or ids that cover a different
+ * number of rows than ott_store_len (OTT_ERR_INVALID); nq x group_size x n_groups x 8 bytes above 2 GiB (OTT_ERR_UNSUPPORTED); a
+ * multi-GPU store (OTT_ERR_UNSUPPORTED).  Why the last: a group's second-best row may sit in a shard where the group is not among
+ * that shard's top-k groups (its best row there loses to k other groups' bests), so — unlike for one hit per group — the shards'
+ * lists of k_eff groups do not contain the answer; a second round that asks every shard for the winning groups' rows would be needed.
+ * Takes the store shared, like ott_query_groups (staged appends go first). */
+#define OTT_GROUP_SIZE_MAX 16
+int ott_query_groups_top(ott_store* s, const ott_query_desc* d, uint32_t group_size, ott_hit* out, uint64_t cap, uint64_t* n_out,
+                         uint64_t* n_per_query, uint32_t* group_of_hit /* may be NULL */, ott_stats* stats);
+
 /* Late-interaction (MaxSim) search over grouped rows (an extension; ColBERT / ColPali scoring as Qdrant's multivector MaxSim, Vespa
  * and Milvus serve it): the d->nq query vectors are the TOKENS of ONE query, the rows are token or passage embeddings, the store's
  * group ids (ott_store_set_groups) say which document a row belongs to, and the answer is the top-k DOCUMENTS by

@@ -157,6 +157,7 @@ def lib() -> C.CDLL:
         "ott_store_clear_groups": (i32, [vp]),
         "ott_store_group_count": (u32, [vp]),
         "ott_query_groups": (i32, [vp, vp, vp, u64, vp, vp, vp]),
+        "ott_query_groups_top": (i32, [vp, vp, u32, vp, u64, vp, vp, vp, vp]),
         "ott_query_maxsim": (i32, [vp, vp, vp, u64, vp, vp]),
         "ott_query_device": (i32, [vp, vp, vp, u64, vp, vp]),
         "ott_store_sync": (i32, [vp]),

@@ -20,6 +20,8 @@
 // The host half of a sweep over grouped rows is shared with ott_maxsim.hip too (declared in ott_internal.h): sweep_prologue (plan,
 // mask, upload, SweepParams, grid), ensure_zeroed (the "zero when found" table protocol), GroupTopK (key table -> host hits) and
 // check_group_ids.  Queries per pass: ott_sweep_dev.h; the epilogue here adds a key and a slot address, not a list.
+// ott_group_top.hip (up to m hits per group) uses the same host half, run_groups itself for m = 1, and the select /
+// compact kernels on the first plane of its [query][level][group] table: that is what their q_stride argument is for.
 #include <string.h>
 
 #include <algorithm>
@@ -62,13 +64,14 @@ __global__ __launch_bounds__(64 * SW_WAVES) void group_sweep_kernel(GroupParams 
 }
 
 // One wave per workgroup; blockIdx.x = list, blockIdx.y = query of the pass.  The wave walks tiles of 64 slots, list by list
-// strided, and offers the non-empty ones; the slots it read are left zeroed (the next query's sweep needs no memset).
+// strided, and offers the non-empty ones; the slots it read are left zeroed (the next query's sweep needs no memset).  q_stride:
+// slots between the tables of two queries of the pass (n_groups; group_size x n_groups where ott_group_top.hip keeps deeper planes).
 template <int E>
-__global__ __launch_bounds__(64) void group_select_kernel(unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t k, Cand* lists,
+__global__ __launch_bounds__(64) void group_select_kernel(unsigned long long* table, uint32_t n_groups, uint64_t q_stride, uint32_t q0, uint32_t k, Cand* lists,
                                                           uint32_t n_lists, uint32_t list_stride) {
     const int lane = threadIdx.x;
     const uint32_t qy = blockIdx.y;
-    unsigned long long* tab = table + (size_t)qy * n_groups;
+    unsigned long long* tab = table + (size_t)qy * q_stride;
     const uint32_t n_tiles = (n_groups + 63) / 64;
     WaveList<E> L;
     wl_init(L);
@@ -104,11 +107,11 @@ __global__ __launch_bounds__(64) void group_select_kernel(unsigned long long* ta
 
 // k_eff > 512: every non-empty slot of the pass's table becomes a (key, query) pair behind the cursor — one returning atomic
 // per wave and tile that holds any — and is zeroed.  blockIdx.y = query of the pass.
-__global__ __launch_bounds__(256) void group_compact_kernel(unsigned long long* table, uint32_t n_groups, uint32_t q0, uint64_t* keys, uint32_t* qs,
+__global__ __launch_bounds__(256) void group_compact_kernel(unsigned long long* table, uint32_t n_groups, uint64_t q_stride, uint32_t q0, uint64_t* keys, uint32_t* qs,
                                                             unsigned long long* cursor, uint64_t cap) {
     const int lane = threadIdx.x & 63;
     const uint32_t qy = blockIdx.y;
-    unsigned long long* tab = table + (size_t)qy * n_groups;
+    unsigned long long* tab = table + (size_t)qy * q_stride;
     const uint32_t n_round = (n_groups + 63) & ~63u;  // whole waves stay together for the ballot
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t key = 0;
@@ -155,11 +158,12 @@ int launch_sweep(ott_store* s, const GroupParams& p, uint32_t nq_tile, uint32_t 
     }
 }
 
-int launch_group_select(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint32_t k, int E, Cand* lists, uint32_t n_lists) {
+int launch_group_select(ott_store* s, unsigned long long* table, uint32_t n_groups, uint64_t q_stride, uint32_t q0, uint32_t nq_here, uint32_t k, int E, Cand* lists,
+                        uint32_t n_lists) {
 #define OTT_GSEL(Ev)                                                                                                                       \
     if (E == Ev) {                                                                                                                         \
-        hipLaunchKernelGGL((group_select_kernel<Ev>), dim3(n_lists, nq_here), dim3(64), 0, s->stream, table, n_groups, q0, k, lists, n_lists, \
-                           (uint32_t)(64 * Ev));                                                                                           \
+        hipLaunchKernelGGL((group_select_kernel<Ev>), dim3(n_lists, nq_here), dim3(64), 0, s->stream, table, n_groups, q_stride, q0, k, lists, \
+                           n_lists, (uint32_t)(64 * Ev));                                                                                  \
         OTT_HIP(hipGetLastError());                                                                                                        \
         return OTT_OK;                                                                                                                     \
     }
@@ -168,16 +172,19 @@ int launch_group_select(ott_store* s, unsigned long long* table, uint32_t n_grou
     return fail(OTT_ERR_INVALID, "group select: bad E");
 }
 
-int launch_group_compact(ott_store* s, unsigned long long* table, uint32_t n_groups, uint32_t q0, uint32_t nq_here, uint64_t* keys, uint32_t* qs,
+int launch_group_compact(ott_store* s, unsigned long long* table, uint32_t n_groups, uint64_t q_stride, uint32_t q0, uint32_t nq_here, uint64_t* keys, uint32_t* qs,
                          unsigned long long* cursor, uint64_t cap) {
     uint32_t blocks = (n_groups + 255) / 256;
     if (blocks > (uint32_t)s->n_cu * 8) blocks = (uint32_t)s->n_cu * 8;
-    hipLaunchKernelGGL(group_compact_kernel, dim3(blocks, nq_here), dim3(256), 0, s->stream, table, n_groups, q0, keys, qs, cursor, cap);
+    hipLaunchKernelGGL(group_compact_kernel, dim3(blocks, nq_here), dim3(256), 0, s->stream, table, n_groups, q_stride, q0, keys, qs, cursor, cap);
     OTT_HIP(hipGetLastError());
     return OTT_OK;
 }
 
+}  // namespace
+
 // The grouped query on a context whose `mu` the caller holds (and the owner's `rw`, shared).  k_eff = min(k, n_groups) >= 1.
+// (ott_group_top.hip runs it too: group_size 1 IS this query.)
 int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats_out) {
     int rc;
     OTT_HIP(use_device(s));
@@ -216,8 +223,6 @@ int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* o
     if (stats_out) *stats_out = st;
     return OTT_OK;
 }
-
-}  // namespace
 
 // Stats, run plan, composed row mask, tile prefix and the upload of a sweep over grouped rows; `p` gets what the store, the
 // descriptor and the plan decide (q0 and whatever the kernel's own struct adds are the caller's).  *grid: the persistent grid — a
@@ -290,8 +295,9 @@ int GroupTopK::prepare(ott_store* s, const char* too_many_pairs) {
 }
 
 int GroupTopK::pass(ott_store* s, unsigned long long* table, uint32_t q0, uint32_t nq_here) {
-    if (lists_path) return launch_group_select(s, table, n_groups, q0, nq_here, (uint32_t)k, E, (Cand*)s->d_lists.p, n_lists);
-    return launch_group_compact(s, table, n_groups, q0, nq_here, (uint64_t*)s->l_keysA.p, (uint32_t*)s->l_qA.p, (unsigned long long*)s->d_gctl.p, pair_cap);
+    const uint64_t stride = q_stride ? q_stride : n_groups;
+    if (lists_path) return launch_group_select(s, table, n_groups, stride, q0, nq_here, (uint32_t)k, E, (Cand*)s->d_lists.p, n_lists);
+    return launch_group_compact(s, table, n_groups, stride, q0, nq_here, (uint64_t*)s->l_keysA.p, (uint32_t*)s->l_qA.p, (unsigned long long*)s->d_gctl.p, pair_cap);
 }
 
 int GroupTopK::finish(ott_store* s, bool timing, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query) {

@@ -309,7 +309,8 @@ struct ott_store {
     // ott_store_set_groups and freed by ott_store_clear_groups; nullptr = no groups (and nothing else below exists).  gid_n: the
     // rows the ids cover (a query needs gid_n == n).  Owned by the store (workers alias it), changed only under `rw` exclusive; a
     // reallocation copies the ids (group_grow).  d_gtable: THIS context's table of best keys, [queries per pass][n_groups] x 8 B,
-    // left zeroed by every query's select / compact kernel (gtable_clean); d_gctl: the compact kernel's cursor
+    // left zeroed by every query's select / compact kernel (gtable_clean); d_gctl: the compact kernel's cursor.  ott_group_top.hip keeps
+    // [queries][group_size][n_groups] slots in the same buffer under the same protocol (its deeper planes are cleared by a memset)
     uint32_t* d_gid = nullptr;
     uint64_t gid_n = 0;
     uint32_t n_groups = 0;
@@ -699,6 +700,7 @@ struct GroupTopK {
     bool take_max = false;
     bool index_is_group = false;    // the keys' low words are ~group, not ~row: a hit's index is the group, the count is cut at k
     bool* also_clean = nullptr;
+    uint64_t q_stride = 0;          // slots between the tables of two queries of a pass; 0 = n_groups (ott_group_top.hip: group_size x n_groups)
     bool lists_path = false;        // from here on: prepare's
     int E = 1;
     uint32_t KS = 0, n_lists = 0;
@@ -707,6 +709,8 @@ struct GroupTopK {
     int pass(ott_store* s, unsigned long long* table, uint32_t q0, uint32_t nq_here);
     int finish(ott_store* s, bool timing, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query);
 };
+// ott_group.hip: the grouped query on a context whose `mu` the caller holds; k_eff = min(k, n_groups) >= 1
+int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats_out);
 // ott_multi.hip: grouped search on a multi-GPU store
 int multi_set_groups(ott_store* ms, const uint32_t* gid_host, uint64_t n, uint32_t n_groups);
 int multi_clear_groups(ott_store* ms);

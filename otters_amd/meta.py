@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import Cmp, Metric, Mode, Path, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type
+from .vec import GROUP_SIZE_MAX, Cmp, Metric, Mode, Path, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -736,6 +736,7 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         self._path = Path.Auto
         self._row_ids = None
         self._distinct: Optional[str] = None
+        self._keep = 1  # distinct_by(name, keep=m): rows per distinct value
 
     def meta_filter(self, expr: Expr) -> "MetaQueryPlan":  # src/meta.rs:605-616 (error deferred to collect)
         try:
@@ -764,12 +765,15 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         self._row_ids = ids
         return self
 
-    def distinct_by(self, name: str) -> "MetaQueryPlan":
-        """One best row per distinct value of column `name`, top-k over the values (VecQueryPlan.one_per_group): Int32, Int64
-        and DateTime columns by value, String columns by string; every NULL row is a group of its own.  meta_filter, vec_filter
-        and deleted rows apply before grouping; the default take becomes the number of groups.  Float columns, unknown
-        columns, a batch of queries and with_row_ids raise OttersError at collect()."""
+    def distinct_by(self, name: str, keep: int = 1) -> "MetaQueryPlan":
+        """The best `keep` rows (default: one) per distinct value of column `name`, top-k over the values
+        (VecQueryPlan.one_per_group / per_group): Int32, Int64 and DateTime columns by value, String columns by string; every
+        NULL row is a group of its own.  meta_filter, vec_filter and deleted rows apply before grouping; the default take becomes
+        the number of groups.  With keep > 1 a value's rows come out together, best first, the values in the order of their best
+        row.  Float columns, unknown columns, a batch of queries, with_row_ids and a keep outside 1 .. 16 raise OttersError at
+        collect()."""
         self._distinct = str(name)
+        self._keep = keep
         return self
 
     def resolve(self):
@@ -784,6 +788,8 @@ class MetaQueryPlan:  # src/meta.rs:579-830
                 raise OttersError("distinct_by takes one query, not a batch (a merged list over several queries would need one winner per group across queries)")
             if self._row_ids is not None:
                 raise OttersError("distinct_by cannot be combined with with_row_ids in this version")
+            if isinstance(self._keep, bool) or not isinstance(self._keep, (int, np.integer)) or not 1 <= int(self._keep) <= GROUP_SIZE_MAX:
+                raise OttersError(f"distinct_by: keep must be an integer 1 .. {GROUP_SIZE_MAX}, not {self._keep!r}")
             n_groups = st._distinct_ids(self._distinct)[1]
         k = self.take_count if self.take_count is not None else (n_groups if self._distinct is not None else st._n_rows)  # src/meta.rs:638-640
         take = self.take_type if self.take_type is not None else (infer_default_take_type(self.metric))
@@ -794,7 +800,8 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         fc, ft = (0, 0.0) if self._vec_filter is None else (int(self._vec_filter[1]), self._vec_filter[0])
         q = np.ascontiguousarray(np.stack(self.queries)) if self.queries else np.zeros((0, st._dim), np.float32)
         rq = ResolvedQuery(queries=q, metric=int(self.metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft,
-                           row_mask=None, mode=int(Mode.Merged), path=int(self._path), grouped=self._distinct is not None)
+                           row_mask=None, mode=int(Mode.Merged), path=int(self._path), grouped=self._distinct is not None,
+                           group_size=int(self._keep) if self._distinct is not None and int(self._keep) > 1 else 0)  # (keep = 1: ott_query_groups, as before)
         if self._row_ids is not None:
             ids = as_row_ids(self._row_ids)
             if chunk_mask is not None and ids.size:  # (an id past the store's end stays: the library names it)

@@ -102,6 +102,8 @@ class ResolvedQuery:
     row_ids: Optional[np.ndarray] = None  # uint64[n_ids] (with_row_ids): only these rows are ranked, or None
     grouped: bool = False                 # one_per_group: one best hit per group, top-k over the groups (ott_query_groups)
     max_sim: bool = False                 # max_sim: the query vectors are one query's tokens, top-k groups by the sum of their best scores (ott_query_maxsim)
+    group_size: int = 0                   # per_group(m): up to m hits per group (ott_query_groups_top); 0 = not a per_group plan
+    group_of_hit: Optional[np.ndarray] = None  # OUTPUT of VecStore._run for a per_group plan: uint32[n hits], the dense group id of every hit
 
 
 def as_row_ids(ids) -> np.ndarray:
@@ -141,6 +143,9 @@ def dense_group_ids(ids):
     return np.ascontiguousarray(inv.reshape(-1).astype(np.uint32)), int(uniq.size)
 
 
+GROUP_SIZE_MAX = 16  # include/otters_hip.h: OTT_GROUP_SIZE_MAX
+
+
 def infer_default_take_type(metric: Metric) -> TakeType:  # src/vec.rs:92-98
     return TakeType.Min if metric in (Metric.Euclidean, Metric.Manhattan) else TakeType.Max
 
@@ -162,6 +167,7 @@ class VecQueryPlan:
         self._path = Path.Auto
         self._grouped = False
         self._max_sim = False
+        self._per_group = None  # per_group(m): m as the caller gave it (checked at validate())
 
     @staticmethod
     def new() -> "VecQueryPlan":
@@ -240,6 +246,19 @@ class VecQueryPlan:
             self._grouped = True
         return self
 
+    def per_group(self, m: int) -> "VecQueryPlan":
+        """Up to `m` best hits per group, top-k over the groups (VecStore.set_groups; ott_query_groups_top): of the hits of the same
+        plan with the default take, a hit is kept iff fewer than m earlier hits have its group; the groups rank by their first hit
+        (one_per_group's ranking), take(k) keeps the first k groups, and each group's hits come out contiguous, best first.  It
+        implies grouping — per_group(1) returns one_per_group's hits — and the default take is group_count().  collect_arrays()
+        returns (hits, counts, groups) with the dense group id of every hit; collect() the SearchResults in output order (one
+        list per query with per_query()); collect_groups() [(label, [SearchResult, ...]), ...].  m is 1 .. 16; not together with
+        with_row_ids or max_sim; a batch needs per_query(); not on a multi-GPU store."""
+        if self.error is None:
+            self._grouped = True
+            self._per_group = m
+        return self
+
     def max_sim(self) -> "VecQueryPlan":
         """Late-interaction (MaxSim) search (VecStore.set_groups; ott_query_maxsim): the plan's query vectors are the TOKENS of one
         query; a group's score is the sum over the tokens, in token order, of the token's best score among the group's surviving
@@ -266,6 +285,14 @@ class VecQueryPlan:
             raise OttersError("No queries provided")
         if self.row_ids is not None:
             as_row_ids(self.row_ids)
+        if self._per_group is not None:
+            m = self._per_group
+            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= int(m) <= GROUP_SIZE_MAX:
+                raise OttersError(f"per_group: the group size must be an integer 1 .. {GROUP_SIZE_MAX}, not {m!r}")
+            if self.row_ids is not None:
+                raise OttersError("per_group cannot be combined with with_row_ids in this version; use with_row_mask")
+            if self._max_sim:
+                raise OttersError("max_sim cannot be combined with per_group: a hit of max_sim is a group already")
         if self._grouped and self.row_ids is not None:
             raise OttersError("one_per_group cannot be combined with with_row_ids in this version; use with_row_mask")
         if self._max_sim and self.row_ids is not None:
@@ -297,10 +324,10 @@ class VecQueryPlan:
         return ResolvedQuery(queries=queries, metric=int(self.search_metric), take=int(take), k=max(int(k), 0),
                              filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, mode=int(self._mode), path=int(self._path),
                              row_ids=None if self.row_ids is None else as_row_ids(self.row_ids), grouped=self._grouped,
-                             max_sim=self._max_sim)
+                             max_sim=self._max_sim, group_size=0 if self._per_group is None else int(self._per_group))
 
     def collect(self):  # src/vec.rs:205-311
-        hits, counts = self.collect_arrays()
+        hits, counts = self.collect_arrays()[:2]  # (a per_group plan returns the hits' groups too)
         if self._max_sim:  # a hit is a group: the caller's own label where set_groups made the ids dense
             labels = self.vector_store.group_labels()
             idx = hits["index"].astype(np.int64)
@@ -315,10 +342,38 @@ class VecQueryPlan:
             return out
         return [SearchResult(i, x) for i, x in zip(idx, sc)]
 
+    def collect_groups(self):
+        """A per_group plan's hits by group: [(label, [SearchResult, ...]), ...] in the groups' rank order, each group's hits best
+        first; `label` is the caller's own group label (VecStore.group_labels()) or the dense id where there are none.  One such
+        list per query with per_query()."""
+        if self._per_group is None:
+            raise OttersError("collect_groups needs a per_group(m) plan")
+        hits, counts, groups = self.collect_arrays()
+        labels = self.vector_store.group_labels()
+        lab = (groups.astype(np.int64) if labels is None else labels[groups.astype(np.int64)]).tolist()
+        idx, sc = hits["index"].tolist(), hits["score"].tolist()
+
+        def by_group(lo, hi):  # a group's hits are contiguous: a new group starts where the id changes
+            out = []
+            for i in range(lo, hi):
+                if i == lo or groups[i] != groups[i - 1]:
+                    out.append((lab[i], []))
+                out[-1][1].append(SearchResult(idx[i], sc[i]))
+            return out
+
+        if self._mode == Mode.PerQuery:
+            out, o = [], 0
+            for c in counts:
+                out.append(by_group(o, o + c))
+                o += c
+            return out
+        return by_group(0, len(idx))
+
     def collect_arrays(self):
         """collect() without the per-hit Python objects: (hits, counts) where `hits` is a NumPy record array
         (`index` u64, `score` f32, `query` u32 = which query of the batch scored it) sorted best-first -- per query,
-        concatenated in query order, in per_query() mode -- and `counts[q]` is the number of hits of query q."""
+        concatenated in query order, in per_query() mode -- and `counts[q]` is the number of hits of query q.  A per_group(m) plan
+        returns (hits, counts, groups): `groups[i]` (u32) is the dense group id of hits[i]."""
         rq = self.resolve()
         store = self.vector_store
         hits, counts, stats = store._run(rq)
@@ -327,6 +382,8 @@ class VecQueryPlan:
             return hits, [int(hits.size)]
         if rq.mode != Mode.PerQuery:  # merged: how many of the k hits each query of the batch contributed
             counts = np.bincount(hits["query"], minlength=rq.queries.shape[0]).tolist()
+        if rq.group_size:
+            return hits, counts, rq.group_of_hit if rq.group_of_hit is not None else np.zeros(0, dtype=np.uint32)
         return hits, counts
 
 
@@ -635,6 +692,8 @@ class VecStore:
         cap = max(k_eff * (nq if perq else 1), 1)
         if rq.grouped:  # at most one hit per group and query
             cap = max(min(rq.k, self._n_groups) * nq, 1)
+        if rq.group_size:  # at most group_size hits per group and query
+            cap = max(min(rq.k, self._n_groups) * nq * rq.group_size, 1)
         if rq.max_sim:  # at most one hit per group
             cap = max(min(rq.k, self._n_groups), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)  # ott_query writes n_out entries; only those are returned
@@ -661,6 +720,10 @@ class VecStore:
         if rq.max_sim:
             N.check(N.lib().ott_query_maxsim(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), C.byref(st)))
             per[0] = n_out.value
+        elif rq.group_size:
+            gids = np.empty(cap, dtype=np.uint32)
+            N.check(N.lib().ott_query_groups_top(self._handle(), C.byref(d), rq.group_size, N.ptr(out), cap, C.byref(n_out), per, N.ptr(gids), C.byref(st)))
+            rq.group_of_hit = gids[: n_out.value].copy()
         elif rq.grouped:
             N.check(N.lib().ott_query_groups(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         elif ids is None:
