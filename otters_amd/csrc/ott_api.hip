@@ -456,6 +456,349 @@ int ott::query_on(ott_store* s, const ott_query_desc* d, ott_hit* out_host, void
     return query_core(s, d, out_host, out_dev, cap, n_out, n_per_query, n_out_dev, stats_out, nosync, events_pending, co);
 }
 
+namespace {
+
+// where one query's result goes: the caller's host buffer or device block and the counts beside it
+struct QueryOut {
+    ott_hit* host;
+    void* dev;
+    uint64_t cap;
+    uint64_t* n_out;
+    uint64_t* n_per_query;
+    void* n_dev;
+    bool nosync;
+    bool* events_pending;
+};
+
+// the one way out of a query that went well
+int finish(ott_stats& st, uint64_t t0, ott_stats* stats_out) {
+    st.total_ns = now_ns() - t0;
+    if (stats_out) *stats_out = st;
+    return OTT_OK;
+}
+
+// device output: every slot the scoring path does not write must hold a sentinel.  The fill is queued lazily: the exact path
+// writing a block of exactly its own geometry, and the staged host lists, cover every slot themselves
+int fill_sentinels(ott_store* s, const QueryOut& o) {
+    OTT_HIP(hipMemsetAsync(o.dev, 0xFF, o.cap * sizeof(ott_hit), s->stream));
+    return OTT_OK;
+}
+
+// the rows `which` of a batch's queries, packed (a cascade level or the exact redo over the queries still open)
+std::vector<float> gather_queries(const float* queries, uint32_t dim, const std::vector<uint32_t>& which) {
+    std::vector<float> sub((size_t)which.size() * dim);
+    for (size_t i = 0; i < which.size(); i++) memcpy(&sub[i * dim], queries + (size_t)which[i] * dim, (size_t)dim * 4);
+    return sub;
+}
+
+// The exact route.  *emitted: the result is with the caller already (the host "direct" sorted result, device output of
+// k <= 512); else it is in `lists` (groups: 1 merged, nq per query)
+int exact_route(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t k_eff, const uint64_t* d_mask, uint64_t mask_bits,
+                const QueryOut& o, bool timing, std::vector<std::vector<ott_hit>>& lists, ott_stats& st, bool* emitted) {
+    int rc;
+    const bool perq = d->mode == OTT_MODE_PER_QUERY;
+    st.path_used = OTT_PATH_EXACT;
+    // device output of k <= 512: the merge kernel leaves [groups][KS] sentinel-padded hits in d_hits, copied to the caller's
+    // block on the stream — nothing comes back to the host
+    const bool dev_direct = o.dev != nullptr && k_eff <= 512;
+    const uint32_t groups = perq ? d->nq : 1u;
+    const uint64_t KS = 64ull * (uint64_t)list_E(k_eff), gstride = o.dev ? o.cap / groups : 0;
+    // when the caller's block has exactly the merge kernel's geometry ([groups][KS]: what ott_query_sharded asks for), the
+    // merge writes into it directly: no sentinel fill in front, no copy behind
+    const bool in_place = dev_direct && gstride == KS;
+    // host output in the canonical order: the sort path may write a large result straight into the caller's buffer
+    struct DirectGuard {
+        ott_store* c;
+        ~DirectGuard() {
+            c->direct_out = nullptr;
+            c->direct_cap = 0;
+            c->direct_done = false;
+        }
+    } direct_guard{s};
+    if (o.host && !o.dev && s->cur_tie_sh == 0 && !s->cur_flat) {
+        s->direct_out = o.host;
+        s->direct_cap = o.cap;
+    }
+    s->direct_done = false;
+    rc = run_exact(s, d->queries, d->nq, d, perq, pl, k_eff, d_mask, mask_bits, !dev_direct, lists, st, timing, in_place ? (ott_hit*)o.dev : nullptr,
+                   (uint32_t)KS);
+    if (rc) return rc;
+    *emitted = s->direct_done || dev_direct;
+    if (s->direct_done) {
+        uint64_t total = 0;
+        for (size_t gq = 0; gq < s->direct_counts.size(); gq++) {
+            if (o.n_per_query && perq) o.n_per_query[gq] = s->direct_counts[gq];
+            total += s->direct_counts[gq];
+        }
+        if (o.n_out) *o.n_out = total;
+    } else if (dev_direct) {
+        if (!in_place) {
+            if ((rc = fill_sentinels(s, o))) return rc;
+            const uint64_t width = (KS < gstride ? KS : gstride) * sizeof(ott_hit);  // k_eff <= gstride: no hit is cut
+            const char* src = (const char*)s->d_hits.p + s->res_hits_off;
+            if (groups == 1) OTT_HIP(hipMemcpyAsync(o.dev, src, width, hipMemcpyDeviceToDevice, s->stream));
+            else OTT_HIP(hipMemcpy2DAsync(o.dev, gstride * sizeof(ott_hit), src, KS * sizeof(ott_hit), width, groups, hipMemcpyDeviceToDevice, s->stream));
+        }
+        if (o.n_dev) {
+            hipLaunchKernelGGL(sum_counts_kernel, dim3(1), dim3(64), 0, s->stream, (const uint64_t*)s->d_hits.p, groups, (uint64_t*)o.n_dev);
+            OTT_HIP(hipGetLastError());
+        }
+        if (o.nosync) {
+            if (o.events_pending) *o.events_pending = timing;
+        } else {
+            OTT_HIP(hipStreamSynchronize(s->stream));  // the caller's collective runs on another stream
+            if (timing) read_exact_events(s, &st);
+        }
+    }
+    return OTT_OK;
+}
+
+// what one cascade level adds to the call's stats.  A level starts from a copy of them, so the counters it only ever raises
+// come back accumulated; the level a query meets FIRST sets the rest (and the path), a later one adds to them
+void add_level_stats(ott_stats& st, const ott_stats& lv, bool first) {
+    st.gate_failed = lv.gate_failed;
+    st.bound_violations = lv.bound_violations;
+    if (first) {
+        st.score_ns = lv.score_ns; st.merge_ns = lv.merge_ns; st.rescored = lv.rescored; st.passes = lv.passes;
+        st.bytes_scanned = lv.bytes_scanned; st.path_used = lv.path_used;
+    } else {
+        st.score_ns += lv.score_ns; st.merge_ns += lv.merge_ns; st.rescored += lv.rescored; st.passes += lv.passes;
+        st.bytes_scanned += lv.bytes_scanned;
+    }
+    if (lv.err_ratio_max > st.err_ratio_max) st.err_ratio_max = lv.err_ratio_max;
+}
+
+// The batch route.  Cascade of candidate passes, each certified against the exact re-score: int8 level (a quarter of the f32
+// bytes) -> hi pass (bf16 hi plane: half the bytes, a third of the MFMAs, bound ~2^-8) -> split pass (bound ~2^-16) for the
+// queries it could not certify -> the same re-scoring 4096 per query -> exact path.  Which levels a batch meets is the store's
+// back-off state (ott_policy.h: CascadeState, read through the owner).
+struct Cascade {
+    ott_store* s;
+    const ott_query_desc* d;
+    const RunPlan& pl;
+    uint64_t k_q;
+    const uint64_t* d_mask;
+    uint64_t mask_bits;
+    ott_stats& st;     // the call's stats: every level adds to them (add_level_stats)
+    CascadeState& cs;  // the store's
+    std::vector<std::vector<ott_hit>> pq;  // per query: its list, best first
+    std::vector<uint32_t> unc;             // per query: != 0 while no level has certified it
+    bool hi_pass = false;
+    // the hi plane is looked at (built, extended) only when a level is about to stream it: with the int8 level in front most
+    // stores never need it
+    bool hi_checked = false;
+    bool hi_backing_off = false;  // the hi pass would run but is sitting out: the corpus is dense, the split pass keeps its 512 candidates
+    bool spec_now = false;        // speculative gates for the level a query meets first
+
+    int check_hi() {
+        if (hi_checked || !hi_pass) return OTT_OK;
+        hi_checked = true;
+        const uint16_t* himg = nullptr;
+        float hrel = 0.f;
+        bool is_half = false;
+        const int rc = ensure_hi_plane(s, &himg, &hrel, &is_half);
+        if (rc) return rc;
+        // the format the plane ACTUALLY has decides (a store whose norms spread over many binades falls back to bf16 by itself:
+        // k in 229..363 would then re-score fewer candidates than the bf16 bound needs and every batch would pay a hi pass
+        // that certifies nothing)
+        hi_pass = himg != nullptr && mfma_hi_k_ok(k_q, is_half);
+        if (hi_pass && CascadeState::consume(cs.hi_skip)) {  // backing off: recent batches mostly needed the split pass anyway
+            hi_pass = false;
+            hi_backing_off = true;
+        }
+        return OTT_OK;
+    }
+
+    // one level over the queries `which` (indices into the batch; empty = all of it)
+    int run_level(const std::vector<uint32_t>& which, int level, uint32_t t_min, bool first) {
+        std::vector<float> sub;
+        ott_query_desc d2 = *d;
+        if (!which.empty()) {
+            sub = gather_queries(d->queries, s->dim, which);
+            d2.queries = sub.data();
+            d2.nq = (uint32_t)which.size();
+        }
+        std::vector<std::vector<ott_hit>> pq2;
+        std::vector<uint32_t> unc2;
+        ott_stats st2 = st;
+        // speculative emission thresholds: only where a query meets the cascade FIRST (a level that re-runs the queries
+        // another level could not certify uses conservative gates, whatever the reason they failed), and not while
+        // backing off after a gate failed on this store
+        const bool spec = first && spec_now;
+        // (round 5: ONE query at the int8 level is a streaming sweep with the top-T in its epilogue — three launches instead of
+        //  the cascade's five rounds)
+        const bool single_sweep = level == 2 && i8_single_sweep(d2.nq, k_q, d2.filter_cmp, d2.metric, s->dim, t_min <= 128);
+        const int rc = single_sweep ? run_i8_single(s, &d2, pl, k_q, d_mask, mask_bits, pq2, unc2, st2, t_min)
+                                    : run_mfma(s, &d2, pl, k_q, d_mask, mask_bits, pq2, unc2, st2, level, t_min, spec);
+        if (rc) return rc;
+        add_level_stats(st, st2, first);
+        if (which.empty()) {
+            pq = std::move(pq2);
+            unc = std::move(unc2);
+        } else {
+            for (size_t i = 0; i < which.size(); i++) {
+                for (auto& h : pq2[i]) h.query = which[i];
+                pq[which[i]] = std::move(pq2[i]);
+                unc[which[i]] = unc2[i];
+            }
+        }
+        return OTT_OK;
+    }
+
+    std::vector<uint32_t> open_queries() const {
+        std::vector<uint32_t> v;
+        for (uint32_t q = 0; q < d->nq; q++)
+            if (unc[q]) v.push_back(q);
+        return v;
+    }
+
+    // uncertified queries: recompute on the exact path (per-query lists)
+    int redo_exact() {
+        const std::vector<uint32_t> redo = open_queries();
+        st.retries = (uint32_t)redo.size();
+        if (redo.empty()) return OTT_OK;
+        const std::vector<float> sub = gather_queries(d->queries, s->dim, redo);
+        std::vector<std::vector<ott_hit>> fix;
+        const int rc = run_exact(s, sub.data(), (uint32_t)redo.size(), d, true, pl, k_q, d_mask, mask_bits, true, fix, st);
+        if (rc) return rc;
+        for (size_t i = 0; i < redo.size(); i++) {
+            for (auto& h : fix[i]) h.query = redo[i];
+            pq[redo[i]] = std::move(fix[i]);
+        }
+        return OTT_OK;
+    }
+
+    int run() {
+        int rc;
+        const uint32_t nq = d->nq;
+        hi_pass = mfma_hi_k_ok(k_q, s->opt.hi_fmt != 0) && !s->opt.mfma_f32 && !s->opt.no_hi_pass;
+        // Round 5 (default; option hi_fmt = -1 / 2): an INT8 level in front of the hi pass (cosine / dot, k <= 128): a quarter of the
+        // f32 bytes, one v_mfma_i32_32x32x32_i8 per 32 k, exact integer accumulation — its bound is the measured quantisation loss
+        // alone (~8e-3 relative on uniform 768-d rows), so it re-scores 512 candidates per query and certifies where fewer than
+        // 512 - k rows lie that close to the k-th score; what it leaves open goes to the hi pass.  Same back-off as the hi pass.
+        bool i8_pass = hi_pass && i8_wanted(s->opt) && k_q <= 128;
+        if (i8_pass) {
+            const int8_t* i8 = nullptr;
+            const float* i8s = nullptr;
+            float i8rel = 0.f;
+            if ((rc = ensure_i8_plane(s, &i8, &i8s, &i8rel))) return rc;
+            i8_pass = i8 != nullptr;
+        }
+        if (i8_pass && CascadeState::consume(cs.i8_skip)) i8_pass = false;
+        if (!i8_pass && (rc = check_hi())) return rc;
+        // the split pass is then a later level: it re-scores 512 candidates per query — also while the hi pass backs off (it backs off
+        // on dense or clustered corpora, exactly where k + 28 candidates certify nothing)
+        const bool cascade = hi_pass || i8_pass || hi_backing_off;
+        // the 4096-candidate level is there for every bf16 batch (also k > 228 or no hi plane: split pass, wide split pass, exact)
+        const bool escalate = !s->opt.mfma_f32;
+        // (not while backing off: a speculative gate failed a query on this store recently)
+        spec_now = s->opt.mfma_spec != 0 && !CascadeState::consume(cs.spec_skip);
+        const std::vector<uint32_t> all;
+        std::vector<uint32_t> after_i8;  // the queries the int8 level left open (it ran and certified the rest)
+        if (i8_pass) {
+            const bool i8_wide_now = CascadeState::consume(cs.i8_t512);
+            if ((rc = run_level(all, 2, i8_wide_now ? 512u : 0u, true))) return rc;
+            after_i8 = open_queries();
+            st.i8_refined = (uint32_t)after_i8.size();
+            cs.after_i8(nq, after_i8.size(), st.gate_failed, i8_wide_now, k_q);
+            if (!after_i8.empty() && (rc = check_hi())) return rc;  // what the int8 level left open needs the hi plane now
+        }
+        const std::vector<uint32_t>& rest = i8_pass ? after_i8 : all;  // what the next level runs on; it is a query's first unless the int8 level ran
+        if (i8_pass && after_i8.empty()) {
+            // every query certified by the int8 level: nothing left for the others
+        } else if (hi_pass) {
+            // candidates re-scored per query by the hi pass: 2k + 56, or 512 once this store's queries have failed at that
+            // (dense neighbourhoods: clustered corpora), or what the hi_tmin option says
+            const bool hi_wide_now = cs.hi_wide();
+            const uint32_t hi_t = s->opt.hi_tmin ? (uint32_t)s->opt.hi_tmin : (hi_wide_now ? 512u : 0u);
+            if ((rc = run_level(rest, 0, hi_t, !i8_pass))) return rc;
+            const std::vector<uint32_t> refine = open_queries();
+            st.refined = (uint32_t)refine.size();
+            cs.after_hi(nq, refine.size(), st.gate_failed, hi_wide_now, hi_t);
+            if (!refine.empty() && (rc = run_level(refine, 1, 512, false))) return rc;
+        } else if (escalate && cs.take_wide_first(nq)) {
+            // the 512-candidate level has been failing on this store: start at the 4096-candidate one for a while
+            if ((rc = run_level(rest, 1, 4096, !i8_pass))) return rc;
+        } else {
+            if ((rc = run_level(rest, 1, cascade ? 512u : 0u, !i8_pass))) return rc;
+        }
+        if (spec_now) cs.after_spec(st.gate_failed != 0);
+        if (escalate) {
+            // third level: still more than a couple of exact passes' worth of open queries (near-duplicate clusters: hundreds of
+            // rows within the split pass's bound of the k-th score) — the split pass once more, re-scoring 4096 per query
+            const std::vector<uint32_t> wide = open_queries();
+            if (wide.size() > 8 && st.rescored < (uint64_t)nq * 4096) {
+                cs.arm_wide_first(wide.size(), nq);
+                if ((rc = run_level(wide, 1, 4096, false))) return rc;
+            }
+        }
+        return redo_exact();
+    }
+};
+
+// reference semantics of a merged batch: one list over all (query, row) pairs (src/vec.rs:217-219).  The per-query lists are
+// sorted best first, so the merged top-k is a k-way merge over their heads: k pops of a heap of nq cursors (a partial_sort
+// over all nq x k hits was ~0.1 ms of a 256-query batch)
+std::vector<ott_hit> merge_lists(const std::vector<std::vector<ott_hit>>& pq, const CanonLess& less, size_t k) {
+    std::vector<std::pair<uint32_t, uint32_t>> heap;  // (list, position); the heap's top is the best head
+    auto worse = [&](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) {
+        return less(pq[b.first][b.second], pq[a.first][a.second]);
+    };
+    for (uint32_t q = 0; q < pq.size(); q++)
+        if (!pq[q].empty()) heap.emplace_back(q, 0u);
+    std::make_heap(heap.begin(), heap.end(), worse);
+    std::vector<ott_hit> all;
+    all.reserve(k);
+    while (!heap.empty() && all.size() < k) {
+        std::pop_heap(heap.begin(), heap.end(), worse);
+        const std::pair<uint32_t, uint32_t> cur = heap.back();
+        heap.pop_back();
+        all.push_back(pq[cur.first][cur.second]);
+        if (cur.second + 1 < pq[cur.first].size()) {
+            heap.emplace_back(cur.first, cur.second + 1);
+            std::push_heap(heap.begin(), heap.end(), worse);
+        }
+    }
+    return all;
+}
+
+// device output of host-side lists (batch path, k > 512): [groups][cap / groups] slots, each list best first, the rest
+// sentinels.  ONE copy of the whole block from pinned staging (a copy per query was ~5 us of enqueue each: 5 ms for the 1024
+// queries of a C4 shard)
+int emit_device_staged(ott_store* s, const std::vector<std::vector<ott_hit>>& lists, uint32_t groups, const QueryOut& o) {
+    int rc;
+    const uint64_t gstride = o.cap / groups;
+    const size_t blk = (size_t)groups * gstride * sizeof(ott_hit);
+    if ((rc = s->h_stage.ensure(blk + sizeof(uint64_t)))) return rc;
+    char* hs = (char*)s->h_stage.p;
+    memset(hs, 0xFF, blk);  // sentinels: this block covers every slot of out_dev
+    uint64_t tot = 0;
+    for (uint32_t q = 0; q < groups; q++) {
+        const size_t c = lists[q].size() < gstride ? lists[q].size() : (size_t)gstride;
+        if (c) memcpy(hs + (size_t)q * gstride * sizeof(ott_hit), lists[q].data(), c * sizeof(ott_hit));
+        tot += c;
+    }
+    memcpy(hs + blk, &tot, sizeof(uint64_t));
+    OTT_HIP(hipMemcpyAsync(o.dev, hs, blk, hipMemcpyHostToDevice, s->stream));
+    if (o.n_dev) OTT_HIP(hipMemcpyAsync(o.n_dev, hs + blk, sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
+    if (!o.nosync) OTT_HIP(hipStreamSynchronize(s->stream));  // (nosync: h_stage stays untouched until the caller's own wait)
+    return OTT_OK;
+}
+
+void emit_host(const std::vector<std::vector<ott_hit>>& lists, bool perq, const QueryOut& o) {
+    uint64_t total = 0;
+    for (size_t gq = 0; gq < lists.size(); gq++) {
+        const size_t c = lists[gq].size();
+        if (c) memcpy(o.host + total, lists[gq].data(), c * sizeof(ott_hit));
+        if (o.n_per_query && perq) o.n_per_query[gq] = c;
+        total += c;
+    }
+    if (o.n_out) *o.n_out = total;
+}
+
+}  // namespace
+
+// One plain query on a context: plan, checks, path choice (ott_policy.h: choose_path), one of the two routes above, emit.
 int ott::query_core(ott_store* s, const ott_query_desc* d, ott_hit* out_host, void* out_dev, uint64_t cap, uint64_t* n_out,
                     uint64_t* n_per_query, void* n_out_dev, ott_stats* stats_out, bool nosync, bool* events_pending, const CoreOpts& co) {
     int rc;
@@ -486,23 +829,15 @@ int ott::query_core(ott_store* s, const ott_query_desc* d, ott_hit* out_host, vo
     if (cap < need) return fail(OTT_ERR_INVALID, "ott_query: output capacity is smaller than min(k, rows*nq)");
     if (out_dev && perq && cap % nq != 0) return fail(OTT_ERR_INVALID, "ott_query_device: PER_QUERY capacity must be a multiple of nq");
 
-    // device output: every slot the scoring path does not write must hold a sentinel.  The sentinel fill is queued lazily
-    // (`fill_sentinels`): the exact path writing a block of exactly its own geometry, and the staged host lists, cover every
-    // slot themselves
-    auto fill_sentinels = [&]() -> int {
-        OTT_HIP(hipMemsetAsync(out_dev, 0xFF, cap * sizeof(ott_hit), s->stream));
-        return OTT_OK;
-    };
+    const QueryOut o{out_host, out_dev, cap, n_out, n_per_query, n_out_dev, nosync, events_pending};
     if (out_dev && n_out_dev) OTT_HIP(hipMemsetAsync(n_out_dev, 0, sizeof(uint64_t), s->stream));
     if (n_out) *n_out = 0;
     if (n_per_query)
         for (uint32_t i = 0; i < nq; i++) n_per_query[i] = 0;
     if (k_eff == 0 || pl.rows_scored == 0) {  // k == 0 (src/vec_compute.rs:174) or nothing to score
-        if (out_dev && (rc = fill_sentinels())) return rc;
+        if (out_dev && (rc = fill_sentinels(s, o))) return rc;
         if (out_dev && !nosync) OTT_HIP(hipStreamSynchronize(s->stream));
-        st.total_ns = now_ns() - t0;
-        if (stats_out) *stats_out = st;
-        return OTT_OK;
+        return finish(st, t0, stats_out);
     }
 
     // row mask -> device: the ONE place every mask joins (the caller's or the evaluated one, an id list's, the live mask)
@@ -510,410 +845,40 @@ int ott::query_core(ott_store* s, const ott_query_desc* d, ott_hit* out_host, vo
     uint64_t mask_bits = 0;
     if ((rc = compose_row_mask(s, d, &d_mask, &mask_bits))) return rc;
 
-    // ---- path choice --------------------------------------------------------------------------------
-    // per-query k for the batch path: the merged top-k is contained in the union of per-query top-k
-    const uint64_t k_q = d->k < pl.rows_scored ? d->k : pl.rows_scored;
-    const bool mfma_ok = k_q + 28 <= 512 && s->dim >= 8;
-    bool use_mfma;
-    if (co.flat) use_mfma = false;  // (the flat pass exists on the exact-order kernel only)
-    else if (d->metric == OTT_METRIC_MANHATTAN) use_mfma = false;  // EXACT only, decided before the cost model looks at the planes (img_mu)
-    else if (d->path == OTT_PATH_MFMA) {
-        if (!mfma_ok) return fail(OTT_ERR_UNSUPPORTED, "ott_query: the MFMA path needs dim >= 8 and k <= 484");
-        use_mfma = true;
-    } else if (d->path == OTT_PATH_EXACT) use_mfma = false;
-    else {
-        // AUTO: cost model fitted to MI355X measurements (benchmarks/small_corpus.py, nq_sweep.py), in milliseconds.
-        // exact: up to 4 queries share one pass; a pass of m queries costs 0.05 / 0.06 / 0.085 / 0.115 ms of launches + latency and
-        //        streams at ~6.5 TB/s, 2.7 % slower per extra query (round 4, benchmarks/auto_choice.py on 300k .. 10M x 768:
-        //        one query 0.187 / 0.517 / 1.40 / 4.54 ms, four 0.257 / 0.590 / 1.59 / 4.90; the 0.11 ms per pass this model
-        //        carried since round 1 sent single queries on 262k-480k-row stores through the cascade, 20 % slower).
-        // mfma:  ~0.16 ms of rounds / select / finalize / transfer, ~4.5 us per query of re-scoring and host merge, then the
-        //        slower of the corpus stream (~6 TB/s per 256-query block) and the matrix pipe.
-        const double bytes = (double)pl.rows_scored * (4.0 * s->dim + 4.0);
-        const uint32_t full_passes = nq / 4, last_m = nq % 4;
-        static const double pass_fixed[5] = {0.0, 0.05, 0.06, 0.085, 0.115};
-        auto t_pass = [&](uint32_t m) { return pass_fixed[m] + bytes / 6.5e9 * (1.0 + 0.027 * (m - 1)); };
-        const double t_exact = full_passes * t_pass(4) + (last_m ? t_pass(last_m) : 0.0);
-        const uint32_t bn = nq <= 16 ? 16u : nq <= 32 ? 32u : nq <= 64 ? 64u : nq <= 128 ? 128u : 256u;
-        const double nq_pad = (double)((nq + bn - 1) / bn * bn);
-        const bool f32pipe = s->opt.mfma_f32;
-        // (the plane's actual format once it exists — it may have fallen back to bf16 — else what the option asks for)
-        const ott_store* own_c = s->owner ? s->owner : s;
-        const PlaneSnapshot ps = plane_snapshot(s);  // (under img_mu: another context may be building or dropping a plane right now)
-        const bool plane_half = ps.have_hi ? ps.hi_f16 : s->opt.hi_fmt != 0;
-        const bool hi_ok = !f32pipe && mfma_hi_k_ok(d->k < pl.rows_scored ? d->k : pl.rows_scored, plane_half) && !s->opt.no_hi_pass;
-        // round 5: the int8 plane in front (cosine / dot, k <= 128): a quarter of the bytes, twice the matrix rate, 512 candidates
-        const bool i8_ok = hi_ok && i8_wanted(s->opt) && !ps.i8_off && k_q <= 128;
-        // the hi pass streams the 16-bit hi plane: half the bytes
-        const double t_stream = (i8_ok ? 0.25 : hi_ok ? 0.5 : 1.0) * bytes * (double)((nq + 255) / 256) / (i8_ok ? 6.0e9 : hi_ok ? (nq <= 32 ? 6.5e9 : 6.2e9) : 5.9e9);  // (non-temporal row pieces, round 2: 6.6-6.8 TB/s up to 32 queries, ~6 at 64-128)
-        // matrix pipe: ~125 TFLOP/s on the f32 pipe, ~330 TFLOP/s (f32-equivalent) with the split-bf16 operands, ~800 for the hi pass, ~1500 int8
-        const double t_pipe = 2.0 * s->dim * (double)pl.rows_scored * nq_pad / (i8_ok ? 1500e9 : hi_ok ? 800e9 : (bn >= 32 && !f32pipe) ? 330e9 : 125e9);
-        // (the candidates re-scored per query grow with k — 2k + 56 on the hi pass, in steps of 64; 512 on the int8 pass — and finalize /
-        //  select with them: top-100 costs the cascade 0.03-0.05 ms more than top-10 at one query, benchmarks/auto_choice.py)
-        const double t_cand = i8_ok ? 0.0003 * 384.0 : hi_ok && k_q > 36 ? 0.0003 * (double)((2 * k_q + 56 + 63) / 64 * 64 - 128) : 0.0;
-        double t_mfma = 0.16 + 0.0045 * nq + t_cand + (t_stream > t_pipe ? t_stream : t_pipe);
-        // ONE query at the int8 level, k <= 24: a streaming sweep with the top-128 in its epilogue (run_i8_single): ~0.11 ms of
-        // launches, merge and re-score around a quarter of the bytes at 6.5 TB/s (profiles/round5/auto_choice.md: 150k x 768 rows
-        // 0.13 ms, 1M 0.24, 10M 1.29; the exact kernel 0.12 / 0.54 / 4.7)
-        if (i8_ok && nq == 1 && k_q <= 24 && d->filter_cmp != OTT_CMP_EQ && d->metric != OTT_METRIC_EUCLIDEAN && s->dim <= 3584 && own_c->i8_t512.load() <= 0)
-            t_mfma = 0.11 + 0.25 * bytes / 6.5e9;
-        // a SINGLE query takes the exact-order kernel (no second copy of the corpus is built for the most common call) — unless
-        // the bf16 hi plane is ALREADY resident (a batch query or ott_store_prepare_batch built it) and covers every row: then
-        // the cascade streams half the bytes (10M x 768: 2.5 ms against 4.5) and returns the same bits;
-        // 2-4 queries share one exact pass unless the hi pass (half the bytes) is cheaper; without it the batch path needs > 4
-        const bool batch_worthy = nq > (hi_ok ? 1u : 4u) || (nq == 1 && hi_ok && first_plane_ready(s));
-        use_mfma = mfma_ok && batch_worthy && pl.rows_scored >= 2048 && t_mfma < t_exact;
-        // small stores, small batches (round 3): rows8 scores up to 8 queries per pass in ~(40 us + 0.7 us per thousand rows) behind
-        // ~35 us of launches and merge, against the batch path's ~(120 us + 3.5 us per query) of rounds, select and finalize
-        // (benchmarks/small_corpus.py: 10k x 768, 8 queries: 84 us against 150)
-        const uint64_t k_e = d->k < pl.rows_scored * nq ? d->k : pl.rows_scored * nq;
-        if (use_mfma && nq <= 16 && k_e <= 128 && s->dimq <= 2048 && s->opt.exact_small != 0 && s->opt.exact_small != 1 &&
-            pl.rows_scored / 64 + pl.runs.size() <= 1024) {
-            const double t_rows8 = 0.035 + (double)((nq + 7) / 8) * (0.040 + 0.7e-6 * (double)pl.rows_scored);
-            if (t_rows8 < 0.9 * (0.12 + 0.0035 * nq)) use_mfma = false;
-        }
-    }
+    ott_store* own = s->owner ? s->owner : s;
+    const Options& op = s->opt;
+    const PathIn in{pl.rows_scored, pl.runs.size(), s->dim, s->dimq, nq, d->k, d->metric, d->filter_cmp, d->path, co.flat,
+                    op.mfma_f32, op.no_hi_pass, op.no_batch_image, op.hi_fmt, op.exact_small};
+    const PathChoice path = choose_path(
+        in,
+        [&] {
+            const PlaneSnapshot ps = plane_snapshot(s);
+            return PathPlanes{ps.have_hi, ps.hi_f16, ps.i8_off, own->cascade.i8_widened()};
+        },
+        [&] { return first_plane_ready(s); });
+    if (path == PATH_CHOICE_REFUSED) return fail(OTT_ERR_UNSUPPORTED, kMfmaRefusal);
 
     std::vector<std::vector<ott_hit>> lists;  // groups: 1 (merged) or nq
-    if (!use_mfma) {
-        st.path_used = OTT_PATH_EXACT;
+    if (path == PATH_CHOICE_EXACT) {
         // kernel timing (three event records, each a barrier packet between the launches) only when the caller asked for stats
-        const bool timing = stats_out != nullptr;
-        // device output of k <= 512: the merge kernel leaves [groups][KS] sentinel-padded hits in d_hits, copied to the caller's
-        // block on the stream — nothing comes back to the host
-        const bool dev_direct = out_dev != nullptr && k_eff <= 512;
-        const uint32_t groups_x = perq ? nq : 1u;
-        const uint64_t KSx = 64ull * (uint64_t)list_E(k_eff), gstride_x = out_dev ? cap / groups_x : 0;
-        // when the caller's block has exactly the merge kernel's geometry ([groups][KS]: what ott_query_sharded asks for), the
-        // merge writes into it directly: no sentinel fill in front, no copy behind
-        const bool in_place = dev_direct && gstride_x == KSx;
-        // host output in the canonical order: the sort path may write a large result straight into the caller's buffer
-        struct DirectGuard {
-            ott_store* c;
-            ~DirectGuard() {
-                c->direct_out = nullptr;
-                c->direct_cap = 0;
-                c->direct_done = false;
-            }
-        } direct_guard{s};
-        if (out_host && !out_dev && s->cur_tie_sh == 0 && !s->cur_flat) {
-            s->direct_out = out_host;
-            s->direct_cap = cap;
-        }
-        s->direct_done = false;
-        rc = run_exact(s, d->queries, nq, d, perq, pl, k_eff, d_mask, mask_bits, !dev_direct, lists, st, timing, in_place ? (ott_hit*)out_dev : nullptr,
-                       (uint32_t)KSx);
-        if (rc) return rc;
-        if (s->direct_done) {
-            uint64_t total = 0;
-            for (size_t gq = 0; gq < s->direct_counts.size(); gq++) {
-                if (n_per_query && perq) n_per_query[gq] = s->direct_counts[gq];
-                total += s->direct_counts[gq];
-            }
-            if (n_out) *n_out = total;
-            st.total_ns = now_ns() - t0;
-            if (stats_out) *stats_out = st;
-            return OTT_OK;
-        }
-        if (dev_direct) {
-            const uint32_t groups = groups_x;
-            const uint64_t KS = KSx, gstride = gstride_x;
-            if (!in_place) {
-                if ((rc = fill_sentinels())) return rc;
-                const uint64_t width = (KS < gstride ? KS : gstride) * sizeof(ott_hit);  // k_eff <= gstride: no hit is cut
-                const char* src = (const char*)s->d_hits.p + s->res_hits_off;
-                if (groups == 1) OTT_HIP(hipMemcpyAsync(out_dev, src, width, hipMemcpyDeviceToDevice, s->stream));
-                else OTT_HIP(hipMemcpy2DAsync(out_dev, gstride * sizeof(ott_hit), src, KS * sizeof(ott_hit), width, groups, hipMemcpyDeviceToDevice, s->stream));
-            }
-            if (n_out_dev) {
-                hipLaunchKernelGGL(sum_counts_kernel, dim3(1), dim3(64), 0, s->stream, (const uint64_t*)s->d_hits.p, groups, (uint64_t*)n_out_dev);
-                OTT_HIP(hipGetLastError());
-            }
-            if (nosync) {
-                if (events_pending) *events_pending = timing;
-            } else {
-                OTT_HIP(hipStreamSynchronize(s->stream));  // the caller's collective runs on another stream
-                if (timing) read_exact_events(s, &st);
-            }
-            st.total_ns = now_ns() - t0;
-            if (stats_out) *stats_out = st;
-            return OTT_OK;
-        }
+        bool emitted = false;
+        if ((rc = exact_route(s, d, pl, k_eff, d_mask, mask_bits, o, stats_out != nullptr, lists, st, &emitted))) return rc;
+        if (emitted) return finish(st, t0, stats_out);
     } else {
-        std::vector<std::vector<ott_hit>> pq;
-        std::vector<uint32_t> unc;
-        // Cascade of candidate passes, each certified against the exact re-score: hi pass (bf16 hi plane: half the bytes, a
-        // third of the MFMAs, bound ~2^-8) -> split pass (bound ~2^-16) for the queries it could not certify -> exact path.
-        ott_store* own = s->owner ? s->owner : s;
-        bool hi_pass = mfma_hi_k_ok(k_q, s->opt.hi_fmt != 0) && !s->opt.mfma_f32 && !s->opt.no_hi_pass;
-        // the hi plane is looked at (built, extended) only when a level is about to stream it: with the int8 level in front most
-        // stores never need it
-        bool hi_checked = false;
-        bool hi_backing_off = false;  // the hi pass would run but is sitting out: the corpus is dense, the split pass keeps its 512 candidates
-        auto check_hi = [&]() -> int {
-            if (hi_checked || !hi_pass) return OTT_OK;
-            hi_checked = true;
-            const uint16_t* himg = nullptr;
-            float hrel = 0.f;
-            bool is_half = false;
-            const int rc2 = ensure_hi_plane(s, &himg, &hrel, &is_half);
-            if (rc2) return rc2;
-            // the format the plane ACTUALLY has decides (a store whose norms spread over many binades falls back to bf16 by itself:
-            // k in 229..363 would then re-score fewer candidates than the bf16 bound needs and every batch would pay a hi pass
-            // that certifies nothing)
-            hi_pass = himg != nullptr && mfma_hi_k_ok(k_q, is_half);
-            if (hi_pass && own->hi_skip.load() > 0) {  // backing off: recent batches mostly needed the split pass anyway
-                own->hi_skip.fetch_sub(1);
-                hi_pass = false;
-                hi_backing_off = true;
-            }
-            return OTT_OK;
-        };
-        // Round 5 (default; option hi_fmt = -1 / 2): an INT8 level in front of the hi pass (cosine / dot, k <= 128): a quarter of the
-        // f32 bytes, one v_mfma_i32_32x32x32_i8 per 32 k, exact integer accumulation — its bound is the measured quantisation loss
-        // alone (~8e-3 relative on uniform 768-d rows), so it re-scores 512 candidates per query and certifies where fewer than
-        // 512 - k rows lie that close to the k-th score; what it leaves open goes to the hi pass.  Same back-off as the hi pass.
-        bool i8_pass = hi_pass && i8_wanted(s->opt) && k_q <= 128;
-        if (i8_pass) {
-            const int8_t* i8 = nullptr;
-            const float* i8s = nullptr;
-            float i8rel = 0.f;
-            if ((rc = ensure_i8_plane(s, &i8, &i8s, &i8rel))) return rc;
-            i8_pass = i8 != nullptr;
-        }
-        if (i8_pass && own->i8_skip.load() > 0) {
-            own->i8_skip.fetch_sub(1);
-            i8_pass = false;
-        }
-        if (!i8_pass && (rc = check_hi())) return rc;
-        // the split pass is then a later level: it re-scores 512 candidates per query — also while the hi pass backs off (it backs off
-        // on dense or clustered corpora, exactly where k + 28 candidates certify nothing)
-        const bool cascade = hi_pass || i8_pass || hi_backing_off;
-        // the 4096-candidate level is there for every bf16 batch (also k > 228 or no hi plane: split pass, wide split pass, exact)
-        const bool escalate = !s->opt.mfma_f32;
-        bool spec_now = s->opt.mfma_spec != 0;
-        if (spec_now && own->spec_skip.load() > 0) {  // backing off: a speculative gate failed a query on this store recently
-            own->spec_skip.fetch_sub(1);
-            spec_now = false;
-        }
-        // one level of the cascade over the queries `which` (indices into the batch; empty = all of it)
-        auto run_level = [&](const std::vector<uint32_t>& which, int level, uint32_t t_min, bool first) -> int {
-            std::vector<float> sub;
-            ott_query_desc d2 = *d;
-            if (!which.empty()) {
-                sub.resize((size_t)which.size() * s->dim);
-                for (size_t i = 0; i < which.size(); i++) memcpy(&sub[i * s->dim], d->queries + (size_t)which[i] * s->dim, (size_t)s->dim * 4);
-                d2.queries = sub.data();
-                d2.nq = (uint32_t)which.size();
-            }
-            std::vector<std::vector<ott_hit>> pq2;
-            std::vector<uint32_t> unc2;
-            ott_stats st2 = st;
-            // speculative emission thresholds: only where a query meets the cascade FIRST (a level that re-runs the queries
-            // another level could not certify uses conservative gates, whatever the reason they failed), and not while
-            // backing off after a gate failed on this store
-            const bool spec = first && spec_now;
-            // (round 5: ONE query at the int8 level is a streaming sweep with the top-T in its epilogue — three launches instead of
-            //  the cascade's five rounds)
-            //  — while the list it keeps is 128 entries (k <= 24: the wave lists of 256 / 512 entries cost the sweep more than the
-            //  rounds cost the cascade: top-100 at 10M x 768 1.97 ms against 1.46)
-            const bool single_sweep = level == 2 && d2.nq == 1 && d2.filter_cmp != OTT_CMP_EQ && d2.metric != OTT_METRIC_EUCLIDEAN && s->dim <= 3584 && k_q <= 24 && t_min <= 128;  // (the sweep kernel scores cosine / dot)
-            int rc2 = single_sweep ? run_i8_single(s, &d2, pl, k_q, d_mask, mask_bits, pq2, unc2, st2, t_min)
-                                   : run_mfma(s, &d2, pl, k_q, d_mask, mask_bits, pq2, unc2, st2, level, t_min, spec);
-            if (rc2) return rc2;
-            st.gate_failed = st2.gate_failed;  // (st2 started as a copy of st: accumulated)
-            st.bound_violations = st2.bound_violations;
-            if (first) {
-                st.score_ns = st2.score_ns; st.merge_ns = st2.merge_ns; st.rescored = st2.rescored; st.passes = st2.passes;
-                st.bytes_scanned = st2.bytes_scanned; st.path_used = st2.path_used;
-            } else {
-                st.score_ns += st2.score_ns; st.merge_ns += st2.merge_ns; st.rescored += st2.rescored; st.passes += st2.passes;
-                st.bytes_scanned += st2.bytes_scanned;
-            }
-            if (st2.err_ratio_max > st.err_ratio_max) st.err_ratio_max = st2.err_ratio_max;
-            if (which.empty()) {
-                pq = std::move(pq2);
-                unc = std::move(unc2);
-            } else {
-                for (size_t i = 0; i < which.size(); i++) {
-                    for (auto& h : pq2[i]) h.query = which[i];
-                    pq[which[i]] = std::move(pq2[i]);
-                    unc[which[i]] = unc2[i];
-                }
-            }
-            return OTT_OK;
-        };
-        auto open_queries = [&]() {
-            std::vector<uint32_t> v;
-            for (uint32_t q = 0; q < nq; q++)
-                if (unc[q]) v.push_back(q);
-            return v;
-        };
-        const std::vector<uint32_t> all;
-        std::vector<uint32_t> after_i8;  // the queries the int8 level left open (it ran and certified the rest)
-        bool i8_ran = false;
-        if (i8_pass) {
-            // (i8_t512 = calls left that re-score 512 candidates per query: 64 after a failure at less, counted down by the calls
-            //  that follow — one query in a dense neighbourhood does not widen the store's every later call for good)
-            const bool i8_wide_now = own->i8_t512.load() > 0;
-            if (i8_wide_now) own->i8_t512.fetch_sub(1);
-            if ((rc = run_level(all, 2, i8_wide_now ? 512u : 0u, true))) return rc;
-            i8_ran = true;
-            after_i8 = open_queries();
-            st.i8_refined = (uint32_t)after_i8.size();
-            const size_t genuine8 = after_i8.size() > st.gate_failed ? after_i8.size() - st.gate_failed : 0;
-            // A batch in which ANY query stays open pays a second pass — the hi pass over the half plane, ~2.4 ms at 10M x 768
-            // however few the queries — so the int8 level only pays while most batches certify whole: measured on near-duplicate
-            // clusters (7-17 of 256 queries open in EVERY batch) int8 first took 5.65 ms per batch where the hi pass alone takes
-            // 4.8.  Batches of more than 512 queries are the exception: their int8 pass saves more than the second pass costs
-            // (1024 queries: 9.4 + 2.4 ms against 15.4).  Back-off as for the hi pass: more than 1/8 of a batch open, or more than
-            // ~half (small batches: ~40 %) of the recent batches needing the second pass at all.
-            const int ema8 = (3 * own->i8_fail_ema.load() + (genuine8 == 0 ? 0 : 1024)) / 4;
-            own->i8_fail_ema.store(ema8);
-            if (genuine8 * 8 > nq && !i8_wide_now && 4 * k_q + 88 < 512) {
-                own->i8_t512.store(64);  // first answer to dense neighbourhoods: re-score 512 per query for the next 64 calls
-                own->i8_fail_ema.store(0);
-            } else if (genuine8 * 8 > nq || (nq <= 512 && ema8 > (nq <= 128 ? 400 : 512))) {
-                int b = own->i8_backoff.load() * 2;
-                b = b < 4 ? 4 : b > 64 ? 64 : b;
-                own->i8_backoff.store(b);
-                own->i8_skip.store(b);
-            } else if (genuine8 == 0) own->i8_backoff.store(0);
-        }
-        if (i8_ran && !after_i8.empty() && (rc = check_hi())) return rc;  // what the int8 level left open needs the hi plane now
-        if (i8_ran && after_i8.empty()) {
-            // every query certified by the int8 level: nothing left for the others
-        } else if (hi_pass) {
-            // candidates re-scored per query by the hi pass: 2k + 56, or 512 once this store's queries have failed at that
-            // (dense neighbourhoods: clustered corpora), or what the hi_tmin option says
-            const bool hi_wide_now = own->hi_t512.load() != 0;
-            const uint32_t hi_t = s->opt.hi_tmin ? (uint32_t)s->opt.hi_tmin : (hi_wide_now ? 512u : 0u);
-            if ((rc = run_level(i8_ran ? after_i8 : all, 0, hi_t, !i8_ran))) return rc;
-            std::vector<uint32_t> refine = open_queries();
-            st.refined = (uint32_t)refine.size();
-            // queries that failed only through their speculative gate say nothing about the hi pass's error bound
-            const size_t genuine = refine.size() > st.gate_failed ? refine.size() - st.gate_failed : 0;
-            if (genuine * 8 > nq && !hi_wide_now && hi_t < 512u) {
-                // first answer to a store whose queries sit in dense neighbourhoods: keep the hi pass, re-score 512 per query
-                // from the next batch on (this batch's open queries go to the split pass below); only if THAT keeps failing does
-                // the store back off from the hi pass
-                own->hi_t512.store(1);
-                own->hi_fail_ema.store(0);
-            } else {
-                const int ema = (3 * own->hi_fail_ema.load() + (genuine == 0 ? 0 : 1024)) / 4;
-                own->hi_fail_ema.store(ema);
-                if (genuine * 8 > nq || ema > 512) {
-                    int b = own->hi_backoff.load() * 2;
-                    b = b < 4 ? 4 : b > 64 ? 64 : b;
-                    own->hi_backoff.store(b);
-                    own->hi_skip.store(b);
-                } else if (genuine == 0) own->hi_backoff.store(0);
-            }
-            if (!refine.empty() && (rc = run_level(refine, 1, 512, false))) return rc;
-        } else if (escalate && nq > 8 && own->wide_first.load() > 0) {
-            // the 512-candidate level has been failing on this store: start at the 4096-candidate one for a while
-            own->wide_first.fetch_sub(1);
-            if ((rc = run_level(i8_ran ? after_i8 : all, 1, 4096, !i8_ran))) return rc;
-        } else {
-            if ((rc = run_level(i8_ran ? after_i8 : all, 1, cascade ? 512u : 0u, !i8_ran))) return rc;
-        }
-        if (spec_now) {  // gate back-off: conservative for 8, 16, .. 256 batches after a failure, forgotten after a clean batch
-            if (st.gate_failed) {
-                int b = own->spec_backoff.load() * 2;
-                b = b < 8 ? 8 : b > 256 ? 256 : b;
-                own->spec_backoff.store(b);
-                own->spec_skip.store(b);
-            } else own->spec_backoff.store(0);
-        }
-        if (escalate) {
-            // third level: still more than a couple of exact passes' worth of open queries (near-duplicate clusters: hundreds of
-            // rows within the split pass's bound of the k-th score) — the split pass once more, re-scoring 4096 per query
-            std::vector<uint32_t> wide = open_queries();
-            if (wide.size() > 8 && st.rescored < (uint64_t)nq * 4096) {
-                if (wide.size() * 2 > nq) own->wide_first.store(16);  // most of the batch: skip the 512 level next time
-                if ((rc = run_level(wide, 1, 4096, false))) return rc;
-            }
-        }
-        // uncertified queries: recompute on the exact path (per-query lists)
-        std::vector<uint32_t> redo;
-        for (uint32_t q = 0; q < nq; q++)
-            if (unc[q]) redo.push_back(q);
-        st.retries = (uint32_t)redo.size();
-        if (!redo.empty()) {
-            std::vector<float> sub((size_t)redo.size() * s->dim);
-            for (size_t i = 0; i < redo.size(); i++) memcpy(&sub[i * s->dim], d->queries + (size_t)redo[i] * s->dim, (size_t)s->dim * 4);
-            std::vector<std::vector<ott_hit>> fix;
-            rc = run_exact(s, sub.data(), (uint32_t)redo.size(), d, true, pl, k_q, d_mask, mask_bits, true, fix, st);
-            if (rc) return rc;
-            for (size_t i = 0; i < redo.size(); i++) {
-                for (auto& h : fix[i]) h.query = redo[i];
-                pq[redo[i]] = std::move(fix[i]);
-            }
-        }
-        if (perq) lists = std::move(pq);
+        // per-query k for the batch path: the merged top-k is contained in the union of per-query top-k
+        const uint64_t k_q = d->k < pl.rows_scored ? d->k : pl.rows_scored;
+        Cascade c{s, d, pl, k_q, d_mask, mask_bits, st, own->cascade};
+        if ((rc = c.run())) return rc;
+        if (perq) lists = std::move(c.pq);
         else {
-            // reference semantics: one list over all (query, row) pairs (src/vec.rs:217-219).  The per-query lists are sorted
-            // best first, so the merged top-k is a k-way merge over their heads: k pops of a heap of nq cursors (a
-            // partial_sort over all nq x k hits was ~0.1 ms of a 256-query batch)
-            const CanonLess less{d->take == OTT_TAKE_MAX, co.tie_sh, tie_base(s)};
-            std::vector<std::pair<uint32_t, uint32_t>> heap;  // (list, position); the heap's top is the best head
-            auto worse = [&](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) {
-                return less(pq[b.first][b.second], pq[a.first][a.second]);
-            };
-            for (uint32_t q = 0; q < nq; q++)
-                if (!pq[q].empty()) heap.emplace_back(q, 0u);
-            std::make_heap(heap.begin(), heap.end(), worse);
-            std::vector<ott_hit> all;
-            all.reserve((size_t)k_eff < (size_t)nq * k_q ? (size_t)k_eff : (size_t)nq * k_q);
-            while (!heap.empty() && all.size() < k_eff) {
-                std::pop_heap(heap.begin(), heap.end(), worse);
-                const std::pair<uint32_t, uint32_t> cur = heap.back();
-                heap.pop_back();
-                all.push_back(pq[cur.first][cur.second]);
-                if (cur.second + 1 < pq[cur.first].size()) {
-                    heap.emplace_back(cur.first, cur.second + 1);
-                    std::push_heap(heap.begin(), heap.end(), worse);
-                }
-            }
-            lists.assign(1, std::move(all));
+            const size_t most = (size_t)k_eff < (size_t)nq * k_q ? (size_t)k_eff : (size_t)nq * k_q;
+            lists.assign(1, merge_lists(c.pq, CanonLess{d->take == OTT_TAKE_MAX, co.tie_sh, tie_base(s)}, most));
         }
     }
-
     if (out_dev) {
-        // device output of host-side lists (batch path, k > 512): [groups][cap / groups] slots, each list best first, the rest
-        // sentinels (already memset).  ONE copy of the whole block from pinned staging (a copy per query was ~5 us of enqueue
-        // each: 5 ms for the 1024 queries of a C4 shard)
-        const uint32_t groups = perq ? nq : 1u;
-        const uint64_t gstride = cap / groups;
-        const size_t blk = (size_t)groups * gstride * sizeof(ott_hit);
-        if ((rc = s->h_stage.ensure(blk + sizeof(uint64_t)))) return rc;
-        char* hs = (char*)s->h_stage.p;
-        memset(hs, 0xFF, blk);  // sentinels, as the memset of out_dev left them
-        uint64_t tot = 0;
-        for (uint32_t q = 0; q < groups; q++) {
-            const size_t c = lists[q].size() < gstride ? lists[q].size() : (size_t)gstride;
-            if (c) memcpy(hs + (size_t)q * gstride * sizeof(ott_hit), lists[q].data(), c * sizeof(ott_hit));
-            tot += c;
-        }
-        memcpy(hs + blk, &tot, sizeof(uint64_t));
-        OTT_HIP(hipMemcpyAsync(out_dev, hs, blk, hipMemcpyHostToDevice, s->stream));
-        if (n_out_dev) OTT_HIP(hipMemcpyAsync(n_out_dev, hs + blk, sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
-        if (!nosync) OTT_HIP(hipStreamSynchronize(s->stream));  // (nosync: h_stage stays untouched until the caller's own wait)
-        st.total_ns = now_ns() - t0;
-        if (stats_out) *stats_out = st;
-        return OTT_OK;
-    }
-    uint64_t total = 0;
-    for (size_t gq = 0; gq < lists.size(); gq++) {
-        const size_t c = lists[gq].size();
-        if (c) memcpy(out_host + total, lists[gq].data(), c * sizeof(ott_hit));
-        if (n_per_query && perq) n_per_query[gq] = c;
-        total += c;
-    }
-    if (n_out) *n_out = total;
-    st.total_ns = now_ns() - t0;
-    if (stats_out) *stats_out = st;
-    return OTT_OK;
+        if ((rc = emit_device_staged(s, lists, perq ? nq : 1u, o))) return rc;
+    } else emit_host(lists, perq, o);
+    return finish(st, t0, stats_out);
 }
 
 namespace {

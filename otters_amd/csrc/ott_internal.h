@@ -15,6 +15,7 @@
 
 #include "../../include/otters_hip.h"
 #include "ott_host.h"  // the host-side concurrency (thread pool, context pool, staged appends, background worker): HIP-free, sanitizer-tested
+#include "ott_policy.h"  // path choice and the batch cascade's back-off rules: HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
 #include "ott_audit.h"  // test build: every HIP call below goes through a device-affinity check (see "which GPU a call is for")
 #endif
@@ -253,19 +254,7 @@ struct ott_store {
     bool img8_off = false;
     uint32_t* d_img8_rel = nullptr;  // [0] running max of the measured loss (float bits), [1] rows marked irregular
     float img8_rel = 0.0f;
-    // hi-pass back-off: a batch in which ANY query falls through pays for both passes (the split pass streams the whole corpus
-    // again for the few), so the hi pass only pays while fewer than ~half the batches need the second one.  When more than 1/8
-    // of a batch falls through, or more than half of the recent batches needed the split pass, the next `hi_skip` batches go
-    // straight to it; the skip doubles (4 .. 64) while re-probes keep failing
-    std::atomic<int> hi_skip{0}, hi_backoff{0};
-    std::atomic<int> i8_skip{0}, i8_backoff{0};  // the same back-off for the int8 level in front of it
-    std::atomic<int> i8_t512{0};                 // calls left for which the int8 level re-scores 512 candidates per query (it failed queries at fewer)
-    std::atomic<int> i8_fail_ema{0};             // share (x1024, exponential average) of recent int8-level batches that needed a second pass at all
-    std::atomic<int> spec_skip{0};    // batches left that run with conservative gates (a speculative gate failed a query recently)
-    std::atomic<int> spec_backoff{0};
-    std::atomic<int> wide_first{0};   // batches left that start at the 4096-candidate level (the 512-candidate one kept failing)
-    std::atomic<int> hi_t512{0};      // the hi pass re-scores 512 candidates per query on this store (it failed queries at 2k + 56: dense neighbourhoods)
-    std::atomic<int> hi_fail_ema{0};  // share (x1024, exponential average) of recent hi-pass batches that needed the split pass at all
+    ott::CascadeState cascade;  // the batch cascade's back-off state (ott_policy.h), shared by the store's contexts: read through the owner
 
     hipStream_t stream = nullptr;
     hipEvent_t ev[7] = {};  // 0-2 batch path timing, 3-5 exact path timing, 6 multi-GPU store: this shard's candidate block is ready
@@ -396,7 +385,7 @@ void ctx_release(ott_store* w);
 int ensure_batch_image(ott_store* ctx, const uint16_t** img_out);
 int ensure_hi_plane(ott_store* ctx, const uint16_t** img_out, float* rel_max_out, bool* f16_out = nullptr, float* scale_out = nullptr);  // *img_out = nullptr when unavailable
 bool hi_plane_ready(ott_store* ctx);  // the plane exists and covers every row (nothing is built by asking)
-inline bool i8_wanted(const Options& o) { return (o.hi_fmt == -1 || o.hi_fmt == 2) && !o.mfma_f32 && !o.no_hi_pass && !o.no_batch_image; }
+inline bool i8_wanted(const Options& o) { return i8_wanted(o.hi_fmt, o.mfma_f32, o.no_hi_pass, o.no_batch_image); }
 // the plane the cascade STARTS with on this store — the int8 plane where the options ask for it and it fits, else the hi plane —
 // built / extended now (background builder, ott_store_prepare_batch); an existing hi plane is kept up to date beside it
 int ensure_first_plane(ott_store* ctx);
@@ -587,9 +576,6 @@ int upload_exact_inputs(ott_store* s, const float* queries, uint32_t nq, const R
 int run_mfma(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t k_q, const uint64_t* d_mask, uint64_t mask_bits,
              std::vector<std::vector<ott_hit>>& out, std::vector<uint32_t>& uncertified, ott_stats& st, int level, uint32_t t_min,  // t_min: re-score at least this many (0, 512, 4096)
              bool spec_gate);  // speculative emission thresholds between the row rounds (select_kernel); first level of a cascade only
-// the hi pass re-scores T >= 2k + 56 candidates per query (T <= 512); on a half plane, whose bound is ~8x tighter, k + k / 3 + 28
-// is enough (k <= 363 instead of 228: about 0.23 k rows lie within the bound of the k-th score on uniform rows)
-inline bool mfma_hi_k_ok(uint64_t k, bool half) { return half ? k + k / 3 + 28 <= 512 : 2 * k + 56 <= 512; }
 int launch_rand_fill(ott_store* s, uint64_t first_row, uint64_t n_rows, uint64_t seed);
 // ott_mfma.hip: the int8 level for ONE query as a streaming sweep (no matrix cores: the query is a vector) — exact_kernel<..., I8>
 // over the int8 plane with a wave-list top-T in its epilogue, merge, exact re-score + certification (finalize_kernel): three
