@@ -459,7 +459,13 @@ int ott_query_maxsim(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64
 /* Same, but the result stays on the GPU: out_dev holds `cap` ott_hit slots in device memory
  * of the store's GPU, padded with sentinel hits (index = UINT64_MAX); *n_out_dev (device
  * uint64) receives the count.  PER_QUERY mode: cap must be a multiple of nq; query q's hits
- * start at slot q * (cap / nq), each group sentinel padded.  Launched on the store's stream; returns once the kernels have
+ * start at slot q * (cap / nq), each group sentinel padded.  Every slot below cap holds a hit or a sentinel whose 16 bytes are all
+ * 0xFF; slots at and past cap are never written, on any route.  With groups = 1 (MERGED) or nq (PER_QUERY): a block of exactly
+ * cap / groups == 64 * list_E(k) slots per group (list_E: 1 up to k = 64, 2 up to 128, 4 up to 256, 8 up to 512 — what
+ * ott_query_sharded asks for) is the merge kernel's own geometry and is written IN PLACE, hits and sentinels by the one kernel;
+ * any other cap is filled with sentinels first and receives the hits by a copy of min(cap / groups, 64 * list_E(k)) slots per
+ * group; k > 512 and the cascade's results are staged on the host and arrive as one block of cap slots.
+ * Launched on the calling context's stream; returns once the kernels have
  * completed (the caller's collective runs on another stream).  Used for the multi-GPU
  * all-gather of candidates. */
 int ott_query_device(ott_store* s, const ott_query_desc* d, void* out_dev, uint64_t cap, void* n_out_dev,
