@@ -16,6 +16,7 @@
 #include "../../include/otters_hip.h"
 #include "ott_host.h"  // the host-side concurrency (thread pool, context pool, staged appends, background worker): HIP-free, sanitizer-tested
 #include "ott_policy.h"  // path choice and the batch cascade's back-off rules: HIP-free, CPU-tested
+#include "ott_plane_policy.h"  // the two format decisions of the cascade's planes: HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
 #include "ott_audit.h"  // test build: every HIP call below goes through a device-affinity check (see "which GPU a call is for")
 #endif
@@ -61,6 +62,12 @@ inline void attr_done(std::atomic<uint64_t>& seen, int device) {
 
 inline uint64_t now_ns() {
     return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// blocks of a grid-stride launch: one per `per_block` items, at most `per_cu` per compute unit, at least one
+inline uint32_t grid_blocks(uint64_t items, uint32_t per_block, int n_cu, uint32_t per_cu = 8) {
+    const uint64_t want = (items + per_block - 1) / per_block, most = (uint64_t)n_cu * per_cu;
+    return (uint32_t)(want < 1 ? 1 : want < most ? want : most);
 }
 
 // ---- device buffers that grow on demand -----------------------------------------------------
@@ -176,6 +183,40 @@ struct Rccl {
 constexpr int kNcclUint8 = 1;  // ncclDataType_t::ncclUint8 (rccl.h)
 Rccl* rccl();
 
+// ---- the cascade's planes (ott_planes.hip; their life cycle: DESIGN.md 2, "The cascade's planes") ---------------------------
+// One compact copy of the corpus for the batch path: built lazily by the first query that needs it (or declined), extended after
+// appends, kept in step by write_rows, dropped by whatever moves the rows and built again on demand.
+struct Plane {
+    void* d = nullptr;          // [cap rows of the plane's pitch]; nullptr = not there
+    uint64_t rows = 0;          // rows [0, rows) are converted
+    bool off = false;           // declined (no room, an option, the wrong format for the store); survives a drop
+    uint32_t* d_rel = nullptr;  // hi, int8: 16 B of device words, survive a drop — [0] running max of the measured loss over the regular
+                                // rows (float bits, atomicMax), [1] rows marked irregular, [2] scratch (min_regular_inv_kernel)
+    float rel = 0.0f;           // host copy of d_rel[0]: MEASURED, which makes the pass's error bound rigorous and tighter than the worst case
+};
+struct PlaneSet {
+    std::mutex mu;  // guards every field here, for all three planes: held by whoever builds or extends one (also from other query contexts
+                    // while the store is only held shared), so a query that needs a plane waits for the builder
+    // Split image: every row pre-split into bf16 hi + bf16 lo, per 32-k stage [32 hi | 32 lo] (the same 128 B a stage of f32 takes;
+    // row pitch = dim rounded up to 32 floats).  Doubles the store's HBM footprint; without it the kernel splits the f32 rows in
+    // registers.  Only built when a query falls through to the split pass.  split.off also switches the other two off.
+    Plane split;
+    // Hi plane: the 16-bit round-to-nearest value of every element, row pitch = dim rounded up to 64 elements — HALF the corpus
+    // bytes; the first candidate pass of a store without an int8 plane streams only this (one 16-bit MFMA per 16 k).
+    Plane hi;
+    HiFormat hi_format{false, 1.0f};  // IEEE half (11 significant bits, ~8x tighter bound) or bf16; half's one factor (hi_plane_format)
+    // Int8 plane (option hi_fmt = -1 / 2): every row as int8 with ONE f32 scale per row (s_v = max|v_i| / 127, element =
+    // rint(v_i / s_v)), row pitch = dim rounded up to 128 bytes — a QUARTER of the corpus bytes.  The batch path's cheapest
+    // candidate pass streams it (v_mfma_i32_32x32x32_i8: the integer accumulation is exact, so the pass's error bound is pure
+    // quantisation).  Rows that measure more than 2^-5 (one huge element among small ones) are marked irregular.
+    Plane i8;
+    float* d_i8_scale = nullptr;  // [cap] s_v
+    // d_flag bytes (bit 1: the half plane's factor does not suit the row; bit 2: int8 loses too much of it): ONE writer at a time —
+    // the plane builders, under `mu` — while other contexts' kernels read them.  Readers tolerate either value of a bit that is
+    // being set or taken back: a set bit only forces the row into the candidate list and its exact re-score (never changes a result),
+    // and a bit is cleared only together with dropping the plane whose passes consult it (ensure_i8_plane's rollback).
+};
+
 struct Column {
     uint32_t dtype;
     void* d_vals;
@@ -218,42 +259,7 @@ struct ott_store {
     uint32_t sk_words = 0, sk_pitch = 0, sk_stage0 = 0;  // code words per row, line pitch in words, first sketched stage
     uint32_t sk_bits = 0;                                // bits per sketched dim of the lines that are there (1 or 3)
     uint8_t* d_flag = nullptr;  // [cap] 1 = row norm is inf / NaN / > 1e18 / tiny but non-zero / underflowed (always re-scored exactly by the MFMA path)
-    // Batch-path image of the corpus: every row pre-split into bf16 hi + bf16 lo, per 32-k stage [32 hi | 32 lo] (the same
-    // 128 B a stage of f32 takes; row pitch = dim rounded up to 32 floats).  Built lazily by the first batch query, extended
-    // after appends, dropped on write_rows / reallocation; doubles the store's HBM footprint (skipped when it does not fit:
-    // the kernel then splits the f32 rows in registers).  Owner store only; guarded by img_mu.
-    uint16_t* d_img = nullptr;
-    uint64_t img_rows = 0, img_cap = 0;
-    bool img_off = false;
-    std::mutex img_mu;
-    // Hi plane: the bf16 (round-to-nearest) value of every element, row pitch = dim rounded up to 64 elements — HALF the
-    // corpus bytes.  The batch path's first candidate pass streams only this (one bf16 MFMA per 16 k); `imgh_rel` is the
-    // MEASURED max over regular rows of ||v - bf16(v)|| / ||v|| (hi_rows_kernel), which is what makes that pass's error
-    // bound rigorous and ~2.4x tighter than the worst case 2^-8.  Same life cycle as d_img (the split image is then only
-    // built when a query falls through to the split pass).
-    uint16_t* d_imgh = nullptr;
-    uint64_t imgh_rows = 0;
-    bool imgh_f16 = false;     // the plane holds IEEE half (round 3: 11 significant bits, ~8x tighter bound) instead of bf16
-    float imgh_scale = 1.0f;   // half only: the power-of-two factor every row was multiplied by before the conversion
-    bool imgh_off = false;
-    uint32_t* d_imgh_rel = nullptr;  // device word behind imgh_rel (float bits, atomicMax)
-    float imgh_rel = 0.0f;
-    // Int8 plane (round 5, option hi_fmt = 2): every row as int8 with ONE f32 scale per row (s_v = max|v_i| / 127, element =
-    // rint(v_i / s_v)), row pitch = dim rounded up to 128 bytes — a QUARTER of the corpus bytes.  The batch path's cheapest
-    // candidate pass streams it (v_mfma_i32_32x32x32_i8: the integer accumulation is exact, so the pass's error bound is pure
-    // quantisation, MEASURED per row when the plane is built: `img8_rel` = max over the regular rows of ||v - s_v v~|| / ||v||).
-    // Rows that measure more than 2^-5 (one huge element among small ones) are marked irregular (bit 2 of d_flag): always
-    // listed, always re-scored exactly.  Same life cycle as the hi plane; guarded by img_mu.
-    // d_flag bytes (bit 1: the half plane's factor does not suit the row; bit 2: int8 loses too much of it): ONE writer at a time —
-    // the plane builders, under img_mu — while other contexts' kernels read them.  Readers tolerate either value of a bit that is
-    // being set or taken back: a set bit only forces the row into the candidate list and its exact re-score (never changes a result),
-    // and a bit is cleared only together with dropping the plane whose passes consult it (ensure_i8_plane's rollback).
-    int8_t* d_img8 = nullptr;
-    float* d_img8_scale = nullptr;   // [cap] s_v
-    uint64_t img8_rows = 0;
-    bool img8_off = false;
-    uint32_t* d_img8_rel = nullptr;  // [0] running max of the measured loss (float bits), [1] rows marked irregular
-    float img8_rel = 0.0f;
+    ott::PlaneSet planes;       // the cascade's compact copies of the corpus (owner store only: contexts reach them through `owner`)
     ott::CascadeState cascade;  // the batch cascade's back-off state (ott_policy.h), shared by the store's contexts: read through the owner
 
     hipStream_t stream = nullptr;
@@ -323,7 +329,7 @@ struct ott_store {
     uint32_t cur_tie_sh = 0, cur_tie_off = 0;
     bool cur_flat = false;
 
-    ott::host::QuietWorker* builder = nullptr;  // ott_store.hip: the background thread behind option hi_prebuild (owner stores only)
+    ott::host::QuietWorker* builder = nullptr;  // ott_planes.hip: the background thread behind option hi_prebuild (owner stores only)
     std::vector<ott::Column> columns;
     // Concurrency (ott_query is re-entrant on a store from several host threads, append needs exclusive
     // access).  `rw`: queries hold it shared, everything that changes the store holds it exclusive.  `mu` guards ONE query
@@ -372,7 +378,7 @@ int multi_query(ott_store* ms, const ott_query_desc* d, ott_hit* out, uint64_t c
 // ott_store.hip: staged appends.  store_rows = rows appended (resident + staged); store_flush brings the staged ones to the GPU
 // (takes the store exclusively when there are any; call it WITHOUT holding the store's locks)
 void mfma_warm(hipStream_t stream, int device);  // ott_mfma.hip: loads the batch path's code object and warms the runtime's H2D copy path (background plane builder)
-void kick_plane_build(ott_store* s);  // ott_store.hip: rows were appended — (re)build the hi plane in the background if the policy says so
+void kick_plane_build(ott_store* s);  // ott_planes.hip: rows were appended — (re)build the first plane in the background if the policy says so
 inline uint64_t store_rows(const ott_store* s) { return s->n + s->pend.count(); }
 int store_flush(ott_store* s);
 int store_flush_locked(ott_store* s);  // the caller holds `rw` exclusively and `mu`
@@ -382,6 +388,16 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
 constexpr size_t OTT_MAX_WORKERS = 15;
 ott_store* ctx_acquire(ott_store* s);  // returns s or a worker, with its `mu` held
 void ctx_release(ott_store* w);
+// ---- ott_planes.hip: the cascade's planes (struct PlaneSet).  Everything below takes the planes' mutex itself. -----------------
+// The steps of the life cycle that belong to whoever changes the store (the caller holds it exclusively, on its device):
+void planes_drop(ott_store* own);     // the rows moved or changed wholesale: every plane goes (rebuilt on demand)
+bool planes_any(ott_store* own);      // a plane is there (its buffer would be given back by planes_drop)
+void planes_release(ott_store* own);  // ott_store_destroy: planes_drop + the loss words
+int planes_rewrite(ott_store* s, uint64_t first, uint64_t n);  // rows [first, first + n) were rewritten: converted again where a plane covers them; waits
+int planes_clear_marks(ott_store* s, uint64_t n);              // the planes' marks (bits 1, 2) in the flag bytes of rows [0, n), on s->stream
+void planes_enable(ott_store* own, bool enabled);              // ott_store_set_batch_image: off = drop and decline all three, on = allow them again
+void planes_set_options(ott_store* own, const Options& o);     // own->opt = o; a plane that an option declined is allowed again once the option allows it
+// The query side: built / extended on demand
 int ensure_batch_image(ott_store* ctx, const uint16_t** img_out);
 int ensure_hi_plane(ott_store* ctx, const uint16_t** img_out, float* rel_max_out, bool* f16_out = nullptr, float* scale_out = nullptr);  // *img_out = nullptr when unavailable
 bool hi_plane_ready(ott_store* ctx);  // the plane exists and covers every row (nothing is built by asking)
@@ -390,7 +406,7 @@ inline bool i8_wanted(const Options& o) { return i8_wanted(o.hi_fmt, o.mfma_f32,
 // built / extended now (background builder, ott_store_prepare_batch); an existing hi plane is kept up to date beside it
 int ensure_first_plane(ott_store* ctx);
 bool first_plane_ready(ott_store* ctx);
-// What the planes look like right now, read under img_mu (ensure_i8_plane / ensure_hi_plane change these fields from other query
+// What the planes look like right now, read under the planes' mutex (ensure_i8_plane / ensure_hi_plane change these fields from other query
 // contexts while the store is only held shared): the AUTO cost model, the background builder and kick_plane_build decide from this
 // snapshot.  A snapshot may be stale by the time it is used — every consumer only chooses a path or skips a build from it, and the
 // ensure_* calls that follow re-read the fields under the mutex.
@@ -412,7 +428,7 @@ int launch_i8_rows(hipStream_t stream, const float* rows, uint32_t ld, uint32_t 
 int launch_hi_rows(hipStream_t stream, const float* rows, uint32_t ld, uint32_t dim, uint32_t ldh, uint64_t n, uint16_t* out,
                    const float* scale, float* rel_out, int n_cu, bool f16 = false, float gscale = 1.0f);  // f16: IEEE half of x * scale[r] * gscale (gscale a power of two)
 int launch_split_rows(hipStream_t stream, const float* rows, uint32_t ld, uint32_t dim, uint32_t ldi, uint64_t n, uint16_t* out,
-                      const float* scale, int n_cu);  // f32 rows -> [32 hi | 32 lo] bf16 per 32-k stage (optionally row-scaled first)  // ott_store.hip; *img_out = nullptr when unavailable
+                      const float* scale, int n_cu);  // f32 rows -> [32 hi | 32 lo] bf16 per 32-k stage (optionally row-scaled first)
 }  // namespace ott
 
 namespace ott {

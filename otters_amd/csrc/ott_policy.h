@@ -37,7 +37,7 @@ struct PathIn {
     bool mfma_f32, no_hi_pass, no_batch_image;
     int hi_fmt, exact_small;
 };
-// what the planes look like right now (PlaneSnapshot, read under img_mu) and whether the int8 level is widened (i8_t512 > 0)
+// what the planes look like right now (PlaneSnapshot, read under the planes' mutex) and whether the int8 level is widened (i8_t512 > 0)
 struct PathPlanes {
     bool have_hi, hi_f16, i8_off, i8_widened;
 };
@@ -45,7 +45,7 @@ enum PathChoice { PATH_CHOICE_EXACT = 0, PATH_CHOICE_MFMA = 1, PATH_CHOICE_REFUS
 constexpr const char* kMfmaRefusal = "ott_query: the MFMA path needs dim >= 8 and k <= 484";
 
 // `planes()` -> PathPlanes is called on the AUTO branch only, `first_plane_ready()` -> bool only for ONE query that the hi pass
-// could serve: both take the store's img_mu, and a Manhattan, flat or explicit-path query touches no plane state
+// could serve: both take the mutex of the store's planes, and a Manhattan, flat or explicit-path query touches no plane state
 template <class Planes, class Ready>
 inline PathChoice choose_path(const PathIn& in, Planes&& planes, Ready&& first_plane_ready) {
     const uint32_t nq = in.nq;
@@ -53,7 +53,7 @@ inline PathChoice choose_path(const PathIn& in, Planes&& planes, Ready&& first_p
     const uint64_t k_q = in.k < in.rows_scored ? in.k : in.rows_scored;
     const bool mfma_ok = k_q + 28 <= 512 && in.dim >= 8;
     if (in.flat) return PATH_CHOICE_EXACT;  // (the flat pass exists on the exact-order kernel only)
-    if (in.metric == OTT_METRIC_MANHATTAN) return PATH_CHOICE_EXACT;  // EXACT only, decided before the cost model looks at the planes (img_mu)
+    if (in.metric == OTT_METRIC_MANHATTAN) return PATH_CHOICE_EXACT;  // EXACT only, decided before the cost model looks at the planes (their mutex)
     if (in.path == OTT_PATH_MFMA) return mfma_ok ? PATH_CHOICE_MFMA : PATH_CHOICE_REFUSED;
     if (in.path == OTT_PATH_EXACT) return PATH_CHOICE_EXACT;
     // AUTO: cost model fitted to MI355X measurements (benchmarks/small_corpus.py, nq_sweep.py), in milliseconds.
@@ -72,7 +72,7 @@ inline PathChoice choose_path(const PathIn& in, Planes&& planes, Ready&& first_p
     const double nq_pad = (double)((nq + bn - 1) / bn * bn);
     const bool f32pipe = in.mfma_f32;
     // (the plane's actual format once it exists — it may have fallen back to bf16 — else what the option asks for)
-    const PathPlanes ps = planes();  // (under img_mu: another context may be building or dropping a plane right now)
+    const PathPlanes ps = planes();  // (under the planes' mutex: another context may be building or dropping a plane right now)
     const bool plane_half = ps.have_hi ? ps.hi_f16 : in.hi_fmt != 0;
     const bool hi_ok = !f32pipe && mfma_hi_k_ok(k_q, plane_half) && !in.no_hi_pass;
     // round 5: the int8 plane in front (cosine / dot, k <= 128): a quarter of the bytes, twice the matrix rate, 512 candidates

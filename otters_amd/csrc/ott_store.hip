@@ -4,7 +4,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <chrono>
 #include <thread>
 
 #include <algorithm>
@@ -313,9 +312,7 @@ int update_min_pos_inv(ott_store* s, uint64_t first_row, uint64_t n_rows) {
     if (rc) return rc;
     const uint32_t init = 0x7F800000u;
     OTT_HIP(hipMemcpyAsync(s->d_minpos.p, &init, 4, hipMemcpyHostToDevice, s->stream));
-    uint64_t blocks = (n_rows + 255) / 256;
-    if (blocks > (uint64_t)s->n_cu * 8) blocks = (uint64_t)s->n_cu * 8;
-    hipLaunchKernelGGL(min_pos_inv_kernel, dim3((uint32_t)blocks), dim3(256), 0, s->stream, s->d_inv, first_row, n_rows,
+    hipLaunchKernelGGL(min_pos_inv_kernel, dim3(grid_blocks(n_rows, 256, s->n_cu)), dim3(256), 0, s->stream, s->d_inv, first_row, n_rows,
                        (uint32_t*)s->d_minpos.p);
     OTT_HIP(hipGetLastError());
     uint32_t got = init;
@@ -486,13 +483,12 @@ static int update_sketch(ott_store* s, uint64_t first_row, uint64_t n_rows) {
         }
     }
     const uint64_t lo = first_row < s->sk_n ? first_row : s->sk_n, hi = first_row + n_rows;
-    uint64_t blocks = ((hi - lo + 63) / 64 + 3) / 4;  // a wave per 64 rows, as launch_inv_norms
-    if (blocks > (uint64_t)s->n_cu * 8) blocks = (uint64_t)s->n_cu * 8;
+    const uint32_t blocks = grid_blocks((hi - lo + 63) / 64, 4, s->n_cu);  // a wave per 64 rows, as launch_inv_norms
     if (s->sk_bits == 3)
-        hipLaunchKernelGGL(tail_sketch_kernel<3>, dim3((uint32_t)blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
+        hipLaunchKernelGGL(tail_sketch_kernel<3>, dim3(blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
                            nst - s->sk_stage0, s->sk_pitch, s->d_sketch);
     else
-        hipLaunchKernelGGL(tail_sketch_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
+        hipLaunchKernelGGL(tail_sketch_kernel<1>, dim3(blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
                            nst - s->sk_stage0, s->sk_pitch, s->d_sketch);
     OTT_HIP(hipGetLastError());
     if (hi > s->sk_n) s->sk_n = hi;
@@ -501,11 +497,7 @@ static int update_sketch(ott_store* s, uint64_t first_row, uint64_t n_rows) {
 
 int launch_inv_norms(ott_store* s, uint64_t first_row, uint64_t n_rows) {
     if (!n_rows) return OTT_OK;
-    uint64_t tiles = (n_rows + 63) / 64;
-    uint64_t blocks = (tiles + 3) / 4;
-    uint64_t cap = (uint64_t)s->n_cu * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(inv_norm_kernel, dim3((uint32_t)blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, first_row,
+    hipLaunchKernelGGL(inv_norm_kernel, dim3(grid_blocks((n_rows + 63) / 64, 4, s->n_cu)), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, first_row,
                        n_rows, s->d_inv, s->d_flag);
     OTT_HIP(hipGetLastError());
     return update_sketch(s, first_row, n_rows);
@@ -518,8 +510,6 @@ int launch_rand_fill(ott_store* s, uint64_t first_row, uint64_t n_rows, uint64_t
     OTT_HIP(hipGetLastError());
     return OTT_OK;
 }
-
-__global__ void clear_flag_bit_kernel(uint8_t* flag, uint64_t n, uint8_t mask);  // below
 
 // (re)allocate rows / inv_norms / row flags for `ncap` rows, keeping the first s->n rows
 static int realloc_store(ott_store* s, uint64_t ncap) {
@@ -553,20 +543,9 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
         // The store's own copies of the corpus for the batch path (int8 plane, 16-bit plane, split image) are dropped by a
         // reallocation anyway: when the new buffers do not fit NEXT TO them, they go first and the allocation is tried once more
         // (a store that grows without a plan must not fail because the background builder took a quarter of the free memory)
-        std::lock_guard<std::mutex> g(s->img_mu);
-        if (attempt == 1 || e != hipErrorOutOfMemory || (!s->d_img && !s->d_imgh && !s->d_img8)) break;
+        if (attempt == 1 || e != hipErrorOutOfMemory || !planes_any(s)) break;
         OTT_HIP(hipStreamSynchronize(s->stream));
-        if (s->d_img) (void)hipFree(s->d_img);
-        if (s->d_imgh) (void)hipFree(s->d_imgh);
-        if (s->d_img8) (void)hipFree(s->d_img8);
-        if (s->d_img8_scale) (void)hipFree(s->d_img8_scale);
-        s->d_img = nullptr;
-        s->d_imgh = nullptr;
-        s->d_img8 = nullptr;
-        s->d_img8_scale = nullptr;
-        s->img_rows = s->img_cap = 0;
-        s->imgh_rows = 0;
-        s->img8_rows = 0;
+        planes_drop(s);
     }
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? OTT_ERR_OOM : OTT_ERR_HIP, std::string("hipMalloc(store): ") + hipGetErrorString(e));
     if (s->n) {
@@ -591,17 +570,7 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
     s->d_sketch = nsk;
     if (!nsk) s->sk_n = 0;
     s->cap = ncap;
-    if (s->d_img) (void)hipFree(s->d_img);  // the batch image is rebuilt lazily at the new capacity
-    s->d_img = nullptr;
-    s->img_rows = s->img_cap = 0;
-    if (s->d_imgh) (void)hipFree(s->d_imgh);
-    s->d_imgh = nullptr;
-    s->imgh_rows = 0;
-    if (s->d_img8) (void)hipFree(s->d_img8);
-    if (s->d_img8_scale) (void)hipFree(s->d_img8_scale);
-    s->d_img8 = nullptr;
-    s->d_img8_scale = nullptr;
-    s->img8_rows = 0;
+    planes_drop(s);  // rebuilt lazily at the new capacity
     return OTT_OK;
 }
 
@@ -634,27 +603,13 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
     s->sk_n = sketch ? n : 0;
     s->n = n;
     s->cap = cap;
-    {
-        std::lock_guard<std::mutex> g(s->img_mu);
-        if (s->d_img) (void)hipFree(s->d_img);
-        s->d_img = nullptr;
-        s->img_rows = s->img_cap = 0;
-        if (s->d_imgh) (void)hipFree(s->d_imgh);
-        s->d_imgh = nullptr;
-        s->imgh_rows = 0;
-        if (s->d_img8) (void)hipFree(s->d_img8);
-        if (s->d_img8_scale) (void)hipFree(s->d_img8_scale);
-        s->d_img8 = nullptr;
-        s->d_img8_scale = nullptr;
-        s->img8_rows = 0;
-    }
+    planes_drop(s);
     s->evalmask_bits = 0;
     s->min_pos_inv = __builtin_inff();
     if (!n) return OTT_OK;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->n_cu * 8);
-    hipLaunchKernelGGL(clear_flag_bit_kernel, dim3(grid), dim3(256), 0, s->stream, s->d_flag, n, (uint8_t)0xF9);  // the planes' marks (bits 1, 2)
-    OTT_HIP(hipGetLastError());
-    const int rc = update_min_pos_inv(s, 0, n);
+    int rc = planes_clear_marks(s, n);
+    if (rc) return rc;
+    rc = update_min_pos_inv(s, 0, n);
     kick_plane_build(s);
     return rc;
 }
@@ -666,28 +621,14 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
 // The caller holds the store exclusively and `mu`.
 int store_after_compact(ott_store* s, uint64_t new_n) {
     s->n = new_n;
-    {
-        std::lock_guard<std::mutex> g(s->img_mu);
-        if (s->d_img) (void)hipFree(s->d_img);
-        s->d_img = nullptr;
-        s->img_rows = s->img_cap = 0;
-        if (s->d_imgh) (void)hipFree(s->d_imgh);
-        s->d_imgh = nullptr;
-        s->imgh_rows = 0;
-        if (s->d_img8) (void)hipFree(s->d_img8);
-        if (s->d_img8_scale) (void)hipFree(s->d_img8_scale);
-        s->d_img8 = nullptr;
-        s->d_img8_scale = nullptr;
-        s->img8_rows = 0;
-    }
+    planes_drop(s);
     s->evalmask_bits = 0;
     s->sk_n = 0;
     s->min_pos_inv = __builtin_inff();
     if (!new_n) return OTT_OK;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((new_n + 255) / 256, (uint64_t)s->n_cu * 8);
-    hipLaunchKernelGGL(clear_flag_bit_kernel, dim3(grid), dim3(256), 0, s->stream, s->d_flag, new_n, (uint8_t)0xF9);  // the planes' marks (bits 1, 2)
-    OTT_HIP(hipGetLastError());
-    int rc = update_sketch(s, 0, new_n);
+    int rc = planes_clear_marks(s, new_n);
+    if (rc) return rc;
+    rc = update_sketch(s, 0, new_n);
     if (rc) return rc;
     rc = update_min_pos_inv(s, 0, new_n);
     kick_plane_build(s);
@@ -743,10 +684,6 @@ int store_flush(ott_store* s) {
     return store_flush_locked(s);
 }
 
-}  // namespace ott
-
-namespace ott {
-
 static ott_store* make_worker(ott_store* s) {
     ott_store* w = new ott_store();
     w->is_worker = true;
@@ -796,476 +733,6 @@ static void alias_corpus(ott_store* w, const ott_store* s) {
     w->n_groups = s->n_groups;
 }
 
-// rows [first, first + n) -> batch image: one thread per (row, 4 floats)
-__global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ rows, uint32_t ld, uint32_t dim, uint32_t ldi,
-                                                          uint64_t first, uint64_t n, uint16_t* __restrict__ img,
-                                                          const float* __restrict__ scale) {  // scale: optional per-row factor
-    const uint32_t quads = ldi / 4;
-    const uint64_t total = n * quads;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t r = first + i / quads;
-        const uint32_t c = (uint32_t)(i % quads) * 4;
-        float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < ld) x = *reinterpret_cast<const float4*>(rows + r * (uint64_t)ld + c);  // ld is a multiple of 4, padded with zeros
-        const float v[4] = {x.x, x.y, x.z, x.w};
-        uint16_t h[4], l[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const float xe = (c + e < dim) ? (scale ? v[e] * scale[r] : v[e]) : 0.0f;
-            const __bf16 hb = (__bf16)xe;
-            const __bf16 lb = (__bf16)(xe - (float)hb);
-            h[e] = __builtin_bit_cast(uint16_t, hb);
-            l[e] = __builtin_bit_cast(uint16_t, lb);
-        }
-        uint16_t* dst = img + r * (uint64_t)ldi * 2 + (c / 32) * 64 + (c % 32);
-        *reinterpret_cast<uint2*>(dst) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
-        *reinterpret_cast<uint2*>(dst + 32) = make_uint2((uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16));
-    }
-}
-
-int launch_split_rows(hipStream_t stream, const float* rows, uint32_t ld, uint32_t dim, uint32_t ldi, uint64_t n, uint16_t* out,
-                      const float* scale, int n_cu) {
-    const uint64_t work = n * (ldi / 4);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((work + 255) / 256, (uint64_t)n_cu * 16);
-    hipLaunchKernelGGL(split_rows_kernel, dim3(grid ? grid : 1), dim3(256), 0, stream, rows, ld, dim, ldi, (uint64_t)0, n, out, scale);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-// rows [first, first + n) -> hi plane (bf16 round-to-nearest of every element), one wave per row.  Also measures what the
-// rounding lost: rel = ||x - bf16(x)|| / ||x|| per row (f64 sums: the squares of a 1e-18-norm row underflow in f32), written
-// to rel_out[r] (optional) and folded into *rel_max (optional; float bits, rows with flag[r] != 0 excluded — those are always
-// re-scored exactly).  This measured figure, not the worst case 2^-8, is what the hi pass's certification uses.
-// F16 = false: bf16 (round to nearest even) of every element.  F16 = true (round 3): IEEE half — the same two bytes carry
-// 11 significant bits instead of 8, so the measured rounding loss ||v - h(v)|| / ||v|| is ~8x smaller (2.1e-4 against 1.65e-3
-// on uniform rows) and the hi pass's error bound with it; the price is half's narrow exponent range, met by ONE
-// power-of-two factor for all rows (`gscale`, exact; chosen in ensure_hi_plane).  A row whose elements
-// then fall into half's subnormals (a norm far below the store's largest) or overflow (appended after the plane was
-// scaled) simply MEASURES a large loss: rows above `rel_flag` are marked irregular (`flag_rw`, bit 1) — excluded from the
-// store's maximum, always listed, always re-scored exactly — exactly like rows outside the bf16 pass's error model.
-template <bool F16>
-__global__ __launch_bounds__(256) void hi_rows_kernel(const float* __restrict__ rows, uint32_t ld, uint32_t dim, uint32_t ldh,
-                                                       uint64_t first, uint64_t n, uint16_t* __restrict__ img,
-                                                       const float* __restrict__ scale, float* __restrict__ rel_out,
-                                                       uint32_t* __restrict__ rel_max, const uint8_t* flag, float gscale,
-                                                       float rel_flag, uint8_t* flag_rw) {  // (flag and flag_rw may be the same array)
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wid = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (uint64_t)gridDim.x * 4;
-    for (uint64_t i = wid; i < n; i += nw) {
-        const uint64_t r = first + i;
-        const float sc = scale ? __fmul_rn(scale[r], gscale) : gscale;  // gscale is a power of two (1 for bf16): exact
-        double se = 0.0, sx = 0.0;
-        for (uint32_t c = lane * 4; c < ldh; c += 256) {
-            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < ld) x = *reinterpret_cast<const float4*>(rows + r * (uint64_t)ld + c);  // ld is a multiple of 4, padded with zeros
-            const float v[4] = {x.x, x.y, x.z, x.w};
-            uint16_t h[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const float xe = (c + e < dim) ? ((scale || F16) ? __fmul_rn(v[e], sc) : v[e]) : 0.0f;
-                float back;
-                if constexpr (F16) {
-                    const _Float16 hb = (_Float16)xe;  // v_cvt_f16_f32: round to nearest even, overflow -> inf, gradual underflow
-                    back = (float)hb;
-                    h[e] = __builtin_bit_cast(uint16_t, hb);
-                } else {
-                    const __bf16 hb = (__bf16)xe;
-                    back = (float)hb;
-                    h[e] = __builtin_bit_cast(uint16_t, hb);
-                }
-                const double df = (double)xe - (double)back;
-                se += df * df;
-                sx += (double)xe * (double)xe;
-            }
-            *reinterpret_cast<uint2*>(img + r * (uint64_t)ldh + c) =
-                make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            se += __shfl_xor(se, off);
-            sx += __shfl_xor(sx, off);
-        }
-        if (lane == 0) {
-            // rounded up (1 + 1e-4 covers the f64 sums and the f32 conversion); a non-finite row measures as 1 = "cannot certify"
-            float rel = sx > 0.0 ? (float)(sqrt(se / sx) * 1.0001) : 0.0f;
-            if (!(rel <= 1.0f)) rel = 1.0f;
-            if (rel_out) rel_out[i] = rel;
-            bool irregular = flag && (flag[r] & 1u);
-            if (flag_rw && rel > rel_flag && !irregular) {
-                flag_rw[r] = (uint8_t)(flag_rw[r] | 2u);  // bit 1: outside the HALF hi pass's error model only (see mfma_score_kernel)
-                irregular = true;
-                if (rel_max) atomicAdd(rel_max + 1, 1u);  // how many rows the plane's one factor does not suit
-            }
-            // (look first: one atomic per row on ONE address serialises — 10M rows took 113 ms; the running max settles at once)
-            if (rel_max && !irregular && __float_as_uint(rel) > __hip_atomic_load(rel_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                atomicMax(rel_max, __float_as_uint(rel));
-        }
-    }
-}
-
-int launch_hi_rows(hipStream_t stream, const float* rows, uint32_t ld, uint32_t dim, uint32_t ldh, uint64_t n, uint16_t* out,
-                   const float* scale, float* rel_out, int n_cu, bool f16, float gscale) {
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 3) / 4, (uint64_t)n_cu * 8);
-    if (f16)
-        hipLaunchKernelGGL(hi_rows_kernel<true>, dim3(grid ? grid : 1), dim3(256), 0, stream, rows, ld, dim, ldh, (uint64_t)0, n, out, scale, rel_out,
-                           (uint32_t*)nullptr, (const uint8_t*)nullptr, gscale, 2.0f, (uint8_t*)nullptr);
-    else
-        hipLaunchKernelGGL(hi_rows_kernel<false>, dim3(grid ? grid : 1), dim3(256), 0, stream, rows, ld, dim, ldh, (uint64_t)0, n, out, scale, rel_out,
-                           (uint32_t*)nullptr, (const uint8_t*)nullptr, 1.0f, 2.0f, (uint8_t*)nullptr);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-// smallest non-zero inverse norm over the REGULAR rows (the largest norm the half plane's factor has to accommodate)
-__global__ __launch_bounds__(256) void min_regular_inv_kernel(const float* __restrict__ inv, const uint8_t* __restrict__ flag, uint64_t n, uint32_t* out) {
-    uint32_t best = 0x7F800000u;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t b = __float_as_uint(inv[i]);
-        if (b != 0 && b < best && !(flag[i] & 1u)) best = b;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t other = __shfl_xor(best, o);
-        best = other < best ? other : best;
-    }
-    if ((threadIdx.x & 63) == 0) atomicMin(out, best);
-}
-
-__global__ __launch_bounds__(256) void clear_flag_bit_kernel(uint8_t* flag, uint64_t n, uint8_t mask) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) flag[i] = (uint8_t)(flag[i] & mask);
-}
-
-// rows [first, first + cnt) of the store -> its hi plane, in the plane's format (half: scaled by the plane's factor, rows that
-// measure a loss above 2^-10 — five times what a row of ordinary dynamic range measures — marked irregular)
-static int launch_store_hi_rows(ott_store* own, hipStream_t stream, uint64_t first, uint64_t cnt) {
-    const uint32_t ldh = (own->dim + 63u) & ~63u;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((cnt + 3) / 4, (uint64_t)own->n_cu * 8);
-    if (own->imgh_f16)
-        hipLaunchKernelGGL(hi_rows_kernel<true>, dim3(grid), dim3(256), 0, stream, own->d_rows, own->ld, own->dim, ldh, first, cnt, own->d_imgh,
-                           (const float*)nullptr, (float*)nullptr, own->d_imgh_rel, own->d_flag, own->imgh_scale, 9.765625e-4f, own->d_flag);
-    else
-        hipLaunchKernelGGL(hi_rows_kernel<false>, dim3(grid), dim3(256), 0, stream, own->d_rows, own->ld, own->dim, ldh, first, cnt, own->d_imgh,
-                           (const float*)nullptr, (float*)nullptr, own->d_imgh_rel, own->d_flag, 1.0f, 2.0f, (uint8_t*)nullptr);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-// the store's hi plane, built / extended on demand (see ott_internal.h); *img_out = nullptr when it is unavailable
-int ensure_hi_plane(ott_store* ctx, const uint16_t** img_out, float* rel_max_out, bool* f16_out, float* scale_out) {
-    *img_out = nullptr;
-    if (f16_out) *f16_out = false;
-    if (scale_out) *scale_out = 1.0f;
-    ott_store* own = ctx->owner ? ctx->owner : ctx;
-    std::lock_guard<std::mutex> g(own->img_mu);
-    if (own->imgh_off || own->img_off || own->n == 0) return OTT_OK;
-    const uint32_t ldh = (own->dim + 63u) & ~63u;
-    if (!own->d_imgh) {
-        const size_t bytes = (size_t)own->cap * ldh * 2;
-        size_t free_b = 0, total_b = 0;
-        if (own->opt.no_batch_image || own->opt.no_hi_pass || hipMemGetInfo(&free_b, &total_b) != hipSuccess ||
-            free_b < bytes + (size_t)(2ull << 30) || hipMalloc((void**)&own->d_imgh, bytes) != hipSuccess) {
-            own->d_imgh = nullptr;
-            own->imgh_off = true;  // does not fit (or switched off): the batch path starts at the split pass
-            (void)hipGetLastError();
-            return OTT_OK;
-        }
-        own->imgh_rows = 0;
-    }
-    if (!own->d_imgh_rel) {  // [0] running max of the measured rounding loss (float bits), [1] rows the half plane's factor does not suit, [2] scratch
-        OTT_HIP(hipMalloc((void**)&own->d_imgh_rel, 16));
-        OTT_HIP(hipMemsetAsync(own->d_imgh_rel, 0, 16, ctx->stream));
-    }
-    if (own->imgh_rows == 0) {
-        // format of the plane: IEEE half unless the store asks for bf16 (option hi_fmt = 0).  Half needs ONE power-of-two factor
-        // for all rows, derived from the largest REGULAR row norm
-        own->imgh_f16 = own->opt.hi_fmt != 0;
-        own->imgh_scale = 1.0f;
-        OTT_HIP(hipMemsetAsync(own->d_imgh_rel, 0, 16, ctx->stream));
-        if (own->imgh_f16) {
-            const uint32_t init = 0x7F800000u;
-            uint32_t got = init;
-            OTT_HIP(hipMemcpyAsync(own->d_imgh_rel + 2, &init, 4, hipMemcpyHostToDevice, ctx->stream));
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((own->n + 255) / 256, (uint64_t)own->n_cu * 8);
-            hipLaunchKernelGGL(min_regular_inv_kernel, dim3(grid), dim3(256), 0, ctx->stream, own->d_inv, own->d_flag, own->n, own->d_imgh_rel + 2);
-            OTT_HIP(hipGetLastError());
-            OTT_HIP(hipMemcpyAsync(&got, own->d_imgh_rel + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
-            OTT_HIP(hipStreamSynchronize(ctx->stream));
-            float min_inv;
-            memcpy(&min_inv, &got, 4);
-            const float max_norm = (got != init && min_inv > 0.0f) ? 1.0f / min_inv : 1.0f;
-            // factor = 2^-round(log2(max_norm) / 4).  The batch path multiplies its query operands by the RECIPROCAL (so the
-            // accumulators need no correction): rows then sit around max_norm^0.75 / sqrt(dim), unit-length (cosine) queries
-            // around max_norm^0.25 / sqrt(dim), raw (dot / L2) queries of similar length around max_norm^1.25 / sqrt(dim) — all
-            // inside half's normal range for norms from ~1e-3 to a few thousand (cosine: to ~1e6).  Outside that, bf16.
-            int e = 0;
-            (void)frexpf(max_norm, &e);              // max_norm = m * 2^e, m in [0.5, 1)
-            own->imgh_scale = ldexpf(1.0f, -(e / 4));
-            if (!(own->imgh_scale > 0.0f) || !(own->imgh_scale < __builtin_inff()) || max_norm > 1e6f || max_norm < 1e-3f) {
-                own->imgh_f16 = false;
-                own->imgh_scale = 1.0f;
-            }
-        }
-    }
-    if (own->imgh_rows < own->n) {
-        const bool from_scratch = own->imgh_rows == 0;
-        const uint64_t first = own->imgh_rows, cnt = own->n - first;
-        int rch = launch_store_hi_rows(own, ctx->stream, first, cnt);
-        if (rch) return rch;
-        uint32_t bits[2] = {0, 0};
-        OTT_HIP(hipMemcpyAsync(bits, own->d_imgh_rel, 8, hipMemcpyDeviceToHost, ctx->stream));
-        OTT_HIP(hipStreamSynchronize(ctx->stream));  // published below: other contexts' streams may read it at once
-        if (own->imgh_f16 && from_scratch && (uint64_t)bits[1] * 64 > cnt) {
-            // more than 1 row in 64 does not fit the one factor (norms spread over many binades): half is the wrong format for
-            // this store.  The marks are taken back and the plane is built again as bf16, whose exponent range is f32's
-            own->imgh_f16 = false;
-            own->imgh_scale = 1.0f;
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((own->n + 255) / 256, (uint64_t)own->n_cu * 8);
-            hipLaunchKernelGGL(clear_flag_bit_kernel, dim3(grid), dim3(256), 0, ctx->stream, own->d_flag, own->n, (uint8_t)0xFD);
-            OTT_HIP(hipGetLastError());
-            OTT_HIP(hipMemsetAsync(own->d_imgh_rel, 0, 16, ctx->stream));
-            if ((rch = launch_store_hi_rows(own, ctx->stream, first, cnt))) return rch;
-            OTT_HIP(hipMemcpyAsync(bits, own->d_imgh_rel, 8, hipMemcpyDeviceToHost, ctx->stream));
-            OTT_HIP(hipStreamSynchronize(ctx->stream));
-        }
-        memcpy(&own->imgh_rel, &bits[0], 4);
-        own->imgh_rows = own->n;
-    }
-    *img_out = own->d_imgh;
-    *rel_max_out = own->imgh_rel;
-    if (f16_out) *f16_out = own->imgh_f16;
-    if (scale_out) *scale_out = own->imgh_scale;
-    return OTT_OK;
-}
-
-bool hi_plane_ready(ott_store* ctx) {
-    ott_store* own = ctx->owner ? ctx->owner : ctx;
-    std::lock_guard<std::mutex> g(own->img_mu);
-    return own->d_imgh != nullptr && !own->imgh_off && !own->img_off && own->n != 0 && own->imgh_rows == own->n;
-}
-
-int ensure_batch_image(ott_store* ctx, const uint16_t** img_out) {
-    *img_out = nullptr;
-    ott_store* own = ctx->owner ? ctx->owner : ctx;
-    std::lock_guard<std::mutex> g(own->img_mu);
-    if (own->img_off || own->n == 0) return OTT_OK;
-    const uint32_t ldi = (own->dim + 31u) & ~31u;
-    if (!own->d_img) {
-        const size_t bytes = (size_t)own->cap * ldi * 4;
-        size_t free_b = 0, total_b = 0;
-        if (own->opt.no_batch_image || hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + (size_t)(2ull << 30) ||
-            hipMalloc((void**)&own->d_img, bytes) != hipSuccess) {
-            own->d_img = nullptr;
-            own->img_off = true;  // does not fit (or switched off): split in registers instead
-            (void)hipGetLastError();
-            return OTT_OK;
-        }
-        own->img_cap = own->cap;
-        own->img_rows = 0;
-    }
-    if (own->img_rows < own->n) {
-        const uint64_t first = own->img_rows, cnt = own->n - first;
-        const uint64_t work = cnt * (ldi / 4);
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((work + 255) / 256, (uint64_t)own->n_cu * 16);
-        hipLaunchKernelGGL(split_rows_kernel, dim3(grid), dim3(256), 0, ctx->stream, own->d_rows, own->ld, own->dim, ldi, first, cnt, own->d_img, nullptr);
-        OTT_HIP(hipGetLastError());
-        OTT_HIP(hipStreamSynchronize(ctx->stream));  // published below: other contexts' streams may read it at once
-        own->img_rows = own->n;
-    }
-    *img_out = own->d_img;
-    return OTT_OK;
-}
-
-// ---- int8 plane (round 5) --------------------------------------------------------------------------------------------------
-// rows [first, first + n) -> int8, one wave per row.  Per-row scale s = max|x| / 127 (or the caller's common scale), element =
-// rint(x / s) clamped to +-127.  What the rounding lost is MEASURED in f64 against the values actually stored:
-// rel = ||x - s x~|| / ||x|| (rounded up), into rel_out[r] and — regular rows only — the running maximum *rel_max; a row above
-// rel_flag is marked irregular (bit 2 of flag_rw) and counted in rel_max[1] instead.
-constexpr float I8_REL_FLAG = 0.03125f;  // 2^-5: eight times what a row of ordinary dynamic range measures at dim 768
-__global__ __launch_bounds__(256) void i8_rows_kernel(const float* __restrict__ rows, uint32_t ld, uint32_t dim, uint32_t ld8, uint64_t first, uint64_t n,
-                                                       int8_t* __restrict__ img, const float* __restrict__ pre, float common_scale,
-                                                       float* __restrict__ scale_out, float* __restrict__ rel_out, uint32_t* __restrict__ rel_max,
-                                                       const uint8_t* flag, float rel_flag, uint8_t* flag_rw) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wid = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (uint64_t)gridDim.x * 4;
-    for (uint64_t i = wid; i < n; i += nw) {
-        const uint64_t r = first + i;
-        const float pf = pre ? pre[r] : 1.0f;
-        const float* x = rows + r * (uint64_t)ld;
-        float s = common_scale;
-        if (!(common_scale > 0.0f)) {
-            float mx = 0.0f;
-            for (uint32_t c = lane * 4; c < ld; c += 256) {
-                const float4 v = *reinterpret_cast<const float4*>(x + c);  // ld is a multiple of 4, padded with zeros
-                mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v.x * pf), fabsf(v.y * pf)), fmaxf(fabsf(v.z * pf), fabsf(v.w * pf))));  // (fmaxf drops a NaN operand)
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-            s = mx / 127.0f;
-            if (!(s < __builtin_inff())) s = 0.0f;  // a non-finite row: flagged at append, always re-scored exactly; its plane row is zeros
-        }
-        const float inv_s = s > 0.0f ? 1.0f / s : 0.0f;
-        double se = 0.0, sx = 0.0;
-        for (uint32_t c = lane * 4; c < ld8; c += 256) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < ld) v = *reinterpret_cast<const float4*>(x + c);
-            const float xe[4] = {v.x * pf, v.y * pf, v.z * pf, v.w * pf};
-            int q[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                float t = (c + e < dim) ? rintf(xe[e] * inv_s) : 0.0f;
-                t = t == t ? fminf(fmaxf(t, -127.0f), 127.0f) : 0.0f;
-                q[e] = (int)t;
-                if (c + e < dim) {
-                    const double df = (double)xe[e] - (double)s * (double)q[e];
-                    se += df * df;
-                    sx += (double)xe[e] * (double)xe[e];
-                }
-            }
-            *reinterpret_cast<uint32_t*>(img + r * (uint64_t)ld8 + c) =
-                (uint32_t)(uint8_t)q[0] | ((uint32_t)(uint8_t)q[1] << 8) | ((uint32_t)(uint8_t)q[2] << 16) | ((uint32_t)(uint8_t)q[3] << 24);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            se += __shfl_xor(se, off);
-            sx += __shfl_xor(sx, off);
-        }
-        if (lane == 0) {
-            if (scale_out) scale_out[r] = s;
-            float rel = sx > 0.0 ? (float)(sqrt(se / sx) * 1.0001) : 0.0f;
-            if (!(rel <= 1.0f)) rel = 1.0f;
-            if (rel_out) rel_out[i] = rel;
-            bool irregular = flag && (flag[r] & 1u);
-            if (flag_rw && !irregular) {
-                if (rel > rel_flag) {
-                    flag_rw[r] = (uint8_t)(flag_rw[r] | 4u);
-                    irregular = true;
-                    if (rel_max) atomicAdd(rel_max + 1, 1u);
-                } else if (flag_rw[r] & 4u) {
-                    flag_rw[r] = (uint8_t)(flag_rw[r] & ~4u);  // a rewritten row that suits the format again
-                }
-            }
-            if (rel_max && !irregular && __float_as_uint(rel) > __hip_atomic_load(rel_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                atomicMax(rel_max, __float_as_uint(rel));
-        }
-    }
-}
-
-int launch_i8_rows(hipStream_t stream, const float* rows, uint32_t ld, uint32_t dim, uint32_t ld8, uint64_t first, uint64_t n, int8_t* out,
-                   const float* pre, float common_scale, float* scale_out, float* rel_out, uint32_t* rel_max, const uint8_t* flag, float rel_flag,
-                   uint8_t* flag_rw, int n_cu) {
-    if (!n) return OTT_OK;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 3) / 4, (uint64_t)n_cu * 8);
-    hipLaunchKernelGGL(i8_rows_kernel, dim3(grid ? grid : 1), dim3(256), 0, stream, rows, ld, dim, ld8, first, n, out, pre, common_scale, scale_out, rel_out,
-                       rel_max, flag, rel_flag, flag_rw);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-int ensure_i8_plane(ott_store* ctx, const int8_t** img_out, const float** scale_out, float* rel_max_out) {
-    *img_out = nullptr;
-    *scale_out = nullptr;
-    ott_store* own = ctx->owner ? ctx->owner : ctx;
-    std::lock_guard<std::mutex> g(own->img_mu);
-    if (own->img8_off || own->img_off || own->n == 0 || !i8_wanted(own->opt) || own->dim < 8) return OTT_OK;
-    const uint32_t ld8 = (own->dim + 127u) & ~127u;
-    if (!own->d_img8) {
-        const size_t bytes = (size_t)own->cap * ld8;
-        size_t free_b = 0, total_b = 0;
-        if (own->opt.no_batch_image || own->opt.no_hi_pass || hipMemGetInfo(&free_b, &total_b) != hipSuccess ||
-            free_b < bytes + (size_t)own->cap * 4 + (size_t)(2ull << 30) || hipMalloc((void**)&own->d_img8, bytes) != hipSuccess) {
-            own->d_img8 = nullptr;
-            own->img8_off = true;  // does not fit (or switched off): the cascade starts at the hi pass
-            (void)hipGetLastError();
-            return OTT_OK;
-        }
-        if (hipMalloc((void**)&own->d_img8_scale, (size_t)own->cap * 4) != hipSuccess) {
-            (void)hipFree(own->d_img8);
-            own->d_img8 = nullptr;
-            own->d_img8_scale = nullptr;
-            own->img8_off = true;
-            (void)hipGetLastError();
-            return OTT_OK;
-        }
-        own->img8_rows = 0;
-    }
-    if (!own->d_img8_rel) {
-        OTT_HIP(hipMalloc((void**)&own->d_img8_rel, 16));
-        OTT_HIP(hipMemsetAsync(own->d_img8_rel, 0, 16, ctx->stream));
-    }
-    if (own->img8_rows == 0) OTT_HIP(hipMemsetAsync(own->d_img8_rel, 0, 16, ctx->stream));
-    if (own->img8_rows < own->n) {
-        const bool from_scratch = own->img8_rows == 0;
-        const uint64_t first = own->img8_rows, cnt = own->n - first;
-        int rc = launch_i8_rows(ctx->stream, own->d_rows, own->ld, own->dim, ld8, first, cnt, own->d_img8, nullptr, 0.0f, own->d_img8_scale, nullptr,
-                                own->d_img8_rel, own->d_flag, I8_REL_FLAG, own->d_flag, own->n_cu);
-        if (rc) return rc;
-        uint32_t bits[2] = {0, 0};
-        OTT_HIP(hipMemcpyAsync(bits, own->d_img8_rel, 8, hipMemcpyDeviceToHost, ctx->stream));
-        OTT_HIP(hipStreamSynchronize(ctx->stream));  // published below: other contexts' streams may read it at once
-        if (from_scratch && (uint64_t)bits[1] * 64 > cnt) {
-            // more than 1 row in 64 does not suit int8 (heavy-tailed elements): the wrong format for this store.  The marks are
-            // taken back, the plane is freed and the cascade starts at the hi pass
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((own->n + 255) / 256, (uint64_t)own->n_cu * 8);
-            hipLaunchKernelGGL(clear_flag_bit_kernel, dim3(grid), dim3(256), 0, ctx->stream, own->d_flag, own->n, (uint8_t)0xFB);
-            OTT_HIP(hipGetLastError());
-            OTT_HIP(hipStreamSynchronize(ctx->stream));
-            (void)hipFree(own->d_img8);
-            (void)hipFree(own->d_img8_scale);
-            own->d_img8 = nullptr;
-            own->d_img8_scale = nullptr;
-            own->img8_off = true;
-            return OTT_OK;
-        }
-        memcpy(&own->img8_rel, &bits[0], 4);
-        own->img8_rows = own->n;
-    }
-    *img_out = own->d_img8;
-    *scale_out = own->d_img8_scale;
-    *rel_max_out = own->img8_rel;
-    return OTT_OK;
-}
-
-int ensure_first_plane(ott_store* ctx) {
-    ott_store* own = ctx->owner ? ctx->owner : ctx;
-    float rel = 0.f;
-    if (i8_wanted(own->opt)) {
-        const int8_t* i8 = nullptr;
-        const float* i8s = nullptr;
-        const int rc = ensure_i8_plane(ctx, &i8, &i8s, &rel);
-        if (rc) return rc;
-        bool have_hi;
-        {
-            std::lock_guard<std::mutex> g(own->img_mu);
-            have_hi = own->d_imgh != nullptr;
-        }
-        if (i8 && !have_hi) return OTT_OK;  // the hi plane is built when a query first needs it
-    }
-    const uint16_t* img = nullptr;
-    return ensure_hi_plane(ctx, &img, &rel);
-}
-
-PlaneSnapshot plane_snapshot(const ott_store* s) {
-    ott_store* own = const_cast<ott_store*>(s->owner ? s->owner : s);
-    std::lock_guard<std::mutex> g(own->img_mu);
-    return PlaneSnapshot{own->d_img8 != nullptr, own->img8_off, own->d_imgh != nullptr, own->imgh_f16, own->imgh_off, own->img_off,
-                         own->img8_rows, own->imgh_rows};
-}
-
-bool first_plane_ready(ott_store* ctx) {
-    ott_store* own = ctx->owner ? ctx->owner : ctx;
-    bool i8_on;
-    {
-        std::lock_guard<std::mutex> g(own->img_mu);
-        i8_on = i8_wanted(own->opt) && !own->img8_off && own->dim >= 8;
-    }
-    return i8_on ? i8_plane_ready(ctx) : hi_plane_ready(ctx);
-}
-
-bool i8_plane_ready(ott_store* ctx) {
-    ott_store* own = ctx->owner ? ctx->owner : ctx;
-    std::lock_guard<std::mutex> g(own->img_mu);
-    return own->d_img8 != nullptr && !own->img8_off && !own->img_off && own->n != 0 && own->img8_rows == own->n;
-}
-
 // the store's own context when it is free, else a worker context that aliases the corpus (ott::host::ContextPool)
 ott_store* ctx_acquire(ott_store* s) {
     return s->pool.acquire(
@@ -1280,51 +747,6 @@ ott_store* ctx_acquire(ott_store* s) {
 }
 
 void ctx_release(ott_store* w) { (w->owner ? w->owner : w)->pool.release(w); }
-
-}  // namespace ott
-
-// The hi plane off the first batch's critical path (round 4).  A first 256-query batch on a fresh 10M x 768 store took 19 ms:
-// 15 of them the allocation and conversion of the 16-bit plane.  With option hi_prebuild (automatic for stores of 262144 rows
-// and more) every append ends by waking this thread, which takes the store like a query does (shared), converts the rows that
-// are new (~10 ms per 30 GB, on a context of its own) and goes back to sleep; a batch that arrives while it is at work waits for
-// it on the plane's mutex exactly as it would have built the plane itself.  Results never depend on it.
-namespace ott {
-
-// one run of the background builder (ott::host::QuietWorker calls it once the appends have been quiet for 20 ms: a store loaded
-// in pieces is not converted piece by piece — each conversion holds the store shared, i.e. the next append waits for it, and a
-// growing store's reallocation drops the plane again: a 30-GB load in 100k-row pieces went from 2.4 to 4.0 s without the wait)
-static void plane_builder_run(ott_store* s) {
-    ott::host::SharedLock rd(s->rw);
-    if (use_device(s) != hipSuccess) return;
-    if (s->opt.hi_prebuild < 0) {  // automatic: only while the plane is a modest share of what is free
-        size_t free_b = 0, total_b = 0;
-        const PlaneSnapshot ps = plane_snapshot(s);
-        const bool i8 = i8_wanted(s->opt) && !ps.i8_off;
-        const size_t bytes = i8 ? (size_t)s->cap * ((s->dim + 127u) & ~127u) : (size_t)s->cap * ((s->dim + 63u) & ~63u) * 2;
-        if (!(i8 ? ps.have_i8 : ps.have_hi) && (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4)) return;
-    }
-    ott_store* ctx = ctx_acquire(s);
-    mfma_warm(ctx->stream, s->device);  // the batch path's kernels onto the device first: the first batch of a process paid 10-15 ms for that
-    (void)ensure_first_plane(ctx);  // (a failure leaves the plane to the first batch, as before)
-    ctx_release(ctx);
-    (void)hipGetLastError();
-}
-
-void kick_plane_build(ott_store* s) {
-    if (s->is_worker || s->multi) return;
-    const int pol = s->opt.hi_prebuild;
-    const PlaneSnapshot ps = plane_snapshot(s);
-    if (pol == 0 || s->opt.no_hi_pass || s->opt.no_batch_image || s->opt.mfma_f32 || ps.hi_off || ps.img_off) return;
-    if (pol < 0 && s->n < 262144) return;
-    if (s->dim < 8) return;
-    {
-        const bool i8 = i8_wanted(s->opt) && !ps.i8_off;
-        const bool i8_stale = i8 && ps.i8_rows < s->n, hi_stale = (!i8 || ps.have_hi) && ps.hi_rows < s->n;
-        if (!i8_stale && !hi_stale) return;
-    }
-    if (!s->builder) s->builder = new ott::host::QuietWorker([s] { plane_builder_run(s); }, std::chrono::milliseconds(20));
-    s->builder->kick();
-}
 
 }  // namespace ott
 
@@ -1409,14 +831,7 @@ int ott_store_destroy(ott_store* s) {
     if (s->d_inv) (void)hipFree(s->d_inv);
     if (s->d_flag) (void)hipFree(s->d_flag);
     if (s->d_sketch) (void)hipFree(s->d_sketch);
-    if (s->d_img && !s->is_worker) (void)hipFree(s->d_img);
-    if (s->d_imgh && !s->is_worker) (void)hipFree(s->d_imgh);
-    if (s->d_imgh_rel && !s->is_worker) (void)hipFree(s->d_imgh_rel);
-    if (!s->is_worker) {
-        if (s->d_img8) (void)hipFree(s->d_img8);
-        if (s->d_img8_scale) (void)hipFree(s->d_img8_scale);
-        if (s->d_img8_rel) (void)hipFree(s->d_img8_rel);
-    }
+    planes_release(s);  // (a worker has none of its own)
     for (ott::DevBuf* b : {&s->d_queries, &s->d_qinv, &s->d_rowmask, &s->d_runs, &s->d_prefix, &s->d_lists, &s->d_lists2, &s->d_hits,
                            &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_gather, &s->d_gtable, &s->d_gctl, &s->d_mstable, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
                            &s->m_tau, &s->m_cntA, &s->m_cntB, &s->m_candA, &s->m_candB, &s->m_over, &s->m_out, &s->m_outcnt,
@@ -1564,30 +979,8 @@ int ott_store_set_batch_image(ott_store* s, int enabled) {
     if (!s) return fail(OTT_ERR_INVALID, "ott_store_set_batch_image: store is NULL");
     if (s->multi) return multi_set_batch_image(s, enabled);
     ott::host::ExclusiveLock wr(s->rw);  // no query is running on any context
-    std::lock_guard<std::mutex> g(s->img_mu);
-    if (!enabled && s->d_img) {
-        OTT_HIP(use_device(s));
-        (void)hipFree(s->d_img);
-        s->d_img = nullptr;
-        s->img_rows = s->img_cap = 0;
-    }
-    if (!enabled && s->d_imgh) {
-        OTT_HIP(use_device(s));
-        (void)hipFree(s->d_imgh);
-        s->d_imgh = nullptr;
-        s->imgh_rows = 0;
-    }
-    if (!enabled && s->d_img8) {
-        OTT_HIP(use_device(s));
-        (void)hipFree(s->d_img8);
-        if (s->d_img8_scale) (void)hipFree(s->d_img8_scale);
-        s->d_img8 = nullptr;
-        s->d_img8_scale = nullptr;
-        s->img8_rows = 0;
-    }
-    if (enabled) s->img8_off = false;
-    s->img_off = !enabled;
-    if (enabled) s->imgh_off = false;
+    if (!enabled && planes_any(s)) OTT_HIP(use_device(s));
+    planes_enable(s, enabled != 0);
     return OTT_OK;
 }
 
@@ -1595,13 +988,9 @@ int ott_store_set_option(ott_store* s, const char* name, int64_t value) {
     if (!s || !name) return fail(OTT_ERR_INVALID, "ott_store_set_option: NULL argument");
     if (s->multi) return multi_set_option(s, name, value);
     ott::host::ExclusiveLock wr(s->rw);  // no query is running on any context
-    std::lock_guard<std::mutex> g(s->img_mu);
     Options o = s->opt;
     if (option_set(o, name, (long long)value)) return fail(OTT_ERR_INVALID, std::string("ott_store_set_option: unknown option or bad value: ") + name);
-    // a copy of the corpus that was declined because of an option can be built again once the option allows it
-    if (s->opt.no_hi_pass && !o.no_hi_pass) s->imgh_off = false;
-    if (s->opt.no_batch_image && !o.no_batch_image) s->imgh_off = s->img_off = s->img8_off = false;
-    s->opt = o;
+    planes_set_options(s, o);
     return OTT_OK;
 }
 
@@ -1645,33 +1034,7 @@ int ott_store_write_rows(ott_store* s, uint64_t first_row, const float* rows_hos
                              (size_t)s->dim * 4, n_rows, hipMemcpyHostToDevice, s->stream));
     int rc = launch_inv_norms(s, first_row, n_rows);
     if (rc) return rc;
-    if (s->d_img && first_row < s->img_rows) {  // keep the batch image in step with the rewritten rows
-        const uint64_t cnt = (first_row + n_rows <= s->img_rows ? first_row + n_rows : s->img_rows) - first_row;
-        const uint32_t ldi = (s->dim + 31u) & ~31u;
-        const uint64_t work = cnt * (ldi / 4);
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((work + 255) / 256, (uint64_t)s->n_cu * 16);
-        hipLaunchKernelGGL(split_rows_kernel, dim3(grid), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, ldi, first_row, cnt, s->d_img, nullptr);
-        OTT_HIP(hipGetLastError());
-    }
-    if (s->d_imgh && first_row < s->imgh_rows) {  // and the hi plane (its measured rounding loss can only grow)
-        const uint64_t cnt = (first_row + n_rows <= s->imgh_rows ? first_row + n_rows : s->imgh_rows) - first_row;
-        int rch = launch_store_hi_rows(s, s->stream, first_row, cnt);
-        if (rch) return rch;
-        uint32_t bits = 0;
-        OTT_HIP(hipMemcpyAsync(&bits, s->d_imgh_rel, 4, hipMemcpyDeviceToHost, s->stream));
-        OTT_HIP(hipStreamSynchronize(s->stream));
-        memcpy(&s->imgh_rel, &bits, 4);
-    }
-    if (s->d_img8 && first_row < s->img8_rows) {  // and the int8 plane (its measured loss can only grow; marks of rewritten rows are re-taken)
-        const uint64_t cnt = (first_row + n_rows <= s->img8_rows ? first_row + n_rows : s->img8_rows) - first_row;
-        int rch = launch_i8_rows(s->stream, s->d_rows, s->ld, s->dim, (s->dim + 127u) & ~127u, first_row, cnt, s->d_img8, nullptr, 0.0f, s->d_img8_scale,
-                                 nullptr, s->d_img8_rel, s->d_flag, I8_REL_FLAG, s->d_flag, s->n_cu);
-        if (rch) return rch;
-        uint32_t bits = 0;
-        OTT_HIP(hipMemcpyAsync(&bits, s->d_img8_rel, 4, hipMemcpyDeviceToHost, s->stream));
-        OTT_HIP(hipStreamSynchronize(s->stream));
-        memcpy(&s->img8_rel, &bits, 4);
-    }
+    if ((rc = planes_rewrite(s, first_row, n_rows))) return rc;
     return update_min_pos_inv(s, first_row, n_rows);
 }
 

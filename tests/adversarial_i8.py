@@ -63,7 +63,7 @@ def exact_scores(rows, q, metric):
 
 
 def i8_plane(rows):
-    """the plane as i8_rows_kernel builds it (ott_store.hip): s_v = max|v| / 127, element = rint(v * (1 / s_v)); and the measured
+    """the plane as i8_rows_kernel builds it (ott_planes.hip): s_v = max|v| / 127, element = rint(v * (1 / s_v)); and the measured
     relative loss per row"""
     mx = np.abs(rows).max(axis=1).astype(f32)
     s = (mx / f32(127)).astype(f32)
