@@ -676,7 +676,7 @@ struct Cascade {
         // f32 bytes, one v_mfma_i32_32x32x32_i8 per 32 k, exact integer accumulation — its bound is the measured quantisation loss
         // alone (~8e-3 relative on uniform 768-d rows), so it re-scores 512 candidates per query and certifies where fewer than
         // 512 - k rows lie that close to the k-th score; what it leaves open goes to the hi pass.  Same back-off as the hi pass.
-        bool i8_pass = hi_pass && i8_wanted(s->opt) && k_q <= 128;
+        bool i8_pass = hi_pass && i8_wanted(s->opt) && k_q <= I8_K_MAX;
         if (i8_pass) {
             const int8_t* i8 = nullptr;
             const float* i8s = nullptr;

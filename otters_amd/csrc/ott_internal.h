@@ -17,6 +17,7 @@
 #include "ott_host.h"  // the host-side concurrency (thread pool, context pool, staged appends, background worker): HIP-free, sanitizer-tested
 #include "ott_policy.h"  // path choice and the batch cascade's back-off rules: HIP-free, CPU-tested
 #include "ott_plane_policy.h"  // the two format decisions of the cascade's planes: HIP-free, CPU-tested
+#include "ott_mfma_plan.h"  // the batch path's host-side plan (tile geometry, candidate budget, error bound, query norms, query block): HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
 #include "ott_audit.h"  // test build: every HIP call below goes through a device-affinity check (see "which GPU a call is for")
 #endif
@@ -588,9 +589,10 @@ int upload_exact_inputs(ott_store* s, const float* queries, uint32_t nq, const R
 
 // MFMA batch path: per-query exact top-k lists on the host; uncertified[q] != 0 means the
 // list for q could not be certified and must be recomputed on the exact path.
-// level 0 = hi pass (bf16 hi plane, one MFMA per 16 k; needs mfma_hi_ok), level 1 = split-bf16 / f32-pipe pass
+// level 0 = hi pass (16-bit hi plane, one MFMA per 16 k; needs mfma_hi_k_ok), level 1 = split-bf16 / f32-pipe pass, level 2 = int8 pass.
+// How many candidates a level re-scores and the bound it certifies against: ott_mfma_plan.h (level_budget, error_model)
 int run_mfma(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t k_q, const uint64_t* d_mask, uint64_t mask_bits,
-             std::vector<std::vector<ott_hit>>& out, std::vector<uint32_t>& uncertified, ott_stats& st, int level, uint32_t t_min,  // t_min: re-score at least this many (0, 512, 4096)
+             std::vector<std::vector<ott_hit>>& out, std::vector<uint32_t>& uncertified, ott_stats& st, int level, uint32_t t_min,  // t_min: re-score at least this many (0, 512, 4096; ott_mfma_plan.h: level_budget)
              bool spec_gate);  // speculative emission thresholds between the row rounds (select_kernel); first level of a cascade only
 int launch_rand_fill(ott_store* s, uint64_t first_row, uint64_t n_rows, uint64_t seed);
 // ott_mfma.hip: the int8 level for ONE query as a streaming sweep (no matrix cores: the query is a vector) — exact_kernel<..., I8>

@@ -1060,19 +1060,6 @@ __device__ __forceinline__ void fl_offer(FList<E>& L, uint64_t& tk, uint32_t T, 
     }
 }
 
-// The int8 passes' accumulation constant for cosine / dot, in units of 2^-24 relative to ||q|| ||v||: a bound on
-// |approximate - EXACT-ORDER f32 score| beyond the measured quantisation losses.  Two sides:
-//  * the approximate score: the integer accumulation is exact; one i32 -> f32 conversion, the row factor's two multiplies and the
-//    score's one, the per-element rounding of the pre-scaled cosine operand: 16 units cover them;
-//  * the exact-order re-score it is compared with (src/vec_compute.rs:9-22) is NOT the real dot product: a lane chain is dim/8
-//    rounded products and rounded adds, then three adds of reduce_add, the remainder's chain (at most 7 + 1 adds) and cosine's two
-//    multiplies — |fl - real| <= gamma(dim/8 + 6) * sum|q_i v_i| <= (dim/8 + 16) units of ||q|| ||v|| (Higham, recursive summation;
-//    the 1 / (1 - n u) factor is inside the slack for every dim the store accepts).
-// Round 5 priced the first side only ("pure quantisation"): with int8-REPRESENTABLE rows and queries the measured losses are ~1e-7,
-// the bound collapsed to ~17 units, and nearly constant rows — whose lane sums drift by 30-150 units, every add rounding the same
-// way — were left outside a "certified" list (tests/adversarial_i8.py, tests/test_gpu_i8_bound.py, profiles/round6/i8_bound.md).
-static inline float i8_c_eps_units(uint32_t dim) { return 0.125f * (float)dim + 32.0f; }
-
 struct FinalParams {
     const float* rows;
     const float* inv;
@@ -1410,17 +1397,9 @@ __global__ __launch_bounds__(64 * FIN_WAVES) void finalize_kernel(FinalParams p)
 // ---------------------------------------------------------------------------------------------
 // host orchestration
 // ---------------------------------------------------------------------------------------------
-static float host_sqnorm(const float* v, uint32_t dim) {
-    double s = 0;
-    for (uint32_t i = 0; i < dim; i++) s += (double)v[i] * v[i];
-    return (float)s;
-}
-static float host_norm(const float* v, uint32_t dim) {
-    double s = 0;
-    for (uint32_t i = 0; i < dim; i++) s += (double)v[i] * v[i];
-    return (float)(sqrt(s) * (1.0 + 1e-6));
-}
-float host_inv_norm_exact(const float* v, uint32_t dim);  // ott_api.hip (reference order)
+// What is decided before anything is launched — tile geometry, candidate budget, error bound, query norms, the layout of the
+// query block — is ott_mfma_plan.h (HIP-free, CPU-tested); it restates three of this file's constants
+static_assert(MKC == (int)MFMA_K_STAGE && CNT_STRIDE == QB_CNT_STRIDE && sizeof(ott_run) == QB_RUN_BYTES, "ott_mfma_plan.h");
 
 static double host_ms() {
     timespec ts;
@@ -1428,165 +1407,153 @@ static double host_ms() {
     return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
 
+// results: finalize_kernel writes hits | counts | certification flags | error ratios straight into pinned host memory (no D2H
+// copies behind the launch: three copy enqueues were ~40 us of a small batch).  Byte offsets of the four parts
+struct ResultBlock {
+    size_t cnt, unc, err, total;
+    ResultBlock(uint32_t nq, uint32_t k) : cnt((size_t)nq * k * sizeof(ott_hit)), unc(cnt + (size_t)nq * 8), err(unc + (size_t)nq * 4), total(err + (size_t)nq * 4) {}
+};
+
+// mfma_debug: the in-kernel stamps of the last (largest) round, which ran with a grid of nwg workgroups, averaged per tile
+static int dump_tile_timing(ott_store* s, size_t nwg) {
+    std::vector<unsigned long long> h(nwg * 12);
+    OTT_HIP(hipMemcpyAsync(h.data(), s->d_misc.p, h.size() * 8, hipMemcpyDeviceToHost, s->stream));
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    double a = 0, b = 0, c = 0, t = 0;
+    double rt = 0;
+    for (size_t i = 0; i < nwg; i++) rt += h[nwg * 4 + i];
+    for (size_t i = 0; i < nwg; i++) { a += h[i * 4]; b += h[i * 4 + 1]; c += h[i * 4 + 2]; t += h[i * 4 + 3]; }
+    double wd = 0, wb = 0;
+    for (size_t i = 0; i < nwg; i++) { wd += h[nwg * 5 + i]; wb += h[nwg * 6 + i]; }
+    double e[5] = {0, 0, 0, 0, 0};
+    for (int j = 0; j < 5; j++)
+        for (size_t i = 0; i < nwg; i++) e[j] += h[nwg * (7 + j) + i];
+    if (t > 0) fprintf(stderr, "[ott mfma dbg] per tile (s_memtime ticks, wave 0): prologue %.0f  K-loop %.0f (of which waiting for its DMA %.0f, at the stage barrier %.0f)  epilogue %.0f (setup %.0f, walk %.0f, queue flush %.0f, drain of its stores %.0f; wave 0 listed something in %.0f %% of the tiles)  (tiles %.0f; ~%.0f MHz)\n", a / t, b / t, wd / t, wb / t, c / t, e[0] / t, e[1] / t, e[2] / t, e[3] / t, 100.0 * e[4] / t, t, rt > 0 ? (a + b + c) / rt * 100.0 : 0.0);
+    return OTT_OK;
+}
+
+// finalize_kernel's arguments, for both runners: the query block `qb` at the front of m_Q, the results into the pinned block at
+// `hh_dev` (laid out by `rb`); (cand, cnt): the lists it re-scores, `bud.cap` slots per query
+static FinalParams fill_final_params(ott_store* s, const ott_query_desc* d, int level, uint32_t nq, uint32_t k, const Budget& bud, uint32_t ldq,
+                                     const ErrorModel& em, float mx_norm, const QueryBlock& qb, char* hh_dev, const ResultBlock& rb,
+                                     const CandEntry* cand, const uint32_t* cnt) {
+    const char* dblk = (const char*)s->m_Q.p;
+    FinalParams f;
+    memset(&f, 0, sizeof(f));
+    f.rows = s->d_rows;
+    f.inv = s->d_inv;
+    f.Q = (const float*)(dblk + qb.qraw);  // == the operand block unless that holds something else (pre-scaled, split, 16-bit)
+    f.qinv = (const float*)(dblk + qb.qinv);
+    f.tau = (const float*)(dblk + qb.tau);
+    f.gate = (const float*)(dblk + qb.gate);
+    f.cnt = cnt;
+    f.cand = cand;
+    f.overflow = (const uint32_t*)(dblk + qb.over);
+    f.out = (ott_hit*)hh_dev;
+    f.out_cnt = (uint64_t*)(hh_dev + rb.cnt);
+    f.uncertified = (uint32_t*)(hh_dev + rb.unc);
+    f.base_offset = s->base_offset;
+    f.cap = bud.cap;
+    f.ld = s->ld;
+    f.dim = s->dim;
+    f.ldq = ldq;
+    f.nq = nq;
+    f.k = k;
+    f.T = bud.T;
+    f.out_stride = k;  // only the k exact hits travel back
+    f.metric = d->metric;
+    f.take_max = d->take == OTT_TAKE_MAX;
+    f.cmp = d->filter_cmp;
+    f.reduce = s->reduce;
+    f.thr = d->filter_thr;
+    f.eps_c = em.eps_c;
+    f.max_norm = mx_norm;
+    f.qnorm = (const float*)(dblk + qb.qnorm);
+    f.qrel = level_is_hi(level) ? (const float*)(dblk + qb.qrel) : nullptr;
+    f.qrel_cap = em.qrel_cap;
+    f.eps_r = em.eps_r;
+    f.eps_scale = em.eps_scale;
+    f.err_ratio = (uint32_t*)(hh_dev + rb.err);
+    return f;
+}
+
+// (defined behind run_mfma: the kernels of this file are instantiated in the order the scoring rounds, then finalize, launch them)
+static int launch_finalize(hipStream_t stream, uint32_t nq, int E, bool wide, const FinalParams& f);
+
+// After the wait: the result block (h_hits) into per-query lists and flags, the level's stats.  qnorm: [nq], as the error model
+// saw them; the events ev[0..2] bracket the scoring and the finalize launches.
+static void unpack_results(ott_store* s, const ott_query_desc* d, const ResultBlock& rb, uint32_t k, uint32_t T, const float* qnorm, uint32_t passes,
+                           uint64_t rows_scored, std::vector<std::vector<ott_hit>>& out, std::vector<uint32_t>& uncertified, ott_stats& st) {
+    const char* hh = (const char*)s->h_hits.p;
+    const ott_hit* hits = (const ott_hit*)hh;
+    const uint64_t* cnts = (const uint64_t*)(hh + rb.cnt);
+    const uint32_t* unc = (const uint32_t*)(hh + rb.unc);
+    const uint32_t nq = d->nq;
+    out.assign(nq, {});
+    uncertified.assign(nq, 0);
+    for (uint32_t q = 0; q < nq; q++) {
+        out[q].assign(hits + (size_t)q * k, hits + (size_t)q * k + cnts[q]);
+        uncertified[q] = (unc[q] || !query_regular(qnorm[q])) ? 1u : 0u;
+        if (unc[q] == 2u) st.gate_failed++;  // would have been certified but for its speculative gate
+        float er;
+        memcpy(&er, hh + rb.err + (size_t)q * 4, 4);
+        if (er > st.err_ratio_max) st.err_ratio_max = er;
+        // The certification checks itself: eps is a bound on |approximate - exact|, and every re-scored candidate MEASURES that
+        // difference.  A ratio above 1 is a violated bound (the matrix unit's accumulation is not documented; the model behind
+        // eps is this library's): whatever the kernel concluded from it is void — the query goes to the next level of the
+        // cascade like any uncertified one, and finally to the exact-order kernel (src/vec_compute.rs:9-54).
+        if (er > 1.0f) {
+            st.bound_violations++;
+            uncertified[q] = 1u;
+        }
+    }
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) st.score_ns = (uint64_t)(ms * 1e6);
+    if (hipEventElapsedTime(&ms, s->ev[1], s->ev[2]) == hipSuccess) st.merge_ns = (uint64_t)(ms * 1e6);
+    st.path_used = OTT_PATH_MFMA;
+    st.passes = passes;
+    st.rescored = (uint64_t)nq * T;
+    st.bytes_scanned = (uint64_t)passes * rows_scored * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));
+}
+
+// A batch at one level of the cascade.  The stages, in order: planes -> plan (ott_mfma_plan.h) -> stage and upload the query block
+// -> convert the operands -> pick the kernel -> rounds -> finalize -> unpack.  The stages in the middle are used once and read
+// most of what the plan produced, so they are blocks of this function; what the sweep below shares are the functions above.
 int run_mfma(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t k_q, const uint64_t* d_mask, uint64_t mask_bits,
              std::vector<std::vector<ott_hit>>& out, std::vector<uint32_t>& uncertified, ott_stats& st, int level, uint32_t t_min, bool spec_gate) {
     const double hm0 = host_ms();
-    const uint32_t nq = d->nq;
-    const bool i8 = level == 2;  // int8 pass (round 5): rows and queries as scaled int8, from the store's int8 plane; cosine / dot
-    const bool hi = level == 0 || i8;  // hi pass: 16-bit roundings only, from the store's hi plane (the int8 pass shares its tile geometry and its measured bound)
-    // tile width: 16 or 32 queries (micro / narrow variants, 4-deep ring), 64, 128 or 256 (the micro tile is f32 only)
-    const int NB = (nq <= 16 && !hi) ? -1 : nq <= 32 ? 0 : nq <= 64 ? 1 : nq <= 128 ? 2 : 4;
-    const uint32_t BN = NB == -1 ? 16u : NB == 0 ? 32u : 64u * NB;
-    const uint32_t nq_pad = (nq + BN - 1) / BN * BN;
-    // query blocks per launch (mfma_score_kernel): the 256-wide tile takes up to 4 blocks of one row tile back to back
-    const uint32_t qblk_max = NB == 4 ? std::min<uint32_t>(4u, nq_pad / BN) : 1u;
-    const size_t MFMA_SMEM = (size_t)mfma_nbuf(NB) * (A_FLOATS + BN * MKC) * 4 + BM * 8 + (size_t)BN * 8 * qblk_max + (size_t)8 * mfma_qw(NB) * 8 + 16 + (i8 ? BM * 4 : 0);
-    // split-bf16 candidate pass (three bf16 MFMAs per 16 k) on every 32x32 tile; OTT_MFMA_F32=1 keeps the f32 matrix pipe
-    const bool bf3 = hi || (NB >= 0 && !s->opt.mfma_f32);
-    uint32_t wg_per_cu = 1;  // (narrow tiles ran two workgroups of a 2-deep ring per CU until the ring went 4 deep)
-    if (s->opt.mfma_wg > 0) wg_per_cu = (uint32_t)s->opt.mfma_wg;  // store option (experiments)
-    const uint32_t ldq = (s->dim + MKC - 1) / MKC * MKC;
-    const uint32_t ldh = i8 ? ((s->dim + 127u) & ~127u) / 2 : (s->dim + 63u) & ~63u;  // hi pass: operand rows are ldh 16-bit units = ldh / 2 four-byte units (int8: ld8 bytes)
+    int rc;
+    const uint32_t nq = d->nq, k = (uint32_t)k_q, metric = d->metric;
+    const bool i8 = level_is_i8(level), hi = level_is_hi(level);
+    const bool cosine = metric == OTT_METRIC_COSINE, tmax = d->take == OTT_TAKE_MAX;
+
+    // ---- planes: the one this level streams, and what was measured when it was built -----------------------------------------
     const uint16_t* hi_img = nullptr;
     float hi_rel = 0.0f, hi_scale = 1.0f;
     bool hi_f16 = false;  // the plane (and therefore the query operands) are IEEE half, pre-scaled by powers of two
     const float* i8_scale = nullptr;
     if (i8) {
         const int8_t* img8 = nullptr;
-        int rch = ensure_i8_plane(s, &img8, &i8_scale, &hi_rel);
-        if (rch) return rch;
+        if ((rc = ensure_i8_plane(s, &img8, &i8_scale, &hi_rel))) return rc;
         if (!img8) return fail(OTT_ERR_UNSUPPORTED, "run_mfma: the int8 plane is unavailable");
         hi_img = (const uint16_t*)img8;
     } else if (hi) {
-        int rch = ensure_hi_plane(s, &hi_img, &hi_rel, &hi_f16, &hi_scale);
-        if (rch) return rch;
+        if ((rc = ensure_hi_plane(s, &hi_img, &hi_rel, &hi_f16, &hi_scale))) return rc;
         if (!hi_img) return fail(OTT_ERR_UNSUPPORTED, "run_mfma: the hi plane is unavailable");
     }
-    const bool cosine = d->metric == OTT_METRIC_COSINE;
-    const bool tmax = d->take == OTT_TAKE_MAX;
-    const uint32_t k = (uint32_t)k_q;
-    // T = re-scored candidates per query: k plus slack, a multiple of 64.  The hi pass's bound is ~100x wider, so it needs
-    // every row within it of the k-th score among the re-scored: at least 2k + 56
-    int E = 1;
-    // (t_min: the split pass as a later level of the cascade sees the queries whose k-th score sits in a dense neighbourhood —
-    // that is why the pass before failed them — so it re-scores more: 512 as the second level, 4096 as the third)
-    // (round 3: the hi pass re-scores `t_min` = 512 per query once it has failed a store's queries at 2k + 56 (ott_api.hip,
-    //  hi_t512) — what certifies clustered corpora in ONE pass: 20 000 clusters of ~500 near neighbours each, 256 queries,
-    //  top-100: 10.5 ms with every query through the split pass -> 4.9 ms; on uniform rows it would cost ~0.15 ms of wall per batch)
-    const uint32_t hi_floor = t_min;
-    // (int8: a bound ~15x the half plane's — every row within ~8e-3 of the k-th score must be among the re-scored: 512)
-    // (the int8 pass: about 2.7 k rows of a uniform 768-d corpus lie within its bound of the k-th score — 4k + 88 re-scored, at most 512;
-    //  a store whose queries fail at that is asked for 512 from then on, t_min)
-    const uint32_t t_want = i8 ? (t_min > 4u * k + 88u ? t_min : (4u * k + 88u < 512u ? 4u * k + 88u : 512u)) : hi ? (hi_floor > 2u * k + 56u ? hi_floor : 2u * k + 56u) : (t_min > k + 28u ? t_min : k + 28u);
-    while (64u * E < (t_want < 512u ? t_want : 512u) && E < 8) E *= 2;
-    const bool wide = !hi && t_min > 512u;  // T = 4096: lists of 64K entries, finalize sorts 4096 candidates in LDS
-    const uint32_t T = wide ? 4096u : 64u * E;
-    if (wide) {  // E now only sizes the exact top-k list
-        E = 1;
-        while (64u * E < k && E < 8) E *= 2;
-    }
-    if (k > T || k > 512u) return fail(OTT_ERR_UNSUPPORTED, "run_mfma: k too large for the batch path");
-    const uint32_t cap_max = wide ? 65536u : 16384u;  // a round leaves ~8 T survivors per query
-    uint32_t cap = cap_max;
-    {   // small stores: the list can hold every row, no need for all the slots
-        uint64_t want = pl.rows_scored + 64;
-        uint32_t c2 = 1024;
-        while (c2 < want && c2 < cap_max) c2 <<= 1;
-        cap = c2;
-    }
+
+    // ---- plan (ott_mfma_plan.h) ------------------------------------------------------------------------------------------------
+    const TileGeometry g = tile_geometry(nq, level, s->dim);
+    const uint32_t BN = g.BN, nq_pad = g.nq_pad, ldq = g.ldq;
+    // split-bf16 candidate pass (three bf16 MFMAs per 16 k) on every 32x32 tile; OTT_MFMA_F32=1 keeps the f32 matrix pipe
+    const bool bf3 = hi || (g.NB >= 0 && !s->opt.mfma_f32);
+    const Budget bud = level_budget(level, k, t_min, pl.rows_scored, false);
+    if (bud.k_too_large) return fail(OTT_ERR_UNSUPPORTED, "run_mfma: k too large for the batch path");
     const std::vector<uint32_t> prefix = tile_prefix(pl, BM);
     const uint32_t n_tiles = prefix.back();
-
-    // ---- error bound on |approx - exact| (see DESIGN.md "MFMA path: certification") -----------
-    const float u = 5.9604645e-8f;  // 2^-24
-    // f32 pipe: recursive-summation bounds of both orders.  Split bf16: three products per element are accumulated (3*dim
-    // terms), and each element's product loses at most 3 * 2^-16 (1 + 2^-8) of |q_i v_i| to the dropped lo*lo / residual terms
-    // Hi pass: |q~.v~ - q.v| = |q~.(v~ - v) + (q~ - q).v| <= ||q~|| ||v~ - v|| + ||q~ - q|| ||v|| with both rounding losses MEASURED
-    // (rows: hi_rel, max over the store's regular rows; queries: per query, added in finalize_kernel), plus the accumulation terms.
-    // what the relaxed filter below assumes of any query: the format's worst-case relative rounding loss (bf16 RNE 2^-8, half 2^-11)
-    // int8: the queries share ONE scale per batch, so a query's loss depends on its largest element against the batch's; what the
-    // relaxed filter assumes of any certified query is a measured loss of at most 2^-6 (uniform 768-d queries measure 4e-3)
-    const float fmt_u = i8 ? 0.015625f : hi_f16 ? 4.8828125e-4f : 0.00390625f;
-    const float qrel_cap = 1.01f * fmt_u;
-    // test-only option eps_scale_ppm: every term of the bound shrunk on purpose, to show that a VIOLATED bound is noticed (the
-    // measured |approximate - exact| / eps of the re-scored candidates exceeds 1) and the query falls through to the next level
-    const float esc = s->opt.eps_scale_ppm == 1000000 ? 1.0f : (float)s->opt.eps_scale_ppm * 1e-6f;
-    const float c_eps = esc * (i8    ? (d->metric == OTT_METRIC_EUCLIDEAN ? (2.0f * (float)s->dim + 32.0f) * u  // (||v||^2 from the stored inverse norm: see below)
-                                                                          : i8_c_eps_units(s->dim) * u)
-                               : hi  ? (2.5f * (float)s->dim + 32.0f) * u
-                               : bf3 ? (3.75f * (float)s->dim + 32.0f) * u + 3.03f * 1.52587890625e-5f
-                                     : ((d->metric == OTT_METRIC_EUCLIDEAN ? 2.0f : 1.25f) * (float)s->dim + 32.0f) * u);
-    // (squared L2 on the f32 pipe: besides the two summation orders, ||v||^2 comes from the stored inverse norm, whose
-    //  sequential f32 sum carries up to dim * 2^-24 of relative error itself)
-    const float eps_r = hi ? esc * (1.001f * (1.0f + fmt_u) * hi_rel) : 0.0f;  // rows' share of the hi pass's rounding loss (||q~|| <= (1 + u) ||q||)
-    const float r_max = hi ? eps_r + esc * (1.001f * qrel_cap) : 0.0f;         // + the most any certified query adds
-    const uint32_t metric = d->metric;
+    const ErrorModel em = error_model(level, hi_f16, s->dim, metric, bf3, s->opt.eps_scale_ppm, hi_rel);
     std::vector<float> qnorm(nq_pad, 0.f), qinv(nq_pad, 0.f), qamax(i8 ? nq : 0, 0.f);
-    float qn_max = 0.f;
-    // Norms of EIGHT queries at a time: the reference-order inverse norm is one dependent float add chain per query
-    // (src/vec.rs:387-397: sequential sum of squares, separate multiply and add — this file is built with -ffp-contract=off,
-    // and the baseline x86-64 target has no fused multiply-add anyway), so eight independent chains keep the host core busy.
-    // The UPPER BOUND on ||q|| the error model needs comes from that same float sum with its worst-case error as margin
-    // (relative error of a sequential f32 sum of non-negative terms <= dim * 2^-24; of its root, half that); the f64 sum is
-    // taken only where it is needed: squared L2 (||q||^2 rides in the qinv slot) and queries whose float norm is outside
-    // [1e-15, 1e18] (squares underflowing or overflowing in f32: zero, tiny, huge, non-finite — the irregular ones).
-    // 1024 queries x 768 (a C4 shard's batch): the whole host prepare phase in front of the first launch 0.32-0.49 -> 0.18-0.24 ms
-    // (diagnostic build's host timers, benchmarks/hostprof.py); 256 queries 0.10 -> 0.06 ms.
-    {
-        constexpr uint32_t G = 8;
-        const bool need_f64 = metric == OTT_METRIC_EUCLIDEAN;
-        const uint32_t dim = s->dim;
-        for (uint32_t i0 = 0; i0 < nq; i0 += G) {
-            const uint32_t g = nq - i0 < G ? nq - i0 : G;
-            const float* v[G];
-            float fs[G];
-            double ds[G];
-            for (uint32_t a = 0; a < G; a++) {
-                v[a] = d->queries + (size_t)(i0 + (a < g ? a : 0)) * dim;
-                fs[a] = 0.0f;
-                ds[a] = 0.0;
-            }
-            if (need_f64) {
-                for (uint32_t j = 0; j < dim; j++)
-                    for (uint32_t a = 0; a < G; a++) {
-                        const float x = v[a][j];
-                        const float sq = x * x;
-                        fs[a] = fs[a] + sq;
-                        ds[a] += (double)x * x;
-                    }
-            } else {
-                for (uint32_t j = 0; j < dim; j++)
-                    for (uint32_t a = 0; a < G; a++) {
-                        const float x = v[a][j];
-                        const float sq = x * x;
-                        fs[a] = fs[a] + sq;
-                    }
-            }
-            if (i8)  // the largest element of every query: the batch's ONE quantisation scale comes from them
-                for (uint32_t a = 0; a < g; a++) {
-                    float m = 0.0f;
-                    for (uint32_t j = 0; j < dim; j++) m = fmaxf(m, fabsf(v[a][j]));
-                    qamax[i0 + a] = m;
-                }
-            for (uint32_t a = 0; a < g; a++) {
-                const uint32_t i = i0 + a;
-                const float nrm = sqrtf(fs[a]);
-                double nd;
-                if (need_f64) nd = sqrt(ds[a]);
-                else if (nrm >= 1e-15f && nrm <= 1e18f) nd = (double)nrm * (1.0 + (double)dim * 5.9604644775390625e-8);
-                else {
-                    double t = 0.0;
-                    for (uint32_t j = 0; j < dim; j++) t += (double)v[a][j] * (double)v[a][j];
-                    nd = sqrt(t);
-                    ds[a] = t;
-                }
-                qnorm[i] = (float)(nd * (1.0 + 1e-6));
-                if (metric == OTT_METRIC_EUCLIDEAN) qinv[i] = (float)ds[a];  // ||q||^2 rides in the qinv slot
-                else qinv[i] = nrm != 0.0f ? 1.0f / nrm : 0.0f;
-                if (qnorm[i] > qn_max) qn_max = qnorm[i];
-            }
-        }
-    }
+    const float qn_max = query_norms(d->queries, nq, s->dim, metric, i8, qnorm.data(), qinv.data(), qamax.data());
     // Half plane, dot / squared L2: the operands are the RAW queries times the reciprocal of the plane's factor (below); when
     // that product is far outside half's range (query norms x sqrt(row norms) beyond ~10^5 per element: vectors with norms
     // in the tens of thousands) every operand would overflow and the pass could certify nothing — it is skipped outright
@@ -1602,58 +1569,33 @@ int run_mfma(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t 
         st.bytes_scanned = 0;
         return OTT_OK;
     }
-    const float max_norm = s->min_pos_inv < __builtin_inff() ? (1.0f / s->min_pos_inv) * 1.000001f : 0.0f;
-    float eps_max;
-    if (cosine) eps_max = c_eps + r_max;
-    else if (metric == OTT_METRIC_DOT) eps_max = (c_eps + r_max) * max_norm * qn_max;
-    else eps_max = c_eps * (qn_max + max_norm) * (qn_max + max_norm) + 2.0f * r_max * qn_max * max_norm;
+    const float mx_norm = max_norm(s->min_pos_inv);
+    const float eps_max = em.eps_max(metric, qn_max, mx_norm);
     if (!(eps_max < __builtin_inff())) return fail(OTT_ERR_UNSUPPORTED, "run_mfma: non-finite error bound");
-    float flo = -__builtin_inff(), fhi = __builtin_inff();
-    switch (d->filter_cmp) {
-        case OTT_CMP_GT: case OTT_CMP_GTE: flo = d->filter_thr - eps_max; break;
-        case OTT_CMP_LT: case OTT_CMP_LTE: fhi = d->filter_thr + eps_max; break;
-        case OTT_CMP_EQ: flo = d->filter_thr - eps_max; fhi = d->filter_thr + eps_max; break;
-        default: break;
-    }
-
-    // ---- buffers ------------------------------------------------------------------------------
-    int rc;
-    // ONE input block, staged in pinned memory and uploaded with one copy: Q (zero padded) | qinv | qnorm | tau |
-    // cntA | cntB | overflow (zeros) | runs | tile prefix.  (Six copies and three memsets were ~50 us of blit kernels
-    // in front of every batch.)
-    const size_t q_bytes = (size_t)nq_pad * ldq * 4;
-    const size_t off_qinv = q_bytes, off_qnorm = off_qinv + (size_t)nq_pad * 4, off_tau = off_qnorm + (size_t)nq_pad * 4;
-    const size_t off_cntA = (off_tau + (size_t)nq_pad * 4 + 127) & ~(size_t)127, off_cntB = off_cntA + (size_t)nq_pad * CNT_STRIDE * 4;
-    const size_t off_over = off_cntB + (size_t)nq_pad * CNT_STRIDE * 4;
-    const size_t off_qrel = off_over + (size_t)nq_pad * 4;  // hi pass: measured rounding loss of each operand row
-    const size_t off_gate = off_qrel + (size_t)nq_pad * 4;  // emission threshold of the scoring rounds (select_kernel)
-    const size_t off_runs = (off_gate + (size_t)nq_pad * 4 + 15) & ~(size_t)15;
-    const size_t off_prefix = off_runs + pl.runs.size() * sizeof(ott_run);
+    const FilterInterval fi = relaxed_filter(d->filter_cmp, d->filter_thr, eps_max);
     // cosine: the MFMA operand is the query pre-scaled by 1/||q|| (one multiply less per accumulator in the epilogue; the
     // extra rounding, one ulp per element, is inside the error bound's slack); the exact re-score needs the raw query
     const bool own_operand = cosine || bf3;
-    const size_t off_qraw = own_operand ? ((off_prefix + prefix.size() * 4 + 127) & ~(size_t)127) : 0;
-    const size_t tot = own_operand ? off_qraw + q_bytes : off_prefix + prefix.size() * 4;
-    if ((rc = s->m_Q.ensure(tot))) return rc;
-    if ((rc = s->m_candA.ensure((size_t)nq_pad * cap * sizeof(CandEntry)))) return rc;
-    if ((rc = s->m_candB.ensure((size_t)nq_pad * cap * sizeof(CandEntry)))) return rc;
-    // results: finalize_kernel writes hits | counts | certification flags straight into pinned host memory (no D2H copies
-    // behind the launch: three copy enqueues were ~40 us of a small batch)
-    const size_t hb = (size_t)nq * k * sizeof(ott_hit), cb = (size_t)nq * 8, ub = (size_t)nq * 4;
-    if ((rc = s->h_hits.ensure(hb + cb + 2 * ub))) return rc;  // hits | counts | certification flags | error ratios
-    char* hh = (char*)s->h_hits.p;
+    const QueryBlock qb = query_block(nq_pad, ldq, pl.runs.size(), prefix.size(), own_operand);
+    const ResultBlock rb(nq, k);
+
+    // ---- buffers; the query block staged in pinned memory and uploaded with one copy -----------------------------------------
+    if ((rc = s->m_Q.ensure(qb.total))) return rc;
+    if ((rc = s->m_candA.ensure((size_t)nq_pad * bud.cap * sizeof(CandEntry)))) return rc;
+    if ((rc = s->m_candB.ensure((size_t)nq_pad * bud.cap * sizeof(CandEntry)))) return rc;
+    if ((rc = s->h_hits.ensure(rb.total))) return rc;
     char* hh_dev = nullptr;
-    OTT_HIP(hipHostGetDevicePointer((void**)&hh_dev, hh, 0));
-    if ((rc = s->h_stage.ensure(tot))) return rc;
+    OTT_HIP(hipHostGetDevicePointer((void**)&hh_dev, s->h_hits.p, 0));
+    if ((rc = s->h_stage.ensure(qb.total))) return rc;
     char* hs = (char*)s->h_stage.p;
     // bf3: the operand region [0, q_bytes) is produced on the GPU (padded query rows included), so it is neither cleared nor
     // uploaded; everything behind it is
-    const size_t up0 = bf3 ? q_bytes : 0;
-    memset(hs + up0, 0, tot - up0);
+    const size_t up0 = bf3 ? qb.q_bytes : 0;
+    memset(hs + up0, 0, qb.total - up0);
     float* hQ = (float*)hs;
     for (uint32_t i = 0; i < nq; i++) {
         const float* src = d->queries + (size_t)i * s->dim;
-        if (own_operand) memcpy(hs + off_qraw + (size_t)i * ldq * 4, src, (size_t)s->dim * 4);
+        if (own_operand) memcpy(hs + qb.qraw + (size_t)i * ldq * 4, src, (size_t)s->dim * 4);
         if (bf3) {
             // the operand block ([32 hi | 32 lo] bf16 per 32-k stage, pre-scaled by 1/||q|| for cosine) is produced on the GPU
             // from the raw queries below: at 1024 queries the host loop was 4 ms
@@ -1663,28 +1605,23 @@ int run_mfma(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t 
             memcpy(hQ + (size_t)i * ldq, src, (size_t)s->dim * 4);
         }
     }
-    float* hqinv = (float*)(hs + off_qinv);
-    float* hqnorm = (float*)(hs + off_qnorm);
-    float* htau = (float*)(hs + off_tau);
+    memcpy(hs + qb.qinv, qinv.data(), (size_t)nq_pad * 4);
+    memcpy(hs + qb.qnorm, qnorm.data(), (size_t)nq_pad * 4);
+    float* htau = (float*)(hs + qb.tau);
     for (uint32_t i = 0; i < nq_pad; i++) {
-        hqinv[i] = qinv[i];
-        hqnorm[i] = qnorm[i];
-        // padded queries never emit; real ones start fully open.  A query with a non-finite or astronomically
-        // large norm is outside the error model: it is excluded here (NaN threshold = empty interval) and answered
-        // by the exact path
-        const bool irregular_q = i < nq && !(qnorm[i] <= 1e18f && (qnorm[i] == 0.0f || qnorm[i] >= 1e-18f));
-        htau[i] = (i < nq && !irregular_q) ? (tmax ? -__builtin_inff() : __builtin_inff()) : __builtin_nanf("");
-        ((float*)(hs + off_gate))[i] = htau[i];
+        // padded queries never emit; real ones start fully open.  A query outside the error model (query_regular) is excluded
+        // here (NaN threshold = empty interval) and answered by the exact path
+        htau[i] = (i < nq && query_regular(qnorm[i])) ? (tmax ? -__builtin_inff() : __builtin_inff()) : __builtin_nanf("");
+        ((float*)(hs + qb.gate))[i] = htau[i];
     }
-    memcpy(hs + off_runs, pl.runs.data(), pl.runs.size() * sizeof(ott_run));
-    memcpy(hs + off_prefix, prefix.data(), prefix.size() * 4);
-    OTT_HIP(hipMemcpyAsync((char*)s->m_Q.p + up0, hs + up0, tot - up0, hipMemcpyHostToDevice, s->stream));
+    memcpy(hs + qb.runs, pl.runs.data(), pl.runs.size() * sizeof(ott_run));
+    memcpy(hs + qb.prefix, prefix.data(), prefix.size() * 4);
+    OTT_HIP(hipMemcpyAsync((char*)s->m_Q.p + up0, hs + up0, qb.total - up0, hipMemcpyHostToDevice, s->stream));
     char* dblk = (char*)s->m_Q.p;
-    // half operands: the queries are multiplied by the RECIPROCAL of the plane's power-of-two factor, so the accumulators hold
-    // the plain dot products (nothing to undo in the epilogue).  The plane's factor is 2^-round(log2(largest regular norm) / 4)
-    // (ensure_hi_plane: the compromise between unit-length cosine operands and raw dot / L2 operands); a query whose operand
-    // leaves half's range measures a large rounding loss (or overflows: loss 1) and is not certified here
-    const float q_scale = (hi && hi_f16) ? 1.0f / hi_scale : 1.0f;
+
+    // ---- the level's operands, converted on the GPU from the uploaded raw queries into the front of the block ------------------
+    const float* d_raw = (const float*)(dblk + qb.qraw);
+    const float* d_pre = cosine ? (const float*)(dblk + qb.qinv) : nullptr;
     float i8_qscale = 1.0f;
     if (i8) {
         // ONE quantisation scale for the batch's operands (cosine: the unit-length queries): the largest element any of them has,
@@ -1696,69 +1633,60 @@ int run_mfma(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t 
             if (e == e && e < __builtin_inff() && e > m) m = e;
         }
         i8_qscale = m > 0.0f ? m / 127.0f : 1.0f;
-        if ((rc = launch_i8_rows(s->stream, (const float*)(dblk + off_qraw), ldq, s->dim, ldh * 2, 0, nq_pad, (int8_t*)dblk,
-                                 cosine ? (const float*)(dblk + off_qinv) : nullptr, i8_qscale, nullptr, (float*)(dblk + off_qrel), nullptr, nullptr, 2.0f,
-                                 nullptr, s->n_cu)))
+        if ((rc = launch_i8_rows(s->stream, d_raw, ldq, s->dim, g.ldh * 2, 0, nq_pad, (int8_t*)dblk, d_pre, i8_qscale, nullptr, (float*)(dblk + qb.qrel),
+                                 nullptr, nullptr, 2.0f, nullptr, s->n_cu)))
             return rc;
     } else if (hi) {
-        if ((rc = launch_hi_rows(s->stream, (const float*)(dblk + off_qraw), ldq, s->dim, ldh, nq_pad, (uint16_t*)dblk,
-                                 cosine ? (const float*)(dblk + off_qinv) : nullptr, (float*)(dblk + off_qrel), s->n_cu, hi_f16, q_scale)))
+        // half operands: the queries are multiplied by the RECIPROCAL of the plane's power-of-two factor, so the accumulators hold
+        // the plain dot products (nothing to undo in the epilogue).  The plane's factor is 2^-round(log2(largest regular norm) / 4)
+        // (ensure_hi_plane: the compromise between unit-length cosine operands and raw dot / L2 operands); a query whose operand
+        // leaves half's range measures a large rounding loss (or overflows: loss 1) and is not certified here
+        const float q_scale = hi_f16 ? 1.0f / hi_scale : 1.0f;
+        if ((rc = launch_hi_rows(s->stream, d_raw, ldq, s->dim, g.ldh, nq_pad, (uint16_t*)dblk, d_pre, (float*)(dblk + qb.qrel), s->n_cu, hi_f16, q_scale)))
             return rc;
-    } else if (bf3 && (rc = launch_split_rows(s->stream, (const float*)(dblk + off_qraw), ldq, s->dim, ldq, nq_pad, (uint16_t*)dblk,
-                                              cosine ? (const float*)(dblk + off_qinv) : nullptr, s->n_cu)))
+    } else if (bf3 && (rc = launch_split_rows(s->stream, d_raw, ldq, s->dim, ldq, nq_pad, (uint16_t*)dblk, d_pre, s->n_cu)))
         return rc;  // rows nq .. nq_pad of the raw block are zero, so are their operand rows
-    float* d_qinv = (float*)(dblk + off_qinv);
-    float* d_qnorm = (float*)(dblk + off_qnorm);
-    float* d_tau = (float*)(dblk + off_tau);
-    float* d_gate = (float*)(dblk + off_gate);
-    uint32_t* d_cntA = (uint32_t*)(dblk + off_cntA);
-    uint32_t* d_cntB = (uint32_t*)(dblk + off_cntB);
-    uint32_t* d_over = (uint32_t*)(dblk + off_over);
+    float* d_tau = (float*)(dblk + qb.tau);
+    float* d_gate = (float*)(dblk + qb.gate);
+    uint32_t* d_over = (uint32_t*)(dblk + qb.over);
 
+    // ---- the scoring kernel and its arguments ---------------------------------------------------------------------------------
     MfmaParams p;
     memset(&p, 0, sizeof(p));
     p.rows = s->d_rows;
     p.inv = s->d_inv;
     p.flag = s->d_flag;
+    p.img = hi_img;
     // operand mode of the candidate pass: 0 = f32 matrix pipe, 1 = split bf16 with the rows split in registers, 2 = split
-    // bf16 from the store's pre-split batch image (built / extended here on first use; mode 1 when it does not fit)
+    // bf16 from the store's pre-split batch image (built / extended here on first use; mode 1 when it does not fit),
+    // 3 / 4 = bf16 / half hi plane, 5 = int8 plane
     int bf3mode = 0;
     if (i8) {
         bf3mode = 5;
-        p.img = hi_img;
         p.i8_scale = i8_scale;
         p.i8_qscale = i8_qscale;
     } else if (hi) {
         bf3mode = hi_f16 ? 4 : 3;
-        p.img = hi_img;
     } else if (bf3) {
-        const uint16_t* img = nullptr;
-        if ((rc = ensure_batch_image(s, &img))) return rc;
-        bf3mode = img ? 2 : 1;
-        p.img = img;
+        if ((rc = ensure_batch_image(s, &p.img))) return rc;
+        bf3mode = p.img ? 2 : 1;
     }
-    p.Q = (const float*)s->m_Q.p;
-    p.qinv = d_qinv;
+    p.Q = (const float*)dblk;
+    p.qinv = (const float*)(dblk + qb.qinv);
     p.tau = d_gate;  // the scoring rounds emit against the gate (== tau unless speculative)
-    p.runs = (const ott_run*)(dblk + off_runs);
-    p.tile_prefix = (const uint32_t*)(dblk + off_prefix);
+    p.runs = (const ott_run*)(dblk + qb.runs);
+    p.tile_prefix = (const uint32_t*)(dblk + qb.prefix);
     p.row_mask = d_mask;
     p.row_mask_bits = mask_bits;
-    p.cap = cap;
+    p.cap = bud.cap;
     p.ld = s->ld;
     p.dim = s->dim;
-    p.ldq = hi ? ldh / 2 : ldq;
+    p.ldq = hi ? g.ldh / 2 : ldq;
     p.n_runs = (uint32_t)pl.runs.size();
     p.metric = metric;
     p.take_max = tmax;
-    p.flo = flo;
-    p.fhi = fhi;
-
-    uint32_t* cnt_cur = d_cntA;
-    uint32_t* cnt_oth = d_cntB;
-    CandEntry* cand_cur = (CandEntry*)s->m_candA.p;
-    CandEntry* cand_oth = (CandEntry*)s->m_candB.p;
-
+    p.flo = fi.flo;
+    p.fhi = fi.fhi;
     // mfma_debug option: in-kernel s_memtime stamps (never quote such a run's time).  The stamped kernel variants exist only
     // in a library built with -DOTT_MFMA_DEBUG_BUILD (make EXTRA=-DOTT_MFMA_DEBUG_BUILD); the shipped one carries none.
 #ifdef OTT_MFMA_DEBUG_BUILD
@@ -1770,7 +1698,7 @@ int run_mfma(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t 
 #define OTT_KERN(NBv, BFv) (mfma_score_kernel<NBv, false, BFv>)
 #endif
     void (*kern)(MfmaParams) = nullptr;
-    switch (NB) {
+    switch (g.NB) {
         case -1: kern = OTT_KERN(-1, 0); break;
 #define OTT_PICK(NBv) kern = bf3mode == 5 ? OTT_KERN(NBv, 5) : bf3mode == 4 ? OTT_KERN(NBv, 4) : bf3mode == 3 ? OTT_KERN(NBv, 3) : bf3mode == 2 ? OTT_KERN(NBv, 2) : bf3mode == 1 ? OTT_KERN(NBv, 1) : OTT_KERN(NBv, 0)
         case 0: OTT_PICK(0); break;
@@ -1780,25 +1708,33 @@ int run_mfma(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t 
 #undef OTT_PICK
 #undef OTT_KERN
     }
-    const uint32_t wg_slots = (uint32_t)s->n_cu * wg_per_cu;  // the persistent grid
-    const size_t smem_bytes = MFMA_SMEM;
+    const size_t smem = (size_t)mfma_nbuf(g.NB) * (A_FLOATS + BN * MKC) * 4 + BM * 8 + (size_t)BN * 8 * g.qblk_max + (size_t)8 * mfma_qw(g.NB) * 8 + 16 + (i8 ? BM * 4 : 0);
+    uint32_t wg_per_cu = 1;  // (narrow tiles ran two workgroups of a 2-deep ring per CU until the ring went 4 deep)
+    if (s->opt.mfma_wg > 0) wg_per_cu = (uint32_t)s->opt.mfma_wg;  // store option (experiments)
+    const uint32_t slots = (uint32_t)s->n_cu * wg_per_cu;  // the persistent grid: one workgroup per CU (more only through the mfma_wg option)
     {   // once per kernel variant and device (the attribute call is not free: it sat in front of every batch)
         static std::mutex attr_mu;
         static std::vector<std::pair<const void*, int>> attr_done;
-        std::lock_guard<std::mutex> g(attr_mu);
+        std::lock_guard<std::mutex> lk(attr_mu);
         const std::pair<const void*, int> key((const void*)kern, s->device);
         if (std::find(attr_done.begin(), attr_done.end(), key) == attr_done.end()) {
-            OTT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_bytes));
+            OTT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
             attr_done.push_back(key);
         }
     }
     if (dbg_on) {
-        if ((rc = s->d_misc.ensure((size_t)wg_slots * 14 * 8))) return rc;
-        OTT_HIP(hipMemsetAsync(s->d_misc.p, 0, (size_t)wg_slots * 14 * 8, s->stream));
+        if ((rc = s->d_misc.ensure((size_t)slots * 14 * 8))) return rc;
+        OTT_HIP(hipMemsetAsync(s->d_misc.p, 0, (size_t)slots * 14 * 8, s->stream));
         p.dbg = (unsigned long long*)s->d_misc.p;
-        p.dbg_wgs = wg_slots;
+        p.dbg_wgs = slots;
         p.dbg_abl = (uint32_t)s->opt.mfma_abl;
     }
+
+    // ---- rounds ---------------------------------------------------------------------------------------------------------------
+    uint32_t* cnt_cur = (uint32_t*)(dblk + qb.cntA);
+    uint32_t* cnt_oth = (uint32_t*)(dblk + qb.cntB);
+    CandEntry* cand_cur = (CandEntry*)s->m_candA.p;
+    CandEntry* cand_oth = (CandEntry*)s->m_candB.p;
     const double hm1 = host_ms();
     OTT_HIP(hipEventRecord(s->ev[0], s->stream));
     // geometric rounds: 32 tiles (8192 rows, thresholds open: every pair is listed), then x `growth` per round.  With
@@ -1809,36 +1745,35 @@ int run_mfma(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t 
         uint32_t end = begin + width;
         if (end > n_tiles || n_tiles - end < width) end = n_tiles;  // fold a short tail into this round
         const uint32_t tiles = end - begin;
-        const uint32_t slots = wg_slots;  // persistent workgroups: one per CU (more only through the mfma_wg option)
         const uint32_t grid = tiles < slots ? tiles : slots;
         // the first round lists every pair: with one slot per pair there is nothing to count
-        const bool dense = begin == 0 && (uint64_t)tiles * BM <= cap && !s->opt.mfma_no_dense;
+        const bool dense = begin == 0 && (uint64_t)tiles * BM <= bud.cap && !s->opt.mfma_no_dense;
         if (dense) OTT_HIP(hipMemsetD32Async((hipDeviceptr_t)cnt_cur, (int)(tiles * BM), (size_t)nq_pad * CNT_STRIDE, s->stream));
-        const uint32_t qstep = BN * qblk_max;
-        for (uint32_t qb = 0; qb < nq_pad; qb += qstep) {
+        const uint32_t qstep = BN * g.qblk_max;
+        for (uint32_t q0 = 0; q0 < nq_pad; q0 += qstep) {
             p.tile_begin = begin;
             p.tile_end = end;
-            p.q_base = qb;
-            p.n_qblk = std::min<uint32_t>(qblk_max, (nq_pad - qb) / BN);
+            p.q_base = q0;
+            p.n_qblk = std::min<uint32_t>(g.qblk_max, (nq_pad - q0) / BN);
             // 2 or 4 blocks and enough tiles to fill the persistent grid: the blocks of a tile on sibling workgroups of one XCD
             p.coop = (s->opt.mfma_coop != 0 && (p.n_qblk == 2 || p.n_qblk == 4) && grid == slots && slots % (8u * p.n_qblk) == 0 &&
                       (uint64_t)tiles * p.n_qblk >= slots) ? p.n_qblk : 0u;
             p.cnt = cnt_cur;
             p.cand = cand_cur;
             p.dense = dense ? 1u : 0u;
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem_bytes, s->stream, p);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, s->stream, p);
             OTT_HIP(hipGetLastError());
         }
         // speculative gate for the rounds that follow: the j-th best so far with j = 8 T x (share of the tiles seen), at least 8
         // — about 8 T rows of the whole store are expected above it; j >= T (an eighth of the store seen) = conservative
         uint32_t j_gate = 0;
         if (spec_gate && end < n_tiles) {
-            const uint64_t jj = (8ull * T * end + n_tiles - 1) / n_tiles;
+            const uint64_t jj = (8ull * bud.T * end + n_tiles - 1) / n_tiles;
             j_gate = jj < 8 ? 8u : (uint32_t)jj;
-            if (j_gate >= T) j_gate = 0;
+            if (j_gate >= bud.T) j_gate = 0;
         }
         hipLaunchKernelGGL(select_kernel, dim3(nq_pad), dim3(SEL_THREADS), 0, s->stream, cand_cur, cnt_cur, cand_oth, cnt_oth,
-                           d_tau, d_over, cap, T, tmax ? 1u : 0u, d_gate, j_gate);  // keep the T best: k + slack
+                           d_tau, d_over, bud.cap, bud.T, tmax ? 1u : 0u, d_gate, j_gate);  // keep the T best: k + slack
         OTT_HIP(hipGetLastError());
         std::swap(cnt_cur, cnt_oth);
         std::swap(cand_cur, cand_oth);
@@ -1847,114 +1782,36 @@ int run_mfma(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t 
         begin = end;
     }
     OTT_HIP(hipEventRecord(s->ev[1], s->stream));
-    if (dbg_on) {
-        const size_t nwg = wg_slots;  // the last (largest) round ran with this grid
-        std::vector<unsigned long long> h(nwg * 12);
-        OTT_HIP(hipMemcpyAsync(h.data(), s->d_misc.p, h.size() * 8, hipMemcpyDeviceToHost, s->stream));
-        OTT_HIP(hipStreamSynchronize(s->stream));
-        double a = 0, b = 0, c = 0, t = 0;
-        double rt = 0;
-        for (size_t i = 0; i < nwg; i++) rt += h[nwg * 4 + i];
-        for (size_t i = 0; i < nwg; i++) { a += h[i * 4]; b += h[i * 4 + 1]; c += h[i * 4 + 2]; t += h[i * 4 + 3]; }
-        double wd = 0, wb = 0;
-        for (size_t i = 0; i < nwg; i++) { wd += h[nwg * 5 + i]; wb += h[nwg * 6 + i]; }
-        double e[5] = {0, 0, 0, 0, 0};
-        for (int j = 0; j < 5; j++)
-            for (size_t i = 0; i < nwg; i++) e[j] += h[nwg * (7 + j) + i];
-        if (t > 0) fprintf(stderr, "[ott mfma dbg] per tile (s_memtime ticks, wave 0): prologue %.0f  K-loop %.0f (of which waiting for its DMA %.0f, at the stage barrier %.0f)  epilogue %.0f (setup %.0f, walk %.0f, queue flush %.0f, drain of its stores %.0f; wave 0 listed something in %.0f %% of the tiles)  (tiles %.0f; ~%.0f MHz)\n", a / t, b / t, wd / t, wb / t, c / t, e[0] / t, e[1] / t, e[2] / t, e[3] / t, 100.0 * e[4] / t, t, rt > 0 ? (a + b + c) / rt * 100.0 : 0.0);
-    }
+    if (dbg_on && (rc = dump_tile_timing(s, slots))) return rc;
 
-    FinalParams f;
-    memset(&f, 0, sizeof(f));
-    f.rows = s->d_rows;
-    f.inv = s->d_inv;
-    f.Q = (const float*)(dblk + off_qraw);  // == the operand block unless it was pre-scaled (cosine)
-    f.qinv = d_qinv;
-    f.tau = d_tau;
-    f.gate = d_gate;
-    f.cnt = cnt_cur;
-    f.cand = cand_cur;
-    f.overflow = d_over;
-    f.out = (ott_hit*)hh_dev;
-    f.out_cnt = (uint64_t*)(hh_dev + hb);
-    f.uncertified = (uint32_t*)(hh_dev + hb + cb);
-    f.base_offset = s->base_offset;
-    f.cap = cap;
-    f.ld = s->ld;
-    f.dim = s->dim;
-    f.ldq = ldq;
-    f.nq = nq;
-    f.k = k;
-    f.T = T;
-    f.out_stride = k;  // only the k exact hits travel back
-    f.metric = metric;
-    f.take_max = tmax;
-    f.cmp = d->filter_cmp;
-    f.reduce = s->reduce;
-    f.thr = d->filter_thr;
-    f.eps_c = c_eps;
-    f.max_norm = max_norm;
-    f.qnorm = d_qnorm;
-    f.qrel = hi ? (const float*)(dblk + off_qrel) : nullptr;
-    f.qrel_cap = hi ? qrel_cap : 0.0f;
-    f.eps_r = eps_r;
-    f.eps_scale = esc;
-    f.err_ratio = (uint32_t*)(hh_dev + hb + cb + ub);
-    if (wide) {
-        switch (E) {
-            case 1: hipLaunchKernelGGL((finalize_kernel<1, 4096>), dim3(nq), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-            case 2: hipLaunchKernelGGL((finalize_kernel<2, 4096>), dim3(nq), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-            case 4: hipLaunchKernelGGL((finalize_kernel<4, 4096>), dim3(nq), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-            default: hipLaunchKernelGGL((finalize_kernel<8, 4096>), dim3(nq), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-        }
-    } else {
-        switch (E) {
-            case 1: hipLaunchKernelGGL((finalize_kernel<1, 64>), dim3(nq), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-            case 2: hipLaunchKernelGGL((finalize_kernel<2, 128>), dim3(nq), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-            case 4: hipLaunchKernelGGL((finalize_kernel<4, 256>), dim3(nq), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-            default: hipLaunchKernelGGL((finalize_kernel<8, 512>), dim3(nq), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-        }
-    }
-    OTT_HIP(hipGetLastError());
+    // ---- finalize, results to host ----------------------------------------------------------------------------------------------
+    const FinalParams f = fill_final_params(s, d, level, nq, k, bud, ldq, em, mx_norm, qb, hh_dev, rb, cand_cur, cnt_cur);
+    if ((rc = launch_finalize(s->stream, nq, bud.E, bud.wide, f))) return rc;
     OTT_HIP(hipEventRecord(s->ev[2], s->stream));
-
-    // ---- results to host --------------------------------------------------------------------------
     const double hm2 = host_ms();
     OTT_HIP(hipStreamSynchronize(s->stream));
     const double hm3 = host_ms();
-    const ott_hit* hits = (const ott_hit*)hh;
-    const uint64_t* cnts = (const uint64_t*)(hh + hb);
-    const uint32_t* unc = (const uint32_t*)(hh + hb + cb);
-    out.assign(nq, {});
-    uncertified.assign(nq, 0);
-    uint64_t rescored = 0;
-    for (uint32_t q = 0; q < nq; q++) {
-        out[q].assign(hits + (size_t)q * k, hits + (size_t)q * k + cnts[q]);
-        uncertified[q] = (unc[q] || !(qnorm[q] <= 1e18f && (qnorm[q] == 0.0f || qnorm[q] >= 1e-18f))) ? 1u : 0u;
-        if (unc[q] == 2u) st.gate_failed++;  // would have been certified but for its speculative gate
-        {
-            float er;
-            memcpy(&er, hh + hb + cb + ub + (size_t)q * 4, 4);
-            if (er > st.err_ratio_max) st.err_ratio_max = er;
-            // The certification checks itself: eps is a bound on |approximate - exact|, and every re-scored candidate MEASURES that
-            // difference.  A ratio above 1 is a violated bound (the matrix unit's accumulation is not documented; the model behind
-            // eps is this library's): whatever the kernel concluded from it is void — the query goes to the next level of the
-            // cascade like any uncertified one, and finally to the exact-order kernel (src/vec_compute.rs:9-54).
-            if (er > 1.0f) {
-                st.bound_violations++;
-                uncertified[q] = 1u;
-            }
-        }
-        rescored += T;
-    }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) st.score_ns = (uint64_t)(ms * 1e6);
-    if (hipEventElapsedTime(&ms, s->ev[1], s->ev[2]) == hipSuccess) st.merge_ns = (uint64_t)(ms * 1e6);
-    st.path_used = OTT_PATH_MFMA;
-    st.passes = (nq_pad / BN + qblk_max - 1) / qblk_max;  // passes over the plane from HBM
-    st.rescored = rescored;
-    st.bytes_scanned = (uint64_t)st.passes * pl.rows_scored * ((uint64_t)s->dim * 4 + (cosine ? 4 : 0));
+    unpack_results(s, d, rb, k, bud.T, qnorm.data(), g.passes(), pl.rows_scored, out, uncertified, st);
     if (dbg_on) fprintf(stderr, "[ott mfma dbg] host ms: prepare %.3f  enqueue %.3f  wait %.3f  unpack %.3f\n", hm1 - hm0, hm2 - hm1, hm3 - hm2, host_ms() - hm3);
+    return OTT_OK;
+}
+
+
+// one workgroup per query; E sizes the exact list (k <= 64 E), the LDS arrays hold 64 E candidates or the wide level's 4096
+static int launch_finalize(hipStream_t stream, uint32_t nq, int E, bool wide, const FinalParams& f) {
+#define OTT_FIN(Ev, TCAPv) hipLaunchKernelGGL((finalize_kernel<Ev, TCAPv>), dim3(nq), dim3(64 * FIN_WAVES), 0, stream, f)
+    switch (wide ? -E : E) {
+        case -1: OTT_FIN(1, 4096); break;
+        case -2: OTT_FIN(2, 4096); break;
+        case -4: OTT_FIN(4, 4096); break;
+        case -8: OTT_FIN(8, 4096); break;
+        case 1: OTT_FIN(1, 64); break;
+        case 2: OTT_FIN(2, 128); break;
+        case 4: OTT_FIN(4, 256); break;
+        default: OTT_FIN(8, 512); break;
+    }
+#undef OTT_FIN
+    OTT_HIP(hipGetLastError());
     return OTT_OK;
 }
 
@@ -1995,26 +1852,22 @@ __global__ void i8_hits_to_cand_kernel(const ott_hit* hits, const uint64_t* coun
 int run_i8_single(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64_t k_q, const uint64_t* d_mask, uint64_t mask_bits,
                   std::vector<std::vector<ott_hit>>& out, std::vector<uint32_t>& uncertified, ott_stats& st, uint32_t t_min) {
     if (d->nq != 1 || d->metric == OTT_METRIC_EUCLIDEAN || d->filter_cmp == OTT_CMP_EQ) return fail(OTT_ERR_UNSUPPORTED, "run_i8_single: one query, cosine / dot, no equality filter");
+    constexpr int level = 2;
     const int8_t* img8 = nullptr;
     const float* i8_scale = nullptr;
     float i8_rel = 0.0f;
     int rc = ensure_i8_plane(s, &img8, &i8_scale, &i8_rel);
     if (rc) return rc;
     if (!img8) return fail(OTT_ERR_UNSUPPORTED, "run_i8_single: the int8 plane is unavailable");
-    const uint32_t dim = s->dim, ld8 = (dim + 127u) & ~127u, ldq = (dim + MKC - 1) / MKC * MKC;
+    const uint32_t dim = s->dim;
+    const TileGeometry g = tile_geometry(1, level, dim);
+    const uint32_t ld8 = g.ldh * 2;  // bytes of an int8 row
     if (ld8 > OTT_QEMB_MAX * 4) return fail(OTT_ERR_UNSUPPORTED, "run_i8_single: the query does not fit the kernel arguments");
     const bool cosine = d->metric == OTT_METRIC_COSINE, tmax = d->take == OTT_TAKE_MAX;
     const uint32_t k = (uint32_t)k_q;
-    // the list the sweep keeps: 128 candidates while k <= 24 (about 2.7 k rows of a uniform 768-d corpus lie within the bound of the
-    // k-th score), what the cascade's int8 level would re-score otherwise
-    uint32_t t_want = t_min > 128u ? t_min : (k <= 24u ? 128u : (4u * k + 88u < 512u ? 4u * k + 88u : 512u));
-    int E = 2;
-    while (64u * E < t_want && E < 8) E *= 2;
-    const uint32_t T = 64u * E;
-    if (k > T) return fail(OTT_ERR_UNSUPPORTED, "run_i8_single: k too large");
-    int Ek = 1;
-    while (64u * Ek < k && Ek < 8) Ek *= 2;  // (finalize's exact list; its LDS arrays are sized by T)
-    (void)Ek;
+    const Budget bud = level_budget(level, k, t_min, pl.rows_scored, true);
+    if (bud.k_too_large) return fail(OTT_ERR_UNSUPPORTED, "run_i8_single: k too large");
+    const uint32_t T = bud.T;  // (bud.E sizes the sweep's lists and finalize's, whose LDS arrays are sized by T)
 
     // ---- the query: norm, int8 operand, measured loss ---------------------------------------------------------------
     const float* q = d->queries;
@@ -2026,11 +1879,10 @@ int run_i8_single(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint
         amax = fmaxf(amax, fabsf(q[i]));
     }
     const float qnorm = (float)(sqrt(n2) * (1.0 + 1e-6));
-    const bool irregular_q = !(qnorm <= 1e18f && (qnorm == 0.0f || qnorm >= 1e-18f));
     out.assign(1, {});
     uncertified.assign(1, 1u);
     st.path_used = OTT_PATH_MFMA;
-    if (irregular_q) return OTT_OK;  // outside the error model: the next level / the exact path answers
+    if (!query_regular(qnorm)) return OTT_OK;  // outside the error model: the next level / the exact path answers
     const float pf = cosine ? q_inv : 1.0f;
     const float e_max = amax * pf;
     const float s_q = (e_max > 0.0f && e_max < __builtin_inff()) ? e_max / 127.0f : 1.0f;
@@ -2050,45 +1902,37 @@ int run_i8_single(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint
     float qrel = sx > 0.0 ? (float)(sqrt(se / sx) * 1.0001) : 0.0f;
     if (!(qrel <= 1.0f)) qrel = 1.0f;
 
-    // ---- error bound (as run_mfma's int8 level) -----------------------------------------------------------------------
-    const float u = 5.9604645e-8f;
-    const float esc = s->opt.eps_scale_ppm == 1000000 ? 1.0f : (float)s->opt.eps_scale_ppm * 1e-6f;
-    const float fmt_u = 0.015625f, qrel_cap = 1.01f * fmt_u;
-    const float c_eps = esc * i8_c_eps_units(dim) * u;  // both sides of |approximate - exact-order|: see i8_c_eps_units
-    const float eps_r = esc * (1.001f * (1.0f + fmt_u) * i8_rel);
-    const float r_max = eps_r + esc * (1.001f * qrel_cap);
-    const float max_norm = s->min_pos_inv < __builtin_inff() ? (1.0f / s->min_pos_inv) * 1.000001f : 0.0f;
-    const float eps_max = cosine ? c_eps + r_max : (c_eps + r_max) * max_norm * qnorm;
+    // ---- error bound: the int8 level's, as in run_mfma (both sides of |approximate - exact-order|: see i8_c_eps_units) ----------
+    const ErrorModel em = error_model(level, false, dim, d->metric, true, s->opt.eps_scale_ppm, i8_rel);
+    const float mx_norm = max_norm(s->min_pos_inv);
+    const float eps_max = em.eps_max(d->metric, qnorm, mx_norm);
     if (!(eps_max < __builtin_inff())) return fail(OTT_ERR_UNSUPPORTED, "run_i8_single: non-finite error bound");
+    const FilterInterval fi = relaxed_filter(d->filter_cmp, d->filter_thr, eps_max);
 
-    // ---- buffers: [raw query f32 (ldq) | qinv | qnorm | qrel | tau | gate | cnt (one line) | overflow] + candidates + lists ------
+    // ---- buffers: the query block with one row (the raw query in front) + the int8 operand behind it, candidates, lists ----------
     const std::vector<uint32_t> prefix = tile_prefix(pl, 64);
     const uint32_t n_tiles = prefix.back();
     const int grid = exact_grid(s, n_tiles);
-    const uint32_t KS = 64u * (uint32_t)E;
-    const size_t off_qinv = (size_t)ldq * 4, off_qnorm = off_qinv + 4, off_qrel = off_qnorm + 4, off_tau = off_qrel + 4, off_gate = off_tau + 4;
-    const size_t off_cnt = (off_gate + 4 + 127) & ~(size_t)127, off_over = off_cnt + CNT_STRIDE * 4, off_runs = (off_over + 4 + 15) & ~(size_t)15;
-    const size_t off_prefix = off_runs + pl.runs.size() * sizeof(ott_run), off_q8 = (off_prefix + prefix.size() * 4 + 15) & ~(size_t)15;
-    const size_t tot = off_q8 + ld8;
+    const QueryBlock qb = query_block(1, g.ldq, pl.runs.size(), prefix.size(), false);
+    const size_t off_q8 = (qb.total + 15) & ~(size_t)15, tot = off_q8 + ld8;
     if ((rc = s->m_Q.ensure(tot))) return rc;
     if ((rc = s->h_stage.ensure(tot))) return rc;
     if ((rc = s->m_candA.ensure((size_t)T * sizeof(CandEntry)))) return rc;
-    if ((rc = s->d_lists.ensure((size_t)grid * KS * sizeof(Cand)))) return rc;
+    if ((rc = s->d_lists.ensure((size_t)grid * T * sizeof(Cand)))) return rc;
     const size_t cnt_pad = 64;
-    if ((rc = s->d_hits.ensure(cnt_pad + (size_t)KS * sizeof(ott_hit)))) return rc;
-    const size_t hb = (size_t)k * sizeof(ott_hit), cb = 8, ub = 4;
-    if ((rc = s->h_hits.ensure(hb + cb + 2 * ub))) return rc;
-    char* hh = (char*)s->h_hits.p;
+    if ((rc = s->d_hits.ensure(cnt_pad + (size_t)T * sizeof(ott_hit)))) return rc;
+    const ResultBlock rb(1, k);
+    if ((rc = s->h_hits.ensure(rb.total))) return rc;
     char* hh_dev = nullptr;
-    OTT_HIP(hipHostGetDevicePointer((void**)&hh_dev, hh, 0));
+    OTT_HIP(hipHostGetDevicePointer((void**)&hh_dev, s->h_hits.p, 0));
     char* hs = (char*)s->h_stage.p;
     memset(hs, 0, tot);
     memcpy(hs, q, (size_t)dim * 4);
-    *(float*)(hs + off_qinv) = q_inv;
-    *(float*)(hs + off_qnorm) = qnorm;
-    *(float*)(hs + off_qrel) = qrel;
-    memcpy(hs + off_runs, pl.runs.data(), pl.runs.size() * sizeof(ott_run));
-    memcpy(hs + off_prefix, prefix.data(), prefix.size() * 4);
+    *(float*)(hs + qb.qinv) = q_inv;
+    *(float*)(hs + qb.qnorm) = qnorm;
+    *(float*)(hs + qb.qrel) = qrel;
+    memcpy(hs + qb.runs, pl.runs.data(), pl.runs.size() * sizeof(ott_run));
+    memcpy(hs + qb.prefix, prefix.data(), prefix.size() * 4);
     memcpy(hs + off_q8, q8, ld8);
     OTT_HIP(hipMemcpyAsync(s->m_Q.p, hs, tot, hipMemcpyHostToDevice, s->stream));
     char* dblk = (char*)s->m_Q.p;
@@ -2110,12 +1954,12 @@ int run_i8_single(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint
     // relaxed score filter on the approximate score: nothing that can pass exactly is dropped
     p.cmp = OTT_CMP_NONE;
     switch (d->filter_cmp) {
-        case OTT_CMP_GT: case OTT_CMP_GTE: p.cmp = OTT_CMP_GTE; p.thr = d->filter_thr - eps_max; break;
-        case OTT_CMP_LT: case OTT_CMP_LTE: p.cmp = OTT_CMP_LTE; p.thr = d->filter_thr + eps_max; break;
+        case OTT_CMP_GT: case OTT_CMP_GTE: p.cmp = OTT_CMP_GTE; p.thr = fi.flo; break;
+        case OTT_CMP_LT: case OTT_CMP_LTE: p.cmp = OTT_CMP_LTE; p.thr = fi.fhi; break;
         default: break;
     }
     p.k = T;
-    p.list_stride = KS;
+    p.list_stride = T;
     p.lists = (Cand*)s->d_lists.p;
     p.i8 = 1;
     p.i8_qscale = s_q;
@@ -2128,82 +1972,25 @@ int run_i8_single(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint
         for (size_t i = 0; i < prefix.size(); i++) p.eprefix[i] = prefix[i];
     } else {  // a chunk mask with many runs (config 3: every second chunk): run table, tile prefix and the int8 query from the uploaded block
         p.queries = (const float*)(dblk + off_q8);
-        p.qinv = (const float*)(dblk + off_qinv);
-        p.runs = (const ott_run*)(dblk + off_runs);
-        p.tile_prefix = (const uint32_t*)(dblk + off_prefix);
+        p.qinv = (const float*)(dblk + qb.qinv);
+        p.runs = (const ott_run*)(dblk + qb.runs);
+        p.tile_prefix = (const uint32_t*)(dblk + qb.prefix);
     }
     OTT_HIP(hipEventRecord(s->ev[0], s->stream));
-    if ((rc = launch_exact_i8(s, p, E, grid))) return rc;
+    if ((rc = launch_exact_i8(s, p, bud.E, grid))) return rc;
     ott_hit* d_hits = (ott_hit*)((char*)s->d_hits.p + cnt_pad);
     uint64_t* d_counts = (uint64_t*)s->d_hits.p;
-    if ((rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)grid, KS, 0, 1, T, E, tmax, 0, d_hits, KS, d_counts, 0))) return rc;
+    if ((rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)grid, T, 0, 1, T, bud.E, tmax, 0, d_hits, T, d_counts, 0))) return rc;
     OTT_HIP(hipEventRecord(s->ev[1], s->stream));
     hipLaunchKernelGGL(i8_hits_to_cand_kernel, dim3(1), dim3(256), 0, s->stream, (const ott_hit*)d_hits, (const uint64_t*)d_counts, T, tmax ? 1u : 0u,
-                       (CandEntry*)s->m_candA.p, (uint32_t*)(dblk + off_cnt), (float*)(dblk + off_tau), (float*)(dblk + off_gate), (uint32_t*)(dblk + off_over));
+                       (CandEntry*)s->m_candA.p, (uint32_t*)(dblk + qb.cntA), (float*)(dblk + qb.tau), (float*)(dblk + qb.gate), (uint32_t*)(dblk + qb.over));
     OTT_HIP(hipGetLastError());
 
-    FinalParams f;
-    memset(&f, 0, sizeof(f));
-    f.rows = s->d_rows;
-    f.inv = s->d_inv;
-    f.Q = (const float*)dblk;
-    f.qinv = (const float*)(dblk + off_qinv);
-    f.tau = (const float*)(dblk + off_tau);
-    f.gate = (const float*)(dblk + off_gate);
-    f.cnt = (const uint32_t*)(dblk + off_cnt);
-    f.cand = (const CandEntry*)s->m_candA.p;
-    f.overflow = (const uint32_t*)(dblk + off_over);
-    f.out = (ott_hit*)hh_dev;
-    f.out_cnt = (uint64_t*)(hh_dev + hb);
-    f.uncertified = (uint32_t*)(hh_dev + hb + cb);
-    f.base_offset = s->base_offset;
-    f.cap = T;
-    f.ld = s->ld;
-    f.dim = dim;
-    f.ldq = ldq;
-    f.nq = 1;
-    f.k = k;
-    f.T = T;
-    f.out_stride = k;
-    f.metric = d->metric;
-    f.take_max = tmax;
-    f.cmp = d->filter_cmp;
-    f.reduce = s->reduce;
-    f.thr = d->filter_thr;
-    f.eps_c = c_eps;
-    f.max_norm = max_norm;
-    f.qnorm = (const float*)(dblk + off_qnorm);
-    f.qrel = (const float*)(dblk + off_qrel);
-    f.qrel_cap = qrel_cap;
-    f.eps_r = eps_r;
-    f.eps_scale = esc;
-    f.err_ratio = (uint32_t*)(hh_dev + hb + cb + ub);
-    switch (E) {
-        case 2: hipLaunchKernelGGL((finalize_kernel<2, 128>), dim3(1), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-        case 4: hipLaunchKernelGGL((finalize_kernel<4, 256>), dim3(1), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-        default: hipLaunchKernelGGL((finalize_kernel<8, 512>), dim3(1), dim3(64 * FIN_WAVES), 0, s->stream, f); break;
-    }
-    OTT_HIP(hipGetLastError());
+    const FinalParams f = fill_final_params(s, d, level, 1, k, bud, g.ldq, em, mx_norm, qb, hh_dev, rb, (const CandEntry*)s->m_candA.p, (const uint32_t*)(dblk + qb.cntA));
+    if ((rc = launch_finalize(s->stream, 1, bud.E, false, f))) return rc;
     OTT_HIP(hipEventRecord(s->ev[2], s->stream));
     OTT_HIP(hipStreamSynchronize(s->stream));
-    const ott_hit* hits = (const ott_hit*)hh;
-    const uint64_t cnt0 = *(const uint64_t*)(hh + hb);
-    const uint32_t unc = *(const uint32_t*)(hh + hb + cb);
-    out[0].assign(hits, hits + cnt0);
-    uncertified[0] = unc ? 1u : 0u;
-    float er;
-    memcpy(&er, hh + hb + cb + ub, 4);
-    if (er > st.err_ratio_max) st.err_ratio_max = er;
-    if (er > 1.0f) {
-        st.bound_violations++;
-        uncertified[0] = 1u;
-    }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[0], s->ev[1]) == hipSuccess) st.score_ns = (uint64_t)(ms * 1e6);
-    if (hipEventElapsedTime(&ms, s->ev[1], s->ev[2]) == hipSuccess) st.merge_ns = (uint64_t)(ms * 1e6);
-    st.passes = 1;
-    st.rescored = T;
-    st.bytes_scanned = pl.rows_scored * ((uint64_t)dim * 4 + (cosine ? 4 : 0));
+    unpack_results(s, d, rb, k, T, &qnorm, 1, pl.rows_scored, out, uncertified, st);
     return OTT_OK;
 }
 

@@ -8,22 +8,20 @@
 #include <atomic>
 
 #include "../../include/otters_hip.h"
+#include "ott_mfma_plan.h"  // how many candidates each level of the batch path re-scores (mfma_hi_k_ok, t_want_*): the cost model and the back-off read it
 
 namespace ott {
 
-// the hi pass re-scores T >= 2k + 56 candidates per query (T <= 512); on a half plane, whose bound is ~8x tighter, k + k / 3 + 28
-// is enough (k <= 363 instead of 228: about 0.23 k rows lie within the bound of the k-th score on uniform rows)
-inline bool mfma_hi_k_ok(uint64_t k, bool half) { return half ? k + k / 3 + 28 <= 512 : 2 * k + 56 <= 512; }
 // the options ask for the int8 level in front of the hi pass
 inline bool i8_wanted(int hi_fmt, bool mfma_f32, bool no_hi_pass, bool no_batch_image) {
     return (hi_fmt == -1 || hi_fmt == 2) && !mfma_f32 && !no_hi_pass && !no_batch_image;
 }
 // ONE query at the int8 level may run as a streaming sweep with the top-128 in its epilogue (run_i8_single) instead of the
-// cascade's rounds: the sweep kernel scores cosine / dot, has no equality filter, and keeps a list of 128 entries (k <= 24: the
+// cascade's rounds: the sweep kernel scores cosine / dot, has no equality filter, and keeps a list of 128 entries (SWEEP_T, k <= SWEEP_K_MAX = 24: the
 // wave lists of 256 / 512 entries cost the sweep more than the rounds cost the cascade: top-100 at 10M x 768 1.97 ms against
 // 1.46).  `last`: the caller's own condition — the cost model's "the level is not widened", the cascade's "t_min <= 128".
 inline bool i8_single_sweep(uint32_t nq, uint64_t k_q, uint32_t filter_cmp, uint32_t metric, uint32_t dim, bool last) {
-    return nq == 1 && k_q <= 24 && filter_cmp != OTT_CMP_EQ && metric != OTT_METRIC_EUCLIDEAN && dim <= 3584 && last;
+    return nq == 1 && k_q <= SWEEP_K_MAX && filter_cmp != OTT_CMP_EQ && metric != OTT_METRIC_EUCLIDEAN && dim <= 3584 && last;
 }
 
 // ---- path choice ---------------------------------------------------------------------------------------------------------------
@@ -51,7 +49,7 @@ inline PathChoice choose_path(const PathIn& in, Planes&& planes, Ready&& first_p
     const uint32_t nq = in.nq;
     // per-query k for the batch path: the merged top-k is contained in the union of per-query top-k
     const uint64_t k_q = in.k < in.rows_scored ? in.k : in.rows_scored;
-    const bool mfma_ok = k_q + 28 <= 512 && in.dim >= 8;
+    const bool mfma_ok = t_want_split(k_q) <= MFMA_T_MAX && in.dim >= 8;
     if (in.flat) return PATH_CHOICE_EXACT;  // (the flat pass exists on the exact-order kernel only)
     if (in.metric == OTT_METRIC_MANHATTAN) return PATH_CHOICE_EXACT;  // EXACT only, decided before the cost model looks at the planes (their mutex)
     if (in.path == OTT_PATH_MFMA) return mfma_ok ? PATH_CHOICE_MFMA : PATH_CHOICE_REFUSED;
@@ -76,14 +74,15 @@ inline PathChoice choose_path(const PathIn& in, Planes&& planes, Ready&& first_p
     const bool plane_half = ps.have_hi ? ps.hi_f16 : in.hi_fmt != 0;
     const bool hi_ok = !f32pipe && mfma_hi_k_ok(k_q, plane_half) && !in.no_hi_pass;
     // round 5: the int8 plane in front (cosine / dot, k <= 128): a quarter of the bytes, twice the matrix rate, 512 candidates
-    const bool i8_ok = hi_ok && i8_wanted(in.hi_fmt, in.mfma_f32, in.no_hi_pass, in.no_batch_image) && !ps.i8_off && k_q <= 128;
+    const bool i8_ok = hi_ok && i8_wanted(in.hi_fmt, in.mfma_f32, in.no_hi_pass, in.no_batch_image) && !ps.i8_off && k_q <= I8_K_MAX;
     // the hi pass streams the 16-bit hi plane: half the bytes
     const double t_stream = (i8_ok ? 0.25 : hi_ok ? 0.5 : 1.0) * bytes * (double)((nq + 255) / 256) / (i8_ok ? 6.0e9 : hi_ok ? (nq <= 32 ? 6.5e9 : 6.2e9) : 5.9e9);  // (non-temporal row pieces, round 2: 6.6-6.8 TB/s up to 32 queries, ~6 at 64-128)
     // matrix pipe: ~125 TFLOP/s on the f32 pipe, ~330 TFLOP/s (f32-equivalent) with the split-bf16 operands, ~800 for the hi pass, ~1500 int8
     const double t_pipe = 2.0 * in.dim * (double)in.rows_scored * nq_pad / (i8_ok ? 1500e9 : hi_ok ? 800e9 : (bn >= 32 && !f32pipe) ? 330e9 : 125e9);
-    // (the candidates re-scored per query grow with k — 2k + 56 on the hi pass, in steps of 64; 512 on the int8 pass — and finalize /
+    // (the candidates re-scored per query grow with k — ott_mfma_plan.h: t_want_hi on the hi pass, in steps of 64; MFMA_T_MAX on the int8 pass — and finalize /
     //  select with them: top-100 costs the cascade 0.03-0.05 ms more than top-10 at one query, benchmarks/auto_choice.py)
-    const double t_cand = i8_ok ? 0.0003 * 384.0 : hi_ok && k_q > 36 ? 0.0003 * (double)((2 * k_q + 56 + 63) / 64 * 64 - 128) : 0.0;
+    const uint64_t t_hi64 = (t_want_hi(k_q) + 63) / 64 * 64;  // (above 128 from k = 37 on)
+    const double t_cand = i8_ok ? 0.0003 * (double)(MFMA_T_MAX - 128) : hi_ok && t_hi64 > 128 ? 0.0003 * (double)(t_hi64 - 128) : 0.0;
     double t_mfma = 0.16 + 0.0045 * nq + t_cand + (t_stream > t_pipe ? t_stream : t_pipe);
     // ONE query at the int8 level, k <= 24: a streaming sweep with the top-128 in its epilogue (run_i8_single): ~0.11 ms of
     // launches, merge and re-score around a quarter of the bytes at 6.5 TB/s (profiles/round5/auto_choice.md: 150k x 768 rows
@@ -148,7 +147,7 @@ struct CascadeState {
         const size_t genuine = open > gate_failed ? open - gate_failed : 0;
         const int ema = (3 * i8_fail_ema.load() + (genuine == 0 ? 0 : 1024)) / 4;
         i8_fail_ema.store(ema);
-        if (genuine * 8 > nq && !wide_now && 4 * k_q + 88 < 512) {
+        if (genuine * 8 > nq && !wide_now && t_want_i8(k_q) < MFMA_T_MAX) {
             i8_t512.store(64);  // first answer to dense neighbourhoods: re-score 512 per query for the next 64 calls
             i8_fail_ema.store(0);
         } else if (genuine * 8 > nq || (nq <= 512 && ema > (nq <= 128 ? 400 : 512))) back_off(i8_backoff, i8_skip, 4, 64);
@@ -158,7 +157,7 @@ struct CascadeState {
     // gate say nothing about the hi pass's error bound
     void after_hi(uint32_t nq, size_t open, uint32_t gate_failed, bool wide_now, uint32_t hi_t) {
         const size_t genuine = open > gate_failed ? open - gate_failed : 0;
-        if (genuine * 8 > nq && !wide_now && hi_t < 512u) {
+        if (genuine * 8 > nq && !wide_now && hi_t < MFMA_T_MAX) {
             // first answer to a store whose queries sit in dense neighbourhoods: keep the hi pass, re-score 512 per query
             // from the next batch on (this batch's open queries go to the split pass); only if THAT keeps failing does
             // the store back off from the hi pass

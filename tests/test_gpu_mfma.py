@@ -639,3 +639,71 @@ def test_int8_level_takes_squared_l2(oracle, monkeypatch):
     queries = rng.uniform(-1, 1, (33, dim)).astype(np.float32)
     rq, hits, _, stats = run(store.query(queries, Metric.Euclidean).take_min(12).with_path(Path.Mfma))
     assert_bit_exact(hits, oracle_collect(oracle, rq, rows, oracle.TIES_CANONICAL))
+
+
+# the first level of the batch cascade, selected as OPERAND_MODES does (here through the store's options)
+FIRST_LEVELS = {"split_pass_only": {"no_hi_pass": 1}, "bf16_hi_plane": {"hi_fmt": 0}, "half_hi_plane": {"hi_fmt": 1}, "int8_first": {"hi_fmt": 2}}
+
+
+def test_first_level_rescores_its_documented_budget(oracle):
+    """How many candidates a level of the batch path re-scores, and how often it streams its plane, pinned through the stats.  One
+    store of 4096 uniform rows x 72 dims; each level as the cascade's first; every tile width; k on both sides of every step of T.
+    On such rows the first level certifies every query (checked: nothing refined, re-run or failed by a gate), so `rescored` is
+    nq x that level's T, written out here from the documented formulas (ott_mfma_plan.h is not consulted):
+      split pass k + 28, hi pass 2k + 56, int8 level min(4k + 88, 512) — each rounded up to 64, 128, 256 or 512;
+      ONE query at the int8 level, k <= 24, cosine / dot: the streaming sweep, 128 candidates, one pass.
+    Tiles: 32, 64, 128 or 256 queries (16 on the split pass); the 256-wide tile takes up to 4 blocks per pass over the plane;
+    bytes_scanned = passes x rows x (4 dim, + 4 for cosine's inverse norm)."""
+    n, dim = 4096, 72
+    rng = np.random.default_rng(2024)
+    rows = rng.uniform(-1, 1, (n, dim)).astype(np.float32)
+    NQS, KS, METRICS = (1, 5, 33, 70, 130, 300), (1, 10, 24, 25, 100), (Metric.Cosine, Metric.DotProduct, Metric.Euclidean)
+    queries = rng.uniform(-1, 1, (max(NQS), dim)).astype(np.float32)
+    store = VecStore(dim)
+    store.add_vectors(rows)
+
+    def round_T(want):
+        T = 64
+        while T < min(want, 512):
+            T *= 2
+        return T
+
+    def expected(level, nq, k, metric):
+        """(T, passes)"""
+        if level == "int8_first" and nq == 1 and k <= 24 and metric != Metric.Euclidean:
+            return 128, 1
+        T = round_T({"split_pass_only": k + 28, "int8_first": min(4 * k + 88, 512)}.get(level, 2 * k + 56))
+        BN = 16 if (nq <= 16 and level == "split_pass_only") else 32 if nq <= 32 else 64 if nq <= 64 else 128 if nq <= 128 else 256
+        blocks = (nq + BN - 1) // BN
+        per_pass = min(4, blocks) if BN == 256 else 1
+        return T, (blocks + per_pass - 1) // per_pass
+
+    refs = {}  # (nq, k, metric) -> the oracle's hits: computed once, shared by the four levels
+    used = {}  # level -> err_ratio_max of every call: how much of its bound the level used
+    for level, opts in FIRST_LEVELS.items():
+        for name, v in opts.items():
+            store.set_option(name, v)
+        store.set_batch_image(False)  # the planes' formats are fixed when they are built: drop them, the next batch builds them anew
+        store.set_batch_image(True)
+        for nq, k, metric in ((a, b, c) for a in NQS for b in KS for c in METRICS):
+            rq, hits, _, st = run(store.query(queries[:nq], metric).take(k).with_path(Path.Mfma))
+            at = (level, nq, k, metric.name)
+            if (nq, k, metric) not in refs:
+                refs[(nq, k, metric)] = oracle_collect(oracle, rq, rows, oracle.TIES_CANONICAL)
+            assert_bit_exact(hits, refs[(nq, k, metric)])
+            assert st["path_used"] == 2, at
+            used.setdefault(level, []).append(st["err_ratio_max"])
+            # the precondition: the first level certified the whole batch
+            assert st["refined"] == st["i8_refined"] == st["retries"] == st["gate_failed"] == 0, (at, st)
+            T, passes = expected(level, nq, k, metric)
+            assert st["rescored"] == nq * T, (at, st["rescored"], T)
+            assert st["passes"] == passes, (at, st["passes"], passes)
+            assert st["bytes_scanned"] == passes * n * (dim * 4 + (4 if metric == Metric.Cosine else 0)), (at, st["bytes_scanned"])
+        for name in opts:
+            store.set_option(name, -1 if name == "hi_fmt" else 0)
+    # the bf16 and the half plane have the same budget, so nothing above tells them apart: what does is the share of its bound a
+    # level used (the measured |approximate - exact| over a bound built from the plane's own rounding loss).  Were `hi_fmt` ignored,
+    # the two lists would be equal bit for bit
+    assert used["bf16_hi_plane"] != used["half_hi_plane"] and used["half_hi_plane"] != used["int8_first"]
+    assert all(0.0 < e <= 1.0 for v in used.values() for e in v), used
+    store.close()
