@@ -18,6 +18,7 @@
 #include "ott_policy.h"  // path choice and the batch cascade's back-off rules: HIP-free, CPU-tested
 #include "ott_plane_policy.h"  // the two format decisions of the cascade's planes: HIP-free, CPU-tested
 #include "ott_mfma_plan.h"  // the batch path's host-side plan (tile geometry, candidate budget, error bound, query norms, query block): HIP-free, CPU-tested
+#include "ott_sort_plan.h"  // the sort path's host-side plan (pass plans, sweep shape, rank or radix, prefix, slices, group extents, copy pieces): HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
 #include "ott_audit.h"  // test build: every HIP call below goes through a device-affinity check (see "which GPU a call is for")
 #endif
@@ -274,11 +275,14 @@ struct ott_store {
     ott::DevBuf d_minpos;    // device word behind min_pos_inv
     // MFMA path scratch
     ott::DevBuf m_Q, m_qinv, m_qnorm, m_tau, m_cntA, m_cntB, m_candA, m_candB, m_over, m_out, m_outcnt, m_uncert, m_prefix;
+    // sort path (ott_sort.hip): the pairs and the sort's other buffers (ensure_pairs), the radix sort's control block and tile
+    // status words (sort_pairs), the dump's cursor (dump_counted), the groups' start words (group_starts), the gates (radix_slice)
     ott::DevBuf l_keysA, l_keysB, l_qA, l_qB, l_tmp, l_cursor, l_hist, l_gate;
-    ott::DevBuf l_ctl;         // rank-sort path (small results): cursor | tickets | ranks | histogram, kept zeroed between queries
+    ott::DevBuf l_ctl;         // rank-sort path (small_slice): cursor | tickets | ranks | histogram (small_ctl_layout), kept zeroed between queries
     bool l_ctl_clean = false;  // the last query on this context left l_ctl zeroed
     // sort path, results of a million hits and more: written straight into the caller's host buffer (query_core sets
-    // direct_out / direct_cap for the call; run_large_k sets direct_done and the groups' counts when it used them)
+    // direct_out / direct_cap for the call; fetch_pieces sets direct_done and the groups' counts when it used them; run_large_k
+    // withdraws the offer while it merges slices)
     ott_hit* direct_out = nullptr;
     uint64_t direct_cap = 0;
     bool direct_done = false;

@@ -16,7 +16,9 @@
 // Pass plans (least significant first) express every order the large-k path needs — canonical (score, row, query),
 // the reference's visit order (score, row >> 3, query, row & 7: store option tie_order), grouped by query — as a list of
 // (source word, shift, width, direction) digits over the pair.
-#include <math.h>
+// What the host side DECIDES (the pass plan of each order, which kernel sweeps, rank or radix sort, prefix and slice sizes, the
+// groups' extents, the copy pieces) is in ott_sort_plan.h, HIP-free and CPU-tested; this file holds the kernels and, behind
+// them, the launches as stages (large_k_slice -> small_slice | radix_slice; sort_group_pairs).
 #include <stddef.h>
 #include <string.h>
 
@@ -26,24 +28,9 @@
 
 namespace ott {
 
-constexpr int RS_THREADS = 512;
 constexpr int RS_WAVES = RS_THREADS / 64;
-constexpr int RS_ITEMS = 8;
-constexpr int RS_TILE = RS_THREADS * RS_ITEMS;  // 4096 pairs
-constexpr int RS_MAXP = 16;
 constexpr uint32_t RS_SPIN_LIMIT = 1u << 24;    // look-back spins before a workgroup gives up (sets the error word: no hang)
 
-struct RsPass {
-    uint32_t src;    // 0 = key (u64), 1 = query id (u32)
-    uint32_t shift;
-    uint32_t mask;   // (1 << width) - 1, width <= 8
-    uint32_t desc;   // 1 = larger digit first
-};
-struct RsPlan {
-    RsPass pass[RS_MAXP];
-    uint32_t n_pass;
-    uint32_t abl;  // timing ablations (store option mfma_abl, results then WRONG): 1 no look-back, 2 no stores, 4 no loads, 8 no ranking
-};
 // The timing ablations exist only in the diagnostic build (make EXTRA=-DOTT_MFMA_DEBUG_BUILD): in the shipped library the tests
 // below are the constant false and the radix passes carry no branch for them.
 #ifdef OTT_MFMA_DEBUG_BUILD
@@ -56,15 +43,6 @@ __device__ __forceinline__ uint32_t rs_digit(const RsPass& ps, uint64_t key, uin
     const uint32_t d = (ps.src ? (q >> ps.shift) : (uint32_t)(key >> ps.shift)) & ps.mask;
     return ps.desc ? ps.mask - d : d;
 }
-
-// control block in device memory: [0, P*256) digit counts -> exclusive starts, then per pass: skip flag, buffer parity
-struct RsCtl {
-    uint32_t start[RS_MAXP * 256];  // histogram, then (rs_scan_kernel) the exclusive scan: where digit d of pass p starts
-    uint32_t skip[RS_MAXP];         // 1 = every pair has the same digit at this position
-    uint32_t parity[RS_MAXP + 1];   // number of passes that really ran before pass p (buffer A if even, B if odd); [n_pass] = total
-    uint32_t ticket[RS_MAXP];       // next tile index of pass p
-    uint32_t error;                 // a look-back gave up
-};
 
 __global__ __launch_bounds__(1024) void rs_hist_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ qs, uint64_t n, RsPlan plan,
                                                         RsCtl* __restrict__ ctl) {
@@ -317,16 +295,6 @@ __global__ __launch_bounds__(RS_THREADS) void rs_pass_kernel(uint64_t* __restric
     }
 }
 
-static size_t rs_tiles(uint64_t n) { return (size_t)((n + RS_TILE - 1) / RS_TILE); }
-static size_t rs_tmp_bytes(uint64_t n) { return ((sizeof(RsCtl) + 255) & ~(size_t)255) + rs_tiles(n) * 256 * sizeof(uint64_t); }
-
-static void rs_add_digits(RsPlan& pl, uint32_t src, uint32_t lo, uint32_t hi, bool desc) {  // bits [lo, hi) of the source word, LSD
-    for (uint32_t b = lo; b < hi && pl.n_pass < RS_MAXP; b += 8) {
-        const uint32_t w = hi - b < 8 ? hi - b : 8;
-        pl.pass[pl.n_pass++] = RsPass{src, b, (1u << w) - 1u, desc ? 1u : 0u};
-    }
-}
-
 // Sorts the n pairs (keysA, qsA) by the plan (stable, least significant digit first); the result is in the A buffers if
 // *in_A, else in the B buffers.  tmp: rs_tmp_bytes(n) bytes.  Synchronises the stream once (the parity word).
 static int radix_sort_plan(hipStream_t stream, uint64_t* keysA, uint32_t* qsA, uint64_t* keysB, uint32_t* qsB, uint64_t n, const RsPlan& plan, void* tmp,
@@ -380,8 +348,6 @@ __global__ __launch_bounds__(256) void hits_from_sorted_kernel(const uint64_t* k
 // No readback in front of a launch, one host wait behind the last one.  N^2 compares: 10k entries = 1e8, a few microseconds
 // of the whole GPU.  10k rows x 768, default take: 0.22 -> 0.12 ms through the Python mirror (benchmarks/default_take_small.py).
 // ---------------------------------------------------------------------------------------------
-constexpr uint32_t SMALL_PAIRS = 16384;
-constexpr uint32_t SMALL_PERQ_MAX = 1024;  // PER_QUERY: queries (their extents are prefix-summed in LDS)
 
 // Result order as ONE 64-bit word compared descending: the score ordinal on top, below it the row and query bits that order
 // equal scores — canonical (lower row, then lower query) or the reference's visit order (tie_sh = 3: 8-row block, query, row in
@@ -577,265 +543,309 @@ void split_plan(const RunPlan& pl, uint64_t m_rows, RunPlan& a, RunPlan& b) {
     for (const ott_run& r : b.runs) b.rows_scored += r.count;
 }
 
-// One SLICE of the sort path: the (row, query) pairs of `pl` — at most 2^30 of them (run_large_k cuts longer plans) — scored,
-// listed, sorted; lists[g] = the slice's best k_eff hits of result group g, in result order.  gate_in (may be null): per query,
-// a score ordinal that every pair worth listing must reach — the k-th best of the same group over EARLIER slices, a lower bound
-// of the final k-th best (ties included: the merge decides among them).
-static int large_k_slice(ott_store* s, const float* queries, uint32_t nq, const ott_query_desc* d, bool perq, const RunPlan& pl, uint64_t k_eff,
-                         const uint64_t* d_mask, uint64_t mask_bits, std::vector<std::vector<ott_hit>>& lists, ott_stats& st,
-                         const std::vector<uint32_t>* gate_in) {
-    const uint64_t cap = pl.rows_scored * nq;
-    if (cap > (1ull << 30)) return fail(OTT_ERR_INVALID, "large_k_slice: internal error (a slice of more than 2^30 pairs)");
+// ---------------------------------------------------------------------------------------------
+// Host side.  What is DECIDED — pass plans, sweep shape, rank sort or radix sort, prefix and slice sizes, group extents, copy
+// pieces — is in ott_sort_plan.h (HIP-free, CPU-tested); here are the launches, as stages over one context.
+// ---------------------------------------------------------------------------------------------
+struct SortCtx {
+    // over the store's pair arrays, which ensure_pairs / ensure_group_pairs must have sized before: (kA, qA) hold the entries,
+    // (kB, qB) are the sort's other buffers.  largest_row: the largest value of the key's row field
+    SortCtx(ott_store* st, uint32_t n_queries, uint64_t largest_row, uint32_t ablations, bool tmax, uint64_t index_base)
+        : s(st), nq(n_queries), rbits(row_bits(largest_row)), abl(ablations), take_max(tmax), base(index_base), kA((uint64_t*)st->l_keysA.p),
+          kB((uint64_t*)st->l_keysB.p), qA((uint32_t*)st->l_qA.p), qB((uint32_t*)st->l_qB.p) {}
+    ott_store* s;
+    uint32_t nq;
+    uint32_t rbits, abl;  // bits of the key's row field that can differ; timing ablations (diagnostics only; 0 in normal use)
+    bool take_max;
+    uint64_t base;   // what turns a key's row field into a hit's index
+    uint64_t *kA, *kB;
+    uint32_t *qA, *qB;
+    // the scoring half, set by name (a slice only: grouped pairs arrive scored)
+    const float* queries = nullptr;
+    const ott_query_desc* d = nullptr;
+    const uint64_t* d_mask = nullptr;
+    uint64_t mask_bits = 0, cap = 0;  // cap: pairs the dump may list
+    SweepShape sweep{};
+};
+
+static int ensure_pairs(ott_store* s, uint64_t cap) {
     int rc;
     if ((rc = s->l_keysA.ensure(cap * 8))) return rc;
     if ((rc = s->l_keysB.ensure(cap * 8))) return rc;
     if ((rc = s->l_qA.ensure(cap * 4))) return rc;
-    if ((rc = s->l_qB.ensure(cap * 4))) return rc;
-    if ((rc = s->l_cursor.ensure(8))) return rc;
+    return s->l_qB.ensure(cap * 4);
+}
 
-    uint64_t* kA = (uint64_t*)s->l_keysA.p;
-    uint64_t* kB = (uint64_t*)s->l_keysB.p;
-    uint32_t* qA = (uint32_t*)s->l_qA.p;
-    uint32_t* qB = (uint32_t*)s->l_qB.p;
-    const uint32_t groups = perq ? nq : 1;
-    const int tile = nq == 1 ? 1 : 4;
-    const uint32_t passes = (nq + tile - 1) / tile;
-
-    // ---- small results: dump, rank, place — no radix passes, no readback in front of a launch, one host wait (see small_rank_kernel)
-    uint32_t small_qbits = 0, small_rbits = 1;
-    while (nq > 1 && small_qbits < 32 && ((uint64_t)(nq - 1) >> small_qbits) != 0) small_qbits++;
-    while (small_rbits < 32 && ((s->n - 1 + s->cur_tie_off) >> small_rbits) != 0) small_rbits++;
-    if (cap <= SMALL_PAIRS && (perq ? nq <= SMALL_PERQ_MAX : small_rbits + small_qbits <= 32) && s->opt.small_sort != 0 && gate_in == nullptr) {
-        const std::vector<uint32_t> prefix = tile_prefix(pl, 64);
-        const bool lean = nq == 1 && s->dimq <= OTT_QEMB_MAX && pl.runs.size() <= 2;
-        if (!lean && (rc = upload_exact_inputs(s, queries, nq, pl, prefix))) return rc;
-        // [cursor (8 B) | pad | tickets (64 x 4) | rank (cap x 4) | hist (nq x 4)]: one memset
-        const size_t off_ticket = 64, off_rank = off_ticket + 64 * 4, off_hist = off_rank + (size_t)cap * 4, ctl_bytes = off_hist + (size_t)nq * 4;
-        // the block is zero when a query finds it: zeroed when it is (re)allocated, and left zeroed by every query's last kernel
-        // (l_ctl serves this path only; a failed query leaves the stream's work to finish and the block is zeroed again)
-        if (s->l_ctl.cap < ctl_bytes || !s->l_ctl_clean) {
-            if ((rc = s->l_ctl.ensure(ctl_bytes))) return rc;
-            OTT_HIP(hipMemsetAsync(s->l_ctl.p, 0, s->l_ctl.cap, s->stream));
-        }
-        s->l_ctl_clean = false;
-        char* ctl = (char*)s->l_ctl.p;
-        ExactParams p;
-        fill_exact_params(s, d, pl, nq, d_mask, mask_bits, prefix.back(), p);
-        p.k = 1;
-        p.dump_keys = kA;
-        p.dump_q = qA;
-        p.dump_cursor = (unsigned long long*)ctl;
-        p.dump_cap = cap;
-        p.dump_gate = nullptr;
-        if (lean) {  // single query, at most two runs: everything rides in the kernel arguments (no H2D copy in front)
-            p.embedded = 1;
-            p.queries = nullptr;
-            p.qinv = nullptr;
-            p.runs = nullptr;
-            p.tile_prefix = nullptr;
-            memcpy(p.qemb, queries, (size_t)s->dim * 4);
-            p.eqinv = host_inv_norm_exact(queries, s->dim);
-            for (size_t i = 0; i < pl.runs.size(); i++) p.eruns[i] = pl.runs[i];
-            for (size_t i = 0; i < prefix.size(); i++) p.eprefix[i] = prefix[i];
-        }
-        // the sweep: rows8 (eight lanes per row, a workgroup per 64-row tile, up to 8 queries per pass: 10 us for 10k x 768
-        // where the streaming kernel needs 33) wherever it fits, which a store this small nearly always does
-        const bool rows8 = s->dimq <= 2048 && prefix.back() <= 1024 && s->opt.exact_small != 0 && s->opt.exact_small != 1;
-        uint32_t passes_run = passes;
-        OTT_HIP(hipEventRecord(s->ev[3], s->stream));
-        if (rows8) {
-            uint32_t t8 = 1;
-            while (t8 < nq && t8 < 8) t8 <<= 1;
-            passes_run = (nq + t8 - 1) / t8;
-            p.small = 2;
-            p.perq = 0;
-            p.list_stride = 64;
-            for (uint32_t ps = 0; ps < passes_run; ps++) {
-                p.q0 = ps * t8;
-                if ((rc = launch_exact(s, p, (int)t8, 1, (int)prefix.back()))) return rc;
-            }
-        } else {
-            const int grid = exact_grid(s, prefix.back());
-            for (uint32_t ps = 0; ps < passes; ps++) {
-                p.q0 = ps * tile;
-                if ((rc = launch_exact_dump(s, p, tile, grid))) return rc;
-            }
-        }
-        OTT_HIP(hipEventRecord(s->ev[4], s->stream));
-        const uint64_t pool_g = perq ? pl.rows_scored : cap;
-        const uint32_t stride = (uint32_t)(k_eff < pool_g ? k_eff : pool_g);  // slots per group
-        const size_t cnt_bytes = (((size_t)groups * 8) + 63) & ~(size_t)63, hits_bytes = (size_t)groups * stride * sizeof(ott_hit);
-        if ((rc = s->h_hits.ensure(cnt_bytes + hits_bytes))) return rc;
-        char* hh = (char*)s->h_hits.p;
-        void* mapped = nullptr;
-        OTT_HIP(hipHostGetDevicePointer(&mapped, hh, 0));
-        const uint32_t cap32 = (uint32_t)cap;
-        // the entries land in device memory in result order, then travel to the host as one coalesced block
-        if ((rc = s->d_hits.ensure(hits_bytes ? hits_bytes : 16))) return rc;
-        hipLaunchKernelGGL(small_rank_kernel, dim3((cap32 + 255) / 256, (cap32 + 1023) / 1024), dim3(256), 0, s->stream, (const uint64_t*)kA, (const uint32_t*)qA,
-                           (const unsigned long long*)ctl, cap32, perq ? 1u : 0u, nq, s->cur_tie_sh, small_qbits, (uint32_t*)(ctl + off_rank), (uint32_t*)(ctl + off_hist));
-        OTT_HIP(hipGetLastError());
-        hipLaunchKernelGGL(small_place_kernel, dim3((cap32 + 255) / 256), dim3(256), 0, s->stream, (const uint64_t*)kA, (const uint32_t*)qA,
-                           (const unsigned long long*)ctl, cap32, perq ? 1u : 0u, k_eff, stride, (const uint32_t*)(ctl + off_rank),
-                           d->take == OTT_TAKE_MAX ? 1u : 0u, tie_base(s), (ott_hit*)s->d_hits.p);
-        OTT_HIP(hipGetLastError());
-        {
-            const uint32_t n16 = (uint32_t)(hits_bytes / 16);
-            uint32_t blocks = (n16 + 255) / 256;
-            blocks = blocks > 64u ? 64u : (blocks ? blocks : 1u);
-            hipLaunchKernelGGL(small_copy_kernel, dim3(blocks), dim3(256), 0, s->stream, (const uint4*)s->d_hits.p, (uint4*)((char*)mapped + cnt_bytes), n16,
-                               (unsigned long long*)ctl, cap32, perq ? 1u : 0u, nq, k_eff, (uint32_t*)(ctl + off_hist), (uint64_t*)mapped,
-                               (uint32_t*)(ctl + off_ticket), (uint32_t)((off_hist - off_ticket) / 4));
-            OTT_HIP(hipGetLastError());
-        }
-        OTT_HIP(hipEventRecord(s->ev[5], s->stream));
-        OTT_HIP(hipStreamSynchronize(s->stream));  // the one wait
-        s->l_ctl_clean = true;
-        const uint32_t passes = passes_run;  // (what the stats below report)
-        const uint64_t* cnt = (const uint64_t*)hh;
-        const ott_hit* hits = (const ott_hit*)(hh + cnt_bytes);
-        lists.assign(groups, {});
-        for (uint32_t g = 0; g < groups; g++) lists[g].assign(hits + (size_t)g * stride, hits + (size_t)g * stride + cnt[g]);
-        float ms2 = 0.f;
-        if (hipEventElapsedTime(&ms2, s->ev[3], s->ev[4]) == hipSuccess) st.score_ns += (uint64_t)(ms2 * 1e6);
-        if (hipEventElapsedTime(&ms2, s->ev[4], s->ev[5]) == hipSuccess) st.merge_ns += (uint64_t)(ms2 * 1e6);
-        st.passes += passes;
-        st.bytes_scanned += (uint64_t)passes * pl.rows_scored * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));
-        return OTT_OK;
+// One scoring sweep over the rows of `plan` (its inputs uploaded, unless `lean`): every passing pair whose ordinal reaches its
+// query's gate is appended to (kA, qA) at *cursor.  The one place that fills ExactParams for a dump.
+static int sweep_dump(const SortCtx& c, const RunPlan& plan, const std::vector<uint32_t>& prefix, void* cursor, const uint32_t* gate, bool lean) {
+    ott_store* s = c.s;
+    ExactParams p;
+    fill_exact_params(s, c.d, plan, c.nq, c.d_mask, c.mask_bits, prefix.back(), p);
+    p.k = 1;
+    p.dump_keys = c.kA;
+    p.dump_q = c.qA;
+    p.dump_cursor = (unsigned long long*)cursor;
+    p.dump_cap = c.cap;
+    p.dump_gate = gate;
+    if (lean) {  // single query, at most two runs: everything rides in the kernel arguments (no H2D copy in front)
+        p.embedded = 1;
+        p.queries = nullptr;
+        p.qinv = nullptr;
+        p.runs = nullptr;
+        p.tile_prefix = nullptr;
+        memcpy(p.qemb, c.queries, (size_t)s->dim * 4);
+        p.eqinv = host_inv_norm_exact(c.queries, s->dim);
+        for (size_t i = 0; i < plan.runs.size(); i++) p.eruns[i] = plan.runs[i];
+        for (size_t i = 0; i < prefix.size(); i++) p.eprefix[i] = prefix[i];
     }
+    // small stores: the rows8 sweep (eight lanes per row, a workgroup per 64-row tile, up to 8 queries per pass) — one query over
+    // 10k x 768: 10 us where the streaming kernel needs 33; 16 queries: two passes of ~12 us where it needed four of ~110
+    int rc;
+    const int tile = (int)c.sweep.tile, grid = c.sweep.rows8 ? (int)prefix.back() : exact_grid(s, prefix.back());
+    if (c.sweep.rows8) {
+        p.small = 2;
+        p.perq = 0;
+        p.list_stride = 64;
+    }
+    for (p.q0 = 0; p.q0 < c.nq; p.q0 += (uint32_t)tile)
+        if ((rc = c.sweep.rows8 ? launch_exact(s, p, tile, 1, grid) : launch_exact_dump(s, p, tile, grid))) return rc;
+    return OTT_OK;
+}
 
-    // which kernel sweeps: rows8 on small stores (decided on the whole plan; the two phases' sub-plans are smaller still)
-    const bool sweep8 = s->dimq <= 2048 && tile_prefix(pl, 64).back() <= 1024 && s->opt.exact_small != 0 && s->opt.exact_small != 1;
-    uint32_t t8 = 1;
-    while (t8 < nq && t8 < 8) t8 <<= 1;
-    const uint32_t passes_eff = sweep8 ? (nq + t8 - 1) / t8 : passes;  // corpus passes one sweep makes (stats)
-    // one scoring sweep over the rows of `plan`: every passing pair whose ordinal reaches its query's gate is appended to
-    // (keys, qs) behind the `first` entries already there; the number of entries afterwards comes back in *n_entries
-    auto dump = [&](const RunPlan& plan, uint64_t* keys, uint32_t* qs, uint64_t first, const uint32_t* gate, unsigned long long* n_entries) -> int {
-        *n_entries = first;
-        if (plan.rows_scored == 0) return OTT_OK;
-        const std::vector<uint32_t> prefix = tile_prefix(plan, 64);
-        int r = upload_exact_inputs(s, queries, nq, plan, prefix);
-        if (r) return r;
-        OTT_HIP(hipMemsetAsync(s->l_cursor.p, 0, 8, s->stream));
-        if (first) OTT_HIP(hipMemsetD32Async((hipDeviceptr_t)s->l_cursor.p, (int)(uint32_t)first, 1, s->stream));  // first <= cap <= 2^30
-        ExactParams p;
-        fill_exact_params(s, d, plan, nq, d_mask, mask_bits, prefix.back(), p);
-        p.k = 1;
-        p.dump_keys = keys;
-        p.dump_q = qs;
-        p.dump_cursor = (unsigned long long*)s->l_cursor.p;
-        p.dump_cap = cap;
-        p.dump_gate = gate;
-        // small stores: the rows8 sweep (eight lanes per row, a workgroup per 64-row tile, up to 8 queries per pass) — 16 queries
-        // over 10k x 768: two passes of ~12 us where the streaming kernel needed four of ~110
-        if (sweep8) {
-            p.small = 2;
-            p.perq = 0;
-            p.list_stride = 64;
-            for (uint32_t q0 = 0; q0 < nq; q0 += t8) {
-                p.q0 = q0;
-                if ((r = launch_exact(s, p, (int)t8, 1, (int)prefix.back()))) return r;
-            }
-        } else {
-            const int grid = exact_grid(s, prefix.back());
-            for (uint32_t ps = 0; ps < passes; ps++) {
-                p.q0 = ps * tile;
-                if ((r = launch_exact_dump(s, p, tile, grid))) return r;
-            }
-        }
-        OTT_HIP(hipMemcpyAsync(n_entries, s->l_cursor.p, 8, hipMemcpyDeviceToHost, s->stream));
-        OTT_HIP(hipStreamSynchronize(s->stream));
-        if (*n_entries > cap) *n_entries = cap;
-        return OTT_OK;
-    };
-    // sorts entries [0, n) of (kA, qA) into result order (merged: best first overall; per query: grouped by query, best first
-    // in each group); on return kA / qA point at the sorted arrays and kB / qB at the other pair
-    auto sort_entries = [&](uint64_t n, bool score_only) -> int {
-        int r = s->l_tmp.ensure(rs_tmp_bytes(n));
-        if (r) return r;
-        uint32_t qbits = 0;
-        while (nq > 1 && qbits < 32 && ((uint64_t)(nq - 1) >> qbits) != 0) qbits++;
-        RsPlan plan;
-        memset(&plan, 0, sizeof(plan));
-        plan.abl = (uint32_t)s->opt.mfma_abl;  // (diagnostics only; 0 in normal use)
-        // key = ord(score) << 32 | ~row: only the low bits of ~row that can differ between rows of this store are sorted on
-        uint32_t rbits = 1;
-        while (rbits < 32 && ((s->n - 1 + s->cur_tie_off) >> rbits) != 0) rbits++;  // (the key's row field is row + tie_off)
-        const uint32_t sh = s->cur_tie_sh < rbits ? s->cur_tie_sh : 0u;
-        auto key_digits = [&](uint32_t from) {  // bits [from, rbits) of ~row, then the 32 bits of the score ordinal
-            rs_add_digits(plan, 0, from, rbits, true);
-            rs_add_digits(plan, 0, 32, 64, true);
-        };
-        if (score_only) {
-            // first phase: only the k-th best SCORE of each group is wanted (the order among equal scores is the final sort's business)
-            rs_add_digits(plan, 0, 32, 64, true);
-            if (perq) rs_add_digits(plan, 1, 0, qbits, false);
-        } else if (!perq) {
-            if (sh == 0) {
-                // canonical merged order: key (score, then lower row) descending, ties by query ascending — LSD: query first
-                rs_add_digits(plan, 1, 0, qbits, false);
-                key_digits(0);
-            } else {
-                // the reference's visit order among equal scores: 8-row block, then query, then row within the block
-                rs_add_digits(plan, 0, 0, sh, true);
-                rs_add_digits(plan, 1, 0, qbits, false);
-                key_digits(sh);
-            }
-        } else {
-            // grouped by query, each group key descending (one query: row order IS the visit order): key first, then the query
-            key_digits(0);
-            rs_add_digits(plan, 1, 0, qbits, false);
-        }
-        bool in_A = true;
-        if ((r = radix_sort_plan(s->stream, kA, qA, kB, qB, n, plan, s->l_tmp.p, s->n_cu, &in_A))) return r;
-        if (!in_A) {
-            std::swap(kA, kB);
-            std::swap(qA, qB);
-        }
-        return OTT_OK;
-    };
-    // per-query entry counts of the sorted entries (per-query mode: the groups' extents)
-    auto group_starts = [&](uint64_t n) -> int {  // l_hist[q] = first entry of query q among the sorted entries (0xFFFFFFFF: none)
-        int r = s->l_hist.ensure((size_t)nq * 4);
-        if (r) return r;
-        OTT_HIP(hipMemsetAsync(s->l_hist.p, 0xFF, (size_t)nq * 4, s->stream));
-        hipLaunchKernelGGL(group_start_kernel, dim3((uint32_t)s->n_cu * 4), dim3(256), 0, s->stream, qA, n, (uint32_t*)s->l_hist.p);
+// The radix path's sweep: the entries go behind the `first` already there; the number of entries afterwards comes back in
+// *n_entries (one host wait).
+static int dump_counted(const SortCtx& c, const RunPlan& plan, uint64_t first, const uint32_t* gate, unsigned long long* n_entries) {
+    ott_store* s = c.s;
+    *n_entries = first;
+    if (plan.rows_scored == 0) return OTT_OK;
+    const std::vector<uint32_t> prefix = tile_prefix(plan, 64);
+    int rc = upload_exact_inputs(s, c.queries, c.nq, plan, prefix);
+    if (rc) return rc;
+    OTT_HIP(hipMemsetAsync(s->l_cursor.p, 0, 8, s->stream));
+    if (first) OTT_HIP(hipMemsetD32Async((hipDeviceptr_t)s->l_cursor.p, (int)(uint32_t)first, 1, s->stream));  // first <= cap <= 2^30
+    if ((rc = sweep_dump(c, plan, prefix, s->l_cursor.p, gate, false))) return rc;
+    OTT_HIP(hipMemcpyAsync(n_entries, s->l_cursor.p, 8, hipMemcpyDeviceToHost, s->stream));
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    if (*n_entries > c.cap) *n_entries = c.cap;
+    return OTT_OK;
+}
+
+// sorts entries [0, n) of (kA, qA) into `order` (ott_sort_plan.h); on return kA / qA point at the sorted arrays and kB / qB at
+// the other pair
+static int sort_pairs(SortCtx& c, uint64_t n, SortOrder order) {
+    ott_store* s = c.s;
+    // (grouped pairs: ensure_group_pairs sized l_tmp for at least n pairs, so nothing is allocated here, and their order,
+    // SORT_BY_QUERY, does not read the tie shift)
+    int rc = s->l_tmp.ensure(rs_tmp_bytes(n));
+    if (rc) return rc;
+    RsPlan plan;
+    if (!sort_order_plan(order, c.rbits, query_bits(c.nq), s->cur_tie_sh, c.abl, plan))
+        return fail(OTT_ERR_INVALID, "sort path: internal error (a pass plan of more than 16 digits)");
+    bool in_A = true;
+    if ((rc = radix_sort_plan(s->stream, c.kA, c.qA, c.kB, c.qB, n, plan, s->l_tmp.p, s->n_cu, &in_A))) return rc;
+    if (!in_A) {
+        std::swap(c.kA, c.kB);
+        std::swap(c.qA, c.qB);
+    }
+    return OTT_OK;
+}
+
+// l_hist[q] = first entry of query q among the n entries sorted by query (0xFFFFFFFF: none); stays on the device
+static int group_starts(const SortCtx& c, uint64_t n) {
+    ott_store* s = c.s;
+    int rc = s->l_hist.ensure((size_t)c.nq * 4);
+    if (rc) return rc;
+    OTT_HIP(hipMemsetAsync(s->l_hist.p, 0xFF, (size_t)c.nq * 4, s->stream));
+    hipLaunchKernelGGL(group_start_kernel, dim3((uint32_t)s->n_cu * 4), dim3(256), 0, s->stream, (const uint32_t*)c.qA, n, (uint32_t*)s->l_hist.p);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+// the groups' extents on the host (one wait); `on_device` false: ONE group of all n entries, nothing is launched
+static int fetch_group_extents(const SortCtx& c, uint64_t n, uint64_t k, bool on_device, std::vector<uint64_t>& first, std::vector<uint64_t>& count,
+                               uint64_t* total) {
+    std::vector<uint32_t> start(on_device ? c.nq : 1u, 0u);
+    if (on_device) {
+        int rc = group_starts(c, n);
+        if (rc) return rc;
+        OTT_HIP(hipMemcpyAsync(start.data(), c.s->l_hist.p, (size_t)c.nq * 4, hipMemcpyDeviceToHost, c.s->stream));
+        OTT_HIP(hipStreamSynchronize(c.s->stream));
+    }
+    *total = group_extents(start, n, k, first, count);
+    return c.s->d_hits.ensure((size_t)(*total ? *total : 1) * sizeof(ott_hit));
+}
+
+// ---- emission: the groups' first count[g] sorted entries as hits in d_hits, back to back ----
+static int emit_per_group(const SortCtx& c, const std::vector<uint64_t>& first, const std::vector<uint64_t>& count) {
+    uint64_t o = 0;
+    for (size_t g = 0; g < count.size(); g++) {
+        if (!count[g]) continue;
+        hipLaunchKernelGGL(hits_from_sorted_kernel, dim3((uint32_t)((count[g] + 255) / 256)), dim3(256), 0, c.s->stream, (const uint64_t*)c.kA, (const uint32_t*)c.qA,
+                           first[g], count[g], c.take_max ? 1u : 0u, c.base, (ott_hit*)c.s->d_hits.p + o);
         OTT_HIP(hipGetLastError());
-        return OTT_OK;
-    };
-    auto group_hist = [&](uint64_t n, std::vector<uint32_t>& h) -> int {
-        int r = group_starts(n);
-        if (r) return r;
-        std::vector<uint32_t> st(nq);
-        OTT_HIP(hipMemcpyAsync(st.data(), s->l_hist.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
-        OTT_HIP(hipStreamSynchronize(s->stream));
-        h.assign(nq, 0);
-        uint64_t next = n;
-        for (uint32_t q = nq; q-- > 0;) {
-            if (st[q] == 0xFFFFFFFFu) continue;
-            h[q] = (uint32_t)(next - st[q]);
-            next = st[q];
-        }
-        return OTT_OK;
-    };
+        o += count[g];
+    }
+    return OTT_OK;
+}
+// ONE launch for all groups; its table {first entry, first output slot} per group travels through h_hits, behind the hits' room
+static int emit_all_groups(const SortCtx& c, uint64_t n, uint64_t k, const std::vector<uint64_t>& first, const std::vector<uint64_t>& count, uint64_t total) {
+    ott_store* s = c.s;
+    std::vector<uint64_t> tab(count.size() * 2);
+    uint64_t o = 0;
+    for (size_t g = 0; g < count.size(); g++) {
+        tab[2 * g] = first[g];
+        tab[2 * g + 1] = o;
+        o += count[g];
+    }
+    int rc;
+    if ((rc = s->d_misc.ensure(tab.size() * 8))) return rc;
+    if ((rc = s->h_hits.ensure((size_t)(total ? total : 1) * sizeof(ott_hit) + tab.size() * 8))) return rc;
+    uint64_t* htab = (uint64_t*)((char*)s->h_hits.p + (size_t)(total ? total : 1) * sizeof(ott_hit));
+    memcpy(htab, tab.data(), tab.size() * 8);
+    OTT_HIP(hipMemcpyAsync(s->d_misc.p, htab, tab.size() * 8, hipMemcpyHostToDevice, s->stream));
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->n_cu * 8);
+    hipLaunchKernelGGL(hits_from_sorted_grouped_kernel, dim3(blocks), dim3(256), 0, s->stream, c.kA, c.qA, n, (const uint64_t*)s->d_misc.p, k,
+                       c.take_max ? 1u : 0u, c.base, (ott_hit*)s->d_hits.p);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
 
-    // Two phases when k is small beside the store (round 3; store option "large_k_pre").  Phase 1 scores the first m rows and
-    // sorts them; the k-th best of a result group there is a LOWER bound of the group's final k-th best, so phase 2 lists, of
-    // the remaining rows, only the pairs that reach it (ties included: the final sort decides among them) — ~k n / m pairs
-    // instead of n, behind one wave-level atomic per tile that HOLDS a survivor instead of one per tile.  m = sqrt(k x pairs
-    // per group) balances the two lists.  Rows in an unlucky order (best last) only cost the pruning, never the result.  The
-    // flat fill pass of the reference tie order (every score ranks the same) has no bound to use and stays single-phase.
-    uint64_t m_rows = 0;
-    if (s->opt.large_k_pre != 0 && !s->cur_flat && pl.rows_scored > 0) {
-        const double pairs = (double)pl.rows_scored * (perq ? 1.0 : (double)nq);
-        const double f = sqrt((double)k_eff / pairs);
-        if (f <= 0.25) {
-            m_rows = ((uint64_t)ceil(f * (double)pl.rows_scored) + 63) & ~63ull;
-            if (m_rows < 4096) m_rows = 4096;
-            if (m_rows * 4 > pl.rows_scored) m_rows = 0;
+// ---- fetch: d_hits to lists[g], count[g] hits each; all three end with the stream idle ----
+static int fetch_per_group(ott_store* s, const std::vector<uint64_t>& count, std::vector<std::vector<ott_hit>>& lists) {
+    uint64_t o = 0;
+    for (size_t g = 0; g < count.size(); g++) {
+        lists[g].resize((size_t)count[g]);
+        if (count[g]) OTT_HIP(hipMemcpyAsync(lists[g].data(), (ott_hit*)s->d_hits.p + o, (size_t)count[g] * sizeof(ott_hit), hipMemcpyDeviceToHost, s->stream));
+        o += count[g];
+    }
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    return OTT_OK;
+}
+// a result that fits one pinned block (h_hits, which emit_all_groups sized): ONE copy to the host
+static int fetch_block(ott_store* s, const std::vector<uint64_t>& count, uint64_t total, std::vector<std::vector<ott_hit>>& lists) {
+    if (total) OTT_HIP(hipMemcpyAsync(s->h_hits.p, s->d_hits.p, (size_t)total * sizeof(ott_hit), hipMemcpyDeviceToHost, s->stream));
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    const ott_hit* hh = (const ott_hit*)s->h_hits.p;
+    for (size_t g = 0; g < count.size(); g++) {
+        lists[g].assign(hh, hh + count[g]);
+        hh += count[g];
+    }
+    return OTT_OK;
+}
+// Results of a million hits (the reference's default take is every row): a device-to-host copy into pageable memory
+// runs at ~2 GB/s here, through pinned memory at PCIe speed.  Large results (256k hits and more) come over in 2-MB pieces through two
+// pinned buffers, each piece copied on to its list while the next one is on the wire (80 MB: 40 -> ~10 ms).
+static int fetch_pieces(ott_store* s, const std::vector<uint64_t>& count, uint64_t total, std::vector<std::vector<ott_hit>>& lists) {
+    int rc;
+    if ((rc = s->h_hits.ensure(2 * COPY_PIECE * sizeof(ott_hit)))) return rc;
+    ott_hit* pin[2] = {(ott_hit*)s->h_hits.p, (ott_hit*)s->h_hits.p + COPY_PIECE};
+    // straight into the caller's buffer when query_core offered it (the groups back to back, as it would copy them): the
+    // lists stay empty.  Through the lists a result of 3M hits crossed host memory three more times, page faults included
+    // (zero-filled vector, copy in, copy out: 24 ms behind 2 ms of GPU work)
+    const bool direct = s->direct_out != nullptr && total <= s->direct_cap;
+    if (direct) {
+        s->direct_done = true;
+        s->direct_counts.assign(count.begin(), count.end());
+    } else {
+        for (size_t g = 0; g < count.size(); g++) lists[g].resize(count[g]);
+    }
+    const std::vector<CopyPiece> pieces = copy_pieces(count, COPY_PIECE);
+    for (size_t i = 0; i <= pieces.size(); i++) {
+        if (i < pieces.size()) {
+            OTT_HIP(hipMemcpyAsync(pin[i & 1], (ott_hit*)s->d_hits.p + pieces[i].src, pieces[i].n * sizeof(ott_hit), hipMemcpyDeviceToHost, s->stream));
+            OTT_HIP(hipEventRecord(s->ev[i & 1], s->stream));
+        }
+        if (i > 0) {
+            const CopyPiece& pc = pieces[i - 1];
+            OTT_HIP(hipEventSynchronize(s->ev[(i - 1) & 1]));
+            memcpy(direct ? s->direct_out + pc.src : lists[pc.g].data() + pc.at, pin[(i - 1) & 1], pc.n * sizeof(ott_hit));
         }
     }
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    return OTT_OK;
+}
+
+// Small results: dump, rank, place — no radix passes, no readback in front of a launch, one host wait (see small_rank_kernel)
+static int small_slice(SortCtx& c, bool perq, const RunPlan& pl, const std::vector<uint32_t>& prefix, uint64_t k_eff, std::vector<std::vector<ott_hit>>& lists) {
+    ott_store* s = c.s;
+    int rc;
+    const uint32_t nq = c.nq, groups = perq ? nq : 1, cap32 = (uint32_t)c.cap, pq = perq ? 1u : 0u;
+    const bool lean = nq == 1 && s->dimq <= OTT_QEMB_MAX && pl.runs.size() <= 2;
+    if (!lean && (rc = upload_exact_inputs(s, c.queries, nq, pl, prefix))) return rc;
+    const SmallCtl off = small_ctl_layout(c.cap, nq);
+    // the block is zero when a query finds it: zeroed when it is (re)allocated, and left zeroed by every query's last kernel
+    // (l_ctl serves this path only; a failed query leaves the stream's work to finish and the block is zeroed again)
+    if (s->l_ctl.cap < off.total || !s->l_ctl_clean) {
+        if ((rc = s->l_ctl.ensure(off.total))) return rc;
+        OTT_HIP(hipMemsetAsync(s->l_ctl.p, 0, s->l_ctl.cap, s->stream));
+    }
+    s->l_ctl_clean = false;
+    char* ctl = (char*)s->l_ctl.p;
+    OTT_HIP(hipEventRecord(s->ev[3], s->stream));
+    if ((rc = sweep_dump(c, pl, prefix, ctl + off.cursor, nullptr, lean))) return rc;
+    OTT_HIP(hipEventRecord(s->ev[4], s->stream));
+    const uint64_t pool_g = perq ? pl.rows_scored : c.cap;
+    const uint32_t stride = (uint32_t)(k_eff < pool_g ? k_eff : pool_g);  // slots per group
+    const size_t cnt_bytes = (((size_t)groups * 8) + 63) & ~(size_t)63, hits_bytes = (size_t)groups * stride * sizeof(ott_hit);
+    if ((rc = s->h_hits.ensure(cnt_bytes + hits_bytes))) return rc;
+    char* hh = (char*)s->h_hits.p;
+    void* mapped = nullptr;
+    OTT_HIP(hipHostGetDevicePointer(&mapped, hh, 0));
+    // the entries land in device memory in result order, then travel to the host as one coalesced block
+    if ((rc = s->d_hits.ensure(hits_bytes ? hits_bytes : 16))) return rc;
+    hipLaunchKernelGGL(small_rank_kernel, dim3((cap32 + 255) / 256, (cap32 + 1023) / 1024), dim3(256), 0, s->stream, (const uint64_t*)c.kA, (const uint32_t*)c.qA,
+                       (const unsigned long long*)ctl, cap32, pq, nq, s->cur_tie_sh, query_bits(nq), (uint32_t*)(ctl + off.rank), (uint32_t*)(ctl + off.hist));
+    OTT_HIP(hipGetLastError());
+    hipLaunchKernelGGL(small_place_kernel, dim3((cap32 + 255) / 256), dim3(256), 0, s->stream, (const uint64_t*)c.kA, (const uint32_t*)c.qA,
+                       (const unsigned long long*)ctl, cap32, pq, k_eff, stride, (const uint32_t*)(ctl + off.rank), c.take_max ? 1u : 0u, c.base,
+                       (ott_hit*)s->d_hits.p);
+    OTT_HIP(hipGetLastError());
+    const uint32_t n16 = (uint32_t)(hits_bytes / 16);
+    const uint32_t blocks = std::min(std::max((n16 + 255) / 256, 1u), 64u);
+    hipLaunchKernelGGL(small_copy_kernel, dim3(blocks), dim3(256), 0, s->stream, (const uint4*)s->d_hits.p, (uint4*)((char*)mapped + cnt_bytes), n16,
+                       (unsigned long long*)ctl, cap32, pq, nq, k_eff, (uint32_t*)(ctl + off.hist), (uint64_t*)mapped, (uint32_t*)(ctl + off.ticket),
+                       (uint32_t)((off.hist - off.ticket) / 4));
+    OTT_HIP(hipGetLastError());
+    OTT_HIP(hipEventRecord(s->ev[5], s->stream));
+    OTT_HIP(hipStreamSynchronize(s->stream));  // the one wait
+    s->l_ctl_clean = true;
+    const uint64_t* cnt = (const uint64_t*)hh;
+    const ott_hit* hits = (const ott_hit*)(hh + cnt_bytes);
+    lists.assign(groups, {});
+    for (uint32_t g = 0; g < groups; g++) lists[g].assign(hits + (size_t)g * stride, hits + (size_t)g * stride + cnt[g]);
+    return OTT_OK;
+}
+
+// The first phase of two (round 3; store option "large_k_pre"), when k is small beside the store.  It scores the first m rows
+// and sorts them; the k-th best of a result group there is a LOWER bound of the group's final k-th best, so phase 2 lists, of
+// the remaining rows, only the pairs that reach it (ties included: the final sort decides among them) — ~k n / m pairs
+// instead of n, behind one wave-level atomic per tile that HOLDS a survivor instead of one per tile.  Rows in an unlucky order
+// (best last) only cost the pruning, never the result.  Leaves the gates in d_gate (risen from gate0, the earlier slices').
+static int prefix_phase(SortCtx& c, bool perq, const RunPlan& plA, uint64_t k_eff, uint32_t* d_gate, const uint32_t* gate0, unsigned long long* n_entries) {
+    ott_store* s = c.s;
+    int rc;
+    if ((rc = dump_counted(c, plA, 0, gate0, n_entries))) return rc;
+    if (*n_entries) {
+        if ((rc = sort_pairs(c, *n_entries, perq ? SORT_SCORE_BY_QUERY : SORT_SCORE))) return rc;
+        const uint32_t* d_hist = nullptr;
+        if (perq) {  // the groups' extents stay on the device
+            if ((rc = group_starts(c, *n_entries))) return rc;
+            d_hist = (const uint32_t*)s->l_hist.p;
+        }
+        hipLaunchKernelGGL(gate_from_sorted_kernel, dim3(1), dim3(64), 0, s->stream, (const uint64_t*)c.kA, d_hist, (uint64_t)*n_entries, k_eff, c.nq, d_gate, gate0);
+        OTT_HIP(hipGetLastError());
+    } else if (!gate0) {
+        OTT_HIP(hipMemsetAsync(d_gate, 0, (size_t)c.nq * 4, s->stream));
+    }
+    return OTT_OK;
+}
+
+// The radix path: one sweep or two phases list the pairs, the radix sort orders them, the groups' best k_eff come back as hits.
+static int radix_slice(SortCtx& c, bool perq, const RunPlan& pl, uint64_t k_eff, std::vector<std::vector<ott_hit>>& lists, const std::vector<uint32_t>* gate_in) {
+    ott_store* s = c.s;
+    int rc;
+    const uint32_t nq = c.nq, groups = perq ? nq : 1;
+    const uint64_t m_rows = prefix_rows(pl.rows_scored, nq, perq, k_eff, s->opt.large_k_pre != 0, s->cur_flat);
     OTT_HIP(hipEventRecord(s->ev[3], s->stream));
     unsigned long long n_entries = 0;
     if ((rc = s->l_gate.ensure((size_t)nq * 4))) return rc;
@@ -848,141 +858,66 @@ static int large_k_slice(ott_store* s, const float* queries, uint32_t nq, const 
     if (m_rows) {
         RunPlan plA, plB;
         split_plan(pl, m_rows, plA, plB);
-        if ((rc = dump(plA, kA, qA, 0, gate0, &n_entries))) return rc;
-        if (n_entries) {
-            if ((rc = sort_entries(n_entries, true))) return rc;
-            const uint32_t* d_hist = nullptr;
-            if (perq) {  // the groups' extents stay on the device
-                if ((rc = group_starts(n_entries))) return rc;
-                d_hist = (const uint32_t*)s->l_hist.p;
-            }
-            hipLaunchKernelGGL(gate_from_sorted_kernel, dim3(1), dim3(64), 0, s->stream, (const uint64_t*)kA, d_hist, (uint64_t)n_entries, k_eff, nq, d_gate, gate0);
-            OTT_HIP(hipGetLastError());
-        } else if (!gate0) {
-            OTT_HIP(hipMemsetAsync(d_gate, 0, (size_t)nq * 4, s->stream));
-        }
-        if ((rc = dump(plB, kA, qA, n_entries, d_gate, &n_entries))) return rc;
-    } else {
-        if ((rc = dump(pl, kA, qA, 0, gate0, &n_entries))) return rc;
+        if ((rc = prefix_phase(c, perq, plA, k_eff, d_gate, gate0, &n_entries))) return rc;
+        if ((rc = dump_counted(c, plB, n_entries, d_gate, &n_entries))) return rc;
+    } else if ((rc = dump_counted(c, pl, 0, gate0, &n_entries))) {
+        return rc;
     }
     OTT_HIP(hipEventRecord(s->ev[4], s->stream));
 
     lists.assign(groups, {});
-    if (n_entries) {
-        if ((rc = sort_entries(n_entries, false))) return rc;
-        // group extents
-        std::vector<uint64_t> first(groups, 0), count(groups, 0);
-        if (!perq) count[0] = n_entries < k_eff ? n_entries : k_eff;
-        else {
-            std::vector<uint32_t> h;
-            if ((rc = group_hist(n_entries, h))) return rc;
-            uint64_t off = 0;
-            for (uint32_t q = 0; q < nq; q++) {
-                first[q] = off;
-                count[q] = h[q] < k_eff ? h[q] : k_eff;
-                off += h[q];
-            }
-        }
-        uint64_t total = 0;
-        for (uint32_t g = 0; g < groups; g++) total += count[g];
-        if ((rc = s->d_hits.ensure((size_t)(total ? total : 1) * sizeof(ott_hit)))) return rc;
-        uint64_t o = 0;
-        constexpr size_t PIECE = (size_t)128 * 1024;  // hits per piece (2 MB)
-        // several groups, a result that fits one pinned block: ONE launch for all groups, ONE copy to the host
-        const bool one_shot = perq && groups > 2 && total < 2 * PIECE;
-        if (one_shot) {
-            std::vector<uint64_t> tab((size_t)groups * 2);
-            for (uint32_t g = 0; g < groups; g++) {
-                tab[2 * g] = first[g];
-                tab[2 * g + 1] = o;
-                o += count[g];
-            }
-            if ((rc = s->d_misc.ensure(tab.size() * 8))) return rc;
-            if ((rc = s->h_hits.ensure((size_t)(total ? total : 1) * sizeof(ott_hit) + tab.size() * 8))) return rc;
-            uint64_t* htab = (uint64_t*)((char*)s->h_hits.p + (size_t)(total ? total : 1) * sizeof(ott_hit));
-            memcpy(htab, tab.data(), tab.size() * 8);
-            OTT_HIP(hipMemcpyAsync(s->d_misc.p, htab, tab.size() * 8, hipMemcpyHostToDevice, s->stream));
-            const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_entries + 255) / 256, (uint64_t)s->n_cu * 8);
-            hipLaunchKernelGGL(hits_from_sorted_grouped_kernel, dim3(blocks), dim3(256), 0, s->stream, kA, qA, (uint64_t)n_entries, (const uint64_t*)s->d_misc.p,
-                               k_eff, d->take == OTT_TAKE_MAX ? 1u : 0u, tie_base(s), (ott_hit*)s->d_hits.p);
-            OTT_HIP(hipGetLastError());
-            OTT_HIP(hipEventRecord(s->ev[5], s->stream));
-            if (total) OTT_HIP(hipMemcpyAsync(s->h_hits.p, s->d_hits.p, (size_t)total * sizeof(ott_hit), hipMemcpyDeviceToHost, s->stream));
-            OTT_HIP(hipStreamSynchronize(s->stream));
-            const ott_hit* hh = (const ott_hit*)s->h_hits.p;
-            o = 0;
-            for (uint32_t g = 0; g < groups; g++) {
-                lists[g].assign(hh + o, hh + o + count[g]);
-                o += count[g];
-            }
-            float ms1 = 0.f;
-            if (hipEventElapsedTime(&ms1, s->ev[3], s->ev[4]) == hipSuccess) st.score_ns += (uint64_t)(ms1 * 1e6);
-            if (hipEventElapsedTime(&ms1, s->ev[4], s->ev[5]) == hipSuccess) st.merge_ns += (uint64_t)(ms1 * 1e6);
-            st.passes += passes_eff;
-            st.bytes_scanned += (uint64_t)passes_eff * pl.rows_scored * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));
-            return OTT_OK;
-        }
-        for (uint32_t g = 0; g < groups; g++) {
-            if (!count[g]) continue;
-            hipLaunchKernelGGL(hits_from_sorted_kernel, dim3((uint32_t)((count[g] + 255) / 256)), dim3(256), 0, s->stream, kA, qA, first[g],
-                               count[g], d->take == OTT_TAKE_MAX ? 1u : 0u, tie_base(s), (ott_hit*)s->d_hits.p + o);
-            OTT_HIP(hipGetLastError());
-            o += count[g];
-        }
-        OTT_HIP(hipEventRecord(s->ev[5], s->stream));
-        o = 0;
-        // Results of a million hits (the reference's default take is every row): a device-to-host copy into pageable memory
-        // runs at ~2 GB/s here, through pinned memory at PCIe speed.  Large results (256k hits and more) come over in 2-MB pieces through two
-        // pinned buffers, each piece copied on to its list while the next one is on the wire (80 MB: 40 -> ~10 ms).
-        if (total >= 2 * PIECE) {
-            if ((rc = s->h_hits.ensure(2 * PIECE * sizeof(ott_hit)))) return rc;
-            ott_hit* pin[2] = {(ott_hit*)s->h_hits.p, (ott_hit*)s->h_hits.p + PIECE};
-            // straight into the caller's buffer when query_core offered it (the groups back to back, as it would copy them): the
-            // lists stay empty.  Through the lists a result of 3M hits crossed host memory three more times, page faults included
-            // (zero-filled vector, copy in, copy out: 24 ms behind 2 ms of GPU work)
-            const bool direct = s->direct_out != nullptr && total <= s->direct_cap;
-            if (direct) {
-                s->direct_done = true;
-                s->direct_counts.assign(count.begin(), count.end());
-            } else {
-                for (uint32_t g = 0; g < groups; g++) lists[g].resize(count[g]);
-            }
-            // pieces never straddle two lists: (list, offset, n) in order
-            struct Piece { uint32_t g; uint64_t at, n, src; };
-            std::vector<Piece> pieces;
-            for (uint32_t g = 0; g < groups; g++) {
-                for (uint64_t at = 0; at < count[g]; at += PIECE) pieces.push_back({g, at, std::min<uint64_t>(PIECE, count[g] - at), o + at});
-                o += count[g];
-            }
-            for (size_t i = 0; i <= pieces.size(); i++) {
-                if (i < pieces.size()) {
-                    OTT_HIP(hipMemcpyAsync(pin[i & 1], (ott_hit*)s->d_hits.p + pieces[i].src, pieces[i].n * sizeof(ott_hit), hipMemcpyDeviceToHost, s->stream));
-                    OTT_HIP(hipEventRecord(s->ev[i & 1], s->stream));
-                }
-                if (i > 0) {
-                    const Piece& pc = pieces[i - 1];
-                    OTT_HIP(hipEventSynchronize(s->ev[(i - 1) & 1]));
-                    memcpy(direct ? s->direct_out + pc.src : lists[pc.g].data() + pc.at, pin[(i - 1) & 1], pc.n * sizeof(ott_hit));
-                }
-            }
-        } else {
-            for (uint32_t g = 0; g < groups; g++) {
-                lists[g].resize(count[g]);
-                if (count[g]) OTT_HIP(hipMemcpyAsync(lists[g].data(), (ott_hit*)s->d_hits.p + o, count[g] * sizeof(ott_hit), hipMemcpyDeviceToHost, s->stream));
-                o += count[g];
-            }
-        }
-        OTT_HIP(hipStreamSynchronize(s->stream));
-    } else {
+    if (!n_entries) {
         OTT_HIP(hipEventRecord(s->ev[5], s->stream));
         OTT_HIP(hipStreamSynchronize(s->stream));
+        return OTT_OK;
     }
+    // merged: best first overall; per query: grouped by query, best first in each group
+    if ((rc = sort_pairs(c, n_entries, perq ? SORT_BY_QUERY : SORT_MERGED))) return rc;
+    std::vector<uint64_t> first, count;
+    uint64_t total = 0;
+    if ((rc = fetch_group_extents(c, n_entries, k_eff, perq, first, count, &total))) return rc;
+    // several groups, a result that fits one pinned block: ONE launch for all groups, ONE copy to the host (round 4: one launch and
+    // one copy per group were 64 + 64 API calls behind a 64-query batch on a small store)
+    const bool one_shot = perq && groups > 2 && total < 2 * COPY_PIECE;
+    if ((rc = one_shot ? emit_all_groups(c, n_entries, k_eff, first, count, total) : emit_per_group(c, first, count))) return rc;
+    OTT_HIP(hipEventRecord(s->ev[5], s->stream));
+    if (one_shot) return fetch_block(s, count, total, lists);
+    return total >= 2 * COPY_PIECE ? fetch_pieces(s, count, total, lists) : fetch_per_group(s, count, lists);
+}
+
+static void add_sort_stats(const SortCtx& c, const RunPlan& pl, ott_stats& st) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, s->ev[3], s->ev[4]) == hipSuccess) st.score_ns += (uint64_t)(ms * 1e6);
-    if (hipEventElapsedTime(&ms, s->ev[4], s->ev[5]) == hipSuccess) st.merge_ns += (uint64_t)(ms * 1e6);
-    st.passes += passes_eff;
-    st.bytes_scanned += (uint64_t)passes_eff * pl.rows_scored * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));
-    return OTT_OK;
+    if (hipEventElapsedTime(&ms, c.s->ev[3], c.s->ev[4]) == hipSuccess) st.score_ns += (uint64_t)(ms * 1e6);
+    if (hipEventElapsedTime(&ms, c.s->ev[4], c.s->ev[5]) == hipSuccess) st.merge_ns += (uint64_t)(ms * 1e6);
+    st.passes += c.sweep.passes;  // (two phases split ONE sweep over the rows)
+    st.bytes_scanned += sort_bytes_scanned(c.sweep.passes, pl.rows_scored, c.s->dim, c.d->metric);
+}
+
+// One SLICE of the sort path: the (row, query) pairs of `pl` — at most 2^30 of them (run_large_k cuts longer plans) — scored,
+// listed, sorted; lists[g] = the slice's best k_eff hits of result group g, in result order.  gate_in (may be null): per query,
+// a score ordinal that every pair worth listing must reach — the k-th best of the same group over EARLIER slices, a lower bound
+// of the final k-th best (ties included: the merge decides among them).
+static int large_k_slice(ott_store* s, const float* queries, uint32_t nq, const ott_query_desc* d, bool perq, const RunPlan& pl, uint64_t k_eff,
+                         const uint64_t* d_mask, uint64_t mask_bits, std::vector<std::vector<ott_hit>>& lists, ott_stats& st,
+                         const std::vector<uint32_t>* gate_in) {
+    const uint64_t cap = pl.rows_scored * nq;
+    if (cap > (1ull << 30)) return fail(OTT_ERR_INVALID, "large_k_slice: internal error (a slice of more than 2^30 pairs)");
+    int rc;
+    if ((rc = ensure_pairs(s, cap))) return rc;
+    if ((rc = s->l_cursor.ensure(8))) return rc;
+    // which kernel sweeps: decided on the whole plan (the two phases' sub-plans are smaller still)
+    const std::vector<uint32_t> prefix = tile_prefix(pl, 64);
+    SortCtx c(s, nq, s->n - 1 + s->cur_tie_off, (uint32_t)s->opt.mfma_abl, d->take == OTT_TAKE_MAX, tie_base(s));  // (the key's row field is row + tie_off)
+    c.queries = queries;
+    c.d = d;
+    c.d_mask = d_mask;
+    c.mask_bits = mask_bits;
+    c.cap = cap;
+    c.sweep = sweep_shape(nq, s->dimq, prefix.back(), s->opt.exact_small);
+    if (small_path_ok(cap, nq, perq, c.rbits, query_bits(nq), s->opt.small_sort, gate_in != nullptr)) rc = small_slice(c, perq, pl, prefix, k_eff, lists);
+    else rc = radix_slice(c, perq, pl, k_eff, lists, gate_in);
+    if (rc == OTT_OK) add_sort_stats(c, pl, st);
+    return rc;
 }
 
 // The sort path (k > 512, the reference's default take = every row: src/vec.rs:213-219) over ANY number of (row, query) pairs.
@@ -998,8 +933,7 @@ int run_large_k(ott_store* s, const float* queries, uint32_t nq, const ott_query
     const uint64_t slice_pairs = (s->opt.force_fallback & 64) ? (1ull << 14) : (1ull << 29);
     const uint64_t cap = pl.rows_scored * (uint64_t)nq;
     if (cap <= slice_pairs) return large_k_slice(s, queries, nq, d, perq, pl, k_eff, d_mask, mask_bits, lists, st, nullptr);
-    uint64_t slice_rows = (slice_pairs / nq) & ~63ull;
-    if (slice_rows < 64) slice_rows = 64;
+    const uint64_t rows_per_slice = slice_rows(nq, slice_pairs);
     const uint32_t groups = perq ? nq : 1u;
     const bool tmax = d->take == OTT_TAKE_MAX;
     const CanonLess less{tmax, s->cur_tie_sh, tie_base(s)};
@@ -1016,7 +950,7 @@ int run_large_k(ott_store* s, const float* queries, uint32_t nq, const ott_query
     RunPlan rest = pl;
     while (rest.rows_scored) {
         RunPlan head, tail;
-        split_plan(rest, slice_rows, head, tail);
+        split_plan(rest, rows_per_slice, head, tail);
         head.total_chunks = pl.total_chunks;
         head.evaluated = pl.evaluated;
         part.clear();
@@ -1053,75 +987,24 @@ int run_large_k(ott_store* s, const float* queries, uint32_t nq, const ott_query
 // Grouped search above the register lists (ott_group.hip: k_eff > 512, which is what a plan without take() gives).  The compact
 // kernel left the non-empty table slots of every query as (key, query) pairs in (l_keysA, l_qA), in no order; this is the sort
 // path's own last step on them — the same radix sort, plan of a per-query result (key descending, then the query), the groups'
-// extents without atomics, hits_from_sorted*.  Canonical order only (a grouped query has no other).
+// extents without atomics, a launch and a copy per group.  Canonical order only (a grouped query has no other).  Not the one-block
+// transport: it would write d_misc and h_hits, which the grouped caller may still be using.
 int ensure_group_pairs(ott_store* s, uint64_t cap) {
-    int rc;
-    if ((rc = s->l_keysA.ensure(cap * 8))) return rc;
-    if ((rc = s->l_keysB.ensure(cap * 8))) return rc;
-    if ((rc = s->l_qA.ensure(cap * 4))) return rc;
-    if ((rc = s->l_qB.ensure(cap * 4))) return rc;
-    return s->l_tmp.ensure(rs_tmp_bytes(cap));
+    const int rc = ensure_pairs(s, cap);
+    return rc ? rc : s->l_tmp.ensure(rs_tmp_bytes(cap));
 }
 
 int sort_group_pairs(ott_store* s, uint64_t n, uint32_t nq, bool take_max, uint64_t k, std::vector<std::vector<ott_hit>>& lists, uint64_t id_span) {
     int rc;
     lists.assign(nq, {});
     if (n == 0) return OTT_OK;
-    uint64_t* kA = (uint64_t*)s->l_keysA.p;
-    uint64_t* kB = (uint64_t*)s->l_keysB.p;
-    uint32_t* qA = (uint32_t*)s->l_qA.p;
-    uint32_t* qB = (uint32_t*)s->l_qB.p;
-    uint32_t qbits = 0, rbits = 1;
-    while (nq > 1 && qbits < 32 && ((uint64_t)(nq - 1) >> qbits) != 0) qbits++;
-    const uint64_t span = id_span ? id_span : s->n;
-    while (rbits < 32 && ((span - 1) >> rbits) != 0) rbits++;
-    RsPlan plan;
-    memset(&plan, 0, sizeof(plan));
-    rs_add_digits(plan, 0, 0, rbits, true);   // ~row: the lower row first among equal scores
-    rs_add_digits(plan, 0, 32, 64, true);     // the score ordinal
-    rs_add_digits(plan, 1, 0, qbits, false);  // grouped by query
-    bool in_A = true;
-    if ((rc = radix_sort_plan(s->stream, kA, qA, kB, qB, n, plan, s->l_tmp.p, s->n_cu, &in_A))) return rc;
-    if (!in_A) {
-        std::swap(kA, kB);
-        std::swap(qA, qB);
-    }
-    // extents of the query groups
-    std::vector<uint32_t> start(nq, 0u);
-    if (nq > 1) {
-        if ((rc = s->l_hist.ensure((size_t)nq * 4))) return rc;
-        OTT_HIP(hipMemsetAsync(s->l_hist.p, 0xFF, (size_t)nq * 4, s->stream));
-        hipLaunchKernelGGL(group_start_kernel, dim3((uint32_t)s->n_cu * 4), dim3(256), 0, s->stream, (const uint32_t*)qA, n, (uint32_t*)s->l_hist.p);
-        OTT_HIP(hipGetLastError());
-        OTT_HIP(hipMemcpyAsync(start.data(), s->l_hist.p, (size_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
-        OTT_HIP(hipStreamSynchronize(s->stream));
-    }
-    std::vector<uint64_t> first(nq, 0), count(nq, 0);
-    uint64_t next = n, total = 0;
-    for (uint32_t q = nq; q-- > 0;) {
-        if (start[q] == 0xFFFFFFFFu) continue;
-        first[q] = start[q];
-        count[q] = std::min<uint64_t>(next - start[q], k);
-        next = start[q];
-        total += count[q];
-    }
-    if ((rc = s->d_hits.ensure((size_t)(total ? total : 1) * sizeof(ott_hit)))) return rc;
-    uint64_t o = 0;
-    for (uint32_t q = 0; q < nq; q++) {
-        if (!count[q]) continue;
-        hipLaunchKernelGGL(hits_from_sorted_kernel, dim3((uint32_t)((count[q] + 255) / 256)), dim3(256), 0, s->stream, (const uint64_t*)kA, (const uint32_t*)qA, first[q],
-                           count[q], take_max ? 1u : 0u, s->base_offset, (ott_hit*)s->d_hits.p + o);
-        OTT_HIP(hipGetLastError());
-        o += count[q];
-    }
-    o = 0;
-    for (uint32_t q = 0; q < nq; q++) {
-        lists[q].resize((size_t)count[q]);
-        if (count[q]) OTT_HIP(hipMemcpyAsync(lists[q].data(), (ott_hit*)s->d_hits.p + o, (size_t)count[q] * sizeof(ott_hit), hipMemcpyDeviceToHost, s->stream));
-        o += count[q];
-    }
-    OTT_HIP(hipStreamSynchronize(s->stream));
-    return OTT_OK;
+    SortCtx c(s, nq, (id_span ? id_span : s->n) - 1, 0u, take_max, s->base_offset);
+    if ((rc = sort_pairs(c, n, SORT_BY_QUERY))) return rc;
+    std::vector<uint64_t> first, count;
+    uint64_t total = 0;
+    if ((rc = fetch_group_extents(c, n, k, nq > 1, first, count, &total))) return rc;
+    if ((rc = emit_per_group(c, first, count))) return rc;
+    return fetch_per_group(s, count, lists);
 }
 
 }  // namespace ott

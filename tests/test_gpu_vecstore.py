@@ -753,3 +753,94 @@ def test_sort_path_in_row_slices_with_carried_gates(oracle, tie):
             assert np.array_equal(got["index"], ref["index"]) and np.array_equal(got["score"].view(np.uint32), ref["score"].view(np.uint32))
         one.close()
         cut.close()
+
+
+def test_sort_path_branches_report_their_documented_sweeps(oracle):
+    """Which branch a slice of the sort path (k > 512) takes, pinned through what it reports: the smallest shapes that reach the
+    rank sort, the radix sort with its one-launch and its per-group emission, the streaming sweep, the two-phase prefix, row
+    slices and the pinned pieces.  Hits are the oracle's bit for bit; `passes` and `bytes_scanned` equal the figures written out
+    below, from the documented rules (ott_sort_plan.h is not consulted):
+      passes of one sweep = ceil(nq / t8) under rows8 (t8 = the power of two that holds nq, at most 8: stores of up to 1024 tiles
+      of 64 rows unless exact_small = 0), else ceil(nq / 4), or nq for one query; the two phases split ONE sweep;
+      bytes_scanned = passes x rows scored x (4 dim, + 4 for cosine's inverse norm); a sliced query adds up its slices."""
+    rng = np.random.default_rng(1905)
+
+    def check(store, rows, queries, metric, k, perq, passes, nbytes, where):
+        plan = store.query(queries, metric)
+        if k is not None:
+            plan = plan.take(k)
+        if perq:
+            plan = plan.per_query()
+        rq = plan.with_path(Path.Exact).resolve()
+        hits, counts, st = store._run(rq)
+        if perq:
+            per = [oracle.vec_query(rows, queries[q], rq.metric, rq.take, rq.k, ties=oracle.TIES_CANONICAL) for q in range(len(queries))]
+            for q, h in enumerate(per):
+                h["query"] = q
+            assert [int(c) for c in counts] == [len(h) for h in per], where
+            ref = np.concatenate(per)
+        else:
+            ref = oracle_collect(oracle, rq, rows, oracle.TIES_CANONICAL)
+        assert_bit_exact(hits, ref)
+        assert st["passes"] == passes, (where, st["passes"], passes)
+        assert st["bytes_scanned"] == nbytes, (where, st["bytes_scanned"], nbytes)
+
+    def store_of(rows, **options):
+        store = VecStore(rows.shape[1])
+        for name, v in options.items():
+            store.set_option(name, v)
+        store.add_vectors(rows)
+        return store
+
+    C, D, E = Metric.Cosine, Metric.DotProduct, Metric.Euclidean
+    # 10 000 x 24, one query, the default take: rank sort, rows8, the query rides in the kernel arguments.  157 tiles, one pass
+    rows = rng.uniform(-1, 1, (10_000, 24)).astype(np.float32)
+    q = rng.uniform(-1, 1, (1, 24)).astype(np.float32)
+    store = store_of(rows)
+    for metric, nbytes in ((C, 1_000_000), (D, 960_000), (E, 960_000)):  # 10 000 x (96 + 4), 10 000 x 96
+        check(store, rows, q, metric, None, False, 1, nbytes, ("default take", metric.name))
+    store.close()
+    # 3000 x 7, five queries (15 000 pairs), merged take(600) and per query take(900): rank sort (small_sort = 1) or radix sort
+    # (0; per query: five groups, so ONE launch emits them; the prefix floor of 4096 rows is more than the store: one phase).
+    # rows8 carries the five queries in one pass; exact_small = 0: the streaming kernel, four queries at a time, two passes
+    rows = rng.integers(-2, 3, (3000, 7)).astype(np.float32)
+    q = rng.integers(-2, 3, (5, 7)).astype(np.float32)
+    q[np.all(q == 0, axis=1)] = 1.0
+    for small_sort, exact_small in ((1, -1), (0, -1), (1, 0), (0, 0)):
+        store = store_of(rows, small_sort=small_sort, exact_small=exact_small)
+        passes = 1 if exact_small == -1 else 2
+        for metric, per_pass in ((C, 96_000), (D, 84_000)):  # 3000 x (28 + 4), 3000 x 28
+            for k, perq in ((600, False), (900, True)):
+                check(store, rows, q, metric, k, perq, passes, passes * per_pass, ("15000 pairs", small_sort, exact_small, metric.name, k, perq))
+        store.close()
+    # 90 000 x 16, three queries, k = 600: 1407 tiles, so the streaming kernel, three queries in one pass; two phases (a prefix of
+    # 4288 rows merged, 7360 per query), which count as ONE sweep over the 90 000 rows
+    rows = rng.uniform(-1, 1, (90_000, 16)).astype(np.float32)
+    q = rng.uniform(-1, 1, (3, 16)).astype(np.float32)
+    store = store_of(rows)
+    for metric, nbytes in ((C, 6_120_000), (D, 5_760_000)):  # 90 000 x (64 + 4), 90 000 x 64
+        for perq in (False, True):
+            check(store, rows, q, metric, 600, perq, 1, nbytes, ("two phases", metric.name, perq))
+    store.close()
+    # 20 011 x 24, one query, k = 2000, cut at 2^14 pairs: a slice of 16 384 rows (rank sort) and a gated one of 3627 (radix sort),
+    # each one rows8 pass over its own rows
+    rows = rng.uniform(-1, 1, (20_011, 24)).astype(np.float32)
+    q = rng.uniform(-1, 1, (1, 24)).astype(np.float32)
+    store = store_of(rows, force_fallback=64)
+    for metric, nbytes in ((C, 2_001_100), (D, 1_921_056)):  # (16 384 + 3627) x (96 + 4), x 96
+        check(store, rows, q, metric, 2000, False, 2, nbytes, ("two slices", metric.name))
+    store.close()
+    # 300 000 x 8, one query, the default take in the reference's tie order: 300 000 hits (more than 256k) through the pinned pieces
+    # and the lists — the caller's buffer is not offered there.  4688 tiles: the streaming kernel, one pass, one phase (k = every pair)
+    rows = rng.integers(-3, 4, (300_000, 8)).astype(np.float32)
+    q = rng.integers(-2, 3, (1, 8)).astype(np.float32)
+    q[np.all(q == 0, axis=1)] = 1.0
+    store = store_of(rows)
+    store.set_tie_order("reference")
+    rq = store.query(q, D).with_path(Path.Exact).resolve()
+    got, _, st = store._run(rq)
+    lit = oracle_collect(oracle, rq, rows, oracle.TIES_LITERAL)
+    assert got.size == 300_000 and np.array_equal(got["score"].view(np.uint32), lit["score"].view(np.uint32))
+    assert sorted(zip(got["index"].tolist(), got["query"].tolist())) == sorted(zip(lit["index"].tolist(), lit["query"].tolist()))
+    assert st["passes"] == 1 and st["bytes_scanned"] == 9_600_000, st  # 300 000 x 32
+    store.close()
