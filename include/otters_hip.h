@@ -73,9 +73,9 @@ typedef enum { OTT_MODE_MERGED = 0, OTT_MODE_PER_QUERY = 1 } ott_mode;
 /* Which scoring kernel family runs.  EXACT returns exactly what scoring every row in the reference's summation order returns
  * (one pass over the f32 rows per 4 queries); a single query may skip the last dims of rows that provably miss the top-k
  * (option "exact_prune": a bound on the rest of the dot product against a seed's k-th best).  That bound may use a per-row
- * sketch of the row's last dims (options "exact_sketch", "exact_sketch_bits": three bits per dim of the last 5/8 of the row, a
- * half cell width and a remainder norm — 192 B beside a 3072-B row at dim 768, 1/16 of the store's HBM; or one sign bit per dim
- * of the last quarter, 32 B — made once when rows are appended and valid for every later query): per-row metadata of the same kind as the inverse norm, not a plane a query could be answered from — every returned row
+ * sketch of the row's last dims (options "exact_sketch", "exact_sketch_bits": four bits per dim of everything behind the row's first
+ * 32 dims, a half cell width and a remainder norm — 384 B beside a 3072-B row at dim 768, 1/8 of the store's HBM; or three bits per
+ * dim of the last 5/8 of the row, 192 B; or one sign bit per dim of the last quarter, 32 B — made once when rows are appended and valid for every later query): per-row metadata of the same kind as the inverse norm, not a plane a query could be answered from — every returned row
  * is still finished over all of its f32 dims in the reference's summation order.  MFMA is the certified cascade, cosine / Euclidean / dot, k <= 484: candidate passes over compact copies of the corpus
  * — an int8 plane first (k <= 128: a quarter of the f32 bytes; batches on the matrix cores, a single cosine / dot query as a
  * streaming sweep), a 16-bit hi plane for what that cannot certify, split bf16 behind it — every candidate
@@ -296,10 +296,12 @@ int ott_store_batch_ready(const ott_store* s);
  *   what the two leave out; 32 B per row at dim 768, computed behind the inverse norms on every append — and the sweep then
  *   stops a row after three quarters of its dims instead of seven eighths.  Set it before rows are appended: switched on later,
  *   the sketch is made at the next append; a store without one takes the 7/8 form),
- *   "exact_sketch_bits" (3, the default / 1: the sketch's form, read when the store makes its first line.  3 = a three-bit code per
- *   dim of the last 5/8 of the stages, a half cell width and the remainder norm: 192 B per row at dim 768, 1/16 of the row bytes —
- *   1.92 GB of HBM beside a 30.7-GB store of 10M rows — and the sweep stops a row after three eighths of its dims; 1 = the sign
- *   sketch above, 32 B per row),
+ *   "exact_sketch_bits" (4, the default / 3 / 1: the sketch's form, read when the store makes its first line.  4 = a four-bit code per
+ *   dim of every 32-dim stage but the first, a half cell width and the remainder norm: 384 B per row at dim 768, 1/8 of the row
+ *   bytes — 3.84 GB of HBM beside a 30.7-GB store of 10M rows, and nearly two reads of the row when it is appended — and the sweep
+ *   stops a row after its first 32 dims; 3 = a three-bit code per dim of the last 5/8 of the stages: 192 B per row at dim 768, 1/16
+ *   of the row bytes, 1.92 GB at 10M rows, and the sweep stops a row after three eighths of its dims; 1 = the sign sketch above,
+ *   32 B per row),
  *   "id_gather" (-1 auto: lists of up to 10000 ids / 0 never / 1 wherever eligible: whether ott_query_ids scores the listed rows with the gather kernel or
  *   turns the list into a row mask and takes ott_query's paths),
  *   "large_k_from" (k above which host-output queries take the sort path; 0 = default: 512 for one query or a small store,

@@ -170,6 +170,10 @@ __global__ void sum_counts_kernel(const uint64_t* counts, uint32_t n, uint64_t* 
     if (threadIdx.x == 0) *out = t;
 }
 
+// the large-store seed of the pruned sweep's wide sketch forms: rows / 32 (run_exact).  Experiment builds: -DOTT_X_SEED_DIV=64
+#ifndef OTT_X_SEED_DIV
+#define OTT_X_SEED_DIV 32
+#endif
 // EXACT path.  queries: host [nq*dim].  Results: per group (1 for merged, nq for per-query) on the
 // host in `lists`.  `perq` selects the grouping.  If dev_copy != nullptr (merged only) the merged
 // list is also left in device memory at s->d_hits (KS slots, sentinel padded) for ott_query_device.
@@ -226,7 +230,7 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
     // rest, which skips the last stages (from c, 7/8 of them) of every row whose score bound misses it.  Automatic from 2^20 rows
     // and 8 stages (dim >= 225).
     // A store that keeps a tail sketch for every row (option exact_sketch) takes the sketch form in the store's own width (option
-    // exact_sketch_bits): the checkpoint is the sketch's first stage, 3/8 of the stages at three bits per dim, 3/4 at one.
+    // exact_sketch_bits): the checkpoint is the sketch's first stage, stage 1 at four bits per dim, 3/8 of the stages at three, 3/4 at one.
     uint32_t prune_c = 0;
     bool prune_sk = false;
     RunPlan plA, plB;
@@ -237,7 +241,7 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
         uint32_t c = nst * 7 / 8;
         while (c > 0 && c * 32 > s->dim - s->dim % 8) c--;  // the prefix holds whole chunks of eight only (no remainder term yet)
         if (s->opt.exact_sketch != 0 && s->d_sketch != nullptr && s->sk_n >= s->n &&
-            s->sk_words <= (s->sk_bits == 3 ? OTT_SKETCH_MAX_WORDS : OTT_SKETCH1_MAX_WORDS)) {
+            s->sk_words <= (s->sk_bits == 4 ? OTT_SKETCH4_MAX_WORDS : s->sk_bits == 3 ? OTT_SKETCH_MAX_WORDS : OTT_SKETCH1_MAX_WORDS)) {
             const uint32_t cs = s->sk_stage0;
             if (cs >= 1 && cs < nst && cs * 32 <= s->dim - s->dim % 8) {
                 c = cs;
@@ -246,13 +250,13 @@ int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_d
         }
         const bool worth = s->opt.exact_prune == 1 || (nst >= 8 && pl.rows_scored >= (1ull << 20));
         if (worth && c >= 1 && c < nst) {
-            // The seed: a tenth of the rows.  With the three-bit sketch and k <= 64, once that is more than 131072 rows: a
+            // The seed: a tenth of the rows.  With the three- or four-bit sketch and k <= 64, once that is more than 131072 rows: a
             // thirty-second of them, never fewer than 131072 (continuous at 1.31M rows; 10M rows: 312 512 rows read in full instead of
             // 1M, 10M x 768 top-10 2.862 -> 2.753 ms).  A smaller seed gives a lower gate; the wide sketch loses few rows to that, but a
             // longer list's k-th best sits deeper in the seed (k = 500 at 10M x 768: 3.54 -> 3.78 ms with the small seed), and the
             // other forms save less per seed row (their checkpoint is at 3/4 or 7/8 of the row): those keep the tenth
             uint64_t seed = pl.rows_scored / 10;
-            if (prune_sk && s->sk_bits == 3 && E == 1 && seed > 131072) seed = pl.rows_scored / 32 > 131072 ? pl.rows_scored / 32 : 131072;
+            if (prune_sk && s->sk_bits >= 3 && E == 1 && seed > 131072) seed = pl.rows_scored / OTT_X_SEED_DIV > 131072 ? pl.rows_scored / OTT_X_SEED_DIV : 131072;
             seed = (seed + 63) & ~63ull;
             if (seed < 64) seed = 64;
             split_plan(pl, seed, plA, plB);

@@ -112,11 +112,15 @@ __device__ __forceinline__ void exact_glds16(const char* sbase, uint32_t voff, u
 // flight then, so the first eight pieces land in the row staging registers, the others are asked for behind the loop and arrive
 // while the first are decoded (lane = row: the 64 lines of a tile are one contiguous block).  Per dim: a signed field extract,
 // kappa = 2 code + 1, a convert and one fma into D; then prune_score_bound_sketchb with kmax = 7.
+// SK = 4: the four-bit sketch of every stage but the first, so the checkpoint is behind stage 0.  A line is a header piece and one
+// 16-B piece per sketched stage, up to 28.  The 64 lines of a tile are fetched as the row stages are: eight pieces of every line per
+// round, coalesced, through the staging registers into the stage buffer, the next round in flight while the lane decodes its own
+// line's pieces out of LDS.  The same four operations per dim; kmax = 15.
 template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false, int SK = 0>
 __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) {
     static_assert(!I8 || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL), "the int8 sweep takes one query, cosine / dot, merged");
     static_assert(!PRUNE || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL && !I8), "the pruned sweep takes one query, cosine / dot, merged");
-    static_assert((SK == 0 || PRUNE) && (SK == 0 || SK == 1 || SK == 3), "the sketch is the pruned sweep's: none, one bit or three bits per dim");
+    static_assert((SK == 0 || PRUNE) && (SK == 0 || SK == 1 || SK == 3 || SK == 4), "the sketch is the pruned sweep's: none, one, three or four bits per dim");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -311,10 +315,10 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
         // SK: the row's sketch line [a | rho | sign words], fetched now like the inverse norm (non-temporal: read once per sweep)
         typedef uint32_t v4u __attribute__((ext_vector_type(4)));
         [[maybe_unused]] uint32_t skl[2 + SK_MAXW];
-        // SK = 3: the gate is known before the stages (the wave's list changes only when queued rows are finished): no line is fetched
+        // SK >= 3: the gate is known before the stages (the wave's list changes only when queued rows are finished): no line is fetched
         // while it is open
         [[maybe_unused]] uint32_t gate3 = 0;
-        if constexpr (SK == 3) {
+        if constexpr (SK >= 3) {
             gate3 = theta;
             const uint32_t own = (uint32_t)(tk[0] >> 32);
             if (own > gate3) gate3 = own;
@@ -399,6 +403,22 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             }
         };
 
+        // SK = 4: the tile's 64 sketch lines are one contiguous block, fetched like a row stage — round f is pieces 8 f .. 8 f + 7 of
+        // every line, 8 lines x 128 B per wave instruction, through the staging registers and the stage buffer to lane = row.  (A lane
+        // that fetches its own line piece by piece asks L2 for 64 different lines per instruction, and for each line eight times: that
+        // pattern alone took as long as the whole launch, benchmarks/cpp/prefix_stream.hip.)  A piece index is clamped to the line's
+        // last piece and a row past the tile's end to its last row: nothing outside the tile's own lines is read
+        auto load_line = [&](uint32_t f) {
+            const uint32_t np = p.sk_pitch >> 2;
+            const uint32_t pc = (8 * f + (uint32_t)lslot < np) ? 8 * f + (uint32_t)lslot : np - 1;
+            const uint32_t* lb = p.prune_sketch + row0 * (uint64_t)p.sk_pitch + 4 * pc;
+#pragma unroll
+            for (int m = 0; m < 8; m++) {
+                const uint32_t row = 8 * m + lrow;
+                R[m] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(lb + (row < cnt ? row : cnt - 1) * p.sk_pitch));
+            }
+        };
+
         if constexpr (SMALL) {
             for (uint32_t s = 0; s < (uint32_t)(SMALL_RING - 1) && s < nstages; s++) dma_stage(s);
         } else {
@@ -434,6 +454,8 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                 wave_sync();
                 if (s + 1 < s_end) {
                     load_stage(s + 1);
+                } else if constexpr (SK == 4) {
+                    if (gate3 != 0) load_line(0);  // the first round of the tile's lines into the idle staging registers
                 } else if constexpr (SK == 3) {
                     // the row's sketch line into the idle staging registers: pieces 0 .. 7, clamped to the line's last piece (a load
                     // past it would leave the buffer behind the store's last row); lanes past the tile's end read its last row's
@@ -517,9 +539,49 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             uint32_t gate = theta;
             const uint32_t own = (uint32_t)(tk[0] >> 32);
             if (own > gate) gate = own;
-            if constexpr (SK == 3) gate = gate3;  // the gate the line was fetched for: the staging registers hold a line only then
+            if constexpr (SK >= 3) gate = gate3;  // the gate the line was fetched for: the staging registers hold a line only then
             bool keep = valid;
-            if constexpr (SK == 3) {
+            if constexpr (SK == 4) {
+                if (gate != 0) {  // (wave-uniform; round 0 of the lines is in R, or on its way)
+                    const uint32_t np = p.sk_pitch >> 2;  // [a | rho | 0 | 0], then one piece per sketched stage
+                    float D = 0.0f, sk_a = 0.0f, sk_rho = __builtin_inff();
+                    for (uint32_t f = 0; 8 * f < np; f++) {
+                        // round f to the stage buffer (the row stages' swizzle); the next round is in flight while this one is decoded
+#pragma unroll
+                        for (int m = 0; m < 8; m++) {
+                            const int row = 8 * m + lrow;
+                            const v4f v = R[m];
+                            *reinterpret_cast<float4*>(st + row * KC + ((lslot ^ ((row >> 1) & 7)) << 2)) = make_float4(v.x, v.y, v.z, v.w);
+                        }
+                        wave_sync();
+                        if (8 * (f + 1) < np) load_line(f + 1);
+                        for (uint32_t j = 0; j < 8 && 8 * f + j < np; j++) {  // piece 8 f + j of the lane's own line
+                            const float4 w4 = *reinterpret_cast<const float4*>(st + lane * KC + (((int)j ^ sw) << 2));
+                            const uint32_t piece = 8 * f + j;
+                            if (piece == 0) {
+                                sk_a = w4.x;
+                                sk_rho = w4.y;
+                                continue;
+                            }
+                            const uint32_t sj = p.sk_stage0 + piece - 1u;  // piece i >= 1 holds sketched stage i - 1: eight fields per word
+                            if (sj >= p.prune_stage && sj < nstages) {
+                                const uint32_t w[4] = {__float_as_uint(w4.x), __float_as_uint(w4.y), __float_as_uint(w4.z), __float_as_uint(w4.w)};
+#pragma unroll
+                                for (int b = 0; b < 32; b++) {
+                                    const int code = (int)(w[b >> 3] << (28 - 4 * (b & 7))) >> 28;
+                                    D = fmaf((float)(2 * code + 1), Q[sj * KC + b], D);
+                                }
+                            }
+                        }
+                        wave_sync();
+                    }
+                    if (valid) {
+                        const float b = prune_score_bound_sketchb(acc[0], vinv, sk_a, sk_rho, D, 15.0, p.prune_stage * KC, p.dim, p.prune_qt, p.prune_q1,
+                                                                  p.prune_qn, qinv[0], p.metric == OTT_METRIC_COSINE, take_max);
+                        keep = !(b == b && ord_of(b, take_max) < gate);  // (NaN: no bound, the row is finished)
+                    }
+                }
+            } else if constexpr (SK == 3) {
                 if (gate != 0) {  // (wave-uniform; the line is in R)
                     v4f X[SK3_XP];
 #pragma unroll
@@ -1505,13 +1567,13 @@ template <int MK, int NQ, int E, bool PERQ>
 static int launch_one(ott_store* s, const ExactParams& p, int grid) {
     if constexpr (MK == MK_DOT && NQ == 1 && !PERQ) {
         if (p.prune_stage != 0) {
-            const uint32_t sk = p.prune_sketch != nullptr ? p.sk_bits : 0u;  // the sketch form: the store keeps a tail sketch of 1 or 3 bits per dim
-            if (sk != 0 && sk != 1 && sk != 3) return fail(OTT_ERR_INVALID, "launch_exact: a tail sketch has one or three bits per dim");
+            const uint32_t sk = p.prune_sketch != nullptr ? p.sk_bits : 0u;  // the sketch form: the store keeps a tail sketch of 1, 3 or 4 bits per dim
+            if (sk != 0 && sk != 1 && sk != 3 && sk != 4) return fail(OTT_ERR_INVALID, "launch_exact: a tail sketch has one, three or four bits per dim");
             if constexpr (E == 1) {
                 if (p.k > 16)  // (see BLK)
-                    return sk == 3 ? launch_prune<1, true, 3>(s, p, grid) : sk == 1 ? launch_prune<1, true, 1>(s, p, grid) : launch_prune<1, true, 0>(s, p, grid);
+                    return sk == 4 ? launch_prune<1, true, 4>(s, p, grid) : sk == 3 ? launch_prune<1, true, 3>(s, p, grid) : sk == 1 ? launch_prune<1, true, 1>(s, p, grid) : launch_prune<1, true, 0>(s, p, grid);
             }
-            return sk == 3 ? launch_prune<E, (E > 1), 3>(s, p, grid) : sk == 1 ? launch_prune<E, (E > 1), 1>(s, p, grid) : launch_prune<E, (E > 1), 0>(s, p, grid);
+            return sk == 4 ? launch_prune<E, (E > 1), 4>(s, p, grid) : sk == 3 ? launch_prune<E, (E > 1), 3>(s, p, grid) : sk == 1 ? launch_prune<E, (E > 1), 1>(s, p, grid) : launch_prune<E, (E > 1), 0>(s, p, grid);
         }
     }
     if (p.prune_stage != 0) return fail(OTT_ERR_INVALID, "launch_exact: the pruned sweep takes one query, cosine / dot, merged");

@@ -103,9 +103,10 @@ struct Options {
                                   // stages, a mean magnitude and a remainder norm, ~1 % of the row bytes, made when rows are appended): -1 =
                                   // automatic (stores of 8 stages and more, dim >= 225), 0 = never, 1 = always.  A store that keeps one
                                   // stops rows at 3/4 of the stages instead of 7/8
-    int exact_sketch_bits = 3;    // the sketch's form, read when the store makes its first line: 3 = a three-bit code per dim of the last 5/8 of
-                                  // the stages (192 B per row at dim 768, 1/16 of the row bytes; rows stop at 3/8 of the stages), 1 = the sign
-                                  // sketch described above
+    int exact_sketch_bits = 4;    // the sketch's form, read when the store makes its first line: 4 = a four-bit code per dim of every stage but
+                                  // the first (384 B per row at dim 768, 1/8 of the row bytes; rows stop after their first stage), 3 = a
+                                  // three-bit code per dim of the last 5/8 of the stages (192 B per row at dim 768, 1/16 of the row bytes;
+                                  // rows stop at 3/8 of the stages), 1 = the sign sketch described above
     int force_fallback = 0;       // TESTS: bit mask of code paths the library otherwise takes only in rare conditions, forced on so that the
                                   // suite and the option fuzz hold them to the oracle: 1 = block lists merged by insertion (merge_kernel: the
                                   // rank merge's own fallback when a plateau overflows its buffer or there are > 4096 lists), 2 = k <= 64
@@ -259,7 +260,7 @@ struct ott_store {
     uint32_t* d_sketch = nullptr;
     uint64_t sk_n = 0;
     uint32_t sk_words = 0, sk_pitch = 0, sk_stage0 = 0;  // code words per row, line pitch in words, first sketched stage
-    uint32_t sk_bits = 0;                                // bits per sketched dim of the lines that are there (1 or 3)
+    uint32_t sk_bits = 0;                                // bits per sketched dim of the lines that are there (1, 3 or 4)
     uint8_t* d_flag = nullptr;  // [cap] 1 = row norm is inf / NaN / > 1e18 / tiny but non-zero / underflowed (always re-scored exactly by the MFMA path)
     ott::PlaneSet planes;       // the cascade's compact copies of the corpus (owner store only: contexts reach them through `owner`)
     ott::CascadeState cascade;  // the batch cascade's back-off state (ott_policy.h), shared by the store's contexts: read through the owner
@@ -538,6 +539,8 @@ constexpr uint32_t OTT_QEMB_MAX = 896;
 // quarter at most 7 words; a store with more takes the 7/8 form.
 constexpr uint32_t OTT_SKETCH_MAX_WORDS = 54;
 constexpr uint32_t OTT_SKETCH1_MAX_WORDS = 10;  // the sign form keeps its words in registers across the stages: three 16-B loads
+// the four-bit form: up to 27 of the 28 stages sketched, four words each (a line of up to 28 16-B pieces, streamed eight at a time)
+constexpr uint32_t OTT_SKETCH4_MAX_WORDS = 108;
 static_assert(sizeof(ExactParams) <= 4096, "kernel arguments are limited to 4 KB");
 
 int launch_exact(ott_store* s, const ExactParams& p, int nq_tile, int E, int grid);

@@ -196,16 +196,31 @@ OTT_PRUNE_HD inline float prune_score_bound_sketch(const float acc[8], float vin
 // inflated and rounded up exactly as in the sign form.  So a code on a cell boundary, or of a -0, may fall either way (host and
 // device need not agree), and any a >= 0 is a valid sketch.  A tail that holds a NaN or an inf, or whose rho leaves the f32 range:
 // a = 0, rho = +inf.
-// Layout of a line (u32 words): [a | rho | b words per sketched stage], the field of dim 32 s + i at bits b i .. b i + b - 1 of the
+// Layout of a line (u32 words): [a | rho | b words per sketched stage] (b = 4: two zero words first), the field of dim 32 s + i at bits b i .. b i + b - 1 of the
 // stage's b words taken as one little-endian string of 32 b bits; dims past `dim` hold code 0.  Pitch: whole 16-B lines.
-// The first sketched stage: the last quarter of the stages at b = 1, the last 5/8 (rounded up) at b > 1 — at least one stage stays
+// The first sketched stage: the last quarter of the stages at b = 1, the last 5/8 (rounded up) at b = 3 — at least one stage stays
 // in front (the prefix then holds whole chunks of eight: 32 c < dim for every c below the stage count).
+// b = 4 ("four bits per dim"): the same code with sixteen cells, in a layout of whole 16-B pieces — [a | rho | 0 | 0], then piece 1 + j
+// = the four words of sketched stage j, eight fields per word, none across a word (prune_sketchb_word0: the first code word; the
+// pitch, 4 S + 4 words, is what prune_sketch_pitch gives anyway).  At sixteen cells the remainder rho is small enough that the f32
+// prefix is the dearer part of a gated row (the byte model), so the sketch starts at stage 1: one stage of the row
+// in front (whole chunks of eight, as before), every other stage sketched.  Measured against a quarter and an eighth of the stages
+// in front (profiles/exact_sketch4/README.md); experiment builds get those with -DOTT_SK4_STAGE0_DIV=4 or 8.
+#ifndef OTT_SK4_STAGE0_DIV
+#define OTT_SK4_STAGE0_DIV 0
+#endif
 OTT_PRUNE_HD inline uint32_t prune_sketchb_stage0(uint32_t nst, uint32_t bits) {
     if (bits <= 1) return prune_sketch_stage0(nst);
+    if (bits == 4) {
+        const uint32_t div = (uint32_t)(OTT_SK4_STAGE0_DIV), c4 = div ? nst / (div ? div : 1u) : 1u;
+        return nst < 2 ? 0u : c4 < 1 ? 1u : c4;
+    }
     const uint32_t c = nst - (5 * nst + 7) / 8;
     return (c < 1 && nst >= 2) ? 1u : c;
 }
 OTT_PRUNE_HD inline uint32_t prune_sketchb_pitch(uint32_t n_stages, uint32_t bits) { return prune_sketch_pitch(n_stages * bits); }
+// the line word that holds the first code: behind a and rho, at b = 4 behind the whole first 16-B piece
+OTT_PRUNE_HD inline uint32_t prune_sketchb_word0(uint32_t bits) { return bits == 4 ? 4u : 2u; }
 
 // the code of dim i (0 .. 31) of a stage whose b words start at w
 OTT_PRUNE_HD inline int32_t prune_sketchb_code(const uint32_t* w, uint32_t i, uint32_t bits) {
@@ -278,7 +293,7 @@ OTT_PRUNE_HD inline void prune_sketchb_row(const float* v, uint32_t dim, uint32_
         const uint32_t vb = prune_f2u(v[i]);
         const int32_t code = bits > 1 ? prune_sketchb_quant(v[i], inv_delta, bits) : -(int32_t)(vb >> 31);
         const uint32_t pos = bits * ((i - first) & 31u), lo = pos & 31u;
-        uint32_t* w = line + 2 + bits * ((i - first) >> 5) + (pos >> 5);
+        uint32_t* w = line + prune_sketchb_word0(bits) + bits * ((i - first) >> 5) + (pos >> 5);
         const uint32_t f = (uint32_t)code & ((1u << bits) - 1u);
         w[0] |= f << lo;
         if (lo + bits > 32u) w[1] |= f >> (32u - lo);

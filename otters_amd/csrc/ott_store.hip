@@ -80,7 +80,7 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "small_sort") return tri(o.small_sort);
     if (n == "exact_prune") return tri(o.exact_prune);
     if (n == "exact_sketch") return tri(o.exact_sketch);
-    if (n == "exact_sketch_bits") { if (v != 1 && v != 3) return -1; o.exact_sketch_bits = (int)v; return 0; }
+    if (n == "exact_sketch_bits") { if (v != 1 && v != 3 && v != 4) return -1; o.exact_sketch_bits = (int)v; return 0; }
     if (n == "id_gather") return tri(o.id_gather);
 #ifdef OTT_MFMA_DEBUG_BUILD
     if (n == "maxsim_fold") return tri(o.maxsim_fold);
@@ -326,10 +326,11 @@ int update_min_pos_inv(ott_store* s, uint64_t first_row, uint64_t n_rows) {
 
 // The pruned sweep's tail sketch (ott_prune.h: prune_sketchb_row, the same sums in the same order).  Runs right behind
 // inv_norm_kernel for the same rows and reads their sketched stages only (the last quarter of the row at one bit per dim, the last
-// 5/8 at three), staged as there: a wave stages 64 rows x 128 B per step, coalesced, then lane = row walks its 32 dims out of LDS.
+// 5/8 at three, every stage but the first at four), staged as there: a wave stages 64 rows x 128 B per step, coalesced, then lane = row walks its 32 dims out of LDS.
 // BITS > 1: the cell width comes from the tail's largest magnitude, so the stages are walked twice — the maximum first, the codes
 // and the sums after it (a rule that needs one walk, the width from the row norm, clips an eighth of the dims of Gaussian rows).
 // A lane writes its line in 16-B pieces: the groups of four code words as they fill, [a | rho | word 0 | word 1] at the end.
+// BITS = 4: a stage's four code words are one piece, written as the stage ends; [a | rho | 0 | 0] at the end.
 template <int BITS>
 __global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restrict__ rows, uint32_t ld, uint32_t dim, uint64_t first, uint64_t n,
                                                            uint32_t stage0, uint32_t n_stages, uint32_t pitch, uint32_t* __restrict__ sketch) {
@@ -424,6 +425,9 @@ __global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restric
                     }
             }
             wave_fence();
+            if constexpr (BITS == 4) {  // piece 1 + j is this stage's four words
+                if (mine) line[1 + j] = v4u{w[0], w[1], w[2], w[3]};
+            } else {
 #pragma unroll
             for (int b = 0; b < BITS; b++) {
                 const uint32_t k = 2 + BITS * j + b, slot = k & 3;  // the word's place in the line
@@ -440,6 +444,7 @@ __global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restric
                         grp = v4u{0u, 0u, 0u, 0u};
                     }
                 }
+            }
             }
         }
         if constexpr (BITS == 1) a_in = prune_sketchb_mean(sums, dim > stage0 * NKC ? dim - stage0 * NKC : 0u);
@@ -484,7 +489,10 @@ static int update_sketch(ott_store* s, uint64_t first_row, uint64_t n_rows) {
     }
     const uint64_t lo = first_row < s->sk_n ? first_row : s->sk_n, hi = first_row + n_rows;
     const uint32_t blocks = grid_blocks((hi - lo + 63) / 64, 4, s->n_cu);  // a wave per 64 rows, as launch_inv_norms
-    if (s->sk_bits == 3)
+    if (s->sk_bits == 4)
+        hipLaunchKernelGGL(tail_sketch_kernel<4>, dim3(blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
+                           nst - s->sk_stage0, s->sk_pitch, s->d_sketch);
+    else if (s->sk_bits == 3)
         hipLaunchKernelGGL(tail_sketch_kernel<3>, dim3(blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
                            nst - s->sk_stage0, s->sk_pitch, s->d_sketch);
     else
@@ -547,6 +555,26 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
         OTT_HIP(hipStreamSynchronize(s->stream));
         planes_drop(s);
     }
+    if (e == hipErrorOutOfMemory && keep_sk) {
+        // The sketch lines are derived from the rows as well (an eighth of their bytes in the four-bit form): when old and new lines
+        // do not fit next to old and new rows, the planes go (if they have not), the rows move alone, and the lines are made again
+        // behind them.  One more attempt, and only for a store that keeps lines
+        if (planes_any(s)) {
+            OTT_HIP(hipStreamSynchronize(s->stream));
+            planes_drop(s);
+        }
+        e = hipMalloc((void**)&nrows, ncap * s->ld * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc((void**)&ninv, ncap * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc((void**)&nflag, ncap);
+        if (e != hipSuccess) {
+            if (nrows) (void)hipFree(nrows);
+            if (ninv) (void)hipFree(ninv);
+            if (nflag) (void)hipFree(nflag);
+            nrows = ninv = nullptr;
+            nflag = nullptr;
+            (void)hipGetLastError();
+        }
+    }
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? OTT_ERR_OOM : OTT_ERR_HIP, std::string("hipMalloc(store): ") + hipGetErrorString(e));
     if (s->n) {
         OTT_HIP(hipMemcpyAsync(nrows, s->d_rows, s->n * s->ld * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
@@ -571,6 +599,13 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
     if (!nsk) s->sk_n = 0;
     s->cap = ncap;
     planes_drop(s);  // rebuilt lazily at the new capacity
+    if (keep_sk && !nsk && s->n) {  // the lines did not move with the rows: made again, in the form they had
+        const int want = s->opt.exact_sketch_bits;
+        s->opt.exact_sketch_bits = (int)s->sk_bits;
+        const int rc = update_sketch(s, 0, s->n);
+        s->opt.exact_sketch_bits = want;
+        if (rc) return rc;
+    }
     return OTT_OK;
 }
 
