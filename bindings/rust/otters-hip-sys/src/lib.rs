@@ -188,6 +188,8 @@ extern "C" {
     pub fn ott_query_groups(s: *mut ott_store, d: *const ott_query_desc, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int;
     pub fn ott_query_groups_top(s: *mut ott_store, d: *const ott_query_desc, group_size: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, group_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // group_of_hit may be null
     pub fn ott_query_maxsim(s: *mut ott_store, d: *const ott_query_desc, out: *mut ott_hit, cap: u64, n_out: *mut u64, stats: *mut ott_stats) -> c_int;
+    pub fn ott_query_maxsim_groups(s: *mut ott_store, d: *const ott_query_desc, groups: *const c_void, n_groups_listed: u64, out: *mut ott_hit, cap: u64, n_out: *mut u64, stats: *mut ott_stats) -> c_int; // groups: n_groups_listed u32
+    pub fn ott_store_group_index_builds(s: *const ott_store) -> u64;
     pub fn ott_query_device(s: *mut ott_store, d: *const ott_query_desc, out_dev: *mut c_void, cap: u64, n_out_dev: *mut c_void, stats: *mut ott_stats) -> c_int;
     pub fn ott_store_sync(s: *mut ott_store) -> c_int;
     pub fn ott_store_stream(s: *mut ott_store) -> *mut c_void;

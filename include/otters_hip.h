@@ -304,6 +304,9 @@ int ott_store_batch_ready(const ott_store* s);
  *   32 B per row),
  *   "id_gather" (-1 auto: lists of up to 10000 ids / 0 never / 1 wherever eligible: whether ott_query_ids scores the listed rows with the gather kernel or
  *   turns the list into a row mask and takes ott_query's paths),
+ *   "group_gather" (-1 auto: lists whose groups hold up to 1000000 rows / 0 never / 1 wherever eligible: whether ott_query_maxsim_groups
+ *   scores the listed groups' rows with the gather kernel, through the store's group-to-rows index, or turns the list into a row mask
+ *   and runs ott_query_maxsim's sweep; environment preset OTT_GROUP_GATHER, as for every option),
  *   "large_k_from" (k above which host-output queries take the sort path; 0 = default: 512 for one query or a small store,
  *   128 for several queries on a large one), "small_sort" (0: results of up to 16384 (row, query) pairs with k > 512 through
  *   the radix sort instead of the rank sort), "mfma_f32" (batch path: one candidate pass on the f32 matrix pipe),
@@ -457,6 +460,36 @@ int ott_query_groups_top(ott_store* s, const ott_query_desc* d, uint32_t group_s
  * (OTT_ERR_UNSUPPORTED: the table holds all tokens at once), cap < k_eff (OTT_ERR_INVALID).  Takes the store shared, like
  * ott_query_groups (staged appends go first). */
 int ott_query_maxsim(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64_t cap, uint64_t* n_out, ott_stats* stats);
+
+/* MaxSim re-ranking (an extension; the second stage of a ColBERT / ColPali pipeline: a cheap first stage names the candidate
+ * documents, late interaction ranks only those): ott_query_maxsim over a LISTED set of groups.  groups points at n_groups_listed dense
+ * group ids (uint32_t, declared const void* as ott_store_set_groups' ids; each < ott_store_group_count), in any order, duplicates allowed.  The call returns exactly the hits of
+ * ott_query_maxsim for the same descriptor — the dense group id in `index`, the score bits of the sum, the order, query = 0 — with
+ * one more row mask: only rows whose group is listed are kept, ANDed with chunk_mask, the caller's row_mask or the evaluated device
+ * mask, and the live mask of deleted rows.  Everything ott_query_maxsim's contract says holds unchanged: four metrics, both takes,
+ * "best" in the total order, NaN pair scores dropped, a group needs a best for every token, the f32 sum in token order from
+ * best[0], a NaN sum drops the group, the filter applies to the sum, ties go to the lower group id whatever "tie_order" says.
+ * k_eff = min(k, number of DISTINCT listed groups); cap >= k_eff.  n_groups_listed == 0 is a valid query with no hits.
+ * The work follows the list, not the store.  The gather route walks only the listed groups' rows: the store keeps a group-to-rows
+ * index in HBM (the rows ordered by group, 4 B per row, and the groups' extents on the host), built on the device from the group
+ * ids by the first call that may use it, under the store's exclusive lock like a flush of staged appends, and dropped only when the
+ * group ids change (ott_store_set_groups, ott_store_clear_groups); a store that never makes this call allocates and launches nothing
+ * for it.  A workgroup per listed group scores its rows against up to 32 tokens at a time (32 while the padded dim is <= 512, 16 while
+ * <= 1024, 8 while <= 2048) with the exact path's additions in the exact path's order, keeps one running maximum per token and — when
+ * the tokens fit one pass — sums them itself; a 32 x 128 query reads every listed row once.  Served by the gather: a single-GPU
+ * store, path AUTO or EXACT, a padded dim of at most 2048 floats, a store of at most 2^26 groups, at most 2^24 distinct listed
+ * groups holding at most 2^30 rows.  Everything else, and option "group_gather" = 0, takes the mask route: a small kernel turns the
+ * list into row-mask words (no index is needed) and ott_query_maxsim's sweep runs with them.  Same bits either way.
+ * Stats on the gather route: path_used = EXACT, passes = token passes, vectors_compared = the listed groups' rows x nq (before the
+ * masks), bytes_scanned = their bytes per pass; on the mask route ott_query_maxsim's.  ott_store_group_index_builds: how many times
+ * this store has built the index (tests and diagnostics: it rises by one per build, never on a query that found the index there).
+ * Refused on the host before any device work: OTT_MODE_PER_QUERY, OTT_PATH_MFMA and a multi-GPU store (OTT_ERR_UNSUPPORTED, as
+ * ott_query_maxsim); a listed id >= ott_store_group_count, groups == NULL with n_groups_listed > 0, no group ids set or ids that
+ * cover a different number of rows than ott_store_len (OTT_ERR_INVALID); cap < k_eff (OTT_ERR_INVALID); on the mask route nq x
+ * n_groups x 4 bytes above 2 GiB (OTT_ERR_UNSUPPORTED).  Takes the store shared, like ott_query_maxsim (staged appends go first). */
+int ott_query_maxsim_groups(ott_store* s, const ott_query_desc* d, const void* groups, /* uint32_t[n_groups_listed] */ uint64_t n_groups_listed,
+                            ott_hit* out, uint64_t cap, uint64_t* n_out, ott_stats* stats);
+uint64_t ott_store_group_index_builds(const ott_store* s);
 
 /* Same, but the result stays on the GPU: out_dev holds `cap` ott_hit slots in device memory
  * of the store's GPU, padded with sentinel hits (index = UINT64_MAX); *n_out_dev (device

@@ -334,7 +334,7 @@ int GroupTopK::finish(ott_store* s, bool timing, ott_hit* out, uint64_t* n_out, 
         if (also_clean) *also_clean = true;
         if (n_pairs > pair_cap) n_pairs = pair_cap;
         std::vector<std::vector<ott_hit>> lists;
-        if ((rc = sort_group_pairs(s, n_pairs, nq, take_max, k, lists, index_is_group ? n_groups : 0))) return rc;
+        if ((rc = sort_group_pairs(s, n_pairs, nq, take_max, k, lists, index_is_group ? (id_span ? id_span : n_groups) : 0))) return rc;
         if (timing) {
             OTT_HIP(hipEventRecord(s->ev[5], s->stream));
             OTT_HIP(hipStreamSynchronize(s->stream));
@@ -407,6 +407,7 @@ int group_ids_of_hits(ott_store* s, const ott_hit* hits, uint64_t n, uint32_t* o
 }
 
 void group_drop(ott_store* s) {
+    group_index_drop(s);  // the group-to-rows index of listed MaxSim depends on the ids alone: it goes with them
     if (s->d_gid) (void)hipFree(s->d_gid);
     s->d_gid = nullptr;
     s->gid_n = 0;

@@ -18,6 +18,7 @@
 #include "ott_policy.h"  // path choice and the batch cascade's back-off rules: HIP-free, CPU-tested
 #include "ott_plane_policy.h"  // the two format decisions of the cascade's planes: HIP-free, CPU-tested
 #include "ott_mfma_plan.h"  // the batch path's host-side plan (tile geometry, candidate budget, error bound, query norms, query block): HIP-free, CPU-tested
+#include "ott_maxsim_gather_plan.h"  // listed MaxSim's host-side plan (tokens per pass, slot arrays, table sizes, route, the 2 GiB refusal): HIP-free, CPU-tested
 #include "ott_sort_plan.h"  // the sort path's host-side plan (pass plans, sweep shape, rank or radix, prefix, slices, group extents, copy pieces): HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
 #include "ott_audit.h"  // test build: every HIP call below goes through a device-affinity check (see "which GPU a call is for")
@@ -88,9 +89,9 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  TWENTY of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  TWENTY-ONE of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, group_gather, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
@@ -156,6 +157,8 @@ struct Options {
                                   // wait, or the grouped all-gather) on a one-GPU box.  Results never depend on it.
     int id_gather = -1;           // candidate id lists (ott_query_ids): -1 = automatic, 0 = never (the list becomes a row mask and
                                   // takes the mask's paths), 1 = the gather kernel wherever it is eligible
+    int group_gather = -1;        // listed MaxSim (ott_query_maxsim_groups): -1 = automatic, 0 = never (the list becomes a row mask and
+                                  // ott_query_maxsim's sweep runs), 1 = the gather kernel wherever it is eligible
     int maxsim_fold = -1;         // [debug build] late-interaction sweep (ott_maxsim.hip): -1 = the product's epilogue, 0 = one atomic per lane,
                                   // 1 = folded over runs of adjacent lanes of one group first (the A/B of profiles/maxsim)
     int multi_min_shard_rows = 32768;  // multi-GPU store: a shard is only brought in for this many rows (a store of fewer than twice as many stays
@@ -322,6 +325,16 @@ struct ott_store {
     // query's reduce kernel (mstable_clean).  The groups' 8-byte keys the reduce makes go through d_gtable, under its own protocol
     ott::DevBuf d_mstable;
     bool mstable_clean = false;
+    // Listed MaxSim (ott_maxsim_gather.hip): the group-to-rows index.  d_gix: the rows ordered by group, [gid_n] words
+    // (the order inside a group is not defined); gix_start: the groups' extents, [n_groups + 1] prefix sums, kept on the host (it
+    // sizes every launch from them).  Built from d_gid by the first listed query that may take the gather, under `rw` exclusive
+    // (lock_shared_clean's clean step); gix_ready says that step has been taken for the ids that are set (d_gix stays nullptr where
+    // it declined: more than MG_INDEX_MAX_GROUPS groups).  Depends on the group ids alone: group_drop drops it, nothing else does.
+    // Owned by the store (workers alias d_gix and read the extents through `owner`).  gix_builds: how often it was built.
+    uint32_t* d_gix = nullptr;
+    std::vector<uint32_t> gix_start;
+    std::atomic<bool> gix_ready{false};
+    std::atomic<uint64_t> gix_builds{0};
     // Small appends are STAGED: rows of appends below 256 KB (VecStore::add_vector is one row per call, src/vec.rs:357-371)
     // collect in pinned host memory and go to the GPU together — when 4 MB are full, and before anything looks at the rows
     // (queries, reads, columns, other kinds of append).  A single-row append costs a memcpy instead of a copy + a kernel + a
@@ -711,6 +724,7 @@ struct GroupTopK {
     bool take_max = false;
     bool index_is_group = false;    // the keys' low words are ~group, not ~row: a hit's index is the group, the count is cut at k
     bool* also_clean = nullptr;
+    uint64_t id_span = 0;           // index_is_group: the ids in the keys stay below this (0 = n_groups; a listed query's table has fewer slots than the store has groups)
     uint64_t q_stride = 0;          // slots between the tables of two queries of a pass; 0 = n_groups (ott_group_top.hip: group_size x n_groups)
     bool lists_path = false;        // from here on: prepare's
     int E = 1;
@@ -722,6 +736,14 @@ struct GroupTopK {
 };
 // ott_group.hip: the grouped query on a context whose `mu` the caller holds; k_eff = min(k, n_groups) >= 1
 int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats_out);
+// ott_maxsim.hip: the late-interaction query on a context whose `mu` the caller holds; k_eff = min(k, n_groups) >= 1.  The reduce
+// kernel's launch: slot g of `table` ([nq][n_slots] ordinals) is group gid_of[g] (nullptr: group g) in the key it writes to keys[g].
+int run_maxsim(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* out, uint64_t* n_out, ott_stats* stats_out);
+int launch_maxsim_reduce(ott_store* s, uint32_t* table, uint32_t n_slots, uint32_t nq, uint32_t take_max, uint32_t cmp, float thr, unsigned long long* keys,
+                         const uint32_t* gid_of);
+// ott_maxsim_gather.hip: the group-to-rows index of listed MaxSim.  group_index_drop: with the group ids (group_drop calls it; the
+// caller holds the store exclusively)
+void group_index_drop(ott_store* s);
 // ott_multi.hip: grouped search on a multi-GPU store
 int multi_set_groups(ott_store* ms, const uint32_t* gid_host, uint64_t n, uint32_t n_groups);
 int multi_clear_groups(ott_store* ms);

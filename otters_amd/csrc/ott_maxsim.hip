@@ -87,8 +87,9 @@ __global__ __launch_bounds__(64 * SW_WAVES) void maxsim_sweep_kernel(MaxsimParam
 }
 
 // One lane per group.  keys: [n_groups] 8-byte keys, zero when the kernel starts (d_gtable's protocol): only kept groups are written.
+// gid_of: the table's slots are a LIST of groups (ott_maxsim_gather.hip), slot g is group gid_of[g]; nullptr = slot g is group g.
 __global__ __launch_bounds__(256) void maxsim_reduce_kernel(uint32_t* table, uint32_t n_groups, uint32_t nq, uint32_t take_max, uint32_t cmp, float thr,
-                                                            unsigned long long* keys) {
+                                                            unsigned long long* keys, const uint32_t* __restrict__ gid_of) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_groups) return;
     const bool tmax = take_max != 0;
@@ -105,7 +106,15 @@ __global__ __launch_bounds__(256) void maxsim_reduce_kernel(uint32_t* table, uin
             acc = t == 0 ? b : __fadd_rn(acc, b);  // starts from best[0], not from 0.0: a -0.0 stays -0.0
         }
     }
-    if (complete && !(acc != acc) && cmp_holds(acc, cmp, thr)) keys[g] = ((unsigned long long)ord_of(acc, tmax) << 32) | (uint32_t)(~(uint32_t)g);
+    const uint32_t id = gid_of ? gid_of[g] : (uint32_t)g;
+    if (complete && !(acc != acc) && cmp_holds(acc, cmp, thr)) keys[g] = ((unsigned long long)ord_of(acc, tmax) << 32) | (uint32_t)(~id);
+}
+
+int launch_maxsim_reduce(ott_store* s, uint32_t* table, uint32_t n_slots, uint32_t nq, uint32_t take_max, uint32_t cmp, float thr, unsigned long long* keys,
+                         const uint32_t* gid_of) {
+    hipLaunchKernelGGL(maxsim_reduce_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, s->stream, table, n_slots, nq, take_max, cmp, thr, keys, gid_of);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
 }
 
 namespace {
@@ -135,7 +144,10 @@ int launch_sweep(ott_store* s, const MaxsimParams& p, uint32_t nq_tile, uint32_t
     return launch_sweep_fold<MS_FOLD>(s, p, nq_tile, grid);
 }
 
+}  // namespace
+
 // The query on a context whose `mu` the caller holds (and the owner's `rw`, shared).  k_eff = min(k, n_groups) >= 1.
+// (ott_maxsim_gather.hip runs it too: a listed query on the mask route IS this query with one more mask.)
 int run_maxsim(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* out, uint64_t* n_out, ott_stats* stats_out) {
     int rc;
     OTT_HIP(use_device(s));
@@ -168,8 +180,7 @@ int run_maxsim(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* o
             p.q0 = ps * tile;
             if ((rc = launch_sweep(s, p, tile, grid))) return rc;
         }
-        hipLaunchKernelGGL(maxsim_reduce_kernel, dim3((ng + 255) / 256), dim3(256), 0, s->stream, p.table, ng, nq, p.take_max, (uint32_t)d->filter_cmp, d->filter_thr, keys);
-        OTT_HIP(hipGetLastError());
+        if ((rc = launch_maxsim_reduce(s, p.table, ng, nq, p.take_max, (uint32_t)d->filter_cmp, d->filter_thr, keys, nullptr))) return rc;
         if ((rc = tk.pass(s, keys, 0, 1))) return rc;
         if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
         if ((rc = tk.finish(s, timing, out, n_out, nullptr))) return rc;
@@ -179,8 +190,6 @@ int run_maxsim(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* o
     if (stats_out) *stats_out = st;
     return OTT_OK;
 }
-
-}  // namespace
 
 }  // namespace ott
 

@@ -28,12 +28,12 @@ struct OptName {
     const char* name;
     int kind;  // 0 = bool, 1 = tri-state (-1 automatic / 0 / 1), 2 = non-negative int
 };
-// the twenty options of the product library (see struct Options) ...
+// the twenty-one options of the product library (see struct Options) ...
 const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"hi_prebuild", 1},          {"stage_appends", 1},       {"multi_transport", 2},
                              {"multi_rebalance", 0}, {"multi_min_shard_rows", 2}, {"exact_small", 1},     {"large_k_from", 2},        {"small_sort", 1},
                              {"mfma_f32", 0},        {"no_hi_pass", 0},      {"no_batch_image", 0},       {"force_fallback", 2},      {"eps_scale_ppm", 2},
                              {"multi_fake_distinct", 0}, {"exact_prune", 1},            {"exact_sketch", 1},
-                             {"id_gather", 1},       {"exact_sketch_bits", 2},
+                             {"id_gather", 1},       {"exact_sketch_bits", 2},   {"group_gather", 1},
 #ifdef OTT_MFMA_DEBUG_BUILD
                              // ... and, in the diagnostic build only, kernel tuning, timing ablations and every fallback bit by its own name
                              {"mfma_wg", 2},         {"mfma_growth", 2},     {"mfma_debug", 0},           {"mfma_abl", 2},            {"hi_tmin", 2},
@@ -41,11 +41,11 @@ const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"h
                              {"merge_rank1", 1},     {"maxsim_fold", 1},
 #endif
 };
-static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 20
+static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 21
 #ifdef OTT_MFMA_DEBUG_BUILD
                                                             + 12
 #endif
-              , "the product library's option table stays at twenty entries");
+              , "the product library's option table stays at twenty-one entries");
 }  // namespace
 
 int option_set(Options& o, const char* name, long long v) {
@@ -82,6 +82,7 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "exact_sketch") return tri(o.exact_sketch);
     if (n == "exact_sketch_bits") { if (v != 1 && v != 3 && v != 4) return -1; o.exact_sketch_bits = (int)v; return 0; }
     if (n == "id_gather") return tri(o.id_gather);
+    if (n == "group_gather") return tri(o.group_gather);
 #ifdef OTT_MFMA_DEBUG_BUILD
     if (n == "maxsim_fold") return tri(o.maxsim_fold);
     if (n == "mfma_coop") return tri(o.mfma_coop);
@@ -766,6 +767,7 @@ static void alias_corpus(ott_store* w, const ott_store* s) {
     w->d_gid = s->d_gid;
     w->gid_n = s->gid_n;
     w->n_groups = s->n_groups;
+    w->d_gix = s->d_gix;
 }
 
 // the store's own context when it is free, else a worker context that aliases the corpus (ott::host::ContextPool)
@@ -859,7 +861,9 @@ int ott_store_destroy(ott_store* s) {
         s->d_evalmask.cap = 0;
         s->d_live = nullptr;
         s->d_gid = nullptr;
+        s->d_gix = nullptr;
     }
+    if (s->d_gix) (void)hipFree(s->d_gix);
     if (s->d_live) (void)hipFree(s->d_live);
     if (s->d_gid) (void)hipFree(s->d_gid);
     if (s->d_rows) (void)hipFree(s->d_rows);

@@ -103,6 +103,7 @@ class ResolvedQuery:
     grouped: bool = False                 # one_per_group: one best hit per group, top-k over the groups (ott_query_groups)
     max_sim: bool = False                 # max_sim: the query vectors are one query's tokens, top-k groups by the sum of their best scores (ott_query_maxsim)
     group_size: int = 0                   # per_group(m): up to m hits per group (ott_query_groups_top); 0 = not a per_group plan
+    group_list: Optional[np.ndarray] = None    # with_groups: uint32[n listed] dense group ids, in the caller's order, duplicates kept (ott_query_maxsim_groups), or None
     group_of_hit: Optional[np.ndarray] = None  # OUTPUT of VecStore._run for a per_group plan: uint32[n hits], the dense group id of every hit
 
 
@@ -168,6 +169,7 @@ class VecQueryPlan:
         self._grouped = False
         self._max_sim = False
         self._per_group = None  # per_group(m): m as the caller gave it (checked at validate())
+        self.group_list = None  # with_groups: the labels as the caller gave them (mapped at validate())
 
     @staticmethod
     def new() -> "VecQueryPlan":
@@ -266,10 +268,42 @@ class VecQueryPlan:
         usual (Euclidean / Manhattan: the sum of minimum distances); a plan without take ranks by Max and returns every group
         (the default take becomes group_count()).  filter() applies to the sum.  collect_arrays() returns hits whose `index` is
         the dense group id; collect() returns SearchResult(label, score) with the caller's own group label.  Not together with
-        with_row_ids, one_per_group or per_query; not on a multi-GPU store."""
+        with_row_ids, one_per_group or per_query; not on a multi-GPU store.  with_groups(labels) re-ranks only the listed groups."""
         if self.error is None:
             self._max_sim = True
         return self
+
+    def with_groups(self, labels) -> "VecQueryPlan":
+        """Re-rank only the listed groups (ott_query_maxsim_groups): the hits of the same max_sim() plan with a row mask that keeps
+        just the rows whose group is listed, ANDed with with_row_mask and the deleted rows.  The work follows the list, not the
+        store.  `labels` are the caller's own group labels as set_groups got them (dense ids where the ids were set dense), any
+        integer sequence or array, any order, duplicates allowed; a label no row carries raises at validate().  The default take
+        becomes the number of distinct listed groups.  Only with max_sim() in this version."""
+        if self.error is None:
+            self.group_list = labels
+        return self
+
+    def _dense_group_list(self) -> np.ndarray:
+        """with_groups' labels as uint32 dense group ids, in the caller's order (the library sorts and dedupes them)"""
+        a = np.asarray(self.group_list)
+        if a.size == 0:
+            return np.zeros(0, dtype=np.uint32)
+        a = a.ravel()
+        if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+            raise OttersError(f"group labels must be integers, not {a.dtype}")
+        store = self.vector_store
+        labels = store.group_labels()
+        if labels is None:  # the ids were set dense: a label is an id
+            bad = (a < 0) | (a >= store.group_count()) if np.issubdtype(a.dtype, np.signedinteger) else (a >= store.group_count())
+            if bad.any():
+                raise OttersError(f"with_groups: group {int(a[bad][0])} is not one of the store's {store.group_count()} groups")
+            return np.ascontiguousarray(a.astype(np.uint32))
+        at = np.searchsorted(labels, a)  # labels: sorted and duplicate-free (np.unique)
+        at_c = np.minimum(at, labels.size - 1)
+        bad = labels[at_c] != a
+        if bad.any():
+            raise OttersError(f"with_groups: no row carries the group label {int(a[bad][0])}")
+        return np.ascontiguousarray(at_c.astype(np.uint32))
 
     # -- execution -----------------------------------------------------------------------------
     def validate(self) -> None:  # src/vec.rs:170-203
@@ -301,6 +335,16 @@ class VecQueryPlan:
             raise OttersError("max_sim cannot be combined with one_per_group: a hit of max_sim is a group already")
         if self._max_sim and self._mode == Mode.PerQuery:
             raise OttersError("max_sim cannot be combined with per_query: the query vectors are the tokens of one query")
+        if self.group_list is not None:
+            if self._per_group is not None:
+                raise OttersError("with_groups cannot be combined with per_group in this version; use with_row_mask")
+            if self._grouped:
+                raise OttersError("with_groups cannot be combined with one_per_group in this version; use with_row_mask")
+            if self.row_ids is not None:
+                raise OttersError("with_groups cannot be combined with with_row_ids in this version; use with_row_mask")
+            if not self._max_sim:
+                raise OttersError("with_groups needs max_sim in this version; use with_row_mask")
+            self._dense_group_list()
         dim = self.vector_store.dim
         if isinstance(self.query_vectors, np.ndarray):  # a matrix: every row has the same length
             if self.query_vectors.shape[1] != dim:
@@ -318,13 +362,19 @@ class VecQueryPlan:
             queries = self.query_vectors
         else:
             queries = np.ascontiguousarray(np.stack(self.query_vectors).astype(np.float32, copy=False))
-        k = self.take_count if self.take_count is not None else (store.group_count() if self._grouped or self._max_sim else store.len())  # src/vec.rs:213
+        group_list = None if self.group_list is None else self._dense_group_list()
+        if self.take_count is not None:
+            k = self.take_count
+        elif group_list is not None:
+            k = int(np.unique(group_list).size)
+        else:
+            k = store.group_count() if self._grouped or self._max_sim else store.len()  # src/vec.rs:213
         take = self.take_type if self.take_type is not None else TakeType.Max  # src/vec.rs:214
         fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
         return ResolvedQuery(queries=queries, metric=int(self.search_metric), take=int(take), k=max(int(k), 0),
                              filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, mode=int(self._mode), path=int(self._path),
                              row_ids=None if self.row_ids is None else as_row_ids(self.row_ids), grouped=self._grouped,
-                             max_sim=self._max_sim, group_size=0 if self._per_group is None else int(self._per_group))
+                             max_sim=self._max_sim, group_size=0 if self._per_group is None else int(self._per_group), group_list=group_list)
 
     def collect(self):  # src/vec.rs:205-311
         hits, counts = self.collect_arrays()[:2]  # (a per_group plan returns the hits' groups too)
@@ -626,7 +676,7 @@ class VecStore:
         return bool(self._n) and bool(N.lib().ott_store_batch_ready(self._handle()))
 
     def set_option(self, name: str, value: int) -> None:
-        """Behaviour switch of this store (ott_store_set_option; the twenty names are listed in include/otters_hip.h:
+        """Behaviour switch of this store (ott_store_set_option; the twenty-one names are listed in include/otters_hip.h:
         "tie_order", "hi_fmt", "hi_prebuild", ..., "force_fallback").  Results never depend on any but "tie_order"."""
         self._options[name] = int(value)
         if self._h is not None:
@@ -696,6 +746,8 @@ class VecStore:
             cap = max(min(rq.k, self._n_groups) * nq * rq.group_size, 1)
         if rq.max_sim:  # at most one hit per group
             cap = max(min(rq.k, self._n_groups), 1)
+        if rq.group_list is not None:  # ... and per listed group
+            cap = max(min(rq.k, int(np.unique(rq.group_list).size)), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)  # ott_query writes n_out entries; only those are returned
         d = N.QueryDesc()
         d.queries = rq.queries.ctypes.data
@@ -717,7 +769,11 @@ class VecStore:
         n_out = C.c_uint64(0)
         per = (C.c_uint64 * nq)()
         st = N.Stats()
-        if rq.max_sim:
+        if rq.group_list is not None:
+            gl = rq.group_list
+            N.check(N.lib().ott_query_maxsim_groups(self._handle(), C.byref(d), N.ptr(gl) if gl.size else None, gl.size, N.ptr(out), cap, C.byref(n_out), C.byref(st)))
+            per[0] = n_out.value
+        elif rq.max_sim:
             N.check(N.lib().ott_query_maxsim(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), C.byref(st)))
             per[0] = n_out.value
         elif rq.group_size:
@@ -731,7 +787,10 @@ class VecStore:
         else:
             N.check(N.lib().ott_query_ids(self._handle(), C.byref(d), N.ptr(ids), ids.size, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         hits = out if n_out.value == cap else out[: n_out.value].copy()
-        return hits, list(per), st.as_dict()
+        stats = st.as_dict()
+        if rq.group_list is not None:  # how often this store has built its group-to-rows index so far
+            stats["group_index_builds"] = int(N.lib().ott_store_group_index_builds(self._handle()))
+        return hits, list(per), stats
 
     def score_rows(self, queries, metric: Metric, ids) -> np.ndarray:
         """float32[nq, n_ids]: the score of every query against every row of `ids` (ott_store_score_rows) -- the exact path's bits,
