@@ -16,6 +16,7 @@ use std::os::raw::{c_char, c_int, c_void};
 pub const OTT_ABI_VERSION: c_int = 4;
 pub const OTT_COMM_ID_BYTES: usize = 128;
 pub const OTT_GROUP_SIZE_MAX: u32 = 16; // ott_query_groups_top: the largest group_size
+pub const OTT_MAXSIM_BATCH_MAX: u32 = 4096; // ott_query_maxsim_groups_batch: the largest n_queries
 
 // ott_status
 pub const OTT_OK: c_int = 0;
@@ -190,6 +191,7 @@ extern "C" {
     pub fn ott_query_maxsim(s: *mut ott_store, d: *const ott_query_desc, out: *mut ott_hit, cap: u64, n_out: *mut u64, stats: *mut ott_stats) -> c_int;
     pub fn ott_query_maxsim_groups(s: *mut ott_store, d: *const ott_query_desc, groups: *const c_void, n_groups_listed: u64, out: *mut ott_hit, cap: u64, n_out: *mut u64, stats: *mut ott_stats) -> c_int; // groups: n_groups_listed u32
     pub fn ott_store_group_index_builds(s: *const ott_store) -> u64;
+    pub fn ott_query_maxsim_groups_batch(s: *mut ott_store, d: *const ott_query_desc, tokens_per_query: *const c_void, listed_per_query: *const u64, n_queries: u32, groups: *const c_void, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int; // tokens_per_query: n_queries u32; groups: u32, the lists back to back
     pub fn ott_query_device(s: *mut ott_store, d: *const ott_query_desc, out_dev: *mut c_void, cap: u64, n_out_dev: *mut c_void, stats: *mut ott_stats) -> c_int;
     pub fn ott_store_sync(s: *mut ott_store) -> c_int;
     pub fn ott_store_stream(s: *mut ott_store) -> *mut c_void;

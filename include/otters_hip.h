@@ -491,6 +491,38 @@ int ott_query_maxsim_groups(ott_store* s, const ott_query_desc* d, const void* g
                             ott_hit* out, uint64_t cap, uint64_t* n_out, ott_stats* stats);
 uint64_t ott_store_group_index_builds(const ott_store* s);
 
+/* MaxSim re-ranking in batches (an extension; a server that re-ranks for many users at once): B = n_queries queries, each with its
+ * own tokens and its own candidate list, through one upload, one gather launch, one top-k and one host wait.  d->queries holds the
+ * tokens of query 0, then of query 1, and so on; tokens_per_query[b] (uint32_t, declared const void* as the group ids are) says how
+ * many belong to query b, and d->nq is their total.  groups holds the lists in the same order, listed_per_query[b] dense ids each:
+ * any order, duplicates allowed, two queries may list the same group, and listed_per_query[b] == 0 is a valid query with no hits.
+ * The whole batch shares metric, take, the filter, k, chunk_mask, the row mask (the caller's or the device mask) and the live mask
+ * of deleted rows.  For every b the call returns exactly the hits of ott_query_maxsim_groups with d->queries / d->nq replaced by
+ * query b's tokens and with query b's list — the same dense group ids, the same score bits, the same order — except that their
+ * `query` field is b.  The lists come out back to back in query order; n_per_query[b] (n_queries entries, may be NULL) is their
+ * lengths and *n_out their sum.  k_eff_b = min(k, distinct listed groups of b); cap >= the sum of the k_eff_b.  Everything the
+ * contracts of ott_query_maxsim and ott_query_maxsim_groups say holds per query.
+ * The batched gather serves the batch when ott_query_maxsim_groups' gather would serve every query alone and every query's tokens
+ * fit one pass (32 tokens while the padded dim is <= 512, 16 while <= 1024, 8 while <= 2048), n_queries x the largest number of
+ * distinct listed groups stays within 2^24 and the listed rows of all queries within 2^30: the slots of all queries lie back to
+ * back, a persistent workgroup walks a contiguous range of them balanced by listed rows and reloads the token block in LDS where
+ * the query changes; one top-k serves all queries.  Option "group_gather": 1 = wherever eligible, -1 = when every query alone
+ * would take the gather, 0 = never.  Everything else takes the loop route: the queries are answered one by one as
+ * ott_query_maxsim_groups answers them, under the one shared lock.  Same bits either way.
+ * Stats: path_used = EXACT; on the batched gather passes = 1, vectors_compared = the sum over the queries of listed rows x tokens
+ * (before the masks), bytes_scanned = the listed rows' bytes; on the loop route each is the sum of the queries' own.
+ * Refused on the host before any device work, with nothing written: OTT_MODE_PER_QUERY and OTT_PATH_MFMA (OTT_ERR_UNSUPPORTED,
+ * before the store is looked at), a multi-GPU store (OTT_ERR_UNSUPPORTED); n_queries == 0 or above OTT_MAXSIM_BATCH_MAX (it bounds
+ * the staged token block to about 75 MB at 32 x 128 tokens), tokens_per_query or listed_per_query NULL, groups NULL with a listed
+ * id, tokens_per_query[b] == 0, a sum of tokens_per_query other than d->nq, a listed id >= ott_store_group_count (the message names
+ * b and the id), no group ids set or ids that cover a different number of rows than ott_store_len, cap below the sum of the k_eff_b
+ * (all OTT_ERR_INVALID).  Takes the store shared, like ott_query_maxsim_groups: staged appends and the group-to-rows index are
+ * settled first, once for the whole batch. */
+#define OTT_MAXSIM_BATCH_MAX 4096
+int ott_query_maxsim_groups_batch(ott_store* s, const ott_query_desc* d, const void* tokens_per_query, /* uint32_t[n_queries] */
+                                  const uint64_t* listed_per_query, uint32_t n_queries, const void* groups, /* uint32_t[sum of listed_per_query] */
+                                  ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats);
+
 /* Same, but the result stays on the GPU: out_dev holds `cap` ott_hit slots in device memory
  * of the store's GPU, padded with sentinel hits (index = UINT64_MAX); *n_out_dev (device
  * uint64) receives the count.  PER_QUERY mode: cap must be a multiple of nq; query q's hits

@@ -5,8 +5,8 @@ and error strings) over libotters_hip.so: the corpus lives row-major in HBM, sco
 score filtering and top-k run as hand-written HIP kernels.  No CPU fallback.
 """
 from ._native import OttersError  # noqa: F401
-from .vec import (Cmp, Metric, Mode, Path, QueryBatch, SearchResult, TakeType, VecQueryPlan,  # noqa: F401
-                  VecStore)
+from .vec import (Cmp, MaxSimBatchPlan, Metric, Mode, Path, QueryBatch, SearchResult, TakeType,  # noqa: F401
+                  VecQueryPlan, VecStore)
 
 from .col import Column, ColumnError, DataType  # noqa: F401,E402
 from .expr import CmpOp, CompiledFilter, Expr, ExprError, col, lit  # noqa: F401,E402
@@ -15,5 +15,5 @@ from .meta import (MetaBuildStats, MetaQueryPlan, MetaQueryResults, MetaQuerySta
 
 __all__ = ["Column", "ColumnError", "DataType", "CmpOp", "CompiledFilter", "Expr", "ExprError", "col", "lit",
            "MetaBuildStats", "MetaQueryPlan", "MetaQueryResults", "MetaQueryStats", "MetaStore", "MetaStoreBuilder",
-           "OttersError", "Cmp", "Metric", "Mode", "Path", "QueryBatch", "SearchResult", "TakeType",
+           "OttersError", "Cmp", "MaxSimBatchPlan", "Metric", "Mode", "Path", "QueryBatch", "SearchResult", "TakeType",
            "VecQueryPlan", "VecStore"]

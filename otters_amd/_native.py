@@ -161,6 +161,7 @@ def lib() -> C.CDLL:
         "ott_query_maxsim": (i32, [vp, vp, vp, u64, vp, vp]),
         "ott_query_maxsim_groups": (i32, [vp, vp, vp, u64, vp, u64, vp, vp]),
         "ott_store_group_index_builds": (u64, [vp]),
+        "ott_query_maxsim_groups_batch": (i32, [vp, vp, vp, vp, u32, vp, vp, u64, vp, vp, vp]),
         "ott_query_device": (i32, [vp, vp, vp, u64, vp, vp]),
         "ott_store_sync": (i32, [vp]),
         "ott_store_stream": (vp, [vp]),

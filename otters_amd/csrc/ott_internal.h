@@ -744,6 +744,14 @@ int launch_maxsim_reduce(ott_store* s, uint32_t* table, uint32_t n_slots, uint32
 // ott_maxsim_gather.hip: the group-to-rows index of listed MaxSim.  group_index_drop: with the group ids (group_drop calls it; the
 // caller holds the store exclusively)
 void group_index_drop(ott_store* s);
+// ... and what ott_query_maxsim_groups does around and under its lock, for ott_maxsim_batch.hip (`fn`: the entry point the messages
+// name).  check_listed_groups: every listed id is below n_groups.  maxsim_groups_lock: the store shared through lock_shared_clean
+// (staged appends and the index settled in the clean step).  maxsim_groups_locked: one listed query under that lock — ids and list
+// checked again, k_eff, the route, a context, the run.
+int check_listed_groups(const char* fn, const uint32_t* groups, uint64_t n_listed, uint32_t n_groups);
+int maxsim_groups_lock(ott_store* s, const char* fn, ott::host::SharedLock& rd);
+int maxsim_groups_locked(ott_store* s, const ott_query_desc* d, const uint32_t* groups, uint64_t n_groups_listed, ott_hit* out, uint64_t cap, uint64_t* n_out,
+                         ott_stats* stats, const char* fn);
 // ott_multi.hip: grouped search on a multi-GPU store
 int multi_set_groups(ott_store* ms, const uint32_t* gid_host, uint64_t n, uint32_t n_groups);
 int multi_clear_groups(ott_store* ms);

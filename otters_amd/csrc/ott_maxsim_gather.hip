@@ -25,6 +25,9 @@
 //                         list's mask joins (cur_idmask) and ott_maxsim.hip's run_maxsim runs unchanged.  Needs no index.
 //
 // The host-side decisions — tokens per pass, the slot arrays, the tables' sizes, the route — are ott_maxsim_gather_plan.h's.
+// The kernel's per-row step is ott_maxsim_gather_step.inc, its join and its sum ott_maxsim_gather_dev.h: ott_maxsim_batch.hip's kernel
+// (many queries and their lists in one launch) runs the same; what this call does around and under its lock is
+// maxsim_groups_lock / maxsim_groups_locked, which the batch's loop route calls per query.
 // Resources (profiles/maxsim_rerank/resource_usage.txt): no scratch at any of the three widths.
 #include <string.h>
 
@@ -34,10 +37,9 @@
 
 #include "ott_internal.h"
 #include "ott_exact_dev.h"
+#include "ott_maxsim_gather_dev.h"
 
 namespace ott {
-
-constexpr int MG_UNROLL = 8;  // row elements a lane has in flight
 
 struct MgParams {
     const float* rows;
@@ -91,120 +93,21 @@ __global__ __launch_bounds__(64 * MG_WAVES) void maxsim_gather_kernel(MgParams p
         uint32_t best[NT];  // per token: the best ordinal among this lane group's rows of the group (0 = none yet)
 #pragma unroll
         for (int q = 0; q < NT; q++) best[q] = 0u;
-
         for (uint32_t base = 0; base < count; base += MG_STEP_ROWS) {
-            const uint32_t ri = base + 8u * (uint32_t)wave + (uint32_t)grp;
-            bool valid = ri < count;
-            const uint32_t row = p.gix[start + (valid ? ri : count - 1)];  // a place past the group's end is clamped for the loads, invalid for the maxima
-            if (valid && p.row_mask != nullptr && row < p.row_mask_bits) valid = (p.row_mask[row >> 6] >> (row & 63)) & 1;  // src/vec.rs:231-237
-            if (valid && p.chunk_mask != nullptr) {
-                const uint32_t ch = row / p.chunk_rows;
-                valid = (p.chunk_mask[ch >> 6] >> (ch & 63)) & 1;
-            }
-            if (__ballot(valid) == 0) continue;  // every row of this wave's step is masked: they are never read
-            const float* rp = p.rows + (uint64_t)row * p.ld;
-            float vinv = 0.0f;
-            if (p.metric == OTT_METRIC_COSINE) vinv = p.inv[row];
-
-            // chain c of the row, for every token of the pass: acc = acc + term(q[8j + c], v[8j + c]), j ascending (vec_compute.rs:12-13, 39-42)
-            float acc[NT];
-#pragma unroll
-            for (int q = 0; q < NT; q++) acc[q] = 0.0f;
-            auto step = [&](uint32_t jj, float xv) {
-                const float4* tq = reinterpret_cast<const float4*>(sT + (size_t)(8 * jj + c) * NTP);
-#pragma unroll
-                for (int q4 = 0; q4 < NT / 4; q4++) {
-                    const float4 t = tq[q4];
-                    acc[4 * q4 + 0] = __fadd_rn(acc[4 * q4 + 0], exact_term<MK>(t.x, xv));
-                    acc[4 * q4 + 1] = __fadd_rn(acc[4 * q4 + 1], exact_term<MK>(t.y, xv));
-                    acc[4 * q4 + 2] = __fadd_rn(acc[4 * q4 + 2], exact_term<MK>(t.z, xv));
-                    acc[4 * q4 + 3] = __fadd_rn(acc[4 * q4 + 3], exact_term<MK>(t.w, xv));
-                }
-            };
-            uint32_t j = 0;
-            for (; j + MG_UNROLL <= full; j += MG_UNROLL) {
-                float x[MG_UNROLL];
-#pragma unroll
-                for (int u = 0; u < MG_UNROLL; u++) x[u] = rp[8 * (j + u) + c];
-#pragma unroll
-                for (int u = 0; u < MG_UNROLL; u++) step(j + u, x[u]);
-            }
-            for (; j < full; j++) step(j, rp[8 * j + c]);
-            // remainder: sequential sum of the last dim % 8 terms (vec_compute.rs:15-21, 44-53); every lane of the group computes it
-            float tail[NT];
-#pragma unroll
-            for (int q = 0; q < NT; q++) tail[q] = 0.0f;
-            for (uint32_t l = 0; l < nt; l++) {
-                const float xv = rp[8 * full + l];
-                const float4* tq = reinterpret_cast<const float4*>(sT + (size_t)(8 * full + l) * NTP);
-#pragma unroll
-                for (int q4 = 0; q4 < NT / 4; q4++) {
-                    const float4 t = tq[q4];
-                    tail[4 * q4 + 0] = __fadd_rn(tail[4 * q4 + 0], exact_term<MK>(t.x, xv));
-                    tail[4 * q4 + 1] = __fadd_rn(tail[4 * q4 + 1], exact_term<MK>(t.y, xv));
-                    tail[4 * q4 + 2] = __fadd_rn(tail[4 * q4 + 2], exact_term<MK>(t.z, xv));
-                    tail[4 * q4 + 3] = __fadd_rn(tail[4 * q4 + 3], exact_term<MK>(t.w, xv));
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < NT; q++) {
-                // wide::f32x8::reduce_add across the group's eight lanes (exact_gather8_kernel's)
-                float sum;
-                if (p.reduce == OTT_REDUCE_SEQ4) {
-                    const int b = lane & ~7;
-                    float l8[8];
-#pragma unroll
-                    for (int i = 0; i < 8; i++) l8[i] = __shfl(acc[q], b + i);
-                    sum = reduce8(l8, OTT_REDUCE_SEQ4);
-                } else {
-                    const float s1 = __fadd_rn(acc[q], __shfl_xor(acc[q], 4));  // l_c + l_{c^4}
-                    const float s2 = __fadd_rn(s1, __shfl_xor(s1, 2));          // (l0+l4)+(l2+l6) on even-pair lanes, (l1+l5)+(l3+l7) on the others
-                    sum = __fadd_rn(s2, __shfl_xor(s2, 1));                     // (a + b == b + a bit for bit)
-                }
-                float sc = __fadd_rn(sum, tail[q]);
-                if (p.metric == OTT_METRIC_COSINE) sc = __fmul_rn(__fmul_rn(sc, sQi[q]), vinv);  // vec_compute.rs:31
-                const uint32_t o = (valid && !(sc != sc)) ? ord_of(sc, take_max) : 0u;  // NaN dropped: vec_compute.rs:237
-                if (o > best[q]) best[q] = o;
-            }
+#include "ott_maxsim_gather_step.inc"
         }
 
-        // join: over the wave's eight row groups by shuffles (the lanes of one group agree already), over the waves in LDS
-#pragma unroll
-        for (int q = 0; q < NT; q++) {
-            uint32_t b = best[q];
-#pragma unroll
-            for (int d = 8; d < 64; d <<= 1) {
-                const uint32_t ob = (uint32_t)__shfl_xor((int)b, d);
-                if (ob > b) b = ob;
-            }
-            if (lane == 0) sB[wave * NT + q] = b;
-        }
+        // join: over the wave's eight row groups by shuffles, over the waves in LDS (ott_maxsim_gather_dev.h)
+        mg_join_wave<NT>(best, sB, wave, lane);
         __syncthreads();
-        auto joined = [&](uint32_t t) {
-            uint32_t m = sB[t];
-#pragma unroll
-            for (int w = 1; w < (int)MG_WAVES; w++) m = sB[w * NT + t] > m ? sB[w * NT + t] : m;
-            return m;
-        };
         if (p.single) {
-            // one pass holds every token: the sum in token order, started from best[0] (a -0.0 stays -0.0), as maxsim_reduce_kernel makes it
+            // one pass holds every token: the sum in token order, started from best[0], and the key
             if (tid == 0) {
-                bool complete = true;
-                float sum = 0.0f;
-                for (uint32_t t = 0; t < nq_here; t++) {
-                    const uint32_t o = joined(t);
-                    if (o == 0) {
-                        complete = false;
-                    } else {
-                        const float b = score_of(o, take_max);
-                        sum = t == 0 ? b : __fadd_rn(sum, b);
-                    }
-                }
-                if (complete && !(sum != sum) && cmp_holds(sum, p.cmp, p.thr))
-                    p.keys[slot] = ((unsigned long long)ord_of(sum, take_max) << 32) | (uint32_t)(~p.slot_gid[slot]);
+                const unsigned long long key = mg_sum_key<NT>(sB, nq_here, take_max, p.cmp, p.thr, p.slot_gid[slot]);
+                if (key != 0) p.keys[slot] = key;
             }
         } else if ((uint32_t)tid < nq_here) {
-            const uint32_t o = joined((uint32_t)tid);
+            const uint32_t o = mg_joined<NT>(sB, (uint32_t)tid);
             if (o != 0) p.table[(size_t)(q0 + (uint32_t)tid) * p.n_slots + slot] = o;  // (the table is zero when found: an empty slot is not written)
         }
         __syncthreads();  // sB is the next group's
@@ -455,6 +358,8 @@ int run_groups_as_mask(ott_store* s, const ott_query_desc* d, const std::vector<
     return run_maxsim(s, d, k_eff, out, n_out, stats_out);
 }
 
+}  // namespace
+
 int check_listed_groups(const char* fn, const uint32_t* groups, uint64_t n_listed, uint32_t n_groups) {
     if (n_listed && !groups) return fail(OTT_ERR_INVALID, std::string(fn) + ": groups is NULL");
     for (uint64_t i = 0; i < n_listed; i++)
@@ -463,7 +368,42 @@ int check_listed_groups(const char* fn, const uint32_t* groups, uint64_t n_liste
     return OTT_OK;
 }
 
-}  // namespace
+// The store shared, with nothing left to do first: staged rows go to the GPU and — where a listed query of this store may take the
+// gather — the group-to-rows index is there.  Both happen under the exclusive lock, in the clean step; no query waits on a mutex
+// for them.  (ott_query_maxsim_groups_batch takes it once for all its queries.)
+int maxsim_groups_lock(ott_store* s, const char* fn, ott::host::SharedLock& rd) {
+    const auto wants_index = [s] { return mg_wants_index(false, false, s->dimq, s->opt.group_gather); };
+    return ott::host::lock_shared_clean(
+        s->rw, rd, [&] { return s->pend.count() != 0 || (wants_index() && !s->gix_ready.load(std::memory_order_acquire)); },
+        [&] { return wants_index() ? group_index_ensure(s, fn) : store_flush(s); });
+}
+
+// One listed query under the shared lock (`fn`: the entry point the messages name): the route and the run.
+int maxsim_groups_locked(ott_store* s, const ott_query_desc* d, const uint32_t* groups, uint64_t n_groups_listed, ott_hit* out, uint64_t cap, uint64_t* n_out,
+                         ott_stats* stats, const char* fn) {
+    int rc;
+    const std::string name(fn);
+    // what the checks in front of the lock read without it is read again, and k_eff only here: a set_groups may have come in between
+    if ((rc = check_group_ids(s, fn, true))) return rc;
+    if ((rc = check_listed_groups(fn, groups, n_groups_listed, s->n_groups))) return rc;
+    const bool wants_index = mg_wants_index(false, false, s->dimq, s->opt.group_gather);
+    const bool have_index = s->d_gix != nullptr && s->gix_start.size() == (size_t)s->n_groups + 1;
+    MgSlots sl;
+    mg_slots(groups, n_groups_listed, s->n_groups, have_index ? s->gix_start.data() : nullptr, sl);
+    const uint64_t k_eff = d->k < sl.gid.size() ? d->k : sl.gid.size();
+    if (cap < k_eff) return fail(OTT_ERR_INVALID, name + ": output capacity is smaller than min(k, distinct listed groups)");
+    if (!out && cap) return fail(OTT_ERR_INVALID, name + ": out is NULL");
+    if (k_eff == 0) return OTT_OK;  // an empty list, or k == 0: a valid query with no hits
+    const bool gather = mg_takes_gather(wants_index, have_index, s->opt.group_gather, sl.gid.size(), sl.rows);
+    if (!gather && !mg_sweep_table_fits(d->nq, s->n_groups))
+        return fail(OTT_ERR_UNSUPPORTED,
+                    name + ": tokens x groups x 4 bytes is above 2 GiB on the mask route (the sweep's table holds every group of the store); use fewer "
+                           "tokens or groups, or a list the gather kernel serves");
+    ott_store* ctx = ctx_acquire(s);
+    rc = gather ? run_maxsim_gather(ctx, d, sl, k_eff, out, n_out, stats) : run_groups_as_mask(ctx, d, sl.gid, k_eff, out, n_out, stats);
+    ctx_release(ctx);
+    return rc;
+}
 
 }  // namespace ott
 
@@ -491,33 +431,9 @@ int ott_query_maxsim_groups(ott_store* s, const ott_query_desc* d, const void* g
     // before any device work: the ids are set and cover the store, the list names groups that exist
     if ((rc = check_group_ids(s, fn, false))) return rc;
     if ((rc = check_listed_groups(fn, groups, n_groups_listed, ott_store_group_count(s)))) return rc;
-    // The store shared, with nothing left to do first: staged rows go to the GPU and — where this query may take the gather — the
-    // group-to-rows index is there.  Both happen under the exclusive lock, in the clean step; no query waits on a mutex for them.
-    const auto wants_index = [s] { return mg_wants_index(false, false, s->dimq, s->opt.group_gather); };
     ott::host::SharedLock rd;  // the corpus, the group ids and the index cannot change while this query runs
-    if ((rc = ott::host::lock_shared_clean(
-             s->rw, rd, [&] { return s->pend.count() != 0 || (wants_index() && !s->gix_ready.load(std::memory_order_acquire)); },
-             [&] { return wants_index() ? group_index_ensure(s, fn) : store_flush(s); })))
-        return rc;
-    // what the checks above read without the lock is read again, and k_eff only here: a set_groups may have come in between
-    if ((rc = check_group_ids(s, fn, true))) return rc;
-    if ((rc = check_listed_groups(fn, groups, n_groups_listed, s->n_groups))) return rc;
-    const bool have_index = s->d_gix != nullptr && s->gix_start.size() == (size_t)s->n_groups + 1;
-    MgSlots sl;
-    mg_slots(groups, n_groups_listed, s->n_groups, have_index ? s->gix_start.data() : nullptr, sl);
-    const uint64_t k_eff = d->k < sl.gid.size() ? d->k : sl.gid.size();
-    if (cap < k_eff) return fail(OTT_ERR_INVALID, "ott_query_maxsim_groups: output capacity is smaller than min(k, distinct listed groups)");
-    if (!out && cap) return fail(OTT_ERR_INVALID, "ott_query_maxsim_groups: out is NULL");
-    if (k_eff == 0) return OTT_OK;  // an empty list, or k == 0: a valid query with no hits
-    const bool gather = mg_takes_gather(wants_index(), have_index, s->opt.group_gather, sl.gid.size(), sl.rows);
-    if (!gather && !mg_sweep_table_fits(d->nq, s->n_groups))
-        return fail(OTT_ERR_UNSUPPORTED,
-                    "ott_query_maxsim_groups: tokens x groups x 4 bytes is above 2 GiB on the mask route (the sweep's table holds every group of the store); use fewer "
-                    "tokens or groups, or a list the gather kernel serves");
-    ott_store* ctx = ctx_acquire(s);
-    rc = gather ? run_maxsim_gather(ctx, d, sl, k_eff, out, n_out, stats) : run_groups_as_mask(ctx, d, sl.gid, k_eff, out, n_out, stats);
-    ctx_release(ctx);
-    return rc;
+    if ((rc = maxsim_groups_lock(s, fn, rd))) return rc;
+    return maxsim_groups_locked(s, d, groups, n_groups_listed, out, cap, n_out, stats, fn);
 }
 
 uint64_t ott_store_group_index_builds(const ott_store* s) { return s ? s->gix_builds.load(std::memory_order_relaxed) : 0ull; }

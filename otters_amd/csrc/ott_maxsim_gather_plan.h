@@ -1,8 +1,10 @@
 // ott_maxsim_gather_plan.h — what the host decides for ott_query_maxsim_groups (ott_maxsim_gather.hip) before it
 // launches anything: how many tokens share a pass of the gather kernel and what that costs in LDS, the slot arrays of a list of
 // groups (ascending, duplicate-free, with each group's extent in the group-to-rows index), the sizes of the two tables, which of
-// the two routes a query takes and the 2 GiB refusal.  HIP-free: tests/test_maxsim_groups_cpu.py compiles it with the host compiler
-// and holds it to a plain Python restatement.
+// the two routes a query takes and the 2 GiB refusal; and for ott_query_maxsim_groups_batch (ott_maxsim_batch.hip)
+// the slots of a batch of queries, its stride and token width, its route and the split of the slots over the workgroups.  HIP-free:
+// tests/test_maxsim_groups_cpu.py and tests/test_maxsim_batch_cpu.py compile it with the host compiler and hold it to a plain
+// Python restatement.
 #pragma once
 
 #include <stdint.h>
@@ -98,6 +100,72 @@ inline bool mg_takes_gather(bool wants_index, bool have_index, int group_gather,
     if (!wants_index || !have_index) return false;
     if (n_slots > MG_MAX_SLOTS || listed_rows > MG_MAX_ROWS) return false;
     return group_gather == 1 || listed_rows <= MG_AUTO_MAX_ROWS;
+}
+
+// ---- a batch of queries, each with its own tokens and its own list (ott_query_maxsim_groups_batch) ----------------
+// The slots of every query (mg_slots: ascending, duplicate-free, with extents) back to back in query order: slot i belongs to query
+// query[i] and is that query's pos[i]-th slot, so its key goes to keys[query[i] * S + pos[i]] with the stride S = the largest number
+// of distinct listed groups of any query.  NT: the token width every query of the batch runs at (the widest query decides; a
+// narrower query's block is zero padded and its sum stops at its own tokens).
+struct MgBatch {
+    std::vector<uint32_t> gid, start, count, query, pos;  // [T]; start / count only with the index's extents
+    std::vector<uint32_t> tokens, distinct;               // [B]
+    std::vector<uint64_t> rows_of;                        // [B] listed rows of the query (0 without the extents)
+    uint32_t S = 0, NT = 0, max_tokens = 0;
+    uint64_t rows = 0;      // listed rows of all queries
+    uint64_t compared = 0;  // sum over the queries of listed rows x tokens
+};
+inline void mg_batch_build(const uint32_t* groups, const uint32_t* tokens_per_query, const uint64_t* listed_per_query, uint32_t n_queries, uint32_t n_groups,
+                           const uint32_t* starts, uint32_t dimq, MgBatch& out) {
+    out = MgBatch();
+    out.tokens.assign(tokens_per_query, tokens_per_query + n_queries);
+    out.distinct.resize(n_queries);
+    out.rows_of.resize(n_queries);
+    MgSlots sl;
+    uint64_t at = 0;
+    for (uint32_t b = 0; b < n_queries; b++) {
+        mg_slots(groups + at, listed_per_query[b], n_groups, starts, sl);
+        at += listed_per_query[b];
+        const uint32_t n = (uint32_t)sl.gid.size();  // (distinct ids of a store of fewer than 2^32 groups)
+        out.distinct[b] = n;
+        out.rows_of[b] = sl.rows;
+        out.rows += sl.rows;
+        out.compared += sl.rows * tokens_per_query[b];
+        out.S = std::max(out.S, n);
+        out.max_tokens = std::max(out.max_tokens, tokens_per_query[b]);
+        out.gid.insert(out.gid.end(), sl.gid.begin(), sl.gid.end());
+        out.start.insert(out.start.end(), sl.start.begin(), sl.start.end());
+        out.count.insert(out.count.end(), sl.count.begin(), sl.count.end());
+        out.query.insert(out.query.end(), n, b);
+        for (uint32_t i = 0; i < n; i++) out.pos.push_back(i);
+    }
+    out.NT = mg_tokens_per_pass(dimq, out.max_tokens);
+}
+// The batched gather serves the batch when every query fits one token pass (the sum is made in the kernel; the [nq][n_slots] table
+// of a second pass is not carried over), the key table and the rows stay within the launch limits, and the option says so: 1, or -1
+// and every query alone would take the gather — a batch of queries that each prefer the gather only loses per-call overheads.
+// Everything else is answered query by query (the loop route).
+inline bool mg_batch_takes_gather(bool wants_index, bool have_index, int group_gather, uint32_t dimq, const MgBatch& mb) {
+    if (!wants_index || !have_index) return false;
+    if (mb.max_tokens > mg_tokens_cap(dimq)) return false;
+    if ((uint64_t)mb.tokens.size() * mb.S > MG_MAX_SLOTS || mb.rows > MG_MAX_ROWS) return false;
+    if (group_gather == 1) return true;
+    for (const uint64_t r : mb.rows_of)
+        if (r > MG_AUTO_MAX_ROWS) return false;
+    return true;
+}
+// Workgroup w of n_workgroups walks the contiguous slots [first[w], first[w + 1]) (first: n_workgroups + 1 entries), balanced by
+// listed rows: slot i weighs counts[i] + 1 (an empty group still costs a visit), P[i] = the weight before slot i, W = the total, and
+// first[w] = the number of slots with P[i] x n_workgroups < w x W.  Every slot belongs to exactly one workgroup, first never
+// decreases, and a workgroup's weight differs from W / n_workgroups by less than the heaviest slot's.
+inline void mg_batch_split(const uint32_t* counts, uint64_t T, uint32_t n_workgroups, uint32_t* first) {
+    uint64_t W = 0;
+    for (uint64_t i = 0; i < T; i++) W += (uint64_t)counts[i] + 1;  // (at most MG_MAX_ROWS + MG_MAX_SLOTS: the products below fit 64 bits)
+    uint64_t i = 0, P = 0;
+    for (uint32_t w = 0; w <= n_workgroups; w++) {
+        while (i < T && P * n_workgroups < (uint64_t)w * W) P += (uint64_t)counts[i++] + 1;
+        first[w] = (uint32_t)i;
+    }
 }
 
 }  // namespace ott

@@ -144,7 +144,31 @@ def dense_group_ids(ids):
     return np.ascontiguousarray(inv.reshape(-1).astype(np.uint32)), int(uniq.size)
 
 
+def dense_listed_groups(store: "VecStore", listed) -> np.ndarray:
+    """with_groups' labels as uint32 dense group ids of `store`, in the caller's order, duplicates kept (the library sorts and dedupes
+    them); a label no row carries raises OttersError.  Pure host logic."""
+    a = np.asarray(listed)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.uint32)
+    a = a.ravel()
+    if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+        raise OttersError(f"group labels must be integers, not {a.dtype}")
+    labels = store.group_labels()
+    if labels is None:  # the ids were set dense: a label is an id
+        bad = (a < 0) | (a >= store.group_count()) if np.issubdtype(a.dtype, np.signedinteger) else (a >= store.group_count())
+        if bad.any():
+            raise OttersError(f"with_groups: group {int(a[bad][0])} is not one of the store's {store.group_count()} groups")
+        return np.ascontiguousarray(a.astype(np.uint32))
+    at = np.searchsorted(labels, a)  # labels: sorted and duplicate-free (np.unique)
+    at_c = np.minimum(at, labels.size - 1)
+    bad = labels[at_c] != a
+    if bad.any():
+        raise OttersError(f"with_groups: no row carries the group label {int(a[bad][0])}")
+    return np.ascontiguousarray(at_c.astype(np.uint32))
+
+
 GROUP_SIZE_MAX = 16  # include/otters_hip.h: OTT_GROUP_SIZE_MAX
+MAXSIM_BATCH_MAX = 4096  # include/otters_hip.h: OTT_MAXSIM_BATCH_MAX
 
 
 def infer_default_take_type(metric: Metric) -> TakeType:  # src/vec.rs:92-98
@@ -285,25 +309,7 @@ class VecQueryPlan:
 
     def _dense_group_list(self) -> np.ndarray:
         """with_groups' labels as uint32 dense group ids, in the caller's order (the library sorts and dedupes them)"""
-        a = np.asarray(self.group_list)
-        if a.size == 0:
-            return np.zeros(0, dtype=np.uint32)
-        a = a.ravel()
-        if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
-            raise OttersError(f"group labels must be integers, not {a.dtype}")
-        store = self.vector_store
-        labels = store.group_labels()
-        if labels is None:  # the ids were set dense: a label is an id
-            bad = (a < 0) | (a >= store.group_count()) if np.issubdtype(a.dtype, np.signedinteger) else (a >= store.group_count())
-            if bad.any():
-                raise OttersError(f"with_groups: group {int(a[bad][0])} is not one of the store's {store.group_count()} groups")
-            return np.ascontiguousarray(a.astype(np.uint32))
-        at = np.searchsorted(labels, a)  # labels: sorted and duplicate-free (np.unique)
-        at_c = np.minimum(at, labels.size - 1)
-        bad = labels[at_c] != a
-        if bad.any():
-            raise OttersError(f"with_groups: no row carries the group label {int(a[bad][0])}")
-        return np.ascontiguousarray(at_c.astype(np.uint32))
+        return dense_listed_groups(self.vector_store, self.group_list)
 
     # -- execution -----------------------------------------------------------------------------
     def validate(self) -> None:  # src/vec.rs:170-203
@@ -435,6 +441,126 @@ class VecQueryPlan:
         if rq.group_size:
             return hits, counts, rq.group_of_hit if rq.group_of_hit is not None else np.zeros(0, dtype=np.uint32)
         return hits, counts
+
+
+@dataclass
+class ResolvedMaxSimBatch:
+    """What MaxSimBatchPlan hands to ott_query_maxsim_groups_batch once it is validated."""
+    queries: np.ndarray            # [sum of tokens, dim] f32: the tokens of query 0, then of query 1, ...
+    tokens_per_query: np.ndarray   # uint32[B]
+    listed_per_query: np.ndarray   # uint64[B]
+    groups: np.ndarray             # uint32[sum of listed]: the lists back to back, dense ids in the caller's order, duplicates kept
+    distinct_per_query: list       # [B] distinct listed groups of every query
+    metric: int
+    take: int
+    k: int
+    filter_cmp: int
+    filter_thr: float
+    row_mask: Optional[np.ndarray]
+
+
+class MaxSimBatchPlan:
+    """MaxSim re-ranking in batches (VecStore.max_sim_batch; ott_query_maxsim_groups_batch): B queries, each with its own tokens and
+    its own list of groups, through one call.  Query b's result is exactly that of
+    store.query(token_sets[b], metric).max_sim().with_groups(lists[b]) with the same take, filter and row mask.  Lazy like
+    VecQueryPlan: errors surface at validate() / collect()."""
+
+    def __init__(self, store: "VecStore", token_sets, metric: Metric):
+        self.vector_store = store
+        self.token_sets = [QueryBatch(t).queries for t in token_sets]
+        self.search_metric = Metric(metric)
+        self.group_lists = None
+        self.filter_criteria: Optional[tuple] = None
+        self.take_type: Optional[TakeType] = None
+        self.take_count: Optional[int] = None
+        self.row_mask: Optional[np.ndarray] = None
+
+    def with_groups(self, lists_of_labels) -> "MaxSimBatchPlan":
+        """One list of group labels per token set, mapped as VecQueryPlan.with_groups maps them: any order, duplicates allowed, two
+        queries may list the same group, an empty list is a query with no hits.  Required in this version."""
+        self.group_lists = list(lists_of_labels)
+        return self
+
+    def with_row_mask(self, mask) -> "MaxSimBatchPlan":
+        self.row_mask = np.asarray(mask, dtype=bool).ravel()
+        return self
+
+    def filter(self, score: float, cmp: Cmp) -> "MaxSimBatchPlan":
+        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
+        return self
+
+    def _take_with_options(self, count: int, take_type: Optional[TakeType]) -> "MaxSimBatchPlan":
+        self.take_count = int(count)
+        if take_type is not None:
+            self.take_type = take_type
+        elif self.take_type is None:
+            self.take_type = infer_default_take_type(self.search_metric)
+        return self
+
+    def take(self, count: int) -> "MaxSimBatchPlan":
+        return self._take_with_options(count, None)
+
+    def take_min(self, count: int) -> "MaxSimBatchPlan":
+        return self._take_with_options(count, TakeType.Min)
+
+    def take_max(self, count: int) -> "MaxSimBatchPlan":
+        return self._take_with_options(count, TakeType.Max)
+
+    def validate(self) -> None:
+        n = len(self.token_sets)
+        if n == 0:
+            raise OttersError("max_sim_batch: no token sets provided")
+        if n > MAXSIM_BATCH_MAX:
+            raise OttersError(f"max_sim_batch: {n} token sets; a batch holds at most {MAXSIM_BATCH_MAX}")
+        if self.group_lists is None:
+            raise OttersError("max_sim_batch needs with_groups in this version: one list of groups per token set")
+        if len(self.group_lists) != n:
+            raise OttersError(f"max_sim_batch: with_groups got {len(self.group_lists)} lists for {n} token sets")
+        dim = self.vector_store.dim
+        for b, t in enumerate(self.token_sets):
+            if len(t) == 0:
+                raise OttersError(f"max_sim_batch: token set {b} is empty")
+            for q in ([t[0]] if isinstance(t, np.ndarray) else t):
+                if len(q) != dim:
+                    raise OttersError(f"Query vector length {len(q)} does not match expected dimension {dim}")
+        for listed in self.group_lists:
+            dense_listed_groups(self.vector_store, listed)
+
+    def resolve(self) -> ResolvedMaxSimBatch:
+        """Validate and lower the plan.  Pure host logic, no GPU."""
+        self.validate()
+        sets = [t if isinstance(t, np.ndarray) else np.stack(t).astype(np.float32, copy=False) for t in self.token_sets]
+        lists = [dense_listed_groups(self.vector_store, listed) for listed in self.group_lists]
+        distinct = [int(np.unique(g).size) for g in lists]
+        k = self.take_count if self.take_count is not None else max(distinct)  # the default take: the largest number of distinct listed groups
+        take = self.take_type if self.take_type is not None else TakeType.Max
+        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
+        return ResolvedMaxSimBatch(queries=np.ascontiguousarray(np.concatenate(sets), dtype=np.float32),
+                                   tokens_per_query=np.array([t.shape[0] for t in sets], dtype=np.uint32),
+                                   listed_per_query=np.array([g.size for g in lists], dtype=np.uint64),
+                                   groups=np.ascontiguousarray(np.concatenate(lists), dtype=np.uint32), distinct_per_query=distinct,
+                                   metric=int(self.search_metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask)
+
+    def collect_arrays(self):
+        """(hits, counts): `hits` as VecQueryPlan.collect_arrays returns them for a max_sim plan — `index` the dense group id, `score`
+        the sum — every query's list best first, back to back in query order, `query` = the query of the batch; counts[b] = the number
+        of hits of query b."""
+        store = self.vector_store
+        hits, counts, stats = store._run_maxsim_batch(self.resolve())
+        store.last_stats = stats
+        return hits, counts
+
+    def collect(self):
+        """One list of SearchResult(label, score) per query, with the caller's own group labels."""
+        hits, counts = self.collect_arrays()
+        labels = self.vector_store.group_labels()
+        idx = hits["index"].astype(np.int64)
+        lab, sc = (idx if labels is None else labels[idx]).tolist(), hits["score"].tolist()
+        out, o = [], 0
+        for c in counts:
+            out.append([SearchResult(i, x) for i, x in zip(lab[o:o + c], sc[o:o + c])])
+            o += c
+        return out
 
 
 class VecStore:
@@ -790,6 +916,43 @@ class VecStore:
         stats = st.as_dict()
         if rq.group_list is not None:  # how often this store has built its group-to-rows index so far
             stats["group_index_builds"] = int(N.lib().ott_store_group_index_builds(self._handle()))
+        return hits, list(per), stats
+
+    def max_sim_batch(self, token_sets, metric: Metric) -> MaxSimBatchPlan:
+        """MaxSim re-ranking for many queries at once (ott_query_maxsim_groups_batch): `token_sets` is a sequence of token matrices,
+        one per query; .with_groups(lists) gives every query its own candidate list."""
+        return MaxSimBatchPlan(self, token_sets, metric)
+
+    def _run_maxsim_batch(self, rb: ResolvedMaxSimBatch, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
+        """ott_query_maxsim_groups_batch.  Returns (hits HIT_DTYPE array, per-query counts, stats dict)."""
+        B = int(rb.tokens_per_query.size)
+        cap = max(sum(min(rb.k, n) for n in rb.distinct_per_query), 1)
+        out = np.empty(cap, dtype=N.HIT_DTYPE)
+        d = N.QueryDesc()
+        d.queries = rb.queries.ctypes.data
+        d.nq = int(rb.queries.shape[0])
+        d.metric, d.take, d.filter_cmp, d.filter_thr = rb.metric, rb.take, rb.filter_cmp, rb.filter_thr
+        d.mode, d.k, d.path = int(Mode.Merged), rb.k, int(Path.Auto)
+        keep = []
+        if chunk_mask is not None:
+            cm = N.pack_bits(chunk_mask)
+            keep.append(cm)
+            d.chunk_mask = cm.ctypes.data
+        if use_device_row_mask:
+            d.use_device_row_mask = 1
+        elif rb.row_mask is not None and rb.row_mask.size:
+            rm = N.pack_bits(rb.row_mask)
+            keep.append(rm)
+            d.row_mask = rm.ctypes.data
+            d.row_mask_bits = int(rb.row_mask.size)
+        n_out = C.c_uint64(0)
+        per = (C.c_uint64 * B)()
+        st = N.Stats()
+        N.check(N.lib().ott_query_maxsim_groups_batch(self._handle(), C.byref(d), N.ptr(rb.tokens_per_query), N.ptr(rb.listed_per_query), B,
+                                                      N.ptr(rb.groups) if rb.groups.size else None, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        hits = out if n_out.value == cap else out[: n_out.value].copy()
+        stats = st.as_dict()
+        stats["group_index_builds"] = int(N.lib().ott_store_group_index_builds(self._handle()))
         return hits, list(per), stats
 
     def score_rows(self, queries, metric: Metric, ids) -> np.ndarray:
