@@ -93,15 +93,23 @@ void fill_exact_params(ott_store* s, const ott_query_desc* d, const RunPlan& pl,
     p.flat = s->cur_flat ? 1u : 0u;
 }
 
+void embed_exact_inputs(ExactParams& p, const void* query, size_t query_bytes, float inv_norm, const RunPlan& pl, const std::vector<uint32_t>& prefix) {
+    p.embedded = 1;
+    p.queries = nullptr;
+    p.qinv = nullptr;
+    p.runs = nullptr;
+    p.tile_prefix = nullptr;
+    memcpy(p.qemb, query, query_bytes);  // the tail up to dimq stays zero (fill_exact_params cleared the struct)
+    p.eqinv = inv_norm;
+    memset(p.eruns, 0, sizeof(p.eruns));  // (a copy of another launch's parameters may hold that launch's runs)
+    memset(p.eprefix, 0, sizeof(p.eprefix));
+    for (size_t i = 0; i < pl.runs.size(); i++) p.eruns[i] = pl.runs[i];
+    for (size_t i = 0; i < prefix.size(); i++) p.eprefix[i] = prefix[i];
+}
+
 }  // namespace ott
 
 namespace {
-
-uint32_t pow2ceil(uint32_t v) {
-    uint32_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
 
 // chunk mask -> runs of consecutive surviving chunks (candidate_chunks, src/meta.rs:648-659)
 void build_plan(const ott_store* s, const uint64_t* chunk_mask, RunPlan& pl) {
@@ -170,240 +178,213 @@ __global__ void sum_counts_kernel(const uint64_t* counts, uint32_t n, uint64_t* 
     if (threadIdx.x == 0) *out = t;
 }
 
-// the large-store seed of the pruned sweep's wide sketch forms: rows / 32 (run_exact).  Experiment builds: -DOTT_X_SEED_DIV=64
-#ifndef OTT_X_SEED_DIV
-#define OTT_X_SEED_DIV 32
-#endif
-// EXACT path.  queries: host [nq*dim].  Results: per group (1 for merged, nq for per-query) on the
-// host in `lists`.  `perq` selects the grouping.  If dev_copy != nullptr (merged only) the merged
-// list is also left in device memory at s->d_hits (KS slots, sentinel padded) for ott_query_device.
-int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_desc* d, bool perq, const RunPlan& pl, uint64_t k_eff,
-              const uint64_t* d_mask, uint64_t mask_bits, bool fetch, std::vector<std::vector<ott_hit>>& lists, ott_stats& st,
-              bool timing = true, ott_hit* hits_dev_direct = nullptr, uint32_t direct_stride = 0) {
-    // hits_dev_direct (device output only): the merge kernel writes its [groups][KS] sentinel-padded hits straight there
-    // (direct_stride must be the KS this call derives from k_eff) instead of into d_hits
-    if (k_eff > 512) {  // beyond the fused register top-k: score dump + device radix sort
-        if (!fetch) return fail(OTT_ERR_UNSUPPORTED, "ott_query_device: k > 512 is host-output only");
-        return run_large_k(s, queries, nq, d, perq, pl, k_eff, d_mask, mask_bits, lists, st);
-    }
-    // 128 < k <= 512 — four and eight list entries per lane — against the sort path (profiles/round3/large_k_from.md).  Round 2:
-    // the lists lost from 256 up (9.7 against 6.0 ms at 10M x 768, k = 512), and once the sort path's second phase listed only
-    // what can still make the result they lost from 128 up.  With candidates merged into the lists as sorted blocks
-    // (wl_merge_sorted) and the block lists merged by rank (merge_rank_kernel) a SINGLE query is faster on the lists at every k
-    // they hold and every store size measured (10k rows: 0.16 against 0.23 ms at k = 512; 10M rows: 4.81 against 4.93).  Several
-    // queries still go to the sort path from 128 up — its sweep carries four of them, a sweep of the long lists one: 1M rows, 4
-    // queries, k = 300: 1.0 against 2.5 ms — unless the store is small (100k rows x 4 queries: lists 0.45 against 0.58 ms).
-    {
-        const uint64_t pairs = pl.rows_scored * nq;
-        const uint64_t from = s->opt.large_k_from > 0 ? (uint64_t)s->opt.large_k_from : ((nq == 1 || pairs <= (1ull << 19)) ? 512u : 128u);
-        if (k_eff > from && fetch && pairs <= (1ull << 28))
-            return run_large_k(s, queries, nq, d, perq, pl, k_eff, d_mask, mask_bits, lists, st);
-    }
-    int E = k_eff <= 64 ? 1 : k_eff <= 128 ? 2 : k_eff <= 256 ? 4 : 8;
-    const uint32_t KS = 64 * E;
-    const std::vector<uint32_t> prefix = tile_prefix(pl, 64);
-    const uint32_t n_tiles = prefix.back();
-    // 0 = the streaming kernel, 1 = the one-wave small-grid variant (LDS-DMA ring; single query), 2 = rows8: eight lanes per
-    // row, one 8-wave workgroup per tile, up to 8 queries per pass (round 3: 10k x 768 in 25-30 us instead of 64; the
-    // default wherever a small variant fits: stores of up to 1024 tiles ~ 65k rows, batches of up to 16 queries)
-    uint32_t small = 0;
-    {
-        const int forced = s->opt.exact_small;  // store option: 0 / 1 / 2 forces the choice
-        const bool fits1 = nq == 1 && !perq && E <= 2 && s->dimq <= 2048 && n_tiles <= 1024;
-        const bool fits8 = E <= 2 && s->dimq <= 2048 && n_tiles <= 1024 && nq <= 16;
-        if (forced == 1) small = fits1 ? 1u : 0u;
-        else if (forced == 2 || forced < 0) small = fits8 ? 2u : 0u;
-    }
-    uint32_t tile;
-    // queries per corpus pass: 4 is the measured sweet spot of the streaming kernel (1-2 queries 4.95 ms, 4 queries 5.3 ms per
-    // pass at 10M x 768; an 8-wide pass needs 233 VGPRs and ran 14 ms, slower than two 4-wide passes); rows8 takes up to 8
-    // (one accumulator per query and lane)
-    if (E >= 4) tile = 1;
-    else tile = pow2ceil(nq) < (small == 2 ? 8u : 4u) ? pow2ceil(nq) : (small == 2 ? 8u : 4u);
-    const uint32_t passes = (nq + tile - 1) / tile;
-    const int grid = small ? (int)n_tiles : exact_grid(s, n_tiles);
-
-    // single query, at most two runs: everything the kernel needs rides in its arguments (no H2D copy, no staging)
-    const bool lean = nq == 1 && s->dimq <= OTT_QEMB_MAX && pl.runs.size() <= 2;
-    // Pruned sweep (store option exact_prune): one query, merged, cosine / dot, the streaming kernel.  A seed of the
-    // first rows (how many: where `seed` is set below) is scored in full and merged; its k-th best gates the second launch over the
-    // rest, which skips the last stages (from c, 7/8 of them) of every row whose score bound misses it.  Automatic from 2^20 rows
-    // and 8 stages (dim >= 225).
-    // A store that keeps a tail sketch for every row (option exact_sketch) takes the sketch form in the store's own width (option
-    // exact_sketch_bits): the checkpoint is the sketch's first stage, stage 1 at four bits per dim, 3/8 of the stages at three, 3/4 at one.
-    uint32_t prune_c = 0;
-    bool prune_sk = false;
+// One call over the lists (k <= 512): what run_exact's stages share
+struct ExactCtx {
+    ott_store* s;
+    const float* queries;
+    uint32_t nq;
+    const ott_query_desc* d;
+    bool perq;
+    const RunPlan& pl;
+    uint64_t k_eff;
+    bool fetch, timing;
+    const std::vector<uint32_t>& prefix;  // the 64-row tiles of pl
+    ExactPlan x;                          // ott_exact_plan.h
+    uint32_t groups;                      // result groups: 1 merged, nq per query
+    // the pruned sweep (prune.c != 0): the seed's rows and the rest with their tiles and grids, the query's bounds
+    PrunePlan prune{0, false, 0};
     RunPlan plA, plB;
-    double prune_qt = 0.0, prune_qn = 0.0, prune_q1 = 0.0;
-    if (lean && !perq && small == 0 && !s->cur_flat && s->opt.exact_prune != 0 &&
-        (d->metric == OTT_METRIC_COSINE || d->metric == OTT_METRIC_DOT)) {
-        const uint32_t nst = (s->ld + 31) / 32;
-        uint32_t c = nst * 7 / 8;
-        while (c > 0 && c * 32 > s->dim - s->dim % 8) c--;  // the prefix holds whole chunks of eight only (no remainder term yet)
-        if (s->opt.exact_sketch != 0 && s->d_sketch != nullptr && s->sk_n >= s->n &&
-            s->sk_words <= (s->sk_bits == 4 ? OTT_SKETCH4_MAX_WORDS : s->sk_bits == 3 ? OTT_SKETCH_MAX_WORDS : OTT_SKETCH1_MAX_WORDS)) {
-            const uint32_t cs = s->sk_stage0;
-            if (cs >= 1 && cs < nst && cs * 32 <= s->dim - s->dim % 8) {
-                c = cs;
-                prune_sk = true;
-            }
-        }
-        const bool worth = s->opt.exact_prune == 1 || (nst >= 8 && pl.rows_scored >= (1ull << 20));
-        if (worth && c >= 1 && c < nst) {
-            // The seed: a tenth of the rows.  With the three- or four-bit sketch and k <= 64, once that is more than 131072 rows: a
-            // thirty-second of them, never fewer than 131072 (continuous at 1.31M rows; 10M rows: 312 512 rows read in full instead of
-            // 1M, 10M x 768 top-10 2.862 -> 2.753 ms).  A smaller seed gives a lower gate; the wide sketch loses few rows to that, but a
-            // longer list's k-th best sits deeper in the seed (k = 500 at 10M x 768: 3.54 -> 3.78 ms with the small seed), and the
-            // other forms save less per seed row (their checkpoint is at 3/4 or 7/8 of the row): those keep the tenth
-            uint64_t seed = pl.rows_scored / 10;
-            if (prune_sk && s->sk_bits >= 3 && E == 1 && seed > 131072) seed = pl.rows_scored / OTT_X_SEED_DIV > 131072 ? pl.rows_scored / OTT_X_SEED_DIV : 131072;
-            seed = (seed + 63) & ~63ull;
-            if (seed < 64) seed = 64;
-            split_plan(pl, seed, plA, plB);
-            if (plA.runs.size() <= 2 && plB.runs.size() <= 2 && plB.rows_scored > 0 &&
-                prune_query_bounds(queries, s->dim, c * 32, &prune_qt, &prune_qn)) {
-                prune_c = c;
-                prune_q1 = prune_query_l1(queries, s->dim, c * 32);
-            }
-        }
-    }
     std::vector<uint32_t> preA, preB;
     int gridA = 0, gridB = 0;
-    if (prune_c) {
-        preA = tile_prefix(plA, 64);
-        preB = tile_prefix(plB, 64);
-        gridA = exact_grid(s, preA.back());
-        gridB = exact_grid(s, preB.back());
-    }
+    double qt = 0.0, qn = 0.0, q1 = 0.0;
+    // the result block, as the merge kernel sees it
+    ExactResult res{0, 0, 0};
+    uint64_t* d_counts = nullptr;
+    ott_hit* d_hits = nullptr;
+    ExactParams p;
+};
+
+// Whether the pruned sweep runs, and over which rows: the header's plan, and the two conditions that need the runs and the query
+// themselves — the seed and the rest have at most two runs each (they ride in the kernel arguments) and the rest is not empty;
+// prune_query_bounds accepts the query
+void plan_pruned_sweep(ExactCtx& c) {
+    ott_store* s = c.s;
+    const PruneIn in{s->dim, s->ld, c.d->metric, c.perq, c.x.lean, s->cur_flat, c.x.variant, s->opt.exact_prune, s->opt.exact_sketch,
+                     SketchState{s->d_sketch != nullptr, s->sk_n >= s->n, s->sk_bits, s->sk_words, s->sk_stage0}, c.pl.rows_scored, c.x.E};
+    const PrunePlan pp = prune_plan(in);
+    if (!pp.c) return;
+    split_plan(c.pl, pp.seed, c.plA, c.plB);
+    const bool two_runs_each = c.plA.runs.size() <= 2 && c.plB.runs.size() <= 2 && c.plB.rows_scored > 0;
+    if (!two_runs_each || !prune_query_bounds(c.queries, s->dim, pp.c * 32, &c.qt, &c.qn)) return;
+    c.prune = pp;
+    c.q1 = prune_query_l1(c.queries, s->dim, pp.c * 32);
+    c.preA = tile_prefix(c.plA, 64);
+    c.preB = tile_prefix(c.plB, 64);
+    c.gridA = exact_grid(s, c.preA.back());
+    c.gridB = exact_grid(s, c.preB.back());
+}
+
+// the inputs on the device (unless they ride in the arguments), room for the block lists, and the result block
+int ensure_exact_result(ExactCtx& c) {
+    ott_store* s = c.s;
     int rc;
-    if (!lean && (rc = upload_exact_inputs(s, queries, nq, pl, prefix))) return rc;
-    const size_t n_lists_total = prune_c ? (size_t)(gridA + gridB) : perq ? (size_t)nq * grid : (size_t)passes * grid;
-    if ((rc = s->d_lists.ensure(n_lists_total * KS * sizeof(Cand)))) return rc;
-    const uint32_t groups = perq ? nq : 1;
+    if (!c.x.lean && (rc = upload_exact_inputs(s, c.queries, c.nq, c.pl, c.prefix))) return rc;
+    const size_t n_lists_total = exact_n_lists(c.x, c.nq, c.perq, c.prune.c != 0, c.gridA, c.gridB);
+    if ((rc = s->d_lists.ensure(n_lists_total * c.x.KS * sizeof(Cand)))) return rc;
     // results block: [counts (groups x u64, padded to 64 B) | hits (groups x KS)].  Host output: the merge kernel
     // writes it straight into pinned host memory (no D2H copy behind the launch); device output: into d_hits
-    const size_t cnt_pad = (((size_t)groups * sizeof(uint64_t)) + 63) & ~(size_t)63;
-    const size_t res_bytes = cnt_pad + (size_t)groups * KS * sizeof(ott_hit);
+    c.res = exact_result_layout(c.groups, c.x.KS);
     char* res_dev = nullptr;
-    if (fetch) {
-        if ((rc = s->h_hits.ensure(res_bytes + 8))) return rc;  // (+ 8: the pruned sweep's tail counter)
+    if (c.fetch) {
+        if ((rc = s->h_hits.ensure(c.res.host_bytes))) return rc;  // (+ 8: the pruned sweep's tail counter)
         void* mapped = nullptr;
         OTT_HIP(hipHostGetDevicePointer(&mapped, s->h_hits.p, 0));
         res_dev = (char*)mapped;
     } else {
-        if ((rc = s->d_hits.ensure(res_bytes))) return rc;
+        if ((rc = s->d_hits.ensure(c.res.bytes))) return rc;
         res_dev = (char*)s->d_hits.p;
     }
-    uint64_t* d_counts = (uint64_t*)res_dev;
-    ott_hit* d_hits = (ott_hit*)(res_dev + cnt_pad);
-    s->res_hits_off = cnt_pad;
-    if (!fetch && hits_dev_direct != nullptr && direct_stride == KS) d_hits = hits_dev_direct;
+    c.d_counts = (uint64_t*)res_dev;
+    c.d_hits = (ott_hit*)(res_dev + c.res.cnt_pad);
+    return OTT_OK;
+}
 
-    ExactParams p;
-    fill_exact_params(s, d, pl, nq, d_mask, mask_bits, n_tiles, p);
-    p.k = (uint32_t)k_eff;
-    p.perq = perq;
-    p.list_stride = KS;
-    p.small = small;
-    if (lean) {
-        p.embedded = 1;
-        p.queries = nullptr;
-        p.qinv = nullptr;
-        p.runs = nullptr;
-        p.tile_prefix = nullptr;
-        memcpy(p.qemb, queries, (size_t)s->dim * 4);  // the tail up to dimq stays zero (fill_exact_params cleared the struct)
-        p.eqinv = host_inv_norm_exact(queries, s->dim);
-        for (size_t i = 0; i < pl.runs.size(); i++) p.eruns[i] = pl.runs[i];
-        for (size_t i = 0; i < prefix.size(); i++) p.eprefix[i] = prefix[i];
+void fill_exact_call(ExactCtx& c, const uint64_t* d_mask, uint64_t mask_bits) {
+    ott_store* s = c.s;
+    fill_exact_params(s, c.d, c.pl, c.nq, d_mask, mask_bits, c.prefix.back(), c.p);
+    c.p.k = (uint32_t)c.k_eff;
+    c.p.perq = c.perq;
+    c.p.list_stride = c.x.KS;
+    c.p.small = c.x.variant;
+    if (c.x.lean) embed_exact_inputs(c.p, c.queries, (size_t)s->dim * 4, host_inv_norm_exact(c.queries, s->dim), c.pl, c.prefix);
+}
+
+// the call's parameters over a part of its rows (the pruned sweep's seed, or the rest), its block lists at dst
+ExactParams part_params(const ExactCtx& c, const RunPlan& sub, const std::vector<uint32_t>& pre, Cand* dst) {
+    ExactParams q = c.p;
+    q.n_runs = (uint32_t)sub.runs.size();
+    q.n_tiles = pre.back();
+    embed_exact_inputs(q, c.queries, (size_t)c.s->dim * 4, c.p.eqinv, sub, pre);
+    q.lists = dst;
+    return q;
+}
+
+// The pruned sweep: the seed launch, its merge, and the gated launch over the rest
+int pruned_sweep(ExactCtx& c) {
+    ott_store* s = c.s;
+    const uint32_t KS = c.x.KS;
+    int rc;
+    // [count (u64, 64 B) | KS hits]: the seed's merged result, read by the second launch
+    if ((rc = s->d_prune.ensure(64 + (size_t)KS * sizeof(ott_hit)))) return rc;
+    uint64_t* seed_res = (uint64_t*)s->d_prune.p;
+    // the kernel's count of finished tails: a running total in device memory, read back with the result (host output only)
+    unsigned long long* tails_dev = nullptr;
+    if (c.fetch) {
+        if (!s->d_tails.p) {
+            if ((rc = s->d_tails.ensure(8))) return rc;
+            OTT_HIP(hipMemsetAsync(s->d_tails.p, 0, 8, s->stream));
+            s->tails_seen = 0;
+        }
+        tails_dev = (unsigned long long*)s->d_tails.p;
     }
-
-    if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
-    if (prune_c) {
-        // [count (u64, 64 B) | KS hits]: the seed's merged result, read by the second launch
-        if ((rc = s->d_prune.ensure(64 + (size_t)KS * sizeof(ott_hit)))) return rc;
-        uint64_t* seed_res = (uint64_t*)s->d_prune.p;
-        // the kernel's count of finished tails: a running total in device memory, read back with the result (host output only)
-        unsigned long long* tails_dev = nullptr;
-        if (fetch) {
-            if (!s->d_tails.p) {
-                if ((rc = s->d_tails.ensure(8))) return rc;
-                OTT_HIP(hipMemsetAsync(s->d_tails.p, 0, 8, s->stream));
-                s->tails_seen = 0;
-            }
-            tails_dev = (unsigned long long*)s->d_tails.p;
-        }
-        auto part = [&](const RunPlan& sub, const std::vector<uint32_t>& pre, Cand* dst) {
-            ExactParams q = p;
-            q.n_runs = (uint32_t)sub.runs.size();
-            q.n_tiles = pre.back();
-            memset(q.eruns, 0, sizeof(q.eruns));
-            memset(q.eprefix, 0, sizeof(q.eprefix));
-            for (size_t i = 0; i < sub.runs.size(); i++) q.eruns[i] = sub.runs[i];
-            for (size_t i = 0; i < pre.size(); i++) q.eprefix[i] = pre[i];
-            q.lists = dst;
-            return q;
-        };
-        const ExactParams pa = part(plA, preA, (Cand*)s->d_lists.p);
-        if ((rc = launch_exact(s, pa, 1, E, gridA))) return rc;
-        if ((rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)gridA, KS, 0, 1, (uint32_t)k_eff, E, p.take_max != 0, tie_base(s),
-                               (ott_hit*)(seed_res + 8), KS, seed_res, s->cur_tie_sh)))
-            return rc;
-        ExactParams pb = part(plB, preB, (Cand*)s->d_lists.p + (size_t)gridA * KS);
-        pb.prune_stage = prune_c;
-        pb.prune_seed = seed_res;
-        pb.prune_qt = prune_qt;
-        pb.prune_qn = prune_qn;
-        pb.prune_tails = tails_dev;
-        if (prune_sk) {
-            pb.prune_sketch = s->d_sketch;
-            pb.sk_pitch = s->sk_pitch;
-            pb.sk_stage0 = s->sk_stage0;
-            pb.sk_bits = s->sk_bits;
-            pb.prune_q1 = prune_q1;
-        }
-        if ((rc = launch_exact(s, pb, 1, E, gridB))) return rc;
-    } else {
-        for (uint32_t ps = 0; ps < passes; ps++) {
-            p.q0 = ps * tile;
-            // merged: one list group per pass.  per-query: list (query, block) lives at (query*grid + block)*KS; a
-            // 1-query pass runs the single-list kernel, so it is pointed at its query's slot (q0 == ps there)
-            p.lists = (Cand*)s->d_lists.p + ((perq && tile > 1) ? 0 : (size_t)ps * grid * KS);
-            if ((rc = launch_exact(s, p, (int)tile, E, grid))) return rc;
-        }
+    const ExactParams pa = part_params(c, c.plA, c.preA, (Cand*)s->d_lists.p);
+    if ((rc = launch_exact(s, pa, 1, c.x.E, c.gridA))) return rc;
+    if ((rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)c.gridA, KS, 0, 1, (uint32_t)c.k_eff, c.x.E, c.p.take_max != 0, tie_base(s),
+                           (ott_hit*)(seed_res + 8), KS, seed_res, s->cur_tie_sh)))
+        return rc;
+    ExactParams pb = part_params(c, c.plB, c.preB, (Cand*)s->d_lists.p + (size_t)c.gridA * KS);
+    pb.prune_stage = c.prune.c;
+    pb.prune_seed = seed_res;
+    pb.prune_qt = c.qt;
+    pb.prune_qn = c.qn;
+    pb.prune_tails = tails_dev;
+    if (c.prune.sketch) {
+        pb.prune_sketch = s->d_sketch;
+        pb.sk_pitch = s->sk_pitch;
+        pb.sk_stage0 = s->sk_stage0;
+        pb.sk_bits = s->sk_bits;
+        pb.prune_q1 = c.q1;
     }
-    if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
-    if (prune_c)  // the block lists of both launches
-        rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)(gridA + gridB), KS, 0, 1, (uint32_t)k_eff, E, p.take_max != 0,
-                          tie_base(s), d_hits, KS, d_counts, s->cur_tie_sh);
-    else if (perq)
-        rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)grid, KS, (uint64_t)grid * KS, nq, (uint32_t)k_eff, E,
-                          p.take_max != 0, tie_base(s), d_hits, KS, d_counts, s->cur_tie_sh);
-    else
-        rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)(passes * grid), KS, 0, 1, (uint32_t)k_eff, E, p.take_max != 0,
-                          tie_base(s), d_hits, KS, d_counts, s->cur_tie_sh);
-    if (rc) return rc;
-    if (timing) OTT_HIP(hipEventRecord(s->ev[5], s->stream));
-    st.passes += passes;
-    st.bytes_scanned += (uint64_t)passes * pl.rows_scored * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));
-    if (!fetch) return OTT_OK;
+    return launch_exact(s, pb, 1, c.x.E, c.gridB);
+}
 
+int plain_passes(ExactCtx& c) {
+    ott_store* s = c.s;
+    const uint32_t tile = c.x.tile;
+    int rc;
+    for (uint32_t ps = 0; ps < c.x.passes; ps++) {
+        c.p.q0 = ps * tile;
+        // merged: one list group per pass.  per-query: list (query, block) lives at (query*grid + block)*KS; a
+        // 1-query pass runs the single-list kernel, so it is pointed at its query's slot (q0 == ps there)
+        c.p.lists = (Cand*)s->d_lists.p + ((c.perq && tile > 1) ? 0 : (size_t)ps * c.x.grid * c.x.KS);
+        if ((rc = launch_exact(s, c.p, (int)tile, c.x.E, c.x.grid))) return rc;
+    }
+    return OTT_OK;
+}
+
+// the block lists into the result block: per query every query's own `grid` lists, else all of them (the pruned sweep: of both launches)
+int merge_exact(ExactCtx& c) {
+    ott_store* s = c.s;
+    const uint32_t KS = c.x.KS, grid = (uint32_t)c.x.grid;
+    const uint32_t n_lists = c.perq ? grid : (uint32_t)exact_n_lists(c.x, c.nq, false, c.prune.c != 0, c.gridA, c.gridB);
+    return launch_merge(s, (const Cand*)s->d_lists.p, n_lists, KS, c.perq ? (uint64_t)grid * KS : 0, c.groups, (uint32_t)c.k_eff, c.x.E,
+                        c.p.take_max != 0, tie_base(s), c.d_hits, KS, c.d_counts, s->cur_tie_sh);
+}
+
+// host output: the one wait, then the lists out of the pinned block
+int fetch_exact(ExactCtx& c, std::vector<std::vector<ott_hit>>& lists, ott_stats& st) {
+    ott_store* s = c.s;
+    const uint32_t KS = c.x.KS;
     char* hh = (char*)s->h_hits.p;
-    if (prune_c) OTT_HIP(hipMemcpyAsync(hh + res_bytes, s->d_tails.p, 8, hipMemcpyDeviceToHost, s->stream));
+    if (c.prune.c) OTT_HIP(hipMemcpyAsync(hh + c.res.bytes, s->d_tails.p, 8, hipMemcpyDeviceToHost, s->stream));
     OTT_HIP(hipStreamSynchronize(s->stream));
-    if (prune_c) {  // rows whose last stages were read after the checkpoint (the seed's rows are not counted: they have no checkpoint)
+    if (c.prune.c) {  // rows whose last stages were read after the checkpoint (the seed's rows are not counted: they have no checkpoint)
         uint64_t total;
-        memcpy(&total, hh + res_bytes, 8);
+        memcpy(&total, hh + c.res.bytes, 8);
         st.rescored += total - s->tails_seen;
         s->tails_seen = total;
     }
     const uint64_t* counts = (const uint64_t*)hh;
-    const ott_hit* hits = (const ott_hit*)(hh + cnt_pad);
-    lists.assign(groups, {});
-    for (uint32_t g = 0; g < groups; g++) lists[g].assign(hits + (size_t)g * KS, hits + (size_t)g * KS + counts[g]);
+    const ott_hit* hits = (const ott_hit*)(hh + c.res.cnt_pad);
+    lists.assign(c.groups, {});
+    for (uint32_t g = 0; g < c.groups; g++) lists[g].assign(hits + (size_t)g * KS, hits + (size_t)g * KS + counts[g]);
     float ms = 0.f;
-    if (timing && hipEventElapsedTime(&ms, s->ev[3], s->ev[4]) == hipSuccess) st.score_ns += (uint64_t)(ms * 1e6);
-    if (timing && hipEventElapsedTime(&ms, s->ev[4], s->ev[5]) == hipSuccess) st.merge_ns += (uint64_t)(ms * 1e6);
+    if (c.timing && hipEventElapsedTime(&ms, s->ev[3], s->ev[4]) == hipSuccess) st.score_ns += (uint64_t)(ms * 1e6);
+    if (c.timing && hipEventElapsedTime(&ms, s->ev[4], s->ev[5]) == hipSuccess) st.merge_ns += (uint64_t)(ms * 1e6);
     return OTT_OK;
+}
+
+// EXACT path.  queries: host [nq*dim].  Results: per group (1 for merged, nq for per-query) on the
+// host in `lists`.  `perq` selects the grouping.  Device output (!fetch, merged or per query): the merge kernel leaves its
+// [groups][KS] sentinel-padded hits in d_hits for ott_query_device — or, with hits_dev_direct, writes them straight there
+// (direct_stride must be the KS this call derives from k_eff).
+// What the call looks like — lists or sort path, list width, kernel variant, passes, grid, lean, the pruned sweep, the result
+// block — is decided in ott_exact_plan.h; the stages above run it.
+int run_exact(ott_store* s, const float* queries, uint32_t nq, const ott_query_desc* d, bool perq, const RunPlan& pl, uint64_t k_eff,
+              const uint64_t* d_mask, uint64_t mask_bits, bool fetch, std::vector<std::vector<ott_hit>>& lists, ott_stats& st,
+              bool timing = true, ott_hit* hits_dev_direct = nullptr, uint32_t direct_stride = 0) {
+    switch (lists_or_sort(k_eff, nq, pl.rows_scored, s->opt.large_k_from, fetch)) {
+        case EXACT_REFUSED: return fail(OTT_ERR_UNSUPPORTED, "ott_query_device: k > 512 is host-output only");
+        case EXACT_SORT: return run_large_k(s, queries, nq, d, perq, pl, k_eff, d_mask, mask_bits, lists, st);  // score dump + device radix sort
+        case EXACT_LISTS: break;
+    }
+    const std::vector<uint32_t> prefix = tile_prefix(pl, 64);
+    ExactCtx c{s, queries, nq, d, perq, pl, k_eff, fetch, timing, prefix,
+               exact_plan(k_eff, nq, perq, s->dimq, prefix.back(), pl.runs.size(), s->opt.exact_small, exact_grid(s, prefix.back())), perq ? nq : 1u};
+    plan_pruned_sweep(c);
+    int rc;
+    if ((rc = ensure_exact_result(c))) return rc;
+    if (!fetch && hits_dev_direct != nullptr && direct_stride == c.x.KS) c.d_hits = hits_dev_direct;
+    fill_exact_call(c, d_mask, mask_bits);
+
+    if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
+    if ((rc = c.prune.c ? pruned_sweep(c) : plain_passes(c))) return rc;
+    if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
+    if ((rc = merge_exact(c))) return rc;
+    if (timing) OTT_HIP(hipEventRecord(s->ev[5], s->stream));
+    st.passes += c.x.passes;
+    st.bytes_scanned += exact_bytes_scanned(c.x.passes, pl.rows_scored, s->dim, d->metric);
+    return fetch ? fetch_exact(c, lists, st) : OTT_OK;
 }
 
 }  // namespace
@@ -506,7 +487,7 @@ int exact_route(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64
     // block on the stream — nothing comes back to the host
     const bool dev_direct = o.dev != nullptr && k_eff <= 512;
     const uint32_t groups = perq ? d->nq : 1u;
-    const uint64_t KS = 64ull * (uint64_t)list_E(k_eff), gstride = o.dev ? o.cap / groups : 0;
+    const uint64_t KS = list_stride(list_E(k_eff)), gstride = o.dev ? o.cap / groups : 0;  // (the KS and the result block run_exact derives: ott_exact_plan.h)
     // when the caller's block has exactly the merge kernel's geometry ([groups][KS]: what ott_query_sharded asks for), the
     // merge writes into it directly: no sentinel fill in front, no copy behind
     const bool in_place = dev_direct && gstride == KS;
@@ -539,7 +520,7 @@ int exact_route(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint64
         if (!in_place) {
             if ((rc = fill_sentinels(s, o))) return rc;
             const uint64_t width = (KS < gstride ? KS : gstride) * sizeof(ott_hit);  // k_eff <= gstride: no hit is cut
-            const char* src = (const char*)s->d_hits.p + s->res_hits_off;
+            const char* src = (const char*)s->d_hits.p + exact_result_layout(groups, (uint32_t)KS).cnt_pad;  // the hits behind the counts
             if (groups == 1) OTT_HIP(hipMemcpyAsync(o.dev, src, width, hipMemcpyDeviceToDevice, s->stream));
             else OTT_HIP(hipMemcpy2DAsync(o.dev, gstride * sizeof(ott_hit), src, KS * sizeof(ott_hit), width, groups, hipMemcpyDeviceToDevice, s->stream));
         }

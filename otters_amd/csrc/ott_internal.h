@@ -19,6 +19,7 @@
 #include "ott_plane_policy.h"  // the two format decisions of the cascade's planes: HIP-free, CPU-tested
 #include "ott_mfma_plan.h"  // the batch path's host-side plan (tile geometry, candidate budget, error bound, query norms, query block): HIP-free, CPU-tested
 #include "ott_maxsim_gather_plan.h"  // listed MaxSim's host-side plan (tokens per pass, slot arrays, table sizes, route, the 2 GiB refusal): HIP-free, CPU-tested
+#include "ott_exact_plan.h"  // the exact path's host-side plan (lists or sort, list width, kernel variant, passes and grid, lean, pruned sweep, result block): HIP-free, CPU-tested
 #include "ott_sort_plan.h"  // the sort path's host-side plan (pass plans, sweep shape, rank or radix, prefix, slices, group extents, copy pieces): HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
 #include "ott_audit.h"  // test build: every HIP call below goes through a device-affinity check (see "which GPU a call is for")
@@ -343,7 +344,6 @@ struct ott_store {
     ott::host::StagedRows pend;    // rows staged, not yet in HBM (VecStore::len counts them)
     ott::PinBuf h_stage, h_hits, h_hdr;  // h_hdr: this shard's block header of a sharded query (ott_comm.hip)
     size_t in_off_qinv = 0, in_off_runs = 0, in_off_prefix = 0;  // layout of the per-query input block in d_queries
-    size_t res_hits_off = 0;                                       // hits offset inside d_hits (counts come first)
     // candidate order of the query this context is running right now (query_core sets them, the launch wrappers read them)
     uint32_t cur_tie_sh = 0, cur_tie_off = 0;
     bool cur_flat = false;
@@ -544,16 +544,9 @@ struct ExactParams {
     const uint32_t* prune_sketch;
     unsigned long long* prune_tails;
     double prune_qt, prune_qn, prune_q1;
-    float qemb[896];  // last: the embedded query (kernel arguments are limited to 4 KB)
+    float qemb[OTT_QEMB_MAX];  // last: the embedded query (kernel arguments are limited to 4 KB)
 };
-constexpr uint32_t OTT_QEMB_MAX = 896;
-// Code words of a sketch line that the sketch form's kernel decodes.  The embedded query holds at most 28 stages, so a three-bit
-// sketch of the last 5/8 has at most 18 stages of three words (with a and rho fourteen 16-B pieces), a sign sketch of the last
-// quarter at most 7 words; a store with more takes the 7/8 form.
-constexpr uint32_t OTT_SKETCH_MAX_WORDS = 54;
-constexpr uint32_t OTT_SKETCH1_MAX_WORDS = 10;  // the sign form keeps its words in registers across the stages: three 16-B loads
-// the four-bit form: up to 27 of the 28 stages sketched, four words each (a line of up to 28 16-B pieces, streamed eight at a time)
-constexpr uint32_t OTT_SKETCH4_MAX_WORDS = 108;
+// (OTT_QEMB_MAX and the OTT_SKETCH*_MAX_WORDS limits of the sketch forms: ott_exact_plan.h)
 static_assert(sizeof(ExactParams) <= 4096, "kernel arguments are limited to 4 KB");
 
 int launch_exact(ott_store* s, const ExactParams& p, int nq_tile, int E, int grid);
@@ -605,6 +598,10 @@ int run_large_k(ott_store* s, const float* queries, uint32_t nq, const ott_query
 void fill_exact_params(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint32_t nq, const uint64_t* d_mask, uint64_t mask_bits,
                        uint32_t n_tiles, ExactParams& p);
 float host_inv_norm_exact(const float* v, uint32_t dim);  // ott_api.hip: the query-side inverse norm in the reference's order
+// ONE query's inputs into the kernel arguments of `p` (a lean call, ott_exact_plan.h: exact_lean): the query's `query_bytes` bytes, its
+// inverse norm, and the plan's at most two runs with their tile prefix.  The query's tail up to dimq is whatever `p` held (zero
+// after fill_exact_params); n_runs and n_tiles stay the caller's.
+void embed_exact_inputs(ExactParams& p, const void* query, size_t query_bytes, float inv_norm, const RunPlan& pl, const std::vector<uint32_t>& prefix);
 int upload_exact_inputs(ott_store* s, const float* queries, uint32_t nq, const RunPlan& pl, const std::vector<uint32_t>& prefix);
 
 // MFMA batch path: per-query exact top-k lists on the host; uncertified[q] != 0 means the
@@ -669,7 +666,6 @@ inline void merge_heads(std::vector<const ott_hit*>& head, const std::vector<con
         }
     }
 }
-inline int list_E(uint64_t k) { return k <= 64 ? 1 : k <= 128 ? 2 : k <= 256 ? 4 : 8; }  // register list entries per lane for k <= 512
 
 // ott_api.hip.  validate_query: argument checks of ott_query.  query_on: one query on a context whose `mu` the caller
 // holds (and the owner's `rw`, shared).  Device output (out_dev != nullptr): [groups][cap / groups] slots, sentinel

@@ -1966,10 +1966,7 @@ int run_i8_single(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint
     p.i8_scale = i8_scale;
     p.flag = s->d_flag;
     if (pl.runs.size() <= 2) {  // everything the kernel needs rides in its arguments
-        p.embedded = 1;
-        memcpy(p.qemb, q8, ld8);
-        for (size_t i = 0; i < pl.runs.size(); i++) p.eruns[i] = pl.runs[i];
-        for (size_t i = 0; i < prefix.size(); i++) p.eprefix[i] = prefix[i];
+        embed_exact_inputs(p, q8, ld8, 0.0f, pl, prefix);  // (the int8 query; eqinv stays zero on this sweep)
     } else {  // a chunk mask with many runs (config 3: every second chunk): run table, tile prefix and the int8 query from the uploaded block
         p.queries = (const float*)(dblk + off_q8);
         p.qinv = (const float*)(dblk + qb.qinv);

@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "../../include/otters_hip.h"
+#include "ott_exact_plan.h"  // small_variant_fits: whether rows8 would take the query on the exact path
 #include "ott_mfma_plan.h"  // how many candidates each level of the batch path re-scores (mfma_hi_k_ok, t_want_*): the cost model and the back-off read it
 
 namespace ott {
@@ -98,8 +99,8 @@ inline PathChoice choose_path(const PathIn& in, Planes&& planes, Ready&& first_p
     // ~35 us of launches and merge, against the batch path's ~(120 us + 3.5 us per query) of rounds, select and finalize
     // (benchmarks/small_corpus.py: 10k x 768, 8 queries: 84 us against 150)
     const uint64_t k_e = in.k < in.rows_scored * nq ? in.k : in.rows_scored * nq;
-    if (use_mfma && nq <= 16 && k_e <= 128 && in.dimq <= 2048 && in.exact_small != 0 && in.exact_small != 1 &&
-        in.rows_scored / 64 + in.n_runs <= 1024) {
+    if (use_mfma && nq <= 16 && k_e <= 128 && in.exact_small != 0 && in.exact_small != 1 &&
+        small_variant_fits(in.dimq, in.rows_scored / 64 + in.n_runs)) {  // (the tiles: an estimate from above, no prefix is built yet)
         const double t_rows8 = 0.035 + (double)((nq + 7) / 8) * (0.040 + 0.7e-6 * (double)in.rows_scored);
         if (t_rows8 < 0.9 * (0.12 + 0.0035 * nq)) use_mfma = false;
     }

@@ -588,17 +588,8 @@ static int sweep_dump(const SortCtx& c, const RunPlan& plan, const std::vector<u
     p.dump_cursor = (unsigned long long*)cursor;
     p.dump_cap = c.cap;
     p.dump_gate = gate;
-    if (lean) {  // single query, at most two runs: everything rides in the kernel arguments (no H2D copy in front)
-        p.embedded = 1;
-        p.queries = nullptr;
-        p.qinv = nullptr;
-        p.runs = nullptr;
-        p.tile_prefix = nullptr;
-        memcpy(p.qemb, c.queries, (size_t)s->dim * 4);
-        p.eqinv = host_inv_norm_exact(c.queries, s->dim);
-        for (size_t i = 0; i < plan.runs.size(); i++) p.eruns[i] = plan.runs[i];
-        for (size_t i = 0; i < prefix.size(); i++) p.eprefix[i] = prefix[i];
-    }
+    // single query, at most two runs: everything rides in the kernel arguments (no H2D copy in front)
+    if (lean) embed_exact_inputs(p, c.queries, (size_t)s->dim * 4, host_inv_norm_exact(c.queries, s->dim), plan, prefix);
     // small stores: the rows8 sweep (eight lanes per row, a workgroup per 64-row tile, up to 8 queries per pass) — one query over
     // 10k x 768: 10 us where the streaming kernel needs 33; 16 queries: two passes of ~12 us where it needed four of ~110
     int rc;
@@ -770,7 +761,7 @@ static int small_slice(SortCtx& c, bool perq, const RunPlan& pl, const std::vect
     ott_store* s = c.s;
     int rc;
     const uint32_t nq = c.nq, groups = perq ? nq : 1, cap32 = (uint32_t)c.cap, pq = perq ? 1u : 0u;
-    const bool lean = nq == 1 && s->dimq <= OTT_QEMB_MAX && pl.runs.size() <= 2;
+    const bool lean = exact_lean(nq, s->dimq, pl.runs.size());
     if (!lean && (rc = upload_exact_inputs(s, c.queries, nq, pl, prefix))) return rc;
     const SmallCtl off = small_ctl_layout(c.cap, nq);
     // the block is zero when a query finds it: zeroed when it is (re)allocated, and left zeroed by every query's last kernel

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/otters_hip.h"  // (and through it stdint.h)
+#include "ott_exact_plan.h"            // small_variant_fits, exact_bytes_scanned: the sweep is the exact path's
 
 namespace ott {
 
@@ -107,14 +108,14 @@ struct SweepShape {
 };
 inline SweepShape sweep_shape(uint32_t nq, uint32_t dimq, uint32_t tiles, int exact_small) {
     SweepShape w;
-    w.rows8 = dimq <= 2048 && tiles <= 1024 && exact_small != 0 && exact_small != 1;
+    w.rows8 = small_variant_fits(dimq, tiles) && exact_small != 0 && exact_small != 1;
     w.tile = w.rows8 || nq == 1 ? 1u : 4u;
     while (w.rows8 && w.tile < nq && w.tile < 8) w.tile <<= 1;
     w.passes = (nq + w.tile - 1) / w.tile;
     return w;
 }
 inline uint64_t sort_bytes_scanned(uint32_t passes, uint64_t rows_scored, uint32_t dim, uint32_t metric) {
-    return (uint64_t)passes * rows_scored * ((uint64_t)dim * 4 + (metric == OTT_METRIC_COSINE ? 4 : 0));
+    return exact_bytes_scanned(passes, rows_scored, dim, metric);  // the same sweep, the same bytes
 }
 
 // ---- small results, sorted by rank (small_rank_kernel) -----------------------------------------------------------------------------

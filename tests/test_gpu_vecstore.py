@@ -844,3 +844,124 @@ def test_sort_path_branches_report_their_documented_sweeps(oracle):
     assert sorted(zip(got["index"].tolist(), got["query"].tolist())) == sorted(zip(lit["index"].tolist(), lit["query"].tolist()))
     assert st["passes"] == 1 and st["bytes_scanned"] == 9_600_000, st  # 300 000 x 32
     store.close()
+
+
+def test_exact_path_branches_report_their_documented_passes(oracle):
+    """Which branch a call over the lists (k <= 512, run_exact) takes, pinned through what it reports, at the smallest shapes that
+    reach each: rows8 with one and eight queries per pass, the streaming kernel with four, seventeen queries that do not fit
+    rows8, the three list widths above 64, the lists against the sort path, the pruned sweep in its four forms and the calls it
+    does not take, and device output.  Hits are the oracle's bit for bit; `path_used`, `passes`, `bytes_scanned` and `rescored`
+    equal the figures written out below, from the documented rules (ott_exact_plan.h is not consulted):
+      queries per pass = the power of two that holds nq, at most 4, or 8 under rows8 (stores of up to 1024 tiles of 64 rows and
+      up to 16 queries, k <= 128, unless exact_small = 0), and 1 from k = 129 (four and eight list entries per lane);
+      bytes_scanned = passes x rows scored x (4 dim, + 4 for cosine's inverse norm);
+      rescored = the rows whose tails the pruned sweep finished: behind a seed of a tenth of the rows (whole tiles), every row
+      while the gate is open."""
+    import ctypes as C
+
+    import torch
+
+    from otters_amd import _native as N
+    rng = np.random.default_rng(2024)
+    EXACT = int(Path.Exact)
+
+    def reference(rows, queries, rq, perq, row_mask=None):
+        if not perq:
+            return oracle.vec_query(rows, queries, rq.metric, rq.take, rq.k, rq.filter_cmp, rq.filter_thr, row_mask=row_mask, ties=oracle.TIES_CANONICAL), None
+        per = [oracle.vec_query(rows, queries[q], rq.metric, rq.take, rq.k, rq.filter_cmp, rq.filter_thr, row_mask=row_mask, ties=oracle.TIES_CANONICAL)
+               for q in range(len(queries))]
+        for q, h in enumerate(per):
+            h["query"] = q
+        return np.concatenate(per), [len(h) for h in per]
+
+    def check(store, rows, queries, k, perq, passes, nbytes, rescored, where, filt=None, chunk_mask=None, row_mask=None):
+        plan = store.query(queries, Metric.Cosine)
+        if filt:
+            plan = plan.filter(*filt)
+        plan = plan.take(k)
+        if perq:
+            plan = plan.per_query()
+        rq = plan.with_path(Path.Exact).resolve()
+        hits, counts, st = store._run(rq, chunk_mask=chunk_mask)
+        ref, ref_counts = reference(rows, queries, rq, perq, row_mask)
+        assert_bit_exact(hits, ref)
+        if perq:
+            assert [int(c) for c in counts] == ref_counts, where
+        got = (st["path_used"], st["passes"], st["bytes_scanned"], st["rescored"])
+        print(where, "path_used, passes, bytes_scanned, rescored:", got)
+        assert got == (EXACT, passes, nbytes, rescored), (where, got, (EXACT, passes, nbytes, rescored))
+        return hits
+
+    def store_of(rows, chunk=None, **options):
+        store = VecStore(rows.shape[1])
+        if chunk:
+            store.set_chunk_size(chunk)
+        for name, v in options.items():
+            store.set_option(name, v)
+        store.add_vectors(rows)
+        return store
+
+    # 5000 x 24 (79 tiles), cosine, k = 10: one, five and seventeen queries.  rows8 (the default): 1, 8, and — seventeen do not fit —
+    # the streaming kernel's 4 queries per pass: 1 / 1 / 5 passes; exact_small = 0: 1 / 2 / 5.  A pass reads 5000 x (96 + 4) bytes
+    rows = rng.uniform(-1, 1, (5000, 24)).astype(np.float32)
+    qs = rng.uniform(-1, 1, (17, 24)).astype(np.float32)
+    host = {}
+    stores = {es: store_of(rows, exact_small=es) for es in (-1, 0)}
+    for es, want in ((-1, (1, 1, 5)), (0, (1, 2, 5))):
+        for nq, passes in zip((1, 5, 17), want):
+            for perq in (False, True):
+                host[es, nq, perq] = check(stores[es], rows, qs[:nq], 10, perq, passes, passes * 500_000, 0, ("5000 x 24", es, nq, perq))
+        # three queries: k = 100, two entries per lane, still one pass; k = 200, four entries: a query per pass; k = 300, one query, eight
+        check(stores[es], rows, qs[:3], 100, False, 1, 500_000, 0, ("k 100", es))
+        check(stores[es], rows, qs[:3], 200, False, 3, 1_500_000, 0, ("k 200", es))
+        check(stores[es], rows, qs[:1], 300, False, 1, 500_000, 0, ("k 300", es))
+    # device output of the same calls equals the host output: the caller's block of k slots per group (copied out of d_hits), and for
+    # five queries per query the merge kernel's own geometry, 64 slots per group (written in place, sentinel padded)
+    for es, nq, perq, slots in [(es, nq, perq, 10) for es in (-1, 0) for nq in (1, 5, 17) for perq in (False, True)] + [(-1, 5, True, 64), (0, 5, True, 64)]:
+        groups = nq if perq else 1
+        cap = groups * slots
+        buf = torch.full((cap * 16,), 0x5A, dtype=torch.uint8, device="cuda:0")
+        nout = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+        q = np.ascontiguousarray(qs[:nq])
+        d = N.QueryDesc()
+        d.queries, d.nq, d.metric, d.take, d.k = q.ctypes.data, nq, int(Metric.Cosine), 1, 10
+        d.mode, d.path = (1 if perq else 0), EXACT
+        N.check(N.lib().ott_query_device(stores[es]._handle(), C.byref(d), C.c_void_p(buf.data_ptr()), cap, C.c_void_p(nout.data_ptr()), None))
+        torch.cuda.synchronize()
+        got = buf.cpu().numpy().view(N.HIT_DTYPE).reshape(groups, slots)
+        assert int(nout.cpu()[0]) == groups * 10, (es, nq, perq, slots)
+        assert_bit_exact(got[:, :10].reshape(-1), host[es, nq, perq])
+        assert np.all(got[:, 10:].copy().view(np.uint8) == 0xFF), (es, nq, perq, slots)
+    for s in stores.values():
+        s.close()
+    # 180 000 x 8, three queries, k = 200: 540 000 pairs are more than 2^19, so several queries at k > 128 take the sort path — one
+    # streaming sweep of the three (2813 tiles: no rows8) — unless large_k_from = 512 keeps them on the lists: a query per pass
+    rows = rng.uniform(-1, 1, (180_000, 8)).astype(np.float32)
+    q3 = rng.uniform(-1, 1, (3, 8)).astype(np.float32)
+    for large_k_from, passes in ((0, 1), (512, 3)):
+        store = store_of(rows, large_k_from=large_k_from)
+        check(store, rows, q3, 200, False, passes, passes * 6_480_000, 0, ("180000 x 8", large_k_from))  # 180 000 x (32 + 4)
+        store.close()
+    # 30 080 x 64 (two stages: the checkpoint is stage 1 in every form), one query, the streaming kernel, exact_prune = 1: the 7/8 form
+    # and the sketch forms of 1, 3 and 4 bits.  The seed is 3008 rows; a filter that nothing passes leaves the gate open, so every row
+    # behind the seed is finished: 27 072.  A pass reads 30 080 x (256 + 4) bytes whatever is skipped.  exact_prune = 0: no pruned
+    # sweep.  A chunk mask that leaves three runs (chunks of 1000 rows, two dropped: 28 080 rows) does not ride in the kernel
+    # arguments: no pruned sweep either
+    rows = rng.uniform(-1, 1, (30_080, 64)).astype(np.float32)
+    q1 = rng.uniform(-1, 1, (1, 64)).astype(np.float32)
+    cmask = np.ones(31, bool)
+    cmask[[5, 20]] = False
+    rmask = np.repeat(cmask, 1000)[:30_080]
+    nothing = (2.0, Cmp.Gt)
+    for sketch, bits in ((0, 4), (1, 1), (1, 3), (1, 4)):
+        store = store_of(rows, chunk=1000, exact_small=0, exact_prune=1, exact_sketch=sketch, exact_sketch_bits=bits)
+        where = ("30080 x 64", sketch, bits)
+        assert check(store, rows, q1, 10, False, 1, 7_820_800, 27_072, where + ("open gate",), filt=nothing).size == 0
+        check(store, rows, q1, 10, False, 1, 7_300_800, 0, where + ("three runs",), chunk_mask=cmask, row_mask=rmask)
+        plan = store.query(q1, Metric.Cosine).take(10).with_path(Path.Exact)  # a gate that closes: the oracle's hits, some tails skipped
+        hits, _, st = store._run(plan.resolve())
+        assert_bit_exact(hits, oracle.vec_query(rows, q1, oracle.METRIC_COSINE, oracle.TAKE_MAX, 10, ties=oracle.TIES_CANONICAL))
+        assert (st["path_used"], st["passes"], st["bytes_scanned"]) == (EXACT, 1, 7_820_800) and 0 < st["rescored"] <= 27_072, (where, st)
+        store.set_option("exact_prune", 0)
+        check(store, rows, q1, 10, False, 1, 7_820_800, 0, where + ("exact_prune 0",), filt=nothing)
+        store.close()
