@@ -378,6 +378,39 @@ int ott_query_ids(ott_store* s, const ott_query_desc* d, const uint64_t* ids, ui
 int ott_store_score_rows(ott_store* s, const float* queries, uint32_t nq, uint32_t metric, const uint64_t* ids, uint64_t n_ids,
                          float* out_scores);
 
+/* MMR diversity re-ranking (an extension; maximal marginal relevance, Carbonell and Goldstein — LangChain's
+ * max_marginal_relevance_search, Qdrant's mmr query): of a query's best fetch_k hits, pick d->k greedily, each pick the most relevant
+ * and the least similar to what is already picked.  The CANDIDATES are exactly the hits ott_query (ott_query_ids when ids is given)
+ * returns for the same descriptor with k = fetch_k — index, score bits and order, under every metric, take, filter, mask, path and
+ * tie order; candidate i has row r_i, relevance rel_i and position i; n <= fetch_k of them exist.  g(x) = x for OTT_TAKE_MAX, -x for
+ * OTT_TAKE_MIN.  The PAIR SCORE P[s][c] is the metric's score with candidate s's STORED row as the query and candidate c's stored
+ * row as the row, the exact path's bits in the store's reduce order; cosine is (dot * inv[r_s]) * inv[r_c] with the store's inverse
+ * norms (the roundings are not symmetric: the selected row plays the query).  Pair scores read stored data: masks and the filter
+ * act on the first stage only.  SELECTION, in f32, every operation rounded on its own (no FMA), om = 1.0f - lambda: pick 0 is
+ * candidate 0 with value lambda * g(rel_0); every unpicked c keeps red_c, set to g(P[s_0][c]) after pick 0 and after each later pick
+ * s, with x = g(P[s][c]): unchanged if x is NaN, else x if red_c is NaN, else x if x > red_c; value_c = (lambda * g(rel_c)) -
+ * (om * red_c); the next pick has the largest ordinal of its value (the library's total order, +0.0 above -0.0, a NaN value below
+ * every other), equal ordinals go to the lower position; k_eff = min(k, n) picks.  OUTPUT: one ott_hit per pick in pick order, as
+ * the first stage gave it (index, relevance bits, query); out_values[i], if given, the f32 value of pick i (a NaN value is written
+ * as 0x7FC00000).  With lambda = 1 and finite scores the result is the first k_eff candidates; with fetch_k = k it is the plain
+ * top-k as a set.  OTT_MODE_MERGED takes one query; OTT_MODE_PER_QUERY runs one independent MMR per query (hits grouped by query,
+ * counts in n_per_query, as ott_query).  cap >= min(k, rows) (rows: ott_store_len, or the distinct listed ids), x nq in PER_QUERY;
+ * out_values holds cap floats.  stats is the first stage's; total_ns covers both stages and the event time of the two kernels below
+ * is added to merge_ns.
+ * The first stage runs through ott_query's own internals and hands its hits over the host (one more wait, an upload of at most
+ * 12 KB per query).  A pair kernel then fills P across the GPU — the gather kernel's geometry, eight lanes per row, with eight
+ * candidates' rows read from the store BY ID into LDS as a workgroup's queries; nothing is gathered to a temporary — and a greedy
+ * kernel, one workgroup per query and one thread per candidate, runs every round in one launch.  Scratch (nq x fetch_k^2 x 4 B of
+ * pair scores) belongs to the query context.  A store that never makes this call allocates and launches nothing for it.
+ * Refused on the host before any device work, with nothing written: d->k == 0, d->k > fetch_k, fetch_k > OTT_MMR_MAX_FETCH, lambda
+ * outside [0, 1] or NaN (OTT_ERR_INVALID, checked before the store is looked at); the errors of ott_query and ott_query_ids; cap too
+ * small (OTT_ERR_INVALID); OTT_MODE_MERGED with nq > 1, a multi-GPU store (candidate rows lie on different shards), rows longer than
+ * 2048 floats, nq x fetch_k^2 x 4 B above 256 MiB (OTT_ERR_UNSUPPORTED).  Takes the store shared, like ott_query, once for both stages. */
+#define OTT_MMR_MAX_FETCH 1024
+int ott_query_mmr(ott_store* s, const ott_query_desc* d, const uint64_t* ids, uint64_t n_ids, /* NULL, 0: no id list */
+                  uint64_t fetch_k, float lambda, ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query,
+                  float* out_values /* may be NULL; cap floats */, ott_stats* stats);
+
 /* Grouped search (an extension; Elasticsearch field collapse, Qdrant search_groups, Milvus group_by_field): one best hit per group,
  * top-k over the groups — top-10 DOCUMENTS of a store of chunks.  A store may carry one dense group id per row (uint32, < n_groups,
  * resident in HBM at 4 B per row).  ott_query_groups returns exactly the hits — index, score bits, order, per-query counts — of the

@@ -1,6 +1,7 @@
 // ott_exact_dev.h — device helpers of the exact-order kernels, shared by ott_exact.hip (exact_kernel, exact_rows8_kernel, the merge
-// kernels) and ott_gather.hip (exact_gather8_kernel): the candidate order, the wave-wide sorted candidate list, the score
-// filter, the per-element term of every metric and wide's horizontal sum.  Inline only: a kernel that includes this compiles
+// kernels), ott_gather.hip (exact_gather8_kernel) and ott_mmr.hip (mmr_pair_kernel): the candidate order, the wave-wide sorted
+// candidate list, the score filter, the per-element term of every metric, wide's horizontal sum and the per-row step of the kernels
+// that read scattered rows with eight lanes per row.  Inline only: a kernel that includes this compiles
 // to what it compiled to when the code stood in ott_exact.hip.
 #pragma once
 
@@ -248,6 +249,70 @@ __device__ __forceinline__ float reduce8(const float* l, uint32_t mode) {
     }
     return __fadd_rn(__fadd_rn(__fadd_rn(l[0], l[4]), __fadd_rn(l[2], l[6])),
                      __fadd_rn(__fadd_rn(l[1], l[5]), __fadd_rn(l[3], l[7])));
+}
+
+// The per-row step of the eight-lanes-per-row kernels that read scattered rows (exact_gather8_kernel, ott_gather.hip; mmr_pair_kernel,
+// ott_mmr.hip): one row against NQ queries that sit in LDS ([NQ][dimq], zero padded).  Lane c = lane & 7 of the row's 8-lane group
+// carries chain c of the reference's f32x8: acc = acc + q[8j + c] * v[8j + c], j ascending (vec_compute.rs:12-13, 39-42), the
+// cross-lane sum is wide's reduce_add in either order, the remainder is sequential and every lane of the group computes it
+// (vec_compute.rs:15-21, 44-53); cosine scales the sum by the query's and then the row's inverse norm (vec_compute.rs:31).  Every
+// lane of the group ends with the same sc[q].  The rows are scattered: a wave instruction touches 8 rows x 32 B, and the four steps
+// that share a 128-B line hit in the vector L1.
+template <int MK, int NQ, int UNROLL>
+__device__ __forceinline__ void rows8_scores(const float* sQ, uint32_t dimq, const float* rp, uint32_t dim, int lane, uint32_t reduce, bool cosine,
+                                             const float* qinv, float vinv, float* sc) {
+    const int c = lane & 7;
+    const uint32_t full = dim >> 3;
+    float acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) acc[q] = 0.0f;
+    auto step = [&](uint32_t jj, float xv) {
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            const float qv = sQ[(uint32_t)q * dimq + 8 * jj + c];
+            acc[q] = __fadd_rn(acc[q], exact_term<MK>(qv, xv));
+        }
+    };
+    uint32_t j = 0;
+    for (; j + UNROLL <= full; j += UNROLL) {
+        float x[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) x[u] = rp[8 * (j + u) + c];
+#pragma unroll
+        for (int u = 0; u < UNROLL; u++) step(j + u, x[u]);
+    }
+    for (; j < full; j++) step(j, rp[8 * j + c]);
+    float tail[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) tail[q] = 0.0f;
+    const uint32_t nt = dim & 7u;
+    for (uint32_t l = 0; l < nt; l++) {
+        const float xv = rp[8 * full + l];
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            const float qv = sQ[(uint32_t)q * dimq + 8 * full + l];
+            tail[q] = __fadd_rn(tail[q], exact_term<MK>(qv, xv));
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+        // wide::f32x8::reduce_add across the group's eight lanes
+        float sum;
+        if (reduce == OTT_REDUCE_SEQ4) {
+            const int b = lane & ~7;
+            float l8[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) l8[i] = __shfl(acc[q], b + i);
+            sum = reduce8(l8, OTT_REDUCE_SEQ4);
+        } else {
+            const float s1 = __fadd_rn(acc[q], __shfl_xor(acc[q], 4));  // l_c + l_{c^4}
+            const float s2 = __fadd_rn(s1, __shfl_xor(s1, 2));          // (l0+l4)+(l2+l6) on even-pair lanes, (l1+l5)+(l3+l7) on the others
+            sum = __fadd_rn(s2, __shfl_xor(s2, 1));                     // (a + b == b + a bit for bit)
+        }
+        float v = __fadd_rn(sum, tail[q]);
+        if (cosine) v = __fmul_rn(__fmul_rn(v, qinv[q]), vinv);  // vec_compute.rs:31
+        sc[q] = v;
+    }
 }
 
 }  // namespace ott

@@ -86,58 +86,12 @@ __global__ __launch_bounds__(64 * G8_WAVES) void exact_gather8_kernel(GatherPara
     if (p.metric == OTT_METRIC_COSINE) vinv = p.inv[my_row];
     __syncthreads();  // the queries are in LDS
 
-    // chain c of the row, for every query of the pass: acc = acc + q[8j + c] * v[8j + c], j ascending (vec_compute.rs:12-13, 39-42).
-    // The rows are scattered: a wave instruction touches 8 rows x 32 B, and the four steps that share a 128-B line hit in the vector L1
-    const uint32_t full = p.dim >> 3;
-    float acc[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) acc[q] = 0.0f;
-    auto step = [&](uint32_t jj, float xv) {
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            const float qv = sQ[(uint32_t)q * p.dimq + 8 * jj + c];
-            acc[q] = __fadd_rn(acc[q], exact_term<MK>(qv, xv));
-        }
-    };
-    uint32_t j = 0;
-    for (; j + G8_UNROLL <= full; j += G8_UNROLL) {
-        float x[G8_UNROLL];
-#pragma unroll
-        for (int u = 0; u < G8_UNROLL; u++) x[u] = rp[8 * (j + u) + c];
-#pragma unroll
-        for (int u = 0; u < G8_UNROLL; u++) step(j + u, x[u]);
-    }
-    for (; j < full; j++) step(j, rp[8 * j + c]);
-    // remainder: sequential sum of the last dim % 8 terms (vec_compute.rs:15-21, 44-53); every lane of the group computes it
-    float tail[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) tail[q] = 0.0f;
-    const uint32_t nt = p.dim & 7u;
-    for (uint32_t l = 0; l < nt; l++) {
-        const float xv = rp[8 * full + l];
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            const float qv = sQ[(uint32_t)q * p.dimq + 8 * full + l];
-            tail[q] = __fadd_rn(tail[q], exact_term<MK>(qv, xv));
-        }
-    }
+    // the row against every query of the pass: the eight chains, wide's reduce_add, the remainder (ott_exact_dev.h: rows8_scores)
+    float scq[NQ];
+    rows8_scores<MK, NQ, G8_UNROLL>(sQ, p.dimq, rp, p.dim, lane, p.reduce, p.metric == OTT_METRIC_COSINE, qinv, vinv, scq);
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
-        // wide::f32x8::reduce_add across the group's eight lanes
-        float sum;
-        if (p.reduce == OTT_REDUCE_SEQ4) {
-            const int b = lane & ~7;
-            float l8[8];
-#pragma unroll
-            for (int i = 0; i < 8; i++) l8[i] = __shfl(acc[q], b + i);
-            sum = reduce8(l8, OTT_REDUCE_SEQ4);
-        } else {
-            const float s1 = __fadd_rn(acc[q], __shfl_xor(acc[q], 4));  // l_c + l_{c^4}
-            const float s2 = __fadd_rn(s1, __shfl_xor(s1, 2));          // (l0+l4)+(l2+l6) on even-pair lanes, (l1+l5)+(l3+l7) on the others
-            sum = __fadd_rn(s2, __shfl_xor(s2, 1));                     // (a + b == b + a bit for bit)
-        }
-        float sc = __fadd_rn(sum, tail[q]);
-        if (p.metric == OTT_METRIC_COSINE) sc = __fmul_rn(__fmul_rn(sc, qinv[q]), vinv);  // vec_compute.rs:31
+        const float sc = scq[q];
         if constexpr (RAW) {
             if (c == 0 && valid && (uint32_t)q < nq_here) p.raw_out[(uint64_t)(p.q0 + q) * p.raw_stride + p.pos[my_slot]] = sc;
         } else {
@@ -466,6 +420,8 @@ int score_rows_on(ott_store* s, const float* queries, uint32_t nq, uint32_t metr
     return OTT_OK;
 }
 
+}  // namespace
+
 int check_ids(const char* who, const uint64_t* ids, uint64_t n_ids, uint64_t len) {
     if (n_ids && !ids) return fail(OTT_ERR_INVALID, std::string(who) + ": ids is NULL");
     for (uint64_t i = 0; i < n_ids; i++)
@@ -474,7 +430,26 @@ int check_ids(const char* who, const uint64_t* ids, uint64_t n_ids, uint64_t len
     return OTT_OK;
 }
 
-}  // namespace
+// The ranked query over a list on a context whose `mu` the caller holds (and the owner's `rw`, shared): the gather kernel or the mask
+// route.  u: ascending, duplicate-free, every id < the store's length; d->k = min(k, pool) >= 1; n_listed: the ids as the caller listed them.
+int query_ids_on(ott_store* ctx, const ott_query_desc* d, std::vector<uint64_t>& u, uint64_t n_listed, ott_hit* out, uint64_t cap, uint64_t* n_out,
+                 uint64_t* n_per_query, ott_stats* stats) {
+    // The gather kernel serves the canonical order, the lists rows8 builds (k <= 128), up to 1024 tiles of 64 ids, up to 16 queries
+    // (two passes of eight, as rows8) of up to 2048 floats, on path AUTO or EXACT; everything else takes the mask.
+    // AUTO (id_gather = -1): the gather for lists of up to 10000 ids, the mask above.  Measured on 10M x 768, cosine top-10, one
+    // query, random ids, against a caller-built row mask over the store (profiles/idlist/README.md): 100 ids 0.048 against 0.465 ms,
+    // 1000 ids 0.054 / 0.485, 10000 ids 0.388 / 0.561 — and 65536 ids 2.84 / 0.95: the kernels take 50 us there, the host's sort
+    // of the list 2.7 ms.  The crossover lies near 12500 ids; 10000 is the largest size at which the gather measured faster.
+    const uint64_t k_eff = d->k;
+    const bool eligible = ctx->opt.tie_order == 0 && ctx->opt.id_gather != 0 && (ctx->opt.id_gather == 1 || n_listed <= G8_AUTO_MAX_IDS) &&
+                          d->path != OTT_PATH_MFMA && k_eff <= 128 && u.size() <= 64ull * G8_MAX_TILES && ctx->dimq <= G8_QMAX && d->nq <= 16;
+    if (!eligible) return run_ids_as_mask(ctx, d, u, out, cap, n_out, n_per_query, stats);
+    if (d->chunk_mask) {  // a host pointer: ids of cleared chunks go here
+        const uint64_t cs = ctx->chunk_size;
+        u.erase(std::remove_if(u.begin(), u.end(), [&](uint64_t r) { const uint64_t c = r / cs; return !((d->chunk_mask[c >> 6] >> (c & 63)) & 1); }), u.end());
+    }
+    return run_gather(ctx, d, u, k_eff, out, n_out, n_per_query, stats);
+}
 
 }  // namespace ott
 
@@ -506,24 +481,8 @@ int ott_query_ids(ott_store* s, const ott_query_desc* d, const uint64_t* ids, ui
     if (s->multi) return multi_query_ids(s, &d2, u, out, cap, n_out, n_per_query, stats);
     ott::host::SharedLock rd;  // the corpus cannot change while this query runs
     if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
-    // The gather kernel serves the canonical order, the lists rows8 builds (k <= 128), up to 1024 tiles of 64 ids, up to 16 queries
-    // (two passes of eight, as rows8) of up to 2048 floats, on path AUTO or EXACT; everything else takes the mask.
-    // AUTO (id_gather = -1): the gather for lists of up to 10000 ids, the mask above.  Measured on 10M x 768, cosine top-10, one
-    // query, random ids, against a caller-built row mask over the store (profiles/idlist/README.md): 100 ids 0.048 against 0.465 ms,
-    // 1000 ids 0.054 / 0.485, 10000 ids 0.388 / 0.561 — and 65536 ids 2.84 / 0.95: the kernels take 50 us there, the host's sort
-    // of the list 2.7 ms.  The crossover lies near 12500 ids; 10000 is the largest size at which the gather measured faster.
-    const bool eligible = s->opt.tie_order == 0 && s->opt.id_gather != 0 && (s->opt.id_gather == 1 || n_ids <= G8_AUTO_MAX_IDS) &&
-                          d->path != OTT_PATH_MFMA && k_eff <= 128 && u.size() <= 64ull * G8_MAX_TILES && s->dimq <= G8_QMAX && d->nq <= 16;
     ott_store* ctx = ctx_acquire(s);
-    if (eligible) {
-        if (d->chunk_mask) {  // a host pointer: ids of cleared chunks go here
-            const uint64_t cs = s->chunk_size;
-            u.erase(std::remove_if(u.begin(), u.end(), [&](uint64_t r) { const uint64_t c = r / cs; return !((d->chunk_mask[c >> 6] >> (c & 63)) & 1); }), u.end());
-        }
-        rc = run_gather(ctx, &d2, u, k_eff, out, n_out, n_per_query, stats);
-    } else {
-        rc = run_ids_as_mask(ctx, &d2, u, out, cap, n_out, n_per_query, stats);
-    }
+    rc = query_ids_on(ctx, &d2, u, n_ids, out, cap, n_out, n_per_query, stats);
     ctx_release(ctx);
     return rc;
 }

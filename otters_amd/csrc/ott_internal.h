@@ -20,6 +20,7 @@
 #include "ott_mfma_plan.h"  // the batch path's host-side plan (tile geometry, candidate budget, error bound, query norms, query block): HIP-free, CPU-tested
 #include "ott_maxsim_gather_plan.h"  // listed MaxSim's host-side plan (tokens per pass, slot arrays, table sizes, route, the 2 GiB refusal): HIP-free, CPU-tested
 #include "ott_exact_plan.h"  // the exact path's host-side plan (lists or sort, list width, kernel variant, passes and grid, lean, pruned sweep, result block): HIP-free, CPU-tested
+#include "ott_mmr_plan.h"  // MMR re-ranking's host-side plan (refusals, scratch layout, the pair grid, the greedy launch): HIP-free, CPU-tested
 #include "ott_sort_plan.h"  // the sort path's host-side plan (pass plans, sweep shape, rank or radix, prefix, slices, group extents, copy pieces): HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
 #include "ott_audit.h"  // test build: every HIP call below goes through a device-affinity check (see "which GPU a call is for")
@@ -310,6 +311,9 @@ struct ott_store {
     // 64 B) | raw scores of ott_store_score_rows]
     ott::DevBuf d_idmask, d_gather;
     uint64_t* cur_idmask = nullptr;
+    // MMR re-ranking (ott_mmr.hip), THIS context's scratch, allocated by the first ott_query_mmr that runs on it:
+    // [candidate rows | relevances | counts | picks | values | the pair scores] (ott_mmr_plan.h: MmrLayout)
+    ott::DevBuf d_mmr;
     // Grouped search (ott_group.hip).  d_gid: one dense group id per row slot, [cap] words, allocated by
     // ott_store_set_groups and freed by ott_store_clear_groups; nullptr = no groups (and nothing else below exists).  gid_n: the
     // rows the ids cover (a query needs gid_n == n).  Owned by the store (workers alias it), changed only under `rw` exclusive; a
@@ -692,6 +696,11 @@ int compose_row_mask(ott_store* s, const ott_query_desc* d, const uint64_t** d_m
 int multi_query_ids(ott_store* ms, const ott_query_desc* d, const std::vector<uint64_t>& ids, ott_hit* out, uint64_t cap, uint64_t* n_out,
                     uint64_t* n_per_query, ott_stats* stats);
 int multi_score_rows(ott_store* ms, const float* queries, uint32_t nq, uint32_t metric, const uint64_t* ids, uint64_t n_ids, float* out_scores);
+// ott_gather.hip: ott_query_ids on a context whose `mu` the caller holds (and the owner's `rw`, shared), for ott_query_mmr's first stage.
+// u: the list ascending and duplicate-free (ids of cleared chunks are dropped from it), d->k = min(k, pool) >= 1, n_listed: the ids as listed
+int query_ids_on(ott_store* ctx, const ott_query_desc* d, std::vector<uint64_t>& u, uint64_t n_listed, ott_hit* out, uint64_t cap, uint64_t* n_out,
+                 uint64_t* n_per_query, ott_stats* stats);
+int check_ids(const char* who, const uint64_t* ids, uint64_t n_ids, uint64_t len);  // an id list's argument errors, for entry point `who`
 // Grouped search (ott_group.hip).  group_grow: the rows were reallocated to ncap slots (realloc_store keeps the ids that are there);
 // group_drop: the ids go.  make_run_plan (ott_api.hip): chunk mask -> runs of surviving chunks, as every query builds them.
 // sort_group_pairs (ott_sort.hip): the n (key, query) pairs a grouped query compacted into (l_keysA, l_qA) through the radix sort,

@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import GROUP_SIZE_MAX, Cmp, Metric, Mode, Path, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type
+from .vec import GROUP_SIZE_MAX, Cmp, Metric, Mode, Path, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type, mmr_args
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -737,6 +737,7 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         self._row_ids = None
         self._distinct: Optional[str] = None
         self._keep = 1  # distinct_by(name, keep=m): rows per distinct value
+        self._mmr = None  # mmr(): (lambda_mult, fetch_k or None)
 
     def meta_filter(self, expr: Expr) -> "MetaQueryPlan":  # src/meta.rs:605-616 (error deferred to collect)
         try:
@@ -776,6 +777,13 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         self._keep = keep
         return self
 
+    def mmr(self, lambda_mult: float = 0.5, fetch_k: Optional[int] = None) -> "MetaQueryPlan":
+        """MMR diversity re-ranking (VecQueryPlan.mmr): of the best `fetch_k` rows that pass meta_filter and vec_filter, take(k)
+        picked greedily by relevance and dissimilarity to the rows already picked; the result rows come out in pick order.  Needs
+        take(k); one query, not a batch; not together with distinct_by.  Refused at collect()."""
+        self._mmr = (lambda_mult, fetch_k)
+        return self
+
     def resolve(self):
         """Host-side part of collect (src/meta.rs:632-669): k / take defaults, zonemap prune.
         Returns (ResolvedQuery, chunk_mask or None, compiled filter or None)."""
@@ -791,6 +799,13 @@ class MetaQueryPlan:  # src/meta.rs:579-830
             if isinstance(self._keep, bool) or not isinstance(self._keep, (int, np.integer)) or not 1 <= int(self._keep) <= GROUP_SIZE_MAX:
                 raise OttersError(f"distinct_by: keep must be an integer 1 .. {GROUP_SIZE_MAX}, not {self._keep!r}")
             n_groups = st._distinct_ids(self._distinct)[1]
+        mmr = None
+        if self._mmr is not None:
+            if self._distinct is not None:
+                raise OttersError("mmr cannot be combined with distinct_by in this version")
+            if len(self.queries) > 1:
+                raise OttersError("mmr takes one query, not a batch")
+            mmr = mmr_args(self._mmr[0], self._mmr[1], self.take_count)
         k = self.take_count if self.take_count is not None else (n_groups if self._distinct is not None else st._n_rows)  # src/meta.rs:638-640
         take = self.take_type if self.take_type is not None else (infer_default_take_type(self.metric))
         for q in self.queries:
@@ -802,6 +817,7 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         rq = ResolvedQuery(queries=q, metric=int(self.metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft,
                            row_mask=None, mode=int(Mode.Merged), path=int(self._path), grouped=self._distinct is not None,
                            group_size=int(self._keep) if self._distinct is not None and int(self._keep) > 1 else 0)  # (keep = 1: ott_query_groups, as before)
+        rq.mmr = mmr
         if self._row_ids is not None:
             ids = as_row_ids(self._row_ids)
             if chunk_mask is not None and ids.size:  # (an id past the store's end stays: the library names it)

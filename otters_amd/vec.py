@@ -105,6 +105,8 @@ class ResolvedQuery:
     group_size: int = 0                   # per_group(m): up to m hits per group (ott_query_groups_top); 0 = not a per_group plan
     group_list: Optional[np.ndarray] = None    # with_groups: uint32[n listed] dense group ids, in the caller's order, duplicates kept (ott_query_maxsim_groups), or None
     group_of_hit: Optional[np.ndarray] = None  # OUTPUT of VecStore._run for a per_group plan: uint32[n hits], the dense group id of every hit
+    mmr: Optional[tuple] = None                # mmr: (lambda as float32, fetch_k) -- the picks of ott_query_mmr instead of the top-k
+    mmr_values: Optional[np.ndarray] = None    # OUTPUT of VecStore._run for an mmr plan: float32[n hits], the value of every pick
 
 
 def as_row_ids(ids) -> np.ndarray:
@@ -169,6 +171,33 @@ def dense_listed_groups(store: "VecStore", listed) -> np.ndarray:
 
 GROUP_SIZE_MAX = 16  # include/otters_hip.h: OTT_GROUP_SIZE_MAX
 MAXSIM_BATCH_MAX = 4096  # include/otters_hip.h: OTT_MAXSIM_BATCH_MAX
+MMR_MAX_FETCH = 1024  # include/otters_hip.h: OTT_MMR_MAX_FETCH
+
+
+def mmr_default_fetch_k(k: int) -> int:
+    """mmr()'s candidate count when the caller names none: five times the picks, at least 20, at most OTT_MMR_MAX_FETCH"""
+    return min(MMR_MAX_FETCH, max(20, 5 * int(k)))
+
+
+def mmr_args(lam, fetch_k, take_count):
+    """mmr()'s arguments checked against the plan's take: (lambda as float32, fetch_k).  Pure host logic."""
+    if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not 0.0 <= float(lam) <= 1.0:
+        raise OttersError(f"mmr: lambda_mult must be a number in [0, 1], not {lam!r}")
+    if take_count is None:
+        raise OttersError("mmr needs an explicit take: the number of picks (take, take_min or take_max)")
+    k = int(take_count)
+    if k < 1:
+        raise OttersError(f"mmr: take must be at least 1, not {k}")
+    if fetch_k is None:
+        fetch_k = mmr_default_fetch_k(k)
+    elif isinstance(fetch_k, bool) or not isinstance(fetch_k, (int, np.integer)):
+        raise OttersError(f"mmr: fetch_k must be an integer, not {fetch_k!r}")
+    fetch_k = int(fetch_k)
+    if fetch_k > MMR_MAX_FETCH:
+        raise OttersError(f"mmr: fetch_k {fetch_k} is above the limit of {MMR_MAX_FETCH} candidates")
+    if k > fetch_k:
+        raise OttersError(f"mmr: take({k}) asks for more picks than fetch_k = {fetch_k} candidates")
+    return np.float32(lam), fetch_k
 
 
 def infer_default_take_type(metric: Metric) -> TakeType:  # src/vec.rs:92-98
@@ -194,6 +223,7 @@ class VecQueryPlan:
         self._max_sim = False
         self._per_group = None  # per_group(m): m as the caller gave it (checked at validate())
         self.group_list = None  # with_groups: the labels as the caller gave them (mapped at validate())
+        self._mmr = None        # mmr(): (lambda_mult, fetch_k or None) as the caller gave them (checked at validate())
 
     @staticmethod
     def new() -> "VecQueryPlan":
@@ -307,6 +337,21 @@ class VecQueryPlan:
             self.group_list = labels
         return self
 
+    def mmr(self, lambda_mult: float = 0.5, fetch_k: Optional[int] = None) -> "VecQueryPlan":
+        """MMR diversity re-ranking (maximal marginal relevance; ott_query_mmr): of the plan's best `fetch_k` hits -- exactly the
+        hits of the same plan with take(fetch_k) -- pick take(k) greedily, each pick the one that maximises lambda_mult x relevance
+        - (1 - lambda_mult) x its largest similarity to a row already picked (for a Min take both terms change sign).  Similarity
+        is the plan's own metric between the stored rows.  lambda_mult = 1 returns the plain top-k, 0 ranks by diversity alone.
+        fetch_k defaults to min(1024, max(20, 5 k)).  The hits come out in pick order; collect_mmr() also returns every pick's
+        value.  Needs an explicit take / take_min / take_max; combines with filter, with_row_mask, with_row_ids, per_query (one
+        MMR per query) and with_path; not with one_per_group, per_group or max_sim; not on a multi-GPU store."""
+        if self.error is None:
+            self._mmr = (lambda_mult, fetch_k)
+        return self
+
+    def _mmr_args(self):
+        return mmr_args(self._mmr[0], self._mmr[1], self.take_count)
+
     def _dense_group_list(self) -> np.ndarray:
         """with_groups' labels as uint32 dense group ids, in the caller's order (the library sorts and dedupes them)"""
         return dense_listed_groups(self.vector_store, self.group_list)
@@ -351,6 +396,16 @@ class VecQueryPlan:
             if not self._max_sim:
                 raise OttersError("with_groups needs max_sim in this version; use with_row_mask")
             self._dense_group_list()
+        if self._mmr is not None:
+            if self._per_group is not None:
+                raise OttersError("mmr cannot be combined with per_group in this version")
+            if self._grouped:
+                raise OttersError("mmr cannot be combined with one_per_group in this version")
+            if self._max_sim:
+                raise OttersError("mmr cannot be combined with max_sim: a hit of max_sim is a group, not a row")
+            if len(self.query_vectors) > 1 and self._mode != Mode.PerQuery:
+                raise OttersError("mmr takes one query; a batch needs per_query() (one MMR per query)")
+            self._mmr_args()
         dim = self.vector_store.dim
         if isinstance(self.query_vectors, np.ndarray):  # a matrix: every row has the same length
             if self.query_vectors.shape[1] != dim:
@@ -380,7 +435,8 @@ class VecQueryPlan:
         return ResolvedQuery(queries=queries, metric=int(self.search_metric), take=int(take), k=max(int(k), 0),
                              filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, mode=int(self._mode), path=int(self._path),
                              row_ids=None if self.row_ids is None else as_row_ids(self.row_ids), grouped=self._grouped,
-                             max_sim=self._max_sim, group_size=0 if self._per_group is None else int(self._per_group), group_list=group_list)
+                             max_sim=self._max_sim, group_size=0 if self._per_group is None else int(self._per_group), group_list=group_list,
+                             mmr=None if self._mmr is None else self._mmr_args())
 
     def collect(self):  # src/vec.rs:205-311
         hits, counts = self.collect_arrays()[:2]  # (a per_group plan returns the hits' groups too)
@@ -424,6 +480,19 @@ class VecQueryPlan:
                 o += c
             return out
         return by_group(0, len(idx))
+
+    def collect_mmr(self):
+        """An mmr() plan's picks with their values: (hits, counts, values) -- collect_arrays()'s hits and counts, in pick order, and
+        `values[i]` (f32) = lambda x relevance - (1 - lambda) x redundancy of hits[i] at the moment it was picked."""
+        if self._mmr is None:
+            raise OttersError("collect_mmr needs an mmr() plan")
+        rq = self.resolve()
+        store = self.vector_store
+        hits, counts, stats = store._run(rq)
+        store.last_stats = stats
+        if rq.mode != Mode.PerQuery:
+            counts = np.bincount(hits["query"], minlength=rq.queries.shape[0]).tolist()
+        return hits, counts, rq.mmr_values if rq.mmr_values is not None else np.zeros(0, dtype=np.float32)
 
     def collect_arrays(self):
         """collect() without the per-hit Python objects: (hits, counts) where `hits` is a NumPy record array
@@ -908,6 +977,12 @@ class VecStore:
             rq.group_of_hit = gids[: n_out.value].copy()
         elif rq.grouped:
             N.check(N.lib().ott_query_groups(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        elif rq.mmr is not None:
+            lam, fetch_k = rq.mmr
+            vals = np.empty(cap, dtype=np.float32)
+            N.check(N.lib().ott_query_mmr(self._handle(), C.byref(d), None if ids is None else N.ptr(ids), 0 if ids is None else ids.size, fetch_k,
+                                          float(lam), N.ptr(out), cap, C.byref(n_out), per, N.ptr(vals), C.byref(st)))
+            rq.mmr_values = vals[: n_out.value].copy()
         elif ids is None:
             N.check(N.lib().ott_query(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         else:
