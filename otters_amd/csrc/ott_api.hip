@@ -197,6 +197,7 @@ struct ExactCtx {
     std::vector<uint32_t> preA, preB;
     int gridA = 0, gridB = 0;
     double qt = 0.0, qn = 0.0, q1 = 0.0;
+    PruneQuant qq{0, 0.0f, 0.0f, 0.0, 0};  // four bits per dim: the quantised query (ott_prune.h)
     // the result block, as the merge kernel sees it
     ExactResult res{0, 0, 0};
     uint64_t* d_counts = nullptr;
@@ -211,7 +212,9 @@ void plan_pruned_sweep(ExactCtx& c) {
     ott_store* s = c.s;
     const PruneIn in{s->dim, s->ld, c.d->metric, c.perq, c.x.lean, s->cur_flat, c.x.variant, s->opt.exact_prune, s->opt.exact_sketch,
                      SketchState{s->d_sketch != nullptr, s->sk_n >= s->n, s->sk_bits, s->sk_words, s->sk_stage0}, c.pl.rows_scored, c.x.E};
-    const PrunePlan pp = prune_plan(in);
+    PrunePlan pp = prune_plan(in);
+    // (the four-bit form needs the quantised query; a query the quantiser refuses takes the plan of a store without a sketch)
+    if (prune_plan_needs_quant(in, pp) && !prune_query_quant(c.queries, s->dim, pp.c * 32, &c.qq)) pp = prune_plan_quant_refused(in);
     if (!pp.c) return;
     split_plan(c.pl, pp.seed, c.plA, c.plB);
     const bool two_runs_each = c.plA.runs.size() <= 2 && c.plB.runs.size() <= 2 && c.plB.rows_scored > 0;
@@ -304,6 +307,10 @@ int pruned_sweep(ExactCtx& c) {
         pb.sk_stage0 = s->sk_stage0;
         pb.sk_bits = s->sk_bits;
         pb.prune_q1 = c.q1;
+        pb.prune_qe1 = c.qq.qe1;
+        pb.prune_qscale = c.qq.scale;
+        pb.prune_qinv_scale = c.qq.inv_scale;
+        pb.prune_qsum = c.qq.qsum;
     }
     return launch_exact(s, pb, 1, c.x.E, c.gridB);
 }

@@ -40,7 +40,16 @@ constexpr int EXACT_SMEM_DUMP = EXACT_SMEM + WAVES * DUMP_QCAP * 12;
 // plus a whole tile's 64 more
 constexpr int PQ_CAP = 128;
 constexpr int PQ_WORDS = 10;
-constexpr int EXACT_SMEM_PRUNE = EXACT_SMEM + WAVES * PQ_CAP * PQ_WORDS * 4;  // 52 KB: two workgroups per CU
+// four bits per dim: the digit planes of the quantised query behind the queues — per stage three digits x four words (ott_prune.h)
+constexpr int QD_WORDS = (int)(OTT_QEMB_MAX / KC) * 12;
+constexpr int EXACT_SMEM_PRUNE = EXACT_SMEM + WAVES * PQ_CAP * PQ_WORDS * 4 + QD_WORDS * 4;  // 53.3 KB: two workgroups per CU
+// experiment builds only: -DOTT_SK4_DECODE_F32 keeps the four-bit form's former decode (an f32 chain, one fma per dim, and
+// prune_score_bound_sketchb) so that both decodes can be alternated in one job
+#ifdef OTT_SK4_DECODE_F32
+constexpr bool SK4_INT = false;
+#else
+constexpr bool SK4_INT = true;
+#endif
 // sketch form of the pruned sweep (SK = 1): the sign words of a row's sketch line a lane keeps in registers — with a and rho at most
 // three 16-B loads (OTT_SKETCH1_MAX_WORDS, ott_internal.h)
 constexpr int SK_MAXW = (int)OTT_SKETCH1_MAX_WORDS;
@@ -115,7 +124,9 @@ __device__ __forceinline__ void exact_glds16(const char* sbase, uint32_t voff, u
 // SK = 4: the four-bit sketch of every stage but the first, so the checkpoint is behind stage 0.  A line is a header piece and one
 // 16-B piece per sketched stage, up to 28.  The 64 lines of a tile are fetched as the row stages are: eight pieces of every line per
 // round, coalesced, through the staging registers into the stage buffer, the next round in flight while the lane decodes its own
-// line's pieces out of LDS.  The same four operations per dim; kmax = 15.
+// line's pieces out of LDS.  The decode is integer: the workgroup quantises the query once (ott_prune.h: prune_quant_word) and keeps
+// its three base-16 digit planes in LDS; a piece's four code words meet the stage's digit words in twelve v_dot8_i32_i4, three
+// independent i32 sums, and prune_score_bound_sketchq takes K = sum qhat kappa, exact.
 template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false, int SK = 0>
 __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) {
     static_assert(!I8 || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL), "the int8 sweep takes one query, cosine / dot, merged");
@@ -196,6 +207,21 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
     const uint32_t gw = blockIdx.x * BW + wave, nw = gridDim.x * BW;
     const int sw = (lane >> 1) & 7;
     const uint32_t nstages = (p.ld + KC - 1) / KC;
+    // SK = 4: the digit planes of the quantised query, [stage][digit][word]; one thread per word of eight dims (zeros past dim)
+    [[maybe_unused]] uint32_t* qd = reinterpret_cast<uint32_t*>(smem + WAVES * STAGE_FLOATS + WAVES * PQ_CAP * PQ_WORDS);
+    if constexpr (SK == 4 && SK4_INT) {
+        const uint32_t nqs = nstages < (uint32_t)(QD_WORDS / 12) ? nstages : (uint32_t)(QD_WORDS / 12);
+        for (uint32_t i = threadIdx.x; i < nqs * 4; i += 64 * BW) {
+            float q8[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) q8[j] = (8 * i + j < p.dim) ? Q[8 * i + j] : 0.0f;
+            uint32_t d3[3];
+            prune_quant_word(q8, p.prune_qinv_scale, d3);
+#pragma unroll
+            for (int d = 0; d < 3; d++) qd[(i >> 2) * 12 + d * 4 + (i & 3)] = d3[d];
+        }
+        __syncthreads();
+    }
     const int lrow = lane >> 3;          // row within an 8-row load group
     const int lslot = lane & 7;          // 16-B slot within the 128-B line
     // its float offset, kept inside a short row (dim < 29): the staging loads are unconditional, so a slot past the row's
@@ -544,7 +570,9 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             if constexpr (SK == 4) {
                 if (gate != 0) {  // (wave-uniform; round 0 of the lines is in R, or on its way)
                     const uint32_t np = p.sk_pitch >> 2;  // [a | rho | 0 | 0], then one piece per sketched stage
-                    float D = 0.0f, sk_a = 0.0f, sk_rho = __builtin_inff();
+                    [[maybe_unused]] float D = 0.0f;
+                    [[maybe_unused]] int K0 = 0, K1 = 0, K2 = 0;
+                    float sk_a = 0.0f, sk_rho = __builtin_inff();
                     for (uint32_t f = 0; 8 * f < np; f++) {
                         // round f to the stage buffer (the row stages' swizzle); the next round is in flight while this one is decoded
 #pragma unroll
@@ -566,18 +594,38 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                             const uint32_t sj = p.sk_stage0 + piece - 1u;  // piece i >= 1 holds sketched stage i - 1: eight fields per word
                             if (sj >= p.prune_stage && sj < nstages) {
                                 const uint32_t w[4] = {__float_as_uint(w4.x), __float_as_uint(w4.y), __float_as_uint(w4.z), __float_as_uint(w4.w)};
+                                if constexpr (SK4_INT) {
+                                    // the stage's digit words: three broadcast reads (a wave-uniform address)
+                                    const v4u* dp = reinterpret_cast<const v4u*>(qd + sj * 12);
+                                    const v4u d0 = dp[0], d1 = dp[1], d2 = dp[2];
 #pragma unroll
-                                for (int b = 0; b < 32; b++) {
-                                    const int code = (int)(w[b >> 3] << (28 - 4 * (b & 7))) >> 28;
-                                    D = fmaf((float)(2 * code + 1), Q[sj * KC + b], D);
+                                    for (int i = 0; i < 4; i++) {
+                                        K0 = __builtin_amdgcn_sdot8((int)w[i], (int)d0[i], K0, false);
+                                        K1 = __builtin_amdgcn_sdot8((int)w[i], (int)d1[i], K1, false);
+                                        K2 = __builtin_amdgcn_sdot8((int)w[i], (int)d2[i], K2, false);
+                                    }
+                                } else {
+#pragma unroll
+                                    for (int b = 0; b < 32; b++) {
+                                        const int code = (int)(w[b >> 3] << (28 - 4 * (b & 7))) >> 28;
+                                        D = fmaf((float)(2 * code + 1), Q[sj * KC + b], D);
+                                    }
                                 }
                             }
                         }
                         wave_sync();
                     }
                     if (valid) {
-                        const float b = prune_score_bound_sketchb(acc[0], vinv, sk_a, sk_rho, D, 15.0, p.prune_stage * KC, p.dim, p.prune_qt, p.prune_q1,
-                                                                  p.prune_qn, qinv[0], p.metric == OTT_METRIC_COSINE, take_max);
+                        float b;
+                        if constexpr (SK4_INT) {
+                            // kappa = 2 code + 1: K = sum qhat kappa = 2 sum qhat code + sum qhat
+                            const int K = 2 * (256 * K2 + 16 * K1 + K0) + p.prune_qsum;
+                            b = prune_score_bound_sketchq(acc[0], vinv, sk_a, sk_rho, K, p.prune_qscale, p.dim, p.prune_qt, p.prune_qe1, p.prune_qn, qinv[0],
+                                                          p.metric == OTT_METRIC_COSINE, take_max);
+                        } else {
+                            b = prune_score_bound_sketchb(acc[0], vinv, sk_a, sk_rho, D, 15.0, p.prune_stage * KC, p.dim, p.prune_qt, p.prune_q1,
+                                                          p.prune_qn, qinv[0], p.metric == OTT_METRIC_COSINE, take_max);
+                        }
                         keep = !(b == b && ord_of(b, take_max) < gate);  // (NaN: no bound, the row is finished)
                     }
                 }

@@ -173,6 +173,14 @@ inline PrunePlan prune_plan(const PruneIn& in) {
     if (seed < 64) seed = 64;
     return PrunePlan{c, sketch, seed};
 }
+// The four-bit form decodes a line against the quantised query (ott_prune.h: prune_query_quant), so a plan in that form needs the
+// quantiser to accept the query.  Where it refuses, the call takes the plan it would take had the store no sketch: the 7/8 form
+// with its own checkpoint and seed (or none, when prune_query_bounds refuses the query too) — never a slower four-bit decode.
+inline bool prune_plan_needs_quant(const PruneIn& in, const PrunePlan& pp) { return pp.c != 0 && pp.sketch && in.sk.bits == 4; }
+inline PrunePlan prune_plan_quant_refused(PruneIn in) {
+    in.exact_sketch = 0;
+    return prune_plan(in);
+}
 
 // ---- the result block --------------------------------------------------------------------------------------------------------------
 // [counts (groups x u64, padded to 64 B) | hits (groups x KS)], and on the host 8 bytes more behind it: the pruned sweep's tail counter

@@ -548,6 +548,11 @@ struct ExactParams {
     const uint32_t* prune_sketch;
     unsigned long long* prune_tails;
     double prune_qt, prune_qn, prune_q1;
+    // four bits per dim: the quantised query of the integer decode (ott_prune.h: PruneQuant) — the scale 2^e and its reciprocal, an
+    // upper bound of the tail's quantisation error in the 1-norm, the tail's integer sum.  The kernel quantises the query itself.
+    double prune_qe1;
+    float prune_qscale, prune_qinv_scale;
+    int32_t prune_qsum;
     float qemb[OTT_QEMB_MAX];  // last: the embedded query (kernel arguments are limited to 4 KB)
 };
 // (OTT_QEMB_MAX and the OTT_SKETCH*_MAX_WORDS limits of the sketch forms: ott_exact_plan.h)

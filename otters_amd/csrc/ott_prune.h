@@ -306,6 +306,126 @@ OTT_PRUNE_HD inline void prune_sketchb_row(const float* v, uint32_t dim, uint32_
     line[1] = prune_f2u(rho);
 }
 
+// ---- the quantised query of the four-bit form ("the integer decode") --------------------------------------------
+// The four-bit line stores eight two's-complement codes per word: one operand of a signed 4-bit dot product.  The query's other
+// operand: q_i = 2^e qhat_i + e_i with integers |qhat_i| <= 1911 = 7 * 273, split into balanced base-16 digits qhat = 256 d2 + 16 d1
+// + d0, every d in [-8, 7].  The digit of dim 32 s + 8 w + j sits at bits 4 j .. 4 j + 3 of word w of stage s, where the code of that
+// dim sits in its piece, so sum_i code_i qhat_i = 256 K2 + 16 K1 + K0 with K_d = the dot products of the code words and the digit
+// words, exact in i32 (896 dims x 8 x 8 < 2^16), and K = sum_i kappa_i qhat_i = 2 (256 K2 + 16 K1 + K0) + sum_i qhat_i.
+// 2^e is a power of two taken from max |q_i| over the WHOLE query, so q_i 2^-e and 2^e qhat_i are exact wherever they do not
+// underflow; the quantiser is one function for host and kernel, a single f32 multiply (no contraction) and a round to nearest even.
+// A product that underflows, to a subnormal or to zero, rounds to 0 either way.
+constexpr int32_t PRUNE_QHAT_MAX = 1911;
+OTT_PRUNE_HD inline int32_t prune_quant_q(float q, float inv_scale) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float t = __fmul_rn(q, inv_scale);
+#else
+    volatile float t0 = q * inv_scale;
+    const float t = t0;
+#endif
+    const float r = rintf(t);
+    if (!(r == r)) return 0;
+    return r > (float)PRUNE_QHAT_MAX ? PRUNE_QHAT_MAX : r < -(float)PRUNE_QHAT_MAX ? -PRUNE_QHAT_MAX : (int32_t)r;
+}
+// the balanced digits of |qhat| <= 1911 (all of [-2184, 1911] has them)
+OTT_PRUNE_HD inline void prune_quant_digits(int32_t qhat, int32_t d[3]) {
+    d[0] = ((qhat + 8) & 15) - 8;
+    const int32_t r1 = (qhat - d[0]) >> 4;  // (exact: a multiple of 16)
+    d[1] = ((r1 + 8) & 15) - 8;
+    d[2] = (r1 - d[1]) >> 4;
+}
+// eight consecutive dims of the query (zeros past `dim`) -> their word of each digit plane
+OTT_PRUNE_HD inline void prune_quant_word(const float q8[8], float inv_scale, uint32_t out[3]) {
+    out[0] = out[1] = out[2] = 0u;
+    for (int j = 0; j < 8; j++) {
+        int32_t d[3];
+        prune_quant_digits(prune_quant_q(q8[j], inv_scale), d);
+        for (int k = 0; k < 3; k++) out[k] |= ((uint32_t)d[k] & 15u) << (4 * j);
+    }
+}
+// sum over the eight nibbles of a and b, both signed: what v_dot8_i32_i4 adds to its accumulator (plain C; the kernel calls the
+// instruction, tests/test_exact_prune_sketchq_bound.py holds this restatement to the direct sum)
+OTT_PRUNE_HD inline int32_t prune_dot8_i4(uint32_t a, uint32_t b, int32_t acc) {
+    for (int j = 0; j < 8; j++) acc += ((int32_t)(a << (28 - 4 * j)) >> 28) * ((int32_t)(b << (28 - 4 * j)) >> 28);
+    return acc;
+}
+
+struct PruneQuant {
+    int e;                   // the scale is 2^e
+    float scale, inv_scale;  // 2^e and 2^-e, both normal floats
+    double qe1;              // >= sum over i >= m of |q_i - 2^e qhat_i| (double, inflated like the norms)
+    int32_t qsum;            // sum over i >= m of qhat_i, exact
+};
+// Host: the scale of a finite query and the two tail sums the bound needs (m a multiple of 32).  The smallest 2^e with
+// max |q_i| 2^-e <= 1911.  False — the integer decode is not available for this query — when the query is zero or not finite, or
+// when 2^e or 2^-e is not a normal float (max |q_i| below about 2^-116).
+inline bool prune_query_quant(const float* q, uint32_t dim, uint32_t m, PruneQuant* out) {
+    float mx = 0.0f;
+    for (uint32_t i = 0; i < dim; i++) {
+        const float x = fabsf(q[i]);
+        if (!(x <= 3.4028234e38f)) return false;
+        if (x > mx) mx = x;
+    }
+    if (!(mx > 0.0f)) return false;
+    int x2;
+    (void)frexp((double)mx, &x2);  // mx = f 2^x2, f in [0.5, 1); 1911 = 0.933.. x 2^11
+    int e = x2 - 11;
+    if (ldexp((double)mx, -e) > (double)PRUNE_QHAT_MAX) e++;
+    if (e < -126 || e > 126) return false;  // 2^e and 2^-e are normal floats exactly for e in [-126, 126]
+    out->e = e;
+    out->scale = (float)ldexp(1.0, e);
+    out->inv_scale = (float)ldexp(1.0, -e);
+    double t = 0.0;
+    int64_t sum = 0;
+    for (uint32_t i = m; i < dim; i++) {
+        const int32_t h = prune_quant_q(q[i], out->inv_scale);
+        t += fabs((double)q[i] - (double)out->scale * (double)h);  // (2^e qhat and the difference: exact in double)
+        sum += h;
+    }
+    out->qe1 = t * (1.0 + 0x1p-30);
+    out->qsum = (int32_t)sum;  // (|sum| <= 1911 dim: the launch carries at most 896 dims; any dim <= 2^20 fits)
+    return true;
+}
+
+// The bound of the integer decode.  With v_t = a kappa + r, ||r|| <= rho, q_i = 2^e qhat_i + e_i and K = sum qhat_i kappa_i:
+//   q_t . v_t = a 2^e K + a (e_t . kappa) + q_t . r  <=  a 2^e K + a kmax qe1 + ||q_t|| rho,        kmax = 15
+// C = a 2^e K is exact in double (a has 24 bits, |K| <= 1911 * 15 * 864 < 2^25); the f32 chain's term a n_t u' kmax ||q_t||_1 is
+// gone.  Everything else is prune_score_bound_sketchb's: Pa, G, the slack, the outward rounding, the cosine scaling, the zero rule,
+// the NaN cases, Take Min as the mirror image.  Valid for every line: a 4-bit code gives |kappa_i| <= 15 whatever it holds.
+OTT_PRUNE_HD inline float prune_score_bound_sketchq(const float acc[8], float vinv, float a, float rho, int32_t K, float scale, uint32_t dim,
+                                                    double qt, double qe1, double qn, float qinv, bool cosine, bool upper) {
+    const float nan = prune_u2f(0x7FC00000u);
+    if (!(vinv >= 0x1p-50f && vinv <= 3.4028234e38f)) return nan;  // zero, tiny, huge, inf or NaN norm: no bound
+    if (!(rho >= 0.0f && rho <= 3.4028234e38f)) return nan;        // no sketch of this tail
+    if (!(a >= 0.0f && a <= 3.4028234e38f)) return nan;
+    if (cosine && !(qinv > 0.0f && qinv <= 3.4028234e38f)) return nan;
+    double P = 0.0, Pa = 0.0;
+    for (int l = 0; l < 8; l++) {
+        const double x = (double)acc[l];
+        if (!(x - x == 0.0)) return nan;
+        P += x;
+        Pa += fabs(x);
+    }
+    const double u = 0x1p-24;
+    const double iv = 1.0 / (double)vinv;
+    const double vn2 = iv * iv * (1.0 + 2.0 * ((double)dim + 8.0) * u) + (double)dim * 0x1p-148;
+    const double C = (double)a * (double)scale * (double)K;              // the centre of the tail: exact
+    const double W = (double)a * (15.0 * qe1) + qt * (double)rho;        // its half width
+    const double G = 2.0 * ((double)(dim / 8) + 9.0) * u * qn * sqrt(vn2);
+    const double r = W + G + (Pa + fabs(C) + W + G) * 0x1p-40 + (double)dim * 0x1p-147;
+    float S = upper ? prune_f32_up(P + C + r) : prune_f32_down(P + C - r);
+    if (cosine) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        S = __fmul_rn(__fmul_rn(S, qinv), vinv);
+#else
+        volatile float t1 = S * qinv;  // (two separate f32 roundings, as in the kernel)
+        S = t1 * vinv;
+#endif
+    }
+    if (S == 0.0f) S = upper ? 0.0f : -0.0f;
+    return S;
+}
+
 // The sign sketch's own names: the b = 1 case of the functions above (sum v_i kappa_i = sum |v_i| there, sum kappa_i^2 = n, the same
 // operations in the same order: the same bits).
 typedef PruneSketchSumsB PruneSketchSums;
