@@ -2,10 +2,14 @@
 // `c` of the row's 128-B stages (8 rows x 128 B per wave instruction, one stage in flight, as exact_kernel does) and then one
 // `pitch`-byte line per row from a second buffer with lane = row (16 B per lane and instruction at a stride of `pitch`), all with
 // non-temporal loads; the values go into a checksum so nothing is optimised away.  Prints TB/s of bytes REQUESTED.
-//   prefix_stream [rows=10000000] [dim=768] [c=9] [pitch=192] [workgroups per CU=2] [lines as stages=0]
-//   (dim a multiple of 32, pitch of 16, <= 512)
+//   prefix_stream [rows=10000000] [dim=768] [c=9] [pitch=192] [workgroups per CU=2] [lines as stages=0] [head=0] [pipelined=0]
+//   (dim a multiple of 32, pitch of 16, <= 512; c = 0 reads no row stage)
 // lines as stages = 1: the tile's 64 lines are read as the row stages are — eight 16-B pieces of every line per round, 8 lines x
 // 128 B per wave instruction — which is how the four-bit form of the sweep fetches them
+// head = 1: the tile's 64 inverse norms are read as well, one f32 per row with lane = row; head = 2: a 16-B record and two f32
+// per row from three plain arrays, lane = row (the head of DESIGN.md 3.1b: stage 0's codes, rho_all and the inverse norm)
+// pipelined = 1 (c = 0 and lines as stages only): the next round of lines, or the next tile's first round and its head, is asked
+// for before the current round is summed, so a tile's first round does not wait behind the last tile's sums
 //   hipcc -O3 --offload-arch=gfx950 prefix_stream.hip -o prefix_stream
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -14,7 +18,8 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
 __global__ __launch_bounds__(256) void sweep(const float* __restrict__ rows, const char* __restrict__ lines, uint64_t n_tiles, uint32_t ld,
-                                             uint32_t c, uint32_t pitch, int staged, float* out) {
+                                             uint32_t c, uint32_t pitch, int staged, int head, const v4f* __restrict__ hcode, const float* __restrict__ hrho,
+                                             const float* __restrict__ hinv, float* out) {
     const int lane = threadIdx.x & 63;
     const uint32_t gw = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
     const int lrow = lane >> 3, lslot = lane & 7;
@@ -22,6 +27,11 @@ __global__ __launch_bounds__(256) void sweep(const float* __restrict__ rows, con
     float acc = 0.f;
     for (uint64_t t = gw; t < n_tiles; t += nw) {
         const float* base = rows + t * 64 * (uint64_t)ld;
+        if (head) acc += __builtin_nontemporal_load(hinv + t * 64 + lane);
+        if (head > 1) {
+            const v4f hc = __builtin_nontemporal_load(hcode + t * 64 + lane);
+            acc += hc.x + hc.y + hc.z + hc.w + __builtin_nontemporal_load(hrho + t * 64 + lane);
+        }
         for (uint32_t s = 0; s < c; s++) {  // s < c <= ld / 32: inside the row
             v4f r[8];
 #pragma unroll
@@ -52,6 +62,47 @@ __global__ __launch_bounds__(256) void sweep(const float* __restrict__ rows, con
     if (acc == 12345.678f) out[0] = acc;
 }
 
+// c = 0, lines as stages, one round ahead across rounds and tiles
+__global__ __launch_bounds__(256) void sweep_pipe(const char* __restrict__ lines, uint64_t n_tiles, uint32_t pitch, int head, const v4f* __restrict__ hcode,
+                                                  const float* __restrict__ hrho, const float* __restrict__ hinv, float* out) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t gw = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
+    const int lrow = lane >> 3, lslot = lane & 7;
+    const uint32_t np = pitch >> 4;
+    float acc = 0.f;
+    v4f cur[8], nxt[8], hc = {0.f, 0.f, 0.f, 0.f}, hcn = {0.f, 0.f, 0.f, 0.f};
+    float hs = 0.f, hsn = 0.f;
+    uint64_t t = gw;
+    uint32_t i = 0;
+    if (t >= n_tiles) return;
+#pragma unroll
+    for (int m = 0; m < 8; m++) cur[m] = __builtin_nontemporal_load((const v4f*)(lines + (t * 64 + 8 * m + lrow) * (uint64_t)pitch + 16 * (lslot < np ? lslot : np - 1)));
+    if (head) hs = __builtin_nontemporal_load(hinv + t * 64 + lane);
+    if (head > 1) { hc = __builtin_nontemporal_load(hcode + t * 64 + lane); hs += __builtin_nontemporal_load(hrho + t * 64 + lane); }
+    for (;;) {
+        const bool last = i + 8 >= np;
+        const uint64_t t2 = last ? t + nw : t;
+        const uint32_t i2 = last ? 0 : i + 8;
+        const bool more = t2 < n_tiles;  // t2 < n_tiles: inside the arrays
+        if (more) {
+            const uint32_t pc = i2 + lslot < np ? i2 + lslot : np - 1;
+#pragma unroll
+            for (int m = 0; m < 8; m++) nxt[m] = __builtin_nontemporal_load((const v4f*)(lines + (t2 * 64 + 8 * m + lrow) * (uint64_t)pitch + 16 * pc));
+            if (last && head) hsn = __builtin_nontemporal_load(hinv + t2 * 64 + lane);
+            if (last && head > 1) { hcn = __builtin_nontemporal_load(hcode + t2 * 64 + lane); hsn += __builtin_nontemporal_load(hrho + t2 * 64 + lane); }
+        }
+#pragma unroll
+        for (int m = 0; m < 8; m++) acc += cur[m].x + cur[m].y + cur[m].z + cur[m].w;
+        if (i == 0) acc += hs + hc.x + hc.y + hc.z + hc.w;
+        if (!more) break;
+#pragma unroll
+        for (int m = 0; m < 8; m++) cur[m] = nxt[m];
+        if (last) { hs = hsn; hc = hcn; }
+        t = t2; i = i2;
+    }
+    if (acc == 12345.678f) out[0] = acc;
+}
+
 int main(int argc, char** argv) {
     const uint64_t n = argc > 1 ? strtoull(argv[1], nullptr, 10) : 10000000ull;
     const uint32_t ld = argc > 2 ? (uint32_t)atoi(argv[2]) : 768u;
@@ -59,28 +110,38 @@ int main(int argc, char** argv) {
     const uint32_t pitch = argc > 4 ? (uint32_t)atoi(argv[4]) : 192u;
     const int per_cu = argc > 5 ? atoi(argv[5]) : 2;
     const int staged = argc > 6 ? atoi(argv[6]) : 0;
-    if (n < 64 || ld == 0 || ld % 32 || c < 1 || c > ld / 32 || pitch < 16 || pitch % 16 || pitch > 512 || per_cu < 1 || per_cu > 8) {
+    const int head = argc > 7 ? atoi(argv[7]) : 0;
+    const int pipe = argc > 8 ? atoi(argv[8]) : 0;
+    if (head < 0 || head > 2 || pipe < 0 || pipe > 1 || (pipe && (c || !staged))) {
+        printf("bad arguments\n");
+        return 1;
+    }
+    if (n < 64 || ld == 0 || ld % 32 || c > ld / 32 || pitch < 16 || pitch % 16 || pitch > 512 || per_cu < 1 || per_cu > 8) {
         printf("bad arguments\n");
         return 1;
     }
     hipDeviceProp_t prop;
     CK(hipGetDeviceProperties(&prop, 0));
     const uint64_t n_tiles = n / 64;  // whole tiles only
-    float *d, *o;
-    char* l;
+    float *d, *o, *hr, *hi;
+    char *l, *hc;
+    CK(hipMalloc(&hc, n_tiles * 64 * 16)); CK(hipMalloc(&hr, n_tiles * 64 * 4)); CK(hipMalloc(&hi, n_tiles * 64 * 4));
+    CK(hipMemset(hc, 0, n_tiles * 64 * 16)); CK(hipMemset(hr, 0, n_tiles * 64 * 4)); CK(hipMemset(hi, 0, n_tiles * 64 * 4));
     CK(hipMalloc(&d, n_tiles * 64 * (size_t)ld * 4)); CK(hipMalloc(&l, n_tiles * 64 * (size_t)pitch)); CK(hipMalloc(&o, 4));
     CK(hipMemset(d, 0, n_tiles * 64 * (size_t)ld * 4)); CK(hipMemset(l, 0, n_tiles * 64 * (size_t)pitch));
     hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
     float best = 1e9f;
     for (int it = 0; it < 8; it++) {
         CK(hipEventRecord(a));
-        hipLaunchKernelGGL(sweep, dim3(prop.multiProcessorCount * per_cu), dim3(256), 0, 0, d, l, n_tiles, ld, c, pitch, staged, o);
+        if (pipe) hipLaunchKernelGGL(sweep_pipe, dim3(prop.multiProcessorCount * per_cu), dim3(256), 0, 0, l, n_tiles, pitch, head, (const v4f*)hc, hr, hi, o);
+        else hipLaunchKernelGGL(sweep, dim3(prop.multiProcessorCount * per_cu), dim3(256), 0, 0, d, l, n_tiles, ld, c, pitch, staged, head, (const v4f*)hc, hr, hi, o);
         CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
         float ms; CK(hipEventElapsedTime(&ms, a, b));
         if (it && ms < best) best = ms;
     }
-    const double bytes = (double)n_tiles * 64 * (c * 128.0 + pitch);
-    printf("rows %llu dim %u c %u pitch %u%s, %d workgroups per CU: %.3f ms  %.3f GB requested  %.2f TB/s\n", (unsigned long long)n, ld, c, pitch, staged ? " (lines as stages)" : "", per_cu,
+    const double bytes = (double)n_tiles * 64 * (c * 128.0 + pitch + (head == 2 ? 24 : head ? 4 : 0));
+    printf("rows %llu dim %u c %u pitch %u%s%s%s, %d workgroups per CU: %.3f ms  %.3f GB requested  %.2f TB/s\n", (unsigned long long)n, ld, c, pitch, staged ? " (lines as stages)" : "",
+           head == 2 ? " head 24 B" : head ? " inverse norms" : "", pipe ? " pipelined" : "", per_cu,
            best, bytes / 1e9, bytes / best / 1e9);
     return 0;
 }

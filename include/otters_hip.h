@@ -302,6 +302,13 @@ int ott_store_batch_ready(const ott_store* s);
  *   stops a row after its first 32 dims; 3 = a three-bit code per dim of the last 5/8 of the stages: 192 B per row at dim 768, 1/16
  *   of the row bytes, 1.92 GB at 10M rows, and the sweep stops a row after three eighths of its dims; 1 = the sign sketch above,
  *   32 B per row),
+ *   "exact_sketch_head" (-1, the default, and 1: wherever the store keeps four-bit lines it keeps a head beside them — per row the
+ *   four-bit codes of the first 32 dims and the norm of what all codes leave out, 20 B per row, 0.2 GB at 10M rows, made with the
+ *   lines — and the sweep then reads no f32 dims of a row whose bound misses the gate; 0 = never: the sweep reads the first 32 dims
+ *   of every row, as on a store without a head.  The sweep reads the option on every query: set to 0, the very next query reads the
+ *   first 32 dims again, whether the store still holds a head or not.  The head itself is dropped, or made for every row, at the
+ *   next append after a switch, so switched back on the option shows from that append.  Lists of k > 256 always take the sweep
+ *   without a head: the head kernel's registers leave one wave per SIMD there, and it measured slower),
  *   "id_gather" (-1 auto: lists of up to 10000 ids / 0 never / 1 wherever eligible: whether ott_query_ids scores the listed rows with the gather kernel or
  *   turns the list into a row mask and takes ott_query's paths),
  *   "group_gather" (-1 auto: lists whose groups hold up to 1000000 rows / 0 never / 1 wherever eligible: whether ott_query_maxsim_groups

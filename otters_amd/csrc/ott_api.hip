@@ -198,6 +198,7 @@ struct ExactCtx {
     int gridA = 0, gridB = 0;
     double qt = 0.0, qn = 0.0, q1 = 0.0;
     PruneQuant qq{0, 0.0f, 0.0f, 0.0, 0};  // four bits per dim: the quantised query (ott_prune.h)
+    bool head = false;                     // ... in the head form: no f32 stage in front, the query-side values over the whole query
     // the result block, as the merge kernel sees it
     ExactResult res{0, 0, 0};
     uint64_t* d_counts = nullptr;
@@ -214,13 +215,23 @@ void plan_pruned_sweep(ExactCtx& c) {
                      SketchState{s->d_sketch != nullptr, s->sk_n >= s->n, s->sk_bits, s->sk_words, s->sk_stage0}, c.pl.rows_scored, c.x.E};
     PrunePlan pp = prune_plan(in);
     // (the four-bit form needs the quantised query; a query the quantiser refuses takes the plan of a store without a sketch)
-    if (prune_plan_needs_quant(in, pp) && !prune_query_quant(c.queries, s->dim, pp.c * 32, &c.qq)) pp = prune_plan_quant_refused(in);
+    bool quant_ok = false;
+    if (prune_plan_needs_quant(in, pp) && !(quant_ok = prune_query_quant(c.queries, s->dim, pp.c * 32, &c.qq))) pp = prune_plan_quant_refused(in);
     if (!pp.c) return;
+    // (the head form: the same plan, the checkpoint in front of stage 0 — the quantiser's answer does not depend on m)
+#ifdef OTT_SK4_DECODE_F32  // (experiment builds with the former f32 decode have no head kernel)
+    const bool head = false;
+#else
+    const bool head = prune_plan_head(in, pp, quant_ok, HeadState{s->d_head != nullptr, s->head_n >= s->n, s->opt.exact_sketch_head});
+#endif
+    const uint32_t m = head ? 0u : pp.c * 32;
+    if (head) (void)prune_query_quant(c.queries, s->dim, 0, &c.qq);
     split_plan(c.pl, pp.seed, c.plA, c.plB);
     const bool two_runs_each = c.plA.runs.size() <= 2 && c.plB.runs.size() <= 2 && c.plB.rows_scored > 0;
-    if (!two_runs_each || !prune_query_bounds(c.queries, s->dim, pp.c * 32, &c.qt, &c.qn)) return;
+    if (!two_runs_each || !prune_query_bounds(c.queries, s->dim, m, &c.qt, &c.qn)) return;
     c.prune = pp;
-    c.q1 = prune_query_l1(c.queries, s->dim, pp.c * 32);
+    c.head = head;
+    c.q1 = prune_query_l1(c.queries, s->dim, m);
     c.preA = tile_prefix(c.plA, 64);
     c.preB = tile_prefix(c.plB, 64);
     c.gridA = exact_grid(s, c.preA.back());
@@ -311,6 +322,10 @@ int pruned_sweep(ExactCtx& c) {
         pb.prune_qscale = c.qq.scale;
         pb.prune_qinv_scale = c.qq.inv_scale;
         pb.prune_qsum = c.qq.qsum;
+        if (c.head) {
+            pb.prune_head_codes = reinterpret_cast<const uint32_t*>(s->d_head);
+            pb.prune_head_rho = reinterpret_cast<const float*>(s->d_head + s->cap * (size_t)16);
+        }
     }
     return launch_exact(s, pb, 1, c.x.E, c.gridB);
 }

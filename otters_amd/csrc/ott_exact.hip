@@ -131,7 +131,10 @@ template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = fals
 __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) {
     static_assert(!I8 || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL), "the int8 sweep takes one query, cosine / dot, merged");
     static_assert(!PRUNE || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL && !I8), "the pruned sweep takes one query, cosine / dot, merged");
-    static_assert((SK == 0 || PRUNE) && (SK == 0 || SK == 1 || SK == 3 || SK == 4), "the sketch is the pruned sweep's: none, one, three or four bits per dim");
+    static_assert((SK == 0 || PRUNE) && (SK == 0 || SK == 1 || SK == 3 || SK == 4 || SK == 5), "the sketch is the pruned sweep's: none, one, three or four bits per dim (5: four with a head)");
+    constexpr bool HD = SK == 5;               // the head form of the four-bit sketch: the checkpoint in front of stage 0
+    constexpr bool SK4 = SK == 4 || SK == 5;   // either four-bit form
+    static_assert(!HD || SK4_INT, "the head form decodes by integer dot products only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -209,7 +212,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
     const uint32_t nstages = (p.ld + KC - 1) / KC;
     // SK = 4: the digit planes of the quantised query, [stage][digit][word]; one thread per word of eight dims (zeros past dim)
     [[maybe_unused]] uint32_t* qd = reinterpret_cast<uint32_t*>(smem + WAVES * STAGE_FLOATS + WAVES * PQ_CAP * PQ_WORDS);
-    if constexpr (SK == 4 && SK4_INT) {
+    if constexpr (SK4 && SK4_INT) {
         const uint32_t nqs = nstages < (uint32_t)(QD_WORDS / 12) ? nstages : (uint32_t)(QD_WORDS / 12);
         for (uint32_t i = threadIdx.x; i < nqs * 4; i += 64 * BW) {
             float q8[8];
@@ -230,7 +233,8 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
 
     // PRUNE: the gate (the seed's k-th best score ordinal, 0 = open while the seed listed fewer than k rows), the stages a tile
     // runs in the sweep, the wave's queue, and how queued rows are finished
-    const uint32_t s_end = PRUNE ? p.prune_stage : nstages;
+    const uint32_t pstage = HD ? 0u : p.prune_stage;  // the checkpoint
+    const uint32_t s_end = PRUNE ? pstage : nstages;
     uint32_t theta = 0;
     if constexpr (PRUNE) {
         if (p.prune_seed[0] >= p.k) theta = ord_of(reinterpret_cast<const ott_hit*>(p.prune_seed + 8)[p.k - 1].score, take_max);
@@ -263,8 +267,8 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
 #pragma unroll
             for (int m = 0; m < 8; m++) R[m] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(rp[m] + soff));
         };
-        load_stage(p.prune_stage);
-        for (uint32_t s = p.prune_stage; s < nstages; s++) {
+        load_stage(pstage);
+        for (uint32_t s = pstage; s < nstages; s++) {
             const bool cok = s * KC + lslot * 4 < p.ld;
 #pragma unroll
             for (int m = 0; m < 8; m++) {
@@ -313,6 +317,169 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
         tails_done += n;
     };
 
+    if constexpr (HD) {
+        // The head form (ott_prune.h: prune_sketch4_head_row).  A gated tile reads no row stage: its 64 lines as in the SK = 4 form,
+        // eight pieces of every line per round through R into the stage buffer, and lane = row the 64 heads (16 B of stage 0's codes
+        // and rho_all, two plain arrays) and inverse norms.  Nothing of a tile hides its first round any more, so the loop is
+        // pipelined ACROSS tiles: while the last round of a tile is decoded, round 0 of the next tile that has a row to score, its
+        // heads and its inverse norms are in flight (`pf`).  The bound is prune_score_bound_sketchq at m = 0: an all-zero acc,
+        // rho_all, K over every stage.  A survivor is queued with zero accumulators and pq_finish runs all of its stages: the loads
+        // and additions of the full sweep in its order, so the same bits.  While the gate is open no line and no head is fetched
+        // and every row is queued.
+        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+        const uint32_t np = p.sk_pitch >> 2;  // [a | rho | 0 | 0], then one piece per stage from stage 1
+        auto locate = [&](uint32_t t, uint64_t& row0, uint32_t& cnt, uint64_t& vm) {  // tile -> rows and the lanes that score one
+            uint32_t lo = 0, hi = p.n_runs;
+            while (hi - lo > 1) {
+                uint32_t mid = (lo + hi) >> 1;
+                if (tile_prefix[mid] <= t) lo = mid;
+                else hi = mid;
+            }
+            const uint64_t rs = runs[lo].start, rc = runs[lo].count;
+            const uint64_t off = (uint64_t)(t - tile_prefix[lo]) * 64;
+            row0 = rs + off;
+            cnt = (rc - off) < 64 ? (uint32_t)(rc - off) : 64u;
+            const uint64_t r = row0 + lane;
+            bool valid = (uint32_t)lane < cnt;
+            if (p.row_mask != nullptr && valid && r < p.row_mask_bits) valid = (p.row_mask[r >> 6] >> (r & 63)) & 1;  // src/vec.rs:231-237
+            vm = __ballot(valid);
+        };
+        auto next_tile = [&](uint32_t t, uint64_t& row0, uint32_t& cnt, uint64_t& vm) -> uint32_t {  // (a whole tile masked: its rows are never read)
+            for (; t < p.n_tiles; t += nw) {
+                locate(t, row0, cnt, vm);
+                if (vm != 0) break;
+            }
+            return t;
+        };
+        v4f R[8];
+        v4u hc = {0u, 0u, 0u, 0u};
+        float hrho = __builtin_inff(), hinv = 0.0f;
+        // a piece index is clamped to the line's last piece, a row past the tile's end to its last row: nothing outside the tile's
+        // own lines, heads and inverse norms is read
+        auto load_line = [&](uint64_t row0, uint32_t cnt, uint32_t f) {
+            const uint32_t pc = (8 * f + (uint32_t)lslot < np) ? 8 * f + (uint32_t)lslot : np - 1;
+            const uint32_t* lb = p.prune_sketch + row0 * (uint64_t)p.sk_pitch + 4 * pc;
+#pragma unroll
+            for (int m = 0; m < 8; m++) {
+                const uint32_t row = 8 * m + lrow;
+                R[m] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(lb + (row < cnt ? row : cnt - 1) * p.sk_pitch));
+            }
+        };
+        auto load_head = [&](uint64_t row0, uint32_t cnt) {
+            const uint64_t r = row0 + ((uint32_t)lane < cnt ? (uint32_t)lane : cnt - 1);
+            hc = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p.prune_head_codes) + r);
+            hrho = __builtin_nontemporal_load(p.prune_head_rho + r);
+            hinv = __builtin_nontemporal_load(p.inv + r);
+        };
+        uint64_t row0 = 0, vm = 0;
+        uint32_t cnt = 0;
+        uint32_t t = next_tile(gw, row0, cnt, vm);
+        bool pf = false;  // round 0 of tile t's lines is in R, its heads and inverse norms in hc / hrho / hinv, or on their way (wave-uniform)
+        while (t < p.n_tiles) {
+            // the gate: the seed's k-th best or, once higher, the wave's own (0 while its list holds fewer than k).  It only rises, so
+            // a tile that was fetched for is gated
+            uint32_t gate = theta;
+            const uint32_t own = (uint32_t)(tk[0] >> 32);
+            if (own > gate) gate = own;
+            const uint64_t my_row = row0 + lane;
+            const bool valid = (vm >> lane) & 1;
+            uint64_t row0n = 0, vmn = 0;
+            uint32_t cntn = 0;
+            const uint32_t tn = next_tile(t + nw, row0n, cntn, vmn);
+            bool keep = valid;
+            float vinv = 0.0f;
+            if (gate != 0) {
+                if (!pf) {
+                    load_line(row0, cnt, 0);
+                    load_head(row0, cnt);
+                }
+                const v4u c0 = hc;
+                const float rho_all = hrho;
+                vinv = hinv;
+                pf = false;
+                int K0 = 0, K1 = 0, K2 = 0;
+                float sk_a = 0.0f;
+                for (uint32_t f = 0; 8 * f < np; f++) {
+#pragma unroll
+                    for (int m = 0; m < 8; m++) {
+                        const int row = 8 * m + lrow;
+                        const v4f v = R[m];
+                        *reinterpret_cast<float4*>(st + row * KC + ((lslot ^ ((row >> 1) & 7)) << 2)) = make_float4(v.x, v.y, v.z, v.w);
+                    }
+                    wave_sync();
+                    if (8 * (f + 1) < np) {
+                        load_line(row0, cnt, f + 1);
+                    } else if (tn < p.n_tiles) {  // the last round: the next tile's first
+                        load_line(row0n, cntn, 0);
+                        load_head(row0n, cntn);
+                        pf = true;
+                    }
+                    for (uint32_t j = 0; j < 8 && 8 * f + j < np; j++) {  // piece 8 f + j of the lane's own line
+                        const float4 w4 = *reinterpret_cast<const float4*>(st + lane * KC + (((int)j ^ sw) << 2));
+                        const uint32_t piece = 8 * f + j;
+                        if (piece == 0) {
+                            sk_a = w4.x;
+                            continue;
+                        }
+                        const uint32_t sj = p.sk_stage0 + piece - 1u;
+                        if (sj < nstages) {
+                            const uint32_t w[4] = {__float_as_uint(w4.x), __float_as_uint(w4.y), __float_as_uint(w4.z), __float_as_uint(w4.w)};
+                            const v4u* dp = reinterpret_cast<const v4u*>(qd + sj * 12);
+                            const v4u d0 = dp[0], d1 = dp[1], d2 = dp[2];
+#pragma unroll
+                            for (int i = 0; i < 4; i++) {
+                                K0 = __builtin_amdgcn_sdot8((int)w[i], (int)d0[i], K0, false);
+                                K1 = __builtin_amdgcn_sdot8((int)w[i], (int)d1[i], K1, false);
+                                K2 = __builtin_amdgcn_sdot8((int)w[i], (int)d2[i], K2, false);
+                            }
+                        }
+                    }
+                    wave_sync();
+                }
+                {  // stage 0: the head's codes against the stage's digit words
+                    const v4u* dp = reinterpret_cast<const v4u*>(qd);
+                    const v4u d0 = dp[0], d1 = dp[1], d2 = dp[2];
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        K0 = __builtin_amdgcn_sdot8((int)c0[i], (int)d0[i], K0, false);
+                        K1 = __builtin_amdgcn_sdot8((int)c0[i], (int)d1[i], K1, false);
+                        K2 = __builtin_amdgcn_sdot8((int)c0[i], (int)d2[i], K2, false);
+                    }
+                }
+                if (valid) {
+                    const float zero[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    const int K = 2 * (256 * K2 + 16 * K1 + K0) + p.prune_qsum;
+                    const float b = prune_score_bound_sketchq(zero, vinv, sk_a, rho_all, K, p.prune_qscale, p.dim, p.prune_qt, p.prune_qe1, p.prune_qn, qinv[0],
+                                                              p.metric == OTT_METRIC_COSINE, take_max);
+                    keep = !(b == b && ord_of(b, take_max) < gate);  // (NaN: no bound, the row is finished)
+                }
+            } else if (valid) {
+                vinv = p.inv[my_row];
+            }
+            const uint64_t km = __ballot(keep);
+            if (keep) {
+                const uint32_t at = (pq_head + pq_n + (uint32_t)__popcll(km & ((1ull << lane) - 1ull))) & (PQ_CAP - 1);
+#pragma unroll
+                for (int l = 0; l < 8; l++) pq[l * PQ_CAP + at] = 0.0f;
+                pq[8 * PQ_CAP + at] = vinv;
+                pq_row[at] = (uint32_t)my_row;
+            }
+            pq_n += (uint32_t)__popcll(km);
+            if (pq_n >= 64) {
+                // (64 survivors: about one tile in seventy at the headline's rate.  What was asked for ahead is asked for again behind
+                // the finish instead of being kept across it: its 38 registers would sit on top of the finish's own staging registers)
+                pq_finish(64);
+                if (pf) {
+                    load_line(row0n, cntn, 0);
+                    load_head(row0n, cntn);
+                }
+            }
+            t = tn;
+            row0 = row0n;
+            cnt = cntn;
+            vm = vmn;
+        }
+    } else
     for (uint32_t t = gw; t < p.n_tiles; t += nw) {
         // tile -> run of surviving chunks (wave-uniform scalar search)
         uint32_t lo = 0, hi = p.n_runs;
@@ -1611,17 +1778,30 @@ static int launch_prune(ott_store* s, const ExactParams& p, int grid) {
     return OTT_OK;
 }
 
+// (the head form exists with the integer decode only: an -DOTT_SK4_DECODE_F32 experiment build never plans it; and for lists of
+// up to four entries per lane only, k <= 256: with eight the kernel needs 256 VGPRs + 8 AGPRs, runs one wave per SIMD and measured
+// slower than the c = 1 form, so prune_plan_head never asks for it and it is not instantiated)
+template <int E, bool BLK>
+static int launch_prune_head(ott_store* s, const ExactParams& p, int grid) {
+    if constexpr (SK4_INT && E <= 4) return launch_prune<E, BLK, 5>(s, p, grid);
+    else return fail(OTT_ERR_INVALID, "launch_exact: the head form needs the integer decode and a list of k <= 256");
+}
+
 template <int MK, int NQ, int E, bool PERQ>
 static int launch_one(ott_store* s, const ExactParams& p, int grid) {
     if constexpr (MK == MK_DOT && NQ == 1 && !PERQ) {
         if (p.prune_stage != 0) {
-            const uint32_t sk = p.prune_sketch != nullptr ? p.sk_bits : 0u;  // the sketch form: the store keeps a tail sketch of 1, 3 or 4 bits per dim
-            if (sk != 0 && sk != 1 && sk != 3 && sk != 4) return fail(OTT_ERR_INVALID, "launch_exact: a tail sketch has one, three or four bits per dim");
+            uint32_t sk = p.prune_sketch != nullptr ? p.sk_bits : 0u;  // the sketch form: the store keeps a tail sketch of 1, 3 or 4 bits per dim
+            if (p.prune_head_codes != nullptr) {  // the head form: four bits per dim, no f32 stage in front (instantiated as SK = 5)
+                if (sk != 4 || p.prune_head_rho == nullptr || !SK4_INT) return fail(OTT_ERR_INVALID, "launch_exact: the head belongs to the four-bit sketch and its integer decode");
+                sk = 5;
+            }
+            if (sk != 0 && sk != 1 && sk != 3 && sk != 4 && sk != 5) return fail(OTT_ERR_INVALID, "launch_exact: a tail sketch has one, three or four bits per dim");
             if constexpr (E == 1) {
                 if (p.k > 16)  // (see BLK)
-                    return sk == 4 ? launch_prune<1, true, 4>(s, p, grid) : sk == 3 ? launch_prune<1, true, 3>(s, p, grid) : sk == 1 ? launch_prune<1, true, 1>(s, p, grid) : launch_prune<1, true, 0>(s, p, grid);
+                    return sk == 5 ? launch_prune_head<1, true>(s, p, grid) : sk == 4 ? launch_prune<1, true, 4>(s, p, grid) : sk == 3 ? launch_prune<1, true, 3>(s, p, grid) : sk == 1 ? launch_prune<1, true, 1>(s, p, grid) : launch_prune<1, true, 0>(s, p, grid);
             }
-            return sk == 4 ? launch_prune<E, (E > 1), 4>(s, p, grid) : sk == 3 ? launch_prune<E, (E > 1), 3>(s, p, grid) : sk == 1 ? launch_prune<E, (E > 1), 1>(s, p, grid) : launch_prune<E, (E > 1), 0>(s, p, grid);
+            return sk == 5 ? launch_prune_head<E, (E > 1)>(s, p, grid) : sk == 4 ? launch_prune<E, (E > 1), 4>(s, p, grid) : sk == 3 ? launch_prune<E, (E > 1), 3>(s, p, grid) : sk == 1 ? launch_prune<E, (E > 1), 1>(s, p, grid) : launch_prune<E, (E > 1), 0>(s, p, grid);
         }
     }
     if (p.prune_stage != 0) return fail(OTT_ERR_INVALID, "launch_exact: the pruned sweep takes one query, cosine / dot, merged");

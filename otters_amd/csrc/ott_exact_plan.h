@@ -177,6 +177,20 @@ inline PrunePlan prune_plan(const PruneIn& in) {
 // quantiser to accept the query.  Where it refuses, the call takes the plan it would take had the store no sketch: the 7/8 form
 // with its own checkpoint and seed (or none, when prune_query_bounds refuses the query too) — never a slower four-bit decode.
 inline bool prune_plan_needs_quant(const PruneIn& in, const PrunePlan& pp) { return pp.c != 0 && pp.sketch && in.sk.bits == 4; }
+// The head form of the four-bit sketch (ott_prune.h: prune_sketch4_head_row): the launch runs with its checkpoint in front of stage
+// 0 — a gated row reads its line and its head and no f32 stage — when the plan is the four-bit sketch form, the quantiser accepted
+// the query, the store's head covers every row and the option (exact_sketch_head) allows it.  The plan itself, its checkpoint and
+// its seed stay what prune_plan says; the query-side values are then taken with m = 0.  Lists of up to four entries per lane
+// (k <= 256) only: with eight the head kernel needs 256 VGPRs and runs one wave per SIMD, and measured slower than the c = 1 form
+// (10M x 768, k = 500: 1.95 against 1.86 ms, profiles/exact_head/README.md).
+struct HeadState {
+    bool present;  // the store holds a head
+    bool covers;   // ... for every row (head_n >= n)
+    int option;    // exact_sketch_head: -1 / 1 use it, 0 never
+};
+inline bool prune_plan_head(const PruneIn& in, const PrunePlan& pp, bool quant_ok, const HeadState& hd) {
+    return prune_plan_needs_quant(in, pp) && quant_ok && hd.present && hd.covers && hd.option != 0 && in.E <= 4;
+}
 inline PrunePlan prune_plan_quant_refused(PruneIn in) {
     in.exact_sketch = 0;
     return prune_plan(in);

@@ -91,7 +91,7 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  TWENTY-ONE of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  TWENTY-TWO of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
 // want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, group_gather, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
@@ -110,6 +110,9 @@ struct Options {
                                   // the first (384 B per row at dim 768, 1/8 of the row bytes; rows stop after their first stage), 3 = a
                                   // three-bit code per dim of the last 5/8 of the stages (192 B per row at dim 768, 1/16 of the row bytes;
                                   // rows stop at 3/8 of the stages), 1 = the sign sketch described above
+    int exact_sketch_head = -1;   // the head of the four-bit lines (20 B per row: stage 0's codes and a remainder norm over every stage, made with
+                                  // the lines): -1 / 1 = kept and used wherever the store keeps four-bit lines — a gated row then reads no f32
+                                  // stage at all — 0 = never: the sweep reads stage 0 of every row, as it does on a store without a head
     int force_fallback = 0;       // TESTS: bit mask of code paths the library otherwise takes only in rare conditions, forced on so that the
                                   // suite and the option fuzz hold them to the oracle: 1 = block lists merged by insertion (merge_kernel: the
                                   // rank merge's own fallback when a plateau overflows its buffer or there are > 4096 lists), 2 = k <= 64
@@ -266,6 +269,11 @@ struct ott_store {
     uint64_t sk_n = 0;
     uint32_t sk_words = 0, sk_pitch = 0, sk_stage0 = 0;  // code words per row, line pitch in words, first sketched stage
     uint32_t sk_bits = 0;                                // bits per sketched dim of the lines that are there (1, 3 or 4)
+    // the head of the four-bit lines (ott_prune.h: prune_sketch4_head_row), two plain arrays in one allocation: [16 cap bytes of stage
+    // 0's codes | cap floats rho_all], made by the launch that makes the lines and kept wherever they are kept (option
+    // exact_sketch_head).  head_n: rows [0, head_n) hold one — the sweep reads no f32 stage only when that covers the store
+    char* d_head = nullptr;
+    uint64_t head_n = 0;
     uint8_t* d_flag = nullptr;  // [cap] 1 = row norm is inf / NaN / > 1e18 / tiny but non-zero / underflowed (always re-scored exactly by the MFMA path)
     ott::PlaneSet planes;       // the cascade's compact copies of the corpus (owner store only: contexts reach them through `owner`)
     ott::CascadeState cascade;  // the batch cascade's back-off state (ott_policy.h), shared by the store's contexts: read through the owner
@@ -406,7 +414,7 @@ inline uint64_t store_rows(const ott_store* s) { return s->n + s->pend.count(); 
 int store_flush(ott_store* s);
 int store_flush_locked(ott_store* s);  // the caller holds `rw` exclusively and `mu`
 // ott_store.hip: a shard takes over freshly filled buffers (rows moved between the GPUs of a multi-GPU store)
-int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* sketch, uint32_t sketch_bits, uint64_t n, uint64_t cap);
+int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* sketch, uint32_t sketch_bits, char* head, uint64_t n, uint64_t cap);
 
 constexpr size_t OTT_MAX_WORKERS = 15;
 ott_store* ctx_acquire(ott_store* s);  // returns s or a worker, with its `mu` held
@@ -546,6 +554,11 @@ struct ExactParams {
     uint32_t sk_pitch, sk_stage0, sk_bits;
     const uint64_t* prune_seed;
     const uint32_t* prune_sketch;
+    // the head form of the four-bit sketch (prune_head_codes != nullptr): 16 B of stage 0's codes and rho_all per row, indexed by row
+    // like `inv`; the launch then has its checkpoint in front of stage 0 whatever prune_stage says, and the query-side values are
+    // taken over the whole query
+    const uint32_t* prune_head_codes;
+    const float* prune_head_rho;
     unsigned long long* prune_tails;
     double prune_qt, prune_qn, prune_q1;
     // four bits per dim: the quantised query of the integer decode (ott_prune.h: PruneQuant) — the scale 2^e and its reciprocal, an

@@ -203,6 +203,7 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
         float* inv = nullptr;
         uint8_t* flag = nullptr;
         uint32_t* sketch = nullptr;
+        char* head = nullptr;  // the four-bit form's head: [16 cap codes | 4 cap rho_all]
         uint64_t cap = 0;
         bool changed = false;
     };
@@ -217,6 +218,12 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
         else sk_pitch = sh->sk_pitch, sk_bits = sh->sk_bits;
     }
     if (!sk_pitch) move_sk = false;
+    // ... and the heads of the four-bit lines with them, when every shard that holds rows has one for all of them
+    bool move_hd = move_sk && sk_bits == 4;
+    for (size_t g = 0; g < G && move_hd; g++) {
+        const ott_store* sh = m->shards[g];
+        if (store_rows(sh) && (!sh->d_head || sh->head_n < sh->n || sh->opt.exact_sketch_head == 0)) move_hd = false;
+    }
     // deleted rows: the live bits of rows that move travel through the host — read from every shard now, loaded into the shards
     // that took fresh buffers once they have adopted them (a relayout is a rare, heavy step: 1.25 MB per 10M rows does not show)
     std::vector<uint64_t> live_all;
@@ -245,6 +252,7 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
             if (fr[g].inv) (void)hipFree(fr[g].inv);
             if (fr[g].flag) (void)hipFree(fr[g].flag);
             if (fr[g].sketch) (void)hipFree(fr[g].sketch);
+            if (fr[g].head) (void)hipFree(fr[g].head);
         }
     };
     if (moves) {
@@ -267,6 +275,7 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
             if (e == hipSuccess) e = hipMalloc((void**)&fr[g].inv, cap * sizeof(float));
             if (e == hipSuccess) e = hipMalloc((void**)&fr[g].flag, cap);
             if (e == hipSuccess && move_sk) e = hipMalloc((void**)&fr[g].sketch, cap * (size_t)sk_pitch * 4);
+            if (e == hipSuccess && move_hd) e = hipMalloc((void**)&fr[g].head, cap * (size_t)20);
             if (e == hipSuccess && s->ld != s->dim && cap > cnt)  // padding columns of rows still to come must be zero
                 e = hipMemsetAsync(fr[g].rows + cnt * s->ld, 0, (cap - cnt) * s->ld * sizeof(float), s->stream);
             if (e != hipSuccess) {
@@ -291,6 +300,10 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
                 if (e == hipSuccess) e = hipMemcpyPeerAsync(fr[g].flag + d0, m->devs[g], src->d_flag + s0, m->devs[h], cnt, s->stream);
                 if (e == hipSuccess && move_sk)
                     e = hipMemcpyPeerAsync(fr[g].sketch + d0 * sk_pitch, m->devs[g], src->d_sketch + s0 * sk_pitch, m->devs[h], cnt * (size_t)sk_pitch * 4, s->stream);
+                if (e == hipSuccess && move_hd)
+                    e = hipMemcpyPeerAsync(fr[g].head + d0 * 16, m->devs[g], src->d_head + s0 * 16, m->devs[h], cnt * (size_t)16, s->stream);
+                if (e == hipSuccess && move_hd)
+                    e = hipMemcpyPeerAsync(fr[g].head + fr[g].cap * 16 + d0 * 4, m->devs[g], src->d_head + src->cap * 16 + s0 * 4, m->devs[h], cnt * (size_t)4, s->stream);
                 if (e != hipSuccess) {
                     (void)hipGetLastError();
                     for (size_t x = 0; x < G; x++) {
@@ -309,8 +322,9 @@ int relayout(ott_store* ms, const std::vector<uint64_t>& target, uint64_t plan_r
         // phase C: the shards take the fresh buffers over (the old ones are freed)
         for (size_t g = 0; g < G; g++) {
             if (!fr[g].changed) continue;
-            const int rc = store_adopt(m->shards[g], fr[g].rows, fr[g].inv, fr[g].flag, fr[g].sketch, sk_bits, new_r[g].hi - new_r[g].lo, fr[g].cap);
+            const int rc = store_adopt(m->shards[g], fr[g].rows, fr[g].inv, fr[g].flag, fr[g].sketch, sk_bits, fr[g].head, new_r[g].hi - new_r[g].lo, fr[g].cap);
             fr[g].sketch = nullptr;
+            fr[g].head = nullptr;
             fr[g].rows = nullptr;
             fr[g].inv = nullptr;
             fr[g].flag = nullptr;

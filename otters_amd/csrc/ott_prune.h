@@ -306,6 +306,39 @@ OTT_PRUNE_HD inline void prune_sketchb_row(const float* v, uint32_t dim, uint32_
     line[1] = prune_f2u(rho);
 }
 
+// ---- the head of the four-bit form ("no f32 stage in front") ------------------------------------------------------
+// A companion record per row beside its four-bit line, so that a gated row reads no f32 stage at all: the four words of STAGE 0's
+// codes, in the layout of a line piece (eight fields per word, code 0 past `dim`), made with the line's own cell width — a value
+// beyond the tail's +-max clamps — and rho_all >= ||v - a kappa|| over ALL stages, for the a and the codes that are stored: the
+// line's three double sums carried on over stage 0's dims (the tail's dims first, in order, then stage 0's) and finished by
+// prune_sketchb_finish with the line's a.  A non-finite value anywhere in the row, or a line without a bound (rho = +inf): rho_all =
+// +inf.  The line itself is not touched.  With it the sweep calls prune_score_bound_sketchq with m = 0: an all-zero acc, rho_all,
+// K over every stage, qt = qn, and qe1 and the integer sum of the whole query (prune_query_quant with m = 0).
+// Host restatement of what tail_sketch_kernel<4> writes (ott_store.hip).  v: the row, nst: its stages, line: its four-bit line
+// (prune_sketchb_row with first = 32, nst - 1 stages).
+OTT_PRUNE_HD inline void prune_sketch4_head_row(const float* v, uint32_t dim, uint32_t nst, const uint32_t* line, uint32_t codes[4], float* rho_all) {
+    const uint32_t first = 32;
+    float vmax = 0.0f, inv_delta = 0.0f, a_in = 0.0f;
+    for (uint32_t i = first; i < dim; i++) {
+        const float x = prune_u2f(prune_f2u(v[i]) & 0x7FFFFFFFu);
+        if (x > vmax && x <= 3.4028234e38f) vmax = x;
+    }
+    prune_sketchb_scale(vmax, 4, &inv_delta, &a_in);
+    PruneSketchSumsB t;
+    for (uint32_t i = first; i < dim && i < 32 * nst; i++)  // (the codes that are stored: the kernel's own, or a line of the caller's choosing)
+        prune_sketchb_add(t, prune_f2u(v[i]), 2 * prune_sketchb_code(line + prune_sketchb_word0(4) + 4 * ((i - first) >> 5), i & 31u, 4) + 1);
+    codes[0] = codes[1] = codes[2] = codes[3] = 0u;
+    for (uint32_t i = 0; i < first && i < dim; i++) {
+        const int32_t code = prune_sketchb_quant(v[i], inv_delta, 4);
+        codes[i >> 3] |= ((uint32_t)code & 15u) << (4 * (i & 7u));
+        prune_sketchb_add(t, prune_f2u(v[i]), 2 * code + 1);
+    }
+    const float a = prune_u2f(line[0]), rho = prune_u2f(line[1]);
+    float a2, r = prune_u2f(0x7F800000u);
+    if (rho <= 3.4028234e38f) prune_sketchb_finish(t, a, &a2, &r);
+    *rho_all = r;
+}
+
 // ---- the quantised query of the four-bit form ("the integer decode") --------------------------------------------
 // The four-bit line stores eight two's-complement codes per word: one operand of a signed 4-bit dot product.  The query's other
 // operand: q_i = 2^e qhat_i + e_i with integers |qhat_i| <= 1911 = 7 * 273, split into balanced base-16 digits qhat = 256 d2 + 16 d1

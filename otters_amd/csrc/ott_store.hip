@@ -28,12 +28,12 @@ struct OptName {
     const char* name;
     int kind;  // 0 = bool, 1 = tri-state (-1 automatic / 0 / 1), 2 = non-negative int
 };
-// the twenty-one options of the product library (see struct Options) ...
+// the twenty-two options of the product library (see struct Options) ...
 const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"hi_prebuild", 1},          {"stage_appends", 1},       {"multi_transport", 2},
                              {"multi_rebalance", 0}, {"multi_min_shard_rows", 2}, {"exact_small", 1},     {"large_k_from", 2},        {"small_sort", 1},
                              {"mfma_f32", 0},        {"no_hi_pass", 0},      {"no_batch_image", 0},       {"force_fallback", 2},      {"eps_scale_ppm", 2},
                              {"multi_fake_distinct", 0}, {"exact_prune", 1},            {"exact_sketch", 1},
-                             {"id_gather", 1},       {"exact_sketch_bits", 2},   {"group_gather", 1},
+                             {"id_gather", 1},       {"exact_sketch_bits", 2},   {"group_gather", 1},         {"exact_sketch_head", 1},
 #ifdef OTT_MFMA_DEBUG_BUILD
                              // ... and, in the diagnostic build only, kernel tuning, timing ablations and every fallback bit by its own name
                              {"mfma_wg", 2},         {"mfma_growth", 2},     {"mfma_debug", 0},           {"mfma_abl", 2},            {"hi_tmin", 2},
@@ -41,11 +41,11 @@ const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"h
                              {"merge_rank1", 1},     {"maxsim_fold", 1},
 #endif
 };
-static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 21
+static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 22
 #ifdef OTT_MFMA_DEBUG_BUILD
                                                             + 12
 #endif
-              , "the product library's option table stays at twenty-one entries");
+              , "the product library's option table stays at twenty-two entries");
 }  // namespace
 
 int option_set(Options& o, const char* name, long long v) {
@@ -81,6 +81,7 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "exact_prune") return tri(o.exact_prune);
     if (n == "exact_sketch") return tri(o.exact_sketch);
     if (n == "exact_sketch_bits") { if (v != 1 && v != 3 && v != 4) return -1; o.exact_sketch_bits = (int)v; return 0; }
+    if (n == "exact_sketch_head") return tri(o.exact_sketch_head);
     if (n == "id_gather") return tri(o.id_gather);
     if (n == "group_gather") return tri(o.group_gather);
 #ifdef OTT_MFMA_DEBUG_BUILD
@@ -332,9 +333,13 @@ int update_min_pos_inv(ott_store* s, uint64_t first_row, uint64_t n_rows) {
 // and the sums after it (a rule that needs one walk, the width from the row norm, clips an eighth of the dims of Gaussian rows).
 // A lane writes its line in 16-B pieces: the groups of four code words as they fill, [a | rho | word 0 | word 1] at the end.
 // BITS = 4: a stage's four code words are one piece, written as the stage ends; [a | rho | 0 | 0] at the end.
+// BITS = 4 with a head (head_codes != nullptr; ott_prune.h: prune_sketch4_head_row): stage 0 is walked behind the last sketched
+// stage — its codes with the line's cell width into head_codes[4 row ..], its dims added to the line's sums, which then give
+// head_rho[row]; the line's own a and rho are taken before that and are what they are without a head.
 template <int BITS>
 __global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restrict__ rows, uint32_t ld, uint32_t dim, uint64_t first, uint64_t n,
-                                                           uint32_t stage0, uint32_t n_stages, uint32_t pitch, uint32_t* __restrict__ sketch) {
+                                                           uint32_t stage0, uint32_t n_stages, uint32_t pitch, uint32_t* __restrict__ sketch,
+                                                           uint32_t* __restrict__ head_codes, float* __restrict__ head_rho) {
     __shared__ __attribute__((aligned(16))) float smem[4 * 64 * NKC];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -399,11 +404,13 @@ __global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restric
         PruneSketchSumsB sums;
         uint32_t w01[2] = {0u, 0u};          // code words 0 and 1: they share the first 16 B with a and rho
         v4u grp = {0u, 0u, 0u, 0u};          // the 16-B piece that is filling (line words 4 g .. 4 g + 3)
+        float a = 0.0f, rho = 0.0f;          // the line's, taken behind its last stage
+        const uint32_t n_walk = n_stages + ((BITS == 4 && head_codes != nullptr) ? 1u : 0u);
         load_stage(stage0);
-        for (uint32_t j = 0; j < n_stages; j++) {
-            const uint32_t sg = stage0 + j;
+        for (uint32_t j = 0; j < n_walk; j++) {
+            const uint32_t sg = j < n_stages ? stage0 + j : 0u;  // (the head: stage 0 last)
             to_lds();
-            if (j + 1 < n_stages) load_stage(sg + 1);
+            if (j + 1 < n_walk) load_stage(j + 1 < n_stages ? sg + 1 : 0u);
             uint32_t w[BITS];
 #pragma unroll
             for (int b = 0; b < BITS; b++) w[b] = 0u;
@@ -427,7 +434,10 @@ __global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restric
             }
             wave_fence();
             if constexpr (BITS == 4) {  // piece 1 + j is this stage's four words
-                if (mine) line[1 + j] = v4u{w[0], w[1], w[2], w[3]};
+                if (mine) {
+                    if (j < n_stages) line[1 + j] = v4u{w[0], w[1], w[2], w[3]};
+                    else reinterpret_cast<v4u*>(head_codes)[row0 + lane] = v4u{w[0], w[1], w[2], w[3]};
+                }
             } else {
 #pragma unroll
             for (int b = 0; b < BITS; b++) {
@@ -447,13 +457,30 @@ __global__ __launch_bounds__(256) void tail_sketch_kernel(const float* __restric
                 }
             }
             }
+            if (j + 1 == n_stages) {
+                if constexpr (BITS == 1) a_in = prune_sketchb_mean(sums, dim > stage0 * NKC ? dim - stage0 * NKC : 0u);
+                prune_sketchb_finish(sums, a_in, &a, &rho);
+            }
         }
-        if constexpr (BITS == 1) a_in = prune_sketchb_mean(sums, dim > stage0 * NKC ? dim - stage0 * NKC : 0u);
-        float a, rho;
-        prune_sketchb_finish(sums, a_in, &a, &rho);
         if (mine) line[0] = v4u{__float_as_uint(a), __float_as_uint(rho), w01[0], w01[1]};
+        if (n_walk > n_stages) {  // rho_all: the sums over every stage, for the a that is stored
+            float a2, rho_all = __builtin_inff();
+            if (rho <= 3.4028234e38f) prune_sketchb_finish(sums, a, &a2, &rho_all);
+            if (mine) head_rho[row0 + lane] = rho_all;
+        }
     }
 }
+
+// the head of the four-bit form (ott_prune.h: prune_sketch4_head_row): kept wherever the store keeps four-bit lines, unless the option says never
+static bool store_wants_head(const ott_store* s) { return s->d_sketch != nullptr && s->sk_bits == 4 && s->opt.exact_sketch_head != 0; }
+static void head_drop(ott_store* s) {
+    if (s->d_head) (void)hipFree(s->d_head);
+    s->d_head = nullptr;
+    s->head_n = 0;
+}
+// codes at [0, 16 cap), rho_all behind them
+static uint32_t* head_codes(const ott_store* s) { return reinterpret_cast<uint32_t*>(s->d_head); }
+static float* head_rho(const ott_store* s) { return s->d_head ? reinterpret_cast<float*>(s->d_head + s->cap * (size_t)16) : nullptr; }
 
 bool store_wants_sketch(const ott_store* s) {
     const uint32_t nst = (s->ld + 31) / 32;
@@ -470,6 +497,7 @@ static int update_sketch(ott_store* s, uint64_t first_row, uint64_t n_rows) {
             OTT_HIP(hipStreamSynchronize(s->stream));
             (void)hipFree(s->d_sketch);
             s->d_sketch = nullptr;
+            head_drop(s);
         }
         s->sk_n = 0;
         return OTT_OK;
@@ -488,19 +516,35 @@ static int update_sketch(ott_store* s, uint64_t first_row, uint64_t n_rows) {
             return OTT_OK;
         }
     }
-    const uint64_t lo = first_row < s->sk_n ? first_row : s->sk_n, hi = first_row + n_rows;
+    // the head, made in the same launch: a store that wants one and has none yet (first line, the option switched back on, rows that
+    // arrived with lines alone) gets it for every row; no room for it: the store stays without one (the sweep reads stage 0 then)
+    if (!store_wants_head(s)) {
+        if (s->d_head) {
+            OTT_HIP(hipStreamSynchronize(s->stream));
+            head_drop(s);
+        }
+    } else if (!s->d_head) {
+        s->head_n = 0;
+        if (hipMalloc((void**)&s->d_head, s->cap * (size_t)20) != hipSuccess) {
+            (void)hipGetLastError();
+            s->d_head = nullptr;
+        }
+    }
+    const uint64_t have = s->d_head && s->head_n < s->sk_n ? s->head_n : s->sk_n;
+    const uint64_t lo = first_row < have ? first_row : have, hi = first_row + n_rows;
     const uint32_t blocks = grid_blocks((hi - lo + 63) / 64, 4, s->n_cu);  // a wave per 64 rows, as launch_inv_norms
     if (s->sk_bits == 4)
         hipLaunchKernelGGL(tail_sketch_kernel<4>, dim3(blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
-                           nst - s->sk_stage0, s->sk_pitch, s->d_sketch);
+                           nst - s->sk_stage0, s->sk_pitch, s->d_sketch, head_codes(s), head_rho(s));
     else if (s->sk_bits == 3)
         hipLaunchKernelGGL(tail_sketch_kernel<3>, dim3(blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
-                           nst - s->sk_stage0, s->sk_pitch, s->d_sketch);
+                           nst - s->sk_stage0, s->sk_pitch, s->d_sketch, nullptr, nullptr);
     else
         hipLaunchKernelGGL(tail_sketch_kernel<1>, dim3(blocks), dim3(256), 0, s->stream, s->d_rows, s->ld, s->dim, lo, hi - lo, s->sk_stage0,
-                           nst - s->sk_stage0, s->sk_pitch, s->d_sketch);
+                           nst - s->sk_stage0, s->sk_pitch, s->d_sketch, nullptr, nullptr);
     OTT_HIP(hipGetLastError());
     if (hi > s->sk_n) s->sk_n = hi;
+    if (s->d_head) s->head_n = s->sk_n;  // (lo <= head_n: every line this store has was made, or made again, with its head)
     return OTT_OK;
 }
 
@@ -534,20 +578,25 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
     uint8_t* nflag = nullptr;
     uint32_t* nsk = nullptr;  // the tail sign sketch is allocated, grown and copied exactly as the inverse norms are
     const bool keep_sk = s->d_sketch != nullptr && store_wants_sketch(s);
+    char* nhd = nullptr;  // ... and so is the head of the four-bit form, which goes wherever the lines go
+    const bool keep_hd = keep_sk && s->d_head != nullptr && store_wants_head(s);
     hipError_t e = hipSuccess;
     for (int attempt = 0; attempt < 2; attempt++) {
         e = hipMalloc((void**)&nrows, ncap * s->ld * sizeof(float));
         if (e == hipSuccess) e = hipMalloc((void**)&ninv, ncap * sizeof(float));
         if (e == hipSuccess) e = hipMalloc((void**)&nflag, ncap);
         if (e == hipSuccess && keep_sk) e = hipMalloc((void**)&nsk, ncap * (size_t)s->sk_pitch * 4);
+        if (e == hipSuccess && keep_hd) e = hipMalloc((void**)&nhd, ncap * (size_t)20);
         if (e == hipSuccess) break;
         if (nrows) (void)hipFree(nrows);
         if (ninv) (void)hipFree(ninv);
         if (nflag) (void)hipFree(nflag);
         if (nsk) (void)hipFree(nsk);
+        if (nhd) (void)hipFree(nhd);
         nrows = ninv = nullptr;
         nflag = nullptr;
         nsk = nullptr;
+        nhd = nullptr;
         (void)hipGetLastError();  // reported here: the store stays as it was, and the next launch check must not see this again
         // The store's own copies of the corpus for the batch path (int8 plane, 16-bit plane, split image) are dropped by a
         // reallocation anyway: when the new buffers do not fit NEXT TO them, they go first and the allocation is tried once more
@@ -585,6 +634,11 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
             const uint64_t have = s->sk_n < s->n ? s->sk_n : s->n;
             OTT_HIP(hipMemcpyAsync(nsk, s->d_sketch, have * (size_t)s->sk_pitch * 4, hipMemcpyDeviceToDevice, s->stream));
         }
+        if (nhd && s->head_n) {  // (the rho_all array sits behind the codes of `cap` rows: two pieces)
+            const uint64_t have = s->head_n < s->n ? s->head_n : s->n;
+            OTT_HIP(hipMemcpyAsync(nhd, s->d_head, have * (size_t)16, hipMemcpyDeviceToDevice, s->stream));
+            OTT_HIP(hipMemcpyAsync(nhd + ncap * (size_t)16, s->d_head + s->cap * (size_t)16, have * (size_t)4, hipMemcpyDeviceToDevice, s->stream));
+        }
     }
     if (s->ld != s->dim)  // padding columns must be zero
         OTT_HIP(hipMemsetAsync(nrows + s->n * s->ld, 0, (ncap - s->n) * s->ld * sizeof(float), s->stream));
@@ -593,14 +647,17 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
     if (s->d_inv) (void)hipFree(s->d_inv);
     if (s->d_flag) (void)hipFree(s->d_flag);
     if (s->d_sketch) (void)hipFree(s->d_sketch);
+    if (s->d_head) (void)hipFree(s->d_head);
     s->d_rows = nrows;
     s->d_inv = ninv;
     s->d_flag = nflag;
     s->d_sketch = nsk;
+    s->d_head = nhd;
     if (!nsk) s->sk_n = 0;
+    if (!nhd) s->head_n = 0;
     s->cap = ncap;
     planes_drop(s);  // rebuilt lazily at the new capacity
-    if (keep_sk && !nsk && s->n) {  // the lines did not move with the rows: made again, in the form they had
+    if (((keep_sk && !nsk) || (keep_hd && !nhd)) && s->n) {  // the lines, or their heads, did not move with the rows: made again, in the form they had
         const int want = s->opt.exact_sketch_bits;
         s->opt.exact_sketch_bits = (int)s->sk_bits;
         const int rc = update_sketch(s, 0, s->n);
@@ -613,7 +670,7 @@ static int realloc_store(ott_store* s, uint64_t ncap) {
 // A shard of a multi-GPU store takes over buffers the relayout filled (rows [0, n) valid, capacity `cap`): the old ones are
 // freed, the 16-bit copies of the corpus are dropped (rebuilt lazily), the hi plane's per-row marks are cleared, the smallest
 // inverse norm is measured again, the evaluated row mask is forgotten.  The caller holds the multi store exclusively.
-int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* sketch, uint32_t sketch_bits, uint64_t n, uint64_t cap) {
+int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* sketch, uint32_t sketch_bits, char* head, uint64_t n, uint64_t cap) {
     // the shard's own lock too: its background plane builder reads the rows under it (shared) and must be out before they go
     ott::host::ExclusiveLock wr(s->rw);
     std::lock_guard<std::mutex> g(s->mu);
@@ -623,6 +680,7 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
     if (s->d_inv) (void)hipFree(s->d_inv);
     if (s->d_flag) (void)hipFree(s->d_flag);
     if (s->d_sketch) (void)hipFree(s->d_sketch);
+    head_drop(s);
     live_drop(s);  // (the rows are other rows now: whoever moved them loads their live bits afterwards, live_load)
     group_drop(s); // (a store with group ids moves no rows: nothing to drop unless a caller forced the move)
     s->d_rows = rows;
@@ -637,6 +695,8 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
         s->sk_pitch = prune_sketch_pitch(s->sk_words);
     }
     s->sk_n = sketch ? n : 0;
+    s->d_head = head;  // (nullptr: lines without heads — the next append makes the head, and the lines again, for the whole shard)
+    s->head_n = head ? n : 0;
     s->n = n;
     s->cap = cap;
     planes_drop(s);
@@ -660,6 +720,7 @@ int store_after_compact(ott_store* s, uint64_t new_n) {
     planes_drop(s);
     s->evalmask_bits = 0;
     s->sk_n = 0;
+    s->head_n = 0;
     s->min_pos_inv = __builtin_inff();
     if (!new_n) return OTT_OK;
     int rc = planes_clear_marks(s, new_n);
@@ -754,6 +815,8 @@ static void alias_corpus(ott_store* w, const ott_store* s) {
     w->d_inv = s->d_inv;
     w->d_flag = s->d_flag;
     w->d_sketch = s->d_sketch;
+    w->d_head = s->d_head;
+    w->head_n = s->head_n;
     w->sk_n = s->sk_n;
     w->sk_words = s->sk_words;
     w->sk_bits = s->sk_bits;
@@ -857,6 +920,7 @@ int ott_store_destroy(ott_store* s) {
         s->d_inv = nullptr;
         s->d_flag = nullptr;
         s->d_sketch = nullptr;
+        s->d_head = nullptr;
         s->d_evalmask.p = nullptr;
         s->d_evalmask.cap = 0;
         s->d_live = nullptr;
@@ -870,6 +934,7 @@ int ott_store_destroy(ott_store* s) {
     if (s->d_inv) (void)hipFree(s->d_inv);
     if (s->d_flag) (void)hipFree(s->d_flag);
     if (s->d_sketch) (void)hipFree(s->d_sketch);
+    if (s->d_head) (void)hipFree(s->d_head);
     planes_release(s);  // (a worker has none of its own)
     for (ott::DevBuf* b : {&s->d_queries, &s->d_qinv, &s->d_rowmask, &s->d_runs, &s->d_prefix, &s->d_lists, &s->d_lists2, &s->d_hits,
                            &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_gather, &s->d_mmr, &s->d_gtable, &s->d_gctl, &s->d_mstable, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,

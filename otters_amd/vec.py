@@ -871,7 +871,7 @@ class VecStore:
         return bool(self._n) and bool(N.lib().ott_store_batch_ready(self._handle()))
 
     def set_option(self, name: str, value: int) -> None:
-        """Behaviour switch of this store (ott_store_set_option; the twenty-one names are listed in include/otters_hip.h:
+        """Behaviour switch of this store (ott_store_set_option; the twenty-two names are listed in include/otters_hip.h:
         "tie_order", "hi_fmt", "hi_prebuild", ..., "force_fallback").  Results never depend on any but "tie_order"."""
         self._options[name] = int(value)
         if self._h is not None:
