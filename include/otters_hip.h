@@ -418,6 +418,45 @@ int ott_query_mmr(ott_store* s, const ott_query_desc* d, const uint64_t* ids, ui
                   uint64_t fetch_k, float lambda, ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query,
                   float* out_values /* may be NULL; cap floats */, ott_stats* stats);
 
+/* Recommend by example rows (an extension; Qdrant's recommend with the best_score strategy): "more like these rows, less like
+ * those".  The examples are rows of the store, named by id counted from the store's first row like ott_query_ids' (not shifted by
+ * base_offset); duplicates inside one list count once; a deleted row may be an example (stored data is read, as in
+ * ott_store_score_rows).  d carries metric, take, filter, k, chunk_mask, row_mask / use_device_row_mask and path; d->queries must be
+ * NULL, d->nq 0 and d->mode MERGED.
+ * PAIR SCORE: P[e][r] is ott_query_mmr's — example e's STORED row as the query and row r as the row, the exact path's bits in the
+ * store's reduce order; cosine is (dot * inv[e]) * inv[r] with the store's inverse norms.  All four metrics.
+ * BEST SCORES: ord(x) = the library's 32-bit ordinal of x under d->take (larger is better; the total order, +0.0 above -0.0 under
+ * Max).  bp(r) = the largest ord(P[p][r]) over the positives p whose pair score is not NaN, bn(r) the same over the negatives, 0 =
+ * none; BP and BN are the scores those ordinals decode to.
+ * CANDIDATES: rows that survive chunk_mask, the caller's row mask or the evaluated device mask and the live mask of deleted rows,
+ * are not themselves an example (positive or negative), have bp != 0, and whose BP passes the score filter (the filter always acts
+ * on BP, on both sides).
+ * SIDES: positive (side_of_hit = 1) when bn == 0 or bp > bn; negative (side_of_hit = 0) when bp <= bn — a comparison of ordinals: a
+ * row as close to a negative as to its best positive is on the negative side.
+ * ORDER: first every positive-side candidate by bp descending, then the lower row; then, only with OTT_RECOMMEND_FILL, the
+ * negative-side candidates by bn ASCENDING (the row least like its nearest negative first), then the lower row; cut at
+ * k_eff = min(k, ott_store_len).  Always this canonical order, whatever option "tie_order" says.
+ * OUTPUT: one ott_hit per pick — index = base_offset + row, score = BP on the positive side and BN on the negative side, query = 0;
+ * side_of_hit[i], if given, the side of hit i.  cap >= k_eff.  With one positive and no negative the hits are the plain top-k of
+ * that stored row used as a query with the row itself masked out; with no negatives the flag has no effect.
+ * One streaming sweep scores four examples per pass (one pass for a single example, else ceil(examples / 4)) and keeps every row's
+ * {bp, bn} in an 8-byte state (scratch of the query context, [rows] x 8 B); a keys kernel and grouped search's top-k give the
+ * positive side, and a second keys kernel and top-k the negative side — only when the flag is set, negatives exist and the positive
+ * side returned fewer than k_eff (one more host wait in that case alone).  The examples' rows are gathered on the device.
+ * stats: path_used = EXACT, passes, vectors_compared = rows scored x examples, bytes_scanned per pass, score_ns / merge_ns as
+ * ott_query_maxsim counts them (the first round's).
+ * Refused on the host before any device work, with nothing written: n_positive == 0, more than OTT_RECOMMEND_MAX_EXAMPLES distinct
+ * examples, a list pointer NULL with a count above 0, an id >= ott_store_len, a row listed as both positive and negative, unknown
+ * flag bits, d->nq != 0 or d->queries != NULL, cap < k_eff, out == NULL with cap > 0 (OTT_ERR_INVALID); OTT_MODE_PER_QUERY,
+ * OTT_PATH_MFMA (AUTO takes the sweep and never builds, extends or waits for a plane), a multi-GPU store (the examples' rows lie on
+ * different shards), a store of more than 2^32 - 16 rows (OTT_ERR_UNSUPPORTED).  Takes the store shared, like ott_query (staged
+ * appends go first). */
+#define OTT_RECOMMEND_MAX_EXAMPLES 64
+#define OTT_RECOMMEND_FILL 1u /* flags bit 0 */
+int ott_query_recommend(ott_store* s, const ott_query_desc* d, const uint64_t* positive, uint64_t n_positive, const uint64_t* negative,
+                        uint64_t n_negative, uint32_t flags, ott_hit* out, uint64_t cap, uint64_t* n_out,
+                        uint32_t* side_of_hit /* may be NULL; cap entries */, ott_stats* stats);
+
 /* Grouped search (an extension; Elasticsearch field collapse, Qdrant search_groups, Milvus group_by_field): one best hit per group,
  * top-k over the groups — top-10 DOCUMENTS of a store of chunks.  A store may carry one dense group id per row (uint32, < n_groups,
  * resident in HBM at 4 B per row).  ott_query_groups returns exactly the hits — index, score bits, order, per-query counts — of the

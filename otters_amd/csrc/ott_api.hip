@@ -51,7 +51,8 @@ int upload_exact_inputs(ott_store* s, const float* queries, uint32_t nq, const R
     char* hs = (char*)s->h_stage.p;
     float* hq = (float*)(hs + off_q);
     memset(hq, 0, q_bytes + qi_bytes);
-    for (uint32_t i = 0; i < nq; i++) {
+    // (queries == nullptr: the block goes up zeroed and a kernel fills it from stored rows, ott_recommend.hip)
+    for (uint32_t i = 0; queries != nullptr && i < nq; i++) {
         memcpy(hq + (size_t)i * s->dimq, queries + (size_t)i * s->dim, (size_t)s->dim * 4);
         ((float*)(hs + off_qi))[i] = host_inv_norm_exact(queries + (size_t)i * s->dim, s->dim);
     }

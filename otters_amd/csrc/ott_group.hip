@@ -229,9 +229,14 @@ int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* o
 // workgroup of four waves per four tiles, at most SW_BLOCKS_PER_CU per CU: from 4 x SW_BLOCKS_PER_CU x n_cu tiles (2048 tiles =
 // 131072 rows on 256 CUs) a wave takes a second tile — or 0: no row survives the chunk mask, `st` is complete and nothing was uploaded.
 int sweep_prologue(ott_store* s, const ott_query_desc* d, ott_stats* st, SweepParams* p, uint32_t* grid) {
+    return sweep_prologue(s, d, d->queries, d->nq, st, p, grid);
+}
+
+// ... with the query block named apart from the descriptor: `queries` nullptr = nq zeroed slots that a kernel of the caller's fills
+// from stored rows before the sweep reads them (ott_recommend.hip)
+int sweep_prologue(ott_store* s, const ott_query_desc* d, const float* queries, uint32_t nq, ott_stats* st, SweepParams* p, uint32_t* grid) {
     int rc;
     memset(st, 0, sizeof(*st));
-    const uint32_t nq = d->nq;
     RunPlan pl;
     make_run_plan(s, d->chunk_mask, pl);
     st->path_used = OTT_PATH_EXACT;
@@ -243,7 +248,7 @@ int sweep_prologue(ott_store* s, const ott_query_desc* d, ott_stats* st, SweepPa
     if (pl.rows_scored == 0) return OTT_OK;
     if ((rc = compose_row_mask(s, d, &p->row_mask, &p->row_mask_bits))) return rc;
     const std::vector<uint32_t> prefix = tile_prefix(pl, 64);
-    if ((rc = upload_exact_inputs(s, d->queries, nq, pl, prefix))) return rc;
+    if ((rc = upload_exact_inputs(s, queries, nq, pl, prefix))) return rc;
     st->passes = nq == 1 ? 1u : (nq + SW_NQ - 1) / SW_NQ;
     st->bytes_scanned = (uint64_t)st->passes * pl.rows_scored * ((uint64_t)s->dim * 4 + 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));  // (+ 4: the group id)
     p->rows = s->d_rows;

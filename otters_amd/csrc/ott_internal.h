@@ -20,6 +20,7 @@
 #include "ott_mfma_plan.h"  // the batch path's host-side plan (tile geometry, candidate budget, error bound, query norms, query block): HIP-free, CPU-tested
 #include "ott_maxsim_gather_plan.h"  // listed MaxSim's host-side plan (tokens per pass, slot arrays, table sizes, route, the 2 GiB refusal): HIP-free, CPU-tested
 #include "ott_exact_plan.h"  // the exact path's host-side plan (lists or sort, list width, kernel variant, passes and grid, lean, pruned sweep, result block): HIP-free, CPU-tested
+#include "ott_recommend_plan.h"  // recommend-by-example's host-side plan (refusals, example layout, passes, k_eff, the second round, scratch bytes): HIP-free, CPU-tested
 #include "ott_mmr_plan.h"  // MMR re-ranking's host-side plan (refusals, scratch layout, the pair grid, the greedy launch): HIP-free, CPU-tested
 #include "ott_sort_plan.h"  // the sort path's host-side plan (pass plans, sweep shape, rank or radix, prefix, slices, group extents, copy pieces): HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
@@ -322,6 +323,13 @@ struct ott_store {
     // MMR re-ranking (ott_mmr.hip), THIS context's scratch, allocated by the first ott_query_mmr that runs on it:
     // [candidate rows | relevances | counts | picks | values | the pair scores] (ott_mmr_plan.h: MmrLayout)
     ott::DevBuf d_mmr;
+    // Recommend by example (ott_recommend.hip), THIS context's scratch: the rows' best ordinals {bp, bn}, [n] x 8 B,
+    // 0 = none; zeroed when it is (re)allocated or after a failed query and left zeroed by the kernel that reads it last
+    // (rectable_clean) — or, where a second round could have run and did not, by a memset behind the first round: the flag is then
+    // set without draining the stream, because the context's one stream orders the memset before the next query's sweep.  The rows'
+    // 8-byte keys go through d_gtable, under its own protocol
+    ott::DevBuf d_rectable;
+    bool rectable_clean = false;
     // Grouped search (ott_group.hip).  d_gid: one dense group id per row slot, [cap] words, allocated by
     // ott_store_set_groups and freed by ott_store_clear_groups; nullptr = no groups (and nothing else below exists).  gid_n: the
     // rows the ids cover (a query needs gid_n == n).  Owned by the store (workers alias it), changed only under `rw` exclusive; a
@@ -736,6 +744,7 @@ int ensure_group_pairs(ott_store* s, uint64_t cap);  // the pair arrays for up t
 // finds it.  check_group_ids: the ids are set and cover the store, for entry point `fn`, before and under the lock.
 struct SweepParams;
 int sweep_prologue(ott_store* s, const ott_query_desc* d, ott_stats* st, SweepParams* p, uint32_t* grid);
+int sweep_prologue(ott_store* s, const ott_query_desc* d, const float* queries, uint32_t nq, ott_stats* st, SweepParams* p, uint32_t* grid);  // queries: nullptr = nq zeroed slots
 int ensure_zeroed(ott_store* s, DevBuf& b, bool& clean, size_t bytes);
 int check_group_ids(const ott_store* s, const char* fn, bool locked);
 // The top-k over a table of [queries of a pass][n_groups] 8-byte keys in d_gtable (0 = empty): prepare, pass() after every sweep

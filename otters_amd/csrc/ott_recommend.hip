@@ -1,0 +1,306 @@
+// ott_recommend.hip — recommend by example rows (Qdrant's recommend with the best_score strategy):
+// ott_query_recommend ranks the store's rows by their best score against the POSITIVE example rows, and keeps the rows that are
+// closer to a NEGATIVE example than to every positive one for the end of the list, or out of it.  The examples are rows of the
+// store, named by id: nothing of them crosses the host.
+//
+//   recommend_gather_kernel  the examples' stored rows into the context's query block (upload_exact_inputs' layout: zero padded to
+//                            dimq, the slots past the last example zero) and their STORED inverse norms into the qinv slots: the
+//                            pair score P[e][r] is ott_query_mmr's, the example's row plays the query.
+//   recommend_sweep_kernel   sweep_tiles (ott_sweep_dev.h: the streaming tile loop of the grouped sweeps, examples in the place of
+//                            queries: the bits are the oracle's) and this epilogue per row: the pass's up to four ordinals
+//                            o = ord_of(score, take) — 0 for a NaN score, a padding slot or a masked row — are reduced in registers
+//                            into a positive and a negative maximum (slot q0 + q is positive iff it lies below first_neg) and folded
+//                            into the row's 8-byte state {bp, bn}: a plain load, max and a streaming vector store.  A row belongs to one lane of a pass
+//                            and the passes are launches on one stream, so nothing is atomic; the first pass finds the table zero
+//                            and does not load.  A row no lane ever wrote (masked, deleted, pruned chunk) keeps {0, 0}.
+//   recommend_clear_kernel   the examples' own slots back to {0, 0}: an example is never a candidate.
+//   recommend_keys_kernel    one lane per row, side 1 or 0: candidate (bp != 0, the filter holds for BP) on that side ->
+//                            key = ordinal << 32 | ~row in the context's key table, else nothing (the table is zero when found).
+//                            Side 1 (bn == 0 or bp > bn): ordinal bp.  Side 0 (bp <= bn): ord_of(BN, !take) = ~bn, so that the
+//                            top-k with the FLIPPED take ranks ascending bn and decodes BN.  The kernel that reads the state last
+//                            zeroes it (`last`).
+//
+// The key table has the shape grouped search takes its top-k from with one "group" per row: the rest is ott_group.hip's GroupTopK
+// (index_is_group = false: a hit's index is base_offset + row).  Side 0 is a second keys kernel and a second GroupTopK, run only
+// when OTT_RECOMMEND_FILL is set, negatives exist and side 1 returned fewer than k_eff: one more host wait in that case alone.
+// When that round can run but does not, the state table is cleared by a memset behind the first round.
+// Examples per pass: ott_sweep_dev.h; the epilogue adds two ordinals (profiles/recommend/resource_usage.txt: no scratch).
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "ott_internal.h"
+#include "ott_sweep_dev.h"
+
+namespace ott {
+
+static_assert(REC_NQ == SW_NQ, "ott_recommend_plan.h counts the passes of ott_sweep_dev.h's sweep");
+
+struct RecommendParams : SweepParams {
+    uint2* state;        // [n] {bp, bn}; 0 = none
+    uint32_t first_neg;  // slots below it are positives
+};
+
+struct RecommendGatherParams {
+    const float* rows;
+    const float* inv;
+    float* queries;  // [slots * dimq]
+    float* qinv;     // [slots]
+    uint2* state;    // recommend_clear_kernel
+    uint32_t ld, dim, dimq, n;
+    uint32_t ex[REC_MAX_EXAMPLES];  // the examples' rows, every one below the store's length (checked on the host)
+};
+
+// blockIdx.x = example.  Every float of the slot's dimq is written: the row's dim, then zeros.
+__global__ __launch_bounds__(256) void recommend_gather_kernel(RecommendGatherParams p) {
+    const uint32_t e = blockIdx.x;
+    if (e >= p.n) return;
+    const float* src = p.rows + (uint64_t)p.ex[e] * p.ld;
+    float* dst = p.queries + (size_t)e * p.dimq;
+    for (uint32_t i = threadIdx.x; i < p.dimq; i += blockDim.x) dst[i] = i < p.dim ? src[i] : 0.0f;
+    if (threadIdx.x == 0) p.qinv[e] = p.inv[p.ex[e]];
+}
+
+__global__ __launch_bounds__(64) void recommend_clear_kernel(RecommendGatherParams p) {
+    if (threadIdx.x < p.n) p.state[p.ex[threadIdx.x]] = make_uint2(0u, 0u);
+}
+
+template <int MK, int NQ>
+__global__ __launch_bounds__(64 * SW_WAVES) void recommend_sweep_kernel(RecommendParams p) {
+    const bool take_max = p.take_max != 0;
+    sweep_tiles<MK, NQ>(p, [&](uint64_t my_row, bool valid, uint32_t, const float (&sc)[NQ], uint32_t nq_here) {
+        uint32_t bp = 0, bn = 0;
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            const float s = sc[q];
+            const uint32_t o = (valid && (uint32_t)q < nq_here && !(s != s)) ? ord_of(s, take_max) : 0u;  // NaN dropped: vec_compute.rs:237
+            if (p.q0 + (uint32_t)q < p.first_neg) bp = o > bp ? o : bp;
+            else bn = o > bn ? o : bn;
+        }
+        if (valid && (bp | bn) != 0) {
+            uint2* slot = p.state + my_row;
+            if (p.q0 != 0) {  // (wave-uniform: the first pass finds the table zero)
+                const uint2 cur = *slot;
+                bp = cur.x > bp ? cur.x : bp;
+                bn = cur.y > bn ? cur.y : bn;
+            }
+            // streamed like the rows: nothing reads the slot again before the next launch (a plain store was measurably slower:
+            // profiles/recommend/README.md)
+            typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+            v2u v;
+            v.x = bp;
+            v.y = bn;
+            __builtin_nontemporal_store(v, reinterpret_cast<v2u*>(slot));
+        }
+    });
+}
+
+// One lane per row.  keys: [n] 8-byte keys, zero when the kernel starts (d_gtable's protocol): only candidates of `side` are written.
+__global__ __launch_bounds__(256) void recommend_keys_kernel(uint2* state, uint32_t n, uint32_t side, uint32_t take_max, uint32_t cmp, float thr, uint32_t last,
+                                                             unsigned long long* keys) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint2 st = state[r];
+    if ((st.x | st.y) == 0) return;
+    if (last) state[r] = make_uint2(0u, 0u);
+    const uint32_t bp = st.x, bn = st.y;
+    if (bp == 0 || !cmp_holds(score_of(bp, take_max != 0), cmp, thr)) return;  // the filter acts on BP, on both sides
+    const bool positive = bn == 0 || bp > bn;
+    if (positive != (side != 0)) return;
+    const uint32_t o = positive ? bp : ~bn;  // ~bn == ord_of(BN, !take): never 0, bn is the ordinal of a non-NaN
+    keys[r] = ((unsigned long long)o << 32) | (uint32_t)(~(uint32_t)r);
+}
+
+namespace {
+
+template <int MK>
+int launch_sweep_mk(ott_store* s, const RecommendParams& p, uint32_t nq_tile, uint32_t grid) {
+    if (nq_tile == 1) hipLaunchKernelGGL((recommend_sweep_kernel<MK, 1>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
+    else hipLaunchKernelGGL((recommend_sweep_kernel<MK, (int)SW_NQ>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+
+int launch_sweep(ott_store* s, const RecommendParams& p, uint32_t nq_tile, uint32_t grid) {
+    switch (metric_kind(p.metric)) {
+        case MK_L2: return launch_sweep_mk<MK_L2>(s, p, nq_tile, grid);
+        case MK_L1: return launch_sweep_mk<MK_L1>(s, p, nq_tile, grid);
+        default: return launch_sweep_mk<MK_DOT>(s, p, nq_tile, grid);
+    }
+}
+
+int launch_keys(ott_store* s, uint2* state, uint32_t n, uint32_t side, bool take_max, const ott_query_desc* d, bool last, unsigned long long* keys) {
+    hipLaunchKernelGGL(recommend_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s->stream, state, n, side, take_max ? 1u : 0u, (uint32_t)d->filter_cmp, d->filter_thr,
+                       last ? 1u : 0u, keys);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+
+const char* refusal_text(RecRefusal r) {
+    switch (r) {
+        case REC_NO_POSITIVE: return "ott_query_recommend: at least one positive example is needed";
+        case REC_NULL_LIST: return "ott_query_recommend: an example list is NULL";
+        case REC_BAD_FLAGS: return "ott_query_recommend: unknown flag bits";
+        case REC_HAS_QUERIES: return "ott_query_recommend: the examples are the queries; d->queries must be NULL and d->nq 0";
+        case REC_PER_QUERY: return "ott_query_recommend: the examples make ONE query; PER_QUERY is not served";
+        case REC_MFMA: return "ott_query_recommend: the MFMA path does not serve recommend queries; use path AUTO or EXACT";
+        case REC_MULTI_GPU: return "ott_query_recommend: a multi-GPU store is not served (the examples' rows lie on different shards)";
+        case REC_TOO_MANY_ROWS: return "ott_query_recommend: a store of more than 2^32 - 16 rows is not served";
+        case REC_TOO_MANY: return "ott_query_recommend: more than OTT_RECOMMEND_MAX_EXAMPLES (64) distinct examples";
+        case REC_SMALL_CAP: return "ott_query_recommend: output capacity is smaller than min(k, rows)";
+        case REC_NULL_OUT: return "ott_query_recommend: out is NULL";
+        default: return "";
+    }
+}
+
+int refuse(RecRefusal r, uint64_t id = 0, uint64_t len = 0) {
+    const int code = rec_refusal_is_invalid(r) ? OTT_ERR_INVALID : OTT_ERR_UNSUPPORTED;
+    if (r == REC_BAD_ID) return fail(code, "ott_query_recommend: example id " + std::to_string(id) + " is not below the store's length " + std::to_string(len));
+    if (r == REC_BOTH_SIDES) return fail(code, "ott_query_recommend: row " + std::to_string(id) + " is listed as both a positive and a negative example");
+    return fail(code, refusal_text(r));
+}
+
+// The query on a context whose `mu` the caller holds (and the owner's `rw`, shared).  k_eff = min(k, rows) >= 1; every example < s->n.
+int run_recommend(ott_store* s, const ott_query_desc* d, const RecExamples& ex, uint32_t flags, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint32_t* side_of_hit,
+                  ott_stats* stats_out) {
+    int rc;
+    OTT_HIP(use_device(s));
+    const uint64_t t0 = now_ns();
+    ott_stats st;
+    const uint32_t n = (uint32_t)s->n;
+    RecommendParams p{};
+    uint32_t grid = 0;
+    if ((rc = sweep_prologue(s, d, nullptr, ex.n, &st, &p, &grid))) return rc;
+    uint64_t n1 = 0, n0 = 0;
+    if (grid != 0) {
+        st.bytes_scanned = (uint64_t)st.passes * (st.vectors_compared / ex.n) * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));  // (no group id is read)
+        // the states are left zeroed by the keys kernel that reads them last (or the memset below), the keys by the select / compact kernel
+        if ((rc = ensure_zeroed(s, s->d_rectable, s->rectable_clean, rec_state_bytes(n)))) return rc;
+        if ((rc = ensure_zeroed(s, s->d_gtable, s->gtable_clean, rec_key_bytes(n)))) return rc;
+        unsigned long long* keys = (unsigned long long*)s->d_gtable.p;
+        p.gid = nullptr;  // (a store with groups has ids: this sweep does not read them)
+        p.state = (uint2*)s->d_rectable.p;
+        p.first_neg = ex.first_neg;
+        const bool take_max = p.take_max != 0;
+        const bool fill = rec_fill_possible(flags, ex);
+
+        RecommendGatherParams gp;
+        memset(&gp, 0, sizeof(gp));
+        gp.rows = s->d_rows;
+        gp.inv = s->d_inv;
+        gp.queries = (float*)s->d_queries.p;
+        gp.qinv = (float*)((char*)s->d_queries.p + s->in_off_qinv);
+        gp.state = p.state;
+        gp.ld = s->ld;
+        gp.dim = s->dim;
+        gp.dimq = s->dimq;
+        gp.n = ex.n;
+        memcpy(gp.ex, ex.rows, sizeof(uint32_t) * ex.n);
+
+        GroupTopK tk;
+        tk.n_groups = n;
+        tk.nq = 1;
+        tk.k = k_eff;
+        tk.take_max = take_max;
+        tk.also_clean = fill ? nullptr : &s->rectable_clean;
+        if ((rc = tk.prepare(s, nullptr))) return rc;
+        const bool timing = stats_out != nullptr;
+        hipLaunchKernelGGL(recommend_gather_kernel, dim3(ex.n), dim3(256), 0, s->stream, gp);
+        OTT_HIP(hipGetLastError());
+        if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
+        const uint32_t tile = rec_tile(ex.n);
+        for (uint32_t ps = 0; ps < st.passes; ps++) {
+            p.q0 = ps * tile;
+            if ((rc = launch_sweep(s, p, tile, grid))) return rc;
+        }
+        hipLaunchKernelGGL(recommend_clear_kernel, dim3(1), dim3(64), 0, s->stream, gp);
+        OTT_HIP(hipGetLastError());
+        if ((rc = launch_keys(s, p.state, n, 1u, take_max, d, !fill, keys))) return rc;
+        if ((rc = tk.pass(s, keys, 0, 1))) return rc;
+        if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
+        if ((rc = tk.finish(s, timing, out, &n1, nullptr))) return rc;
+        if (timing) read_exact_events(s, &st);
+        if (n1 > k_eff) return fail(OTT_ERR_HIP, "ott_query_recommend: the top-k returned more hits than k");
+        if (fill) {
+            const uint64_t k2 = rec_second_k(fill, k_eff, n1);
+            if (k2 != 0) {
+                // the negative side: ascending bn through the flipped take; this keys kernel reads the states last
+                if ((rc = ensure_zeroed(s, s->d_gtable, s->gtable_clean, rec_key_bytes(n)))) return rc;
+                GroupTopK t2;
+                t2.n_groups = n;
+                t2.nq = 1;
+                t2.k = k2;
+                t2.take_max = !take_max;
+                t2.also_clean = &s->rectable_clean;
+                if ((rc = t2.prepare(s, nullptr))) return rc;
+                if ((rc = launch_keys(s, p.state, n, 0u, take_max, d, true, keys))) return rc;
+                if ((rc = t2.pass(s, keys, 0, 1))) return rc;
+                if ((rc = t2.finish(s, false, out + n1, &n0, nullptr))) return rc;
+                if (n0 > k2) return fail(OTT_ERR_HIP, "ott_query_recommend: the second top-k returned more hits than it was asked for");
+            } else {
+                // no second round after all: nothing reads the states again
+                OTT_HIP(hipMemsetAsync(s->d_rectable.p, 0, rec_state_bytes(n), s->stream));
+                s->rectable_clean = true;  // (the stream orders the memset before the next query's sweep)
+            }
+        }
+    }
+    if (side_of_hit) {
+        for (uint64_t i = 0; i < n1; i++) side_of_hit[i] = 1u;
+        for (uint64_t i = 0; i < n0; i++) side_of_hit[n1 + i] = 0u;
+    }
+    if (n_out) *n_out = n1 + n0;
+    st.total_ns = now_ns() - t0;
+    if (stats_out) *stats_out = st;
+    return OTT_OK;
+}
+
+}  // namespace
+
+}  // namespace ott
+
+using namespace ott;
+
+extern "C" {
+
+int ott_query_recommend(ott_store* s, const ott_query_desc* d, const uint64_t* positive, uint64_t n_positive, const uint64_t* negative, uint64_t n_negative,
+                        uint32_t flags, ott_hit* out, uint64_t cap, uint64_t* n_out, uint32_t* side_of_hit, ott_stats* stats) {
+    // what the arguments and the descriptor alone decide comes first: these refusals need no store
+    if (!d) return fail(OTT_ERR_INVALID, "ott_query_recommend: desc is NULL");
+    RecRefusal why = rec_check_args(positive == nullptr, n_positive, negative == nullptr, n_negative, flags, d->nq != 0 || d->queries != nullptr,
+                                    d->mode == OTT_MODE_PER_QUERY, d->path == OTT_PATH_MFMA);
+    if (why != REC_OK) return refuse(why);
+    if (d->metric > OTT_METRIC_MANHATTAN) return fail(OTT_ERR_INVALID, "ott_query_recommend: unknown metric");
+    if (d->take > OTT_TAKE_MAX) return fail(OTT_ERR_INVALID, "ott_query_recommend: unknown take type");
+    if (d->filter_cmp > OTT_CMP_EQ) return fail(OTT_ERR_INVALID, "ott_query_recommend: unknown filter comparator");
+    if (d->mode > OTT_MODE_PER_QUERY) return fail(OTT_ERR_INVALID, "ott_query_recommend: unknown mode");
+    if (d->path > OTT_PATH_MFMA) return fail(OTT_ERR_INVALID, "ott_query_recommend: unknown path");
+    if (!s) return fail(OTT_ERR_INVALID, "ott_query_recommend: store is NULL");
+    const uint64_t len = ott_store_len(s);
+    if ((why = rec_check_store(s->multi != nullptr, len)) != REC_OK) return refuse(why);
+    if (d->use_device_row_mask && s->evalmask_bits == 0 && s->n)
+        return fail(OTT_ERR_INVALID, "ott_query_recommend: use_device_row_mask set but ott_store_eval_row_mask was not called");
+    RecExamples ex;
+    uint64_t bad = 0;
+    if ((why = rec_examples(positive, n_positive, negative, n_negative, len, &ex, &bad)) != REC_OK) return refuse(why, bad, len);
+    if ((why = rec_check_out(rec_k_eff(d->k, len), cap, out == nullptr)) != REC_OK) return refuse(why);
+    ott::host::SharedLock rd;  // the corpus cannot change while this query runs
+    int rc;
+    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
+    // what the checks above read without the lock is read again, and k_eff only here: appends (this call's own flush of rows another
+    // thread staged after `len` was read) or a compact may have come in between, so the store may be longer or shorter than `len`
+    if ((why = rec_check_store(false, s->n)) != REC_OK) return refuse(why);
+    for (uint32_t e = 0; e < ex.n; e++)
+        if (ex.rows[e] >= s->n) return refuse(REC_BAD_ID, ex.rows[e], s->n);
+    const uint64_t k_eff = rec_k_eff(d->k, s->n);
+    if ((why = rec_check_out(k_eff, cap, out == nullptr)) != REC_OK) return refuse(why);
+    if (n_out) *n_out = 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (k_eff == 0) return OTT_OK;
+    ott_store* ctx = ctx_acquire(s);
+    rc = run_recommend(ctx, d, ex, flags, k_eff, out, n_out, side_of_hit, stats);
+    ctx_release(ctx);
+    return rc;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // ott_sweep_dev.h — the streaming tile loop of the two sweeps over grouped rows: group_sweep_kernel (ott_group.hip) and
-// maxsim_sweep_kernel (ott_maxsim.hip).  exact_kernel's streaming geometry with every variant stripped: lane = row, 64-row tiles per
-// wave, 128-B stages through the swizzled LDS tile, queries through the constant address space, a persistent grid over the run lists
+// maxsim_sweep_kernel (ott_maxsim.hip), and of recommend_sweep_kernel (ott_recommend.hip), which reads no group ids.
+// exact_kernel's streaming geometry with every variant stripped: lane = row, 64-row tiles per wave, 128-B stages through the swizzled LDS tile, queries through the constant address space, a persistent grid over the run lists
 // of surviving chunks, the scoring terms of ott_exact_dev.h, so the bits are the oracle's.  A kernel is sweep_tiles plus its epilogue;
 // what guards the loop against reading past the allocation (lsl4, the clamp to the tile's last row) exists here and nowhere else.
 // exact_kernel and exact_rows8_kernel (ott_exact.hip) keep their own loop: it carries the prune checkpoints, the int8 and dump forms.
@@ -31,7 +31,7 @@ struct SweepParams {
     uint64_t row_mask_bits;
     const ott_run* runs;
     const uint32_t* tile_prefix;  // [n_runs + 1]
-    const uint32_t* gid;          // [n] dense group ids, every one < n_groups (checked on the host when they were set)
+    const uint32_t* gid;          // [n] dense group ids, every one < n_groups (checked on the host when they were set); nullptr = none are read
     uint32_t ld, dim, dimq;
     uint32_t n_runs, n_tiles;
     uint32_t q0, nq_total;
@@ -91,7 +91,7 @@ __device__ __forceinline__ void sweep_tiles(const SweepParams& p, Epilogue&& epi
         float vinv = 0.0f;
         uint32_t g = 0xFFFFFFFFu;
         if (valid) {
-            g = p.gid[my_row];
+            if (p.gid != nullptr) g = p.gid[my_row];  // (wave-uniform: a sweep over a store without groups, ott_recommend.hip, has no ids)
             if (p.metric == OTT_METRIC_COSINE) vinv = p.inv[my_row];
         }
         float acc[NQ][8];

@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import GROUP_SIZE_MAX, Cmp, Metric, Mode, Path, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type, mmr_args
+from .vec import GROUP_SIZE_MAX, Cmp, Metric, Mode, Path, RecommendPlan, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type, mmr_args
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -474,6 +474,11 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
     def query_batch(self, queries, metric: Metric) -> "MetaQueryPlan":  # src/meta.rs:574-576
         return MetaQueryPlan(self, [np.asarray(q, dtype=np.float32).ravel() for q in queries], metric)
 
+    def recommend(self, positive, negative=(), metric: Metric = Metric.Cosine) -> "MetaRecommendPlan":
+        """Recommend by example rows (VecStore.recommend; ott_query_recommend) with a meta_filter: `positive` and `negative` are row
+        ids of this store."""
+        return MetaRecommendPlan(self, positive, negative, metric)
+
     # -- zonemap prune: build_chunk_mask_for_plan, src/meta.rs:407-428 ----------------------------------
     def build_chunk_mask_for_plan(self, compiled: CompiledFilter) -> np.ndarray:
         n = self._n_chunks
@@ -874,3 +879,95 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         names = sorted(st._schema)  # src/meta.rs:723-724
         data = {name: st._columns[name].take(indices) for name in names}  # src/meta.rs:728-821
         return MetaQueryResults(names, data, indices, scores)
+
+
+class MetaRecommendPlan:
+    """Recommend by example rows over a MetaStore (MetaStore.recommend; VecStore.recommend's contract): meta_filter prunes chunks
+    by their zone maps and masks rows on the device, as for MetaQueryPlan.mmr; vec_filter acts on a row's best positive score.  An
+    example need not pass the filter: stored data is read.  Errors surface at collect()."""
+
+    def __init__(self, store: MetaStore, positive, negative, metric: Metric):
+        self.store = store
+        self.metric = Metric(metric)
+        self._meta_filter: Optional[CompiledFilter] = None
+        self.meta_error: Optional[str] = None
+        self._plan = RecommendPlan(store._store, positive, negative, metric)
+
+    def meta_filter(self, expr: Expr) -> "MetaRecommendPlan":
+        try:
+            self._meta_filter = expr.compile(self.store._schema)
+            self.meta_error = None
+        except ExprError as e:
+            self.meta_error = f"meta_filter compile error: {e}"
+        return self
+
+    def vec_filter(self, score: float, cmp: Cmp) -> "MetaRecommendPlan":
+        self._plan.filter(score, cmp)
+        return self
+
+    filter = vec_filter
+
+    def take(self, k: int) -> "MetaRecommendPlan":
+        self._plan.take(k)
+        return self
+
+    def take_min(self, k: int) -> "MetaRecommendPlan":
+        self._plan.take_min(k)
+        return self
+
+    def take_max(self, k: int) -> "MetaRecommendPlan":
+        self._plan.take_max(k)
+        return self
+
+    def with_row_mask(self, mask) -> "MetaRecommendPlan":
+        self._plan.with_row_mask(mask)
+        return self
+
+    def with_path(self, path: Path) -> "MetaRecommendPlan":
+        self._plan.with_path(path)
+        return self
+
+    def fill_negative_side(self, fill: bool = True) -> "MetaRecommendPlan":
+        self._plan.fill_negative_side(fill)
+        return self
+
+    def collect_arrays(self):
+        """(hits, sides), as RecommendPlan.collect_arrays returns them."""
+        if self.meta_error is not None:
+            raise OttersError(self.meta_error)
+        st = self.store
+        if st._store is None:
+            raise OttersError("recommend: the store holds no vectors, so no row can be an example")
+        rr = self._plan.resolve()
+        compiled = self._meta_filter
+        chunk_mask = st.build_chunk_mask_for_plan(compiled) if compiled is not None else None
+        if chunk_mask is not None and not chunk_mask.any():
+            return np.zeros(0, dtype=N.HIT_DTYPE), np.zeros(0, dtype=np.uint32)
+        with st._mask_lock:  # the device row mask is store-global state: built and read in one critical section (MetaQueryPlan.collect)
+            use_dev = False
+            if compiled is not None and not st.row_mask_is_all_true(compiled, chunk_mask):
+                if st._device_mask_ok(compiled):
+                    if rr.row_mask is not None:
+                        raise OttersError("recommend: with_row_mask cannot be combined with a meta_filter that needs a row mask of its own")
+                    st.build_row_mask_device(compiled)
+                    use_dev = True
+                else:
+                    host = st.build_row_mask_host(compiled)
+                    if rr.row_mask is not None:
+                        m = np.ones(host.size, bool)
+                        m[: min(rr.row_mask.size, host.size)] = rr.row_mask[: host.size]
+                        host &= m
+                    rr.row_mask = host
+            hits, sides, gstats = st._store._run_recommend(rr, chunk_mask=chunk_mask, use_device_row_mask=use_dev)
+        st._store.last_stats = gstats
+        return hits, sides
+
+    def collect(self):
+        """(MetaQueryResults, sides): the hits' rows materialised as MetaQueryPlan.collect does, and their sides as a list."""
+        hits, sides = self.collect_arrays()
+        st = self.store
+        indices = [int(i) for i in hits["index"]]
+        scores = [float(s) for s in hits["score"]]
+        names = sorted(st._schema)
+        data = {name: st._columns[name].take(indices) for name in names}
+        return MetaQueryResults(names, data, indices, scores), sides.tolist()

@@ -632,6 +632,135 @@ class MaxSimBatchPlan:
         return out
 
 
+RECOMMEND_MAX_EXAMPLES = 64  # include/otters_hip.h: OTT_RECOMMEND_MAX_EXAMPLES
+RECOMMEND_FILL = 1           # include/otters_hip.h: OTT_RECOMMEND_FILL
+
+
+def recommend_examples(positive, negative, n_rows: int):
+    """recommend()'s example lists checked as ott_query_recommend checks them, with its messages: (uint64 positives, uint64
+    negatives) as listed.  Pure host logic."""
+    pos, neg = as_row_ids(positive), as_row_ids(negative)
+    if pos.size == 0:
+        raise OttersError("ott_query_recommend: at least one positive example is needed")
+    # the library's walk (ott_recommend_plan.h: rec_examples), id by id, the positives first: the first fault it meets is the one named
+    seen_pos, seen = set(), set()
+    for ids, is_neg in ((pos, False), (neg, True)):
+        for i in ids.tolist():
+            if i >= n_rows:
+                raise OttersError(f"ott_query_recommend: example id {i} is not below the store's length {n_rows}")
+            if is_neg and i in seen_pos:
+                raise OttersError(f"ott_query_recommend: row {i} is listed as both a positive and a negative example")
+            if i in seen:
+                continue
+            if len(seen) == RECOMMEND_MAX_EXAMPLES:
+                raise OttersError("ott_query_recommend: more than OTT_RECOMMEND_MAX_EXAMPLES (64) distinct examples")
+            seen.add(i)
+        if not is_neg:
+            seen_pos = set(seen)
+    return pos, neg
+
+
+@dataclass
+class ResolvedRecommend:
+    """What RecommendPlan hands to ott_query_recommend once it is validated."""
+    positive: np.ndarray  # uint64[n_positive], as listed
+    negative: np.ndarray  # uint64[n_negative], as listed
+    metric: int
+    take: int
+    k: int
+    filter_cmp: int
+    filter_thr: float
+    row_mask: Optional[np.ndarray]
+    path: int
+    flags: int
+
+
+class RecommendPlan:
+    """Recommend by example rows (VecStore.recommend; ott_query_recommend, Qdrant's recommend with the best_score strategy): rank the
+    rows by their best score against the `positive` rows of the store; a row at least as close to a `negative` row as to its best
+    positive leaves the positive side and follows it — least like its nearest negative first — unless fill_negative_side(False).
+    Lazy like VecQueryPlan: errors surface at validate() / collect()."""
+
+    def __init__(self, store: "VecStore", positive, negative, metric: Metric):
+        self.vector_store = store
+        self.positive, self.negative = positive, negative
+        self.search_metric = Metric(metric)
+        self.filter_criteria: Optional[tuple] = None
+        self.take_type: Optional[TakeType] = None
+        self.take_count: Optional[int] = None
+        self.row_mask: Optional[np.ndarray] = None
+        self.path = Path.Auto
+        self.fill = True
+
+    def with_row_mask(self, mask) -> "RecommendPlan":
+        self.row_mask = np.asarray(mask, dtype=bool).ravel()
+        return self
+
+    def filter(self, score: float, cmp: Cmp) -> "RecommendPlan":
+        """The score filter acts on a row's best POSITIVE score, on both sides."""
+        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
+        return self
+
+    def _take_with_options(self, count: int, take_type: Optional[TakeType]) -> "RecommendPlan":
+        self.take_count = int(count)
+        if take_type is not None:
+            self.take_type = take_type
+        elif self.take_type is None:
+            self.take_type = infer_default_take_type(self.search_metric)
+        return self
+
+    def take(self, count: int) -> "RecommendPlan":
+        return self._take_with_options(count, None)
+
+    def take_min(self, count: int) -> "RecommendPlan":
+        return self._take_with_options(count, TakeType.Min)
+
+    def take_max(self, count: int) -> "RecommendPlan":
+        return self._take_with_options(count, TakeType.Max)
+
+    def with_path(self, path: Path) -> "RecommendPlan":
+        self.path = Path(path)
+        return self
+
+    def fill_negative_side(self, fill: bool = True) -> "RecommendPlan":
+        """True (default): when the positive side has fewer than take(k) rows, the negative-side rows follow it.  False: they never
+        come out."""
+        self.fill = bool(fill)
+        return self
+
+    def validate(self) -> None:
+        st = self.vector_store
+        recommend_examples(self.positive, self.negative, len(st))
+        if self.path == Path.Mfma:
+            raise OttersError("ott_query_recommend: the MFMA path does not serve recommend queries; use path AUTO or EXACT")
+        if st.devices is not None:
+            raise OttersError("ott_query_recommend: a multi-GPU store is not served (the examples' rows lie on different shards)")
+
+    def resolve(self) -> ResolvedRecommend:
+        """Validate and lower the plan.  Pure host logic, no GPU."""
+        self.validate()
+        pos, neg = recommend_examples(self.positive, self.negative, len(self.vector_store))
+        k = self.take_count if self.take_count is not None else len(self.vector_store)
+        take = self.take_type if self.take_type is not None else infer_default_take_type(self.search_metric)
+        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
+        return ResolvedRecommend(positive=pos, negative=neg, metric=int(self.search_metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft,
+                                 row_mask=self.row_mask, path=int(self.path), flags=RECOMMEND_FILL if self.fill else 0)
+
+    def collect_arrays(self):
+        """(hits, sides): `hits` a NumPy record array (`index` u64, `score` f32 — the best positive score on the positive side, the
+        best negative score on the negative side —, `query` = 0) in the call's order, `sides[i]` (u32) 1 = positive side, 0 =
+        negative side."""
+        store = self.vector_store
+        hits, sides, stats = store._run_recommend(self.resolve())
+        store.last_stats = stats
+        return hits, sides
+
+    def collect(self):
+        """(results, sides): one SearchResult(index, score) per hit, and the hits' sides as a list."""
+        hits, sides = self.collect_arrays()
+        return [SearchResult(i, s) for i, s in zip(hits["index"].tolist(), hits["score"].tolist())], sides.tolist()
+
+
 class VecStore:
     """src/vec.rs:338-412: row-major f32 vectors + per-row inverse norms, resident in HBM."""
 
@@ -1029,6 +1158,39 @@ class VecStore:
         stats = st.as_dict()
         stats["group_index_builds"] = int(N.lib().ott_store_group_index_builds(self._handle()))
         return hits, list(per), stats
+
+    def recommend(self, positive, negative=(), metric: Metric = Metric.Cosine) -> RecommendPlan:
+        """Recommend by example rows (ott_query_recommend): `positive` and `negative` are row ids counted from the store's first row
+        (not shifted by the base offset); .take(k).collect() returns the hits and their sides."""
+        return RecommendPlan(self, positive, negative, metric)
+
+    def _run_recommend(self, rr: ResolvedRecommend, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
+        """ott_query_recommend.  Returns (hits HIT_DTYPE array, sides uint32 array, stats dict)."""
+        cap = max(min(rr.k, self._n), 1)
+        out = np.empty(cap, dtype=N.HIT_DTYPE)
+        sides = np.empty(cap, dtype=np.uint32)
+        d = N.QueryDesc()
+        d.queries = None
+        d.nq = 0
+        d.metric, d.take, d.filter_cmp, d.filter_thr = rr.metric, rr.take, rr.filter_cmp, rr.filter_thr
+        d.mode, d.k, d.path = int(Mode.Merged), rr.k, rr.path
+        keep = []
+        if chunk_mask is not None:
+            cm = N.pack_bits(chunk_mask)
+            keep.append(cm)
+            d.chunk_mask = cm.ctypes.data
+        if use_device_row_mask:
+            d.use_device_row_mask = 1
+        elif rr.row_mask is not None and rr.row_mask.size:
+            rm = N.pack_bits(rr.row_mask)
+            keep.append(rm)
+            d.row_mask = rm.ctypes.data
+            d.row_mask_bits = int(rr.row_mask.size)
+        n_out = C.c_uint64(0)
+        st = N.Stats()
+        N.check(N.lib().ott_query_recommend(self._handle(), C.byref(d), N.ptr(rr.positive), rr.positive.size, N.ptr(rr.negative) if rr.negative.size else None,
+                                            rr.negative.size, rr.flags, N.ptr(out), cap, C.byref(n_out), N.ptr(sides), C.byref(st)))
+        return out[: n_out.value].copy(), sides[: n_out.value].copy(), st.as_dict()
 
     def score_rows(self, queries, metric: Metric, ids) -> np.ndarray:
         """float32[nq, n_ids]: the score of every query against every row of `ids` (ott_store_score_rows) -- the exact path's bits,
