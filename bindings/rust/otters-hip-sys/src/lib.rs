@@ -19,6 +19,8 @@ pub const OTT_GROUP_SIZE_MAX: u32 = 16; // ott_query_groups_top: the largest gro
 pub const OTT_MAXSIM_BATCH_MAX: u32 = 4096; // ott_query_maxsim_groups_batch: the largest n_queries
 pub const OTT_MMR_MAX_FETCH: u32 = 1024; // ott_query_mmr: the largest fetch_k
 pub const OTT_RECOMMEND_MAX_EXAMPLES: u32 = 64; // ott_query_recommend: the most distinct examples, positives and negatives together
+pub const OTT_DISCOVER_MAX_PAIRS: u32 = 32; // ott_query_discover: the most context pairs
+pub const OTT_NO_ROW: u64 = u64::MAX; // ott_query_discover: target_row when no stored row is the target
 pub const OTT_RECOMMEND_FILL: u32 = 1; // ott_query_recommend flags bit 0: the negative side follows the positive side
 
 // ott_status
@@ -188,6 +190,7 @@ extern "C" {
     pub fn ott_store_score_rows(s: *mut ott_store, queries: *const f32, nq: u32, metric: u32, ids: *const u64, n_ids: u64, out_scores: *mut f32) -> c_int;
     pub fn ott_query_mmr(s: *mut ott_store, d: *const ott_query_desc, ids: *const u64, n_ids: u64, fetch_k: u64, lambda: f32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, out_values: *mut f32, stats: *mut ott_stats) -> c_int; // ids: null, 0 = no id list; out_values: null or cap floats
     pub fn ott_query_recommend(s: *mut ott_store, d: *const ott_query_desc, positive: *const u64, n_positive: u64, negative: *const u64, n_negative: u64, flags: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, side_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // d.queries null, d.nq 0; side_of_hit: null or cap entries
+    pub fn ott_query_discover(s: *mut ott_store, d: *const ott_query_desc, target_row: u64, positive: *const u64, negative: *const u64, n_pairs: u64, min_wins: u32, flags: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, wins_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // target: d.queries with d.nq 1, or target_row, or neither (context search); wins_of_hit: null or cap entries
     pub fn ott_store_set_groups(s: *mut ott_store, gid_host: *const c_void, n: u64, n_groups: u32) -> c_int; // gid_host: n u32
     pub fn ott_store_clear_groups(s: *mut ott_store) -> c_int;
     pub fn ott_store_group_count(s: *const ott_store) -> u32;

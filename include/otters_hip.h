@@ -457,6 +457,49 @@ int ott_query_recommend(ott_store* s, const ott_query_desc* d, const uint64_t* p
                         uint64_t n_negative, uint32_t flags, ott_hit* out, uint64_t cap, uint64_t* n_out,
                         uint32_t* side_of_hit /* may be NULL; cap entries */, ott_stats* stats);
 
+/* Discovery and context search (an extension; Qdrant's Discovery API): rank the rows by CONTEXT PAIRS of stored rows, each a
+ * (positive, negative), and optionally by a TARGET.  Pair i is (positive[i], negative[i]), i < n_pairs, 1 <= n_pairs <=
+ * OTT_DISCOVER_MAX_PAIRS; ids are counted from the store's first row like ott_query_recommend's (not shifted by base_offset).  A row
+ * may occur in several pairs, on either side; nothing is deduplicated: slot 2i of the sweep is the positive and slot 2i + 1 the
+ * negative of pair i.  A deleted row may be an example.  positive[i] == negative[i] is refused.
+ * TARGET: a vector — d->queries with d->nq == 1: the target score T[r] is exactly ott_query's exact-path score of that vector, the
+ * host-side query norm included; a stored row — target_row != OTT_NO_ROW with d->nq == 0: T[r] is the pair score of that row; none —
+ * d->nq == 0 and target_row == OTT_NO_ROW: context search.  A vector together with a row is refused.
+ * PAIR SCORE: P[e][r] is ott_query_mmr's / ott_query_recommend's — example e's STORED row as the query, the exact path's bits in the
+ * store's reduce order; cosine is (dot * inv[e]) * inv[r] with the store's inverse norms.  All four metrics.
+ * WINS: ord(x) = the library's 32-bit ordinal of x under d->take.  Pair i is won by r iff ord(P[pos_i][r]) > ord(P[neg_i][r]);
+ * wins(r) = the number of pairs won, 0 .. n_pairs.
+ * LOSS: starts at +0.0f; for i = 0 .. n_pairs - 1 in that order: d = P[pos_i][r] - P[neg_i][r] under take Max, P[neg_i][r] -
+ * P[pos_i][r] under take Min (one f32 subtraction, round to nearest); t = (d < 0) ? d : 0.0f (a NaN d from inf - inf gives 0);
+ * loss = loss + t (one f32 addition).
+ * CANDIDATES: rows that survive chunk_mask, the caller's row mask or the evaluated device mask and the live mask of deleted rows,
+ * are no example and not the target row, have no NaN pair score, wins(r) >= min_wins, with a target a T[r] that is not NaN, and whose
+ * score — T[r] with a target, loss(r) without — passes the score filter.
+ * ORDER: with a target: wins descending, then ord(T[r]) descending, then the lower row.  Without: loss descending in the total order
+ * (take Max's ordinal of the loss, whatever d->take is), then the lower row.  Cut at k_eff = min(k, ott_store_len).  Always this
+ * canonical order, whatever option "tie_order" says.
+ * OUTPUT: ott_hit{index = base_offset + row, score = T[r] or loss(r), query = 0}; wins_of_hit[i], if given, the hit's wins.
+ * cap >= k_eff.
+ * One streaming sweep scores four slots — two whole pairs — per pass, passes = ceil((2 * n_pairs + T) / 4) with T = 1 with a target:
+ * the target rides in the last pass's free slots when n_pairs is odd and takes a pass of its own otherwise.  Every row keeps
+ * {wins, loss or target ordinal} in an 8-byte state (scratch of the query context, [rows] x 8 B, shared with ott_query_recommend).
+ * Without a target a keys kernel and grouped search's top-k finish.  With one, a count kernel makes the candidates per wins level, a
+ * select kernel derives the level L* the k_eff-th hit lies on, hands that level's rows to the top-k and lists the fewer than k_eff
+ * rows above it; the host sorts that list behind the one wait.  The examples' rows are gathered on the device.
+ * stats: path_used = EXACT, passes, vectors_compared = rows scored x (2 * n_pairs + T), bytes_scanned per pass as
+ * ott_query_recommend counts it, score_ns / merge_ns.
+ * Refused on the host before any device work, with nothing written: n_pairs == 0 or above OTT_DISCOVER_MAX_PAIRS, a NULL list, an
+ * id >= ott_store_len (the target row included), a pair with the same row on both sides, a vector target together with a target
+ * row, d->nq > 1 (or d->queries and d->nq that disagree), min_wins > n_pairs, nonzero flags, cap < k_eff, out == NULL with cap > 0
+ * (OTT_ERR_INVALID); OTT_MODE_PER_QUERY, OTT_PATH_MFMA (AUTO takes the sweep and never builds, extends or waits for a plane), a
+ * multi-GPU store, a store of more than 2^32 - 16 rows (OTT_ERR_UNSUPPORTED).  Takes the store shared, like ott_query (staged
+ * appends go first). */
+#define OTT_DISCOVER_MAX_PAIRS 32
+#define OTT_NO_ROW UINT64_MAX /* target_row: no stored row is the target */
+int ott_query_discover(ott_store* s, const ott_query_desc* d, uint64_t target_row, const uint64_t* positive, const uint64_t* negative,
+                       uint64_t n_pairs, uint32_t min_wins, uint32_t flags, ott_hit* out, uint64_t cap, uint64_t* n_out,
+                       uint32_t* wins_of_hit /* may be NULL; cap entries */, ott_stats* stats);
+
 /* Grouped search (an extension; Elasticsearch field collapse, Qdrant search_groups, Milvus group_by_field): one best hit per group,
  * top-k over the groups — top-10 DOCUMENTS of a store of chunks.  A store may carry one dense group id per row (uint32, < n_groups,
  * resident in HBM at 4 B per row).  ott_query_groups returns exactly the hits — index, score bits, order, per-query counts — of the

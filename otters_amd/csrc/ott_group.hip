@@ -317,6 +317,7 @@ int GroupTopK::finish(ott_store* s, bool timing, ott_hit* out, uint64_t* n_out, 
         if ((rc = launch_merge(s, (const Cand*)s->d_lists.p, n_lists, KS, (uint64_t)n_lists * KS, nq, (uint32_t)k, E, take_max, index_is_group ? 0 : s->base_offset,
                                (ott_hit*)((char*)mapped + cnt_pad), KS, (uint64_t*)mapped, 0)))
             return rc;
+        if (after_merge && (rc = after_merge(s, after_arg, (const ott_hit*)((const char*)mapped + cnt_pad), (const uint64_t*)mapped))) return rc;
         if (timing) OTT_HIP(hipEventRecord(s->ev[5], s->stream));
         OTT_HIP(hipStreamSynchronize(s->stream));
         s->gtable_clean = true;

@@ -20,6 +20,7 @@
 #include "ott_mfma_plan.h"  // the batch path's host-side plan (tile geometry, candidate budget, error bound, query norms, query block): HIP-free, CPU-tested
 #include "ott_maxsim_gather_plan.h"  // listed MaxSim's host-side plan (tokens per pass, slot arrays, table sizes, route, the 2 GiB refusal): HIP-free, CPU-tested
 #include "ott_exact_plan.h"  // the exact path's host-side plan (lists or sort, list width, kernel variant, passes and grid, lean, pruned sweep, result block): HIP-free, CPU-tested
+#include "ott_discover_plan.h"  // discovery / context search's host-side plan (refusals, slot layout, passes, k_eff, scratch bytes, the level cut): HIP-free, CPU-tested
 #include "ott_recommend_plan.h"  // recommend-by-example's host-side plan (refusals, example layout, passes, k_eff, the second round, scratch bytes): HIP-free, CPU-tested
 #include "ott_mmr_plan.h"  // MMR re-ranking's host-side plan (refusals, scratch layout, the pair grid, the greedy launch): HIP-free, CPU-tested
 #include "ott_sort_plan.h"  // the sort path's host-side plan (pass plans, sweep shape, rank or radix, prefix, slices, group extents, copy pieces): HIP-free, CPU-tested
@@ -330,6 +331,13 @@ struct ott_store {
     // 8-byte keys go through d_gtable, under its own protocol
     ott::DevBuf d_rectable;
     bool rectable_clean = false;
+    // Discovery and context search (ott_discover.hip), THIS context's scratch, allocated by the first
+    // ott_query_discover that runs on it.  The rows' 8-byte states {wins | flags, loss bits or target ordinal} live in d_rectable
+    // under its protocol (the kernel that reads them last leaves them zeroed), the keys in d_gtable under its own.  d_disc: [the
+    // candidates per wins level and the list's cursor | the candidates above the cut level | one byte of wins per row]
+    // (ott_discover_plan.h), h_disc: its pinned copy the host reads behind the one wait
+    ott::DevBuf d_disc;
+    ott::PinBuf h_disc;
     // Grouped search (ott_group.hip).  d_gid: one dense group id per row slot, [cap] words, allocated by
     // ott_store_set_groups and freed by ott_store_clear_groups; nullptr = no groups (and nothing else below exists).  gid_n: the
     // rows the ids cover (a query needs gid_n == n).  Owned by the store (workers alias it), changed only under `rw` exclusive; a
@@ -762,6 +770,10 @@ struct GroupTopK {
     int E = 1;
     uint32_t KS = 0, n_lists = 0;
     uint64_t pair_cap = 0;
+    // k <= 512 only: called behind the merge kernel, before the host waits, with the device's view of the pinned hits and counts
+    // (ott_discover.hip looks up a per-hit value there); nullptr = nothing
+    int (*after_merge)(ott_store* s, void* arg, const ott_hit* d_hits, const uint64_t* d_counts) = nullptr;
+    void* after_arg = nullptr;
     int prepare(ott_store* s, const char* too_many_pairs);  // the refusal's text for more than 2^32 - 16 pairs (nullptr: cannot happen)
     int pass(ott_store* s, unsigned long long* table, uint32_t q0, uint32_t nq_here);
     int finish(ott_store* s, bool timing, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query);

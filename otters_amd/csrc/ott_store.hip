@@ -937,12 +937,13 @@ int ott_store_destroy(ott_store* s) {
     if (s->d_head) (void)hipFree(s->d_head);
     planes_release(s);  // (a worker has none of its own)
     for (ott::DevBuf* b : {&s->d_queries, &s->d_qinv, &s->d_rowmask, &s->d_runs, &s->d_prefix, &s->d_lists, &s->d_lists2, &s->d_hits,
-                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_gather, &s->d_mmr, &s->d_rectable, &s->d_gtable, &s->d_gctl, &s->d_mstable, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
+                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_gather, &s->d_mmr, &s->d_rectable, &s->d_disc, &s->d_gtable, &s->d_gctl, &s->d_mstable, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
                            &s->m_tau, &s->m_cntA, &s->m_cntB, &s->m_candA, &s->m_candB, &s->m_over, &s->m_out, &s->m_outcnt,
                            &s->m_uncert, &s->m_prefix, &s->x_send, &s->x_recv, &s->l_keysA, &s->l_keysB, &s->l_qA, &s->l_qB, &s->l_tmp, &s->l_cursor, &s->l_hist, &s->l_gate, &s->l_ctl})
         b->release();
     s->h_stage.release();
     s->h_hits.release();
+    s->h_disc.release();
     s->h_hdr.release();
     s->h_pend.release();
     for (auto& c : s->columns) {

@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import GROUP_SIZE_MAX, Cmp, Metric, Mode, Path, RecommendPlan, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type, mmr_args
+from .vec import GROUP_SIZE_MAX, Cmp, DiscoverPlan, Metric, Mode, Path, RecommendPlan, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type, mmr_args
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -473,6 +473,11 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
 
     def query_batch(self, queries, metric: Metric) -> "MetaQueryPlan":  # src/meta.rs:574-576
         return MetaQueryPlan(self, [np.asarray(q, dtype=np.float32).ravel() for q in queries], metric)
+
+    def discover(self, context, target=None, target_row=None, metric: Metric = Metric.Cosine) -> "MetaDiscoverPlan":
+        """Discovery and context search (VecStore.discover; ott_query_discover) with a meta_filter: `context` is a sequence of
+        (positive, negative) row id pairs counted from the store's first row."""
+        return MetaDiscoverPlan(self, context, target, target_row, metric)
 
     def recommend(self, positive, negative=(), metric: Metric = Metric.Cosine) -> "MetaRecommendPlan":
         """Recommend by example rows (VecStore.recommend; ott_query_recommend) with a meta_filter: `positive` and `negative` are row
@@ -971,3 +976,93 @@ class MetaRecommendPlan:
         names = sorted(st._schema)
         data = {name: st._columns[name].take(indices) for name in names}
         return MetaQueryResults(names, data, indices, scores), sides.tolist()
+
+
+class MetaDiscoverPlan:
+    """Discovery and context search over a MetaStore (MetaStore.discover; VecStore.discover's contract): meta_filter prunes chunks
+    by their zone maps and masks rows on the device, as for MetaRecommendPlan; vec_filter acts on the hit's score.  An example or
+    the target row need not pass the filter: stored data is read.  Errors surface at collect()."""
+
+    def __init__(self, store: MetaStore, context, target, target_row, metric: Metric):
+        self.store = store
+        self.metric = Metric(metric)
+        self._meta_filter: Optional[CompiledFilter] = None
+        self.meta_error: Optional[str] = None
+        self._plan = DiscoverPlan(store._store, context, target, target_row, metric) if store._store is not None else None
+
+    def _forward(self, name, *a) -> "MetaDiscoverPlan":
+        if self._plan is not None:
+            getattr(self._plan, name)(*a)
+        return self
+
+    def meta_filter(self, expr: Expr) -> "MetaDiscoverPlan":
+        try:
+            self._meta_filter = expr.compile(self.store._schema)
+            self.meta_error = None
+        except ExprError as e:
+            self.meta_error = f"meta_filter compile error: {e}"
+        return self
+
+    def vec_filter(self, score: float, cmp: Cmp) -> "MetaDiscoverPlan":
+        return self._forward("filter", score, cmp)
+
+    filter = vec_filter
+
+    def take(self, k: int) -> "MetaDiscoverPlan":
+        return self._forward("take", k)
+
+    def take_min(self, k: int) -> "MetaDiscoverPlan":
+        return self._forward("take_min", k)
+
+    def take_max(self, k: int) -> "MetaDiscoverPlan":
+        return self._forward("take_max", k)
+
+    def with_row_mask(self, mask) -> "MetaDiscoverPlan":
+        return self._forward("with_row_mask", mask)
+
+    def with_path(self, path: Path) -> "MetaDiscoverPlan":
+        return self._forward("with_path", path)
+
+    def min_wins(self, n: int) -> "MetaDiscoverPlan":
+        return self._forward("min_wins", n)
+
+    def collect_arrays(self):
+        """(hits, wins), as DiscoverPlan.collect_arrays returns them."""
+        if self.meta_error is not None:
+            raise OttersError(self.meta_error)
+        st = self.store
+        if st._store is None or self._plan is None:
+            raise OttersError("discover: the store holds no vectors, so no row can be an example")
+        rd = self._plan.resolve()
+        compiled = self._meta_filter
+        chunk_mask = st.build_chunk_mask_for_plan(compiled) if compiled is not None else None
+        if chunk_mask is not None and not chunk_mask.any():
+            return np.zeros(0, dtype=N.HIT_DTYPE), np.zeros(0, dtype=np.uint32)
+        with st._mask_lock:  # the device row mask is store-global state: built and read in one critical section (MetaQueryPlan.collect)
+            use_dev = False
+            if compiled is not None and not st.row_mask_is_all_true(compiled, chunk_mask):
+                if st._device_mask_ok(compiled):
+                    if rd.row_mask is not None:
+                        raise OttersError("discover: with_row_mask cannot be combined with a meta_filter that needs a row mask of its own")
+                    st.build_row_mask_device(compiled)
+                    use_dev = True
+                else:
+                    host = st.build_row_mask_host(compiled)
+                    if rd.row_mask is not None:
+                        m = np.ones(host.size, bool)
+                        m[: min(rd.row_mask.size, host.size)] = rd.row_mask[: host.size]
+                        host &= m
+                    rd.row_mask = host
+            hits, wins, gstats = st._store._run_discover(rd, chunk_mask=chunk_mask, use_device_row_mask=use_dev)
+        st._store.last_stats = gstats
+        return hits, wins
+
+    def collect(self):
+        """(MetaQueryResults, wins): the hits' rows materialised as MetaQueryPlan.collect does, and the pairs each hit wins as a list."""
+        hits, wins = self.collect_arrays()
+        st = self.store
+        indices = [int(i) for i in hits["index"]]
+        scores = [float(s) for s in hits["score"]]
+        names = sorted(st._schema)
+        data = {name: st._columns[name].take(indices) for name in names}
+        return MetaQueryResults(names, data, indices, scores), wins.tolist()

@@ -761,6 +761,165 @@ class RecommendPlan:
         return [SearchResult(i, s) for i, s in zip(hits["index"].tolist(), hits["score"].tolist())], sides.tolist()
 
 
+DISCOVER_MAX_PAIRS = 32     # include/otters_hip.h: OTT_DISCOVER_MAX_PAIRS
+NO_ROW = 2 ** 64 - 1        # include/otters_hip.h: OTT_NO_ROW
+
+
+def discover_context(context, target_row, n_rows: int):
+    """discover()'s context pairs and target row checked as ott_query_discover checks them, with its messages, in its order:
+    (uint64 positives, uint64 negatives).  Pure host logic."""
+    pairs = [tuple(p) for p in context]
+    if any(len(p) != 2 for p in pairs):
+        raise OttersError("discover: the context is a sequence of (positive, negative) row id pairs")
+    if not 1 <= len(pairs) <= DISCOVER_MAX_PAIRS:
+        raise OttersError("ott_query_discover: between 1 and OTT_DISCOVER_MAX_PAIRS (32) context pairs are needed")
+    pos, neg = as_row_ids([p[0] for p in pairs]), as_row_ids([p[1] for p in pairs])
+    # the library's walk (ott_discover_plan.h: disc_slots), pair by pair, the target row last: the first fault it meets is the one named
+    for a, b in zip(pos.tolist(), neg.tolist()):
+        for i in (a, b):
+            if i >= n_rows:
+                raise OttersError(f"ott_query_discover: row id {i} is not below the store's length {n_rows}")
+        if a == b:
+            raise OttersError(f"ott_query_discover: row {a} is both the positive and the negative of a pair")
+    if target_row is not None and target_row >= n_rows:
+        raise OttersError(f"ott_query_discover: row id {target_row} is not below the store's length {n_rows}")
+    return pos, neg
+
+
+@dataclass
+class ResolvedDiscover:
+    """What DiscoverPlan hands to ott_query_discover once it is validated."""
+    positive: np.ndarray           # uint64[n_pairs]
+    negative: np.ndarray           # uint64[n_pairs]
+    target: Optional[np.ndarray]   # float32[dim], or None
+    target_row: int                # NO_ROW = none
+    min_wins: int
+    metric: int
+    take: int
+    k: int
+    filter_cmp: int
+    filter_thr: float
+    row_mask: Optional[np.ndarray]
+    path: int
+
+
+@dataclass
+class DiscoverResult:
+    """One hit of a discovery or context search: the row, its score (the target score, or the loss without a target), the pairs it wins."""
+    index: int
+    score: float
+    wins: int
+
+
+class DiscoverPlan:
+    """Discovery and context search (VecStore.discover; ott_query_discover, Qdrant's Discovery API).  `context` is a sequence of
+    (positive, negative) row id pairs; a row WINS a pair when it is closer to the pair's positive than to its negative.  With a
+    target — a vector (`target`) or a stored row (`target_row`) — the rows are ranked by the pairs they win, then by their score
+    against the target; without one (context search) by a loss that is zero where every pair is won and falls with every violated
+    pair.  Lazy like VecQueryPlan: errors surface at validate() / collect()."""
+
+    def __init__(self, store: "VecStore", context, target, target_row, metric: Metric):
+        self.vector_store = store
+        self.context = list(context)
+        self.target = target
+        self.target_row = target_row
+        self.search_metric = Metric(metric)
+        self.filter_criteria: Optional[tuple] = None
+        self.take_type: Optional[TakeType] = None
+        self.take_count: Optional[int] = None
+        self.row_mask: Optional[np.ndarray] = None
+        self.path = Path.Auto
+        self.min_wins_count = 0
+
+    def with_row_mask(self, mask) -> "DiscoverPlan":
+        self.row_mask = np.asarray(mask, dtype=bool).ravel()
+        return self
+
+    def filter(self, score: float, cmp: Cmp) -> "DiscoverPlan":
+        """The score filter acts on the hit's score: the target score with a target, the loss without one."""
+        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
+        return self
+
+    def _take_with_options(self, count: int, take_type: Optional[TakeType]) -> "DiscoverPlan":
+        self.take_count = int(count)
+        if take_type is not None:
+            self.take_type = take_type
+        elif self.take_type is None:
+            self.take_type = infer_default_take_type(self.search_metric)
+        return self
+
+    def take(self, count: int) -> "DiscoverPlan":
+        return self._take_with_options(count, None)
+
+    def take_min(self, count: int) -> "DiscoverPlan":
+        return self._take_with_options(count, TakeType.Min)
+
+    def take_max(self, count: int) -> "DiscoverPlan":
+        return self._take_with_options(count, TakeType.Max)
+
+    def with_path(self, path: Path) -> "DiscoverPlan":
+        self.path = Path(path)
+        return self
+
+    def min_wins(self, n: int) -> "DiscoverPlan":
+        """Only rows that win at least `n` of the pairs come out (n = the number of pairs: only rows inside the fenced region)."""
+        self.min_wins_count = int(n)
+        return self
+
+    def _target_vector(self) -> Optional[np.ndarray]:
+        if self.target is None:
+            return None
+        t = np.asarray(self.target, dtype=np.float32)
+        if t.ndim == 2 and t.shape[0] != 1:
+            raise OttersError("ott_query_discover: at most one target vector (d->nq <= 1)")
+        t = np.ascontiguousarray(t.ravel())
+        if t.size != self.vector_store.dim:
+            raise OttersError(f"Query vector length {t.size} does not match expected dimension {self.vector_store.dim}")
+        return t
+
+    def resolve(self) -> ResolvedDiscover:
+        """Validate and lower the plan.  Pure host logic, no GPU.  The library's refusals in the library's order."""
+        st = self.vector_store
+        pairs = [tuple(p) for p in self.context]
+        if not 1 <= len(pairs) <= DISCOVER_MAX_PAIRS:
+            raise OttersError("ott_query_discover: between 1 and OTT_DISCOVER_MAX_PAIRS (32) context pairs are needed")
+        tv = self._target_vector()
+        trow = None
+        if self.target_row is not None:
+            trow = int(as_row_ids([self.target_row])[0])
+        if tv is not None and trow is not None:
+            raise OttersError("ott_query_discover: a target vector and a target row are both given")
+        if self.min_wins_count < 0 or self.min_wins_count > len(pairs):
+            raise OttersError("ott_query_discover: min_wins is above the number of pairs" if self.min_wins_count > 0 else "discover: min_wins is negative")
+        if self.path == Path.Mfma:
+            raise OttersError("ott_query_discover: the MFMA path does not serve discovery queries; use path AUTO or EXACT")
+        if st.devices is not None:
+            raise OttersError("ott_query_discover: a multi-GPU store is not served (the examples' rows lie on different shards)")
+        pos, neg = discover_context(pairs, trow, len(st))
+        k = self.take_count if self.take_count is not None else len(st)
+        take = self.take_type if self.take_type is not None else infer_default_take_type(self.search_metric)
+        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
+        return ResolvedDiscover(positive=pos, negative=neg, target=tv, target_row=NO_ROW if trow is None else trow, min_wins=self.min_wins_count,
+                                metric=int(self.search_metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask,
+                                path=int(self.path))
+
+    def validate(self) -> None:
+        self.resolve()
+
+    def collect_arrays(self):
+        """(hits, wins): `hits` a NumPy record array (`index` u64, `score` f32 — the target score, or the loss without a target —,
+        `query` = 0) in the call's order, `wins[i]` (u32) the pairs hit i wins."""
+        store = self.vector_store
+        hits, wins, stats = store._run_discover(self.resolve())
+        store.last_stats = stats
+        return hits, wins
+
+    def collect(self):
+        """One DiscoverResult(index, score, wins) per hit."""
+        hits, wins = self.collect_arrays()
+        return [DiscoverResult(i, s, w) for i, s, w in zip(hits["index"].tolist(), hits["score"].tolist(), wins.tolist())]
+
+
 class VecStore:
     """src/vec.rs:338-412: row-major f32 vectors + per-row inverse norms, resident in HBM."""
 
@@ -1191,6 +1350,45 @@ class VecStore:
         N.check(N.lib().ott_query_recommend(self._handle(), C.byref(d), N.ptr(rr.positive), rr.positive.size, N.ptr(rr.negative) if rr.negative.size else None,
                                             rr.negative.size, rr.flags, N.ptr(out), cap, C.byref(n_out), N.ptr(sides), C.byref(st)))
         return out[: n_out.value].copy(), sides[: n_out.value].copy(), st.as_dict()
+
+    def discover(self, context, target=None, target_row=None, metric: Metric = Metric.Cosine) -> DiscoverPlan:
+        """Discovery search (ott_query_discover): `context` is a sequence of (positive, negative) row id pairs counted from the
+        store's first row (not shifted by the base offset); `target` a vector or `target_row` a stored row, or neither for a context
+        search.  .take(k).collect() returns the hits with the pairs they win."""
+        return DiscoverPlan(self, context, target, target_row, metric)
+
+    def _run_discover(self, rd: ResolvedDiscover, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
+        """ott_query_discover.  Returns (hits HIT_DTYPE array, wins uint32 array, stats dict)."""
+        cap = max(min(rd.k, self._n), 1)
+        out = np.empty(cap, dtype=N.HIT_DTYPE)
+        wins = np.empty(cap, dtype=np.uint32)
+        d = N.QueryDesc()
+        keep = []
+        if rd.target is not None:
+            keep.append(rd.target)
+            d.queries = rd.target.ctypes.data
+            d.nq = 1
+        else:
+            d.queries = None
+            d.nq = 0
+        d.metric, d.take, d.filter_cmp, d.filter_thr = rd.metric, rd.take, rd.filter_cmp, rd.filter_thr
+        d.mode, d.k, d.path = int(Mode.Merged), rd.k, rd.path
+        if chunk_mask is not None:
+            cm = N.pack_bits(chunk_mask)
+            keep.append(cm)
+            d.chunk_mask = cm.ctypes.data
+        if use_device_row_mask:
+            d.use_device_row_mask = 1
+        elif rd.row_mask is not None and rd.row_mask.size:
+            rm = N.pack_bits(rd.row_mask)
+            keep.append(rm)
+            d.row_mask = rm.ctypes.data
+            d.row_mask_bits = int(rd.row_mask.size)
+        n_out = C.c_uint64(0)
+        st = N.Stats()
+        N.check(N.lib().ott_query_discover(self._handle(), C.byref(d), rd.target_row, N.ptr(rd.positive), N.ptr(rd.negative), rd.positive.size, rd.min_wins, 0,
+                                           N.ptr(out), cap, C.byref(n_out), N.ptr(wins), C.byref(st)))
+        return out[: n_out.value].copy(), wins[: n_out.value].copy(), st.as_dict()
 
     def score_rows(self, queries, metric: Metric, ids) -> np.ndarray:
         """float32[nq, n_ids]: the score of every query against every row of `ids` (ott_store_score_rows) -- the exact path's bits,
