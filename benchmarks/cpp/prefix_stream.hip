@@ -2,7 +2,7 @@
 // `c` of the row's 128-B stages (8 rows x 128 B per wave instruction, one stage in flight, as exact_kernel does) and then one
 // `pitch`-byte line per row from a second buffer with lane = row (16 B per lane and instruction at a stride of `pitch`), all with
 // non-temporal loads; the values go into a checksum so nothing is optimised away.  Prints TB/s of bytes REQUESTED.
-//   prefix_stream [rows=10000000] [dim=768] [c=9] [pitch=192] [workgroups per CU=2] [lines as stages=0] [head=0] [pipelined=0]
+//   prefix_stream [rows=10000000] [dim=768] [c=9] [pitch=192] [workgroups per CU=2] [lines as stages=0] [head=0] [pipelined=0] [seed rows=0] [keep=10]
 //   (dim a multiple of 32, pitch of 16, <= 512; c = 0 reads no row stage)
 // lines as stages = 1: the tile's 64 lines are read as the row stages are — eight 16-B pieces of every line per round, 8 lines x
 // 128 B per wave instruction — which is how the four-bit form of the sweep fetches them
@@ -10,6 +10,10 @@
 // per row from three plain arrays, lane = row (the head of DESIGN.md 3.1b: stage 0's codes, rho_all and the inverse norm)
 // pipelined = 1 (c = 0 and lines as stages only): the next round of lines, or the next tile's first round and its head, is asked
 // for before the current round is summed, so a tile's first round does not wait behind the last tile's sums
+// seed rows = N > 0 (c = 0, lines as stages, head = 2, pipelined): the pattern of the seed's estimate pass instead — the pipelined
+// line / head pattern over the first N rows only, and then per wave `keep` WHOLE rows of its first tile, read as the sweep finishes
+// queued rows: a 128-B stage of eight rows per wave instruction, the next stage in flight while one is summed
+//   prefix_stream 10000000 768 0 384 2 1 2 1 312512 10
 //   hipcc -O3 --offload-arch=gfx950 prefix_stream.hip -o prefix_stream
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -63,8 +67,8 @@ __global__ __launch_bounds__(256) void sweep(const float* __restrict__ rows, con
 }
 
 // c = 0, lines as stages, one round ahead across rounds and tiles
-__global__ __launch_bounds__(256) void sweep_pipe(const char* __restrict__ lines, uint64_t n_tiles, uint32_t pitch, int head, const v4f* __restrict__ hcode,
-                                                  const float* __restrict__ hrho, const float* __restrict__ hinv, float* out) {
+__device__ __forceinline__ float pipe_body(const char* __restrict__ lines, uint64_t n_tiles, uint32_t pitch, int head, const v4f* __restrict__ hcode,
+                                           const float* __restrict__ hrho, const float* __restrict__ hinv) {
     const int lane = threadIdx.x & 63;
     const uint32_t gw = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
     const int lrow = lane >> 3, lslot = lane & 7;
@@ -74,7 +78,7 @@ __global__ __launch_bounds__(256) void sweep_pipe(const char* __restrict__ lines
     float hs = 0.f, hsn = 0.f;
     uint64_t t = gw;
     uint32_t i = 0;
-    if (t >= n_tiles) return;
+    if (t >= n_tiles) return acc;
 #pragma unroll
     for (int m = 0; m < 8; m++) cur[m] = __builtin_nontemporal_load((const v4f*)(lines + (t * 64 + 8 * m + lrow) * (uint64_t)pitch + 16 * (lslot < np ? lslot : np - 1)));
     if (head) hs = __builtin_nontemporal_load(hinv + t * 64 + lane);
@@ -100,6 +104,42 @@ __global__ __launch_bounds__(256) void sweep_pipe(const char* __restrict__ lines
         if (last) { hs = hsn; hc = hcn; }
         t = t2; i = i2;
     }
+    return acc;
+}
+__global__ __launch_bounds__(256) void sweep_pipe(const char* __restrict__ lines, uint64_t n_tiles, uint32_t pitch, int head, const v4f* __restrict__ hcode,
+                                                  const float* __restrict__ hrho, const float* __restrict__ hinv, float* out) {
+    const float acc = pipe_body(lines, n_tiles, pitch, head, hcode, hrho, hinv);
+    if (acc == 12345.678f) out[0] = acc;
+}
+// the seed's estimate pass: the pipelined pattern over the seed's tiles, then `keep` <= 64 whole rows of the wave's first tile
+__global__ __launch_bounds__(256) void sweep_seed(const float* __restrict__ rows, const char* __restrict__ lines, uint64_t n_tiles, uint32_t ld, uint32_t pitch,
+                                                  uint32_t keep, const v4f* __restrict__ hcode, const float* __restrict__ hrho, const float* __restrict__ hinv,
+                                                  float* out) {
+    float acc = pipe_body(lines, n_tiles, pitch, 2, hcode, hrho, hinv);
+    const int lane = threadIdx.x & 63;
+    const uint32_t gw = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lrow = lane >> 3, lslot = lane & 7;
+    if (gw < n_tiles) {  // (its first tile is inside the seed: every row read is one of that tile's 64)
+        const float* rp[8];
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            const uint32_t i = 8 * m + lrow;
+            rp[m] = rows + ((uint64_t)gw * 64 + (i < keep ? (i * 5) & 63 : 0)) * ld + lslot * 4;  // (past keep: the first row again, as the sweep does)
+        }
+        v4f r[8], rn[8];
+#pragma unroll
+        for (int m = 0; m < 8; m++) r[m] = __builtin_nontemporal_load((const v4f*)rp[m]);
+        for (uint32_t s = 0; s < ld / 32; s++) {
+            if (s + 1 < ld / 32) {
+#pragma unroll
+                for (int m = 0; m < 8; m++) rn[m] = __builtin_nontemporal_load((const v4f*)(rp[m] + (s + 1) * 32));
+            }
+#pragma unroll
+            for (int m = 0; m < 8; m++) acc += r[m].x + r[m].y + r[m].z + r[m].w;
+#pragma unroll
+            for (int m = 0; m < 8; m++) r[m] = rn[m];
+        }
+    }
     if (acc == 12345.678f) out[0] = acc;
 }
 
@@ -112,6 +152,12 @@ int main(int argc, char** argv) {
     const int staged = argc > 6 ? atoi(argv[6]) : 0;
     const int head = argc > 7 ? atoi(argv[7]) : 0;
     const int pipe = argc > 8 ? atoi(argv[8]) : 0;
+    const uint64_t seed = argc > 9 ? strtoull(argv[9], nullptr, 10) : 0ull;
+    const uint32_t keep = argc > 10 ? (uint32_t)atoi(argv[10]) : 10u;
+    if (seed && (seed < 64 || seed > n || !pipe || head != 2 || keep < 1 || keep > 64)) {
+        printf("bad arguments\n");
+        return 1;
+    }
     if (head < 0 || head > 2 || pipe < 0 || pipe > 1 || (pipe && (c || !staged))) {
         printf("bad arguments\n");
         return 1;
@@ -133,11 +179,19 @@ int main(int argc, char** argv) {
     float best = 1e9f;
     for (int it = 0; it < 8; it++) {
         CK(hipEventRecord(a));
-        if (pipe) hipLaunchKernelGGL(sweep_pipe, dim3(prop.multiProcessorCount * per_cu), dim3(256), 0, 0, l, n_tiles, pitch, head, (const v4f*)hc, hr, hi, o);
+        if (seed) hipLaunchKernelGGL(sweep_seed, dim3(prop.multiProcessorCount * per_cu), dim3(256), 0, 0, d, l, seed / 64, ld, pitch, keep, (const v4f*)hc, hr, hi, o);
+        else if (pipe) hipLaunchKernelGGL(sweep_pipe, dim3(prop.multiProcessorCount * per_cu), dim3(256), 0, 0, l, n_tiles, pitch, head, (const v4f*)hc, hr, hi, o);
         else hipLaunchKernelGGL(sweep, dim3(prop.multiProcessorCount * per_cu), dim3(256), 0, 0, d, l, n_tiles, ld, c, pitch, staged, head, (const v4f*)hc, hr, hi, o);
         CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
         float ms; CK(hipEventElapsedTime(&ms, a, b));
         if (it && ms < best) best = ms;
+    }
+    if (seed) {
+        const uint64_t waves = (uint64_t)prop.multiProcessorCount * per_cu * 4, with_rows = waves < seed / 64 ? waves : seed / 64;
+        const double sb = (double)(seed / 64) * 64 * (pitch + 24.0) + (double)with_rows * keep * ld * 4.0;
+        printf("estimate pass: %llu of %llu rows, dim %u, pitch %u, head 24 B, pipelined, %u whole rows on each of %llu waves, %d workgroups per CU: %.4f ms  %.3f GB requested  %.2f TB/s\n",
+               (unsigned long long)(seed / 64 * 64), (unsigned long long)n, ld, pitch, keep, (unsigned long long)with_rows, per_cu, best, sb / 1e9, sb / best / 1e9);
+        return 0;
     }
     const double bytes = (double)n_tiles * 64 * (c * 128.0 + pitch + (head == 2 ? 24 : head ? 4 : 0));
     printf("rows %llu dim %u c %u pitch %u%s%s%s, %d workgroups per CU: %.3f ms  %.3f GB requested  %.2f TB/s\n", (unsigned long long)n, ld, c, pitch, staged ? " (lines as stages)" : "",

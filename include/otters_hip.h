@@ -131,7 +131,9 @@ typedef struct {
     uint32_t passes;            /* corpus passes (EXACT path: ceil(nq / queries per pass)) */
     uint64_t rescored;          /* MFMA path: candidates re-scored in reference order.  EXACT path, pruned sweep of one query (host
                                    output): rows that passed the checkpoint and had their last stages read (of the rows behind the
-                                   seed; 0 when the sweep was not pruned) */
+                                   seed; where the seed is an estimate pass — the head form, k <= 64, no filter, stores from 1 310 720
+                                   rows — of ALL rows, which the gated launch then covers: the few rows the estimate pass itself
+                                   finished are not counted; 0 when the sweep was not pruned) */
     uint32_t retries;           /* MFMA path: queries no candidate pass could certify, recomputed on the exact path */
     uint32_t refined;           /* MFMA path: queries the hi pass (bf16 hi plane) could not certify, re-run through the split pass */
     float err_ratio_max;        /* MFMA path: max over the re-scored candidates of |approximate - exact score| / eps, eps the error bound

@@ -200,6 +200,7 @@ struct ExactCtx {
     double qt = 0.0, qn = 0.0, q1 = 0.0;
     PruneQuant qq{0, 0.0f, 0.0f, 0.0, 0};  // four bits per dim: the quantised query (ott_prune.h)
     bool head = false;                     // ... in the head form: no f32 stage in front, the query-side values over the whole query
+    bool seed_est = false;                 // the seed is an estimate pass over plA; plB is then the WHOLE plan and the final merge takes its lists alone
     // the result block, as the merge kernel sees it
     ExactResult res{0, 0, 0};
     uint64_t* d_counts = nullptr;
@@ -227,11 +228,16 @@ void plan_pruned_sweep(ExactCtx& c) {
 #endif
     const uint32_t m = head ? 0u : pp.c * 32;
     if (head) (void)prune_query_quant(c.queries, s->dim, 0, &c.qq);
-    split_plan(c.pl, pp.seed, c.plA, c.plB);
+    // (the seed as an estimate pass: over the first rows, the plan's seed unless an experiment build says otherwise; the gated launch
+    // then takes every row, the seed's included)
+    const uint64_t est_rows = prune_plan_seed_est(in, pp, head, c.d->filter_cmp != OTT_CMP_NONE);
+    split_plan(c.pl, est_rows ? est_rows : pp.seed, c.plA, c.plB);
     const bool two_runs_each = c.plA.runs.size() <= 2 && c.plB.runs.size() <= 2 && c.plB.rows_scored > 0;
     if (!two_runs_each || !prune_query_bounds(c.queries, s->dim, m, &c.qt, &c.qn)) return;
     c.prune = pp;
     c.head = head;
+    c.seed_est = est_rows != 0;
+    if (c.seed_est) c.plB = c.pl;  // (a lean call: at most two runs)
     c.q1 = prune_query_l1(c.queries, s->dim, m);
     c.preA = tile_prefix(c.plA, 64);
     c.preB = tile_prefix(c.plB, 64);
@@ -302,32 +308,40 @@ int pruned_sweep(ExactCtx& c) {
         }
         tails_dev = (unsigned long long*)s->d_tails.p;
     }
-    const ExactParams pa = part_params(c, c.plA, c.preA, (Cand*)s->d_lists.p);
+    ExactParams pa = part_params(c, c.plA, c.preA, (Cand*)s->d_lists.p);
+    // what both launches of the sketch forms read: the lines, the quantised query's values, the head
+    auto sketch_inputs = [&](ExactParams& q) {
+        q.prune_stage = c.prune.c;
+        q.prune_qt = c.qt;
+        q.prune_qn = c.qn;
+        if (!c.prune.sketch) return;
+        q.prune_sketch = s->d_sketch;
+        q.sk_pitch = s->sk_pitch;
+        q.sk_stage0 = s->sk_stage0;
+        q.sk_bits = s->sk_bits;
+        q.prune_q1 = c.q1;
+        q.prune_qe1 = c.qq.qe1;
+        q.prune_qscale = c.qq.scale;
+        q.prune_qinv_scale = c.qq.inv_scale;
+        q.prune_qsum = c.qq.qsum;
+        if (c.head) {
+            q.prune_head_codes = reinterpret_cast<const uint32_t*>(s->d_head);
+            q.prune_head_rho = reinterpret_cast<const float*>(s->d_head + s->cap * (size_t)16);
+        }
+    };
+    if (c.seed_est) {  // the estimate pass: no gate and no tail counter
+        sketch_inputs(pa);
+        pa.seed_est = 1;
+        pa.seed_keep = prune_seed_keep(c.k_eff);
+    }
     if ((rc = launch_exact(s, pa, 1, c.x.E, c.gridA))) return rc;
     if ((rc = launch_merge(s, (const Cand*)s->d_lists.p, (uint32_t)c.gridA, KS, 0, 1, (uint32_t)c.k_eff, c.x.E, c.p.take_max != 0, tie_base(s),
                            (ott_hit*)(seed_res + 8), KS, seed_res, s->cur_tie_sh)))
         return rc;
     ExactParams pb = part_params(c, c.plB, c.preB, (Cand*)s->d_lists.p + (size_t)c.gridA * KS);
-    pb.prune_stage = c.prune.c;
+    sketch_inputs(pb);
     pb.prune_seed = seed_res;
-    pb.prune_qt = c.qt;
-    pb.prune_qn = c.qn;
     pb.prune_tails = tails_dev;
-    if (c.prune.sketch) {
-        pb.prune_sketch = s->d_sketch;
-        pb.sk_pitch = s->sk_pitch;
-        pb.sk_stage0 = s->sk_stage0;
-        pb.sk_bits = s->sk_bits;
-        pb.prune_q1 = c.q1;
-        pb.prune_qe1 = c.qq.qe1;
-        pb.prune_qscale = c.qq.scale;
-        pb.prune_qinv_scale = c.qq.inv_scale;
-        pb.prune_qsum = c.qq.qsum;
-        if (c.head) {
-            pb.prune_head_codes = reinterpret_cast<const uint32_t*>(s->d_head);
-            pb.prune_head_rho = reinterpret_cast<const float*>(s->d_head + s->cap * (size_t)16);
-        }
-    }
     return launch_exact(s, pb, 1, c.x.E, c.gridB);
 }
 
@@ -345,10 +359,14 @@ int plain_passes(ExactCtx& c) {
     return OTT_OK;
 }
 
-// the block lists into the result block: per query every query's own `grid` lists, else all of them (the pruned sweep: of both launches)
+// the block lists into the result block: per query every query's own `grid` lists, else all of them (the pruned sweep: of both
+// launches — behind an estimate pass of the gated launch alone, which saw every row: a seed row would appear twice)
 int merge_exact(ExactCtx& c) {
     ott_store* s = c.s;
     const uint32_t KS = c.x.KS, grid = (uint32_t)c.x.grid;
+    if (c.seed_est)
+        return launch_merge(s, (const Cand*)s->d_lists.p + (size_t)c.gridA * KS, (uint32_t)c.gridB, KS, 0, c.groups, (uint32_t)c.k_eff, c.x.E,
+                            c.p.take_max != 0, tie_base(s), c.d_hits, KS, c.d_counts, s->cur_tie_sh);
     const uint32_t n_lists = c.perq ? grid : (uint32_t)exact_n_lists(c.x, c.nq, false, c.prune.c != 0, c.gridA, c.gridB);
     return launch_merge(s, (const Cand*)s->d_lists.p, n_lists, KS, c.perq ? (uint64_t)grid * KS : 0, c.groups, (uint32_t)c.k_eff, c.x.E,
                         c.p.take_max != 0, tie_base(s), c.d_hits, KS, c.d_counts, s->cur_tie_sh);
@@ -361,7 +379,9 @@ int fetch_exact(ExactCtx& c, std::vector<std::vector<ott_hit>>& lists, ott_stats
     char* hh = (char*)s->h_hits.p;
     if (c.prune.c) OTT_HIP(hipMemcpyAsync(hh + c.res.bytes, s->d_tails.p, 8, hipMemcpyDeviceToHost, s->stream));
     OTT_HIP(hipStreamSynchronize(s->stream));
-    if (c.prune.c) {  // rows whose last stages were read after the checkpoint (the seed's rows are not counted: they have no checkpoint)
+    // rows whose last stages were read after the checkpoint (the seed's rows are not counted: they have no checkpoint; behind an
+    // estimate pass the gated launch covers every row, the few rows that pass finished are not counted)
+    if (c.prune.c) {
         uint64_t total;
         memcpy(&total, hh + c.res.bytes, 8);
         st.rescored += total - s->tails_seen;

@@ -127,7 +127,13 @@ __device__ __forceinline__ void exact_glds16(const char* sbase, uint32_t voff, u
 // line's pieces out of LDS.  The decode is integer: the workgroup quantises the query once (ott_prune.h: prune_quant_word) and keeps
 // its three base-16 digit planes in LDS; a piece's four code words meet the stage's digit words in twelve v_dot8_i32_i4, three
 // independent i32 sums, and prune_score_bound_sketchq takes K = sum qhat kappa, exact.
-template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false, int SK = 0>
+// SEED (with the head form, SK = 5, E = 1): the seed as an estimate pass (ott_exact_plan.h: prune_plan_seed_est).  The launch has no
+// gate.  A tile is read as a gated tile is — lines, heads, inverse norms, the same clamps and masks, the same twelve dot products
+// per piece — and in place of the bound test every eligible lane offers (ord(estimate), ~row) to the wave's list, which keeps the
+// p.seed_keep best (ott_prune.h: prune_score_est_sketchq; a NaN estimate is not offered).  Behind the wave's last tile those rows go
+// to the deferred-tail queue with zero accumulators, the list is emptied, and one pq_finish scores them in the full sweep's loads
+// and additions and offers the exact scores: the block list holds exact scores of eligible rows only.
+template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false, int SK = 0, bool SEED = false>
 __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) {
     static_assert(!I8 || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL), "the int8 sweep takes one query, cosine / dot, merged");
     static_assert(!PRUNE || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL && !I8), "the pruned sweep takes one query, cosine / dot, merged");
@@ -135,6 +141,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
     constexpr bool HD = SK == 5;               // the head form of the four-bit sketch: the checkpoint in front of stage 0
     constexpr bool SK4 = SK == 4 || SK == 5;   // either four-bit form
     static_assert(!HD || SK4_INT, "the head form decodes by integer dot products only");
+    static_assert(!SEED || (HD && E == 1), "the estimate pass is the head form's, one list entry per lane");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -236,7 +243,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
     const uint32_t pstage = HD ? 0u : p.prune_stage;  // the checkpoint
     const uint32_t s_end = PRUNE ? pstage : nstages;
     uint32_t theta = 0;
-    if constexpr (PRUNE) {
+    if constexpr (PRUNE && !SEED) {
         if (p.prune_seed[0] >= p.k) theta = ord_of(reinterpret_cast<const ott_hit*>(p.prune_seed + 8)[p.k - 1].score, take_max);
     }
     float* pq = smem + WAVES * STAGE_FLOATS + wave * (PQ_CAP * PQ_WORDS);  // [acc 0..7 | vinv | row] x PQ_CAP
@@ -388,7 +395,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             const uint32_t tn = next_tile(t + nw, row0n, cntn, vmn);
             bool keep = valid;
             float vinv = 0.0f;
-            if (gate != 0) {
+            if (SEED || gate != 0) {
                 if (!pf) {
                     load_line(row0, cnt, 0);
                     load_head(row0, cnt);
@@ -446,7 +453,19 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                         K2 = __builtin_amdgcn_sdot8((int)c0[i], (int)d2[i], K2, false);
                     }
                 }
-                if (valid) {
+                if constexpr (SEED) {
+                    const int K = 2 * (256 * K2 + 16 * K1 + K0) + p.prune_qsum;
+                    const float est = prune_score_est_sketchq(vinv, sk_a, rho_all, K, p.prune_qscale, qinv[0], p.metric == OTT_METRIC_COSINE);
+                    const bool offer = valid && est - est == 0.0f;  // (NaN or infinite: not offered)
+                    const uint64_t key = ((uint64_t)ord_of(est, take_max) << 32) | (uint32_t)(~(uint32_t)my_row);
+                    if (fresh[0]) {
+                        wl_fill_sorted(L[0], tk[0], tq[0], p.seed_keep, offer, key, p.q0, lane, 0u);
+                        fresh[0] = false;
+                    } else {
+                        wl_offer(L[0], tk[0], tq[0], p.seed_keep, offer, key, p.q0, lane, 0u);
+                    }
+                    keep = false;
+                } else if (valid) {
                     const float zero[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                     const int K = 2 * (256 * K2 + 16 * K1 + K0) + p.prune_qsum;
                     const float b = prune_score_bound_sketchq(zero, vinv, sk_a, rho_all, K, p.prune_qscale, p.dim, p.prune_qt, p.prune_qe1, p.prune_qn, qinv[0],
@@ -456,8 +475,8 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             } else if (valid) {
                 vinv = p.inv[my_row];
             }
-            const uint64_t km = __ballot(keep);
-            if (keep) {
+            const uint64_t km = SEED ? 0ull : __ballot(keep);
+            if (!SEED && keep) {
                 const uint32_t at = (pq_head + pq_n + (uint32_t)__popcll(km & ((1ull << lane) - 1ull))) & (PQ_CAP - 1);
 #pragma unroll
                 for (int l = 0; l < 8; l++) pq[l * PQ_CAP + at] = 0.0f;
@@ -465,7 +484,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                 pq_row[at] = (uint32_t)my_row;
             }
             pq_n += (uint32_t)__popcll(km);
-            if (pq_n >= 64) {
+            if (!SEED && pq_n >= 64) {
                 // (64 survivors: about one tile in seventy at the headline's rate.  What was asked for ahead is asked for again behind
                 // the finish instead of being kept across it: its 38 registers would sit on top of the finish's own staging registers)
                 pq_finish(64);
@@ -478,6 +497,25 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             row0 = row0n;
             cnt = cntn;
             vm = vmn;
+        }
+        if constexpr (SEED) {
+            // the wave's best rows by estimate (positions 0 .. seed_keep - 1 of the list, sentinels behind the real ones) are queued
+            // like survivors, and the list starts again: what it ends up with are their exact scores
+            const bool have = (uint32_t)lane < p.seed_keep && L[0].key[0] != 0ull;
+            const uint64_t hm = __ballot(have);
+            if (have) {
+                const uint32_t r = ~(uint32_t)L[0].key[0];
+                const uint32_t at = (uint32_t)__popcll(hm & ((1ull << lane) - 1ull));
+#pragma unroll
+                for (int l = 0; l < 8; l++) pq[l * PQ_CAP + at] = 0.0f;
+                pq[8 * PQ_CAP + at] = p.inv[r];
+                pq_row[at] = r;
+            }
+            pq_n = (uint32_t)__popcll(hm);
+            wl_init(L[0]);
+            tk[0] = 0;
+            tq[0] = 0xFFFFFFFFu;
+            fresh[0] = true;
         }
     } else
     for (uint32_t t = gw; t < p.n_tiles; t += nw) {
@@ -1765,9 +1803,9 @@ int exact_grid(const ott_store* s, uint32_t n_tiles) {
 }
 
 // the pruned sweep (p.prune_stage != 0): its queue takes the dynamic LDS past 48 KB
-template <int E, bool BLK, int SK>
+template <int E, bool BLK, int SK, bool SEED = false>
 static int launch_prune(ott_store* s, const ExactParams& p, int grid) {
-    auto kern = exact_kernel<MK_DOT, 1, E, false, false, false, BLK, false, true, SK>;
+    auto kern = exact_kernel<MK_DOT, 1, E, false, false, false, BLK, false, true, SK, SEED>;
     static std::atomic<uint64_t> attr_set{0};
     if (ott::attr_needed(attr_set, s->device)) {
         OTT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, EXACT_SMEM_PRUNE));
@@ -1783,6 +1821,10 @@ static int launch_prune(ott_store* s, const ExactParams& p, int grid) {
 // slower than the c = 1 form, so prune_plan_head never asks for it and it is not instantiated)
 template <int E, bool BLK>
 static int launch_prune_head(ott_store* s, const ExactParams& p, int grid) {
+    if constexpr (SK4_INT && E == 1) {  // (the estimate pass of the seed: k <= 64 only, prune_plan_seed_est)
+        if (p.seed_est != 0) return launch_prune<E, BLK, 5, true>(s, p, grid);
+    }
+    if (p.seed_est != 0) return fail(OTT_ERR_INVALID, "launch_exact: the estimate pass needs the integer decode and a list of k <= 64");
     if constexpr (SK4_INT && E <= 4) return launch_prune<E, BLK, 5>(s, p, grid);
     else return fail(OTT_ERR_INVALID, "launch_exact: the head form needs the integer decode and a list of k <= 256");
 }

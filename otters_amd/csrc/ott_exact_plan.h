@@ -191,6 +191,43 @@ struct HeadState {
 inline bool prune_plan_head(const PruneIn& in, const PrunePlan& pp, bool quant_ok, const HeadState& hd) {
     return prune_plan_needs_quant(in, pp) && quant_ok && hd.present && hd.covers && hd.option != 0 && in.E <= 4;
 }
+// The seed as an estimate pass ("the seed by estimate").  The gate only needs k exactly scored rows that score
+// well, so in the head form the seed launch need not read its rows in full: it streams their lines, heads and inverse norms,
+// ranks them by the decode's estimate (ott_prune.h: prune_score_est_sketchq), and each wave finishes its `keep` best exactly.
+// The gated launch then runs over ALL rows and the final merge takes its lists alone.  Returns the rows the estimate pass
+// covers, 0 = the full seed launch of prune_plan.  Non-zero only
+//   * in the head form with one list entry per lane (k <= 64);
+//   * without a score filter: the best rows by estimate might all fail one, the gate would stay open and the gated launch would
+//     finish every row, where the full seed finds k passing rows;
+//   * from a seed of 131 072 rows (stores from 1 310 720 rows): below, nothing changes.
+// Experiment builds: -DOTT_X_SEED_EST=0 keeps the full seed, -DOTT_X_SEED_EST_DIV=16 covers rows / 16 (0 = the plan's seed),
+// -DOTT_X_SEED_KEEP=4 finishes four rows per wave (0 = min(k, 16)).
+#ifndef OTT_X_SEED_EST
+#define OTT_X_SEED_EST 1
+#endif
+#ifndef OTT_X_SEED_EST_DIV
+#define OTT_X_SEED_EST_DIV 0
+#endif
+#ifndef OTT_X_SEED_KEEP
+#define OTT_X_SEED_KEEP 0
+#endif
+constexpr uint64_t SEED_EST_MIN_ROWS = 131072;
+constexpr uint32_t SEED_EST_KEEP_MAX = 16;
+inline uint64_t prune_plan_seed_est(const PruneIn& in, const PrunePlan& pp, bool head, bool filtered) {
+    // (the seed before prune_plan rounds it up to whole tiles: a tenth of 1 310 656 rows is not yet 131 072)
+    if (!OTT_X_SEED_EST || !head || in.E != 1 || filtered || pp.c == 0 || in.rows_scored / 10 < SEED_EST_MIN_ROWS) return 0;
+    uint64_t rows = pp.seed;
+    if (OTT_X_SEED_EST_DIV > 0) {
+        rows = (in.rows_scored / (uint64_t)(OTT_X_SEED_EST_DIV > 0 ? OTT_X_SEED_EST_DIV : 1) + 63) & ~63ull;
+        if (rows < SEED_EST_MIN_ROWS) rows = SEED_EST_MIN_ROWS;
+    }
+    return rows;
+}
+// rows a wave of the estimate pass finishes exactly
+inline uint32_t prune_seed_keep(uint64_t k) {
+    if (OTT_X_SEED_KEEP > 0) return OTT_X_SEED_KEEP < 64 ? (uint32_t)OTT_X_SEED_KEEP : 64u;
+    return k < SEED_EST_KEEP_MAX ? (uint32_t)k : SEED_EST_KEEP_MAX;
+}
 inline PrunePlan prune_plan_quant_refused(PruneIn in) {
     in.exact_sketch = 0;
     return prune_plan(in);

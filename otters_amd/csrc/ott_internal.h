@@ -582,6 +582,9 @@ struct ExactParams {
     double prune_qe1;
     float prune_qscale, prune_qinv_scale;
     int32_t prune_qsum;
+    // the seed as an estimate pass (head form, ott_exact_plan.h: prune_plan_seed_est): seed_est = 1 runs the launch without a gate —
+    // rows are ranked by the decode's estimate and each wave finishes its seed_keep best exactly; no prune_seed, no prune_tails
+    uint32_t seed_est, seed_keep;
     float qemb[OTT_QEMB_MAX];  // last: the embedded query (kernel arguments are limited to 4 KB)
 };
 // (OTT_QEMB_MAX and the OTT_SKETCH*_MAX_WORDS limits of the sketch forms: ott_exact_plan.h)

@@ -459,6 +459,29 @@ OTT_PRUNE_HD inline float prune_score_bound_sketchq(const float acc[8], float vi
     return S;
 }
 
+// The estimate of the integer decode: the centre of the interval whose ends prune_score_bound_sketchq gives at m = 0 with an
+// all-zero acc — C = a 2^e K, exact in double, rounded to f32 once and scaled like a cosine score.  A SELECTION KEY only (the
+// estimate pass of the pruned sweep's seed ranks rows by it and scores the best ones exactly): nothing rests on its
+// accuracy.  It lies between the two bounds of the same line; on uniform rows it is off by about ||q|| rho / sqrt(dim).  NaN —
+// "do not offer this row" — exactly where that bound is NaN at m = 0: a norm, a, rho or (cosine) a query norm that gives no bound.
+OTT_PRUNE_HD inline float prune_score_est_sketchq(float vinv, float a, float rho, int32_t K, float scale, float qinv, bool cosine) {
+    const float nan = prune_u2f(0x7FC00000u);
+    if (!(vinv >= 0x1p-50f && vinv <= 3.4028234e38f)) return nan;
+    if (!(rho >= 0.0f && rho <= 3.4028234e38f)) return nan;
+    if (!(a >= 0.0f && a <= 3.4028234e38f)) return nan;
+    if (cosine && !(qinv > 0.0f && qinv <= 3.4028234e38f)) return nan;
+    float S = (float)((double)a * (double)scale * (double)K);
+    if (cosine) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        S = __fmul_rn(__fmul_rn(S, qinv), vinv);
+#else
+        volatile float t1 = S * qinv;
+        S = t1 * vinv;
+#endif
+    }
+    return S;
+}
+
 // The sign sketch's own names: the b = 1 case of the functions above (sum v_i kappa_i = sum |v_i| there, sum kappa_i^2 = n, the same
 // operations in the same order: the same bits).
 typedef PruneSketchSumsB PruneSketchSums;
