@@ -22,6 +22,9 @@ pub const OTT_RECOMMEND_MAX_EXAMPLES: u32 = 64; // ott_query_recommend: the most
 pub const OTT_DISCOVER_MAX_PAIRS: u32 = 32; // ott_query_discover: the most context pairs
 pub const OTT_NO_ROW: u64 = u64::MAX; // ott_query_discover: target_row when no stored row is the target
 pub const OTT_RECOMMEND_FILL: u32 = 1; // ott_query_recommend flags bit 0: the negative side follows the positive side
+pub const OTT_RECOMMEND_BEST_SCORE: u32 = 0; // ott_query_recommend_strategy: ott_query_recommend itself
+pub const OTT_RECOMMEND_AVERAGE_VECTOR: u32 = 1; // one ordinary query with the vector mean(positives) [+ mean(positives) - mean(negatives)]
+pub const OTT_RECOMMEND_SUM_SCORES: u32 = 2; // rows ranked by the sum of their scores against the positives minus those against the negatives
 
 // ott_status
 pub const OTT_OK: c_int = 0;
@@ -190,6 +193,7 @@ extern "C" {
     pub fn ott_store_score_rows(s: *mut ott_store, queries: *const f32, nq: u32, metric: u32, ids: *const u64, n_ids: u64, out_scores: *mut f32) -> c_int;
     pub fn ott_query_mmr(s: *mut ott_store, d: *const ott_query_desc, ids: *const u64, n_ids: u64, fetch_k: u64, lambda: f32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, out_values: *mut f32, stats: *mut ott_stats) -> c_int; // ids: null, 0 = no id list; out_values: null or cap floats
     pub fn ott_query_recommend(s: *mut ott_store, d: *const ott_query_desc, positive: *const u64, n_positive: u64, negative: *const u64, n_negative: u64, flags: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, side_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // d.queries null, d.nq 0; side_of_hit: null or cap entries
+    pub fn ott_query_recommend_strategy(s: *mut ott_store, d: *const ott_query_desc, strategy: u32, positive: *const u64, n_positive: u64, negative: *const u64, n_negative: u64, flags: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, side_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // strategy 0 = ott_query_recommend; 1 / 2: flags 0, side_of_hit all 1
     pub fn ott_query_discover(s: *mut ott_store, d: *const ott_query_desc, target_row: u64, positive: *const u64, negative: *const u64, n_pairs: u64, min_wins: u32, flags: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, wins_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // target: d.queries with d.nq 1, or target_row, or neither (context search); wins_of_hit: null or cap entries
     pub fn ott_store_set_groups(s: *mut ott_store, gid_host: *const c_void, n: u64, n_groups: u32) -> c_int; // gid_host: n u32
     pub fn ott_store_clear_groups(s: *mut ott_store) -> c_int;

@@ -459,6 +459,33 @@ int ott_query_recommend(ott_store* s, const ott_query_desc* d, const uint64_t* p
                         uint64_t n_negative, uint32_t flags, ott_hit* out, uint64_t cap, uint64_t* n_out,
                         uint32_t* side_of_hit /* may be NULL; cap entries */, ott_stats* stats);
 
+/* Recommend by example rows with a STRATEGY (an extension; Qdrant's three recommend strategies).  OTT_RECOMMEND_BEST_SCORE is
+ * ott_query_recommend itself: the same arguments, results, refusals and messages (they name ott_query_recommend).  For the other
+ * two the examples are checked and laid out as there — slots e_0 .. e_{m-1}: the distinct positives in first-occurrence order, then
+ * the distinct negatives, at most OTT_RECOMMEND_MAX_EXAMPLES; a deleted row may be an example; an example is never a hit —,
+ * d->queries must be NULL, d->nq 0, d->mode MERGED and flags 0 (OTT_RECOMMEND_FILL belongs to best_score).  chunk_mask, the caller's
+ * row mask or the evaluated device mask and the live mask of deleted rows all apply.  side_of_hit[i], if given, is 1 for every hit.
+ * SUM_SCORES: with the pair score P[e][r] of ott_query_recommend, S(r) starts as P[e_0][r] itself (a -0.0 stays -0.0); for i = 1 ..
+ * m - 1 in slot order S = S + P[e_i][r] for a positive e_i, S = S - P[e_i][r] for a negative one — each step one f32 operation,
+ * round to nearest, no contraction; a NaN pair score or inf - inf makes S NaN.  CANDIDATES: rows that survive the masks, are no
+ * example, have an S that is not NaN and passes the score filter.  ORDER: ord(S) under d->take descending, then the lower row; cut
+ * at k_eff = min(k, ott_store_len); always this canonical order, whatever option "tie_order" says.  OUTPUT: {base_offset + row, S,
+ * 0}.  OTT_PATH_MFMA is refused; AUTO and EXACT take ott_query_recommend's sweep (four examples per pass, the running sum in the
+ * same 8-byte state) and never build or wait for a plane.  stats as ott_query_recommend counts them.
+ * AVERAGE_VECTOR: q[i] = mp (no negatives) or (mp + mp) - mn, with sp = row(p_0)[i], sp = sp + row(p_j)[i] in slot order, mp = sp /
+ * (float)n_pos (one correctly rounded f32 division), mn likewise over the negatives; stored f32 values, nothing normalised.  The
+ * vector is built on the device and comes back once (dim floats: ott_query's host side computes the query norm).  The hits are
+ * EXACTLY ott_query's for d with queries = q, nq = 1 and one more row mask, every bit set but the examples': the same path choice
+ * (AUTO / EXACT / MFMA as ott_query treats them for the metric), options ("tie_order" included), stats and k_eff.
+ * Refused on the host before any device work, with nothing written, in messages that name ott_query_recommend_strategy: an unknown
+ * strategy, nonzero flags, and what ott_query_recommend refuses for its arguments (OTT_ERR_INVALID); OTT_MODE_PER_QUERY,
+ * OTT_PATH_MFMA with SUM_SCORES, a multi-GPU store, a store of more than 2^32 - 16 rows (OTT_ERR_UNSUPPORTED).  Takes the store
+ * shared, like ott_query_recommend. */
+typedef enum { OTT_RECOMMEND_BEST_SCORE = 0, OTT_RECOMMEND_AVERAGE_VECTOR = 1, OTT_RECOMMEND_SUM_SCORES = 2 } ott_recommend_strategy;
+int ott_query_recommend_strategy(ott_store* s, const ott_query_desc* d, uint32_t strategy, const uint64_t* positive,
+                                 uint64_t n_positive, const uint64_t* negative, uint64_t n_negative, uint32_t flags, ott_hit* out,
+                                 uint64_t cap, uint64_t* n_out, uint32_t* side_of_hit /* may be NULL */, ott_stats* stats);
+
 /* Discovery and context search (an extension; Qdrant's Discovery API): rank the rows by CONTEXT PAIRS of stored rows, each a
  * (positive, negative), and optionally by a TARGET.  Pair i is (positive[i], negative[i]), i < n_pairs, 1 <= n_pairs <=
  * OTT_DISCOVER_MAX_PAIRS; ids are counted from the store's first row like ott_query_recommend's (not shifted by base_offset).  A row

@@ -5,8 +5,8 @@ and error strings) over libotters_hip.so: the corpus lives row-major in HBM, sco
 score filtering and top-k run as hand-written HIP kernels.  No CPU fallback.
 """
 from ._native import OttersError  # noqa: F401
-from .vec import (Cmp, DiscoverPlan, DiscoverResult, MaxSimBatchPlan, Metric, Mode, Path, QueryBatch, RecommendPlan, SearchResult, TakeType,  # noqa: F401
-                  VecQueryPlan, VecStore)
+from .vec import (Cmp, DiscoverPlan, DiscoverResult, MaxSimBatchPlan, Metric, Mode, Path, QueryBatch, RecommendPlan, RecommendStrategy, SearchResult,  # noqa: F401
+                  TakeType, VecQueryPlan, VecStore)
 
 from .col import Column, ColumnError, DataType  # noqa: F401,E402
 from .expr import CmpOp, CompiledFilter, Expr, ExprError, col, lit  # noqa: F401,E402
@@ -15,5 +15,5 @@ from .meta import (MetaBuildStats, MetaQueryPlan, MetaQueryResults, MetaQuerySta
 
 __all__ = ["Column", "ColumnError", "DataType", "CmpOp", "CompiledFilter", "Expr", "ExprError", "col", "lit",
            "MetaBuildStats", "MetaQueryPlan", "MetaQueryResults", "MetaQueryStats", "MetaStore", "MetaStoreBuilder",
-           "OttersError", "Cmp", "DiscoverPlan", "DiscoverResult", "MaxSimBatchPlan", "Metric", "Mode", "Path", "QueryBatch", "RecommendPlan", "SearchResult", "TakeType",
+           "OttersError", "Cmp", "DiscoverPlan", "DiscoverResult", "MaxSimBatchPlan", "Metric", "Mode", "Path", "QueryBatch", "RecommendPlan", "RecommendStrategy", "SearchResult", "TakeType",
            "VecQueryPlan", "VecStore"]

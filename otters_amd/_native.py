@@ -155,6 +155,7 @@ def lib() -> C.CDLL:
         "ott_store_score_rows": (i32, [vp, vp, u32, u32, vp, u64, vp]),
         "ott_query_mmr": (i32, [vp, vp, vp, u64, u64, C.c_float, vp, u64, vp, vp, vp, vp]),
         "ott_query_recommend": (i32, [vp, vp, vp, u64, vp, u64, u32, vp, u64, vp, vp, vp]),
+        "ott_query_recommend_strategy": (i32, [vp, vp, u32, vp, u64, vp, u64, u32, vp, u64, vp, vp, vp]),
         "ott_query_discover": (i32, [vp, vp, u64, vp, vp, u64, u32, u32, vp, u64, vp, vp, vp]),
         "ott_store_set_groups": (i32, [vp, vp, u64, u32]),
         "ott_store_clear_groups": (i32, [vp]),

@@ -25,6 +25,8 @@
 // when OTT_RECOMMEND_FILL is set, negatives exist and side 1 returned fewer than k_eff: one more host wait in that case alone.
 // When that round can run but does not, the state table is cleared by a memset behind the first round.
 // Examples per pass: ott_sweep_dev.h; the epilogue adds two ordinals (profiles/recommend/resource_usage.txt: no scratch).
+// ott_query_recommend_strategy adds Qdrant's other two strategies below: sum_scores, the same sweep with a running
+// f32 sum in the state, and average_vector, one ordinary query with a vector built from the examples' rows; strategy 0 is the call above.
 #include <string.h>
 
 #include <algorithm>
@@ -112,7 +114,89 @@ __global__ __launch_bounds__(256) void recommend_keys_kernel(uint2* state, uint3
     keys[r] = ((unsigned long long)o << 32) | (uint32_t)(~(uint32_t)r);
 }
 
+// ---- the sum_scores and average_vector strategies (ott_query_recommend_strategy) ---------------------------------------
+//   recommend_sum_sweep_kernel  sweep_tiles and this epilogue per row: the running sum S of the row's pair scores, slot by slot — the
+//                               first slot's score itself, then one __fadd_rn per positive slot and one __fsub_rn per negative one —
+//                               kept as {bits of S, REC_SUM_MARK} in the row's 8-byte state.  The first pass does not load it; a later
+//                               pass loads S, continues the chain over its up to four slots and streams the state back.
+//   recommend_sum_keys_kernel   one lane per row: marked, S not NaN, the filter holds for S -> key = ord_of(S) << 32 | ~row.  It reads
+//                               the state last and leaves it zeroed.
+//   recommend_average_kernel    one thread per dim: the examples' stored values summed in slot order, one division per side, and
+//                               (mp + mp) - mn with negatives, into the context's id-mask scratch behind the mask; the first threads
+//                               clear the examples' bits of that mask (filled with ones on the stream before).
+template <int MK, int NQ>
+__global__ __launch_bounds__(64 * SW_WAVES) void recommend_sum_sweep_kernel(RecommendParams p) {
+    sweep_tiles<MK, NQ>(p, [&](uint64_t my_row, bool valid, uint32_t, const float (&sc)[NQ], uint32_t nq_here) {
+        if (!valid) return;
+        uint2* slot = p.state + my_row;
+        float S = sc[0];  // slot 0 is a positive: the chain starts as its score itself (a -0.0 stays -0.0)
+        if (p.q0 != 0) {  // (wave-uniform: only the first pass starts the chain)
+            const float cur = __uint_as_float(slot->x);
+            S = rec_slot_positive(p.q0, p.first_neg) ? __fadd_rn(cur, sc[0]) : __fsub_rn(cur, sc[0]);
+        }
+#pragma unroll
+        for (int q = 1; q < NQ; q++)
+            if ((uint32_t)q < nq_here) S = rec_slot_positive(p.q0 + (uint32_t)q, p.first_neg) ? __fadd_rn(S, sc[q]) : __fsub_rn(S, sc[q]);  // (wave-uniform)
+        typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+        v2u v;
+        v.x = __float_as_uint(S);
+        v.y = REC_SUM_MARK;
+        __builtin_nontemporal_store(v, reinterpret_cast<v2u*>(slot));  // streamed, as recommend_sweep_kernel's
+    });
+}
+
+// One lane per row.  keys: [n] 8-byte keys, zero when the kernel starts (d_gtable's protocol): only candidates are written.
+__global__ __launch_bounds__(256) void recommend_sum_keys_kernel(uint2* state, uint32_t n, uint32_t take_max, uint32_t cmp, float thr, unsigned long long* keys) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint2 st = state[r];
+    if (st.y == 0) return;  // never written, or an example's cleared slot: {0, 0}
+    state[r] = make_uint2(0u, 0u);
+    const float S = __uint_as_float(st.x);
+    if (S != S || !cmp_holds(S, cmp, thr)) return;
+    keys[r] = ((unsigned long long)ord_of(S, take_max != 0) << 32) | (uint32_t)(~(uint32_t)r);
+}
+
+struct RecommendAverageParams {
+    const float* rows;
+    float* q;                  // [dim]
+    unsigned long long* mask;  // [ceil(rows / 64)] words of ones
+    uint32_t ld, dim, n, first_neg;
+    uint32_t ex[REC_MAX_EXAMPLES];  // the examples' rows, every one below the store's length (checked on the host)
+};
+
+__global__ __launch_bounds__(256) void recommend_average_kernel(RecommendAverageParams p) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < p.n) atomicAnd(p.mask + (p.ex[i] >> 6), ~(1ull << (p.ex[i] & 63)));  // (at most 64: all in the first workgroup)
+    if (i >= p.dim) return;
+    float sp = p.rows[(uint64_t)p.ex[0] * p.ld + i];
+    for (uint32_t e = 1; e < p.first_neg; e++) sp = __fadd_rn(sp, p.rows[(uint64_t)p.ex[e] * p.ld + i]);
+    float q = __fdiv_rn(sp, (float)p.first_neg);  // correctly rounded, not a multiply by a reciprocal
+    if (p.first_neg < p.n) {
+        float sn = p.rows[(uint64_t)p.ex[p.first_neg] * p.ld + i];
+        for (uint32_t e = p.first_neg + 1; e < p.n; e++) sn = __fadd_rn(sn, p.rows[(uint64_t)p.ex[e] * p.ld + i]);
+        q = __fsub_rn(__fadd_rn(q, q), __fdiv_rn(sn, (float)(p.n - p.first_neg)));
+    }
+    p.q[i] = q;
+}
+
 namespace {
+
+template <int MK>
+int launch_sum_sweep_mk(ott_store* s, const RecommendParams& p, uint32_t nq_tile, uint32_t grid) {
+    if (nq_tile == 1) hipLaunchKernelGGL((recommend_sum_sweep_kernel<MK, 1>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
+    else hipLaunchKernelGGL((recommend_sum_sweep_kernel<MK, (int)SW_NQ>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+
+int launch_sum_sweep(ott_store* s, const RecommendParams& p, uint32_t nq_tile, uint32_t grid) {
+    switch (metric_kind(p.metric)) {
+        case MK_L2: return launch_sum_sweep_mk<MK_L2>(s, p, nq_tile, grid);
+        case MK_L1: return launch_sum_sweep_mk<MK_L1>(s, p, nq_tile, grid);
+        default: return launch_sum_sweep_mk<MK_DOT>(s, p, nq_tile, grid);
+    }
+}
 
 template <int MK>
 int launch_sweep_mk(ott_store* s, const RecommendParams& p, uint32_t nq_tile, uint32_t grid) {
@@ -255,6 +339,126 @@ int run_recommend(ott_store* s, const ott_query_desc* d, const RecExamples& ex, 
     return OTT_OK;
 }
 
+int refuse_strategy(RecRefusal r, uint64_t id = 0, uint64_t len = 0) {
+    const int code = rec_refusal_is_invalid(r) ? OTT_ERR_INVALID : OTT_ERR_UNSUPPORTED;
+    if (r == REC_BAD_ID) return fail(code, "ott_query_recommend_strategy: example id " + std::to_string(id) + " is not below the store's length " + std::to_string(len));
+    if (r == REC_BOTH_SIDES) return fail(code, "ott_query_recommend_strategy: row " + std::to_string(id) + " is listed as both a positive and a negative example");
+    return fail(code, rec_strategy_text(r));
+}
+
+// sum_scores on a context whose `mu` the caller holds (and the owner's `rw`, shared): run_recommend with the running sum in the
+// state table and one round.  k_eff = min(k, rows) >= 1; every example < s->n.
+int run_recommend_sum(ott_store* s, const ott_query_desc* d, const RecExamples& ex, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint32_t* side_of_hit,
+                      ott_stats* stats_out) {
+    int rc;
+    OTT_HIP(use_device(s));
+    const uint64_t t0 = now_ns();
+    ott_stats st;
+    const uint32_t n = (uint32_t)s->n;
+    RecommendParams p{};
+    uint32_t grid = 0;
+    if ((rc = sweep_prologue(s, d, nullptr, ex.n, &st, &p, &grid))) return rc;
+    uint64_t n1 = 0;
+    if (grid != 0) {
+        st.bytes_scanned = (uint64_t)st.passes * (st.vectors_compared / ex.n) * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));  // (no group id is read)
+        // the states are left zeroed by the keys kernel, the keys by the top-k's select / compact kernel
+        if ((rc = ensure_zeroed(s, s->d_rectable, s->rectable_clean, rec_state_bytes(n)))) return rc;
+        if ((rc = ensure_zeroed(s, s->d_gtable, s->gtable_clean, rec_key_bytes(n)))) return rc;
+        unsigned long long* keys = (unsigned long long*)s->d_gtable.p;
+        p.gid = nullptr;  // (a store with groups has ids: this sweep does not read them)
+        p.state = (uint2*)s->d_rectable.p;
+        p.first_neg = ex.first_neg;
+        const bool take_max = p.take_max != 0;
+
+        RecommendGatherParams gp;
+        memset(&gp, 0, sizeof(gp));
+        gp.rows = s->d_rows;
+        gp.inv = s->d_inv;
+        gp.queries = (float*)s->d_queries.p;
+        gp.qinv = (float*)((char*)s->d_queries.p + s->in_off_qinv);
+        gp.state = p.state;
+        gp.ld = s->ld;
+        gp.dim = s->dim;
+        gp.dimq = s->dimq;
+        gp.n = ex.n;
+        memcpy(gp.ex, ex.rows, sizeof(uint32_t) * ex.n);
+
+        GroupTopK tk;
+        tk.n_groups = n;
+        tk.nq = 1;
+        tk.k = k_eff;
+        tk.take_max = take_max;
+        tk.also_clean = &s->rectable_clean;
+        if ((rc = tk.prepare(s, nullptr))) return rc;
+        const bool timing = stats_out != nullptr;
+        hipLaunchKernelGGL(recommend_gather_kernel, dim3(ex.n), dim3(256), 0, s->stream, gp);
+        OTT_HIP(hipGetLastError());
+        if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
+        const uint32_t tile = rec_tile(ex.n);
+        for (uint32_t ps = 0; ps < st.passes; ps++) {
+            p.q0 = ps * tile;
+            if ((rc = launch_sum_sweep(s, p, tile, grid))) return rc;
+        }
+        hipLaunchKernelGGL(recommend_clear_kernel, dim3(1), dim3(64), 0, s->stream, gp);
+        OTT_HIP(hipGetLastError());
+        hipLaunchKernelGGL(recommend_sum_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s->stream, p.state, n, take_max ? 1u : 0u, (uint32_t)d->filter_cmp, d->filter_thr, keys);
+        OTT_HIP(hipGetLastError());
+        if ((rc = tk.pass(s, keys, 0, 1))) return rc;
+        if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
+        if ((rc = tk.finish(s, timing, out, &n1, nullptr))) return rc;
+        if (timing) read_exact_events(s, &st);
+        if (n1 > k_eff) return fail(OTT_ERR_HIP, "ott_query_recommend_strategy: the top-k returned more hits than k");
+    }
+    if (side_of_hit)
+        for (uint64_t i = 0; i < n1; i++) side_of_hit[i] = 1u;
+    if (n_out) *n_out = n1;
+    st.total_ns = now_ns() - t0;
+    if (stats_out) *stats_out = st;
+    return OTT_OK;
+}
+
+// average_vector on a context whose `mu` the caller holds: the vector and the mask of every row but the examples are made on the
+// device, the vector comes back (ott_query's host side computes its norm), and the query is ott_query's with that mask joined where
+// every row mask reaches the kernels (run_ids_as_mask's route, ott_gather.hip).  Every example < s->n; s->n >= 1.
+int run_recommend_average(ott_store* s, const ott_query_desc* d, const RecExamples& ex, ott_hit* out, uint64_t cap, uint64_t* n_out, uint32_t* side_of_hit,
+                          ott_stats* stats_out) {
+    int rc;
+    OTT_HIP(use_device(s));
+    const uint64_t words = rec_mask_words(s->n);
+    if ((rc = s->d_idmask.ensure(rec_mask_bytes(s->n, s->dim)))) return rc;
+    uint64_t* d_words = (uint64_t*)s->d_idmask.p;
+    RecommendAverageParams ap;
+    memset(&ap, 0, sizeof(ap));
+    ap.rows = s->d_rows;
+    ap.q = (float*)(d_words + 2 * words);
+    ap.mask = (unsigned long long*)d_words;
+    ap.ld = s->ld;
+    ap.dim = s->dim;
+    ap.n = ex.n;
+    ap.first_neg = ex.first_neg;
+    memcpy(ap.ex, ex.rows, sizeof(uint32_t) * ex.n);
+    OTT_HIP(hipMemsetAsync(d_words, 0xFF, (size_t)words * 8, s->stream));
+    hipLaunchKernelGGL(recommend_average_kernel, dim3((std::max(s->dim, ex.n) + 255) / 256), dim3(256), 0, s->stream, ap);
+    OTT_HIP(hipGetLastError());
+    std::vector<float> q(s->dim);
+    OTT_HIP(hipMemcpyAsync(q.data(), ap.q, (size_t)s->dim * 4, hipMemcpyDeviceToHost, s->stream));
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    ott_query_desc d2 = *d;
+    d2.queries = q.data();
+    d2.nq = 1;
+    struct IdMaskGuard {
+        ott_store* c;
+        ~IdMaskGuard() { c->cur_idmask = nullptr; }
+    } guard{s};
+    s->cur_idmask = d_words;
+    uint64_t n1 = 0;
+    if ((rc = query_on(s, &d2, out, nullptr, cap, &n1, nullptr, nullptr, stats_out))) return rc;
+    if (side_of_hit)
+        for (uint64_t i = 0; i < n1; i++) side_of_hit[i] = 1u;
+    if (n_out) *n_out = n1;
+    return OTT_OK;
+}
+
 }  // namespace
 
 }  // namespace ott
@@ -299,6 +503,48 @@ int ott_query_recommend(ott_store* s, const ott_query_desc* d, const uint64_t* p
     if (k_eff == 0) return OTT_OK;
     ott_store* ctx = ctx_acquire(s);
     rc = run_recommend(ctx, d, ex, flags, k_eff, out, n_out, side_of_hit, stats);
+    ctx_release(ctx);
+    return rc;
+}
+
+int ott_query_recommend_strategy(ott_store* s, const ott_query_desc* d, uint32_t strategy, const uint64_t* positive, uint64_t n_positive, const uint64_t* negative,
+                                 uint64_t n_negative, uint32_t flags, ott_hit* out, uint64_t cap, uint64_t* n_out, uint32_t* side_of_hit, ott_stats* stats) {
+    if (strategy == REC_BEST_SCORE) return ott_query_recommend(s, d, positive, n_positive, negative, n_negative, flags, out, cap, n_out, side_of_hit, stats);
+    // as ott_query_recommend: what the arguments and the descriptor alone decide comes first
+    if (!rec_strategy_known(strategy)) return refuse_strategy(REC_BAD_STRATEGY);
+    if (!d) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: desc is NULL");
+    RecRefusal why = rec_strategy_check_args(strategy, positive == nullptr, n_positive, negative == nullptr, n_negative, flags, d->nq != 0 || d->queries != nullptr,
+                                             d->mode == OTT_MODE_PER_QUERY, d->path == OTT_PATH_MFMA, d->metric == OTT_METRIC_MANHATTAN);
+    if (why != REC_OK) return refuse_strategy(why);
+    if (d->metric > OTT_METRIC_MANHATTAN) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: unknown metric");
+    if (d->take > OTT_TAKE_MAX) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: unknown take type");
+    if (d->filter_cmp > OTT_CMP_EQ) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: unknown filter comparator");
+    if (d->mode > OTT_MODE_PER_QUERY) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: unknown mode");
+    if (d->path > OTT_PATH_MFMA) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: unknown path");
+    if (!s) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: store is NULL");
+    const uint64_t len = ott_store_len(s);
+    if ((why = rec_check_store(s->multi != nullptr, len)) != REC_OK) return refuse_strategy(why);
+    if (d->use_device_row_mask && s->evalmask_bits == 0 && s->n)
+        return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: use_device_row_mask set but ott_store_eval_row_mask was not called");
+    RecExamples ex;
+    uint64_t bad = 0;
+    if ((why = rec_examples(positive, n_positive, negative, n_negative, len, &ex, &bad)) != REC_OK) return refuse_strategy(why, bad, len);
+    if ((why = rec_check_out(rec_k_eff(d->k, len), cap, out == nullptr)) != REC_OK) return refuse_strategy(why);
+    ott::host::SharedLock rd;  // the corpus cannot change while this query runs
+    int rc;
+    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
+    // what the checks above read without the lock is read again under it (ott_query_recommend)
+    if ((why = rec_check_store(false, s->n)) != REC_OK) return refuse_strategy(why);
+    for (uint32_t e = 0; e < ex.n; e++)
+        if (ex.rows[e] >= s->n) return refuse_strategy(REC_BAD_ID, ex.rows[e], s->n);
+    const uint64_t k_eff = rec_k_eff(d->k, s->n);
+    if ((why = rec_check_out(k_eff, cap, out == nullptr)) != REC_OK) return refuse_strategy(why);
+    if (n_out) *n_out = 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (k_eff == 0) return OTT_OK;
+    ott_store* ctx = ctx_acquire(s);
+    if (strategy == REC_SUM_SCORES) rc = run_recommend_sum(ctx, d, ex, k_eff, out, n_out, side_of_hit, stats);
+    else rc = run_recommend_average(ctx, d, ex, out, cap, n_out, side_of_hit, stats);
     ctx_release(ctx);
     return rc;
 }

@@ -1,7 +1,8 @@
 // ott_recommend_plan.h — what the host decides for ott_query_recommend (ott_recommend.hip) before it launches
 // anything: the refusals, the example layout (distinct positives, then distinct negatives), the passes of the sweep, k_eff, whether
-// a second top-k round can and does run, and the bytes of the context's scratch.  HIP-free: tests/test_recommend_cpu.py compiles it
-// with the host compiler under AddressSanitizer and walks it.
+// a second top-k round can and does run, and the bytes of the context's scratch; and, at the end, what ott_query_recommend_strategy
+//  adds for the strategies sum_scores and average_vector.  HIP-free: tests/test_recommend_cpu.py and
+// tests/test_recommend_strategy_cpu.py compile it with the host compiler under AddressSanitizer and walk it.
 #pragma once
 
 #include <stddef.h>
@@ -30,8 +31,13 @@ enum RecRefusal {
     REC_BOTH_SIDES,    // OTT_ERR_INVALID: a row listed as both positive and negative
     REC_SMALL_CAP,     // OTT_ERR_INVALID: cap < k_eff
     REC_NULL_OUT,      // OTT_ERR_INVALID: out == NULL with cap > 0
+    // ott_query_recommend_strategy alone
+    REC_BAD_STRATEGY,  // OTT_ERR_INVALID: no such strategy
+    REC_MFMA_L1,       // OTT_ERR_UNSUPPORTED: average_vector on OTT_PATH_MFMA with the Manhattan metric (ott_query's refusal)
 };
-inline bool rec_refusal_is_invalid(RecRefusal r) { return r != REC_OK && !(r == REC_PER_QUERY || r == REC_MFMA || r == REC_MULTI_GPU || r == REC_TOO_MANY_ROWS); }
+inline bool rec_refusal_is_invalid(RecRefusal r) {
+    return r != REC_OK && !(r == REC_PER_QUERY || r == REC_MFMA || r == REC_MULTI_GPU || r == REC_TOO_MANY_ROWS || r == REC_MFMA_L1);
+}
 
 // what the lists' shape, the flags and the descriptor alone decide (no store is looked at)
 inline RecRefusal rec_check_args(bool positive_null, uint64_t n_positive, bool negative_null, uint64_t n_negative, uint32_t flags, bool has_queries, bool per_query,
@@ -106,5 +112,63 @@ inline uint64_t rec_second_k(bool fill_possible, uint64_t k_eff, uint64_t n_firs
 // the context's scratch: the rows' {bp, bn} states (the key table is grouped search's, under its own protocol)
 inline size_t rec_state_bytes(uint64_t len) { return (size_t)len * 8; }
 inline size_t rec_key_bytes(uint64_t len) { return (size_t)len * 8; }
+
+// ---- strategies (ott_query_recommend_strategy) -------------------------------------------------------------------------
+constexpr uint32_t REC_BEST_SCORE = 0;      // OTT_RECOMMEND_BEST_SCORE: ott_query_recommend itself
+constexpr uint32_t REC_AVERAGE_VECTOR = 1;  // OTT_RECOMMEND_AVERAGE_VECTOR: one ordinary query with a vector built from the examples
+constexpr uint32_t REC_SUM_SCORES = 2;      // OTT_RECOMMEND_SUM_SCORES: the sweep with a running f32 sum per row
+constexpr uint32_t REC_SUM_MARK = 1u;       // the state's second word once a lane wrote the row: S's bits alone may be 0
+
+inline bool rec_strategy_known(uint32_t strategy) { return strategy <= REC_SUM_SCORES; }
+// the flags a strategy takes: best_score its fill bit, the other two none
+inline uint32_t rec_strategy_flags(uint32_t strategy) { return strategy == REC_BEST_SCORE ? REC_FILL : 0u; }
+// the MFMA path: never for the sweeps; average_vector is ott_query's, which does not score Manhattan there
+inline RecRefusal rec_strategy_mfma(uint32_t strategy, bool mfma, bool manhattan) {
+    if (!mfma) return REC_OK;
+    if (strategy == REC_AVERAGE_VECTOR) return manhattan ? REC_MFMA_L1 : REC_OK;
+    return REC_MFMA;
+}
+// what the strategy, the lists' shape, the flags and the descriptor alone decide for average_vector and sum_scores, in the order
+// the call refuses (best_score is handed to ott_query_recommend whole: rec_check_args)
+inline RecRefusal rec_strategy_check_args(uint32_t strategy, bool positive_null, uint64_t n_positive, bool negative_null, uint64_t n_negative, uint32_t flags,
+                                          bool has_queries, bool per_query, bool mfma, bool manhattan) {
+    if (!rec_strategy_known(strategy)) return REC_BAD_STRATEGY;
+    if (n_positive == 0) return REC_NO_POSITIVE;
+    if (positive_null || (negative_null && n_negative != 0)) return REC_NULL_LIST;
+    if (flags & ~rec_strategy_flags(strategy)) return REC_BAD_FLAGS;
+    if (has_queries) return REC_HAS_QUERIES;
+    if (per_query) return REC_PER_QUERY;
+    return rec_strategy_mfma(strategy, mfma, manhattan);
+}
+// the refusals' texts (the two with an id in them are put together by the caller)
+inline const char* rec_strategy_text(RecRefusal r) {
+    switch (r) {
+        case REC_BAD_STRATEGY: return "ott_query_recommend_strategy: unknown strategy";
+        case REC_NO_POSITIVE: return "ott_query_recommend_strategy: at least one positive example is needed";
+        case REC_NULL_LIST: return "ott_query_recommend_strategy: an example list is NULL";
+        case REC_BAD_FLAGS: return "ott_query_recommend_strategy: flags must be 0 (OTT_RECOMMEND_FILL belongs to best_score)";
+        case REC_HAS_QUERIES: return "ott_query_recommend_strategy: the examples are the queries; d->queries must be NULL and d->nq 0";
+        case REC_PER_QUERY: return "ott_query_recommend_strategy: the examples make ONE query; PER_QUERY is not served";
+        case REC_MFMA: return "ott_query_recommend_strategy: the MFMA path does not serve sum_scores; use path AUTO or EXACT";
+        case REC_MFMA_L1: return "ott_query_recommend_strategy: the MFMA path does not score the Manhattan metric; use path AUTO or EXACT";
+        case REC_MULTI_GPU: return "ott_query_recommend_strategy: a multi-GPU store is not served (the examples' rows lie on different shards)";
+        case REC_TOO_MANY_ROWS: return "ott_query_recommend_strategy: a store of more than 2^32 - 16 rows is not served";
+        case REC_TOO_MANY: return "ott_query_recommend_strategy: more than OTT_RECOMMEND_MAX_EXAMPLES (64) distinct examples";
+        case REC_SMALL_CAP: return "ott_query_recommend_strategy: output capacity is smaller than min(k, rows)";
+        case REC_NULL_OUT: return "ott_query_recommend_strategy: out is NULL";
+        default: return "";
+    }
+}
+// sum_scores: slot e adds its pair score when it is a positive, subtracts it when a negative
+constexpr bool rec_slot_positive(uint32_t e, uint32_t first_neg) { return e < first_neg; }  // (constexpr: the sweep kernel calls it too)
+// average_vector: the context's id-mask scratch [every row but the examples | that & the caller's mask (compose_row_mask) | the vector]
+inline uint64_t rec_mask_words(uint64_t len) { return (len + 63) / 64; }
+inline size_t rec_mask_bytes(uint64_t len, uint32_t dim) { return (size_t)rec_mask_words(len) * 16 + (size_t)dim * 4; }
+// ... its first block on the host, as the device leaves it: ones (past the store's end too, like the live mask), the examples' bits cleared
+inline void rec_mask_fill(const RecExamples& ex, uint64_t len, uint64_t* words) {
+    for (uint64_t w = 0; w < rec_mask_words(len); w++) words[w] = ~0ull;
+    for (uint32_t e = 0; e < ex.n; e++)
+        if (ex.rows[e] < len) words[ex.rows[e] >> 6] &= ~(1ull << (ex.rows[e] & 63));
+}
 
 }  // namespace ott

@@ -1,5 +1,5 @@
 // ott_sweep_dev.h — the streaming tile loop of the two sweeps over grouped rows: group_sweep_kernel (ott_group.hip) and
-// maxsim_sweep_kernel (ott_maxsim.hip), and of recommend_sweep_kernel (ott_recommend.hip), which reads no group ids.
+// maxsim_sweep_kernel (ott_maxsim.hip), and of recommend_sweep_kernel and recommend_sum_sweep_kernel (ott_recommend.hip), which read no group ids.
 // exact_kernel's streaming geometry with every variant stripped: lane = row, 64-row tiles per wave, 128-B stages through the swizzled LDS tile, queries through the constant address space, a persistent grid over the run lists
 // of surviving chunks, the scoring terms of ott_exact_dev.h, so the bits are the oracle's.  A kernel is sweep_tiles plus its epilogue;
 // what guards the loop against reading past the allocation (lsl4, the clamp to the tile's last row) exists here and nowhere else.

@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import GROUP_SIZE_MAX, Cmp, DiscoverPlan, Metric, Mode, Path, RecommendPlan, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type, mmr_args
+from .vec import GROUP_SIZE_MAX, Cmp, DiscoverPlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type, mmr_args
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -479,10 +479,10 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
         (positive, negative) row id pairs counted from the store's first row."""
         return MetaDiscoverPlan(self, context, target, target_row, metric)
 
-    def recommend(self, positive, negative=(), metric: Metric = Metric.Cosine) -> "MetaRecommendPlan":
-        """Recommend by example rows (VecStore.recommend; ott_query_recommend) with a meta_filter: `positive` and `negative` are row
-        ids of this store."""
-        return MetaRecommendPlan(self, positive, negative, metric)
+    def recommend(self, positive, negative=(), metric: Metric = Metric.Cosine, strategy: RecommendStrategy = RecommendStrategy.BestScore) -> "MetaRecommendPlan":
+        """Recommend by example rows (VecStore.recommend; ott_query_recommend, or ott_query_recommend_strategy for another `strategy`
+        than BestScore) with a meta_filter: `positive` and `negative` are row ids of this store."""
+        return MetaRecommendPlan(self, positive, negative, metric, strategy)
 
     # -- zonemap prune: build_chunk_mask_for_plan, src/meta.rs:407-428 ----------------------------------
     def build_chunk_mask_for_plan(self, compiled: CompiledFilter) -> np.ndarray:
@@ -888,15 +888,16 @@ class MetaQueryPlan:  # src/meta.rs:579-830
 
 class MetaRecommendPlan:
     """Recommend by example rows over a MetaStore (MetaStore.recommend; VecStore.recommend's contract): meta_filter prunes chunks
-    by their zone maps and masks rows on the device, as for MetaQueryPlan.mmr; vec_filter acts on a row's best positive score.  An
+    by their zone maps and masks rows on the device, as for MetaQueryPlan.mmr; vec_filter acts on a row's best positive score (the strategy
+    BestScore), on the sum S (SumScores) or on the query's score (AverageVector), as RecommendPlan.filter.  An
     example need not pass the filter: stored data is read.  Errors surface at collect()."""
 
-    def __init__(self, store: MetaStore, positive, negative, metric: Metric):
+    def __init__(self, store: MetaStore, positive, negative, metric: Metric, strategy: RecommendStrategy = RecommendStrategy.BestScore):
         self.store = store
         self.metric = Metric(metric)
         self._meta_filter: Optional[CompiledFilter] = None
         self.meta_error: Optional[str] = None
-        self._plan = RecommendPlan(store._store, positive, negative, metric)
+        self._plan = RecommendPlan(store._store, positive, negative, metric, strategy)
 
     def meta_filter(self, expr: Expr) -> "MetaRecommendPlan":
         try:

@@ -636,24 +636,30 @@ RECOMMEND_MAX_EXAMPLES = 64  # include/otters_hip.h: OTT_RECOMMEND_MAX_EXAMPLES
 RECOMMEND_FILL = 1           # include/otters_hip.h: OTT_RECOMMEND_FILL
 
 
-def recommend_examples(positive, negative, n_rows: int):
+class RecommendStrategy(enum.IntEnum):  # include/otters_hip.h: ott_recommend_strategy (Qdrant's three recommend strategies)
+    BestScore = 0      # ott_query_recommend: a row's best positive score against its best negative one
+    AverageVector = 1  # one ordinary query with mean(positives) [+ mean(positives) - mean(negatives)]
+    SumScores = 2      # the sum of a row's scores against the positives minus those against the negatives
+
+
+def recommend_examples(positive, negative, n_rows: int, who: str = "ott_query_recommend"):
     """recommend()'s example lists checked as ott_query_recommend checks them, with its messages: (uint64 positives, uint64
-    negatives) as listed.  Pure host logic."""
+    negatives) as listed.  `who`: the call the messages name (ott_query_recommend_strategy for the other strategies).  Pure host logic."""
     pos, neg = as_row_ids(positive), as_row_ids(negative)
     if pos.size == 0:
-        raise OttersError("ott_query_recommend: at least one positive example is needed")
+        raise OttersError(f"{who}: at least one positive example is needed")
     # the library's walk (ott_recommend_plan.h: rec_examples), id by id, the positives first: the first fault it meets is the one named
     seen_pos, seen = set(), set()
     for ids, is_neg in ((pos, False), (neg, True)):
         for i in ids.tolist():
             if i >= n_rows:
-                raise OttersError(f"ott_query_recommend: example id {i} is not below the store's length {n_rows}")
+                raise OttersError(f"{who}: example id {i} is not below the store's length {n_rows}")
             if is_neg and i in seen_pos:
-                raise OttersError(f"ott_query_recommend: row {i} is listed as both a positive and a negative example")
+                raise OttersError(f"{who}: row {i} is listed as both a positive and a negative example")
             if i in seen:
                 continue
             if len(seen) == RECOMMEND_MAX_EXAMPLES:
-                raise OttersError("ott_query_recommend: more than OTT_RECOMMEND_MAX_EXAMPLES (64) distinct examples")
+                raise OttersError(f"{who}: more than OTT_RECOMMEND_MAX_EXAMPLES (64) distinct examples")
             seen.add(i)
         if not is_neg:
             seen_pos = set(seen)
@@ -673,18 +679,23 @@ class ResolvedRecommend:
     row_mask: Optional[np.ndarray]
     path: int
     flags: int
+    strategy: int = 0  # RecommendStrategy; 0 lowers to ott_query_recommend, the others to ott_query_recommend_strategy with flags 0
 
 
 class RecommendPlan:
     """Recommend by example rows (VecStore.recommend; ott_query_recommend, Qdrant's recommend with the best_score strategy): rank the
     rows by their best score against the `positive` rows of the store; a row at least as close to a `negative` row as to its best
     positive leaves the positive side and follows it — least like its nearest negative first — unless fill_negative_side(False).
-    Lazy like VecQueryPlan: errors surface at validate() / collect()."""
+    With strategy AverageVector the hits are those of store.query(q) for q = mean(positives), or mean(positives) +
+    mean(positives) - mean(negatives), with the examples masked out; with SumScores the rows are ranked by the sum of their scores
+    against the positives minus the sum of those against the negatives (ott_query_recommend_strategy).  Both have the positive side
+    only: fill_negative_side() does not reach them.  Lazy like VecQueryPlan: errors surface at validate() / collect()."""
 
-    def __init__(self, store: "VecStore", positive, negative, metric: Metric):
+    def __init__(self, store: "VecStore", positive, negative, metric: Metric, strategy: RecommendStrategy = RecommendStrategy.BestScore):
         self.vector_store = store
         self.positive, self.negative = positive, negative
         self.search_metric = Metric(metric)
+        self.strategy = RecommendStrategy(strategy)
         self.filter_criteria: Optional[tuple] = None
         self.take_type: Optional[TakeType] = None
         self.take_count: Optional[int] = None
@@ -697,7 +708,8 @@ class RecommendPlan:
         return self
 
     def filter(self, score: float, cmp: Cmp) -> "RecommendPlan":
-        """The score filter acts on a row's best POSITIVE score, on both sides."""
+        """The score filter acts on the hit's score: with BestScore on a row's best POSITIVE score BP, on both sides; with SumScores
+        on the sum S; with AverageVector on the query's score, as VecQueryPlan.filter does."""
         self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
         return self
 
@@ -728,28 +740,37 @@ class RecommendPlan:
         self.fill = bool(fill)
         return self
 
+    def _who(self) -> str:
+        return "ott_query_recommend" if self.strategy == RecommendStrategy.BestScore else "ott_query_recommend_strategy"
+
     def validate(self) -> None:
         st = self.vector_store
-        recommend_examples(self.positive, self.negative, len(st))
+        recommend_examples(self.positive, self.negative, len(st), self._who())
         if self.path == Path.Mfma:
-            raise OttersError("ott_query_recommend: the MFMA path does not serve recommend queries; use path AUTO or EXACT")
+            if self.strategy == RecommendStrategy.BestScore:
+                raise OttersError("ott_query_recommend: the MFMA path does not serve recommend queries; use path AUTO or EXACT")
+            if self.strategy == RecommendStrategy.SumScores:
+                raise OttersError("ott_query_recommend_strategy: the MFMA path does not serve sum_scores; use path AUTO or EXACT")
+            if self.search_metric == Metric.Manhattan:
+                raise OttersError("ott_query_recommend_strategy: the MFMA path does not score the Manhattan metric; use path AUTO or EXACT")
         if st.devices is not None:
-            raise OttersError("ott_query_recommend: a multi-GPU store is not served (the examples' rows lie on different shards)")
+            raise OttersError(f"{self._who()}: a multi-GPU store is not served (the examples' rows lie on different shards)")
 
     def resolve(self) -> ResolvedRecommend:
         """Validate and lower the plan.  Pure host logic, no GPU."""
         self.validate()
-        pos, neg = recommend_examples(self.positive, self.negative, len(self.vector_store))
+        pos, neg = recommend_examples(self.positive, self.negative, len(self.vector_store), self._who())
         k = self.take_count if self.take_count is not None else len(self.vector_store)
         take = self.take_type if self.take_type is not None else infer_default_take_type(self.search_metric)
         fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
         return ResolvedRecommend(positive=pos, negative=neg, metric=int(self.search_metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft,
-                                 row_mask=self.row_mask, path=int(self.path), flags=RECOMMEND_FILL if self.fill else 0)
+                                 row_mask=self.row_mask, path=int(self.path),
+                                 flags=(RECOMMEND_FILL if self.fill else 0) if self.strategy == RecommendStrategy.BestScore else 0, strategy=int(self.strategy))
 
     def collect_arrays(self):
         """(hits, sides): `hits` a NumPy record array (`index` u64, `score` f32 — the best positive score on the positive side, the
         best negative score on the negative side —, `query` = 0) in the call's order, `sides[i]` (u32) 1 = positive side, 0 =
-        negative side."""
+        negative side (all 1 with the strategies AverageVector and SumScores, whose score is the query's score and the sum S)."""
         store = self.vector_store
         hits, sides, stats = store._run_recommend(self.resolve())
         store.last_stats = stats
@@ -1318,13 +1339,15 @@ class VecStore:
         stats["group_index_builds"] = int(N.lib().ott_store_group_index_builds(self._handle()))
         return hits, list(per), stats
 
-    def recommend(self, positive, negative=(), metric: Metric = Metric.Cosine) -> RecommendPlan:
-        """Recommend by example rows (ott_query_recommend): `positive` and `negative` are row ids counted from the store's first row
-        (not shifted by the base offset); .take(k).collect() returns the hits and their sides."""
-        return RecommendPlan(self, positive, negative, metric)
+    def recommend(self, positive, negative=(), metric: Metric = Metric.Cosine, strategy: RecommendStrategy = RecommendStrategy.BestScore) -> RecommendPlan:
+        """Recommend by example rows (ott_query_recommend; ott_query_recommend_strategy for another `strategy`): `positive` and
+        `negative` are row ids counted from the store's first row (not shifted by the base offset); .take(k).collect() returns the
+        hits and their sides."""
+        return RecommendPlan(self, positive, negative, metric, strategy)
 
     def _run_recommend(self, rr: ResolvedRecommend, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
-        """ott_query_recommend.  Returns (hits HIT_DTYPE array, sides uint32 array, stats dict)."""
+        """ott_query_recommend, or ott_query_recommend_strategy for another strategy than BestScore.  Returns (hits HIT_DTYPE array,
+        sides uint32 array, stats dict)."""
         cap = max(min(rr.k, self._n), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)
         sides = np.empty(cap, dtype=np.uint32)
@@ -1347,8 +1370,13 @@ class VecStore:
             d.row_mask_bits = int(rr.row_mask.size)
         n_out = C.c_uint64(0)
         st = N.Stats()
-        N.check(N.lib().ott_query_recommend(self._handle(), C.byref(d), N.ptr(rr.positive), rr.positive.size, N.ptr(rr.negative) if rr.negative.size else None,
-                                            rr.negative.size, rr.flags, N.ptr(out), cap, C.byref(n_out), N.ptr(sides), C.byref(st)))
+        neg = N.ptr(rr.negative) if rr.negative.size else None
+        if rr.strategy == int(RecommendStrategy.BestScore):
+            N.check(N.lib().ott_query_recommend(self._handle(), C.byref(d), N.ptr(rr.positive), rr.positive.size, neg, rr.negative.size, rr.flags, N.ptr(out), cap,
+                                                C.byref(n_out), N.ptr(sides), C.byref(st)))
+        else:
+            N.check(N.lib().ott_query_recommend_strategy(self._handle(), C.byref(d), rr.strategy, N.ptr(rr.positive), rr.positive.size, neg, rr.negative.size, rr.flags,
+                                                         N.ptr(out), cap, C.byref(n_out), N.ptr(sides), C.byref(st)))
         return out[: n_out.value].copy(), sides[: n_out.value].copy(), st.as_dict()
 
     def discover(self, context, target=None, target_row=None, metric: Metric = Metric.Cosine) -> DiscoverPlan:
