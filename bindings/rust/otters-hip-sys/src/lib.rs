@@ -21,6 +21,10 @@ pub const OTT_MMR_MAX_FETCH: u32 = 1024; // ott_query_mmr: the largest fetch_k
 pub const OTT_RECOMMEND_MAX_EXAMPLES: u32 = 64; // ott_query_recommend: the most distinct examples, positives and negatives together
 pub const OTT_DISCOVER_MAX_PAIRS: u32 = 32; // ott_query_discover: the most context pairs
 pub const OTT_NO_ROW: u64 = u64::MAX; // ott_query_discover: target_row when no stored row is the target
+pub const OTT_NO_MASK: u32 = 4294967295; // ott_query_masks: mask_of_query[b] when query b has no mask of its own (0xFFFFFFFF)
+pub const OTT_MASK_SLOT_BASE: u32 = 2147483648; // ott_query_masks: mask_of_query[b] = OTT_MASK_SLOT_BASE + slot names a device mask slot (0x80000000)
+pub const OTT_MASK_SLOTS: u32 = 64; // the device mask slots of a store
+pub const OTT_MASKS_MAX_QUERIES: u32 = 1024; // ott_query_masks: the most queries of one call
 pub const OTT_RECOMMEND_FILL: u32 = 1; // ott_query_recommend flags bit 0: the negative side follows the positive side
 pub const OTT_RECOMMEND_BEST_SCORE: u32 = 0; // ott_query_recommend_strategy: ott_query_recommend itself
 pub const OTT_RECOMMEND_AVERAGE_VECTOR: u32 = 1; // one ordinary query with the vector mean(positives) [+ mean(positives) - mean(negatives)]
@@ -189,6 +193,10 @@ extern "C" {
     pub fn ott_store_eval_row_mask(s: *mut ott_store, leaves: *const ott_leaf, n_leaves: u32, n_clauses: u32, out_host: *mut u64) -> c_int;
 
     pub fn ott_query(s: *mut ott_store, d: *const ott_query_desc, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int;
+    pub fn ott_query_masks(s: *mut ott_store, d: *const ott_query_desc, masks: *const u64, n_masks: u32, mask_bits: u64, mask_of_query: *const c_void, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int; // mask_of_query: d.nq u32
+    pub fn ott_store_eval_row_mask_slot(s: *mut ott_store, slot: u32, leaves: *const ott_leaf, n_leaves: u32, n_clauses: u32, out_host: *mut u64) -> c_int;
+    pub fn ott_store_write_row_mask_slot(s: *mut ott_store, slot: u32, bits: *const u64, n_bits: u64) -> c_int;
+    pub fn ott_store_clear_row_mask_slots(s: *mut ott_store) -> c_int;
     pub fn ott_query_ids(s: *mut ott_store, d: *const ott_query_desc, ids: *const u64, n_ids: u64, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int;
     pub fn ott_store_score_rows(s: *mut ott_store, queries: *const f32, nq: u32, metric: u32, ids: *const u64, n_ids: u64, out_scores: *mut f32) -> c_int;
     pub fn ott_query_mmr(s: *mut ott_store, d: *const ott_query_desc, ids: *const u64, n_ids: u64, fetch_k: u64, lambda: f32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, out_values: *mut f32, stats: *mut ott_stats) -> c_int; // ids: null, 0 = no id list; out_values: null or cap floats

@@ -316,6 +316,8 @@ int ott_store_batch_ready(const ott_store* s);
  *   "group_gather" (-1 auto: lists whose groups hold up to 1000000 rows / 0 never / 1 wherever eligible: whether ott_query_maxsim_groups
  *   scores the listed groups' rows with the gather kernel, through the store's group-to-rows index, or turns the list into a row mask
  *   and runs ott_query_maxsim's sweep; environment preset OTT_GROUP_GATHER, as for every option),
+ *   "masks_sweep" (2 auto, the default / 0 always by mask group / 1 the masks sweep wherever eligible: which route answers
+ *   ott_query_masks; environment preset OTT_MASKS_SWEEP),
  *   "large_k_from" (k above which host-output queries take the sort path; 0 = default: 512 for one query or a small store,
  *   128 for several queries on a large one), "small_sort" (0: results of up to 16384 (row, query) pairs with k > 512 through
  *   the radix sort instead of the rank sort), "mfma_f32" (batch path: one candidate pass on the f32 matrix pipe),
@@ -386,6 +388,50 @@ int ott_query_ids(ott_store* s, const ott_query_desc* d, const uint64_t* ids, ui
  * rows of at most 2048 floats.  Errors as ott_query_ids.  Takes the store shared. */
 int ott_store_score_rows(ott_store* s, const float* queries, uint32_t nq, uint32_t metric, const uint64_t* ids, uint64_t n_ids,
                          float* out_scores);
+
+/* Batch search with a row mask per query (an extension; a metadata filter per request: Qdrant's search_batch, FAISS's per-query
+ * IDSelector).  masks: n_masks host masks back to back, each (mask_bits + 63) / 64 words of BitVec<usize, Lsb0>, 1 = keep.
+ * mask_of_query points at d->nq uint32_t (declared const void*, as the group ids are): [b] < n_masks names a host mask,
+ * OTT_MASK_SLOT_BASE + slot a device mask slot (below), OTT_NO_MASK no mask of its own.  d->mode must be OTT_MODE_PER_QUERY.
+ * Query b's hits are exactly the hits ott_query returns for that query alone — index, score bits, order and count — with the same
+ * descriptor and a row mask equal to the descriptor's own mask (row_mask or use_device_row_mask, joined with the live mask of
+ * deleted rows and chunk_mask, as in ott_query) ANDed with mask mask_of_query[b]: every metric, take, filter, k, path and tie order.
+ * Rows at or beyond a mask's bit count are kept (src/vec.rs:234).  hit.query is b; the lists come out in the caller's query order,
+ * their lengths in n_per_query; cap follows ott_query's PER_QUERY rule (nq * min(k, rows)).  Stats may differ from the per-query
+ * calls, hits may not.
+ * Two routes, the same bits.  BY MASK GROUP serves everything: under one shared lock, one PER_QUERY run of ott_query's own
+ * internals per distinct mask id with all of that mask's queries (so queries that share a mask get the batch paths), the mask
+ * joined where every row mask reaches the kernels.  THE MASKS SWEEP (canonical tie order, path AUTO or EXACT, a single-GPU store
+ * of fewer than 2^32 - 16 rows): the queries are ordered stably by mask id and swept four per pass; all masks are on the device
+ * (host masks in one upload, slots in place); per pass a small kernel writes common AND (m0 OR m1 OR m2 OR m3) as the pass's row
+ * mask, so a tile in which no query of the pass has a surviving row is never read; the sweep's epilogue tests each query's own
+ * mask bit and stores the candidate key into a table of 4 x rows 8-byte slots (scratch of the query context); grouped search's
+ * top-k takes each query's list from the table; one host wait for the whole batch.  Option "masks_sweep" chooses: 0 = always by
+ * mask group, 1 = the sweep wherever eligible, 2 (default) = auto (ott_masks_plan.h: measured constants).
+ * Refused with OTT_ERR_INVALID before any device work, with nothing written: d->nq of 0 or above OTT_MASKS_MAX_QUERIES,
+ * OTT_MODE_MERGED, mask_of_query NULL, masks NULL with n_masks > 0, an entry at or above n_masks that is neither a slot
+ * reference nor OTT_NO_MASK, a reference to a slot at or above OTT_MASK_SLOTS or to one that was never filled (or was dropped
+ * since), and what ott_query refuses.  A multi-GPU store is answered by mask group with host masks (use_device_row_mask together
+ * with a per-query mask is OTT_ERR_UNSUPPORTED there).  Takes the store shared, like ott_query (staged appends go first).
+ *
+ * Device mask slots: OTT_MASK_SLOTS row masks resident in HBM beside the single mask of ott_store_eval_row_mask (which they never
+ * touch), so a filter evaluated on the GPU never travels to the host and back.  eval: ott_store_eval_row_mask's kernel and
+ * semantics, written into slot `slot` (out_host, if given, receives the words too).  write: n_bits bits of a host mask into the
+ * slot (n_bits == 0 empties it).  clear: every slot is emptied.  A slot covers the rows the store had when it was filled (rows
+ * appended later are kept, as with any mask); every slot is dropped when the rows are reallocated or compacted or a shard adopts
+ * moved rows.  All three take the store exclusively, like ott_store_eval_row_mask; slot >= OTT_MASK_SLOTS is OTT_ERR_INVALID; on
+ * a multi-GPU store they return OTT_ERR_UNSUPPORTED. */
+#define OTT_NO_MASK 4294967295u        /* 0xFFFFFFFF: mask_of_query[b] = no mask of its own */
+#define OTT_MASK_SLOT_BASE 2147483648u /* 0x80000000: mask_of_query[b] = OTT_MASK_SLOT_BASE + slot, a device slot */
+#define OTT_MASK_SLOTS 64
+#define OTT_MASKS_MAX_QUERIES 1024
+int ott_query_masks(ott_store* s, const ott_query_desc* d, const uint64_t* masks, uint32_t n_masks, uint64_t mask_bits,
+                    const void* mask_of_query /* uint32_t[d->nq] */, ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query,
+                    ott_stats* stats);
+int ott_store_eval_row_mask_slot(ott_store* s, uint32_t slot, const ott_leaf* leaves, uint32_t n_leaves, uint32_t n_clauses,
+                                 uint64_t* out_host);
+int ott_store_write_row_mask_slot(ott_store* s, uint32_t slot, const uint64_t* bits, uint64_t n_bits);
+int ott_store_clear_row_mask_slots(ott_store* s);
 
 /* MMR diversity re-ranking (an extension; maximal marginal relevance, Carbonell and Goldstein — LangChain's
  * max_marginal_relevance_search, Qdrant's mmr query): of a query's best fetch_k hits, pick d->k greedily, each pick the most relevant

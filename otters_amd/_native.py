@@ -59,6 +59,10 @@ class Leaf(C.Structure):
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
 COMM_ID_BYTES = 128
 ABI_VERSION = 4
+NO_MASK = 0xFFFFFFFF          # OTT_NO_MASK: mask_of_query[b] = no mask of its own
+MASK_SLOT_BASE = 0x80000000   # OTT_MASK_SLOT_BASE + slot: a device mask slot
+MASK_SLOTS = 64               # OTT_MASK_SLOTS
+MASKS_MAX_QUERIES = 1024      # OTT_MASKS_MAX_QUERIES
 
 _lib = None
 
@@ -153,6 +157,10 @@ def lib() -> C.CDLL:
         "ott_query": (i32, [vp, vp, vp, u64, vp, vp, vp]),
         "ott_query_ids": (i32, [vp, vp, vp, u64, vp, u64, vp, vp, vp]),
         "ott_store_score_rows": (i32, [vp, vp, u32, u32, vp, u64, vp]),
+        "ott_query_masks": (i32, [vp, vp, vp, u32, u64, vp, vp, u64, vp, vp, vp]),
+        "ott_store_eval_row_mask_slot": (i32, [vp, u32, vp, u32, u32, vp]),
+        "ott_store_write_row_mask_slot": (i32, [vp, u32, vp, u64]),
+        "ott_store_clear_row_mask_slots": (i32, [vp]),
         "ott_query_mmr": (i32, [vp, vp, vp, u64, u64, C.c_float, vp, u64, vp, vp, vp, vp]),
         "ott_query_recommend": (i32, [vp, vp, vp, u64, vp, u64, u32, vp, u64, vp, vp, vp]),
         "ott_query_recommend_strategy": (i32, [vp, vp, u32, vp, u64, vp, u64, u32, vp, u64, vp, vp, vp]),

@@ -460,6 +460,8 @@ int ott::compose_row_mask(ott_store* s, const ott_query_desc* d, const uint64_t*
         }
         mask_bits = s->n;
     }
+    // a by-mask-group run of ott_query_masks (ott_masks.hip): the queries' own mask joins the same way, in that call's scratch
+    if (s->cur_qmask && (rc = masks_join(s, &d_mask, &mask_bits))) return rc;
     // deleted rows (ott_tomb.hip): the store's live mask joins here — as the mask itself when the query brought none, else ANDed
     // with it into this context's scratch.  A store without deletions has no live mask and takes neither branch.
     if (s->n_dead && (rc = live_compose(s, &d_mask, &mask_bits))) return rc;

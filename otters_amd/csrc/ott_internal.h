@@ -23,6 +23,7 @@
 #include "ott_discover_plan.h"  // discovery / context search's host-side plan (refusals, slot layout, passes, k_eff, scratch bytes, the level cut): HIP-free, CPU-tested
 #include "ott_recommend_plan.h"  // recommend-by-example's host-side plan (refusals, example layout, passes, k_eff, the second round, scratch bytes): HIP-free, CPU-tested
 #include "ott_mmr_plan.h"  // MMR re-ranking's host-side plan (refusals, scratch layout, the pair grid, the greedy launch): HIP-free, CPU-tested
+#include "ott_masks_plan.h"  // ott_query_masks' host-side plan (refusals, the queries' order by mask id, the route and its auto rule): HIP-free, CPU-tested
 #include "ott_sort_plan.h"  // the sort path's host-side plan (pass plans, sweep shape, rank or radix, prefix, slices, group extents, copy pieces): HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
 #include "ott_audit.h"  // test build: every HIP call below goes through a device-affinity check (see "which GPU a call is for")
@@ -93,9 +94,9 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  TWENTY-TWO of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  TWENTY-THREE of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, group_gather, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, group_gather, masks_sweep, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
@@ -166,6 +167,8 @@ struct Options {
                                   // takes the mask's paths), 1 = the gather kernel wherever it is eligible
     int group_gather = -1;        // listed MaxSim (ott_query_maxsim_groups): -1 = automatic, 0 = never (the list becomes a row mask and
                                   // ott_query_maxsim's sweep runs), 1 = the gather kernel wherever it is eligible
+    int masks_sweep = 2;          // a row mask per query (ott_query_masks): 2 = automatic (ott_masks_plan.h), 0 = always by mask group
+                                  // (one PER_QUERY run per distinct mask), 1 = the masks sweep wherever it is eligible
     int maxsim_fold = -1;         // [debug build] late-interaction sweep (ott_maxsim.hip): -1 = the product's epilogue, 0 = one atomic per lane,
                                   // 1 = folded over runs of adjacent lanes of one group first (the A/B of profiles/maxsim)
     int multi_min_shard_rows = 32768;  // multi-GPU store: a shard is only brought in for this many rows (a store of fewer than twice as many stays
@@ -306,6 +309,17 @@ struct ott_store {
     ott::DevBuf x_send, x_recv;  // sharded queries: this shard's candidate block, the gathered blocks of all shards
     ott::DevBuf d_evalmask;  // mask built by ott_store_eval_row_mask
     uint64_t evalmask_bits = 0;
+    // A row mask per query (ott_masks.hip).  d_mslot / mslot_bits: the device mask slots, filled by
+    // ott_store_eval_row_mask_slot / ott_store_write_row_mask_slot under `rw` exclusive; mslot_bits[i] = the rows slot i covers, 0 =
+    // empty.  Owned by the store: worker contexts read them through `owner` (the caller holds `rw` shared).  Dropped wherever the
+    // rows move (mask_slots_drop).  d_qmasks: THIS context's scratch of one ott_query_masks call (ott_masks_plan.h:
+    // masks_scratch_bytes); cur_qmask / cur_qmask_bits: the per-query mask of the by-mask-group run this context is making right
+    // now (compose_row_mask joins it, like cur_idmask), nullptr = none
+    ott::DevBuf d_mslot[OTT_MASK_SLOTS];
+    uint64_t mslot_bits[OTT_MASK_SLOTS] = {};
+    ott::DevBuf d_qmasks;
+    const uint64_t* cur_qmask = nullptr;
+    uint64_t cur_qmask_bits = 0;
     // Deleted rows (ott_tomb.hip): the LIVE mask, one bit per row slot, 1 = live — [(cap + 63) / 64] words,
     // allocated by the first ott_store_delete_rows and freed again by ott_store_compact; nullptr = no row was ever deleted (and
     // the query path is then exactly what it was).  Every bit at and past `n` is 1 in every word, so appended rows are live
@@ -729,6 +743,14 @@ int query_core(ott_store* s, const ott_query_desc* d, ott_hit* out_host, void* o
                void* n_out_dev, ott_stats* stats_out, bool nosync, bool* events_pending, const CoreOpts& co);
 // ott_api.hip: the row mask the kernels of a query get (caller's or evaluated mask & id list on the mask route & live mask), nullptr = none
 int compose_row_mask(ott_store* s, const ott_query_desc* d, const uint64_t** d_mask, uint64_t* mask_bits);
+// ott_masks.hip: a row mask per query.  masks_join: the mask a by-mask-group run's kernels get — *d_mask (device words or nullptr)
+// ANDed with the context's cur_qmask over s->n rows, in the context's scratch; bits at and beyond either mask's count are kept.
+// mask_slots_drop: every device mask slot is emptied and its memory given back (the caller holds the store exclusively, on its device).
+// ott_mask.hip: eval_row_mask_into — ott_store_eval_row_mask's checks, kernel and wait for entry point `fn`, the words into `dst`
+// (*dst_bits = the rows they cover, 0 while they are being made); the caller holds the store exclusively and `mu`.
+int masks_join(ott_store* s, const uint64_t** d_mask, uint64_t* mask_bits);
+void mask_slots_drop(ott_store* s);
+int eval_row_mask_into(ott_store* s, const char* fn, const ott_leaf* leaves, uint32_t n_leaves, DevBuf& dst, uint64_t* dst_bits, uint64_t* out_host);
 // ott_multi.hip: candidate id lists on a multi-GPU store (ott_gather.hip).  ids: ascending, duplicate-free, every id < the store's length
 int multi_query_ids(ott_store* ms, const ott_query_desc* d, const std::vector<uint64_t>& ids, ott_hit* out, uint64_t cap, uint64_t* n_out,
                     uint64_t* n_per_query, ott_stats* stats);

@@ -162,6 +162,60 @@ __global__ __launch_bounds__(256) void zone_stat_kernel(const T* __restrict__ va
     }
 }
 
+// The body of ott_store_eval_row_mask and of ott_store_eval_row_mask_slot (ott_masks.hip), for entry point `fn`: the leaves bound to
+// the resident columns, the kernel, the words into `dst` (and to out_host), one wait.  *dst_bits is 0 while the words are being
+// made and the store's length afterwards.  The caller holds the store exclusively and `mu`.
+int eval_row_mask_into(ott_store* s, const char* fn, const ott_leaf* leaves, uint32_t n_leaves, DevBuf& dst, uint64_t* dst_bits, uint64_t* out_host) {
+    const std::string name(fn);
+    OTT_HIP(use_device(s));
+    {
+        const int rcf = store_flush_locked(s);
+        if (rcf) return rcf;
+    }
+    const uint64_t n = s->n;
+    const size_t words = (size_t)((n + 63) / 64);
+    std::vector<DevLeaf> dl(n_leaves);
+    for (uint32_t i = 0; i < n_leaves; i++) {
+        if (leaves[i].column >= s->columns.size()) return fail(OTT_ERR_INVALID, name + ": unknown column id");
+        if (i && leaves[i].clause < leaves[i - 1].clause) return fail(OTT_ERR_INVALID, name + ": leaves must be grouped by clause");
+        const Column& c = s->columns[leaves[i].column];
+        if (c.n != n) return fail(OTT_ERR_INVALID, name + ": column length no longer matches the store");
+        dl[i].vals = c.d_vals;
+        dl[i].nulls = c.d_nulls;
+        dl[i].dtype = c.dtype;
+        dl[i].op = leaves[i].op;
+        dl[i].clause = leaves[i].clause;
+        dl[i].pad = 0;
+        dl[i].lit_i64 = leaves[i].lit_i64;
+        dl[i].lit_f64 = leaves[i].lit_f64;
+    }
+    *dst_bits = 0;
+    if (!n) return OTT_OK;
+    int rc;
+    if ((rc = dst.ensure(words * 8))) return rc;
+    MaskParams mp;
+    memset(&mp, 0, sizeof(mp));
+    mp.n_leaves = n_leaves;
+    mp.n_rows = n;
+    mp.out = (uint64_t*)dst.p;
+    mp.embedded = n_leaves <= MASK_EMBED;
+    if (mp.embedded) {
+        if (n_leaves) memcpy(mp.eleaves, dl.data(), n_leaves * sizeof(DevLeaf));
+    } else {
+        if ((rc = s->d_misc.ensure(n_leaves * sizeof(DevLeaf)))) return rc;
+        OTT_HIP(hipMemcpyAsync(s->d_misc.p, dl.data(), n_leaves * sizeof(DevLeaf), hipMemcpyHostToDevice, s->stream));
+        mp.leaves = (const DevLeaf*)s->d_misc.p;
+    }
+    uint64_t blocks = (words + 4 * MASK_U - 1) / (4 * MASK_U);
+    if (blocks > (uint64_t)s->n_cu * 8) blocks = (uint64_t)s->n_cu * 8;
+    hipLaunchKernelGGL(eval_mask_kernel, dim3((uint32_t)blocks), dim3(256), 0, s->stream, mp);
+    OTT_HIP(hipGetLastError());
+    if (out_host) OTT_HIP(hipMemcpyAsync(out_host, dst.p, words * 8, hipMemcpyDeviceToHost, s->stream));
+    OTT_HIP(hipStreamSynchronize(s->stream));
+    *dst_bits = n;
+    return OTT_OK;
+}
+
 }  // namespace ott
 
 using namespace ott;
@@ -213,53 +267,7 @@ int ott_store_eval_row_mask(ott_store* s, const ott_leaf* leaves, uint32_t n_lea
     (void)n_clauses;
     ott::host::ExclusiveLock wr(s->rw);  // no query is running on any context
     std::lock_guard<std::mutex> g(s->mu);
-    OTT_HIP(use_device(s));
-    {
-        const int rcf = store_flush_locked(s);
-        if (rcf) return rcf;
-    }
-    const uint64_t n = s->n;
-    const size_t words = (size_t)((n + 63) / 64);
-    std::vector<DevLeaf> dl(n_leaves);
-    for (uint32_t i = 0; i < n_leaves; i++) {
-        if (leaves[i].column >= s->columns.size()) return fail(OTT_ERR_INVALID, "ott_store_eval_row_mask: unknown column id");
-        if (i && leaves[i].clause < leaves[i - 1].clause) return fail(OTT_ERR_INVALID, "ott_store_eval_row_mask: leaves must be grouped by clause");
-        const Column& c = s->columns[leaves[i].column];
-        if (c.n != n) return fail(OTT_ERR_INVALID, "ott_store_eval_row_mask: column length no longer matches the store");
-        dl[i].vals = c.d_vals;
-        dl[i].nulls = c.d_nulls;
-        dl[i].dtype = c.dtype;
-        dl[i].op = leaves[i].op;
-        dl[i].clause = leaves[i].clause;
-        dl[i].pad = 0;
-        dl[i].lit_i64 = leaves[i].lit_i64;
-        dl[i].lit_f64 = leaves[i].lit_f64;
-    }
-    s->evalmask_bits = 0;
-    if (!n) return OTT_OK;
-    int rc;
-    if ((rc = s->d_evalmask.ensure(words * 8))) return rc;
-    MaskParams mp;
-    memset(&mp, 0, sizeof(mp));
-    mp.n_leaves = n_leaves;
-    mp.n_rows = n;
-    mp.out = (uint64_t*)s->d_evalmask.p;
-    mp.embedded = n_leaves <= MASK_EMBED;
-    if (mp.embedded) {
-        if (n_leaves) memcpy(mp.eleaves, dl.data(), n_leaves * sizeof(DevLeaf));
-    } else {
-        if ((rc = s->d_misc.ensure(n_leaves * sizeof(DevLeaf)))) return rc;
-        OTT_HIP(hipMemcpyAsync(s->d_misc.p, dl.data(), n_leaves * sizeof(DevLeaf), hipMemcpyHostToDevice, s->stream));
-        mp.leaves = (const DevLeaf*)s->d_misc.p;
-    }
-    uint64_t blocks = (words + 4 * MASK_U - 1) / (4 * MASK_U);
-    if (blocks > (uint64_t)s->n_cu * 8) blocks = (uint64_t)s->n_cu * 8;
-    hipLaunchKernelGGL(eval_mask_kernel, dim3((uint32_t)blocks), dim3(256), 0, s->stream, mp);
-    OTT_HIP(hipGetLastError());
-    if (out_host) OTT_HIP(hipMemcpyAsync(out_host, s->d_evalmask.p, words * 8, hipMemcpyDeviceToHost, s->stream));
-    OTT_HIP(hipStreamSynchronize(s->stream));
-    s->evalmask_bits = n;
-    return OTT_OK;
+    return eval_row_mask_into(s, "ott_store_eval_row_mask", leaves, n_leaves, s->d_evalmask, &s->evalmask_bits, out_host);
 }
 
 int ott_store_zone_stats(ott_store* s, uint32_t column, uint64_t chunk_size, void* out_min, void* out_max, uint64_t* out_non_null) {

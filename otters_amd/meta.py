@@ -705,8 +705,9 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
                     return False
         return True
 
-    def build_row_mask_device(self, compiled: CompiledFilter, fetch: bool = False):
-        """CNF evaluated on the GPU over HBM-resident columns (numeric, datetime, dictionary-coded strings)."""
+    def build_row_mask_device(self, compiled: CompiledFilter, fetch: bool = False, slot: Optional[int] = None):
+        """CNF evaluated on the GPU over HBM-resident columns (numeric, datetime, dictionary-coded strings): into the store's one
+        evaluated mask, or, with `slot`, into that device mask slot (ott_store_eval_row_mask_slot; the one mask is not touched)."""
         leaves = []
         for ci, clause in enumerate(compiled.clauses):
             for leaf in clause:
@@ -729,7 +730,10 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
                 raise OttersError("empty clause in compiled filter")
         arr = (N.Leaf * max(len(leaves), 1))(*leaves)
         out = np.zeros(max((self._n_rows + 63) // 64, 1), dtype=np.uint64) if fetch else None
-        N.check(N.lib().ott_store_eval_row_mask(self._store._handle(), arr, len(leaves), len(compiled.clauses), N.ptr(out)))
+        if slot is None:
+            N.check(N.lib().ott_store_eval_row_mask(self._store._handle(), arr, len(leaves), len(compiled.clauses), N.ptr(out)))
+        else:
+            N.check(N.lib().ott_store_eval_row_mask_slot(self._store._handle(), int(slot), arr, len(leaves), len(compiled.clauses), N.ptr(out)))
         return N.unpack_bits(out, self._n_rows) if fetch else None
 
 
@@ -748,6 +752,22 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         self._distinct: Optional[str] = None
         self._keep = 1  # distinct_by(name, keep=m): rows per distinct value
         self._mmr = None  # mmr(): (lambda_mult, fetch_k or None)
+        self._meta_filters = None  # meta_filters(): one CompiledFilter or None per query of the batch
+
+    def meta_filters(self, exprs) -> "MetaQueryPlan":
+        """A metadata filter per query of a query_batch (a filter per request; ott_query_masks): `exprs` holds one Expr or None per
+        query.  collect_per_query() then returns one MetaQueryResults per query, each exactly what
+        store.query(q).meta_filter(e).take(k).collect() returns for that query alone.  Exclusive with meta_filter; not together
+        with with_row_ids, distinct_by or mmr.  Errors are deferred to collect_per_query()."""
+        try:
+            # (an entry may be a CompiledFilter already: a server compiles a tenant's filter once)
+            self._meta_filters = [e if e is None or isinstance(e, CompiledFilter) else e.compile(self.store._schema) for e in exprs]
+            self.meta_error = None
+        except ExprError as e:
+            self.meta_error = f"meta_filter compile error: {e}"
+        except TypeError:
+            self.meta_error = "meta_filters takes a sequence with one Expr or None per query"
+        return self
 
     def meta_filter(self, expr: Expr) -> "MetaQueryPlan":  # src/meta.rs:605-616 (error deferred to collect)
         try:
@@ -799,6 +819,8 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         Returns (ResolvedQuery, chunk_mask or None, compiled filter or None)."""
         if self.meta_error is not None:
             raise OttersError(self.meta_error)
+        if self._meta_filters is not None:
+            raise OttersError("meta_filters returns one result per query: use collect_per_query()")
         st = self.store
         n_groups = 0
         if self._distinct is not None:
@@ -837,6 +859,12 @@ class MetaQueryPlan:  # src/meta.rs:579-830
                 ids = np.ascontiguousarray(ids[keep])
             rq.row_ids = ids
         return rq, chunk_mask, self._meta_filter
+
+    def collect_per_query(self) -> List[MetaQueryResults]:
+        """One MetaQueryResults per query of a meta_filters() plan, in query order (one ott_query_masks call)."""
+        if self._meta_filters is None and self.meta_error is None:
+            raise OttersError("collect_per_query needs meta_filters(): one Expr or None per query")
+        return _collect_per_query(self)
 
     def collect(self) -> MetaQueryResults:  # src/meta.rs:632-829
         t0 = time.perf_counter()
@@ -884,6 +912,109 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         names = sorted(st._schema)  # src/meta.rs:723-724
         data = {name: st._columns[name].take(indices) for name in names}  # src/meta.rs:728-821
         return MetaQueryResults(names, data, indices, scores)
+
+
+def _same_filter(a: CompiledFilter, b: CompiledFilter) -> bool:
+    key = lambda f: [[(l.column, l.kind, int(l.cmp), repr(l.rhs)) for l in cl] for cl in f.clauses]  # noqa: E731
+    return key(a) == key(b)
+
+
+def _resolve_filters(plan: "MetaQueryPlan"):
+    """Host-side part of MetaQueryPlan.collect_per_query: the refusals, k / take as resolve() infers them, the distinct compiled
+    filters and each one's chunk mask, and the chunk mask the batch shares -- the OR of the per-filter chunk masks (None = every
+    chunk: some query has no filter).  Returns (ResolvedQuery in PerQuery mode, shared chunk mask or None, distinct filters,
+    their chunk masks, filter_of_query: index into the distinct filters or -1)."""
+    if plan.meta_error is not None:
+        raise OttersError(plan.meta_error)
+    st = plan.store
+    if plan._meta_filter is not None:
+        raise OttersError("meta_filters cannot be combined with meta_filter: put the common condition into every filter")
+    if plan._row_ids is not None:
+        raise OttersError("meta_filters cannot be combined with with_row_ids in this version")
+    if plan._distinct is not None:
+        raise OttersError("meta_filters cannot be combined with distinct_by in this version")
+    if plan._mmr is not None:
+        raise OttersError("meta_filters cannot be combined with mmr in this version")
+    if not plan.queries:
+        raise OttersError("No queries provided")
+    if len(plan._meta_filters) != len(plan.queries):
+        raise OttersError(f"meta_filters: {len(plan._meta_filters)} filters for {len(plan.queries)} queries")
+    if len(plan.queries) > N.MASKS_MAX_QUERIES:
+        raise OttersError(f"meta_filters: {len(plan.queries)} queries are above the {N.MASKS_MAX_QUERIES} one call takes")
+    for q in plan.queries:
+        if st._n_rows and q.size != st._dim:
+            raise OttersError(f"Query vector length {q.size} does not match expected dimension {st._dim}")
+    distinct, of_query = [], []
+    for f in plan._meta_filters:
+        if f is None:
+            of_query.append(-1)
+            continue
+        at = next((i for i, g in enumerate(distinct) if g is f or _same_filter(g, f)), None)
+        if at is None:
+            distinct.append(f)
+            at = len(distinct) - 1
+        of_query.append(at)
+    chunk_masks = [st.build_chunk_mask_for_plan(f) for f in distinct]
+    shared = None
+    if distinct and -1 not in of_query:
+        shared = np.zeros(st._n_chunks, dtype=bool)
+        for cm in chunk_masks:
+            shared |= cm
+    k = plan.take_count if plan.take_count is not None else st._n_rows
+    take = plan.take_type if plan.take_type is not None else infer_default_take_type(plan.metric)
+    fc, ft = (0, 0.0) if plan._vec_filter is None else (int(plan._vec_filter[1]), plan._vec_filter[0])
+    rq = ResolvedQuery(queries=np.ascontiguousarray(np.stack(plan.queries)), metric=int(plan.metric), take=int(take), k=max(int(k), 0), filter_cmp=fc,
+                       filter_thr=ft, row_mask=None, mode=int(Mode.PerQuery), path=int(plan._path))
+    return rq, shared, distinct, chunk_masks, of_query
+
+
+def _collect_per_query(plan: "MetaQueryPlan"):
+    """MetaQueryPlan.collect_per_query (meta_filters): every distinct filter becomes ONE mask of ott_query_masks -- evaluated on the
+    GPU into a device mask slot where the evaluator takes the filter and the store is a single-GPU one (the mask never travels),
+    a host mask otherwise (and for what does not fit the slots) -- and the batch runs as one call, all under the store's mask lock."""
+    t0 = time.perf_counter()
+    rq, shared, distinct, chunk_masks, of_query = _resolve_filters(plan)
+    st = plan.store
+    nq = len(plan.queries)
+    prune = time.perf_counter() - t0
+    hits, counts, gstats = np.zeros(0, dtype=N.HIT_DTYPE), [0] * nq, None
+    if st._store is not None and st._n_rows and (shared is None or shared.any()):
+        single_gpu = len(st._store.shards()) <= 1
+        with st._mask_lock:  # the slots are store-global state, like the one evaluated mask: filled and read in one critical section
+            mask_id, host_masks, n_slots = [], [], 0
+            for f, cm in zip(distinct, chunk_masks):
+                if st.row_mask_is_all_true(f, cm):
+                    # the zone statistics decide every row of the filter's own surviving chunks; the chunk mask the batch shares
+                    # is wider than that, so the filter's chunk mask goes as its row mask
+                    host_masks.append(np.repeat(cm, st._chunk_size)[: st._n_rows])
+                    mask_id.append(len(host_masks) - 1)
+                elif single_gpu and n_slots < N.MASK_SLOTS and st._device_mask_ok(f):
+                    st.build_row_mask_device(f, slot=n_slots)
+                    mask_id.append(N.MASK_SLOT_BASE + n_slots)
+                    n_slots += 1
+                else:
+                    host_masks.append(st.build_row_mask_host(f))
+                    mask_id.append(len(host_masks) - 1)
+            rq.mask_of_query = np.asarray([N.NO_MASK if i < 0 else mask_id[i] for i in of_query], dtype=np.uint32)
+            rq.query_masks = np.stack(host_masks) if host_masks else np.ones((0, 0), dtype=bool)
+            hits, counts, gstats = st._store._run(rq, chunk_mask=shared)
+        st._store.last_stats = gstats
+    total_chunks = st._n_chunks
+    evaluated = int(shared.sum()) if shared is not None else total_chunks
+    compared = gstats["vectors_compared"] if gstats is not None else 0
+    merge_d = gstats["merge_ns"] / 1e9 if gstats is not None else 0.0
+    total = time.perf_counter() - t0
+    st._last_stats = MetaQueryStats(total_chunks, total_chunks - evaluated, evaluated, int(compared), prune, max(total - prune - merge_d, 0.0), merge_d, total,
+                                    bytes_scanned=gstats["bytes_scanned"] if gstats else 0, path_used=gstats["path_used"] if gstats else 0,
+                                    gpu_score_ms=(gstats["score_ns"] / 1e6) if gstats else 0.0)
+    names = sorted(st._schema)
+    out, at = [], 0
+    for c in counts:
+        part = hits[at:at + int(c)]
+        at += int(c)
+        indices = [int(i) for i in part["index"]]
+        out.append(MetaQueryResults(names, {name: st._columns[name].take(indices) for name in names}, indices, [float(x) for x in part["score"]]))
+    return out
 
 
 class MetaRecommendPlan:

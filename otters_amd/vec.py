@@ -107,6 +107,8 @@ class ResolvedQuery:
     group_of_hit: Optional[np.ndarray] = None  # OUTPUT of VecStore._run for a per_group plan: uint32[n hits], the dense group id of every hit
     mmr: Optional[tuple] = None                # mmr: (lambda as float32, fetch_k) -- the picks of ott_query_mmr instead of the top-k
     mmr_values: Optional[np.ndarray] = None    # OUTPUT of VecStore._run for an mmr plan: float32[n hits], the value of every pick
+    mask_of_query: Optional[np.ndarray] = None  # with_row_masks: uint32[nq] -- an index into query_masks, N.MASK_SLOT_BASE + slot, or N.NO_MASK (ott_query_masks)
+    query_masks: Optional[np.ndarray] = None    # with_row_masks: bool[n distinct masks, mask bits], every mask padded with True to the longest
 
 
 def as_row_ids(ids) -> np.ndarray:
@@ -174,6 +176,34 @@ MAXSIM_BATCH_MAX = 4096  # include/otters_hip.h: OTT_MAXSIM_BATCH_MAX
 MMR_MAX_FETCH = 1024  # include/otters_hip.h: OTT_MMR_MAX_FETCH
 
 
+def lower_row_masks(masks):
+    """with_row_masks' entries as (mask_of_query uint32[nq], query_masks bool[n distinct, bits]): entries that are the same object
+    or equal arrays share one mask (it is uploaded once), None becomes N.NO_MASK, shorter masks are padded with True to the
+    longest (rows at or beyond a mask's length are kept)."""
+    arrays, of_query, by_id = [], [], {}
+    for m in masks:
+        if m is None:
+            of_query.append(N.NO_MASK)
+            continue
+        if id(m) in by_id:
+            of_query.append(by_id[id(m)])
+            continue
+        a = np.asarray(m, dtype=bool).ravel()
+        at = next((i for i, b in enumerate(arrays) if b.size == a.size and np.array_equal(a, b)), None)
+        if at is None:
+            arrays.append(a)
+            at = len(arrays) - 1
+        by_id[id(m)] = at
+        of_query.append(at)
+    bits = max((a.size for a in arrays), default=0)
+    if bits == 0:  # only empty masks: every row is at or beyond their length, so every row is kept
+        return np.full(len(of_query), N.NO_MASK, dtype=np.uint32), np.ones((0, 0), dtype=bool)
+    qm = np.ones((len(arrays), bits), dtype=bool)
+    for i, a in enumerate(arrays):
+        qm[i, : a.size] = a
+    return np.asarray(of_query, dtype=np.uint32), qm
+
+
 def mmr_default_fetch_k(k: int) -> int:
     """mmr()'s candidate count when the caller names none: five times the picks, at least 20, at most OTT_MMR_MAX_FETCH"""
     return min(MMR_MAX_FETCH, max(20, 5 * int(k)))
@@ -224,6 +254,7 @@ class VecQueryPlan:
         self._per_group = None  # per_group(m): m as the caller gave it (checked at validate())
         self.group_list = None  # with_groups: the labels as the caller gave them (mapped at validate())
         self._mmr = None        # mmr(): (lambda_mult, fetch_k or None) as the caller gave them (checked at validate())
+        self.row_masks = None   # with_row_masks: one boolean array or None per query, as the caller gave them (checked at validate())
 
     @staticmethod
     def new() -> "VecQueryPlan":
@@ -291,6 +322,16 @@ class VecQueryPlan:
         validate(), an id >= len() when the query runs."""
         if self.error is None:
             self.row_ids = ids
+        return self
+
+    def with_row_masks(self, masks) -> "VecQueryPlan":
+        """A row mask per query (a metadata filter per request; ott_query_masks): `masks` holds one entry per query of the batch, a
+        boolean array (True = keep; rows at or beyond its length are kept) or None.  Query b's hits are exactly the hits of the
+        same plan for that query alone with with_row_mask(common & masks[b]); with_row_mask stays the mask common to all.
+        Entries that are the same object or equal arrays are uploaded once, and their queries share batch passes.  Needs
+        per_query(); not together with with_row_ids, one_per_group, per_group, max_sim or mmr in this version."""
+        if self.error is None:
+            self.row_masks = masks
         return self
 
     def one_per_group(self) -> "VecQueryPlan":
@@ -406,6 +447,27 @@ class VecQueryPlan:
             if len(self.query_vectors) > 1 and self._mode != Mode.PerQuery:
                 raise OttersError("mmr takes one query; a batch needs per_query() (one MMR per query)")
             self._mmr_args()
+        if self.row_masks is not None:
+            if self.row_ids is not None:
+                raise OttersError("with_row_masks cannot be combined with with_row_ids in this version; put the ids into the masks")
+            if self._per_group is not None:
+                raise OttersError("with_row_masks cannot be combined with per_group in this version")
+            if self._grouped:
+                raise OttersError("with_row_masks cannot be combined with one_per_group in this version")
+            if self._max_sim:
+                raise OttersError("with_row_masks cannot be combined with max_sim: the query vectors are the tokens of one query")
+            if self._mmr is not None:
+                raise OttersError("with_row_masks cannot be combined with mmr in this version")
+            if self._mode != Mode.PerQuery:
+                raise OttersError("with_row_masks needs per_query(): a merged list over differently masked queries is not served")
+            try:
+                n_given = len(self.row_masks)
+            except TypeError:
+                raise OttersError("with_row_masks takes a sequence with one boolean array or None per query") from None
+            if n_given != len(self.query_vectors):
+                raise OttersError(f"with_row_masks: {n_given} masks for {len(self.query_vectors)} queries")
+            if len(self.query_vectors) > N.MASKS_MAX_QUERIES:
+                raise OttersError(f"with_row_masks: {len(self.query_vectors)} queries are above the {N.MASKS_MAX_QUERIES} one call takes")
         dim = self.vector_store.dim
         if isinstance(self.query_vectors, np.ndarray):  # a matrix: every row has the same length
             if self.query_vectors.shape[1] != dim:
@@ -432,11 +494,12 @@ class VecQueryPlan:
             k = store.group_count() if self._grouped or self._max_sim else store.len()  # src/vec.rs:213
         take = self.take_type if self.take_type is not None else TakeType.Max  # src/vec.rs:214
         fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
+        moq, qm = (None, None) if self.row_masks is None else lower_row_masks(self.row_masks)
         return ResolvedQuery(queries=queries, metric=int(self.search_metric), take=int(take), k=max(int(k), 0),
                              filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, mode=int(self._mode), path=int(self._path),
                              row_ids=None if self.row_ids is None else as_row_ids(self.row_ids), grouped=self._grouped,
                              max_sim=self._max_sim, group_size=0 if self._per_group is None else int(self._per_group), group_list=group_list,
-                             mmr=None if self._mmr is None else self._mmr_args())
+                             mmr=None if self._mmr is None else self._mmr_args(), mask_of_query=moq, query_masks=qm)
 
     def collect(self):  # src/vec.rs:205-311
         hits, counts = self.collect_arrays()[:2]  # (a per_group plan returns the hits' groups too)
@@ -1180,7 +1243,7 @@ class VecStore:
         return bool(self._n) and bool(N.lib().ott_store_batch_ready(self._handle()))
 
     def set_option(self, name: str, value: int) -> None:
-        """Behaviour switch of this store (ott_store_set_option; the twenty-two names are listed in include/otters_hip.h:
+        """Behaviour switch of this store (ott_store_set_option; the twenty-three names are listed in include/otters_hip.h:
         "tie_order", "hi_fmt", "hi_prebuild", ..., "force_fallback").  Results never depend on any but "tie_order"."""
         self._options[name] = int(value)
         if self._h is not None:
@@ -1292,6 +1355,13 @@ class VecStore:
             N.check(N.lib().ott_query_mmr(self._handle(), C.byref(d), None if ids is None else N.ptr(ids), 0 if ids is None else ids.size, fetch_k,
                                           float(lam), N.ptr(out), cap, C.byref(n_out), per, N.ptr(vals), C.byref(st)))
             rq.mmr_values = vals[: n_out.value].copy()
+        elif rq.mask_of_query is not None:  # a row mask per query: the distinct masks back to back, one word row each
+            qm = rq.query_masks
+            n_masks, bits = (0, 0) if qm is None else (int(qm.shape[0]), int(qm.shape[1]))
+            words = np.zeros(0, dtype="<u8") if not n_masks or not bits else np.ascontiguousarray(np.stack([N.pack_bits(m) for m in qm]))
+            moq = np.ascontiguousarray(rq.mask_of_query, dtype=np.uint32)
+            N.check(N.lib().ott_query_masks(self._handle(), C.byref(d), N.ptr(words) if words.size else None, n_masks if words.size else 0, bits,
+                                            N.ptr(moq), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         elif ids is None:
             N.check(N.lib().ott_query(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         else:
