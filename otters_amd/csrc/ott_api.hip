@@ -145,21 +145,32 @@ void build_plan(const ott_store* s, const uint64_t* chunk_mask, RunPlan& pl) {
 namespace ott {
 void make_run_plan(const ott_store* s, const uint64_t* chunk_mask, RunPlan& pl) { build_plan(s, chunk_mask, pl); }
 
+int check_desc_enums(const char* who, const ott_query_desc* d) {
+    const auto unknown = [who](const char* what) { return fail(OTT_ERR_INVALID, std::string(who) + ": unknown " + what); };
+    if (d->metric > OTT_METRIC_MANHATTAN) return unknown("metric");
+    if (d->take > OTT_TAKE_MAX) return unknown("take type");
+    if (d->filter_cmp > OTT_CMP_EQ) return unknown("filter comparator");
+    if (d->mode > OTT_MODE_PER_QUERY) return unknown("mode");
+    if (d->path > OTT_PATH_MFMA) return unknown("path");
+    return OTT_OK;
+}
+
+int check_device_row_mask(const char* who, const ott_store* s, const ott_query_desc* d) {
+    if (d->use_device_row_mask && s->evalmask_bits == 0 && s->n)
+        return fail(OTT_ERR_INVALID, std::string(who) + ": use_device_row_mask set but ott_store_eval_row_mask was not called");
+    return OTT_OK;
+}
+
 int validate_query(const ott_store* s, const ott_query_desc* d) {
+    int rc;
     if (!s) return fail(OTT_ERR_INVALID, "ott_query: store is NULL");
     if (!d) return fail(OTT_ERR_INVALID, "ott_query: desc is NULL");
     if (d->nq == 0) return fail(OTT_ERR_INVALID, "No queries provided");  // src/vec.rs:188-190
     if (!d->queries) return fail(OTT_ERR_INVALID, "ott_query: queries is NULL");
-    if (d->metric > OTT_METRIC_MANHATTAN) return fail(OTT_ERR_INVALID, "ott_query: unknown metric");
-    if (d->take > OTT_TAKE_MAX) return fail(OTT_ERR_INVALID, "ott_query: unknown take type");
-    if (d->filter_cmp > OTT_CMP_EQ) return fail(OTT_ERR_INVALID, "ott_query: unknown filter comparator");
-    if (d->mode > OTT_MODE_PER_QUERY) return fail(OTT_ERR_INVALID, "ott_query: unknown mode");
-    if (d->path > OTT_PATH_MFMA) return fail(OTT_ERR_INVALID, "ott_query: unknown path");
+    if ((rc = check_desc_enums("ott_query", d))) return rc;
     if (d->path == OTT_PATH_MFMA && d->metric == OTT_METRIC_MANHATTAN)  // |q - v| is not a dot product: no candidate pass bounds it
         return fail(OTT_ERR_UNSUPPORTED, "ott_query: the MFMA path does not score the Manhattan metric; use path AUTO or EXACT");
-    if (d->use_device_row_mask && s->evalmask_bits == 0 && s->n)
-        return fail(OTT_ERR_INVALID, "ott_query: use_device_row_mask set but ott_store_eval_row_mask was not called");
-    return OTT_OK;
+    return check_device_row_mask("ott_query", s, d);
 }
 
 void read_exact_events(ott_store* s, ott_stats* st) {
@@ -917,14 +928,10 @@ int query_common(ott_store* s, const ott_query_desc* d, ott_hit* out_host, void*
                  uint64_t* n_per_query, void* n_out_dev, ott_stats* stats_out) {
     int rc = validate_query(s, d);
     if (rc) return rc;
-    // rows of small appends still staged on the host go to the GPU first (that takes the store exclusively); an append may
-    // slip in before the shared lock is held, so the staged count is looked at again under it
     ott::host::SharedLock rd;  // the corpus cannot change while this query runs
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
-    ott_store* ctx = ott::ctx_acquire(s);
-    rc = query_on(ctx, d, out_host, out_dev, cap, n_out, n_per_query, n_out_dev, stats_out);
-    ott::ctx_release(ctx);
-    return rc;
+    if ((rc = lock_store_shared(s, rd))) return rc;
+    CtxLease ctx(s);
+    return query_on(ctx.c, d, out_host, out_dev, cap, n_out, n_per_query, n_out_dev, stats_out);
 }
 
 }  // namespace
@@ -951,11 +958,7 @@ static int merge_hits_common(ott_store* s, const void* lists_dev, uint64_t n_lis
     if (take > OTT_TAKE_MAX) return fail(OTT_ERR_INVALID, "ott_merge_hits_device: unknown take type");
     if (n_lists * list_len > 0xFFFFFFF0ull || n_groups > 0xFFFFull * 16) return fail(OTT_ERR_INVALID, "ott_merge_hits_device: too many candidates");
     ott::host::SharedLock rd(s->rw);
-    struct Ctx {  // query context for the duration of the call
-        ott_store* c;
-        explicit Ctx(ott_store* owner) : c(ott::ctx_acquire(owner)) {}
-        ~Ctx() { ott::ctx_release(c); }
-    } ctx(s);
+    CtxLease ctx(s);
     s = ctx.c;
     OTT_HIP(use_device(s));
     const uint64_t pool = n_lists * list_len;

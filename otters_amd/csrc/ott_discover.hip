@@ -3,9 +3,9 @@
 // their closeness to a target (a vector or a stored row); without a target, by a loss that is zero where every pair is won and
 // falls with every violated pair.  The examples are rows of the store, named by id: nothing of them crosses the host.
 //
-//   discover_gather_kernel  the pairs' stored rows (slot 2i the positive, 2i + 1 the negative of pair i) and a target ROW's into the
-//                           context's query block with their STORED inverse norms, as recommend_gather_kernel does; a vector target
-//                           went up with the block, with its host-side inverse norm (ott_query's).
+//   example_gather_kernel   (ott_recommend.hip, through ExampleFrame) the pairs' stored rows (slot 2i the positive, 2i + 1 the negative
+//                           of pair i) and a target ROW's into the context's query block with their STORED inverse norms; a vector
+//                           target went up with the block, with its host-side inverse norm (ott_query's).
 //   discover_sweep_kernel   sweep_tiles (ott_sweep_dev.h: the bits are the oracle's) and this epilogue per row: slots (0, 1) and
 //                           (2, 3) of a pass are whole pairs, or the target and nothing.  The row's 8-byte state {wins | flags,
 //                           y} is loaded (not in the first pass: the table is zero when found), a won pair adds one to wins, and y
@@ -13,7 +13,7 @@
 //                           order because the passes are launches on one stream), with a target the target score's ordinal.  A NaN
 //                           pair or target score sets the INVALID flag for good.  One streaming vector store; nothing is atomic.
 //                           A row no lane ever wrote (masked, deleted, pruned chunk) keeps {0, 0}: SEEN tells a written row apart.
-//   discover_clear_kernel   the examples' and the target row's states back to {0, 0}: they are never candidates.
+//   example_clear_kernel    (the same) the examples' and the target row's states back to {0, 0}: they are never candidates.
 //   discover_keys_kernel    no target.  One lane per row: candidate -> key = ord_of(loss, Max) << 32 | ~row in the key table and its
 //                           wins in a byte per row; the state is zeroed.  GroupTopK (one "group" per row) does the rest, and
 //                           discover_wins_kernel, behind the merge, looks the hits' wins up before the host waits.
@@ -46,35 +46,11 @@ struct DiscoverParams : SweepParams {
     uint32_t target_slot;   // 2 * n_pairs, or 0xFFFFFFFF: none
 };
 
-struct DiscoverGatherParams {
-    const float* rows;
-    const float* inv;
-    float* queries;  // [slots * dimq]
-    float* qinv;     // [slots]
-    uint2* state;    // discover_clear_kernel
-    uint32_t ld, dim, dimq, n;
-    uint32_t ex[DISC_MAX_SLOTS];  // the gathered slots' rows, every one below the store's length (checked on the host)
-};
-
 // what the kernels behind the sweep ask of a state
 struct DiscoverPick {
     uint32_t min_wins, has_target, take_max, cmp;
     float thr;
 };
-
-// blockIdx.x = slot.  Every float of the slot's dimq is written: the row's dim, then zeros.
-__global__ __launch_bounds__(256) void discover_gather_kernel(DiscoverGatherParams p) {
-    const uint32_t e = blockIdx.x;
-    if (e >= p.n) return;
-    const float* src = p.rows + (uint64_t)p.ex[e] * p.ld;
-    float* dst = p.queries + (size_t)e * p.dimq;
-    for (uint32_t i = threadIdx.x; i < p.dimq; i += blockDim.x) dst[i] = i < p.dim ? src[i] : 0.0f;
-    if (threadIdx.x == 0) p.qinv[e] = p.inv[p.ex[e]];
-}
-
-__global__ __launch_bounds__(128) void discover_clear_kernel(DiscoverGatherParams p) {
-    if (threadIdx.x < p.n) p.state[p.ex[threadIdx.x]] = make_uint2(0u, 0u);
-}
 
 template <int MK, int NQ>
 __global__ __launch_bounds__(64 * SW_WAVES) void discover_sweep_kernel(DiscoverParams p) {
@@ -208,21 +184,6 @@ __global__ __launch_bounds__(256) void discover_select_kernel(uint2* state, uint
 
 namespace {
 
-template <int MK>
-int launch_sweep_mk(ott_store* s, const DiscoverParams& p, uint32_t grid) {
-    hipLaunchKernelGGL((discover_sweep_kernel<MK, (int)SW_NQ>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-int launch_sweep(ott_store* s, const DiscoverParams& p, uint32_t grid) {
-    switch (metric_kind(p.metric)) {
-        case MK_L2: return launch_sweep_mk<MK_L2>(s, p, grid);
-        case MK_L1: return launch_sweep_mk<MK_L1>(s, p, grid);
-        default: return launch_sweep_mk<MK_DOT>(s, p, grid);
-    }
-}
-
 uint32_t row_blocks(const ott_store* s, uint32_t n) {
     uint32_t blocks = (n + 255) / 256;
     if (blocks > (uint32_t)s->n_cu * 8) blocks = (uint32_t)s->n_cu * 8;
@@ -273,33 +234,27 @@ int refuse(DiscRefusal r, uint64_t id = 0, uint64_t len = 0) {
 int run_discover(ott_store* s, const ott_query_desc* d, const DiscSlots& sl, uint32_t min_wins, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint32_t* wins_of_hit,
                  ott_stats* stats_out) {
     int rc;
-    OTT_HIP(use_device(s));
-    const uint64_t t0 = now_ns();
-    ott_stats st;
-    const uint32_t n = (uint32_t)s->n;
     const bool has_target = sl.target != DISC_TARGET_NONE;
+    ExampleFrame fr{s, d, "ott_query_discover", k_eff, stats_out};
     DiscoverParams p{};
-    uint32_t grid = 0;
     // a vector target goes up in its slot, the last, with the host-side inverse norm of ott_query; the other slots go up zeroed
     std::vector<float> qblock;
     if (sl.target == DISC_TARGET_VECTOR) {
         qblock.assign((size_t)sl.n_slots * s->dim, 0.0f);
         memcpy(qblock.data() + (size_t)(sl.n_slots - 1) * s->dim, d->queries, (size_t)s->dim * 4);
     }
-    if ((rc = sweep_prologue(s, d, qblock.empty() ? nullptr : qblock.data(), sl.n_slots, &st, &p, &grid))) return rc;
+    if ((rc = fr.begin(&p, qblock.empty() ? nullptr : qblock.data(), sl.n_slots))) return rc;
     uint64_t total = 0;
-    if (grid != 0) {
-        st.bytes_scanned = (uint64_t)st.passes * (st.vectors_compared / sl.n_slots) * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));  // (no group id is read)
-        // the states are left zeroed by the keys / select kernel, the keys by the top-k's select / compact kernel
-        if ((rc = ensure_zeroed(s, s->d_rectable, s->rectable_clean, disc_state_bytes(n)))) return rc;
-        if ((rc = ensure_zeroed(s, s->d_gtable, s->gtable_clean, disc_key_bytes(n)))) return rc;
+    if (fr.grid != 0) {
+        // (the states are left zeroed by the keys / select kernel)
+        const uint32_t n = fr.n;
+        GroupTopK& tk = fr.tk;
         if ((rc = s->d_disc.ensure(disc_scratch_bytes(has_target, n, k_eff)))) return rc;
-        unsigned long long* keys = (unsigned long long*)s->d_gtable.p;
+        unsigned long long* keys = fr.keys;
         uint32_t* hdr = (uint32_t*)s->d_disc.p;
         DiscAbove* list = (DiscAbove*)((char*)s->d_disc.p + disc_list_off());
         uint8_t* wins8 = (uint8_t*)s->d_disc.p + disc_wins_off();
-        p.gid = nullptr;  // (a store with groups has ids: this sweep does not read them)
-        p.state = (uint2*)s->d_rectable.p;
+        p.state = fr.state;
         p.n_pair_slots = 2 * sl.n_pairs;
         p.target_slot = disc_target_slot(sl);
         const bool take_max = p.take_max != 0;
@@ -310,26 +265,8 @@ int run_discover(ott_store* s, const ott_query_desc* d, const DiscSlots& sl, uin
         pick.cmp = (uint32_t)d->filter_cmp;
         pick.thr = d->filter_thr;
 
-        DiscoverGatherParams gp;
-        memset(&gp, 0, sizeof(gp));
-        gp.rows = s->d_rows;
-        gp.inv = s->d_inv;
-        gp.queries = (float*)s->d_queries.p;
-        gp.qinv = (float*)((char*)s->d_queries.p + s->in_off_qinv);
-        gp.state = p.state;
-        gp.ld = s->ld;
-        gp.dim = s->dim;
-        gp.dimq = s->dimq;
-        gp.n = sl.n_gather;
-        memcpy(gp.ex, sl.rows, sizeof(uint32_t) * sl.n_gather);
-
-        GroupTopK tk;
-        tk.n_groups = n;
-        tk.nq = 1;
-        tk.k = k_eff;
-        tk.take_max = has_target ? take_max : true;  // (the keys of a context search hold the loss's ordinal under Max)
-        tk.also_clean = &s->rectable_clean;
-        if ((rc = tk.prepare(s, nullptr))) return rc;
+        // (the keys of a context search hold the loss's ordinal under Max)
+        if ((rc = fr.prepare(sl.rows, sl.n_gather, has_target ? take_max : true, &s->rectable_clean))) return rc;
         // what the host reads behind the one wait
         const size_t list_bytes = disc_list_off() + (size_t)k_eff * sizeof(DiscAbove);
         WinsLookup wl{};
@@ -350,26 +287,18 @@ int run_discover(ott_store* s, const ott_query_desc* d, const DiscSlots& sl, uin
                 tk.after_arg = &wl;
             }
         }
-        const bool timing = stats_out != nullptr;
-        hipLaunchKernelGGL(discover_gather_kernel, dim3(sl.n_gather), dim3(256), 0, s->stream, gp);
-        OTT_HIP(hipGetLastError());
-        if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
-        for (uint32_t ps = 0; ps < st.passes; ps++) {
-            p.q0 = ps * SW_NQ;
-            if ((rc = launch_sweep(s, p, grid))) return rc;
-        }
-        hipLaunchKernelGGL(discover_clear_kernel, dim3(1), dim3(128), 0, s->stream, gp);
-        OTT_HIP(hipGetLastError());
+        rc = fr.sweep(SW_NQ, [&](uint32_t q0) {  // (NQ = SW_NQ alone: a pass holds whole pairs)
+            p.q0 = q0;
+            return launch_sweep<false>(s->stream, p, SW_NQ, fr.grid, OTT_SWEEP_KERNEL(discover_sweep_kernel));
+        });
+        if (rc) return rc;
         uint64_t n1 = 0;
         if (!has_target) {
             hipLaunchKernelGGL(discover_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s->stream, p.state, n, pick, keys, wins8);
             OTT_HIP(hipGetLastError());
-            if ((rc = tk.pass(s, keys, 0, 1))) return rc;
-            if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
+            if ((rc = fr.rank())) return rc;
             if (wins_of_hit && !tk.lists_path) OTT_HIP(hipMemcpyAsync(s->h_disc.p, wins8, n, hipMemcpyDeviceToHost, s->stream));
-            if ((rc = tk.finish(s, timing, out, &n1, nullptr))) return rc;
-            if (timing) read_exact_events(s, &st);
-            if (n1 > k_eff) return fail(OTT_ERR_HIP, "ott_query_discover: the top-k returned more hits than k");
+            if ((rc = fr.finish(out, &n1))) return rc;
             total = n1;
             if (wins_of_hit) {
                 if (tk.lists_path) {
@@ -385,12 +314,9 @@ int run_discover(ott_store* s, const ott_query_desc* d, const DiscSlots& sl, uin
             OTT_HIP(hipGetLastError());
             hipLaunchKernelGGL(discover_select_kernel, dim3(row_blocks(s, n)), dim3(256), 0, s->stream, p.state, n, pick, hdr, n_levels, k_eff, keys, list);
             OTT_HIP(hipGetLastError());
-            if ((rc = tk.pass(s, keys, 0, 1))) return rc;
-            if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
+            if ((rc = fr.rank())) return rc;
             OTT_HIP(hipMemcpyAsync(s->h_disc.p, s->d_disc.p, list_bytes, hipMemcpyDeviceToHost, s->stream));
-            if ((rc = tk.finish(s, timing, out, &n1, nullptr))) return rc;
-            if (timing) read_exact_events(s, &st);
-            if (n1 > k_eff) return fail(OTT_ERR_HIP, "ott_query_discover: the top-k returned more hits than k");
+            if ((rc = fr.finish(out, &n1))) return rc;
             const uint32_t* hh = (const uint32_t*)s->h_disc.p;
             uint64_t n_above = 0;
             const uint32_t cut = disc_level_cut(hh, n_levels, k_eff, &n_above);
@@ -413,8 +339,7 @@ int run_discover(ott_store* s, const ott_query_desc* d, const DiscSlots& sl, uin
         }
     }
     if (n_out) *n_out = total;
-    st.total_ns = now_ns() - t0;
-    if (stats_out) *stats_out = st;
+    fr.end();
     return OTT_OK;
 }
 
@@ -433,23 +358,18 @@ int ott_query_discover(ott_store* s, const ott_query_desc* d, uint64_t target_ro
     DiscRefusal why = disc_check_args(n_pairs, positive == nullptr, negative == nullptr, flags, d->nq, d->queries == nullptr, target_row != DISC_NO_ROW, min_wins,
                                       d->mode == OTT_MODE_PER_QUERY, d->path == OTT_PATH_MFMA);
     if (why != DISC_OK) return refuse(why);
-    if (d->metric > OTT_METRIC_MANHATTAN) return fail(OTT_ERR_INVALID, "ott_query_discover: unknown metric");
-    if (d->take > OTT_TAKE_MAX) return fail(OTT_ERR_INVALID, "ott_query_discover: unknown take type");
-    if (d->filter_cmp > OTT_CMP_EQ) return fail(OTT_ERR_INVALID, "ott_query_discover: unknown filter comparator");
-    if (d->mode > OTT_MODE_PER_QUERY) return fail(OTT_ERR_INVALID, "ott_query_discover: unknown mode");
-    if (d->path > OTT_PATH_MFMA) return fail(OTT_ERR_INVALID, "ott_query_discover: unknown path");
+    int rc;
+    if ((rc = check_desc_enums("ott_query_discover", d))) return rc;
     if (!s) return fail(OTT_ERR_INVALID, "ott_query_discover: store is NULL");
     const uint64_t len = ott_store_len(s);
     if ((why = disc_check_store(s->multi != nullptr, len)) != DISC_OK) return refuse(why);
-    if (d->use_device_row_mask && s->evalmask_bits == 0 && s->n)
-        return fail(OTT_ERR_INVALID, "ott_query_discover: use_device_row_mask set but ott_store_eval_row_mask was not called");
+    if ((rc = check_device_row_mask("ott_query_discover", s, d))) return rc;
     DiscSlots sl;
     uint64_t bad = 0;
     if ((why = disc_slots(positive, negative, (uint32_t)n_pairs, target_row, d->nq == 1, len, &sl, &bad)) != DISC_OK) return refuse(why, bad, len);
     if ((why = disc_check_out(disc_k_eff(d->k, len), cap, out == nullptr)) != DISC_OK) return refuse(why);
     ott::host::SharedLock rd;  // the corpus cannot change while this query runs
-    int rc;
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
+    if ((rc = lock_store_shared(s, rd))) return rc;
     // what the checks above read without the lock is read again, and k_eff only here: appends (this call's own flush of rows another
     // thread staged after `len` was read) or a compact may have come in between, so the store may be longer or shorter than `len`
     if ((why = disc_check_store(false, s->n)) != DISC_OK) return refuse(why);
@@ -460,10 +380,8 @@ int ott_query_discover(ott_store* s, const ott_query_desc* d, uint64_t target_ro
     if (n_out) *n_out = 0;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (k_eff == 0) return OTT_OK;
-    ott_store* ctx = ctx_acquire(s);
-    rc = run_discover(ctx, d, sl, min_wins, k_eff, out, n_out, wins_of_hit, stats);
-    ctx_release(ctx);
-    return rc;
+    CtxLease ctx(s);
+    return run_discover(ctx.c, d, sl, min_wins, k_eff, out, n_out, wins_of_hit, stats);
 }
 
 }  // extern "C"

@@ -382,10 +382,7 @@ int run_ids_as_mask(ott_store* s, const ott_query_desc* d, const std::vector<uin
         OTT_HIP(hipGetLastError());
         OTT_HIP(hipStreamSynchronize(s->stream));  // (h_stage is the query's own staging next)
     }
-    struct IdMaskGuard {
-        ott_store* c;
-        ~IdMaskGuard() { c->cur_idmask = nullptr; }
-    } guard{s};
+    IdMaskGuard guard{s};
     s->cur_idmask = d_words;
     return query_on(s, d, out, nullptr, cap, n_out, n_per_query, nullptr, stats_out);
 }
@@ -480,11 +477,9 @@ int ott_query_ids(ott_store* s, const ott_query_desc* d, const uint64_t* ids, ui
     d2.k = k_eff;  // at most `pool` pairs can pass: the same hits, and the paths below size their buffers by the list
     if (s->multi) return multi_query_ids(s, &d2, u, out, cap, n_out, n_per_query, stats);
     ott::host::SharedLock rd;  // the corpus cannot change while this query runs
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
-    ott_store* ctx = ctx_acquire(s);
-    rc = query_ids_on(ctx, &d2, u, n_ids, out, cap, n_out, n_per_query, stats);
-    ctx_release(ctx);
-    return rc;
+    if ((rc = lock_store_shared(s, rd))) return rc;
+    CtxLease ctx(s);
+    return query_ids_on(ctx.c, &d2, u, n_ids, out, cap, n_out, n_per_query, stats);
 }
 
 int ott_store_score_rows(ott_store* s, const float* queries, uint32_t nq, uint32_t metric, const uint64_t* ids, uint64_t n_ids, float* out_scores) {
@@ -499,11 +494,9 @@ int ott_store_score_rows(ott_store* s, const float* queries, uint32_t nq, uint32
     if (s->multi) return multi_score_rows(s, queries, nq, metric, ids, n_ids, out_scores);
     if (s->dimq > G8_QMAX) return fail(OTT_ERR_UNSUPPORTED, "ott_store_score_rows: rows of more than 2048 floats are not served");
     ott::host::SharedLock rd;
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
-    ott_store* ctx = ctx_acquire(s);
-    rc = score_rows_on(ctx, queries, nq, metric, ids, n_ids, out_scores);
-    ctx_release(ctx);
-    return rc;
+    if ((rc = lock_store_shared(s, rd))) return rc;
+    CtxLease ctx(s);
+    return score_rows_on(ctx.c, queries, nq, metric, ids, n_ids, out_scores);
 }
 
 }  // extern "C"

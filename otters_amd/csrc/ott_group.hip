@@ -142,22 +142,6 @@ __global__ __launch_bounds__(256) void group_gather_kernel(const uint32_t* __res
 
 namespace {
 
-template <int MK>
-int launch_sweep_mk(ott_store* s, const GroupParams& p, uint32_t nq_tile, uint32_t grid) {
-    if (nq_tile == 1) hipLaunchKernelGGL((group_sweep_kernel<MK, 1>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    else hipLaunchKernelGGL((group_sweep_kernel<MK, (int)SW_NQ>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-int launch_sweep(ott_store* s, const GroupParams& p, uint32_t nq_tile, uint32_t grid) {
-    switch (metric_kind(p.metric)) {
-        case MK_L2: return launch_sweep_mk<MK_L2>(s, p, nq_tile, grid);
-        case MK_L1: return launch_sweep_mk<MK_L1>(s, p, nq_tile, grid);
-        default: return launch_sweep_mk<MK_DOT>(s, p, nq_tile, grid);
-    }
-}
-
 int launch_group_select(ott_store* s, unsigned long long* table, uint32_t n_groups, uint64_t q_stride, uint32_t q0, uint32_t nq_here, uint32_t k, int E, Cand* lists,
                         uint32_t n_lists) {
 #define OTT_GSEL(Ev)                                                                                                                       \
@@ -212,7 +196,7 @@ int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* o
         if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
         for (uint32_t ps = 0; ps < st.passes; ps++) {
             p.q0 = ps * tile;
-            if ((rc = launch_sweep(s, p, tile, grid))) return rc;
+            if ((rc = launch_sweep(s->stream, p, tile, grid, OTT_SWEEP_KERNEL(group_sweep_kernel)))) return rc;
             if ((rc = tk.pass(s, p.table, p.q0, (nq - p.q0) < tile ? (nq - p.q0) : tile))) return rc;
         }
         if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
@@ -388,28 +372,25 @@ int group_grow(ott_store* s, uint64_t ncap) {
 int group_ids_of_hits(ott_store* s, const ott_hit* hits, uint64_t n, uint32_t* out) {
     if (n == 0) return OTT_OK;
     if (!s->d_gid) return fail(OTT_ERR_INVALID, "group_ids_of_hits: no group ids are set");
-    ott_store* ctx = ctx_acquire(s);
-    const int rc = [&]() -> int {
-        int r;
-        OTT_HIP(use_device(ctx));
-        if ((r = ctx->h_stage.ensure((size_t)n * 8))) return r;
-        uint64_t* hr = (uint64_t*)ctx->h_stage.p;
-        for (uint64_t i = 0; i < n; i++) {
-            hr[i] = hits[i].index - ctx->base_offset;
-            if (hr[i] >= ctx->gid_n) return fail(OTT_ERR_INVALID, "group_ids_of_hits: a hit outside the store's rows");
-        }
-        if ((r = ctx->d_gather.ensure(64 + (size_t)n * 12))) return r;
-        uint64_t* d_rows = (uint64_t*)((char*)ctx->d_gather.p + 64);
-        uint32_t* d_out = (uint32_t*)(d_rows + n);
-        OTT_HIP(hipMemcpyAsync(d_rows, hr, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(group_gather_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_gid, (const uint64_t*)d_rows, n, d_out);
-        OTT_HIP(hipGetLastError());
-        OTT_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        OTT_HIP(hipStreamSynchronize(ctx->stream));
-        return OTT_OK;
-    }();
-    ctx_release(ctx);
-    return rc;
+    CtxLease lease(s);
+    ott_store* ctx = lease.c;
+    int r;
+    OTT_HIP(use_device(ctx));
+    if ((r = ctx->h_stage.ensure((size_t)n * 8))) return r;
+    uint64_t* hr = (uint64_t*)ctx->h_stage.p;
+    for (uint64_t i = 0; i < n; i++) {
+        hr[i] = hits[i].index - ctx->base_offset;
+        if (hr[i] >= ctx->gid_n) return fail(OTT_ERR_INVALID, "group_ids_of_hits: a hit outside the store's rows");
+    }
+    if ((r = ctx->d_gather.ensure(64 + (size_t)n * 12))) return r;
+    uint64_t* d_rows = (uint64_t*)((char*)ctx->d_gather.p + 64);
+    uint32_t* d_out = (uint32_t*)(d_rows + n);
+    OTT_HIP(hipMemcpyAsync(d_rows, hr, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(group_gather_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_gid, (const uint64_t*)d_rows, n, d_out);
+    OTT_HIP(hipGetLastError());
+    OTT_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    OTT_HIP(hipStreamSynchronize(ctx->stream));
+    return OTT_OK;
 }
 
 void group_drop(ott_store* s) {
@@ -488,17 +469,15 @@ int ott_query_groups(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64
     if ((rc = check_group_ids(s, "ott_query_groups", false))) return rc;
     if (s->multi) return multi_query_groups(s, d, out, cap, n_out, n_per_query, stats);
     ott::host::SharedLock rd;  // the corpus and the group ids cannot change while this query runs
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
+    if ((rc = lock_store_shared(s, rd))) return rc;
     // what the checks above read without the lock is read again, and k_eff only here: a set_groups may have come in between
     if ((rc = check_group_ids(s, "ott_query_groups", true))) return rc;
     const uint64_t k_eff = d->k < s->n_groups ? d->k : s->n_groups;
     if (cap < k_eff * d->nq) return fail(OTT_ERR_INVALID, "ott_query_groups: output capacity is smaller than nq * min(k, n_groups)");
     if (!out && cap) return fail(OTT_ERR_INVALID, "ott_query_groups: out is NULL");
     if (k_eff == 0) return OTT_OK;
-    ott_store* ctx = ctx_acquire(s);
-    rc = run_groups(ctx, d, k_eff, out, n_out, n_per_query, stats);
-    ctx_release(ctx);
-    return rc;
+    CtxLease ctx(s);
+    return run_groups(ctx.c, d, k_eff, out, n_out, n_per_query, stats);
 }
 
 }  // extern "C"

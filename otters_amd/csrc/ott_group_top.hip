@@ -110,22 +110,6 @@ __global__ __launch_bounds__(256) void group_emit_kernel(const unsigned long lon
 
 namespace {
 
-template <int MK>
-int launch_sweep_mk(ott_store* s, const GroupTopParams& p, uint32_t nq_tile, uint32_t grid) {
-    if (nq_tile == 1) hipLaunchKernelGGL((group_top_sweep_kernel<MK, 1>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    else hipLaunchKernelGGL((group_top_sweep_kernel<MK, (int)SW_NQ>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-int launch_sweep(ott_store* s, const GroupTopParams& p, uint32_t nq_tile, uint32_t grid) {
-    switch (metric_kind(p.metric)) {
-        case MK_L2: return launch_sweep_mk<MK_L2>(s, p, nq_tile, grid);
-        case MK_L1: return launch_sweep_mk<MK_L1>(s, p, nq_tile, grid);
-        default: return launch_sweep_mk<MK_DOT>(s, p, nq_tile, grid);
-    }
-}
-
 // The winners' groups read back out of the deeper planes, and the table zeroed behind it.  `win`: per query in query order, best
 // first, `per[q]` of them.  Hits, counts and group ids go to the caller's buffers.
 int emit_groups(ott_store* s, const GroupTopParams& p, const std::vector<ott_hit>& win, const std::vector<uint64_t>& per, size_t table_bytes, ott_hit* out,
@@ -209,7 +193,7 @@ int run_groups_top(ott_store* s, const ott_query_desc* d, uint32_t m, uint64_t k
         const uint32_t tile = nq == 1 ? 1u : SW_NQ;
         for (uint32_t ps = 0; ps < st.passes; ps++) {
             p.q0 = ps * tile;
-            if ((rc = launch_sweep(s, p, tile, grid))) return rc;
+            if ((rc = launch_sweep(s->stream, p, tile, grid, OTT_SWEEP_KERNEL(group_top_sweep_kernel)))) return rc;
             if ((rc = tk.pass(s, p.table + (size_t)p.q0 * m * ng, p.q0, (nq - p.q0) < tile ? (nq - p.q0) : tile))) return rc;
         }
         if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
@@ -259,7 +243,7 @@ int ott_query_groups_top(ott_store* s, const ott_query_desc* d, uint32_t group_s
                           "or a smaller group_size";
     if (!table_fits(s->n_groups)) return fail(OTT_ERR_UNSUPPORTED, too_big);
     ott::host::SharedLock rd;  // the corpus and the group ids cannot change while this query runs
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
+    if ((rc = lock_store_shared(s, rd))) return rc;
     // what the checks above read without the lock is read again, and k_eff only here: a set_groups may have come in between
     if ((rc = check_group_ids(s, "ott_query_groups_top", true))) return rc;
     if (!table_fits(s->n_groups)) return fail(OTT_ERR_UNSUPPORTED, too_big);
@@ -267,11 +251,12 @@ int ott_query_groups_top(ott_store* s, const ott_query_desc* d, uint32_t group_s
     if (cap < k_eff * d->nq * group_size) return fail(OTT_ERR_INVALID, "ott_query_groups_top: output capacity is smaller than nq * min(k, n_groups) * group_size");
     if (!out && cap) return fail(OTT_ERR_INVALID, "ott_query_groups_top: out is NULL");
     if (k_eff == 0) return OTT_OK;
-    ott_store* ctx = ctx_acquire(s);
     uint64_t total = 0;
-    if (group_size == 1) rc = run_groups(ctx, d, k_eff, out, &total, n_per_query, stats);
-    else rc = run_groups_top(ctx, d, group_size, k_eff, out, &total, n_per_query, group_of_hit, stats);
-    ctx_release(ctx);
+    {
+        CtxLease ctx(s);
+        if (group_size == 1) rc = run_groups(ctx.c, d, k_eff, out, &total, n_per_query, stats);
+        else rc = run_groups_top(ctx.c, d, group_size, k_eff, out, &total, n_per_query, group_of_hit, stats);
+    }
     if (rc) return rc;
     if (n_out) *n_out = total;
     if (group_size == 1 && group_of_hit) return group_ids_of_hits(s, out, total, group_of_hit);  // the existing gather (the store is still held shared)

@@ -449,6 +449,24 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
 constexpr size_t OTT_MAX_WORKERS = 15;
 ott_store* ctx_acquire(ott_store* s);  // returns s or a worker, with its `mu` held
 void ctx_release(ott_store* w);
+// a query context for the rest of the scope
+struct CtxLease {
+    ott_store* c;
+    explicit CtxLease(ott_store* owner) : c(ctx_acquire(owner)) {}
+    ~CtxLease() { ctx_release(c); }
+    CtxLease(const CtxLease&) = delete;
+    CtxLease& operator=(const CtxLease&) = delete;
+};
+// the store shared for a query: rows of small appends still staged on the host go to the GPU first (that takes the store exclusively);
+// an append may slip in before the shared lock is held, so the staged count is looked at again under it
+inline int lock_store_shared(ott_store* s, ott::host::SharedLock& rd) {
+    return ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); });
+}
+// the context's id mask (cur_idmask) is the caller's for the rest of the scope, and nobody's after it
+struct IdMaskGuard {
+    ott_store* c;
+    ~IdMaskGuard() { c->cur_idmask = nullptr; }
+};
 // ---- ott_planes.hip: the cascade's planes (struct PlaneSet).  Everything below takes the planes' mutex itself. -----------------
 // The steps of the life cycle that belong to whoever changes the store (the caller holds it exclusively, on its device):
 void planes_drop(ott_store* own);     // the rows moved or changed wholesale: every plane goes (rebuilt on demand)
@@ -722,10 +740,13 @@ inline void merge_heads(std::vector<const ott_hit*>& head, const std::vector<con
     }
 }
 
-// ott_api.hip.  validate_query: argument checks of ott_query.  query_on: one query on a context whose `mu` the caller
+// ott_api.hip.  check_desc_enums, check_device_row_mask: the descriptor's enum fields are known ones, and use_device_row_mask has an
+// evaluated mask to use — for entry point `who`, which the messages name.  validate_query: argument checks of ott_query.  query_on: one query on a context whose `mu` the caller
 // holds (and the owner's `rw`, shared).  Device output (out_dev != nullptr): [groups][cap / groups] slots, sentinel
 // padded.  nosync: do not wait for the stream before returning — on the EXACT path nothing then waits on the host at all
 // (*events_pending tells the caller to read the kernel timing events ev[3..5] after its own synchronisation).
+int check_desc_enums(const char* who, const ott_query_desc* d);
+int check_device_row_mask(const char* who, const ott_store* s, const ott_query_desc* d);
 int validate_query(const ott_store* s, const ott_query_desc* d);
 int query_on(ott_store* s, const ott_query_desc* d, ott_hit* out_host, void* out_dev, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query,
              void* n_out_dev, ott_stats* stats_out, bool nosync = false, bool* events_pending = nullptr);
@@ -802,6 +823,39 @@ struct GroupTopK {
     int prepare(ott_store* s, const char* too_many_pairs);  // the refusal's text for more than 2^32 - 16 pairs (nullptr: cannot happen)
     int pass(ott_store* s, unsigned long long* table, uint32_t q0, uint32_t nq_here);
     int finish(ott_store* s, bool timing, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query);
+};
+// ott_recommend.hip: the host frame of a sweep whose queries are EXAMPLE ROWS of the store (recommend, sum_scores, discover), on a
+// context whose `mu` the caller holds.  A run calls the steps in this order and puts what is its own between them:
+//   begin    sweep_prologue (host_block: a query block that goes up from the host, nullptr = n_slots zeroed slots), bytes_scanned,
+//            the 8-byte state per row (d_rectable) and the key table (d_gtable) zero, p->gid = nullptr.  grid == 0 after it: no row
+//            survives, nothing else is called but end
+//   prepare  the rows to gather and the top-k over the key table with one "group" per row
+//   sweep    example_gather_kernel, ev[3], a launch_pass(q0) per pass of `tile` slots, example_clear_kernel (an example is no candidate)
+//   rank     behind the run's keys kernel(s): tk.pass, ev[4]
+//   finish   tk.finish, the events, the "more hits than k" failure
+//   end      total_ns, the stats out
+struct ExampleFrame {
+    ott_store* s;
+    const ott_query_desc* d;
+    const char* who;  // the entry point the messages name
+    uint64_t k_eff;
+    ott_stats* stats_out;
+    uint64_t t0 = now_ns();  // total_ns counts from the frame's construction
+    ott_stats st;
+    uint32_t grid = 0;
+    uint32_t n = 0;                      // the store's rows
+    uint2* state = nullptr;              // [n]
+    unsigned long long* keys = nullptr;  // [n]
+    const uint32_t* rows = nullptr;      // the gathered rows, every one below n
+    uint32_t n_rows = 0;
+    GroupTopK tk;
+    bool timing() const { return stats_out != nullptr; }
+    int begin(SweepParams* p, const float* host_block, uint32_t n_slots);
+    int prepare(const uint32_t* gather_rows, uint32_t n_gather, bool tk_take_max, bool* also_clean);
+    int sweep(uint32_t tile, const std::function<int(uint32_t q0)>& launch_pass);
+    int rank();
+    int finish(ott_hit* out, uint64_t* n_hits);
+    void end();
 };
 // ott_group.hip: the grouped query on a context whose `mu` the caller holds; k_eff = min(k, n_groups) >= 1
 int run_groups(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats_out);

@@ -99,22 +99,6 @@ int launch_union(ott_store* s, const UnionParams& u) {
     return OTT_OK;
 }
 
-template <int MK>
-int launch_masks_sweep_mk(ott_store* s, const MasksParams& p, uint32_t nq_tile, uint32_t grid) {
-    if (nq_tile == 1) hipLaunchKernelGGL((masks_sweep_kernel<MK, 1>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    else hipLaunchKernelGGL((masks_sweep_kernel<MK, (int)SW_NQ>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-int launch_masks_sweep(ott_store* s, const MasksParams& p, uint32_t nq_tile, uint32_t grid) {
-    switch (metric_kind(p.metric)) {
-        case MK_L2: return launch_masks_sweep_mk<MK_L2>(s, p, nq_tile, grid);
-        case MK_L1: return launch_masks_sweep_mk<MK_L1>(s, p, nq_tile, grid);
-        default: return launch_masks_sweep_mk<MK_DOT>(s, p, nq_tile, grid);
-    }
-}
-
 // where the masks of one call are once they are on the device: host mask i in the context's scratch, slot masks in place
 struct MaskTable {
     const uint64_t* host0 = nullptr;  // the first uploaded host mask
@@ -263,7 +247,7 @@ int run_masks_sweep(ott_store* s, const ott_query_desc* d, const uint32_t* moq, 
                 p.row_mask = common;
                 p.row_mask_bits = common_bits;
             }
-            if ((rc = launch_masks_sweep(s, p, tile, grid))) return rc;
+            if ((rc = launch_sweep(s->stream, p, tile, grid, OTT_SWEEP_KERNEL(masks_sweep_kernel)))) return rc;
             if ((rc = tk.pass(s, p.table, p.q0, nq_here))) return rc;
         }
         if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
@@ -460,7 +444,7 @@ int ott_query_masks(ott_store* s, const ott_query_desc* d, const uint64_t* masks
     }
 
     ott::host::SharedLock rd;  // the corpus and the slots cannot change while the batch runs
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
+    if ((rc = lock_store_shared(s, rd))) return rc;
     const MasksRefusal rs = masks_check_slots(nq, moq, s->mslot_bits, &bad);
     if (rs != MASKS_OK) return refuse(rs, nq, moq, n_masks, bad);
     RunPlan rp;
@@ -473,17 +457,20 @@ int ott_query_masks(ott_store* s, const ott_query_desc* d, const uint64_t* masks
 
     const bool eligible = masks_sweep_eligible(s->opt.tie_order, d->path, false, s->n, k_eff, nq);
     const bool sweep = masks_takes_sweep(s->opt.masks_sweep, eligible, s->n, s->dim, nq, pl.n_distinct, pl.largest_group);
-    ott_store* ctx = ctx_acquire(s);
-    rc = [&]() -> int {
-        int r2;
-        OTT_HIP(use_device(ctx));
-        MaskTable mt;
-        if ((r2 = upload_masks(ctx, masks, n_masks, mask_bits, mt))) return r2;
-        if (sweep) return run_masks_sweep(ctx, d, moq, pl, mt, k_eff, res, stats ? &st : nullptr);
-        return run_by_group(ctx, d, moq, pl, mt, k_eff, res, stats ? &st : nullptr);
-    }();
-    if (rc) (void)hipStreamSynchronize(ctx->stream);  // (the upload reads the caller's masks: nothing of this call is in flight when it returns)
-    ctx_release(ctx);
+    {
+        CtxLease lease(s);
+        ott_store* ctx = lease.c;
+        rc = [&]() -> int {
+            int r2;
+            OTT_HIP(use_device(ctx));
+            MaskTable mt;
+            if ((r2 = upload_masks(ctx, masks, n_masks, mask_bits, mt))) return r2;
+            if (sweep) return run_masks_sweep(ctx, d, moq, pl, mt, k_eff, res, stats ? &st : nullptr);
+            return run_by_group(ctx, d, moq, pl, mt, k_eff, res, stats ? &st : nullptr);
+        }();
+        // (the upload reads the caller's masks: nothing of this call is in flight when it returns, and the context is given back after that)
+        if (rc) (void)hipStreamSynchronize(ctx->stream);
+    }
     if (rc) return rc;
     return emit();
 }

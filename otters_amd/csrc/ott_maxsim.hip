@@ -119,29 +119,12 @@ int launch_maxsim_reduce(ott_store* s, uint32_t* table, uint32_t n_slots, uint32
 
 namespace {
 
-template <int MK, bool FOLD>
-int launch_sweep_mk(ott_store* s, const MaxsimParams& p, uint32_t nq_tile, uint32_t grid) {
-    if (nq_tile == 1) hipLaunchKernelGGL((maxsim_sweep_kernel<MK, 1, FOLD>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    else hipLaunchKernelGGL((maxsim_sweep_kernel<MK, (int)SW_NQ, FOLD>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-template <bool FOLD>
-int launch_sweep_fold(ott_store* s, const MaxsimParams& p, uint32_t nq_tile, uint32_t grid) {
-    switch (metric_kind(p.metric)) {
-        case MK_L2: return launch_sweep_mk<MK_L2, FOLD>(s, p, nq_tile, grid);
-        case MK_L1: return launch_sweep_mk<MK_L1, FOLD>(s, p, nq_tile, grid);
-        default: return launch_sweep_mk<MK_DOT, FOLD>(s, p, nq_tile, grid);
-    }
-}
-
-int launch_sweep(ott_store* s, const MaxsimParams& p, uint32_t nq_tile, uint32_t grid) {
+int launch_maxsim_sweep(ott_store* s, const MaxsimParams& p, uint32_t nq_tile, uint32_t grid) {
 #ifdef OTT_MFMA_DEBUG_BUILD
     // the diagnostic build carries both epilogues (option maxsim_fold: the A/B of benchmarks/maxsim.py)
-    if (s->opt.maxsim_fold >= 0 && (s->opt.maxsim_fold != 0) != MS_FOLD) return launch_sweep_fold<!MS_FOLD>(s, p, nq_tile, grid);
+    if (s->opt.maxsim_fold >= 0 && (s->opt.maxsim_fold != 0) != MS_FOLD) return launch_sweep(s->stream, p, nq_tile, grid, OTT_SWEEP_KERNEL(maxsim_sweep_kernel, !MS_FOLD));
 #endif
-    return launch_sweep_fold<MS_FOLD>(s, p, nq_tile, grid);
+    return launch_sweep(s->stream, p, nq_tile, grid, OTT_SWEEP_KERNEL(maxsim_sweep_kernel, MS_FOLD));
 }
 
 }  // namespace
@@ -178,7 +161,7 @@ int run_maxsim(ott_store* s, const ott_query_desc* d, uint64_t k_eff, ott_hit* o
         const uint32_t tile = nq == 1 ? 1u : SW_NQ;
         for (uint32_t ps = 0; ps < st.passes; ps++) {
             p.q0 = ps * tile;
-            if ((rc = launch_sweep(s, p, tile, grid))) return rc;
+            if ((rc = launch_maxsim_sweep(s, p, tile, grid))) return rc;
         }
         if ((rc = launch_maxsim_reduce(s, p.table, ng, nq, p.take_max, (uint32_t)d->filter_cmp, d->filter_thr, keys, nullptr))) return rc;
         if ((rc = tk.pass(s, keys, 0, 1))) return rc;
@@ -214,7 +197,7 @@ int ott_query_maxsim(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64
     const char* too_big = "ott_query_maxsim: tokens x groups x 4 bytes is above 2 GiB (the table holds every token's maxima at once); use fewer tokens or groups";
     if (!table_fits(s->n_groups)) return fail(OTT_ERR_UNSUPPORTED, too_big);
     ott::host::SharedLock rd;  // the corpus and the group ids cannot change while this query runs
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
+    if ((rc = lock_store_shared(s, rd))) return rc;
     // what the checks above read without the lock is read again, and k_eff only here: a set_groups may have come in between
     if ((rc = check_group_ids(s, "ott_query_maxsim", true))) return rc;
     if (!table_fits(s->n_groups)) return fail(OTT_ERR_UNSUPPORTED, too_big);
@@ -222,10 +205,8 @@ int ott_query_maxsim(ott_store* s, const ott_query_desc* d, ott_hit* out, uint64
     if (cap < k_eff) return fail(OTT_ERR_INVALID, "ott_query_maxsim: output capacity is smaller than min(k, n_groups)");
     if (!out && cap) return fail(OTT_ERR_INVALID, "ott_query_maxsim: out is NULL");
     if (k_eff == 0) return OTT_OK;
-    ott_store* ctx = ctx_acquire(s);
-    rc = run_maxsim(ctx, d, k_eff, out, n_out, stats);
-    ctx_release(ctx);
-    return rc;
+    CtxLease ctx(s);
+    return run_maxsim(ctx.c, d, k_eff, out, n_out, stats);
 }
 
 }  // extern "C"

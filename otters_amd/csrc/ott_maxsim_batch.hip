@@ -313,10 +313,8 @@ int ott_query_maxsim_groups_batch(ott_store* s, const ott_query_desc* d, const v
     if (k_sum == 0) return OTT_OK;  // empty lists, or k == 0: a valid batch with no hits
 
     if (mg_batch_takes_gather(wants_index, have_index, s->opt.group_gather, s->dimq, mb)) {
-        ott_store* ctx = ctx_acquire(s);
-        rc = run_maxsim_gather_batch(ctx, d, mb, d->k < mb.S ? d->k : mb.S, out, n_out, n_per_query, stats);
-        ctx_release(ctx);
-        return rc;
+        CtxLease ctx(s);
+        return run_maxsim_gather_batch(ctx.c, d, mb, d->k < mb.S ? d->k : mb.S, out, n_out, n_per_query, stats);
     }
     // the loop route: the queries one by one, as ott_query_maxsim_groups answers them, under this lock
     ott_stats sum;

@@ -350,10 +350,7 @@ int run_groups_as_mask(ott_store* s, const ott_query_desc* d, const std::vector<
                        d_words);
     OTT_HIP(hipGetLastError());
     OTT_HIP(hipStreamSynchronize(s->stream));  // (h_stage is the query's own staging next)
-    struct IdMaskGuard {
-        ott_store* c;
-        ~IdMaskGuard() { c->cur_idmask = nullptr; }
-    } guard{s};
+    IdMaskGuard guard{s};
     s->cur_idmask = d_words;
     return run_maxsim(s, d, k_eff, out, n_out, stats_out);
 }
@@ -399,10 +396,8 @@ int maxsim_groups_locked(ott_store* s, const ott_query_desc* d, const uint32_t* 
         return fail(OTT_ERR_UNSUPPORTED,
                     name + ": tokens x groups x 4 bytes is above 2 GiB on the mask route (the sweep's table holds every group of the store); use fewer "
                            "tokens or groups, or a list the gather kernel serves");
-    ott_store* ctx = ctx_acquire(s);
-    rc = gather ? run_maxsim_gather(ctx, d, sl, k_eff, out, n_out, stats) : run_groups_as_mask(ctx, d, sl.gid, k_eff, out, n_out, stats);
-    ctx_release(ctx);
-    return rc;
+    CtxLease ctx(s);
+    return gather ? run_maxsim_gather(ctx.c, d, sl, k_eff, out, n_out, stats) : run_groups_as_mask(ctx.c, d, sl.gid, k_eff, out, n_out, stats);
 }
 
 }  // namespace ott

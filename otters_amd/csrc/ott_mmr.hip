@@ -328,12 +328,8 @@ int ott_query_mmr(ott_store* s, const ott_query_desc* d, const uint64_t* ids, ui
     if (n_first == 0) return OTT_OK;                           // an empty store or an empty list: a valid query with no hits
 
     ott::host::SharedLock rd;  // the corpus cannot change between the two stages
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
-    struct Ctx {  // one query context for both stages
-        ott_store* c;
-        explicit Ctx(ott_store* owner) : c(ctx_acquire(owner)) {}
-        ~Ctx() { ctx_release(c); }
-    } ctx(s);
+    if ((rc = lock_store_shared(s, rd))) return rc;
+    CtxLease ctx(s);  // one query context for both stages
     // first stage: the same descriptor with k = fetch_k, through the query's own internals (every path, the cascade, the tie orders)
     ott_query_desc d1 = *d;
     d1.k = n_first;

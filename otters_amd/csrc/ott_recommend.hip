@@ -3,7 +3,7 @@
 // closer to a NEGATIVE example than to every positive one for the end of the list, or out of it.  The examples are rows of the
 // store, named by id: nothing of them crosses the host.
 //
-//   recommend_gather_kernel  the examples' stored rows into the context's query block (upload_exact_inputs' layout: zero padded to
+//   example_gather_kernel    the examples' stored rows into the context's query block (upload_exact_inputs' layout: zero padded to
 //                            dimq, the slots past the last example zero) and their STORED inverse norms into the qinv slots: the
 //                            pair score P[e][r] is ott_query_mmr's, the example's row plays the query.
 //   recommend_sweep_kernel   sweep_tiles (ott_sweep_dev.h: the streaming tile loop of the grouped sweeps, examples in the place of
@@ -13,7 +13,7 @@
 //                            into the row's 8-byte state {bp, bn}: a plain load, max and a streaming vector store.  A row belongs to one lane of a pass
 //                            and the passes are launches on one stream, so nothing is atomic; the first pass finds the table zero
 //                            and does not load.  A row no lane ever wrote (masked, deleted, pruned chunk) keeps {0, 0}.
-//   recommend_clear_kernel   the examples' own slots back to {0, 0}: an example is never a candidate.
+//   example_clear_kernel     the examples' own slots back to {0, 0}: an example is never a candidate.
 //   recommend_keys_kernel    one lane per row, side 1 or 0: candidate (bp != 0, the filter holds for BP) on that side ->
 //                            key = ordinal << 32 | ~row in the context's key table, else nothing (the table is zero when found).
 //                            Side 1 (bn == 0 or bp > bn): ordinal bp.  Side 0 (bp <= bn): ord_of(BN, !take) = ~bn, so that the
@@ -27,6 +27,8 @@
 // Examples per pass: ott_sweep_dev.h; the epilogue adds two ordinals (profiles/recommend/resource_usage.txt: no scratch).
 // ott_query_recommend_strategy adds Qdrant's other two strategies below: sum_scores, the same sweep with a running
 // f32 sum in the state, and average_vector, one ordinary query with a vector built from the examples' rows; strategy 0 is the call above.
+// The gather and clear kernels and the host frame around a sweep over example rows (ExampleFrame, ott_internal.h) are here once:
+// best_score, sum_scores and discovery search (ott_discover.hip, whose slots are the pairs' rows and a target row) run through them.
 #include <string.h>
 
 #include <algorithm>
@@ -44,18 +46,23 @@ struct RecommendParams : SweepParams {
     uint32_t first_neg;  // slots below it are positives
 };
 
-struct RecommendGatherParams {
+constexpr uint32_t EX_MAX_ROWS = DISC_MAX_SLOTS;  // the rows a call gathers ride in the kernel arguments
+constexpr uint32_t EX_CLEAR_LANES = 128;          // example_clear_kernel's one workgroup: a lane per gathered row
+static_assert(EX_MAX_ROWS >= REC_MAX_EXAMPLES && EX_MAX_ROWS >= DISC_MAX_SLOTS && EX_MAX_ROWS <= EX_CLEAR_LANES,
+              "the gather array holds recommend's examples and discovery's slots, the clear kernel has a lane for each");
+
+struct ExampleGatherParams {
     const float* rows;
     const float* inv;
     float* queries;  // [slots * dimq]
     float* qinv;     // [slots]
-    uint2* state;    // recommend_clear_kernel
+    uint2* state;    // example_clear_kernel
     uint32_t ld, dim, dimq, n;
-    uint32_t ex[REC_MAX_EXAMPLES];  // the examples' rows, every one below the store's length (checked on the host)
+    uint32_t ex[EX_MAX_ROWS];  // the gathered rows (slot e is row ex[e]), every one below the store's length (checked on the host)
 };
 
-// blockIdx.x = example.  Every float of the slot's dimq is written: the row's dim, then zeros.
-__global__ __launch_bounds__(256) void recommend_gather_kernel(RecommendGatherParams p) {
+// blockIdx.x = slot.  Every float of the slot's dimq is written: the row's dim, then zeros.
+__global__ __launch_bounds__(256) void example_gather_kernel(ExampleGatherParams p) {
     const uint32_t e = blockIdx.x;
     if (e >= p.n) return;
     const float* src = p.rows + (uint64_t)p.ex[e] * p.ld;
@@ -64,7 +71,7 @@ __global__ __launch_bounds__(256) void recommend_gather_kernel(RecommendGatherPa
     if (threadIdx.x == 0) p.qinv[e] = p.inv[p.ex[e]];
 }
 
-__global__ __launch_bounds__(64) void recommend_clear_kernel(RecommendGatherParams p) {
+__global__ __launch_bounds__(EX_CLEAR_LANES) void example_clear_kernel(ExampleGatherParams p) {
     if (threadIdx.x < p.n) p.state[p.ex[threadIdx.x]] = make_uint2(0u, 0u);
 }
 
@@ -180,39 +187,79 @@ __global__ __launch_bounds__(256) void recommend_average_kernel(RecommendAverage
     p.q[i] = q;
 }
 
+// ---- the frame of a sweep over example rows (ExampleFrame, ott_internal.h) --------------------------------------------------------------
+int ExampleFrame::begin(SweepParams* p, const float* host_block, uint32_t n_slots) {
+    int rc;
+    OTT_HIP(use_device(s));
+    n = (uint32_t)s->n;
+    if ((rc = sweep_prologue(s, d, host_block, n_slots, &st, p, &grid))) return rc;
+    if (grid == 0) return OTT_OK;
+    st.bytes_scanned = (uint64_t)st.passes * (st.vectors_compared / n_slots) * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));  // (no group id is read)
+    // the states are left zeroed by the run's kernel that reads them last (or its memset), the keys by the top-k's select / compact kernel
+    if ((rc = ensure_zeroed(s, s->d_rectable, s->rectable_clean, rec_state_bytes(n)))) return rc;  // (== disc_state_bytes, disc_key_bytes)
+    if ((rc = ensure_zeroed(s, s->d_gtable, s->gtable_clean, rec_key_bytes(n)))) return rc;
+    state = (uint2*)s->d_rectable.p;
+    keys = (unsigned long long*)s->d_gtable.p;
+    p->gid = nullptr;  // (a store with groups has ids: this sweep does not read them)
+    return OTT_OK;
+}
+
+int ExampleFrame::prepare(const uint32_t* gather_rows, uint32_t n_gather, bool tk_take_max, bool* also_clean) {
+    rows = gather_rows;
+    n_rows = n_gather;
+    tk.n_groups = n;
+    tk.nq = 1;
+    tk.k = k_eff;
+    tk.take_max = tk_take_max;
+    tk.also_clean = also_clean;
+    return tk.prepare(s, nullptr);
+}
+
+int ExampleFrame::sweep(uint32_t tile, const std::function<int(uint32_t q0)>& launch_pass) {
+    int rc;
+    ExampleGatherParams gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.rows = s->d_rows;
+    gp.inv = s->d_inv;
+    gp.queries = (float*)s->d_queries.p;
+    gp.qinv = (float*)((char*)s->d_queries.p + s->in_off_qinv);
+    gp.state = state;
+    gp.ld = s->ld;
+    gp.dim = s->dim;
+    gp.dimq = s->dimq;
+    gp.n = n_rows;
+    memcpy(gp.ex, rows, sizeof(uint32_t) * n_rows);
+    hipLaunchKernelGGL(example_gather_kernel, dim3(n_rows), dim3(256), 0, s->stream, gp);
+    OTT_HIP(hipGetLastError());
+    if (timing()) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
+    for (uint32_t ps = 0; ps < st.passes; ps++)
+        if ((rc = launch_pass(ps * tile))) return rc;
+    hipLaunchKernelGGL(example_clear_kernel, dim3(1), dim3(EX_CLEAR_LANES), 0, s->stream, gp);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+
+int ExampleFrame::rank() {
+    int rc;
+    if ((rc = tk.pass(s, keys, 0, 1))) return rc;
+    if (timing()) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
+    return OTT_OK;
+}
+
+int ExampleFrame::finish(ott_hit* out, uint64_t* n_hits) {
+    int rc;
+    if ((rc = tk.finish(s, timing(), out, n_hits, nullptr))) return rc;
+    if (timing()) read_exact_events(s, &st);
+    if (*n_hits > k_eff) return fail(OTT_ERR_HIP, std::string(who) + ": the top-k returned more hits than k");
+    return OTT_OK;
+}
+
+void ExampleFrame::end() {
+    st.total_ns = now_ns() - t0;
+    if (stats_out) *stats_out = st;
+}
+
 namespace {
-
-template <int MK>
-int launch_sum_sweep_mk(ott_store* s, const RecommendParams& p, uint32_t nq_tile, uint32_t grid) {
-    if (nq_tile == 1) hipLaunchKernelGGL((recommend_sum_sweep_kernel<MK, 1>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    else hipLaunchKernelGGL((recommend_sum_sweep_kernel<MK, (int)SW_NQ>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-int launch_sum_sweep(ott_store* s, const RecommendParams& p, uint32_t nq_tile, uint32_t grid) {
-    switch (metric_kind(p.metric)) {
-        case MK_L2: return launch_sum_sweep_mk<MK_L2>(s, p, nq_tile, grid);
-        case MK_L1: return launch_sum_sweep_mk<MK_L1>(s, p, nq_tile, grid);
-        default: return launch_sum_sweep_mk<MK_DOT>(s, p, nq_tile, grid);
-    }
-}
-
-template <int MK>
-int launch_sweep_mk(ott_store* s, const RecommendParams& p, uint32_t nq_tile, uint32_t grid) {
-    if (nq_tile == 1) hipLaunchKernelGGL((recommend_sweep_kernel<MK, 1>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    else hipLaunchKernelGGL((recommend_sweep_kernel<MK, (int)SW_NQ>), dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, s->stream, p);
-    OTT_HIP(hipGetLastError());
-    return OTT_OK;
-}
-
-int launch_sweep(ott_store* s, const RecommendParams& p, uint32_t nq_tile, uint32_t grid) {
-    switch (metric_kind(p.metric)) {
-        case MK_L2: return launch_sweep_mk<MK_L2>(s, p, nq_tile, grid);
-        case MK_L1: return launch_sweep_mk<MK_L1>(s, p, nq_tile, grid);
-        default: return launch_sweep_mk<MK_DOT>(s, p, nq_tile, grid);
-    }
-}
 
 int launch_keys(ott_store* s, uint2* state, uint32_t n, uint32_t side, bool take_max, const ott_query_desc* d, bool last, unsigned long long* keys) {
     hipLaunchKernelGGL(recommend_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s->stream, state, n, side, take_max ? 1u : 0u, (uint32_t)d->filter_cmp, d->filter_thr,
@@ -238,74 +285,50 @@ const char* refusal_text(RecRefusal r) {
     }
 }
 
-int refuse(RecRefusal r, uint64_t id = 0, uint64_t len = 0) {
+// strategy 0 is ott_query_recommend under its own name and texts; the other two are ott_query_recommend_strategy's
+const char* entry_name(uint32_t strategy) { return strategy == REC_BEST_SCORE ? "ott_query_recommend" : "ott_query_recommend_strategy"; }
+
+int refuse(uint32_t strategy, RecRefusal r, uint64_t id = 0, uint64_t len = 0) {
     const int code = rec_refusal_is_invalid(r) ? OTT_ERR_INVALID : OTT_ERR_UNSUPPORTED;
-    if (r == REC_BAD_ID) return fail(code, "ott_query_recommend: example id " + std::to_string(id) + " is not below the store's length " + std::to_string(len));
-    if (r == REC_BOTH_SIDES) return fail(code, "ott_query_recommend: row " + std::to_string(id) + " is listed as both a positive and a negative example");
-    return fail(code, refusal_text(r));
+    const std::string who = entry_name(strategy);
+    if (r == REC_BAD_ID) return fail(code, who + ": example id " + std::to_string(id) + " is not below the store's length " + std::to_string(len));
+    if (r == REC_BOTH_SIDES) return fail(code, who + ": row " + std::to_string(id) + " is listed as both a positive and a negative example");
+    return fail(code, strategy == REC_BEST_SCORE ? refusal_text(r) : rec_strategy_text(r));
 }
 
-// The query on a context whose `mu` the caller holds (and the owner's `rw`, shared).  k_eff = min(k, rows) >= 1; every example < s->n.
-int run_recommend(ott_store* s, const ott_query_desc* d, const RecExamples& ex, uint32_t flags, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint32_t* side_of_hit,
-                  ott_stats* stats_out) {
+// best_score (`sum` false) and sum_scores on a context whose `mu` the caller holds (and the owner's `rw`, shared): the frame with
+// this strategy's sweep and keys kernels; best_score alone has a second round.  k_eff = min(k, rows) >= 1; every example < s->n.
+int run_recommend(ott_store* s, const ott_query_desc* d, const RecExamples& ex, bool sum, uint32_t flags, uint64_t k_eff, ott_hit* out, uint64_t* n_out,
+                  uint32_t* side_of_hit, ott_stats* stats_out) {
     int rc;
-    OTT_HIP(use_device(s));
-    const uint64_t t0 = now_ns();
-    ott_stats st;
-    const uint32_t n = (uint32_t)s->n;
+    ExampleFrame fr{s, d, entry_name(sum ? REC_SUM_SCORES : REC_BEST_SCORE), k_eff, stats_out};
     RecommendParams p{};
-    uint32_t grid = 0;
-    if ((rc = sweep_prologue(s, d, nullptr, ex.n, &st, &p, &grid))) return rc;
+    if ((rc = fr.begin(&p, nullptr, ex.n))) return rc;
     uint64_t n1 = 0, n0 = 0;
-    if (grid != 0) {
-        st.bytes_scanned = (uint64_t)st.passes * (st.vectors_compared / ex.n) * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));  // (no group id is read)
-        // the states are left zeroed by the keys kernel that reads them last (or the memset below), the keys by the select / compact kernel
-        if ((rc = ensure_zeroed(s, s->d_rectable, s->rectable_clean, rec_state_bytes(n)))) return rc;
-        if ((rc = ensure_zeroed(s, s->d_gtable, s->gtable_clean, rec_key_bytes(n)))) return rc;
-        unsigned long long* keys = (unsigned long long*)s->d_gtable.p;
-        p.gid = nullptr;  // (a store with groups has ids: this sweep does not read them)
-        p.state = (uint2*)s->d_rectable.p;
+    if (fr.grid != 0) {
+        const uint32_t n = fr.n;
+        p.state = fr.state;
         p.first_neg = ex.first_neg;
         const bool take_max = p.take_max != 0;
-        const bool fill = rec_fill_possible(flags, ex);
-
-        RecommendGatherParams gp;
-        memset(&gp, 0, sizeof(gp));
-        gp.rows = s->d_rows;
-        gp.inv = s->d_inv;
-        gp.queries = (float*)s->d_queries.p;
-        gp.qinv = (float*)((char*)s->d_queries.p + s->in_off_qinv);
-        gp.state = p.state;
-        gp.ld = s->ld;
-        gp.dim = s->dim;
-        gp.dimq = s->dimq;
-        gp.n = ex.n;
-        memcpy(gp.ex, ex.rows, sizeof(uint32_t) * ex.n);
-
-        GroupTopK tk;
-        tk.n_groups = n;
-        tk.nq = 1;
-        tk.k = k_eff;
-        tk.take_max = take_max;
-        tk.also_clean = fill ? nullptr : &s->rectable_clean;
-        if ((rc = tk.prepare(s, nullptr))) return rc;
-        const bool timing = stats_out != nullptr;
-        hipLaunchKernelGGL(recommend_gather_kernel, dim3(ex.n), dim3(256), 0, s->stream, gp);
-        OTT_HIP(hipGetLastError());
-        if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
+        const bool fill = !sum && rec_fill_possible(flags, ex);
+        // (with a second round to come the first keys kernel does not read the states last: they are not clean behind the first top-k)
+        if ((rc = fr.prepare(ex.rows, ex.n, take_max, fill ? nullptr : &s->rectable_clean))) return rc;
         const uint32_t tile = rec_tile(ex.n);
-        for (uint32_t ps = 0; ps < st.passes; ps++) {
-            p.q0 = ps * tile;
-            if ((rc = launch_sweep(s, p, tile, grid))) return rc;
+        rc = fr.sweep(tile, [&](uint32_t q0) {
+            p.q0 = q0;
+            return sum ? launch_sweep(s->stream, p, tile, fr.grid, OTT_SWEEP_KERNEL(recommend_sum_sweep_kernel))
+                       : launch_sweep(s->stream, p, tile, fr.grid, OTT_SWEEP_KERNEL(recommend_sweep_kernel));
+        });
+        if (rc) return rc;
+        if (sum) {
+            hipLaunchKernelGGL(recommend_sum_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s->stream, p.state, n, take_max ? 1u : 0u, (uint32_t)d->filter_cmp, d->filter_thr,
+                               fr.keys);
+            OTT_HIP(hipGetLastError());
+        } else if ((rc = launch_keys(s, p.state, n, 1u, take_max, d, !fill, fr.keys))) {
+            return rc;
         }
-        hipLaunchKernelGGL(recommend_clear_kernel, dim3(1), dim3(64), 0, s->stream, gp);
-        OTT_HIP(hipGetLastError());
-        if ((rc = launch_keys(s, p.state, n, 1u, take_max, d, !fill, keys))) return rc;
-        if ((rc = tk.pass(s, keys, 0, 1))) return rc;
-        if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
-        if ((rc = tk.finish(s, timing, out, &n1, nullptr))) return rc;
-        if (timing) read_exact_events(s, &st);
-        if (n1 > k_eff) return fail(OTT_ERR_HIP, "ott_query_recommend: the top-k returned more hits than k");
+        if ((rc = fr.rank())) return rc;
+        if ((rc = fr.finish(out, &n1))) return rc;
         if (fill) {
             const uint64_t k2 = rec_second_k(fill, k_eff, n1);
             if (k2 != 0) {
@@ -318,8 +341,8 @@ int run_recommend(ott_store* s, const ott_query_desc* d, const RecExamples& ex, 
                 t2.take_max = !take_max;
                 t2.also_clean = &s->rectable_clean;
                 if ((rc = t2.prepare(s, nullptr))) return rc;
-                if ((rc = launch_keys(s, p.state, n, 0u, take_max, d, true, keys))) return rc;
-                if ((rc = t2.pass(s, keys, 0, 1))) return rc;
+                if ((rc = launch_keys(s, p.state, n, 0u, take_max, d, true, fr.keys))) return rc;
+                if ((rc = t2.pass(s, fr.keys, 0, 1))) return rc;
                 if ((rc = t2.finish(s, false, out + n1, &n0, nullptr))) return rc;
                 if (n0 > k2) return fail(OTT_ERR_HIP, "ott_query_recommend: the second top-k returned more hits than it was asked for");
             } else {
@@ -334,86 +357,7 @@ int run_recommend(ott_store* s, const ott_query_desc* d, const RecExamples& ex, 
         for (uint64_t i = 0; i < n0; i++) side_of_hit[n1 + i] = 0u;
     }
     if (n_out) *n_out = n1 + n0;
-    st.total_ns = now_ns() - t0;
-    if (stats_out) *stats_out = st;
-    return OTT_OK;
-}
-
-int refuse_strategy(RecRefusal r, uint64_t id = 0, uint64_t len = 0) {
-    const int code = rec_refusal_is_invalid(r) ? OTT_ERR_INVALID : OTT_ERR_UNSUPPORTED;
-    if (r == REC_BAD_ID) return fail(code, "ott_query_recommend_strategy: example id " + std::to_string(id) + " is not below the store's length " + std::to_string(len));
-    if (r == REC_BOTH_SIDES) return fail(code, "ott_query_recommend_strategy: row " + std::to_string(id) + " is listed as both a positive and a negative example");
-    return fail(code, rec_strategy_text(r));
-}
-
-// sum_scores on a context whose `mu` the caller holds (and the owner's `rw`, shared): run_recommend with the running sum in the
-// state table and one round.  k_eff = min(k, rows) >= 1; every example < s->n.
-int run_recommend_sum(ott_store* s, const ott_query_desc* d, const RecExamples& ex, uint64_t k_eff, ott_hit* out, uint64_t* n_out, uint32_t* side_of_hit,
-                      ott_stats* stats_out) {
-    int rc;
-    OTT_HIP(use_device(s));
-    const uint64_t t0 = now_ns();
-    ott_stats st;
-    const uint32_t n = (uint32_t)s->n;
-    RecommendParams p{};
-    uint32_t grid = 0;
-    if ((rc = sweep_prologue(s, d, nullptr, ex.n, &st, &p, &grid))) return rc;
-    uint64_t n1 = 0;
-    if (grid != 0) {
-        st.bytes_scanned = (uint64_t)st.passes * (st.vectors_compared / ex.n) * ((uint64_t)s->dim * 4 + (d->metric == OTT_METRIC_COSINE ? 4 : 0));  // (no group id is read)
-        // the states are left zeroed by the keys kernel, the keys by the top-k's select / compact kernel
-        if ((rc = ensure_zeroed(s, s->d_rectable, s->rectable_clean, rec_state_bytes(n)))) return rc;
-        if ((rc = ensure_zeroed(s, s->d_gtable, s->gtable_clean, rec_key_bytes(n)))) return rc;
-        unsigned long long* keys = (unsigned long long*)s->d_gtable.p;
-        p.gid = nullptr;  // (a store with groups has ids: this sweep does not read them)
-        p.state = (uint2*)s->d_rectable.p;
-        p.first_neg = ex.first_neg;
-        const bool take_max = p.take_max != 0;
-
-        RecommendGatherParams gp;
-        memset(&gp, 0, sizeof(gp));
-        gp.rows = s->d_rows;
-        gp.inv = s->d_inv;
-        gp.queries = (float*)s->d_queries.p;
-        gp.qinv = (float*)((char*)s->d_queries.p + s->in_off_qinv);
-        gp.state = p.state;
-        gp.ld = s->ld;
-        gp.dim = s->dim;
-        gp.dimq = s->dimq;
-        gp.n = ex.n;
-        memcpy(gp.ex, ex.rows, sizeof(uint32_t) * ex.n);
-
-        GroupTopK tk;
-        tk.n_groups = n;
-        tk.nq = 1;
-        tk.k = k_eff;
-        tk.take_max = take_max;
-        tk.also_clean = &s->rectable_clean;
-        if ((rc = tk.prepare(s, nullptr))) return rc;
-        const bool timing = stats_out != nullptr;
-        hipLaunchKernelGGL(recommend_gather_kernel, dim3(ex.n), dim3(256), 0, s->stream, gp);
-        OTT_HIP(hipGetLastError());
-        if (timing) OTT_HIP(hipEventRecord(s->ev[3], s->stream));
-        const uint32_t tile = rec_tile(ex.n);
-        for (uint32_t ps = 0; ps < st.passes; ps++) {
-            p.q0 = ps * tile;
-            if ((rc = launch_sum_sweep(s, p, tile, grid))) return rc;
-        }
-        hipLaunchKernelGGL(recommend_clear_kernel, dim3(1), dim3(64), 0, s->stream, gp);
-        OTT_HIP(hipGetLastError());
-        hipLaunchKernelGGL(recommend_sum_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s->stream, p.state, n, take_max ? 1u : 0u, (uint32_t)d->filter_cmp, d->filter_thr, keys);
-        OTT_HIP(hipGetLastError());
-        if ((rc = tk.pass(s, keys, 0, 1))) return rc;
-        if (timing) OTT_HIP(hipEventRecord(s->ev[4], s->stream));
-        if ((rc = tk.finish(s, timing, out, &n1, nullptr))) return rc;
-        if (timing) read_exact_events(s, &st);
-        if (n1 > k_eff) return fail(OTT_ERR_HIP, "ott_query_recommend_strategy: the top-k returned more hits than k");
-    }
-    if (side_of_hit)
-        for (uint64_t i = 0; i < n1; i++) side_of_hit[i] = 1u;
-    if (n_out) *n_out = n1;
-    st.total_ns = now_ns() - t0;
-    if (stats_out) *stats_out = st;
+    fr.end();
     return OTT_OK;
 }
 
@@ -446,10 +390,7 @@ int run_recommend_average(ott_store* s, const ott_query_desc* d, const RecExampl
     ott_query_desc d2 = *d;
     d2.queries = q.data();
     d2.nq = 1;
-    struct IdMaskGuard {
-        ott_store* c;
-        ~IdMaskGuard() { c->cur_idmask = nullptr; }
-    } guard{s};
+    IdMaskGuard guard{s};
     s->cur_idmask = d_words;
     uint64_t n1 = 0;
     if ((rc = query_on(s, &d2, out, nullptr, cap, &n1, nullptr, nullptr, stats_out))) return rc;
@@ -457,6 +398,45 @@ int run_recommend_average(ott_store* s, const ott_query_desc* d, const RecExampl
         for (uint64_t i = 0; i < n1; i++) side_of_hit[i] = 1u;
     if (n_out) *n_out = n1;
     return OTT_OK;
+}
+
+// The body of both entry points: `strategy` is known, and names the entry point (entry_name).
+int recommend_entry(uint32_t strategy, ott_store* s, const ott_query_desc* d, const uint64_t* positive, uint64_t n_positive, const uint64_t* negative, uint64_t n_negative,
+                    uint32_t flags, ott_hit* out, uint64_t cap, uint64_t* n_out, uint32_t* side_of_hit, ott_stats* stats) {
+    const char* who = entry_name(strategy);
+    int rc;
+    // what the arguments and the descriptor alone decide comes first: these refusals need no store
+    if (!d) return fail(OTT_ERR_INVALID, std::string(who) + ": desc is NULL");
+    const bool has_queries = d->nq != 0 || d->queries != nullptr, per_query = d->mode == OTT_MODE_PER_QUERY, mfma = d->path == OTT_PATH_MFMA;
+    RecRefusal why = strategy == REC_BEST_SCORE
+                         ? rec_check_args(positive == nullptr, n_positive, negative == nullptr, n_negative, flags, has_queries, per_query, mfma)
+                         : rec_strategy_check_args(strategy, positive == nullptr, n_positive, negative == nullptr, n_negative, flags, has_queries, per_query, mfma,
+                                                   d->metric == OTT_METRIC_MANHATTAN);
+    if (why != REC_OK) return refuse(strategy, why);
+    if ((rc = check_desc_enums(who, d))) return rc;
+    if (!s) return fail(OTT_ERR_INVALID, std::string(who) + ": store is NULL");
+    const uint64_t len = ott_store_len(s);
+    if ((why = rec_check_store(s->multi != nullptr, len)) != REC_OK) return refuse(strategy, why);
+    if ((rc = check_device_row_mask(who, s, d))) return rc;
+    RecExamples ex;
+    uint64_t bad = 0;
+    if ((why = rec_examples(positive, n_positive, negative, n_negative, len, &ex, &bad)) != REC_OK) return refuse(strategy, why, bad, len);
+    if ((why = rec_check_out(rec_k_eff(d->k, len), cap, out == nullptr)) != REC_OK) return refuse(strategy, why);
+    ott::host::SharedLock rd;  // the corpus cannot change while this query runs
+    if ((rc = lock_store_shared(s, rd))) return rc;
+    // what the checks above read without the lock is read again, and k_eff only here: appends (this call's own flush of rows another
+    // thread staged after `len` was read) or a compact may have come in between, so the store may be longer or shorter than `len`
+    if ((why = rec_check_store(false, s->n)) != REC_OK) return refuse(strategy, why);
+    for (uint32_t e = 0; e < ex.n; e++)
+        if (ex.rows[e] >= s->n) return refuse(strategy, REC_BAD_ID, ex.rows[e], s->n);
+    const uint64_t k_eff = rec_k_eff(d->k, s->n);
+    if ((why = rec_check_out(k_eff, cap, out == nullptr)) != REC_OK) return refuse(strategy, why);
+    if (n_out) *n_out = 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (k_eff == 0) return OTT_OK;
+    CtxLease ctx(s);
+    if (strategy == REC_AVERAGE_VECTOR) return run_recommend_average(ctx.c, d, ex, out, cap, n_out, side_of_hit, stats);
+    return run_recommend(ctx.c, d, ex, strategy == REC_SUM_SCORES, flags, k_eff, out, n_out, side_of_hit, stats);
 }
 
 }  // namespace
@@ -469,84 +449,14 @@ extern "C" {
 
 int ott_query_recommend(ott_store* s, const ott_query_desc* d, const uint64_t* positive, uint64_t n_positive, const uint64_t* negative, uint64_t n_negative,
                         uint32_t flags, ott_hit* out, uint64_t cap, uint64_t* n_out, uint32_t* side_of_hit, ott_stats* stats) {
-    // what the arguments and the descriptor alone decide comes first: these refusals need no store
-    if (!d) return fail(OTT_ERR_INVALID, "ott_query_recommend: desc is NULL");
-    RecRefusal why = rec_check_args(positive == nullptr, n_positive, negative == nullptr, n_negative, flags, d->nq != 0 || d->queries != nullptr,
-                                    d->mode == OTT_MODE_PER_QUERY, d->path == OTT_PATH_MFMA);
-    if (why != REC_OK) return refuse(why);
-    if (d->metric > OTT_METRIC_MANHATTAN) return fail(OTT_ERR_INVALID, "ott_query_recommend: unknown metric");
-    if (d->take > OTT_TAKE_MAX) return fail(OTT_ERR_INVALID, "ott_query_recommend: unknown take type");
-    if (d->filter_cmp > OTT_CMP_EQ) return fail(OTT_ERR_INVALID, "ott_query_recommend: unknown filter comparator");
-    if (d->mode > OTT_MODE_PER_QUERY) return fail(OTT_ERR_INVALID, "ott_query_recommend: unknown mode");
-    if (d->path > OTT_PATH_MFMA) return fail(OTT_ERR_INVALID, "ott_query_recommend: unknown path");
-    if (!s) return fail(OTT_ERR_INVALID, "ott_query_recommend: store is NULL");
-    const uint64_t len = ott_store_len(s);
-    if ((why = rec_check_store(s->multi != nullptr, len)) != REC_OK) return refuse(why);
-    if (d->use_device_row_mask && s->evalmask_bits == 0 && s->n)
-        return fail(OTT_ERR_INVALID, "ott_query_recommend: use_device_row_mask set but ott_store_eval_row_mask was not called");
-    RecExamples ex;
-    uint64_t bad = 0;
-    if ((why = rec_examples(positive, n_positive, negative, n_negative, len, &ex, &bad)) != REC_OK) return refuse(why, bad, len);
-    if ((why = rec_check_out(rec_k_eff(d->k, len), cap, out == nullptr)) != REC_OK) return refuse(why);
-    ott::host::SharedLock rd;  // the corpus cannot change while this query runs
-    int rc;
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
-    // what the checks above read without the lock is read again, and k_eff only here: appends (this call's own flush of rows another
-    // thread staged after `len` was read) or a compact may have come in between, so the store may be longer or shorter than `len`
-    if ((why = rec_check_store(false, s->n)) != REC_OK) return refuse(why);
-    for (uint32_t e = 0; e < ex.n; e++)
-        if (ex.rows[e] >= s->n) return refuse(REC_BAD_ID, ex.rows[e], s->n);
-    const uint64_t k_eff = rec_k_eff(d->k, s->n);
-    if ((why = rec_check_out(k_eff, cap, out == nullptr)) != REC_OK) return refuse(why);
-    if (n_out) *n_out = 0;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (k_eff == 0) return OTT_OK;
-    ott_store* ctx = ctx_acquire(s);
-    rc = run_recommend(ctx, d, ex, flags, k_eff, out, n_out, side_of_hit, stats);
-    ctx_release(ctx);
-    return rc;
+    return recommend_entry(REC_BEST_SCORE, s, d, positive, n_positive, negative, n_negative, flags, out, cap, n_out, side_of_hit, stats);
 }
 
+// strategy 0 is ott_query_recommend whole, with that name in its messages; an unknown strategy is refused before anything else is looked at
 int ott_query_recommend_strategy(ott_store* s, const ott_query_desc* d, uint32_t strategy, const uint64_t* positive, uint64_t n_positive, const uint64_t* negative,
                                  uint64_t n_negative, uint32_t flags, ott_hit* out, uint64_t cap, uint64_t* n_out, uint32_t* side_of_hit, ott_stats* stats) {
-    if (strategy == REC_BEST_SCORE) return ott_query_recommend(s, d, positive, n_positive, negative, n_negative, flags, out, cap, n_out, side_of_hit, stats);
-    // as ott_query_recommend: what the arguments and the descriptor alone decide comes first
-    if (!rec_strategy_known(strategy)) return refuse_strategy(REC_BAD_STRATEGY);
-    if (!d) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: desc is NULL");
-    RecRefusal why = rec_strategy_check_args(strategy, positive == nullptr, n_positive, negative == nullptr, n_negative, flags, d->nq != 0 || d->queries != nullptr,
-                                             d->mode == OTT_MODE_PER_QUERY, d->path == OTT_PATH_MFMA, d->metric == OTT_METRIC_MANHATTAN);
-    if (why != REC_OK) return refuse_strategy(why);
-    if (d->metric > OTT_METRIC_MANHATTAN) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: unknown metric");
-    if (d->take > OTT_TAKE_MAX) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: unknown take type");
-    if (d->filter_cmp > OTT_CMP_EQ) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: unknown filter comparator");
-    if (d->mode > OTT_MODE_PER_QUERY) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: unknown mode");
-    if (d->path > OTT_PATH_MFMA) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: unknown path");
-    if (!s) return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: store is NULL");
-    const uint64_t len = ott_store_len(s);
-    if ((why = rec_check_store(s->multi != nullptr, len)) != REC_OK) return refuse_strategy(why);
-    if (d->use_device_row_mask && s->evalmask_bits == 0 && s->n)
-        return fail(OTT_ERR_INVALID, "ott_query_recommend_strategy: use_device_row_mask set but ott_store_eval_row_mask was not called");
-    RecExamples ex;
-    uint64_t bad = 0;
-    if ((why = rec_examples(positive, n_positive, negative, n_negative, len, &ex, &bad)) != REC_OK) return refuse_strategy(why, bad, len);
-    if ((why = rec_check_out(rec_k_eff(d->k, len), cap, out == nullptr)) != REC_OK) return refuse_strategy(why);
-    ott::host::SharedLock rd;  // the corpus cannot change while this query runs
-    int rc;
-    if ((rc = ott::host::lock_shared_clean(s->rw, rd, [s] { return s->pend.count() != 0; }, [s] { return store_flush(s); }))) return rc;
-    // what the checks above read without the lock is read again under it (ott_query_recommend)
-    if ((why = rec_check_store(false, s->n)) != REC_OK) return refuse_strategy(why);
-    for (uint32_t e = 0; e < ex.n; e++)
-        if (ex.rows[e] >= s->n) return refuse_strategy(REC_BAD_ID, ex.rows[e], s->n);
-    const uint64_t k_eff = rec_k_eff(d->k, s->n);
-    if ((why = rec_check_out(k_eff, cap, out == nullptr)) != REC_OK) return refuse_strategy(why);
-    if (n_out) *n_out = 0;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (k_eff == 0) return OTT_OK;
-    ott_store* ctx = ctx_acquire(s);
-    if (strategy == REC_SUM_SCORES) rc = run_recommend_sum(ctx, d, ex, k_eff, out, n_out, side_of_hit, stats);
-    else rc = run_recommend_average(ctx, d, ex, out, cap, n_out, side_of_hit, stats);
-    ctx_release(ctx);
-    return rc;
+    if (!rec_strategy_known(strategy)) return refuse(strategy, REC_BAD_STRATEGY);
+    return recommend_entry(strategy, s, d, positive, n_positive, negative, n_negative, flags, out, cap, n_out, side_of_hit, stats);
 }
 
 }  // extern "C"

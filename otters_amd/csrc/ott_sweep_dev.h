@@ -1,5 +1,7 @@
-// ott_sweep_dev.h — the streaming tile loop of the two sweeps over grouped rows: group_sweep_kernel (ott_group.hip) and
-// maxsim_sweep_kernel (ott_maxsim.hip), and of recommend_sweep_kernel and recommend_sum_sweep_kernel (ott_recommend.hip), which read no group ids.
+// ott_sweep_dev.h — the streaming tile loop of every sweep that is "the loop plus an epilogue": group_sweep_kernel (ott_group.hip),
+// group_top_sweep_kernel (ott_group_top.hip) and maxsim_sweep_kernel (ott_maxsim.hip) over grouped rows; recommend_sweep_kernel,
+// recommend_sum_sweep_kernel (ott_recommend.hip) and discover_sweep_kernel (ott_discover.hip), which read no group ids; and
+// masks_sweep_kernel (ott_masks.hip), a row mask per query.  launch_sweep, below the loop, is the one launch of all of them.
 // exact_kernel's streaming geometry with every variant stripped: lane = row, 64-row tiles per wave, 128-B stages through the swizzled LDS tile, queries through the constant address space, a persistent grid over the run lists
 // of surviving chunks, the scoring terms of ott_exact_dev.h, so the bits are the oracle's.  A kernel is sweep_tiles plus its epilogue;
 // what guards the loop against reading past the allocation (lsl4, the clamp to the tile's last row) exists here and nowhere else.
@@ -9,6 +11,8 @@
 // of the next stage: 4 queries are 36 + 32 live floats, which exact_kernel measured as the sweet spot of this geometry (an 8-wide
 // pass needs 233 VGPRs and ran slower than two 4-wide ones).
 #pragma once
+
+#include <type_traits>
 
 #include "ott_exact_dev.h"
 
@@ -21,7 +25,7 @@ constexpr int SW_SMEM = SW_WAVES * SW_STAGE_FLOATS * 4;
 constexpr int SW_BLOCKS_PER_CU = 2;          // the persistent grid of exact_kernel
 constexpr uint32_t SW_NQ = 4;                // queries per pass of a batch
 
-// what both sweeps read; filled by sweep_prologue (ott_group.hip)
+// what every sweep reads; filled by sweep_prologue (ott_group.hip)
 struct SweepParams {
     const float* rows;
     const float* inv;
@@ -172,5 +176,28 @@ __device__ __forceinline__ void sweep_tiles(const SweepParams& p, Epilogue&& epi
         epi(my_row, valid, g, sc, nq_here);
     }
 }
+
+// The one launch of a sweep kernel.  kernel_of(MK, NQ), both as std::integral_constant<int, .>, names the instance: write it with
+// OTT_SWEEP_KERNEL(kernel template, further template arguments ...).  tile: the queries of a pass, 1 or SW_NQ.  HAS_NQ1 = false: the
+// kind has no single-query kernel (ott_discover.hip: a pass holds whole pairs) and only NQ = SW_NQ is instantiated.
+template <bool HAS_NQ1 = true, class Params, class KernelOf>
+int launch_sweep(hipStream_t stream, const Params& p, uint32_t tile, uint32_t grid, KernelOf kernel_of) {
+    const auto pick = [&](auto mk) -> void (*)(Params) {
+        if constexpr (HAS_NQ1) {
+            if (tile == 1) return kernel_of(mk, std::integral_constant<int, 1>{});
+        }
+        return kernel_of(mk, std::integral_constant<int, (int)SW_NQ>{});
+    };
+    void (*kernel)(Params);
+    switch (metric_kind(p.metric)) {
+        case MK_L2: kernel = pick(std::integral_constant<int, MK_L2>{}); break;
+        case MK_L1: kernel = pick(std::integral_constant<int, MK_L1>{}); break;
+        default: kernel = pick(std::integral_constant<int, MK_DOT>{}); break;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * SW_WAVES), SW_SMEM, stream, p);
+    OTT_HIP(hipGetLastError());
+    return OTT_OK;
+}
+#define OTT_SWEEP_KERNEL(name, ...) [](auto mk, auto nq) { return &name<decltype(mk)::value, decltype(nq)::value, ##__VA_ARGS__>; }
 
 }  // namespace ott

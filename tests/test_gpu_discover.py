@@ -169,6 +169,22 @@ def test_pair_counts(corpus, n_pairs, target, passes):
             assert store.last_stats["passes"] == passes and store.last_stats["vectors_compared"] == N_ROWS * (2 * n_pairs + target)
 
 
+def test_the_most_rows_a_call_gathers(corpus):
+    """32 pairs and a target ROW: 65 gathered rows, the last entry of the gather kernel's row array and the 65th lane of the clear
+    kernel (both shared with recommend, whose most is 64).  The target row's state is cleared like the examples': it is no hit."""
+    store, rows, inv, model = corpus
+    rng = np.random.default_rng(65)
+    pool = rng.choice(N_ROWS, 20, replace=False)
+    ctx = context(rng, N_ROWS, 32, pool=pool)
+    target_row = int(rng.choice(np.setdiff1d(np.arange(N_ROWS), pool)))  # a 65th row, not among the pairs'
+    for metric in (Metric.Cosine, Metric.Manhattan):
+        for k in (10, 600):  # the lists and the sort path of the top-k
+            got = run(store, ctx, metric, TAKE[metric], k, target_row=target_row)
+            D.same(got, model(ctx, metric, TAKE[metric], k, target_row=target_row), (metric, k))
+            assert target_row not in got[0]["index"].tolist()
+            assert store.last_stats["passes"] == 17 and store.last_stats["vectors_compared"] == N_ROWS * 65
+
+
 def test_one_row_in_several_pairs_on_both_sides(corpus):
     store, rows, inv, model = corpus
     ctx = [(5, 9), (9, 5), (5, 70), (70, 9), (5, 9)]  # row 5 a positive three times and a negative once; a pair listed twice counts twice
