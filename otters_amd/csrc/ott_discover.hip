@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void discover_select_kernel(uint2* state, uint
 namespace {
 
 uint32_t row_blocks(const ott_store* s, uint32_t n) {
-    uint32_t blocks = (n + 255) / 256;
+    uint32_t blocks = (uint32_t)(((uint64_t)n + 255) / 256);  // (in 64 bits: n + 255 wraps from 2^32 - 255 rows on, below the limit of 2^32 - 16)
     if (blocks > (uint32_t)s->n_cu * 8) blocks = (uint32_t)s->n_cu * 8;
     return blocks < 1 ? 1 : blocks;
 }
@@ -294,7 +294,7 @@ int run_discover(ott_store* s, const ott_query_desc* d, const DiscSlots& sl, uin
         if (rc) return rc;
         uint64_t n1 = 0;
         if (!has_target) {
-            hipLaunchKernelGGL(discover_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s->stream, p.state, n, pick, keys, wins8);
+            hipLaunchKernelGGL(discover_keys_kernel, dim3((uint32_t)(((uint64_t)n + 255) / 256)), dim3(256), 0, s->stream, p.state, n, pick, keys, wins8);
             OTT_HIP(hipGetLastError());
             if ((rc = fr.rank())) return rc;
             if (wins_of_hit && !tk.lists_path) OTT_HIP(hipMemcpyAsync(s->h_disc.p, wins8, n, hipMemcpyDeviceToHost, s->stream));

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(64) void group_select_kernel(unsigned long long* ta
     const int lane = threadIdx.x;
     const uint32_t qy = blockIdx.y;
     unsigned long long* tab = table + (size_t)qy * q_stride;
-    const uint32_t n_tiles = (n_groups + 63) / 64;
+    const uint32_t n_tiles = (uint32_t)(((uint64_t)n_groups + 63) / 64);  // (in 64 bits: n_groups + 63 wraps from 2^32 - 63 groups on)
     WaveList<E> L;
     wl_init(L);
     uint64_t tk = 0;
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void group_compact_kernel(unsigned long long* 
     const int lane = threadIdx.x & 63;
     const uint32_t qy = blockIdx.y;
     unsigned long long* tab = table + (size_t)qy * q_stride;
-    const uint32_t n_round = (n_groups + 63) & ~63u;  // whole waves stay together for the ballot
+    const uint64_t n_round = ((uint64_t)n_groups + 63) & ~63ull;  // whole waves stay together for the ballot
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t key = 0;
         if (i < n_groups) {
@@ -158,7 +158,7 @@ int launch_group_select(ott_store* s, unsigned long long* table, uint32_t n_grou
 
 int launch_group_compact(ott_store* s, unsigned long long* table, uint32_t n_groups, uint64_t q_stride, uint32_t q0, uint32_t nq_here, uint64_t* keys, uint32_t* qs,
                          unsigned long long* cursor, uint64_t cap) {
-    uint32_t blocks = (n_groups + 255) / 256;
+    uint32_t blocks = (uint32_t)(((uint64_t)n_groups + 255) / 256);
     if (blocks > (uint32_t)s->n_cu * 8) blocks = (uint32_t)s->n_cu * 8;
     hipLaunchKernelGGL(group_compact_kernel, dim3(blocks, nq_here), dim3(256), 0, s->stream, table, n_groups, q_stride, q0, keys, qs, cursor, cap);
     OTT_HIP(hipGetLastError());
@@ -273,7 +273,7 @@ int GroupTopK::prepare(ott_store* s, const char* too_many_pairs) {
     lists_path = k <= 512;
     E = lists_path ? list_E(k) : 1;
     KS = 64u * (uint32_t)E;
-    n_lists = std::min((n_groups + 63) / 64, GS_MAX_LISTS);
+    n_lists = std::min((uint32_t)(((uint64_t)n_groups + 63) / 64), GS_MAX_LISTS);
     pair_cap = (uint64_t)nq * n_groups;
     if (lists_path) return s->d_lists.ensure((size_t)nq * n_lists * KS * sizeof(Cand));
     if (too_many_pairs && pair_cap > 0xFFFFFFF0ull) return fail(OTT_ERR_UNSUPPORTED, too_many_pairs);

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void maxsim_reduce_kernel(uint32_t* table, uin
 
 int launch_maxsim_reduce(ott_store* s, uint32_t* table, uint32_t n_slots, uint32_t nq, uint32_t take_max, uint32_t cmp, float thr, unsigned long long* keys,
                          const uint32_t* gid_of) {
-    hipLaunchKernelGGL(maxsim_reduce_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, s->stream, table, n_slots, nq, take_max, cmp, thr, keys, gid_of);
+    hipLaunchKernelGGL(maxsim_reduce_kernel, dim3((uint32_t)(((uint64_t)n_slots + 255) / 256)), dim3(256), 0, s->stream, table, n_slots, nq, take_max, cmp, thr, keys, gid_of);
     OTT_HIP(hipGetLastError());
     return OTT_OK;
 }

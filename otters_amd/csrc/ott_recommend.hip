@@ -262,7 +262,7 @@ void ExampleFrame::end() {
 namespace {
 
 int launch_keys(ott_store* s, uint2* state, uint32_t n, uint32_t side, bool take_max, const ott_query_desc* d, bool last, unsigned long long* keys) {
-    hipLaunchKernelGGL(recommend_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s->stream, state, n, side, take_max ? 1u : 0u, (uint32_t)d->filter_cmp, d->filter_thr,
+    hipLaunchKernelGGL(recommend_keys_kernel, dim3((uint32_t)(((uint64_t)n + 255) / 256)), dim3(256), 0, s->stream, state, n, side, take_max ? 1u : 0u, (uint32_t)d->filter_cmp, d->filter_thr,
                        last ? 1u : 0u, keys);
     OTT_HIP(hipGetLastError());
     return OTT_OK;
@@ -321,7 +321,7 @@ int run_recommend(ott_store* s, const ott_query_desc* d, const RecExamples& ex, 
         });
         if (rc) return rc;
         if (sum) {
-            hipLaunchKernelGGL(recommend_sum_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s->stream, p.state, n, take_max ? 1u : 0u, (uint32_t)d->filter_cmp, d->filter_thr,
+            hipLaunchKernelGGL(recommend_sum_keys_kernel, dim3((uint32_t)(((uint64_t)n + 255) / 256)), dim3(256), 0, s->stream, p.state, n, take_max ? 1u : 0u, (uint32_t)d->filter_cmp, d->filter_thr,
                                fr.keys);
             OTT_HIP(hipGetLastError());
         } else if ((rc = launch_keys(s, p.state, n, 1u, take_max, d, !fill, fr.keys))) {
