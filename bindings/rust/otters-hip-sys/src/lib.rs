@@ -25,6 +25,13 @@ pub const OTT_NO_MASK: u32 = 4294967295; // ott_query_masks: mask_of_query[b] wh
 pub const OTT_MASK_SLOT_BASE: u32 = 2147483648; // ott_query_masks: mask_of_query[b] = OTT_MASK_SLOT_BASE + slot names a device mask slot (0x80000000)
 pub const OTT_MASK_SLOTS: u32 = 64; // the device mask slots of a store
 pub const OTT_MASKS_MAX_QUERIES: u32 = 1024; // ott_query_masks: the most queries of one call
+pub const OTT_BOOST_MAX_TERMS: u32 = 8; // ott_query_boost: the most terms of one formula
+pub const OTT_BOOST_MAX_QUERIES: u32 = 1024; // ott_query_boost: the most queries of one call
+pub const OTT_BOOST_SUM: u32 = 0; // ott_boost_combine: F = Sw + B
+pub const OTT_BOOST_MULT: u32 = 1; // F = Sw * (1 + B)
+pub const OTT_BOOST_VALUE: u32 = 0; // ott_boost_kind: a column's value minus the origin
+pub const OTT_BOOST_LIN_DECAY: u32 = 1; // 1 - |value - origin| / scale, 0 from the scale on
+pub const OTT_BOOST_MASK: u32 = 2; // 1 where a device mask slot keeps the row, else 0
 pub const OTT_RECOMMEND_FILL: u32 = 1; // ott_query_recommend flags bit 0: the negative side follows the positive side
 pub const OTT_RECOMMEND_BEST_SCORE: u32 = 0; // ott_query_recommend_strategy: ott_query_recommend itself
 pub const OTT_RECOMMEND_AVERAGE_VECTOR: u32 = 1; // one ordinary query with the vector mean(positives) [+ mean(positives) - mean(negatives)]
@@ -141,6 +148,19 @@ pub struct ott_leaf {
     pub lit_f64: f64,
 }
 
+/// One term of a boost formula (ott_query_boost): `source` is a column id (VALUE, LIN_DECAY) or a device mask slot (MASK).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct ott_boost_term {
+    pub kind: u32,
+    pub source: u32,
+    pub weight: f32,
+    pub scale: f32,
+    pub origin: f64,
+    pub missing: f32,
+    pub reserved: u32,
+}
+
 #[repr(C)]
 pub struct ott_store {
     _opaque: [u8; 0],
@@ -197,6 +217,7 @@ extern "C" {
     pub fn ott_store_eval_row_mask_slot(s: *mut ott_store, slot: u32, leaves: *const ott_leaf, n_leaves: u32, n_clauses: u32, out_host: *mut u64) -> c_int;
     pub fn ott_store_write_row_mask_slot(s: *mut ott_store, slot: u32, bits: *const u64, n_bits: u64) -> c_int;
     pub fn ott_store_clear_row_mask_slots(s: *mut ott_store) -> c_int;
+    pub fn ott_query_boost(s: *mut ott_store, d: *const ott_query_desc, combine: u32, score_weight: f32, terms: *const c_void, n_terms: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int; // terms: n_terms ott_boost_term
     pub fn ott_query_ids(s: *mut ott_store, d: *const ott_query_desc, ids: *const u64, n_ids: u64, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int;
     pub fn ott_store_score_rows(s: *mut ott_store, queries: *const f32, nq: u32, metric: u32, ids: *const u64, n_ids: u64, out_scores: *mut f32) -> c_int;
     pub fn ott_query_mmr(s: *mut ott_store, d: *const ott_query_desc, ids: *const u64, n_ids: u64, fetch_k: u64, lambda: f32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, out_values: *mut f32, stats: *mut ott_stats) -> c_int; // ids: null, 0 = no id list; out_values: null or cap floats
@@ -259,6 +280,7 @@ const _: () = {
     assert!(std::mem::size_of::<ott_query_desc>() == 72);
     assert!(std::mem::size_of::<ott_stats>() == 120);
     assert!(std::mem::size_of::<ott_leaf>() == 32);
+    assert!(std::mem::size_of::<ott_boost_term>() == 32);
 };
 
 #[cfg(test)]

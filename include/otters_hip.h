@@ -433,6 +433,53 @@ int ott_store_eval_row_mask_slot(ott_store* s, uint32_t slot, const ott_leaf* le
 int ott_store_write_row_mask_slot(ott_store* s, uint32_t slot, const uint64_t* bits, uint64_t n_bits);
 int ott_store_clear_row_mask_slots(ott_store* s);
 
+/* Score boosting (an extension; Qdrant's score boosting / formula queries, Elasticsearch's function_score): rank by a formula of
+ * the score and metadata columns.  It cannot be built on top of take(k): a boost lifts rows that were never among the best k by raw
+ * score, so the formula is applied to EVERY candidate row, in one more streaming sweep.  terms points at n_terms ott_boost_term
+ * (declared const void*, as the group ids and mask_of_query are).
+ * THE FINAL SCORE.  Every candidate row r and query b get a final score F; all of it IEEE f32, round to nearest even, nothing
+ * fused, no flush to zero.  S = the row's score with query b: the exact path's bits.  Sw = fl(score_weight * S).  For each term j,
+ * in the caller's order, a value g_j:
+ *   VALUE      a NULL row: g_j = missing; otherwise g_j = (float)((double)x - origin), x the column's element (INT32, INT64,
+ *              DATETIME, FLOAT32, FLOAT64 each to double by the IEEE conversion), the subtraction in f64, ONE rounding to f32;
+ *   LIN_DECAY  a NULL row: g_j = missing; otherwise, with t VALUE's result and u = fl(|t| / scale): g_j = (u >= 1) ? +0.0f :
+ *              fl(1 - u); a NaN u gives NaN;
+ *   MASK       g_j = 1.0f where the slot's bit for the row is set, and for rows at or beyond the slot's bit count (the rule every
+ *              mask follows, src/vec.rs:234); otherwise 0.0f.
+ * c_j = fl(weight_j * g_j); B = c_0, then B = fl(B + c_j) for j = 1 ...  With n_terms == 0, F = Sw; with OTT_BOOST_SUM,
+ * F = fl(Sw + B); with OTT_BOOST_MULT, F = fl(Sw * fl(1.0f + B)).
+ * CANDIDATES AND ORDER.  The candidates are the rows that survive chunk_mask, the descriptor's row mask (the caller's or the
+ * evaluated device mask) and the live mask of deleted rows, exactly as in ott_query.  A row whose F is NaN is dropped; the filter
+ * (filter_cmp, filter_thr) acts on F; the hits are ordered by F under `take`, equal F by the lower row — ott_query's canonical
+ * order, signed zeros included.  hit.score = F, hit.query = b.  d->mode: OTT_MODE_PER_QUERY, or OTT_MODE_MERGED with nq == 1; cap
+ * is at least nq * min(k, rows).  With n_terms == 0 and score_weight == 1.0f the hits are exactly ott_query's on OTT_PATH_EXACT
+ * with the canonical tie order: index, score bits, order and count.
+ * Refused on the host before any device work, each with its own message (ott_boost_plan.h).  OTT_ERR_INVALID: nq == 0 or above
+ * OTT_BOOST_MAX_QUERIES; MERGED with nq > 1; n_terms above OTT_BOOST_MAX_TERMS; terms NULL with n_terms > 0; an unknown combine
+ * or kind; reserved != 0; a score_weight, weight, origin or missing that is not finite; a LIN_DECAY scale that is not finite or
+ * <= 0; an unknown column id, or a column whose length differs from the store's; a slot at or above OTT_MASK_SLOTS, or an empty
+ * one; cap too small; and what ott_query refuses.  OTT_ERR_UNSUPPORTED: OTT_PATH_MFMA (AUTO takes the sweep and never builds,
+ * extends or waits for a plane); tie_order 1 or 2; a multi-GPU store; a store of 2^32 - 16 rows or more; k_eff > 512 with more
+ * than 2^26 (query, row) pairs.  Takes the store shared, like ott_query (staged appends go first); worker contexts serve
+ * concurrent callers.  Stats: path_used = OTT_PATH_EXACT, passes = ceil(nq / 4), vectors_compared as in the masks sweep,
+ * bytes_scanned its figure plus, per row and pass, the element sizes of the VALUE and LIN_DECAY columns. */
+#define OTT_BOOST_MAX_TERMS 8
+#define OTT_BOOST_MAX_QUERIES 1024
+typedef enum { OTT_BOOST_SUM = 0, OTT_BOOST_MULT = 1 } ott_boost_combine;
+typedef enum { OTT_BOOST_VALUE = 0, OTT_BOOST_LIN_DECAY = 1, OTT_BOOST_MASK = 2 } ott_boost_kind;
+typedef struct {
+    uint32_t kind;      /* ott_boost_kind */
+    uint32_t source;    /* VALUE, LIN_DECAY: column id of ott_store_add_column; MASK: device mask slot */
+    float    weight;
+    float    scale;     /* LIN_DECAY: finite, > 0; otherwise 0 */
+    double   origin;    /* VALUE, LIN_DECAY: subtracted from the value, in f64 */
+    float    missing;   /* VALUE, LIN_DECAY: g of a NULL row */
+    uint32_t reserved;  /* 0 */
+} ott_boost_term;       /* 32 bytes, offsets 0 4 8 12 16 24 28 */
+int ott_query_boost(ott_store* s, const ott_query_desc* d, uint32_t combine, float score_weight,
+                    const void* terms /* ott_boost_term[n_terms] */, uint32_t n_terms,
+                    ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats);
+
 /* MMR diversity re-ranking (an extension; maximal marginal relevance, Carbonell and Goldstein — LangChain's
  * max_marginal_relevance_search, Qdrant's mmr query): of a query's best fetch_k hits, pick d->k greedily, each pick the most relevant
  * and the least similar to what is already picked.  The CANDIDATES are exactly the hits ott_query (ott_query_ids when ids is given)

@@ -55,6 +55,12 @@ class Leaf(C.Structure):
                 ("lit_i64", C.c_int64), ("lit_f64", C.c_double)]
 
 
+class BoostTerm(C.Structure):
+    """ott_boost_term: 32 bytes, offsets 0 4 8 12 16 24 28"""
+    _fields_ = [("kind", C.c_uint32), ("source", C.c_uint32), ("weight", C.c_float), ("scale", C.c_float),
+                ("origin", C.c_double), ("missing", C.c_float), ("reserved", C.c_uint32)]
+
+
 # ott_allgather_fn: int (*)(void* user, const void* send, void* recv, uint64_t bytes)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64)
 COMM_ID_BYTES = 128
@@ -63,6 +69,10 @@ NO_MASK = 0xFFFFFFFF          # OTT_NO_MASK: mask_of_query[b] = no mask of its o
 MASK_SLOT_BASE = 0x80000000   # OTT_MASK_SLOT_BASE + slot: a device mask slot
 MASK_SLOTS = 64               # OTT_MASK_SLOTS
 MASKS_MAX_QUERIES = 1024      # OTT_MASKS_MAX_QUERIES
+BOOST_MAX_TERMS = 8           # OTT_BOOST_MAX_TERMS
+BOOST_MAX_QUERIES = 1024      # OTT_BOOST_MAX_QUERIES
+BOOST_SUM, BOOST_MULT = 0, 1                         # ott_boost_combine
+BOOST_VALUE, BOOST_LIN_DECAY, BOOST_MASK = 0, 1, 2   # ott_boost_kind
 
 _lib = None
 
@@ -161,6 +171,7 @@ def lib() -> C.CDLL:
         "ott_store_eval_row_mask_slot": (i32, [vp, u32, vp, u32, u32, vp]),
         "ott_store_write_row_mask_slot": (i32, [vp, u32, vp, u64]),
         "ott_store_clear_row_mask_slots": (i32, [vp]),
+        "ott_query_boost": (i32, [vp, vp, u32, C.c_float, vp, u32, vp, u64, vp, vp, vp]),
         "ott_query_mmr": (i32, [vp, vp, vp, u64, u64, C.c_float, vp, u64, vp, vp, vp, vp]),
         "ott_query_recommend": (i32, [vp, vp, vp, u64, vp, u64, u32, vp, u64, vp, vp, vp]),
         "ott_query_recommend_strategy": (i32, [vp, vp, u32, vp, u64, vp, u64, u32, vp, u64, vp, vp, vp]),

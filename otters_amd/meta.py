@@ -23,9 +23,9 @@ import numpy as np
 
 from . import _native as N
 from ._native import OttersError
-from .col import Column, DataType, format_datetime
+from .col import Column, DataType, format_datetime, parse_datetime_millis
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import GROUP_SIZE_MAX, Cmp, DiscoverPlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, TakeType, VecStore, as_row_ids, infer_default_take_type, mmr_args
+from .vec import GROUP_SIZE_MAX, BoostCombine, BoostTerm, Cmp, DiscoverPlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, TakeType, VecStore, as_row_ids, boost_args, infer_default_take_type, mmr_args
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -753,6 +753,8 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         self._keep = 1  # distinct_by(name, keep=m): rows per distinct value
         self._mmr = None  # mmr(): (lambda_mult, fetch_k or None)
         self._meta_filters = None  # meta_filters(): one CompiledFilter or None per query of the batch
+        self._boosts: list = []    # boost_by / boost_decay / boost_where, in the caller's order (checked at resolve(), lowered at collect())
+        self._boost_combine = None  # boost_combine(): (combine, score_weight); None = (Sum, 1.0)
 
     def meta_filters(self, exprs) -> "MetaQueryPlan":
         """A metadata filter per query of a query_batch (a filter per request; ott_query_masks): `exprs` holds one Expr or None per
@@ -768,6 +770,42 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         except TypeError:
             self.meta_error = "meta_filters takes a sequence with one Expr or None per query"
         return self
+
+    # -- score boosting (VecQueryPlan.boost; ott_query_boost): rank by a formula of the score and the columns ---------------------------
+    def boost_by(self, name: str, weight: float, origin=0, missing: float = 0.0) -> "MetaQueryPlan":
+        """Adds weight x (column `name` - origin) to the ranking score; a NULL row contributes weight x missing.  Int32, Int64,
+        Float32, Float64 and DateTime columns (a DateTime origin may be a datetime string); a String column is refused at
+        collect(): its dictionary codes are not values.  The terms add up in the order they were given."""
+        self._boosts.append(("boost_by", str(name), weight, origin, None, missing))
+        return self
+
+    def boost_decay(self, name: str, origin, scale: float, weight: float = 1.0, missing: float = 0.0) -> "MetaQueryPlan":
+        """Adds weight x max(0, 1 - |column `name` - origin| / scale): 1 at the origin, 0 from `scale` away (for a DateTime column
+        origin may be a datetime string and scale is in milliseconds); a NULL row contributes weight x missing."""
+        self._boosts.append(("boost_decay", str(name), weight, origin, scale, missing))
+        return self
+
+    def boost_where(self, expr, weight: float) -> "MetaQueryPlan":
+        """Adds `weight` for the rows that match `expr` (an Expr or a CompiledFilter).  The filter is evaluated on the GPU into a
+        device mask slot where the evaluator takes it, on the host otherwise.  Exclusive with meta_filters, which uses the
+        slots; not on a multi-GPU store.  A compile error surfaces at collect()."""
+        try:
+            compiled = expr if isinstance(expr, CompiledFilter) else expr.compile(self.store._schema)
+            self._boosts.append(("boost_where", compiled, weight, None, None, None))
+        except ExprError as e:
+            self._boosts.append(("boost_where", f"boost_where compile error: {e}", weight, None, None, None))
+        except AttributeError:
+            self._boosts.append(("boost_where", "boost_where takes an Expr", weight, None, None, None))
+        return self
+
+    def boost_combine(self, combine: BoostCombine, score_weight: float = 1.0) -> "MetaQueryPlan":
+        """How the boost terms' sum B joins the score S: BoostCombine.Sum (default) ranks by score_weight x S + B, BoostCombine.Mult
+        by score_weight x S x (1 + B).  vec_filter then acts on that final score."""
+        self._boost_combine = (combine, score_weight)
+        return self
+
+    def _boosted(self) -> bool:
+        return bool(self._boosts) or self._boost_combine is not None
 
     def meta_filter(self, expr: Expr) -> "MetaQueryPlan":  # src/meta.rs:605-616 (error deferred to collect)
         try:
@@ -838,6 +876,17 @@ class MetaQueryPlan:  # src/meta.rs:579-830
             if len(self.queries) > 1:
                 raise OttersError("mmr takes one query, not a batch")
             mmr = mmr_args(self._mmr[0], self._mmr[1], self.take_count)
+        if self._boosted():
+            for what, on in (("with_row_ids", self._row_ids is not None), ("distinct_by", self._distinct is not None), ("mmr", self._mmr is not None)):
+                if on:
+                    raise OttersError(f"boost cannot be combined with {what} in this version")
+            if len(self.queries) > 1:
+                raise OttersError("boost takes one query, not a batch (a merged list over several boosted queries is not served)")
+            if self._path == Path.Mfma:
+                raise OttersError("boost cannot be combined with Path.Mfma: a boosted score has no certified bound; use Path.Auto or Path.Exact")
+            if st._store is not None and st._store.devices is not None:
+                raise OttersError("boost: a multi-GPU store is not served (the columns and mask slots of a boost live on one GPU)")
+            _check_boosts(self)
         k = self.take_count if self.take_count is not None else (n_groups if self._distinct is not None else st._n_rows)  # src/meta.rs:638-640
         take = self.take_type if self.take_type is not None else (infer_default_take_type(self.metric))
         for q in self.queries:
@@ -892,6 +941,8 @@ class MetaQueryPlan:  # src/meta.rs:579-830
                         use_dev = True
                     else:
                         rq.row_mask = st.build_row_mask_host(compiled)
+                if self._boosted():  # (the slots are store-global state, like the one evaluated mask: filled and read under the lock)
+                    rq.boost = boost_args(_lower_boosts(self), *(self._boost_combine or (BoostCombine.Sum, 1.0)))
                 hits, _, gstats = st._store._run(rq, chunk_mask=chunk_mask, use_device_row_mask=use_dev)
             st._store.last_stats = gstats
         evaluated = int(chunk_mask.sum()) if chunk_mask is not None else total_chunks
@@ -912,6 +963,68 @@ class MetaQueryPlan:  # src/meta.rs:579-830
         names = sorted(st._schema)  # src/meta.rs:723-724
         data = {name: st._columns[name].take(indices) for name in names}  # src/meta.rs:728-821
         return MetaQueryResults(names, data, indices, scores)
+
+
+def _check_boosts(plan: "MetaQueryPlan"):
+    """The host-side refusals of boost_by / boost_decay / boost_where, and every origin as a number: [(kind, column name or
+    CompiledFilter, weight, origin as float, scale, missing)] in the caller's order.  Pure host logic."""
+    st = plan.store
+    out = []
+    if len(plan._boosts) > N.BOOST_MAX_TERMS:
+        raise OttersError(f"boost: {len(plan._boosts)} terms are above the {N.BOOST_MAX_TERMS} one formula takes")
+    if plan._boost_combine is not None:
+        boost_args([], *plan._boost_combine)
+    for kind, what, weight, origin, scale, missing in plan._boosts:
+        if kind == "boost_where":
+            if isinstance(what, str):
+                raise OttersError(what)
+            out.append((kind, what, weight, 0.0, None, 0.0))
+            continue
+        c = st._columns.get(what)
+        if c is None:
+            raise OttersError(f"{kind}: unknown column '{what}'")
+        if c.dtype() == DataType.String:
+            raise OttersError(f"{kind}: column '{what}' is a String column; its dictionary codes are not values (boost_where takes string predicates)")
+        if isinstance(origin, str):
+            if c.dtype() != DataType.DateTime:
+                raise OttersError(f"{kind}: a datetime string is an origin for a DateTime column; '{what}' is {c.dtype().name}")
+            ms = parse_datetime_millis(origin)
+            if ms is None:
+                raise OttersError(f"{kind}: origin '{origin}' is not a datetime string")
+            origin = ms
+        out.append((kind, what, weight, float(origin), scale, missing))
+    # the numbers, checked as VecQueryPlan.boost checks them (the sources are filled in by _lower_boosts)
+    boost_args([BoostTerm.mask_slot(0, w) if kind == "boost_where" else BoostTerm.value(0, w, o, m) if kind == "boost_by" else BoostTerm.lin_decay(0, o, sc, w, m)
+                for kind, _, w, o, sc, m in out], *(plan._boost_combine or (BoostCombine.Sum, 1.0)))
+    return out
+
+
+def _lower_boosts(plan: "MetaQueryPlan", column_id=None, fill_slot=None):
+    """boost_by / boost_decay / boost_where as the BoostTerms of VecQueryPlan.boost: a column name becomes the id of its HBM-resident
+    column (column_id, default MetaStore._device_column), the i-th boost_where becomes device mask slot i, filled by
+    fill_slot(slot, compiled) -- by default evaluated on the GPU (build_row_mask_device) where _device_mask_ok accepts the filter,
+    evaluated on the host and written otherwise.  The caller holds the store's mask lock."""
+    st = plan.store
+    column_id = column_id or st._device_column
+
+    def default_fill(slot, compiled):
+        if st._device_mask_ok(compiled):
+            st.build_row_mask_device(compiled, slot=slot)
+        else:
+            st._store.write_row_mask_slot(slot, st.build_row_mask_host(compiled))
+
+    fill_slot = fill_slot or default_fill
+    terms, n_slots = [], 0
+    for kind, what, weight, origin, scale, missing in _check_boosts(plan):
+        if kind == "boost_where":
+            fill_slot(n_slots, what)
+            terms.append(BoostTerm.mask_slot(n_slots, weight))
+            n_slots += 1
+        elif kind == "boost_by":
+            terms.append(BoostTerm.value(column_id(what), weight, origin, missing))
+        else:
+            terms.append(BoostTerm.lin_decay(column_id(what), origin, scale, weight, missing))
+    return terms
 
 
 def _same_filter(a: CompiledFilter, b: CompiledFilter) -> bool:
@@ -935,6 +1048,8 @@ def _resolve_filters(plan: "MetaQueryPlan"):
         raise OttersError("meta_filters cannot be combined with distinct_by in this version")
     if plan._mmr is not None:
         raise OttersError("meta_filters cannot be combined with mmr in this version")
+    if plan._boosted():
+        raise OttersError("meta_filters cannot be combined with boost_by, boost_decay or boost_where in this version (boost_where uses the mask slots too)")
     if not plan.queries:
         raise OttersError("No queries provided")
     if len(plan._meta_filters) != len(plan.queries):

@@ -109,6 +109,7 @@ class ResolvedQuery:
     mmr_values: Optional[np.ndarray] = None    # OUTPUT of VecStore._run for an mmr plan: float32[n hits], the value of every pick
     mask_of_query: Optional[np.ndarray] = None  # with_row_masks: uint32[nq] -- an index into query_masks, N.MASK_SLOT_BASE + slot, or N.NO_MASK (ott_query_masks)
     query_masks: Optional[np.ndarray] = None    # with_row_masks: bool[n distinct masks, mask bits], every mask padded with True to the longest
+    boost: Optional[tuple] = None               # boost: (N.BoostTerm array or None, n_terms, combine, score_weight) -- ranked by the formula (ott_query_boost)
 
 
 def as_row_ids(ids) -> np.ndarray:
@@ -230,6 +231,69 @@ def mmr_args(lam, fetch_k, take_count):
     return np.float32(lam), fetch_k
 
 
+class BoostCombine(enum.IntEnum):  # include/otters_hip.h: ott_boost_combine
+    Sum = 0   # F = score_weight * S + B
+    Mult = 1  # F = score_weight * S * (1 + B)
+
+
+@dataclass(frozen=True)
+class BoostTerm:
+    """One term of a boost formula (VecQueryPlan.boost; include/otters_hip.h: ott_boost_term).  `source` is a column id of
+    VecStore.add_column (value, lin_decay) or a device mask slot (mask_slot)."""
+    kind: int
+    source: int
+    weight: float
+    scale: float = 0.0
+    origin: float = 0.0
+    missing: float = 0.0
+
+    @staticmethod
+    def value(column: int, weight: float, origin: float = 0.0, missing: float = 0.0) -> "BoostTerm":
+        """weight x (the column's value - origin); a NULL row contributes weight x missing"""
+        return BoostTerm(N.BOOST_VALUE, int(column), float(weight), 0.0, float(origin), float(missing))
+
+    @staticmethod
+    def lin_decay(column: int, origin: float, scale: float, weight: float = 1.0, missing: float = 0.0) -> "BoostTerm":
+        """weight x max(0, 1 - |value - origin| / scale); a NULL row contributes weight x missing"""
+        return BoostTerm(N.BOOST_LIN_DECAY, int(column), float(weight), float(scale), float(origin), float(missing))
+
+    @staticmethod
+    def mask_slot(slot: int, weight: float) -> "BoostTerm":
+        """weight for the rows device mask slot `slot` keeps (and the rows behind its end), 0 for the others"""
+        return BoostTerm(N.BOOST_MASK, int(slot), float(weight))
+
+
+def boost_args(terms, combine, score_weight):
+    """boost()'s arguments checked as ott_query_boost checks them: (ctypes array of N.BoostTerm or None, n_terms, combine, score
+    weight as float32).  Pure host logic."""
+    try:
+        terms = list(terms)
+    except TypeError:
+        raise OttersError("boost takes a sequence of BoostTerm") from None
+    if any(not isinstance(t, BoostTerm) for t in terms):
+        raise OttersError("boost takes a sequence of BoostTerm (BoostTerm.value, BoostTerm.lin_decay, BoostTerm.mask_slot)")
+    if len(terms) > N.BOOST_MAX_TERMS:
+        raise OttersError(f"boost: {len(terms)} terms are above the {N.BOOST_MAX_TERMS} one formula takes")
+    try:
+        combine = BoostCombine(combine)
+    except ValueError:
+        raise OttersError(f"boost: combine must be BoostCombine.Sum or BoostCombine.Mult, not {combine!r}") from None
+    if not np.isfinite(np.float32(score_weight)):
+        raise OttersError("boost: score_weight is not finite")
+    arr = (N.BoostTerm * max(len(terms), 1))()
+    for j, t in enumerate(terms):
+        if not 0 <= t.source < 2 ** 32:
+            raise OttersError(f"boost: term {j}: {t.source} is no column id or slot")
+        with np.errstate(over="ignore"):
+            w, sc, ms = np.float32(t.weight), np.float32(t.scale), np.float32(t.missing)
+        if not (np.isfinite(w) and np.isfinite(ms) and np.isfinite(t.origin)):
+            raise OttersError(f"boost: term {j}: weight, origin and missing must be finite")
+        if t.kind == N.BOOST_LIN_DECAY and not (np.isfinite(sc) and sc > 0):
+            raise OttersError(f"boost: term {j}: scale must be finite and above 0")
+        arr[j].kind, arr[j].source, arr[j].weight, arr[j].scale, arr[j].origin, arr[j].missing = t.kind, t.source, w, sc, float(t.origin), ms
+    return (arr if terms else None), len(terms), int(combine), float(np.float32(score_weight))
+
+
 def infer_default_take_type(metric: Metric) -> TakeType:  # src/vec.rs:92-98
     return TakeType.Min if metric in (Metric.Euclidean, Metric.Manhattan) else TakeType.Max
 
@@ -255,6 +319,7 @@ class VecQueryPlan:
         self.group_list = None  # with_groups: the labels as the caller gave them (mapped at validate())
         self._mmr = None        # mmr(): (lambda_mult, fetch_k or None) as the caller gave them (checked at validate())
         self.row_masks = None   # with_row_masks: one boolean array or None per query, as the caller gave them (checked at validate())
+        self._boost = None      # boost(): (terms, combine, score_weight) as the caller gave them (checked at validate())
 
     @staticmethod
     def new() -> "VecQueryPlan":
@@ -332,6 +397,17 @@ class VecQueryPlan:
         per_query(); not together with with_row_ids, one_per_group, per_group, max_sim or mmr in this version."""
         if self.error is None:
             self.row_masks = masks
+        return self
+
+    def boost(self, terms, combine: BoostCombine = BoostCombine.Sum, score_weight: float = 1.0) -> "VecQueryPlan":
+        """Score boosting (ott_query_boost): rank by F = score_weight x S + B (Sum) or score_weight x S x (1 + B) (Mult), S the
+        row's score and B the sum, in the given order, of the `terms` (BoostTerm.value / lin_decay / mask_slot over the columns of
+        VecStore.add_column and the slots of VecStore.write_row_mask_slot; at most 8).  Every surviving row is ranked by F, not
+        just the best by S; filter() acts on F, a row whose F is NaN is dropped, collect() and collect_arrays() return F as the
+        score.  All of it in f32, one rounded operation at a time.  A batch needs per_query(); not together with with_row_ids,
+        with_row_masks, one_per_group, per_group, max_sim, mmr or Path.Mfma; not on a multi-GPU store."""
+        if self.error is None:
+            self._boost = (terms, combine, score_weight)
         return self
 
     def one_per_group(self) -> "VecQueryPlan":
@@ -468,6 +544,21 @@ class VecQueryPlan:
                 raise OttersError(f"with_row_masks: {n_given} masks for {len(self.query_vectors)} queries")
             if len(self.query_vectors) > N.MASKS_MAX_QUERIES:
                 raise OttersError(f"with_row_masks: {len(self.query_vectors)} queries are above the {N.MASKS_MAX_QUERIES} one call takes")
+        if self._boost is not None:
+            for what, on in (("with_row_ids", self.row_ids is not None), ("with_row_masks", self.row_masks is not None),
+                             ("per_group", self._per_group is not None), ("one_per_group", self._grouped), ("max_sim", self._max_sim),
+                             ("mmr", self._mmr is not None)):
+                if on:
+                    raise OttersError(f"boost cannot be combined with {what} in this version")
+            if self._path == Path.Mfma:
+                raise OttersError("boost cannot be combined with Path.Mfma: a boosted score has no certified bound; use Path.Auto or Path.Exact")
+            if len(self.query_vectors) > 1 and self._mode != Mode.PerQuery:
+                raise OttersError("boost takes one query; a batch needs per_query() (a merged list over several boosted queries is not served)")
+            if len(self.query_vectors) > N.BOOST_MAX_QUERIES:
+                raise OttersError(f"boost: {len(self.query_vectors)} queries are above the {N.BOOST_MAX_QUERIES} one call takes")
+            if self.vector_store.devices is not None:
+                raise OttersError("boost: a multi-GPU store is not served (the columns and mask slots of a boost live on one GPU)")
+            boost_args(*self._boost)
         dim = self.vector_store.dim
         if isinstance(self.query_vectors, np.ndarray):  # a matrix: every row has the same length
             if self.query_vectors.shape[1] != dim:
@@ -499,7 +590,8 @@ class VecQueryPlan:
                              filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, mode=int(self._mode), path=int(self._path),
                              row_ids=None if self.row_ids is None else as_row_ids(self.row_ids), grouped=self._grouped,
                              max_sim=self._max_sim, group_size=0 if self._per_group is None else int(self._per_group), group_list=group_list,
-                             mmr=None if self._mmr is None else self._mmr_args(), mask_of_query=moq, query_masks=qm)
+                             mmr=None if self._mmr is None else self._mmr_args(), mask_of_query=moq, query_masks=qm,
+                             boost=None if self._boost is None else boost_args(*self._boost))
 
     def collect(self):  # src/vec.rs:205-311
         hits, counts = self.collect_arrays()[:2]  # (a per_group plan returns the hits' groups too)
@@ -1203,6 +1295,37 @@ class VecStore:
         """Number of groups set_groups left (0 = none)."""
         return self._n_groups
 
+    # -- metadata columns and device mask slots of a bare store (include/otters_hip.h: ott_store_add_column, ott_store_write_row_mask_slot)
+    def add_column(self, values, dtype, nulls=None) -> int:
+        """A metadata column resident in HBM beside the rows (ott_store_add_column): `values` holds len() elements of `dtype`
+        (DataType.Int32 / Int64 / Float32 / Float64 / DateTime, or its number), `nulls` an optional boolean array, True = NULL.
+        Returns the column id BoostTerm.value and BoostTerm.lin_decay name."""
+        np_dtype = {0: np.int32, 1: np.int64, 2: np.float32, 3: np.float64, 5: np.int64}.get(int(dtype))
+        if np_dtype is None:
+            raise OttersError("ott_store_add_column: only numeric / datetime columns live on the GPU")
+        vals = np.ascontiguousarray(np.asarray(values).ravel(), dtype=np_dtype)
+        words = None
+        if nulls is not None:
+            nb = np.asarray(nulls, dtype=bool).ravel()
+            if nb.size != vals.size:
+                raise OttersError(f"add_column: {nb.size} NULL flags for {vals.size} values")
+            words = N.pack_bits(nb)
+        cid = C.c_uint32(0)
+        N.check(N.lib().ott_store_add_column(self._handle(), int(dtype), N.ptr(vals), N.ptr(words), vals.size, C.byref(cid)))
+        return int(cid.value)
+
+    def write_row_mask_slot(self, slot: int, mask) -> None:
+        """A boolean row mask (True = keep; rows at or beyond its length are kept) into device mask slot `slot`
+        (ott_store_write_row_mask_slot); an empty mask empties the slot."""
+        m = np.asarray(mask, dtype=bool).ravel()
+        words = N.pack_bits(m)
+        N.check(N.lib().ott_store_write_row_mask_slot(self._handle(), int(slot), N.ptr(words), int(m.size)))
+
+    def clear_row_mask_slots(self) -> None:
+        """Every device mask slot is emptied (ott_store_clear_row_mask_slots)."""
+        if self._h is not None:
+            N.check(N.lib().ott_store_clear_row_mask_slots(self._h))
+
     def shards(self):
         """[(device, first_row, n_rows)] of the store's shards (one entry for a single-GPU store)."""
         h = self._handle()
@@ -1362,6 +1485,9 @@ class VecStore:
             moq = np.ascontiguousarray(rq.mask_of_query, dtype=np.uint32)
             N.check(N.lib().ott_query_masks(self._handle(), C.byref(d), N.ptr(words) if words.size else None, n_masks if words.size else 0, bits,
                                             N.ptr(moq), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        elif rq.boost is not None:
+            terms, n_terms, combine, score_weight = rq.boost
+            N.check(N.lib().ott_query_boost(self._handle(), C.byref(d), combine, score_weight, terms, n_terms, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         elif ids is None:
             N.check(N.lib().ott_query(self._handle(), C.byref(d), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         else:
