@@ -274,7 +274,7 @@ int ott_store_batch_ready(const ott_store* s);
 
 /* Behaviour switches of one store.  The library reads the environment exactly once per store, in ott_store_create
  * (OTT_<NAME>=<int> presets the option of the same name); after that only this call changes them — the query path never calls
- * getenv.  Nineteen options (round 5 retired the rest: experiment switches whose measurements are in DESIGN.md 3.4 and profiles/dead_ends_rounds_2_4.md).
+ * getenv.  Twenty-four options (round 5 retired the rest: experiment switches whose measurements are in DESIGN.md 3.4 and profiles/dead_ends_rounds_2_4.md).
  * Behaviour a host may want:
  *   "tie_order"  0 (default): canonical total order — better score, lower row, lower query.  1: the reference's own outcome at
  *                exact score ties, ONE TopKCollector over the store (VecStore, src/vec.rs:217-310, src/vec_compute.rs:236-277).
@@ -318,6 +318,8 @@ int ott_store_batch_ready(const ott_store* s);
  *   and runs ott_query_maxsim's sweep; environment preset OTT_GROUP_GATHER, as for every option),
  *   "masks_sweep" (2 auto, the default / 0 always by mask group / 1 the masks sweep wherever eligible: which route answers
  *   ott_query_masks; environment preset OTT_MASKS_SWEEP),
+ *   "fuse_device" (-1 auto, the default: the host route / 0 never / 1 wherever eligible: whether ott_query_fuse's first stage leaves the legs' lists
+ *   in HBM for the fuse kernel or returns them to the host first; environment preset OTT_FUSE_DEVICE),
  *   "large_k_from" (k above which host-output queries take the sort path; 0 = default: 512 for one query or a small store,
  *   128 for several queries on a large one), "small_sort" (0: results of up to 16384 (row, query) pairs with k > 512 through
  *   the radix sort instead of the rank sort), "mfma_f32" (batch path: one candidate pass on the f32 matrix pipe),
@@ -479,6 +481,60 @@ typedef struct {
 int ott_query_boost(ott_store* s, const ott_query_desc* d, uint32_t combine, float score_weight,
                     const void* terms /* ott_boost_term[n_terms] */, uint32_t n_terms,
                     ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats);
+
+/* Rank fusion (an extension; Qdrant's fusion queries over prefetches, Elasticsearch's rrf retriever, Weaviate's hybrid fusion):
+ * several queries' hit lists become ONE ranking per request, by reciprocal rank fusion (OTT_FUSE_RRF), distribution-based score
+ * fusion (OTT_FUSE_DBSF) or min-max "relative score" fusion (OTT_FUSE_MINMAX).  The normative statement is the numpy model
+ * tests/fuse_ref.py; ott_fuse_plan.h states the same formulas in C.
+ * LAYOUT (ott_query_maxsim_groups_batch's convention).  d->queries holds the legs of request 0, then of request 1, ...; d->nq is
+ * their total; legs_per_request[b] (uint32_t, declared const void* as the group ids are) says how many belong to request b.  The
+ * whole call shares the metric, the take, the filter, the chunk mask, the row mask (the caller's or the device mask), the live
+ * mask and the path.  d->k = fused hits per request; d->mode must be OTT_MODE_PER_QUERY.
+ * A LEG'S LIST is exactly what ott_query returns for that one query vector with k = min(fetch, rows), PER_QUERY, everything else of
+ * d unchanged: rows, score bits and order, on every path and tie order.  The filter acts on the leg's score: it is part of the leg.
+ * Positions are r = 0, 1, ...; a list may be shorter than fetch, or empty.
+ * CONTRIBUTION of the entry at position r with score s in leg l, w = leg_weights[l] (1 when leg_weights is NULL):
+ *   RRF     c = w / (rrf_k + (float)(r + 1)): one f32 addition, then one f32 division, each rounded to nearest.
+ *   MINMAX  best, worst = the list's first and last score (it is best first under d->take), taken to f64; span = best - worst
+ *           under OTT_TAKE_MAX, worst - best under OTT_TAKE_MIN.  If !(span > 0) every entry of the list gets nrm = 0.5f; otherwise
+ *           nrm = (float)(dist / span) with dist = s - worst (Max) or worst - s (Min), s in f64, every operation a rounded f64 one,
+ *           nothing fused.  c = w * nrm, one f32 multiplication.
+ *   DBSF    the same with worst = mean - 3 sigma (Max) or mean + 3 sigma (Min) and span = (mean + 3 sigma) - (mean - 3 sigma); dist may
+ *           be negative or exceed span: there is no clamp.  mean and the population variance are f64 sums over the list in ONE order:
+ *           partial t (0 <= t < 64) adds the terms at positions t, t + 64, t + 128, ... ascending from +0.0; then p[t] += p[t + h] for
+ *           h = 32, 16, 8, 4, 2, 1; p[0] is divided by n.  The variance's terms are (s - mean) * (s - mean), a rounded f64 product of
+ *           a rounded f64 difference; sigma is the correctly rounded f64 square root; 3 sigma one f64 product.
+ * FUSED SCORE of a row in request b: F = +0.0f, then over b's legs in ascending order, for every leg whose list holds the row,
+ * F = F + c, one rounded f32 addition each.  A row absent from a leg's list gets nothing from that leg.
+ * RANKING: F descending whatever d->take is, equal F to the lower row; a row whose F is NaN is dropped (as ott_query_boost does).
+ * Request b returns min(k, rows with a non-NaN F) hits, score = F, index = the global row, query = b; the lists come out back to
+ * back in request order, n_per_request[b] holds their lengths, *n_out their sum.  cap is at least the sum over b of
+ * min(k, legs_b x min(fetch, ott_store_len)).
+ * The first stage runs through ott_query's own internals on one query context.  On the device route its hits stay in HBM as
+ * sentinel-padded blocks and never travel (one host wait per call on the EXACT path); on the host route they come back, are
+ * staged in pinned memory and go up in one copy (tie orders 1 and 2 always take it).  Store option "fuse_device": -1 automatic
+ * (the host route: the device route measured no faster than the first stage's own spread, profiles/fuse/README.md), 0 never, 1
+ * wherever eligible; both routes run the same kernel and give the same bits.  The kernel: one workgroup per request,
+ * one launch per call; a bitonic sort of 64-bit keys (local row << 13 | leg << 9 | position) in LDS brings a row's entries together in
+ * leg order, the head of each run adds them serially (no atomics), a second sort ranks by F.  12 B of LDS per padded entry.
+ * Refused on the host before any device work, with nothing written, each with its own message (ott_fuse_plan.h).
+ * OTT_ERR_UNSUPPORTED: a mode other than PER_QUERY; a multi-GPU store; a store of 2^51 rows or more.  OTT_ERR_INVALID: n_requests
+ * 0 or above OTT_FUSE_MAX_REQUESTS; legs_per_request NULL; fetch 0 or above OTT_FUSE_MAX_FETCH; a request with 0 legs or more than
+ * OTT_FUSE_MAX_LEGS; legs_b x fetch above OTT_FUSE_MAX_ENTRIES; a sum of legs_per_request other than d->nq; an unknown fusion;
+ * with RRF an rrf_k that is not finite or below 0; a weight that is not finite; k == 0; cap too small; out NULL with cap > 0; and
+ * what ott_query refuses.  An empty store is a valid call with no hits.  Takes the store shared, like ott_query, once for both
+ * stages.  Stats: the first stage's (path_used, passes, bytes_scanned, ...); merge_ns carries the fuse kernel's event time on top;
+ * total_ns is the whole call.
+ * OUT OF SCOPE: a mask, filter or metric per leg (legs with their own filters are ott_query_masks' business; combining the two is a
+ * later change); multi-GPU stores; nested prefetches; legs that are stored rows. */
+typedef enum { OTT_FUSE_RRF = 0, OTT_FUSE_DBSF = 1, OTT_FUSE_MINMAX = 2 } ott_fusion;
+#define OTT_FUSE_MAX_LEGS 16
+#define OTT_FUSE_MAX_FETCH 512
+#define OTT_FUSE_MAX_ENTRIES 8192
+#define OTT_FUSE_MAX_REQUESTS 1024
+int ott_query_fuse(ott_store* s, const ott_query_desc* d, const void* legs_per_request /* uint32_t[n_requests] */, uint32_t n_requests,
+                   uint32_t fusion /* ott_fusion */, float rrf_k, const float* leg_weights /* [d->nq] or NULL = all 1 */, uint64_t fetch,
+                   ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_request, ott_stats* stats);
 
 /* MMR diversity re-ranking (an extension; maximal marginal relevance, Carbonell and Goldstein — LangChain's
  * max_marginal_relevance_search, Qdrant's mmr query): of a query's best fetch_k hits, pick d->k greedily, each pick the most relevant

@@ -73,6 +73,11 @@ BOOST_MAX_TERMS = 8           # OTT_BOOST_MAX_TERMS
 BOOST_MAX_QUERIES = 1024      # OTT_BOOST_MAX_QUERIES
 BOOST_SUM, BOOST_MULT = 0, 1                         # ott_boost_combine
 BOOST_VALUE, BOOST_LIN_DECAY, BOOST_MASK = 0, 1, 2   # ott_boost_kind
+FUSE_MAX_LEGS = 16            # OTT_FUSE_MAX_LEGS
+FUSE_MAX_FETCH = 512          # OTT_FUSE_MAX_FETCH
+FUSE_MAX_ENTRIES = 8192       # OTT_FUSE_MAX_ENTRIES
+FUSE_MAX_REQUESTS = 1024      # OTT_FUSE_MAX_REQUESTS
+FUSE_RRF, FUSE_DBSF, FUSE_MINMAX = 0, 1, 2           # ott_fusion
 
 _lib = None
 
@@ -172,6 +177,7 @@ def lib() -> C.CDLL:
         "ott_store_write_row_mask_slot": (i32, [vp, u32, vp, u64]),
         "ott_store_clear_row_mask_slots": (i32, [vp]),
         "ott_query_boost": (i32, [vp, vp, u32, C.c_float, vp, u32, vp, u64, vp, vp, vp]),
+        "ott_query_fuse": (i32, [vp, vp, vp, u32, u32, C.c_float, vp, u64, vp, u64, vp, vp, vp]),
         "ott_query_mmr": (i32, [vp, vp, vp, u64, u64, C.c_float, vp, u64, vp, vp, vp, vp]),
         "ott_query_recommend": (i32, [vp, vp, vp, u64, vp, u64, u32, vp, u64, vp, vp, vp]),
         "ott_query_recommend_strategy": (i32, [vp, vp, u32, vp, u64, vp, u64, u32, vp, u64, vp, vp, vp]),

@@ -94,9 +94,9 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  TWENTY-THREE of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  TWENTY-FOUR of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, group_gather, masks_sweep, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, group_gather, masks_sweep, fuse_device, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
@@ -174,6 +174,8 @@ struct Options {
     int multi_min_shard_rows = 32768;  // multi-GPU store: a shard is only brought in for this many rows (a store of fewer than twice as many stays
                                   // on its first GPU and is answered by that shard alone: the fan-out over N GPUs costs 50-150 us per query,
                                   // more than a small store's whole query); 0 = always split evenly over all shards
+    int fuse_device = -1;         // rank fusion (ott_query_fuse): -1 = automatic (ott_fuse_plan.h: the host route), 0 = always the host route (the legs'
+                                  // lists come back to the host and go up in one copy), 1 = the device route wherever it is eligible
 };
 void options_from_env(Options& o);                                   // ott_store.hip; called by ott_store_create only
 int option_set(Options& o, const char* name, long long value);       // 0, or -1 for an unknown name / bad value
@@ -402,6 +404,11 @@ struct ott_store {
     ott::host::ContextPool<ott_store> pool;  // the worker contexts (ott_host.h)
     bool is_worker = false;
     ott_store* owner = nullptr;            // workers: the store they belong to
+    // Rank fusion (ott_fuse.hip), THIS context's scratch, allocated by the first ott_query_fuse that runs on it:
+    // [the legs' hit blocks | first leg, legs and weights | counts | fused hits] (ott_fuse_plan.h: FuseLayout); h_fuse: the pinned
+    // memory behind the one upload (the first stage may still own h_stage when it is filled)
+    ott::DevBuf d_fuse;
+    ott::PinBuf h_fuse;
 };
 
 namespace ott {

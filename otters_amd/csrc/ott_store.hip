@@ -28,13 +28,13 @@ struct OptName {
     const char* name;
     int kind;  // 0 = bool, 1 = tri-state (-1 automatic / 0 / 1), 2 = non-negative int
 };
-// the twenty-three options of the product library (see struct Options) ...
+// the twenty-four options of the product library (see struct Options) ...
 const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"hi_prebuild", 1},          {"stage_appends", 1},       {"multi_transport", 2},
                              {"multi_rebalance", 0}, {"multi_min_shard_rows", 2}, {"exact_small", 1},     {"large_k_from", 2},        {"small_sort", 1},
                              {"mfma_f32", 0},        {"no_hi_pass", 0},      {"no_batch_image", 0},       {"force_fallback", 2},      {"eps_scale_ppm", 2},
                              {"multi_fake_distinct", 0}, {"exact_prune", 1},            {"exact_sketch", 1},
                              {"id_gather", 1},       {"exact_sketch_bits", 2},   {"group_gather", 1},         {"exact_sketch_head", 1},
-                             {"masks_sweep", 2},
+                             {"masks_sweep", 2},     {"fuse_device", 1},
 #ifdef OTT_MFMA_DEBUG_BUILD
                              // ... and, in the diagnostic build only, kernel tuning, timing ablations and every fallback bit by its own name
                              {"mfma_wg", 2},         {"mfma_growth", 2},     {"mfma_debug", 0},           {"mfma_abl", 2},            {"hi_tmin", 2},
@@ -42,11 +42,11 @@ const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"h
                              {"merge_rank1", 1},     {"maxsim_fold", 1},
 #endif
 };
-static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 23
+static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 24
 #ifdef OTT_MFMA_DEBUG_BUILD
                                                             + 12
 #endif
-              , "the product library's option table stays at twenty-three entries");
+              , "the product library's option table stays at twenty-four entries");
 }  // namespace
 
 int option_set(Options& o, const char* name, long long v) {
@@ -85,6 +85,7 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "exact_sketch_head") return tri(o.exact_sketch_head);
     if (n == "id_gather") return tri(o.id_gather);
     if (n == "group_gather") return tri(o.group_gather);
+    if (n == "fuse_device") return tri(o.fuse_device);
     if (n == "masks_sweep") { if (v < 0 || v > 2) return -1; o.masks_sweep = (int)v; return 0; }
 #ifdef OTT_MFMA_DEBUG_BUILD
     if (n == "maxsim_fold") return tri(o.maxsim_fold);
@@ -943,12 +944,13 @@ int ott_store_destroy(ott_store* s) {
     planes_release(s);  // (a worker has none of its own)
     mask_slots_drop(s); // (nor any mask slot)
     for (ott::DevBuf* b : {&s->d_queries, &s->d_qinv, &s->d_rowmask, &s->d_runs, &s->d_prefix, &s->d_lists, &s->d_lists2, &s->d_hits,
-                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_qmasks, &s->d_gather, &s->d_mmr, &s->d_rectable, &s->d_disc, &s->d_gtable, &s->d_gctl, &s->d_mstable, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
+                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_qmasks, &s->d_gather, &s->d_mmr, &s->d_fuse, &s->d_rectable, &s->d_disc, &s->d_gtable, &s->d_gctl, &s->d_mstable, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
                            &s->m_tau, &s->m_cntA, &s->m_cntB, &s->m_candA, &s->m_candB, &s->m_over, &s->m_out, &s->m_outcnt,
                            &s->m_uncert, &s->m_prefix, &s->x_send, &s->x_recv, &s->l_keysA, &s->l_keysB, &s->l_qA, &s->l_qB, &s->l_tmp, &s->l_cursor, &s->l_hist, &s->l_gate, &s->l_ctl})
         b->release();
     s->h_stage.release();
     s->h_hits.release();
+    s->h_fuse.release();
     s->h_disc.release();
     s->h_hdr.release();
     s->h_pend.release();

@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime, parse_datetime_millis
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import GROUP_SIZE_MAX, BoostCombine, BoostTerm, Cmp, DiscoverPlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, TakeType, VecStore, as_row_ids, boost_args, infer_default_take_type, mmr_args
+from .vec import GROUP_SIZE_MAX, BoostCombine, BoostTerm, Cmp, DiscoverPlan, FusePlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, TakeType, VecStore, as_row_ids, boost_args, infer_default_take_type, mmr_args
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -478,6 +478,11 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
         """Discovery and context search (VecStore.discover; ott_query_discover) with a meta_filter: `context` is a sequence of
         (positive, negative) row id pairs counted from the store's first row."""
         return MetaDiscoverPlan(self, context, target, target_row, metric)
+
+    def fuse(self, leg_sets, metric: Metric = Metric.Cosine) -> "MetaFusePlan":
+        """Rank fusion (VecStore.fuse; ott_query_fuse) with a meta_filter: `leg_sets` is a sequence of [legs, dim] matrices, one per
+        request; every leg is ranked under the same filter, then the legs of a request are fused."""
+        return MetaFusePlan(self, leg_sets, metric)
 
     def recommend(self, positive, negative=(), metric: Metric = Metric.Cosine, strategy: RecommendStrategy = RecommendStrategy.BestScore) -> "MetaRecommendPlan":
         """Recommend by example rows (VecStore.recommend; ott_query_recommend, or ott_query_recommend_strategy for another `strategy`
@@ -1223,6 +1228,114 @@ class MetaRecommendPlan:
         names = sorted(st._schema)
         data = {name: st._columns[name].take(indices) for name in names}
         return MetaQueryResults(names, data, indices, scores), sides.tolist()
+
+
+class MetaFusePlan:
+    """Rank fusion over a MetaStore (MetaStore.fuse; VecStore.fuse's contract): meta_filter prunes chunks by their zone maps and
+    masks rows on the device, as for MetaRecommendPlan; it and vec_filter act on every leg before the fusion.  Errors surface at
+    collect()."""
+
+    def __init__(self, store: MetaStore, leg_sets, metric: Metric):
+        self.store = store
+        self.metric = Metric(metric)
+        self._meta_filter: Optional[CompiledFilter] = None
+        self.meta_error: Optional[str] = None
+        self._plan = FusePlan(store._store, leg_sets, metric)
+
+    def _do(self, name, *args) -> "MetaFusePlan":
+        getattr(self._plan, name)(*args)
+        return self
+
+    def meta_filter(self, expr: Expr) -> "MetaFusePlan":
+        try:
+            self._meta_filter = expr.compile(self.store._schema)
+            self.meta_error = None
+        except ExprError as e:
+            self.meta_error = f"meta_filter compile error: {e}"
+        return self
+
+    def vec_filter(self, score: float, cmp: Cmp) -> "MetaFusePlan":
+        return self._do("filter", score, cmp)
+
+    filter = vec_filter
+
+    def rrf(self, k: float = 60.0) -> "MetaFusePlan":
+        return self._do("rrf", k)
+
+    def dbsf(self) -> "MetaFusePlan":
+        return self._do("dbsf")
+
+    def min_max(self) -> "MetaFusePlan":
+        return self._do("min_max")
+
+    def weights(self, list_of_lists) -> "MetaFusePlan":
+        return self._do("weights", list_of_lists)
+
+    def fetch(self, n: int) -> "MetaFusePlan":
+        return self._do("fetch", n)
+
+    def take(self, k: int) -> "MetaFusePlan":
+        return self._do("take", k)
+
+    def take_min(self, k: int) -> "MetaFusePlan":
+        return self._do("take_min", k)
+
+    def take_max(self, k: int) -> "MetaFusePlan":
+        return self._do("take_max", k)
+
+    def with_row_mask(self, mask) -> "MetaFusePlan":
+        return self._do("with_row_mask", mask)
+
+    def with_path(self, path: Path) -> "MetaFusePlan":
+        return self._do("with_path", path)
+
+    def validate(self) -> None:
+        if self.meta_error is not None:
+            raise OttersError(self.meta_error)
+        if self.store._store is None:
+            raise OttersError("fuse: the store holds no vectors")
+        self._plan.validate()
+
+    def collect_arrays(self):
+        """(hits, counts), as FusePlan.collect_arrays returns them."""
+        self.validate()
+        st = self.store
+        rf = self._plan.resolve()
+        compiled = self._meta_filter
+        chunk_mask = st.build_chunk_mask_for_plan(compiled) if compiled is not None else None
+        if chunk_mask is not None and not chunk_mask.any():
+            return np.zeros(0, dtype=N.HIT_DTYPE), [0] * int(rf.legs_per_request.size)
+        with st._mask_lock:  # the device row mask is store-global state: built and read in one critical section (MetaQueryPlan.collect)
+            use_dev = False
+            if compiled is not None and not st.row_mask_is_all_true(compiled, chunk_mask):
+                if st._device_mask_ok(compiled):
+                    if rf.row_mask is not None:
+                        raise OttersError("fuse: with_row_mask cannot be combined with a meta_filter that needs a row mask of its own")
+                    st.build_row_mask_device(compiled)
+                    use_dev = True
+                else:
+                    host = st.build_row_mask_host(compiled)
+                    if rf.row_mask is not None:
+                        m = np.ones(host.size, bool)
+                        m[: min(rf.row_mask.size, host.size)] = rf.row_mask[: host.size]
+                        host &= m
+                    rf.row_mask = host
+            hits, counts, gstats = st._store._run_fuse(rf, chunk_mask=chunk_mask, use_device_row_mask=use_dev)
+        st._store.last_stats = gstats
+        return hits, counts
+
+    def collect(self):
+        """One MetaQueryResults per request: the hits' rows materialised as MetaQueryPlan.collect does, scores = the fused scores."""
+        hits, counts = self.collect_arrays()
+        st = self.store
+        names = sorted(st._schema)
+        out, o = [], 0
+        for c in counts:
+            indices = [int(i) for i in hits["index"][o:o + c]]
+            scores = [float(s) for s in hits["score"][o:o + c]]
+            out.append(MetaQueryResults(names, {name: st._columns[name].take(indices) for name in names}, indices, scores))
+            o += c
+        return out
 
 
 class MetaDiscoverPlan:

@@ -1096,6 +1096,198 @@ class DiscoverPlan:
         return [DiscoverResult(i, s, w) for i, s, w in zip(hits["index"].tolist(), hits["score"].tolist(), wins.tolist())]
 
 
+class Fusion(enum.IntEnum):  # include/otters_hip.h: ott_fusion
+    Rrf = 0      # reciprocal rank fusion: weight / (k + rank)
+    Dbsf = 1     # distribution-based score fusion: scores normalised by mean +- 3 sigma of the leg's list
+    MinMax = 2   # min-max ("relative score") fusion: scores normalised by the leg's worst and best
+
+
+def fuse_default_fetch(k: int) -> int:
+    """Hits a leg contributes when the plan does not say: max(4 x take, 32), cut at OTT_FUSE_MAX_FETCH."""
+    return min(max(4 * int(k), 32), N.FUSE_MAX_FETCH)
+
+
+def fuse_args(legs_per_request, nq: int, fetch: int, fusion: int, rrf_k: float, weights, k: int) -> None:
+    """ott_query_fuse's argument refusals (ott_fuse_plan.h: fuse_check_args), in its order and with its texts, before any native call."""
+    who = "ott_query_fuse: "
+    n = len(legs_per_request)
+    if n == 0:
+        raise OttersError(who + "n_requests must be at least 1")
+    if n > N.FUSE_MAX_REQUESTS:
+        raise OttersError(who + f"{n} requests are above OTT_FUSE_MAX_REQUESTS ({N.FUSE_MAX_REQUESTS})")
+    if not 1 <= fetch <= N.FUSE_MAX_FETCH:
+        raise OttersError(who + f"fetch must lie between 1 and OTT_FUSE_MAX_FETCH ({N.FUSE_MAX_FETCH})")
+    for b, l in enumerate(legs_per_request):
+        if not 1 <= l <= N.FUSE_MAX_LEGS:
+            raise OttersError(who + f"request {b} has {l} legs; a request takes 1 to OTT_FUSE_MAX_LEGS ({N.FUSE_MAX_LEGS})")
+        if l * fetch > N.FUSE_MAX_ENTRIES:
+            raise OttersError(who + f"request {b} has {l * fetch} entries (legs x fetch), above OTT_FUSE_MAX_ENTRIES ({N.FUSE_MAX_ENTRIES})")
+    if sum(legs_per_request) != nq:
+        raise OttersError(who + f"legs_per_request adds up to {sum(legs_per_request)}, not to d->nq")
+    if fusion not in (0, 1, 2):
+        raise OttersError(who + "unknown fusion (OTT_FUSE_RRF, OTT_FUSE_DBSF or OTT_FUSE_MINMAX)")
+    if fusion == int(Fusion.Rrf) and not (np.isfinite(np.float32(rrf_k)) and rrf_k >= 0):
+        raise OttersError(who + "rrf_k must be finite and at least 0")
+    if weights is not None:
+        for l, w in enumerate(weights):
+            if not np.isfinite(np.float32(w)):
+                raise OttersError(who + f"the weight of leg {l} is not finite")
+    if k == 0:
+        raise OttersError(who + "k must be at least 1")
+
+
+@dataclass
+class ResolvedFuse:
+    """What FusePlan hands to ott_query_fuse once it is validated."""
+    queries: np.ndarray            # [sum of legs, dim] f32: the legs of request 0, then of request 1, ...
+    legs_per_request: np.ndarray   # uint32[B]
+    fusion: int
+    rrf_k: float
+    weights: Optional[np.ndarray]  # f32[sum of legs], or None = all 1
+    fetch: int
+    metric: int
+    take: int
+    k: int
+    filter_cmp: int
+    filter_thr: float
+    row_mask: Optional[np.ndarray]
+    path: int
+
+
+class FusePlan:
+    """Rank fusion (VecStore.fuse; ott_query_fuse): every request brings several query vectors ("legs"); each leg's best `fetch` hits
+    — exactly what store.query(leg, metric).per_query().take(fetch) returns under the same filter, masks and path — are merged into
+    one ranking per request by reciprocal rank fusion (.rrf(k), the default), distribution-based score fusion (.dbsf()) or min-max
+    score fusion (.min_max()).  A row's fused score F is the f32 sum, in leg order, of its contribution in every leg that lists it;
+    the hits are ranked by F descending, equal F by the lower row, whatever the take type is (it ranks the legs).  Lazy like
+    VecQueryPlan: errors surface at validate() / collect()."""
+
+    def __init__(self, store: "VecStore", leg_sets, metric: Metric):
+        self.vector_store = store
+        self.leg_sets = [QueryBatch(t).queries for t in leg_sets]
+        self.search_metric = Metric(metric)
+        self.fusion = Fusion.Rrf
+        self.rrf_k = 60.0
+        self.leg_weights = None
+        self.fetch_count: Optional[int] = None
+        self.filter_criteria: Optional[tuple] = None
+        self.take_type: Optional[TakeType] = None
+        self.take_count: Optional[int] = None
+        self.row_mask: Optional[np.ndarray] = None
+        self.path = Path.Auto
+
+    def rrf(self, k: float = 60.0) -> "FusePlan":
+        """Reciprocal rank fusion: the entry at position r (0 based) of a leg with weight w contributes w / (k + (r + 1))."""
+        self.fusion, self.rrf_k = Fusion.Rrf, float(k)
+        return self
+
+    def dbsf(self) -> "FusePlan":
+        """Distribution-based score fusion: a leg's scores are normalised by mean -+ 3 sigma of its list (no clamp), times its weight."""
+        self.fusion = Fusion.Dbsf
+        return self
+
+    def min_max(self) -> "FusePlan":
+        """Min-max fusion: a leg's scores are normalised to [0, 1] by its list's worst and best score, times its weight."""
+        self.fusion = Fusion.MinMax
+        return self
+
+    def weights(self, list_of_lists) -> "FusePlan":
+        """One list of weights per request, one weight per leg (default: all 1)."""
+        self.leg_weights = [list(w) for w in list_of_lists]
+        return self
+
+    def fetch(self, n: int) -> "FusePlan":
+        """Hits every leg contributes (default: max(4 x take, 32), at most 512)."""
+        self.fetch_count = int(n)
+        return self
+
+    def with_row_mask(self, mask) -> "FusePlan":
+        self.row_mask = np.asarray(mask, dtype=bool).ravel()
+        return self
+
+    def filter(self, score: float, cmp: Cmp) -> "FusePlan":
+        """The score filter acts on a leg's own score: it is part of the leg, as VecQueryPlan.filter."""
+        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
+        return self
+
+    def _take_with_options(self, count: int, take_type: Optional[TakeType]) -> "FusePlan":
+        self.take_count = int(count)
+        if take_type is not None:
+            self.take_type = take_type
+        elif self.take_type is None:
+            self.take_type = infer_default_take_type(self.search_metric)
+        return self
+
+    def take(self, count: int) -> "FusePlan":
+        return self._take_with_options(count, None)
+
+    def take_min(self, count: int) -> "FusePlan":
+        return self._take_with_options(count, TakeType.Min)
+
+    def take_max(self, count: int) -> "FusePlan":
+        return self._take_with_options(count, TakeType.Max)
+
+    def with_path(self, path: Path) -> "FusePlan":
+        self.path = Path(path)
+        return self
+
+    def _k(self) -> int:
+        return max(int(self.take_count), 0) if self.take_count is not None else max(len(self.vector_store), 1)
+
+    def _fetch(self) -> int:
+        return self.fetch_count if self.fetch_count is not None else fuse_default_fetch(self._k())
+
+    def _flat_weights(self):
+        if self.leg_weights is None:
+            return None
+        if len(self.leg_weights) != len(self.leg_sets) or any(len(w) != len(t) for w, t in zip(self.leg_weights, self.leg_sets)):
+            raise OttersError("fuse: weights takes one list per request with one weight per leg")
+        return [float(x) for w in self.leg_weights for x in w]
+
+    def validate(self) -> None:
+        st = self.vector_store
+        legs = [len(t) for t in self.leg_sets]
+        fuse_args(legs, sum(legs), self._fetch(), int(self.fusion), self.rrf_k, self._flat_weights(), self._k())
+        for t in self.leg_sets:
+            for q in ([t[0]] if isinstance(t, np.ndarray) else t):
+                if len(q) != st.dim:
+                    raise OttersError(f"Query vector length {len(q)} does not match expected dimension {st.dim}")
+        if self.path == Path.Mfma and self.search_metric == Metric.Manhattan:
+            raise OttersError("ott_query: the MFMA path does not score the Manhattan metric; use path AUTO or EXACT")
+        if st.devices is not None:
+            raise OttersError("ott_query_fuse: a multi-GPU store is not served (the legs' lists lie on different GPUs)")
+
+    def resolve(self) -> ResolvedFuse:
+        """Validate and lower the plan.  Pure host logic, no GPU."""
+        self.validate()
+        sets = [t if isinstance(t, np.ndarray) else np.stack(t).astype(np.float32, copy=False) for t in self.leg_sets]
+        w = self._flat_weights()
+        take = self.take_type if self.take_type is not None else infer_default_take_type(self.search_metric)
+        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
+        return ResolvedFuse(queries=np.ascontiguousarray(np.concatenate(sets), dtype=np.float32),
+                            legs_per_request=np.array([t.shape[0] for t in sets], dtype=np.uint32), fusion=int(self.fusion), rrf_k=float(self.rrf_k),
+                            weights=None if w is None else np.array(w, dtype=np.float32), fetch=self._fetch(), metric=int(self.search_metric),
+                            take=int(take), k=self._k(), filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, path=int(self.path))
+
+    def collect_arrays(self):
+        """(hits, counts): `hits` a NumPy record array (`index` u64, `score` f32 = the fused score F, `query` = the request), every
+        request's list best first, back to back in request order; counts[b] = the hits of request b."""
+        store = self.vector_store
+        hits, counts, stats = store._run_fuse(self.resolve())
+        store.last_stats = stats
+        return hits, counts
+
+    def collect(self):
+        """One list of SearchResult(index, fused score) per request."""
+        hits, counts = self.collect_arrays()
+        idx, sc = hits["index"].tolist(), hits["score"].tolist()
+        out, o = [], 0
+        for c in counts:
+            out.append([SearchResult(i, x) for i, x in zip(idx[o:o + c], sc[o:o + c])])
+            o += c
+        return out
+
+
 class VecStore:
     """src/vec.rs:338-412: row-major f32 vectors + per-row inverse norms, resident in HBM."""
 
@@ -1366,7 +1558,7 @@ class VecStore:
         return bool(self._n) and bool(N.lib().ott_store_batch_ready(self._handle()))
 
     def set_option(self, name: str, value: int) -> None:
-        """Behaviour switch of this store (ott_store_set_option; the twenty-three names are listed in include/otters_hip.h:
+        """Behaviour switch of this store (ott_store_set_option; the twenty-four names are listed in include/otters_hip.h:
         "tie_order", "hi_fmt", "hi_prebuild", ..., "force_fallback").  Results never depend on any but "tie_order"."""
         self._options[name] = int(value)
         if self._h is not None:
@@ -1574,6 +1766,43 @@ class VecStore:
             N.check(N.lib().ott_query_recommend_strategy(self._handle(), C.byref(d), rr.strategy, N.ptr(rr.positive), rr.positive.size, neg, rr.negative.size, rr.flags,
                                                          N.ptr(out), cap, C.byref(n_out), N.ptr(sides), C.byref(st)))
         return out[: n_out.value].copy(), sides[: n_out.value].copy(), st.as_dict()
+
+    def fuse(self, leg_sets, metric: Metric) -> FusePlan:
+        """Rank fusion (ott_query_fuse): `leg_sets` is a sequence of [legs, dim] matrices, one per request;
+        .rrf() / .dbsf() / .min_max(), .fetch(n), .take(k).collect() returns one fused ranking per request."""
+        return FusePlan(self, leg_sets, metric)
+
+    def _run_fuse(self, rf: ResolvedFuse, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
+        """ott_query_fuse.  Returns (hits HIT_DTYPE array, per-request counts, stats dict)."""
+        B = int(rf.legs_per_request.size)
+        if self._n == 0:  # an empty store: a valid call with no hits (no native store exists yet)
+            return np.zeros(0, dtype=N.HIT_DTYPE), [0] * B, N.Stats().as_dict()
+        stride = min(rf.fetch, self._n)
+        cap = max(sum(min(rf.k, int(l) * stride) for l in rf.legs_per_request), 1)
+        out = np.empty(cap, dtype=N.HIT_DTYPE)
+        d = N.QueryDesc()
+        d.queries = rf.queries.ctypes.data
+        d.nq = int(rf.queries.shape[0])
+        d.metric, d.take, d.filter_cmp, d.filter_thr = rf.metric, rf.take, rf.filter_cmp, rf.filter_thr
+        d.mode, d.k, d.path = int(Mode.PerQuery), rf.k, rf.path
+        keep = []
+        if chunk_mask is not None:
+            cm = N.pack_bits(chunk_mask)
+            keep.append(cm)
+            d.chunk_mask = cm.ctypes.data
+        if use_device_row_mask:
+            d.use_device_row_mask = 1
+        elif rf.row_mask is not None and rf.row_mask.size:
+            rm = N.pack_bits(rf.row_mask)
+            keep.append(rm)
+            d.row_mask = rm.ctypes.data
+            d.row_mask_bits = int(rf.row_mask.size)
+        n_out = C.c_uint64(0)
+        per = (C.c_uint64 * B)()
+        st = N.Stats()
+        N.check(N.lib().ott_query_fuse(self._handle(), C.byref(d), N.ptr(rf.legs_per_request), B, rf.fusion, rf.rrf_k,
+                                       N.ptr(rf.weights) if rf.weights is not None else None, rf.fetch, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        return out[: n_out.value].copy(), list(per), st.as_dict()
 
     def discover(self, context, target=None, target_row=None, metric: Metric = Metric.Cosine) -> DiscoverPlan:
         """Discovery search (ott_query_discover): `context` is a sequence of (positive, negative) row id pairs counted from the
