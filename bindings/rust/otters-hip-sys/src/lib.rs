@@ -34,6 +34,8 @@ pub const OTT_FUSE_MAX_REQUESTS: u32 = 1024; // the most requests of one call
 pub const OTT_FUSE_RRF: u32 = 0; // ott_fusion: weight / (rrf_k + rank)
 pub const OTT_FUSE_DBSF: u32 = 1; // scores normalised by mean -+ 3 sigma of the leg's list
 pub const OTT_FUSE_MINMAX: u32 = 2; // scores normalised by the leg's worst and best
+pub const OTT_SPARSE_MAX_VOCAB: u32 = 1048576; // ott_store_set_sparse: indices stay below vocab <= 2^20
+pub const OTT_SPARSE_MAX_QUERIES: u32 = 1024; // ott_query_sparse: the most queries of one call
 pub const OTT_BOOST_SUM: u32 = 0; // ott_boost_combine: F = Sw + B
 pub const OTT_BOOST_MULT: u32 = 1; // F = Sw * (1 + B)
 pub const OTT_BOOST_VALUE: u32 = 0; // ott_boost_kind: a column's value minus the origin
@@ -228,6 +230,11 @@ extern "C" {
     pub fn ott_query_ids(s: *mut ott_store, d: *const ott_query_desc, ids: *const u64, n_ids: u64, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int;
     pub fn ott_store_score_rows(s: *mut ott_store, queries: *const f32, nq: u32, metric: u32, ids: *const u64, n_ids: u64, out_scores: *mut f32) -> c_int;
     pub fn ott_query_fuse(s: *mut ott_store, d: *const ott_query_desc, legs_per_request: *const c_void, n_requests: u32, fusion: u32, rrf_k: f32, leg_weights: *const f32, fetch: u64, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_request: *mut u64, stats: *mut ott_stats) -> c_int; // legs_per_request: n_requests u32; leg_weights: null = all 1
+    pub fn ott_store_set_sparse(s: *mut ott_store, indptr: *const u64, indices: *const c_void, values: *const f32, n: u64, vocab: u32) -> c_int; // CSR: indptr n + 1, indices nnz u32 ascending inside a row, values nnz
+    pub fn ott_store_clear_sparse(s: *mut ott_store) -> c_int;
+    pub fn ott_store_sparse_info(s: *const ott_store, vocab: *mut u32, nnz: *mut u64, padded_entries: *mut u64, bytes: *mut u64) -> c_int; // *vocab 0 = no sparse rows
+    pub fn ott_store_read_sparse(s: *const ott_store, first_row: u64, n_rows: u64, indptr_out: *mut u64, indices_out: *mut c_void, values_out: *mut f32, entry_cap: u64) -> c_int; // indices_out: u32
+    pub fn ott_query_sparse(s: *mut ott_store, d: *const ott_query_desc, q_indptr: *const u64, q_indices: *const c_void, q_values: *const f32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int; // d.queries is not read, d.metric = OTT_METRIC_DOT; q_indices: u32
     pub fn ott_query_mmr(s: *mut ott_store, d: *const ott_query_desc, ids: *const u64, n_ids: u64, fetch_k: u64, lambda: f32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, out_values: *mut f32, stats: *mut ott_stats) -> c_int; // ids: null, 0 = no id list; out_values: null or cap floats
     pub fn ott_query_recommend(s: *mut ott_store, d: *const ott_query_desc, positive: *const u64, n_positive: u64, negative: *const u64, n_negative: u64, flags: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, side_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // d.queries null, d.nq 0; side_of_hit: null or cap entries
     pub fn ott_query_recommend_strategy(s: *mut ott_store, d: *const ott_query_desc, strategy: u32, positive: *const u64, n_positive: u64, negative: *const u64, n_negative: u64, flags: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, side_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // strategy 0 = ott_query_recommend; 1 / 2: flags 0, side_of_hit all 1

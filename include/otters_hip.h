@@ -320,6 +320,8 @@ int ott_store_batch_ready(const ott_store* s);
  *   ott_query_masks; environment preset OTT_MASKS_SWEEP),
  *   "fuse_device" (-1 auto, the default: the host route / 0 never / 1 wherever eligible: whether ott_query_fuse's first stage leaves the legs' lists
  *   in HBM for the fuse kernel or returns them to the host first; environment preset OTT_FUSE_DEVICE),
+ *   "sparse_table" (-1 auto, the default / 0 the LDS form wherever eligible / 1 always the device table: where ott_query_sparse's
+ *   kernel looks the query's weights up; environment preset OTT_SPARSE_TABLE),
  *   "large_k_from" (k above which host-output queries take the sort path; 0 = default: 512 for one query or a small store,
  *   128 for several queries on a large one), "small_sort" (0: results of up to 16384 (row, query) pairs with k > 512 through
  *   the radix sort instead of the rank sort), "mfma_f32" (batch path: one candidate pass on the f32 matrix pipe),
@@ -905,6 +907,53 @@ int ott_comm_all_gather_host(ott_comm* c, const void* send_host, void* recv_host
  * src/meta.rs:638-644): every rank's sorted list is exchanged whole (counts first) and merged on the host. */
 int ott_query_sharded(ott_store* s, ott_comm* c, const ott_query_desc* d, ott_hit* out, uint64_t cap, uint64_t* n_out,
                       uint64_t* n_per_query, ott_stats* stats);
+
+/* ---- sparse vectors: a sparse row per stored row, exact sparse dot search ------------------------------
+ * Row r of a store may carry a sparse row beside its dense one: ascending distinct indices below `vocab` with finite f32 values
+ * (learned sparse encoders, BM25 weights).  The rows are attached to the store the way group ids are, so row ids, chunk masks,
+ * row masks, the evaluated mask, mask slots and deleted rows mean the same for a dense and a sparse query, and a later change can
+ * fuse both kinds of list without translating ids.  A collection that has only sparse vectors is a store of dim 1.
+ *
+ * ott_store_set_sparse: the rows as CSR (indptr[n + 1], indices uint32_t[nnz], values[nnz]), n == ott_store_len.  Everything is
+ * checked on the host before any device work, and a refused call changes nothing: indptr[0] == 0, non-decreasing; every index
+ * below vocab; strictly ascending inside a row; every value finite; 1 <= vocab <= OTT_SPARSE_MAX_VOCAB.  Rows without entries
+ * and stored values of 0.0 / -0.0 are allowed and kept.  A second call replaces the first; ott_store_clear_sparse drops the rows.
+ * Both take the store exclusively and flush staged appends first.  While sparse rows are set they count as a resident metadata
+ * column (ott_store_compact is refused).  Rows appended afterwards leave the sparse rows in place, and a sparse query then fails
+ * with OTT_ERR_INVALID ("set them again"), as a grouped query does.  OTT_ERR_UNSUPPORTED on a multi-GPU store.
+ * In HBM the rows are a sliced ELL layout, 64 rows per slice: slice t is as long as its longest row, entry p of row r lies at
+ * base_t + p * 64 + (r & 63).  ott_store_sparse_info reports vocab (0 = no sparse rows), nnz, padded_entries (the sum of 64 L_t)
+ * and the bytes of the layout.  ott_store_read_sparse returns the CSR of a row range from that layout, bit for bit (indptr_out
+ * counts from 0); an entry_cap below the range's entries is OTT_ERR_INVALID with the needed count in the message.
+ *
+ * ott_query_sparse: d->nq sparse queries as CSR (q_indptr[nq + 1], q_indices uint32_t[], q_values); d->queries is not read,
+ * d->metric must be OTT_METRIC_DOT; take, filter, k, chunk mask, row mask or evaluated mask mean what they mean in ott_query_boost.
+ * PER_QUERY, or MERGED with nq == 1; at most OTT_SPARSE_MAX_QUERIES queries; cap >= nq * min(k, rows).  A query's indices are below
+ * the store's vocab and distinct, in any order; its weights are finite; a query without entries returns no hits.
+ * The score (tests/sparse_ref.py is the normative model, ott_sparse_plan.h states it in C), IEEE f32, round to nearest even,
+ * nothing fused, no flush to zero: S = +0.0f; for the row's entries j in ascending index order, wherever index_j is one of the
+ * query's, S = fl(S + fl(value_j * weight(index_j))).  A row is a CANDIDATE iff it shares at least one index with the query,
+ * whatever the values are (a row whose shared entries cancel to +0.0 is a hit, a row that shares nothing is not).  A NaN S drops
+ * the row, the filter acts on S, the order is S under `take` with equal S going to the lower row; hit.score = S, hit.query = b.
+ * OTT_ERR_UNSUPPORTED: OTT_PATH_MFMA (AUTO takes the sweep and never touches a plane), tie orders 1 and 2, a multi-GPU store, a
+ * store of 2^32 - 16 rows or more, k_eff > 512 with more than 2^26 (query, row) pairs.
+ * Store option "sparse_table" chooses where the kernel looks the weights up: -1 automatic, 0 a table in LDS wherever the vocab
+ * allows (<= 32768; one query per pass), 1 always a device table (four queries per pass).  Both give the same bits.
+ * stats: path_used = OTT_PATH_EXACT, passes, vectors_compared = the rows the chunk mask leaves per query, bytes_scanned = the
+ * layout bytes of the slices those rows lie in, per pass.
+ * Out of scope: dense and sparse legs in one ott_query_fuse call, IDF / BM25 weighting on the device, vocabularies above 2^20 or
+ * hashed 32-bit token ids (the caller remaps), multi-GPU stores, reordering rows to cut padding, compaction with sparse rows. */
+#define OTT_SPARSE_MAX_VOCAB 1048576 /* 2^20 */
+#define OTT_SPARSE_MAX_QUERIES 1024
+int ott_store_set_sparse(ott_store* s, const uint64_t* indptr /* [n + 1] */, const void* indices /* uint32_t[nnz] */,
+                         const float* values /* [nnz] */, uint64_t n, uint32_t vocab);
+int ott_store_clear_sparse(ott_store* s);
+int ott_store_sparse_info(const ott_store* s, uint32_t* vocab, uint64_t* nnz, uint64_t* padded_entries, uint64_t* bytes);
+int ott_store_read_sparse(const ott_store* s, uint64_t first_row, uint64_t n_rows, uint64_t* indptr_out /* [n_rows + 1] */,
+                          void* indices_out, float* values_out, uint64_t entry_cap);
+int ott_query_sparse(ott_store* s, const ott_query_desc* d, const uint64_t* q_indptr /* [d->nq + 1] */,
+                     const void* q_indices /* uint32_t[] */, const float* q_values,
+                     ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats);
 
 #ifdef __cplusplus
 }

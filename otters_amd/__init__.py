@@ -6,7 +6,7 @@ score filtering and top-k run as hand-written HIP kernels.  No CPU fallback.
 """
 from ._native import OttersError  # noqa: F401
 from .vec import (BoostCombine, BoostTerm, Cmp, DiscoverPlan, DiscoverResult, FusePlan, Fusion, MaxSimBatchPlan, Metric, Mode, Path, QueryBatch, RecommendPlan, RecommendStrategy, SearchResult,  # noqa: F401
-                  TakeType, VecQueryPlan, VecStore)
+                  SparseQueryPlan, TakeType, VecQueryPlan, VecStore)
 
 from .col import Column, ColumnError, DataType  # noqa: F401,E402
 from .expr import CmpOp, CompiledFilter, Expr, ExprError, col, lit  # noqa: F401,E402
@@ -15,5 +15,5 @@ from .meta import (MetaBuildStats, MetaQueryPlan, MetaQueryResults, MetaQuerySta
 
 __all__ = ["Column", "ColumnError", "DataType", "CmpOp", "CompiledFilter", "Expr", "ExprError", "col", "lit",
            "MetaBuildStats", "MetaQueryPlan", "MetaQueryResults", "MetaQueryStats", "MetaStore", "MetaStoreBuilder",
-           "OttersError", "BoostCombine", "BoostTerm", "Cmp", "DiscoverPlan", "DiscoverResult", "FusePlan", "Fusion", "MaxSimBatchPlan", "Metric", "Mode", "Path", "QueryBatch", "RecommendPlan", "RecommendStrategy", "SearchResult", "TakeType",
+           "OttersError", "BoostCombine", "BoostTerm", "Cmp", "DiscoverPlan", "DiscoverResult", "FusePlan", "Fusion", "MaxSimBatchPlan", "Metric", "Mode", "Path", "QueryBatch", "RecommendPlan", "RecommendStrategy", "SearchResult", "SparseQueryPlan", "TakeType",
            "VecQueryPlan", "VecStore"]

@@ -78,6 +78,8 @@ FUSE_MAX_FETCH = 512          # OTT_FUSE_MAX_FETCH
 FUSE_MAX_ENTRIES = 8192       # OTT_FUSE_MAX_ENTRIES
 FUSE_MAX_REQUESTS = 1024      # OTT_FUSE_MAX_REQUESTS
 FUSE_RRF, FUSE_DBSF, FUSE_MINMAX = 0, 1, 2           # ott_fusion
+SPARSE_MAX_VOCAB = 1 << 20    # OTT_SPARSE_MAX_VOCAB
+SPARSE_MAX_QUERIES = 1024     # OTT_SPARSE_MAX_QUERIES
 
 _lib = None
 
@@ -208,6 +210,11 @@ def lib() -> C.CDLL:
         "ott_comm_set_timeout_ms": (i32, [vp, C.c_int64]),
         "ott_comm_all_gather_host": (i32, [vp, vp, vp, u64]),
         "ott_query_sharded": (i32, [vp, vp, vp, vp, u64, vp, vp, vp]),
+        "ott_store_set_sparse": (i32, [vp, vp, vp, vp, u64, u32]),
+        "ott_store_clear_sparse": (i32, [vp]),
+        "ott_store_sparse_info": (i32, [vp, vp, vp, vp, vp]),
+        "ott_store_read_sparse": (i32, [vp, u64, u64, vp, vp, vp, u64]),
+        "ott_query_sparse": (i32, [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

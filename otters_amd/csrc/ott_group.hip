@@ -216,21 +216,28 @@ int sweep_prologue(ott_store* s, const ott_query_desc* d, ott_stats* st, SweepPa
     return sweep_prologue(s, d, d->queries, d->nq, st, p, grid);
 }
 
+// The stats of `nq` queries, the run plan and — where a row survives the chunk mask — the composed row mask (the descriptor's own,
+// caller's or evaluated, an id list's, the live mask): what a sweep needs before it looks at a query block
+int sweep_plan(ott_store* s, const ott_query_desc* d, uint32_t nq, ott_stats* st, RunPlan* pl, const uint64_t** row_mask, uint64_t* row_mask_bits) {
+    memset(st, 0, sizeof(*st));
+    make_run_plan(s, d->chunk_mask, *pl);
+    st->path_used = OTT_PATH_EXACT;
+    st->total_chunks = pl->total_chunks;
+    st->evaluated_chunks = pl->evaluated;
+    st->pruned_chunks = pl->total_chunks - pl->evaluated;
+    st->vectors_compared = pl->rows_scored * nq;
+    if (pl->rows_scored == 0) return OTT_OK;
+    return compose_row_mask(s, d, row_mask, row_mask_bits);
+}
+
 // ... with the query block named apart from the descriptor: `queries` nullptr = nq zeroed slots that a kernel of the caller's fills
 // from stored rows before the sweep reads them (ott_recommend.hip)
 int sweep_prologue(ott_store* s, const ott_query_desc* d, const float* queries, uint32_t nq, ott_stats* st, SweepParams* p, uint32_t* grid) {
     int rc;
-    memset(st, 0, sizeof(*st));
     RunPlan pl;
-    make_run_plan(s, d->chunk_mask, pl);
-    st->path_used = OTT_PATH_EXACT;
-    st->total_chunks = pl.total_chunks;
-    st->evaluated_chunks = pl.evaluated;
-    st->pruned_chunks = pl.total_chunks - pl.evaluated;
-    st->vectors_compared = pl.rows_scored * nq;
     *grid = 0;
+    if ((rc = sweep_plan(s, d, nq, st, &pl, &p->row_mask, &p->row_mask_bits))) return rc;
     if (pl.rows_scored == 0) return OTT_OK;
-    if ((rc = compose_row_mask(s, d, &p->row_mask, &p->row_mask_bits))) return rc;
     const std::vector<uint32_t> prefix = tile_prefix(pl, 64);
     if ((rc = upload_exact_inputs(s, queries, nq, pl, prefix))) return rc;
     st->passes = nq == 1 ? 1u : (nq + SW_NQ - 1) / SW_NQ;

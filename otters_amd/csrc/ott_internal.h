@@ -24,6 +24,7 @@
 #include "ott_recommend_plan.h"  // recommend-by-example's host-side plan (refusals, example layout, passes, k_eff, the second round, scratch bytes): HIP-free, CPU-tested
 #include "ott_mmr_plan.h"  // MMR re-ranking's host-side plan (refusals, scratch layout, the pair grid, the greedy launch): HIP-free, CPU-tested
 #include "ott_masks_plan.h"  // ott_query_masks' host-side plan (refusals, the queries' order by mask id, the route and its auto rule): HIP-free, CPU-tested
+#include "ott_sparse_plan.h"  // sparse rows and ott_query_sparse's host-side plan (refusals, the sliced-ELL layout, the lookup's form and passes, the score in C): HIP-free, CPU-tested
 #include "ott_sort_plan.h"  // the sort path's host-side plan (pass plans, sweep shape, rank or radix, prefix, slices, group extents, copy pieces): HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
 #include "ott_audit.h"  // test build: every HIP call below goes through a device-affinity check (see "which GPU a call is for")
@@ -94,9 +95,9 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  TWENTY-FOUR of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  TWENTY-FIVE of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, group_gather, masks_sweep, fuse_device, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, group_gather, masks_sweep, fuse_device, sparse_table, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
@@ -176,6 +177,8 @@ struct Options {
                                   // more than a small store's whole query); 0 = always split evenly over all shards
     int fuse_device = -1;         // rank fusion (ott_query_fuse): -1 = automatic (ott_fuse_plan.h: the host route), 0 = always the host route (the legs'
                                   // lists come back to the host and go up in one copy), 1 = the device route wherever it is eligible
+    int sparse_table = -1;        // sparse queries (ott_query_sparse): where the weight lookup reads from: -1 = automatic (ott_sparse_plan.h),
+                                  // 0 = the LDS form wherever it is eligible (vocab <= 32768), 1 = always the device table form
 };
 void options_from_env(Options& o);                                   // ott_store.hip; called by ott_store_create only
 int option_set(Options& o, const char* name, long long value);       // 0, or -1 for an unknown name / bad value
@@ -409,6 +412,21 @@ struct ott_store {
     // memory behind the one upload (the first stage may still own h_stage when it is filled)
     ott::DevBuf d_fuse;
     ott::PinBuf h_fuse;
+    // Sparse rows (ott_sparse.hip).  d_sparse: the sliced-ELL layout in one allocation (ott_sparse_plan.h:
+    // SparseLayout), made by ott_store_set_sparse and freed by ott_store_clear_sparse; nullptr = no sparse rows (and nothing else
+    // below exists).  sparse_n: the rows they cover (a query needs sparse_n == n).  sparse_base: the slices' bases on the host
+    // ([slices + 1]; read_sparse and the stats' bytes read them through `owner`).  Owned by the store (workers alias d_sparse),
+    // changed only under `rw` exclusive; independent of `cap`, so a reallocation of the rows leaves it alone.  d_spq / h_spq: THIS
+    // context's copy of a call's queries (CSR).  d_sptable: THIS context's weight table of the table form ([vocab] float4 | presence
+    // nibbles), zero whenever a query finds it: the clear kernel behind every pass leaves it so (sptable_clean, ensure_zeroed)
+    char* d_sparse = nullptr;
+    uint64_t sparse_n = 0, sparse_nnz = 0;
+    uint32_t sparse_vocab = 0;
+    ott::SparseLayout sparse_lay{};
+    std::vector<uint64_t> sparse_base;
+    ott::DevBuf d_spq, d_sptable;
+    ott::PinBuf h_spq;
+    bool sptable_clean = false;
 };
 
 namespace ott {
@@ -795,6 +813,7 @@ int check_ids(const char* who, const uint64_t* ids, uint64_t n_ids, uint64_t len
 int group_grow(ott_store* s, uint64_t ncap);
 int group_ids_of_hits(ott_store* s, const ott_hit* hits, uint64_t n, uint32_t* out);  // the groups of hits of this store: a gather from the resident ids
 void group_drop(ott_store* s);
+void sparse_drop(ott_store* s);  // ott_sparse.hip: the sparse rows go (the caller holds the store exclusively, on its device)
 void make_run_plan(const ott_store* s, const uint64_t* chunk_mask, RunPlan& pl);
 // id_span: the low key words are ~id with id < id_span (0 = the store's rows, what a grouped query's keys hold; a late-interaction
 // query's hold group ids)
@@ -804,6 +823,9 @@ int ensure_group_pairs(ott_store* s, uint64_t cap);  // the pair arrays for up t
 // upload, the kernel parameters of ott_sweep_dev.h and the grid (0 = no rows).  ensure_zeroed: a table that is zero when a query
 // finds it.  check_group_ids: the ids are set and cover the store, for entry point `fn`, before and under the lock.
 struct SweepParams;
+// sweep_plan: the part of it that needs no query block — the stats of `nq` queries, the run plan and, where a row survives the chunk
+// mask, the composed row mask (ott_sparse.hip's sweep reads no dense rows and takes only this)
+int sweep_plan(ott_store* s, const ott_query_desc* d, uint32_t nq, ott_stats* st, RunPlan* pl, const uint64_t** row_mask, uint64_t* row_mask_bits);
 int sweep_prologue(ott_store* s, const ott_query_desc* d, ott_stats* st, SweepParams* p, uint32_t* grid);
 int sweep_prologue(ott_store* s, const ott_query_desc* d, const float* queries, uint32_t nq, ott_stats* st, SweepParams* p, uint32_t* grid);  // queries: nullptr = nq zeroed slots
 int ensure_zeroed(ott_store* s, DevBuf& b, bool& clean, size_t bytes);

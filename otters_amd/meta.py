@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime, parse_datetime_millis
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import GROUP_SIZE_MAX, BoostCombine, BoostTerm, Cmp, DiscoverPlan, FusePlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, TakeType, VecStore, as_row_ids, boost_args, infer_default_take_type, mmr_args
+from .vec import GROUP_SIZE_MAX, BoostCombine, BoostTerm, Cmp, DiscoverPlan, FusePlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, SparseQueryPlan, TakeType, VecStore, as_row_ids, boost_args, infer_default_take_type, mmr_args
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -272,6 +272,7 @@ class MetaStoreBuilder:  # src/meta.rs:62-306
         self.bloom = ("Fpr", 0.01)
         self.device = device
         self.devices = devices  # several GPUs of this process: one store over all of them (VecStore(devices=...))
+        self.sparse = None      # with_sparse: (indptr, indices, values, vocab)
 
     def with_vectors(self, vectors) -> "MetaStoreBuilder":
         self.vectors = vectors
@@ -301,6 +302,12 @@ class MetaStoreBuilder:  # src/meta.rs:62-306
     def with_columns(self, columns) -> "MetaStoreBuilder":  # src/meta.rs:131-148
         for name, c in columns:
             self.with_column(name, c)
+        return self
+
+    def with_sparse(self, indptr, indices, values, vocab: int) -> "MetaStoreBuilder":
+        """extension: a sparse row per row, as CSR (VecStore.set_sparse), for MetaStore.sparse_query.  A sparse-only collection gives
+        with_vectors a matrix of dim 1."""
+        self.sparse = (indptr, indices, values, int(vocab))
         return self
 
     def with_random_vectors(self, n_rows: int, dim: int, seed: int) -> "MetaStoreBuilder":
@@ -351,6 +358,10 @@ class MetaStoreBuilder:  # src/meta.rs:62-306
                 store.append_random(n_rows, seed)
             else:
                 store.add_vectors(mat)
+            if self.sparse is not None:
+                store.set_sparse(*self.sparse)
+        elif self.sparse is not None and len(self.sparse[0]) != n_rows + 1:
+            raise OttersError(f"with_sparse: indptr has {len(self.sparse[0])} entries for {n_rows} rows")
         ingest = time.perf_counter() - t_ing
 
         tz = time.perf_counter()
@@ -483,6 +494,11 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
         """Rank fusion (VecStore.fuse; ott_query_fuse) with a meta_filter: `leg_sets` is a sequence of [legs, dim] matrices, one per
         request; every leg is ranked under the same filter, then the legs of a request are fused."""
         return MetaFusePlan(self, leg_sets, metric)
+
+    def sparse_query(self, q) -> "MetaSparsePlan":
+        """Exact sparse dot search (VecStore.sparse_query; ott_query_sparse) with a meta_filter: `q` is one (indices, values) pair or
+        a list of them; .meta_filter(expr).vec_filter(...).take(k).collect()."""
+        return MetaSparsePlan(self, q)
 
     def recommend(self, positive, negative=(), metric: Metric = Metric.Cosine, strategy: RecommendStrategy = RecommendStrategy.BestScore) -> "MetaRecommendPlan":
         """Recommend by example rows (VecStore.recommend; ott_query_recommend, or ott_query_recommend_strategy for another `strategy`
@@ -1336,6 +1352,101 @@ class MetaFusePlan:
             out.append(MetaQueryResults(names, {name: st._columns[name].take(indices) for name in names}, indices, scores))
             o += c
         return out
+
+
+class MetaSparsePlan:
+    """Sparse search over a MetaStore (MetaStore.sparse_query; VecStore.sparse_query's contract): meta_filter prunes chunks by their
+    zone maps and masks rows on the device, exactly as the dense meta query does.  Errors surface at collect()."""
+
+    def __init__(self, store: MetaStore, q):
+        self.store = store
+        self._meta_filter: Optional[CompiledFilter] = None
+        self.meta_error: Optional[str] = None
+        self._plan = SparseQueryPlan(store._store, q)
+
+    def _do(self, name, *args) -> "MetaSparsePlan":
+        getattr(self._plan, name)(*args)
+        return self
+
+    def meta_filter(self, expr: Expr) -> "MetaSparsePlan":
+        try:
+            self._meta_filter = expr.compile(self.store._schema)
+            self.meta_error = None
+        except ExprError as e:
+            self.meta_error = f"meta_filter compile error: {e}"
+        return self
+
+    def vec_filter(self, score: float, cmp: Cmp) -> "MetaSparsePlan":
+        return self._do("filter", score, cmp)
+
+    filter = vec_filter
+
+    def take(self, k: int) -> "MetaSparsePlan":
+        return self._do("take", k)
+
+    def take_min(self, k: int) -> "MetaSparsePlan":
+        return self._do("take_min", k)
+
+    def take_max(self, k: int) -> "MetaSparsePlan":
+        return self._do("take_max", k)
+
+    def with_row_mask(self, mask) -> "MetaSparsePlan":
+        return self._do("with_row_mask", mask)
+
+    def with_path(self, path: Path) -> "MetaSparsePlan":
+        return self._do("with_path", path)
+
+    def collect_arrays(self):
+        """(hits, counts), as SparseQueryPlan.collect_arrays returns them."""
+        if self.meta_error is not None:
+            raise OttersError(self.meta_error)
+        st = self.store
+        if st._store is None:
+            raise OttersError("sparse_query: the store holds no vectors")
+        self._plan.vector_store = st._store
+        rs = self._plan.resolve()
+        nq = int(rs.indptr.size - 1)
+        compiled = self._meta_filter
+        chunk_mask = st.build_chunk_mask_for_plan(compiled) if compiled is not None else None
+        if chunk_mask is not None and not chunk_mask.any():
+            return np.zeros(0, dtype=N.HIT_DTYPE), [0] * nq
+        with st._mask_lock:  # the device row mask is store-global state: built and read in one critical section (MetaQueryPlan.collect)
+            use_dev = False
+            if compiled is not None and not st.row_mask_is_all_true(compiled, chunk_mask):
+                if st._device_mask_ok(compiled):
+                    if rs.row_mask is not None:
+                        raise OttersError("sparse_query: with_row_mask cannot be combined with a meta_filter that needs a row mask of its own")
+                    st.build_row_mask_device(compiled)
+                    use_dev = True
+                else:
+                    host = st.build_row_mask_host(compiled)
+                    if rs.row_mask is not None:
+                        m = np.ones(host.size, bool)
+                        m[: min(rs.row_mask.size, host.size)] = rs.row_mask[: host.size]
+                        host &= m
+                    rs.row_mask = host
+            hits, counts, gstats = st._store._run_sparse(rs, chunk_mask=chunk_mask, use_device_row_mask=use_dev)
+        st._store.last_stats = gstats
+        return hits, counts
+
+    def collect_per_query(self):
+        """One MetaQueryResults per query: the hits' rows materialised as MetaQueryPlan.collect does, scores = S."""
+        hits, counts = self.collect_arrays()
+        st = self.store
+        names = sorted(st._schema)
+        out, o = [], 0
+        for c in counts:
+            indices = [int(i) for i in hits["index"][o:o + c]]
+            scores = [float(x) for x in hits["score"][o:o + c]]
+            out.append(MetaQueryResults(names, {name: st._columns[name].take(indices) for name in names}, indices, scores))
+            o += c
+        return out
+
+    def collect(self):
+        """The MetaQueryResults of ONE query; a batch needs collect_per_query()."""
+        if len(self._plan.queries) != 1:
+            raise OttersError("ott_query_sparse: a batch needs OTT_MODE_PER_QUERY (a merged list over several sparse queries is not served)")
+        return self.collect_per_query()[0]
 
 
 class MetaDiscoverPlan:

@@ -1288,6 +1288,122 @@ class FusePlan:
         return out
 
 
+SPARSE_MAX_VOCAB = 1 << 20      # include/otters_hip.h: OTT_SPARSE_MAX_VOCAB
+SPARSE_MAX_QUERIES = 1024       # include/otters_hip.h: OTT_SPARSE_MAX_QUERIES
+
+
+def sparse_csr(rows):
+    """A list of (indices, values) pairs -> (indptr uint64[n + 1], indices uint32[nnz], values float32[nnz]).  Nothing is sorted
+    or merged: ott_store_set_sparse and ott_query_sparse check what they are given."""
+    idx, val, ptr = [], [], [0]
+    for r, (i, v) in enumerate(rows):
+        i = np.asarray(i).ravel()
+        v = np.asarray(v, dtype=np.float32).ravel()
+        if i.size != v.size:
+            raise OttersError(f"sparse vector {r}: {i.size} indices for {v.size} values")
+        if i.size and (i.min() < 0 or i.max() > 0xFFFFFFFF):
+            raise OttersError(f"sparse vector {r}: an index is not a 32-bit unsigned integer")
+        idx.append(i.astype(np.uint32))
+        val.append(v)
+        ptr.append(ptr[-1] + int(i.size))
+    return (np.array(ptr, dtype=np.uint64), np.concatenate(idx) if idx else np.zeros(0, np.uint32),
+            np.concatenate(val) if val else np.zeros(0, np.float32))
+
+
+@dataclass
+class ResolvedSparse:
+    """What SparseQueryPlan hands to ott_query_sparse once it is validated."""
+    indptr: np.ndarray   # uint64[nq + 1]
+    indices: np.ndarray  # uint32[]
+    values: np.ndarray   # float32[]
+    take: int
+    k: int
+    filter_cmp: int
+    filter_thr: float
+    row_mask: Optional[np.ndarray]
+    path: int
+
+
+class SparseQueryPlan:
+    """Exact sparse dot search over the store's sparse rows (VecStore.sparse_query; ott_query_sparse): a row is a hit iff it shares
+    an index with the query; its score adds value x weight over the shared indices in the row's index order, one rounded f32
+    operation at a time.  Lazy like VecQueryPlan: errors surface at collect()."""
+
+    def __init__(self, store: "VecStore", q):
+        self.vector_store = store
+        single = isinstance(q, tuple) and len(q) == 2 and not (len(q[0]) and isinstance(q[0][0], (tuple, list, np.ndarray)))
+        self.queries = [q] if single else list(q)
+        self.filter_criteria: Optional[tuple] = None
+        self.take_type: Optional[TakeType] = None
+        self.take_count: Optional[int] = None
+        self.row_mask: Optional[np.ndarray] = None
+        self.path = Path.Auto
+
+    def with_row_mask(self, mask) -> "SparseQueryPlan":
+        self.row_mask = np.asarray(mask, dtype=bool).ravel()
+        return self
+
+    def filter(self, score: float, cmp: Cmp) -> "SparseQueryPlan":
+        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
+        return self
+
+    def _take_with_options(self, count: int, take_type: Optional[TakeType]) -> "SparseQueryPlan":
+        self.take_count = int(count)
+        if take_type is not None:
+            self.take_type = take_type
+        elif self.take_type is None:
+            self.take_type = infer_default_take_type(Metric.DotProduct)
+        return self
+
+    def take(self, count: int) -> "SparseQueryPlan":
+        return self._take_with_options(count, None)
+
+    def take_min(self, count: int) -> "SparseQueryPlan":
+        return self._take_with_options(count, TakeType.Min)
+
+    def take_max(self, count: int) -> "SparseQueryPlan":
+        return self._take_with_options(count, TakeType.Max)
+
+    def with_path(self, path: Path) -> "SparseQueryPlan":
+        self.path = Path(path)
+        return self
+
+    def resolve(self) -> ResolvedSparse:
+        """Lower the plan.  Pure host logic, no GPU; the library checks the queries against the store's vocab."""
+        if not self.queries:
+            raise OttersError("No queries provided")
+        ptr, idx, val = sparse_csr(self.queries)
+        k = self.take_count if self.take_count is not None else len(self.vector_store)
+        take = self.take_type if self.take_type is not None else infer_default_take_type(Metric.DotProduct)
+        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
+        return ResolvedSparse(indptr=ptr, indices=idx, values=val, take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask,
+                              path=int(self.path))
+
+    def collect_arrays(self):
+        """(hits, counts): `hits` a NumPy record array (`index` u64, `score` f32 = S, `query`), every query's list best first, back
+        to back in query order; counts[b] = the hits of query b."""
+        store = self.vector_store
+        hits, counts, stats = store._run_sparse(self.resolve())
+        store.last_stats = stats
+        return hits, counts
+
+    def collect_per_query(self):
+        """One list of SearchResult(index, score) per query."""
+        hits, counts = self.collect_arrays()
+        idx, sc = hits["index"].tolist(), hits["score"].tolist()
+        out, o = [], 0
+        for c in counts:
+            out.append([SearchResult(i, x) for i, x in zip(idx[o:o + c], sc[o:o + c])])
+            o += c
+        return out
+
+    def collect(self):
+        """The hits of ONE query as a list of SearchResult(index, score); a batch needs collect_per_query()."""
+        if len(self.queries) != 1:
+            raise OttersError("ott_query_sparse: a batch needs OTT_MODE_PER_QUERY (a merged list over several sparse queries is not served)")
+        return self.collect_per_query()[0]
+
+
 class VecStore:
     """src/vec.rs:338-412: row-major f32 vectors + per-row inverse norms, resident in HBM."""
 
@@ -1518,6 +1634,88 @@ class VecStore:
         if self._h is not None:
             N.check(N.lib().ott_store_clear_row_mask_slots(self._h))
 
+    # -- sparse rows (include/otters_hip.h: ott_store_set_sparse, ott_query_sparse) --------------------------------------------
+    def set_sparse(self, indptr, indices, values, vocab: int) -> None:
+        """A sparse row per stored row, as CSR: indptr[len() + 1], ascending distinct indices below `vocab` inside a row, finite
+        values.  The store keeps them in HBM as a sliced ELL layout.  A second call replaces the first; rows appended afterwards
+        need a new call.  While sparse rows are set, compact() is refused.  Not on a multi-GPU store."""
+        ptr = np.ascontiguousarray(np.asarray(indptr).ravel(), dtype=np.uint64)
+        idx = np.asarray(indices).ravel()
+        if idx.size and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+            raise OttersError("ott_store_set_sparse: an index is not a 32-bit unsigned integer")
+        idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        val = np.ascontiguousarray(np.asarray(values).ravel(), dtype=np.float32)
+        if ptr.size == 0 or idx.size != val.size or int(ptr[-1]) != idx.size:
+            raise OttersError(f"ott_store_set_sparse: indptr ends at {int(ptr[-1]) if ptr.size else 0}, {idx.size} indices and {val.size} values were given")
+        if not 0 <= int(vocab) <= 0xFFFFFFFF:
+            raise OttersError(f"ott_store_set_sparse: vocab {vocab} is not in 1 .. OTT_SPARSE_MAX_VOCAB ({SPARSE_MAX_VOCAB}); remap the indices")
+        N.check(N.lib().ott_store_set_sparse(self._handle(), N.ptr(ptr), N.ptr(idx), N.ptr(val), ptr.size - 1, int(vocab)))
+
+    def set_sparse_rows(self, rows, vocab: int) -> None:
+        """set_sparse for a list of (indices, values) pairs, one per stored row."""
+        self.set_sparse(*sparse_csr(rows), vocab)
+
+    def clear_sparse(self) -> None:
+        if self._h is not None:
+            N.check(N.lib().ott_store_clear_sparse(self._h))
+
+    def sparse_info(self) -> Optional[dict]:
+        """{vocab, nnz, padded_entries, bytes} of the sparse rows in HBM, None when none are set."""
+        if self._h is None:
+            return None
+        vocab, nnz, padded, nbytes = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        N.check(N.lib().ott_store_sparse_info(self._h, C.byref(vocab), C.byref(nnz), C.byref(padded), C.byref(nbytes)))
+        if vocab.value == 0:
+            return None
+        return {"vocab": int(vocab.value), "nnz": int(nnz.value), "padded_entries": int(padded.value), "bytes": int(nbytes.value)}
+
+    def read_sparse(self, first: int = 0, n: Optional[int] = None):
+        """(indptr, indices, values): the CSR of sparse rows [first, first + n), read back from the device layout bit for bit."""
+        info = self.sparse_info()
+        if info is None:
+            raise OttersError("ott_store_read_sparse: no sparse rows are set (ott_store_set_sparse)")
+        n = self._n - first if n is None else n
+        ptr = np.zeros(max(n, 0) + 1, dtype=np.uint64)
+        idx = np.zeros(max(info["nnz"], 1), dtype=np.uint32)
+        val = np.zeros(max(info["nnz"], 1), dtype=np.float32)
+        N.check(N.lib().ott_store_read_sparse(self._h, int(first), int(n), N.ptr(ptr), N.ptr(idx), N.ptr(val), info["nnz"]))
+        nnz = int(ptr[-1])
+        return ptr, idx[:nnz].copy(), val[:nnz].copy()
+
+    def sparse_query(self, q) -> SparseQueryPlan:
+        """Exact sparse dot search (ott_query_sparse): `q` is one (indices, values) pair or a list of them; indices distinct and
+        below the store's vocab, in any order.  .take(k).collect() for one query, .collect_per_query() for a batch."""
+        return SparseQueryPlan(self, q)
+
+    def _run_sparse(self, rs: ResolvedSparse, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
+        """ott_query_sparse.  Returns (hits HIT_DTYPE array, per-query counts, stats dict)."""
+        nq = int(rs.indptr.size - 1)
+        cap = max(nq * min(rs.k, self._n), 1)
+        out = np.empty(cap, dtype=N.HIT_DTYPE)
+        d = N.QueryDesc()
+        d.queries = None
+        d.nq = nq
+        d.metric, d.take, d.filter_cmp, d.filter_thr = int(Metric.DotProduct), rs.take, rs.filter_cmp, rs.filter_thr
+        d.mode, d.k, d.path = int(Mode.PerQuery if nq > 1 else Mode.Merged), rs.k, rs.path
+        keep = []
+        if chunk_mask is not None:
+            cm = N.pack_bits(chunk_mask)
+            keep.append(cm)
+            d.chunk_mask = cm.ctypes.data
+        if use_device_row_mask:
+            d.use_device_row_mask = 1
+        elif rs.row_mask is not None and rs.row_mask.size:
+            rm = N.pack_bits(rs.row_mask)
+            keep.append(rm)
+            d.row_mask = rm.ctypes.data
+            d.row_mask_bits = int(rs.row_mask.size)
+        n_out = C.c_uint64(0)
+        per = (C.c_uint64 * max(nq, 1))()
+        st = N.Stats()
+        N.check(N.lib().ott_query_sparse(self._handle(), C.byref(d), N.ptr(rs.indptr), N.ptr(rs.indices) if rs.indices.size else None,
+                                         N.ptr(rs.values) if rs.values.size else None, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        return out[: n_out.value].copy(), list(per)[:nq], st.as_dict()
+
     def shards(self):
         """[(device, first_row, n_rows)] of the store's shards (one entry for a single-GPU store)."""
         h = self._handle()
@@ -1558,7 +1756,7 @@ class VecStore:
         return bool(self._n) and bool(N.lib().ott_store_batch_ready(self._handle()))
 
     def set_option(self, name: str, value: int) -> None:
-        """Behaviour switch of this store (ott_store_set_option; the twenty-four names are listed in include/otters_hip.h:
+        """Behaviour switch of this store (ott_store_set_option; the twenty-five names are listed in include/otters_hip.h:
         "tie_order", "hi_fmt", "hi_prebuild", ..., "force_fallback").  Results never depend on any but "tie_order"."""
         self._options[name] = int(value)
         if self._h is not None:
