@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _native as N
 from .meta import MetaQueryPlan, MetaQueryResults, MetaQueryStats
-from .vec import Metric, Mode, ResolvedQuery, SearchResult, VecQueryPlan, VecStore
+from .vec import Metric, Mode, ResolvedQuery, SearchResult, VecQueryPlan, VecStore, query_desc
 
 SENTINEL_INDEX = np.uint64(0xFFFFFFFFFFFFFFFF)
 
@@ -273,22 +273,9 @@ class ShardedVecStore:
         k_out = min(rq.k, pool)  # the whole job cannot return more than exists
         cap = max(k_out * (nq if perq else 1), 1)
         # ott_query_sharded's contract is cap >= k (or nq * k); a k beyond the corpus is clamped here, identically on every rank
-        d = N.QueryDesc()
-        d.queries = rq.queries.ctypes.data
-        d.nq = nq
-        d.metric, d.take, d.filter_cmp, d.filter_thr = rq.metric, rq.take, rq.filter_cmp, rq.filter_thr
-        d.mode, d.k, d.path = rq.mode, k_out, rq.path
-        keep = []
-        if chunk_mask is not None:  # this shard's zonemap prune (bit c = local chunk c)
-            cm = N.pack_bits(chunk_mask)
-            keep.append(cm)
-            d.chunk_mask = cm.ctypes.data
-        if use_device_row_mask:
-            d.use_device_row_mask = 1
-        elif rq.row_mask is not None and rq.row_mask.size:
-            rm = N.pack_bits(rq.row_mask)
-            keep.append(rm)
-            d.row_mask, d.row_mask_bits = rm.ctypes.data, int(rq.row_mask.size)
+        # chunk_mask: this shard's zonemap prune (bit c = local chunk c)
+        d, keep = query_desc(rq, rq.queries, nq, rq.mode, chunk_mask, use_device_row_mask)
+        d.k = k_out
         out = np.empty(cap, dtype=N.HIT_DTYPE)
         n_out = C.c_uint64(0)
         per = (C.c_uint64 * nq)()

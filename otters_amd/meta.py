@@ -758,7 +758,19 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
         return N.unpack_bits(out, self._n_rows) if fetch else None
 
 
-class MetaQueryPlan:  # src/meta.rs:579-830
+class _MetaFiltered:
+    """A plan over a MetaStore (`store`) with a meta_filter: `_meta_filter` is the compiled filter, `meta_error` what collect() raises."""
+
+    def meta_filter(self, expr: Expr):  # src/meta.rs:605-616 (error deferred to collect)
+        try:
+            self._meta_filter = expr.compile(self.store._schema)
+            self.meta_error = None
+        except ExprError as e:
+            self.meta_error = f"meta_filter compile error: {e}"
+        return self
+
+
+class MetaQueryPlan(_MetaFiltered):  # src/meta.rs:579-830
     def __init__(self, store: MetaStore, queries, metric: Metric):
         self.store = store
         self.queries = queries
@@ -827,14 +839,6 @@ class MetaQueryPlan:  # src/meta.rs:579-830
 
     def _boosted(self) -> bool:
         return bool(self._boosts) or self._boost_combine is not None
-
-    def meta_filter(self, expr: Expr) -> "MetaQueryPlan":  # src/meta.rs:605-616 (error deferred to collect)
-        try:
-            self._meta_filter = expr.compile(self.store._schema)
-            self.meta_error = None
-        except ExprError as e:
-            self.meta_error = f"meta_filter compile error: {e}"
-        return self
 
     def vec_filter(self, score: float, cmp: Cmp) -> "MetaQueryPlan":  # src/meta.rs:618-621
         self._vec_filter = (float(np.float32(score)), Cmp(cmp))
@@ -979,11 +983,7 @@ class MetaQueryPlan:  # src/meta.rs:579-830
                                         max(total - prune - merge_d, 0.0), merge_d, total,
                                         bytes_scanned=gstats["bytes_scanned"] if gstats else 0,
                                         path_used=gstats["path_used"] if gstats else 0, gpu_score_ms=score_d * 1e3)
-        indices = [int(i) for i in hits["index"]]
-        scores = [float(s) for s in hits["score"]]
-        names = sorted(st._schema)  # src/meta.rs:723-724
-        data = {name: st._columns[name].take(indices) for name in names}  # src/meta.rs:728-821
-        return MetaQueryResults(names, data, indices, scores)
+        return _materialise(st, hits)
 
 
 def _check_boosts(plan: "MetaQueryPlan"):
@@ -1143,66 +1143,103 @@ def _collect_per_query(plan: "MetaQueryPlan"):
     st._last_stats = MetaQueryStats(total_chunks, total_chunks - evaluated, evaluated, int(compared), prune, max(total - prune - merge_d, 0.0), merge_d, total,
                                     bytes_scanned=gstats["bytes_scanned"] if gstats else 0, path_used=gstats["path_used"] if gstats else 0,
                                     gpu_score_ms=(gstats["score_ns"] / 1e6) if gstats else 0.0)
-    names = sorted(st._schema)
+    return _materialise(st, hits, counts)
+
+
+def _materialise(st: "MetaStore", hits, counts=None):
+    """The hits' rows as MetaQueryResults (src/meta.rs:722-828); with `counts`, a list of them: the hits split by the per-query
+    counts."""
+    names = sorted(st._schema)  # src/meta.rs:723-724
+
+    def rows(part):
+        indices = [int(i) for i in part["index"]]
+        return MetaQueryResults(names, {name: st._columns[name].take(indices) for name in names}, indices, [float(s) for s in part["score"]])
+
+    if counts is None:
+        return rows(hits)
     out, at = [], 0
     for c in counts:
-        part = hits[at:at + int(c)]
+        out.append(rows(hits[at:at + int(c)]))
         at += int(c)
-        indices = [int(i) for i in part["index"]]
-        out.append(MetaQueryResults(names, {name: st._columns[name].take(indices) for name in names}, indices, [float(x) for x in part["score"]]))
     return out
 
 
-class MetaRecommendPlan:
+def _run_filtered(st: "MetaStore", compiled: Optional[CompiledFilter], resolved, kind: str, run):
+    """The meta filter stage of the extension plans: the zone maps prune chunks, the row mask is evaluated on the device where the
+    evaluator takes the filter and on the host otherwise (there ANDed with the caller's own mask, rows behind its end kept), then
+    `run(resolved, chunk_mask=, use_device_row_mask=)` -- one of VecStore._run_* -- returns (a, b, stats).  Returns (a, b), or
+    None when no chunk survives (nothing runs).  `kind`: the word the refusal names."""
+    chunk_mask = st.build_chunk_mask_for_plan(compiled) if compiled is not None else None
+    if chunk_mask is not None and not chunk_mask.any():
+        return None
+    with st._mask_lock:  # the device row mask is store-global state: built and read in one critical section (MetaQueryPlan.collect)
+        use_dev = False
+        if compiled is not None and not st.row_mask_is_all_true(compiled, chunk_mask):
+            if st._device_mask_ok(compiled):
+                if resolved.row_mask is not None:
+                    raise OttersError(f"{kind}: with_row_mask cannot be combined with a meta_filter that needs a row mask of its own")
+                st.build_row_mask_device(compiled)
+                use_dev = True
+            else:
+                host = st.build_row_mask_host(compiled)
+                if resolved.row_mask is not None:
+                    m = np.ones(host.size, bool)
+                    m[: min(resolved.row_mask.size, host.size)] = resolved.row_mask[: host.size]
+                    host &= m
+                resolved.row_mask = host
+        a, b, gstats = run(resolved, chunk_mask=chunk_mask, use_device_row_mask=use_dev)
+    st._store.last_stats = gstats
+    return a, b
+
+
+class _MetaWrapper(_MetaFiltered):
+    """What the extension plans over a MetaStore share: a meta_filter, and the builder calls of the VecStore plan
+    underneath (`_plan`; None where the store holds no vectors: the calls then do nothing, and collect() names the fault)."""
+
+    def __init__(self, store: MetaStore, plan):
+        self.store = store
+        self._meta_filter: Optional[CompiledFilter] = None
+        self.meta_error: Optional[str] = None
+        self._plan = plan
+
+    def _forward(self, name, *args):
+        if self._plan is not None:
+            getattr(self._plan, name)(*args)
+        return self
+
+    def vec_filter(self, score: float, cmp: Cmp):
+        return self._forward("filter", score, cmp)
+
+    filter = vec_filter
+
+    def take(self, k: int):
+        return self._forward("take", k)
+
+    def take_min(self, k: int):
+        return self._forward("take_min", k)
+
+    def take_max(self, k: int):
+        return self._forward("take_max", k)
+
+    def with_row_mask(self, mask):
+        return self._forward("with_row_mask", mask)
+
+    def with_path(self, path: Path):
+        return self._forward("with_path", path)
+
+
+class MetaRecommendPlan(_MetaWrapper):
     """Recommend by example rows over a MetaStore (MetaStore.recommend; VecStore.recommend's contract): meta_filter prunes chunks
     by their zone maps and masks rows on the device, as for MetaQueryPlan.mmr; vec_filter acts on a row's best positive score (the strategy
     BestScore), on the sum S (SumScores) or on the query's score (AverageVector), as RecommendPlan.filter.  An
     example need not pass the filter: stored data is read.  Errors surface at collect()."""
 
     def __init__(self, store: MetaStore, positive, negative, metric: Metric, strategy: RecommendStrategy = RecommendStrategy.BestScore):
-        self.store = store
+        super().__init__(store, RecommendPlan(store._store, positive, negative, metric, strategy))
         self.metric = Metric(metric)
-        self._meta_filter: Optional[CompiledFilter] = None
-        self.meta_error: Optional[str] = None
-        self._plan = RecommendPlan(store._store, positive, negative, metric, strategy)
-
-    def meta_filter(self, expr: Expr) -> "MetaRecommendPlan":
-        try:
-            self._meta_filter = expr.compile(self.store._schema)
-            self.meta_error = None
-        except ExprError as e:
-            self.meta_error = f"meta_filter compile error: {e}"
-        return self
-
-    def vec_filter(self, score: float, cmp: Cmp) -> "MetaRecommendPlan":
-        self._plan.filter(score, cmp)
-        return self
-
-    filter = vec_filter
-
-    def take(self, k: int) -> "MetaRecommendPlan":
-        self._plan.take(k)
-        return self
-
-    def take_min(self, k: int) -> "MetaRecommendPlan":
-        self._plan.take_min(k)
-        return self
-
-    def take_max(self, k: int) -> "MetaRecommendPlan":
-        self._plan.take_max(k)
-        return self
-
-    def with_row_mask(self, mask) -> "MetaRecommendPlan":
-        self._plan.with_row_mask(mask)
-        return self
-
-    def with_path(self, path: Path) -> "MetaRecommendPlan":
-        self._plan.with_path(path)
-        return self
 
     def fill_negative_side(self, fill: bool = True) -> "MetaRecommendPlan":
-        self._plan.fill_negative_side(fill)
-        return self
+        return self._forward("fill_negative_side", fill)
 
     def collect_arrays(self):
         """(hits, sides), as RecommendPlan.collect_arrays returns them."""
@@ -1211,99 +1248,38 @@ class MetaRecommendPlan:
         st = self.store
         if st._store is None:
             raise OttersError("recommend: the store holds no vectors, so no row can be an example")
-        rr = self._plan.resolve()
-        compiled = self._meta_filter
-        chunk_mask = st.build_chunk_mask_for_plan(compiled) if compiled is not None else None
-        if chunk_mask is not None and not chunk_mask.any():
-            return np.zeros(0, dtype=N.HIT_DTYPE), np.zeros(0, dtype=np.uint32)
-        with st._mask_lock:  # the device row mask is store-global state: built and read in one critical section (MetaQueryPlan.collect)
-            use_dev = False
-            if compiled is not None and not st.row_mask_is_all_true(compiled, chunk_mask):
-                if st._device_mask_ok(compiled):
-                    if rr.row_mask is not None:
-                        raise OttersError("recommend: with_row_mask cannot be combined with a meta_filter that needs a row mask of its own")
-                    st.build_row_mask_device(compiled)
-                    use_dev = True
-                else:
-                    host = st.build_row_mask_host(compiled)
-                    if rr.row_mask is not None:
-                        m = np.ones(host.size, bool)
-                        m[: min(rr.row_mask.size, host.size)] = rr.row_mask[: host.size]
-                        host &= m
-                    rr.row_mask = host
-            hits, sides, gstats = st._store._run_recommend(rr, chunk_mask=chunk_mask, use_device_row_mask=use_dev)
-        st._store.last_stats = gstats
-        return hits, sides
+        got = _run_filtered(st, self._meta_filter, self._plan.resolve(), "recommend", st._store._run_recommend)
+        return got if got is not None else (np.zeros(0, dtype=N.HIT_DTYPE), np.zeros(0, dtype=np.uint32))
 
     def collect(self):
         """(MetaQueryResults, sides): the hits' rows materialised as MetaQueryPlan.collect does, and their sides as a list."""
         hits, sides = self.collect_arrays()
-        st = self.store
-        indices = [int(i) for i in hits["index"]]
-        scores = [float(s) for s in hits["score"]]
-        names = sorted(st._schema)
-        data = {name: st._columns[name].take(indices) for name in names}
-        return MetaQueryResults(names, data, indices, scores), sides.tolist()
+        return _materialise(self.store, hits), sides.tolist()
 
 
-class MetaFusePlan:
+class MetaFusePlan(_MetaWrapper):
     """Rank fusion over a MetaStore (MetaStore.fuse; VecStore.fuse's contract): meta_filter prunes chunks by their zone maps and
     masks rows on the device, as for MetaRecommendPlan; it and vec_filter act on every leg before the fusion.  Errors surface at
     collect()."""
 
     def __init__(self, store: MetaStore, leg_sets, metric: Metric):
-        self.store = store
+        super().__init__(store, FusePlan(store._store, leg_sets, metric))
         self.metric = Metric(metric)
-        self._meta_filter: Optional[CompiledFilter] = None
-        self.meta_error: Optional[str] = None
-        self._plan = FusePlan(store._store, leg_sets, metric)
-
-    def _do(self, name, *args) -> "MetaFusePlan":
-        getattr(self._plan, name)(*args)
-        return self
-
-    def meta_filter(self, expr: Expr) -> "MetaFusePlan":
-        try:
-            self._meta_filter = expr.compile(self.store._schema)
-            self.meta_error = None
-        except ExprError as e:
-            self.meta_error = f"meta_filter compile error: {e}"
-        return self
-
-    def vec_filter(self, score: float, cmp: Cmp) -> "MetaFusePlan":
-        return self._do("filter", score, cmp)
-
-    filter = vec_filter
 
     def rrf(self, k: float = 60.0) -> "MetaFusePlan":
-        return self._do("rrf", k)
+        return self._forward("rrf", k)
 
     def dbsf(self) -> "MetaFusePlan":
-        return self._do("dbsf")
+        return self._forward("dbsf")
 
     def min_max(self) -> "MetaFusePlan":
-        return self._do("min_max")
+        return self._forward("min_max")
 
     def weights(self, list_of_lists) -> "MetaFusePlan":
-        return self._do("weights", list_of_lists)
+        return self._forward("weights", list_of_lists)
 
     def fetch(self, n: int) -> "MetaFusePlan":
-        return self._do("fetch", n)
-
-    def take(self, k: int) -> "MetaFusePlan":
-        return self._do("take", k)
-
-    def take_min(self, k: int) -> "MetaFusePlan":
-        return self._do("take_min", k)
-
-    def take_max(self, k: int) -> "MetaFusePlan":
-        return self._do("take_max", k)
-
-    def with_row_mask(self, mask) -> "MetaFusePlan":
-        return self._do("with_row_mask", mask)
-
-    def with_path(self, path: Path) -> "MetaFusePlan":
-        return self._do("with_path", path)
+        return self._forward("fetch", n)
 
     def validate(self) -> None:
         if self.meta_error is not None:
@@ -1317,84 +1293,20 @@ class MetaFusePlan:
         self.validate()
         st = self.store
         rf = self._plan.resolve()
-        compiled = self._meta_filter
-        chunk_mask = st.build_chunk_mask_for_plan(compiled) if compiled is not None else None
-        if chunk_mask is not None and not chunk_mask.any():
-            return np.zeros(0, dtype=N.HIT_DTYPE), [0] * int(rf.legs_per_request.size)
-        with st._mask_lock:  # the device row mask is store-global state: built and read in one critical section (MetaQueryPlan.collect)
-            use_dev = False
-            if compiled is not None and not st.row_mask_is_all_true(compiled, chunk_mask):
-                if st._device_mask_ok(compiled):
-                    if rf.row_mask is not None:
-                        raise OttersError("fuse: with_row_mask cannot be combined with a meta_filter that needs a row mask of its own")
-                    st.build_row_mask_device(compiled)
-                    use_dev = True
-                else:
-                    host = st.build_row_mask_host(compiled)
-                    if rf.row_mask is not None:
-                        m = np.ones(host.size, bool)
-                        m[: min(rf.row_mask.size, host.size)] = rf.row_mask[: host.size]
-                        host &= m
-                    rf.row_mask = host
-            hits, counts, gstats = st._store._run_fuse(rf, chunk_mask=chunk_mask, use_device_row_mask=use_dev)
-        st._store.last_stats = gstats
-        return hits, counts
+        got = _run_filtered(st, self._meta_filter, rf, "fuse", st._store._run_fuse)
+        return got if got is not None else (np.zeros(0, dtype=N.HIT_DTYPE), [0] * int(rf.legs_per_request.size))
 
     def collect(self):
         """One MetaQueryResults per request: the hits' rows materialised as MetaQueryPlan.collect does, scores = the fused scores."""
-        hits, counts = self.collect_arrays()
-        st = self.store
-        names = sorted(st._schema)
-        out, o = [], 0
-        for c in counts:
-            indices = [int(i) for i in hits["index"][o:o + c]]
-            scores = [float(s) for s in hits["score"][o:o + c]]
-            out.append(MetaQueryResults(names, {name: st._columns[name].take(indices) for name in names}, indices, scores))
-            o += c
-        return out
+        return _materialise(self.store, *self.collect_arrays())
 
 
-class MetaSparsePlan:
+class MetaSparsePlan(_MetaWrapper):
     """Sparse search over a MetaStore (MetaStore.sparse_query; VecStore.sparse_query's contract): meta_filter prunes chunks by their
     zone maps and masks rows on the device, exactly as the dense meta query does.  Errors surface at collect()."""
 
     def __init__(self, store: MetaStore, q):
-        self.store = store
-        self._meta_filter: Optional[CompiledFilter] = None
-        self.meta_error: Optional[str] = None
-        self._plan = SparseQueryPlan(store._store, q)
-
-    def _do(self, name, *args) -> "MetaSparsePlan":
-        getattr(self._plan, name)(*args)
-        return self
-
-    def meta_filter(self, expr: Expr) -> "MetaSparsePlan":
-        try:
-            self._meta_filter = expr.compile(self.store._schema)
-            self.meta_error = None
-        except ExprError as e:
-            self.meta_error = f"meta_filter compile error: {e}"
-        return self
-
-    def vec_filter(self, score: float, cmp: Cmp) -> "MetaSparsePlan":
-        return self._do("filter", score, cmp)
-
-    filter = vec_filter
-
-    def take(self, k: int) -> "MetaSparsePlan":
-        return self._do("take", k)
-
-    def take_min(self, k: int) -> "MetaSparsePlan":
-        return self._do("take_min", k)
-
-    def take_max(self, k: int) -> "MetaSparsePlan":
-        return self._do("take_max", k)
-
-    def with_row_mask(self, mask) -> "MetaSparsePlan":
-        return self._do("with_row_mask", mask)
-
-    def with_path(self, path: Path) -> "MetaSparsePlan":
-        return self._do("with_path", path)
+        super().__init__(store, SparseQueryPlan(store._store, q))
 
     def collect_arrays(self):
         """(hits, counts), as SparseQueryPlan.collect_arrays returns them."""
@@ -1405,42 +1317,12 @@ class MetaSparsePlan:
             raise OttersError("sparse_query: the store holds no vectors")
         self._plan.vector_store = st._store
         rs = self._plan.resolve()
-        nq = int(rs.indptr.size - 1)
-        compiled = self._meta_filter
-        chunk_mask = st.build_chunk_mask_for_plan(compiled) if compiled is not None else None
-        if chunk_mask is not None and not chunk_mask.any():
-            return np.zeros(0, dtype=N.HIT_DTYPE), [0] * nq
-        with st._mask_lock:  # the device row mask is store-global state: built and read in one critical section (MetaQueryPlan.collect)
-            use_dev = False
-            if compiled is not None and not st.row_mask_is_all_true(compiled, chunk_mask):
-                if st._device_mask_ok(compiled):
-                    if rs.row_mask is not None:
-                        raise OttersError("sparse_query: with_row_mask cannot be combined with a meta_filter that needs a row mask of its own")
-                    st.build_row_mask_device(compiled)
-                    use_dev = True
-                else:
-                    host = st.build_row_mask_host(compiled)
-                    if rs.row_mask is not None:
-                        m = np.ones(host.size, bool)
-                        m[: min(rs.row_mask.size, host.size)] = rs.row_mask[: host.size]
-                        host &= m
-                    rs.row_mask = host
-            hits, counts, gstats = st._store._run_sparse(rs, chunk_mask=chunk_mask, use_device_row_mask=use_dev)
-        st._store.last_stats = gstats
-        return hits, counts
+        got = _run_filtered(st, self._meta_filter, rs, "sparse_query", st._store._run_sparse)
+        return got if got is not None else (np.zeros(0, dtype=N.HIT_DTYPE), [0] * int(rs.indptr.size - 1))
 
     def collect_per_query(self):
         """One MetaQueryResults per query: the hits' rows materialised as MetaQueryPlan.collect does, scores = S."""
-        hits, counts = self.collect_arrays()
-        st = self.store
-        names = sorted(st._schema)
-        out, o = [], 0
-        for c in counts:
-            indices = [int(i) for i in hits["index"][o:o + c]]
-            scores = [float(x) for x in hits["score"][o:o + c]]
-            out.append(MetaQueryResults(names, {name: st._columns[name].take(indices) for name in names}, indices, scores))
-            o += c
-        return out
+        return _materialise(self.store, *self.collect_arrays())
 
     def collect(self):
         """The MetaQueryResults of ONE query; a batch needs collect_per_query()."""
@@ -1449,50 +1331,14 @@ class MetaSparsePlan:
         return self.collect_per_query()[0]
 
 
-class MetaDiscoverPlan:
+class MetaDiscoverPlan(_MetaWrapper):
     """Discovery and context search over a MetaStore (MetaStore.discover; VecStore.discover's contract): meta_filter prunes chunks
     by their zone maps and masks rows on the device, as for MetaRecommendPlan; vec_filter acts on the hit's score.  An example or
     the target row need not pass the filter: stored data is read.  Errors surface at collect()."""
 
     def __init__(self, store: MetaStore, context, target, target_row, metric: Metric):
-        self.store = store
+        super().__init__(store, DiscoverPlan(store._store, context, target, target_row, metric) if store._store is not None else None)
         self.metric = Metric(metric)
-        self._meta_filter: Optional[CompiledFilter] = None
-        self.meta_error: Optional[str] = None
-        self._plan = DiscoverPlan(store._store, context, target, target_row, metric) if store._store is not None else None
-
-    def _forward(self, name, *a) -> "MetaDiscoverPlan":
-        if self._plan is not None:
-            getattr(self._plan, name)(*a)
-        return self
-
-    def meta_filter(self, expr: Expr) -> "MetaDiscoverPlan":
-        try:
-            self._meta_filter = expr.compile(self.store._schema)
-            self.meta_error = None
-        except ExprError as e:
-            self.meta_error = f"meta_filter compile error: {e}"
-        return self
-
-    def vec_filter(self, score: float, cmp: Cmp) -> "MetaDiscoverPlan":
-        return self._forward("filter", score, cmp)
-
-    filter = vec_filter
-
-    def take(self, k: int) -> "MetaDiscoverPlan":
-        return self._forward("take", k)
-
-    def take_min(self, k: int) -> "MetaDiscoverPlan":
-        return self._forward("take_min", k)
-
-    def take_max(self, k: int) -> "MetaDiscoverPlan":
-        return self._forward("take_max", k)
-
-    def with_row_mask(self, mask) -> "MetaDiscoverPlan":
-        return self._forward("with_row_mask", mask)
-
-    def with_path(self, path: Path) -> "MetaDiscoverPlan":
-        return self._forward("with_path", path)
 
     def min_wins(self, n: int) -> "MetaDiscoverPlan":
         return self._forward("min_wins", n)
@@ -1504,36 +1350,10 @@ class MetaDiscoverPlan:
         st = self.store
         if st._store is None or self._plan is None:
             raise OttersError("discover: the store holds no vectors, so no row can be an example")
-        rd = self._plan.resolve()
-        compiled = self._meta_filter
-        chunk_mask = st.build_chunk_mask_for_plan(compiled) if compiled is not None else None
-        if chunk_mask is not None and not chunk_mask.any():
-            return np.zeros(0, dtype=N.HIT_DTYPE), np.zeros(0, dtype=np.uint32)
-        with st._mask_lock:  # the device row mask is store-global state: built and read in one critical section (MetaQueryPlan.collect)
-            use_dev = False
-            if compiled is not None and not st.row_mask_is_all_true(compiled, chunk_mask):
-                if st._device_mask_ok(compiled):
-                    if rd.row_mask is not None:
-                        raise OttersError("discover: with_row_mask cannot be combined with a meta_filter that needs a row mask of its own")
-                    st.build_row_mask_device(compiled)
-                    use_dev = True
-                else:
-                    host = st.build_row_mask_host(compiled)
-                    if rd.row_mask is not None:
-                        m = np.ones(host.size, bool)
-                        m[: min(rd.row_mask.size, host.size)] = rd.row_mask[: host.size]
-                        host &= m
-                    rd.row_mask = host
-            hits, wins, gstats = st._store._run_discover(rd, chunk_mask=chunk_mask, use_device_row_mask=use_dev)
-        st._store.last_stats = gstats
-        return hits, wins
+        got = _run_filtered(st, self._meta_filter, self._plan.resolve(), "discover", st._store._run_discover)
+        return got if got is not None else (np.zeros(0, dtype=N.HIT_DTYPE), np.zeros(0, dtype=np.uint32))
 
     def collect(self):
         """(MetaQueryResults, wins): the hits' rows materialised as MetaQueryPlan.collect does, and the pairs each hit wins as a list."""
         hits, wins = self.collect_arrays()
-        st = self.store
-        indices = [int(i) for i in hits["index"]]
-        scores = [float(s) for s in hits["score"]]
-        names = sorted(st._schema)
-        data = {name: st._columns[name].take(indices) for name in names}
-        return MetaQueryResults(names, data, indices, scores), wins.tolist()
+        return _materialise(self.store, hits), wins.tolist()

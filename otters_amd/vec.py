@@ -298,6 +298,74 @@ def infer_default_take_type(metric: Metric) -> TakeType:  # src/vec.rs:92-98
     return TakeType.Min if metric in (Metric.Euclidean, Metric.Manhattan) else TakeType.Max
 
 
+def split_results(hits, counts, index=None) -> list:
+    """Hits and per-query counts -> one list of SearchResult per query.  `index`: what a result reports in place of hits["index"]
+    (the caller's group labels)."""
+    # .tolist() first: building the objects from Python scalars is several times faster than indexing a record array
+    idx, sc = (hits["index"] if index is None else index).tolist(), hits["score"].tolist()
+    out, o = [], 0
+    for c in counts:
+        out.append([SearchResult(i, x) for i, x in zip(idx[o:o + c], sc[o:o + c])])
+        o += c
+    return out
+
+
+class _ScorePlan:
+    """What the extension plans share: the score filter, the take and the caller's row mask, and how they lower.  A plan sets
+    `search_metric`, which decides the take type of a take(n) that names none."""
+
+    def __init__(self):
+        self.filter_criteria: Optional[tuple] = None
+        self.take_type: Optional[TakeType] = None
+        self.take_count: Optional[int] = None
+        self.row_mask: Optional[np.ndarray] = None
+
+    def with_row_mask(self, mask):  # bit i = row i, True = keep
+        self.row_mask = np.asarray(mask, dtype=bool).ravel()
+        return self
+
+    def filter(self, score: float, cmp: Cmp):
+        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
+        return self
+
+    def _take_with_options(self, count: int, take_type: Optional[TakeType]):
+        self.take_count = int(count)
+        if take_type is not None:
+            self.take_type = take_type
+        elif self.take_type is None:
+            self.take_type = infer_default_take_type(self.search_metric)
+        return self
+
+    def take(self, count: int):
+        return self._take_with_options(count, None)
+
+    def take_min(self, count: int):
+        return self._take_with_options(count, TakeType.Min)
+
+    def take_max(self, count: int):
+        return self._take_with_options(count, TakeType.Max)
+
+    def _lowered(self, default_k: int, default_take: Optional[TakeType] = None):
+        """(take, k, filter_cmp, filter_thr) as a resolved record carries them; a plan without a take returns `default_k` hits,
+        ranked by `default_take` (default: what the metric infers)."""
+        k = self.take_count if self.take_count is not None else default_k
+        take = self.take_type if self.take_type is not None else default_take if default_take is not None else infer_default_take_type(self.search_metric)
+        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
+        return int(take), max(int(k), 0), fc, ft
+
+
+class _PathScorePlan(_ScorePlan):
+    """A _ScorePlan whose caller may name the path."""
+
+    def __init__(self):
+        super().__init__()
+        self.path = Path.Auto
+
+    def with_path(self, path: Path):
+        self.path = Path(path)
+        return self
+
+
 class VecQueryPlan:
     """src/vec.rs:55-312: lazy builder; errors surface at collect()."""
 
@@ -599,15 +667,9 @@ class VecQueryPlan:
             labels = self.vector_store.group_labels()
             idx = hits["index"].astype(np.int64)
             return [SearchResult(i, x) for i, x in zip((idx if labels is None else labels[idx]).tolist(), hits["score"].tolist())]
-        # .tolist() first: building the objects from Python scalars is several times faster than indexing a record array
-        idx, sc = hits["index"].tolist(), hits["score"].tolist()
         if self._mode == Mode.PerQuery:
-            out, o = [], 0
-            for c in counts:
-                out.append([SearchResult(i, x) for i, x in zip(idx[o:o + c], sc[o:o + c])])
-                o += c
-            return out
-        return [SearchResult(i, x) for i, x in zip(idx, sc)]
+            return split_results(hits, counts)
+        return split_results(hits, [int(hits.size)])[0]
 
     def collect_groups(self):
         """A per_group plan's hits by group: [(label, [SearchResult, ...]), ...] in the groups' rank order, each group's hits best
@@ -683,52 +745,24 @@ class ResolvedMaxSimBatch:
     row_mask: Optional[np.ndarray]
 
 
-class MaxSimBatchPlan:
+class MaxSimBatchPlan(_ScorePlan):
     """MaxSim re-ranking in batches (VecStore.max_sim_batch; ott_query_maxsim_groups_batch): B queries, each with its own tokens and
     its own list of groups, through one call.  Query b's result is exactly that of
     store.query(token_sets[b], metric).max_sim().with_groups(lists[b]) with the same take, filter and row mask.  Lazy like
     VecQueryPlan: errors surface at validate() / collect()."""
 
     def __init__(self, store: "VecStore", token_sets, metric: Metric):
+        super().__init__()
         self.vector_store = store
         self.token_sets = [QueryBatch(t).queries for t in token_sets]
         self.search_metric = Metric(metric)
         self.group_lists = None
-        self.filter_criteria: Optional[tuple] = None
-        self.take_type: Optional[TakeType] = None
-        self.take_count: Optional[int] = None
-        self.row_mask: Optional[np.ndarray] = None
 
     def with_groups(self, lists_of_labels) -> "MaxSimBatchPlan":
         """One list of group labels per token set, mapped as VecQueryPlan.with_groups maps them: any order, duplicates allowed, two
         queries may list the same group, an empty list is a query with no hits.  Required in this version."""
         self.group_lists = list(lists_of_labels)
         return self
-
-    def with_row_mask(self, mask) -> "MaxSimBatchPlan":
-        self.row_mask = np.asarray(mask, dtype=bool).ravel()
-        return self
-
-    def filter(self, score: float, cmp: Cmp) -> "MaxSimBatchPlan":
-        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
-        return self
-
-    def _take_with_options(self, count: int, take_type: Optional[TakeType]) -> "MaxSimBatchPlan":
-        self.take_count = int(count)
-        if take_type is not None:
-            self.take_type = take_type
-        elif self.take_type is None:
-            self.take_type = infer_default_take_type(self.search_metric)
-        return self
-
-    def take(self, count: int) -> "MaxSimBatchPlan":
-        return self._take_with_options(count, None)
-
-    def take_min(self, count: int) -> "MaxSimBatchPlan":
-        return self._take_with_options(count, TakeType.Min)
-
-    def take_max(self, count: int) -> "MaxSimBatchPlan":
-        return self._take_with_options(count, TakeType.Max)
 
     def validate(self) -> None:
         n = len(self.token_sets)
@@ -756,14 +790,12 @@ class MaxSimBatchPlan:
         sets = [t if isinstance(t, np.ndarray) else np.stack(t).astype(np.float32, copy=False) for t in self.token_sets]
         lists = [dense_listed_groups(self.vector_store, listed) for listed in self.group_lists]
         distinct = [int(np.unique(g).size) for g in lists]
-        k = self.take_count if self.take_count is not None else max(distinct)  # the default take: the largest number of distinct listed groups
-        take = self.take_type if self.take_type is not None else TakeType.Max
-        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
+        take, k, fc, ft = self._lowered(max(distinct), TakeType.Max)  # the default take: the largest number of distinct listed groups
         return ResolvedMaxSimBatch(queries=np.ascontiguousarray(np.concatenate(sets), dtype=np.float32),
                                    tokens_per_query=np.array([t.shape[0] for t in sets], dtype=np.uint32),
                                    listed_per_query=np.array([g.size for g in lists], dtype=np.uint64),
                                    groups=np.ascontiguousarray(np.concatenate(lists), dtype=np.uint32), distinct_per_query=distinct,
-                                   metric=int(self.search_metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask)
+                                   metric=int(self.search_metric), take=take, k=k, filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask)
 
     def collect_arrays(self):
         """(hits, counts): `hits` as VecQueryPlan.collect_arrays returns them for a max_sim plan — `index` the dense group id, `score`
@@ -779,12 +811,7 @@ class MaxSimBatchPlan:
         hits, counts = self.collect_arrays()
         labels = self.vector_store.group_labels()
         idx = hits["index"].astype(np.int64)
-        lab, sc = (idx if labels is None else labels[idx]).tolist(), hits["score"].tolist()
-        out, o = [], 0
-        for c in counts:
-            out.append([SearchResult(i, x) for i, x in zip(lab[o:o + c], sc[o:o + c])])
-            o += c
-        return out
+        return split_results(hits, counts, idx if labels is None else labels[idx])
 
 
 RECOMMEND_MAX_EXAMPLES = 64  # include/otters_hip.h: OTT_RECOMMEND_MAX_EXAMPLES
@@ -837,7 +864,7 @@ class ResolvedRecommend:
     strategy: int = 0  # RecommendStrategy; 0 lowers to ott_query_recommend, the others to ott_query_recommend_strategy with flags 0
 
 
-class RecommendPlan:
+class RecommendPlan(_PathScorePlan):
     """Recommend by example rows (VecStore.recommend; ott_query_recommend, Qdrant's recommend with the best_score strategy): rank the
     rows by their best score against the `positive` rows of the store; a row at least as close to a `negative` row as to its best
     positive leaves the positive side and follows it — least like its nearest negative first — unless fill_negative_side(False).
@@ -847,47 +874,17 @@ class RecommendPlan:
     only: fill_negative_side() does not reach them.  Lazy like VecQueryPlan: errors surface at validate() / collect()."""
 
     def __init__(self, store: "VecStore", positive, negative, metric: Metric, strategy: RecommendStrategy = RecommendStrategy.BestScore):
+        super().__init__()
         self.vector_store = store
         self.positive, self.negative = positive, negative
         self.search_metric = Metric(metric)
         self.strategy = RecommendStrategy(strategy)
-        self.filter_criteria: Optional[tuple] = None
-        self.take_type: Optional[TakeType] = None
-        self.take_count: Optional[int] = None
-        self.row_mask: Optional[np.ndarray] = None
-        self.path = Path.Auto
         self.fill = True
-
-    def with_row_mask(self, mask) -> "RecommendPlan":
-        self.row_mask = np.asarray(mask, dtype=bool).ravel()
-        return self
 
     def filter(self, score: float, cmp: Cmp) -> "RecommendPlan":
         """The score filter acts on the hit's score: with BestScore on a row's best POSITIVE score BP, on both sides; with SumScores
         on the sum S; with AverageVector on the query's score, as VecQueryPlan.filter does."""
-        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
-        return self
-
-    def _take_with_options(self, count: int, take_type: Optional[TakeType]) -> "RecommendPlan":
-        self.take_count = int(count)
-        if take_type is not None:
-            self.take_type = take_type
-        elif self.take_type is None:
-            self.take_type = infer_default_take_type(self.search_metric)
-        return self
-
-    def take(self, count: int) -> "RecommendPlan":
-        return self._take_with_options(count, None)
-
-    def take_min(self, count: int) -> "RecommendPlan":
-        return self._take_with_options(count, TakeType.Min)
-
-    def take_max(self, count: int) -> "RecommendPlan":
-        return self._take_with_options(count, TakeType.Max)
-
-    def with_path(self, path: Path) -> "RecommendPlan":
-        self.path = Path(path)
-        return self
+        return super().filter(score, cmp)
 
     def fill_negative_side(self, fill: bool = True) -> "RecommendPlan":
         """True (default): when the positive side has fewer than take(k) rows, the negative-side rows follow it.  False: they never
@@ -915,10 +912,8 @@ class RecommendPlan:
         """Validate and lower the plan.  Pure host logic, no GPU."""
         self.validate()
         pos, neg = recommend_examples(self.positive, self.negative, len(self.vector_store), self._who())
-        k = self.take_count if self.take_count is not None else len(self.vector_store)
-        take = self.take_type if self.take_type is not None else infer_default_take_type(self.search_metric)
-        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
-        return ResolvedRecommend(positive=pos, negative=neg, metric=int(self.search_metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft,
+        take, k, fc, ft = self._lowered(len(self.vector_store))
+        return ResolvedRecommend(positive=pos, negative=neg, metric=int(self.search_metric), take=take, k=k, filter_cmp=fc, filter_thr=ft,
                                  row_mask=self.row_mask, path=int(self.path),
                                  flags=(RECOMMEND_FILL if self.fill else 0) if self.strategy == RecommendStrategy.BestScore else 0, strategy=int(self.strategy))
 
@@ -987,7 +982,7 @@ class DiscoverResult:
     wins: int
 
 
-class DiscoverPlan:
+class DiscoverPlan(_PathScorePlan):
     """Discovery and context search (VecStore.discover; ott_query_discover, Qdrant's Discovery API).  `context` is a sequence of
     (positive, negative) row id pairs; a row WINS a pair when it is closer to the pair's positive than to its negative.  With a
     target — a vector (`target`) or a stored row (`target_row`) — the rows are ranked by the pairs they win, then by their score
@@ -995,47 +990,17 @@ class DiscoverPlan:
     pair.  Lazy like VecQueryPlan: errors surface at validate() / collect()."""
 
     def __init__(self, store: "VecStore", context, target, target_row, metric: Metric):
+        super().__init__()
         self.vector_store = store
         self.context = list(context)
         self.target = target
         self.target_row = target_row
         self.search_metric = Metric(metric)
-        self.filter_criteria: Optional[tuple] = None
-        self.take_type: Optional[TakeType] = None
-        self.take_count: Optional[int] = None
-        self.row_mask: Optional[np.ndarray] = None
-        self.path = Path.Auto
         self.min_wins_count = 0
-
-    def with_row_mask(self, mask) -> "DiscoverPlan":
-        self.row_mask = np.asarray(mask, dtype=bool).ravel()
-        return self
 
     def filter(self, score: float, cmp: Cmp) -> "DiscoverPlan":
         """The score filter acts on the hit's score: the target score with a target, the loss without one."""
-        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
-        return self
-
-    def _take_with_options(self, count: int, take_type: Optional[TakeType]) -> "DiscoverPlan":
-        self.take_count = int(count)
-        if take_type is not None:
-            self.take_type = take_type
-        elif self.take_type is None:
-            self.take_type = infer_default_take_type(self.search_metric)
-        return self
-
-    def take(self, count: int) -> "DiscoverPlan":
-        return self._take_with_options(count, None)
-
-    def take_min(self, count: int) -> "DiscoverPlan":
-        return self._take_with_options(count, TakeType.Min)
-
-    def take_max(self, count: int) -> "DiscoverPlan":
-        return self._take_with_options(count, TakeType.Max)
-
-    def with_path(self, path: Path) -> "DiscoverPlan":
-        self.path = Path(path)
-        return self
+        return super().filter(score, cmp)
 
     def min_wins(self, n: int) -> "DiscoverPlan":
         """Only rows that win at least `n` of the pairs come out (n = the number of pairs: only rows inside the fenced region)."""
@@ -1072,11 +1037,9 @@ class DiscoverPlan:
         if st.devices is not None:
             raise OttersError("ott_query_discover: a multi-GPU store is not served (the examples' rows lie on different shards)")
         pos, neg = discover_context(pairs, trow, len(st))
-        k = self.take_count if self.take_count is not None else len(st)
-        take = self.take_type if self.take_type is not None else infer_default_take_type(self.search_metric)
-        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
+        take, k, fc, ft = self._lowered(len(st))
         return ResolvedDiscover(positive=pos, negative=neg, target=tv, target_row=NO_ROW if trow is None else trow, min_wins=self.min_wins_count,
-                                metric=int(self.search_metric), take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask,
+                                metric=int(self.search_metric), take=take, k=k, filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask,
                                 path=int(self.path))
 
     def validate(self) -> None:
@@ -1154,7 +1117,7 @@ class ResolvedFuse:
     path: int
 
 
-class FusePlan:
+class FusePlan(_PathScorePlan):
     """Rank fusion (VecStore.fuse; ott_query_fuse): every request brings several query vectors ("legs"); each leg's best `fetch` hits
     — exactly what store.query(leg, metric).per_query().take(fetch) returns under the same filter, masks and path — are merged into
     one ranking per request by reciprocal rank fusion (.rrf(k), the default), distribution-based score fusion (.dbsf()) or min-max
@@ -1163,6 +1126,7 @@ class FusePlan:
     VecQueryPlan: errors surface at validate() / collect()."""
 
     def __init__(self, store: "VecStore", leg_sets, metric: Metric):
+        super().__init__()
         self.vector_store = store
         self.leg_sets = [QueryBatch(t).queries for t in leg_sets]
         self.search_metric = Metric(metric)
@@ -1170,11 +1134,6 @@ class FusePlan:
         self.rrf_k = 60.0
         self.leg_weights = None
         self.fetch_count: Optional[int] = None
-        self.filter_criteria: Optional[tuple] = None
-        self.take_type: Optional[TakeType] = None
-        self.take_count: Optional[int] = None
-        self.row_mask: Optional[np.ndarray] = None
-        self.path = Path.Auto
 
     def rrf(self, k: float = 60.0) -> "FusePlan":
         """Reciprocal rank fusion: the entry at position r (0 based) of a leg with weight w contributes w / (k + (r + 1))."""
@@ -1201,35 +1160,9 @@ class FusePlan:
         self.fetch_count = int(n)
         return self
 
-    def with_row_mask(self, mask) -> "FusePlan":
-        self.row_mask = np.asarray(mask, dtype=bool).ravel()
-        return self
-
     def filter(self, score: float, cmp: Cmp) -> "FusePlan":
         """The score filter acts on a leg's own score: it is part of the leg, as VecQueryPlan.filter."""
-        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
-        return self
-
-    def _take_with_options(self, count: int, take_type: Optional[TakeType]) -> "FusePlan":
-        self.take_count = int(count)
-        if take_type is not None:
-            self.take_type = take_type
-        elif self.take_type is None:
-            self.take_type = infer_default_take_type(self.search_metric)
-        return self
-
-    def take(self, count: int) -> "FusePlan":
-        return self._take_with_options(count, None)
-
-    def take_min(self, count: int) -> "FusePlan":
-        return self._take_with_options(count, TakeType.Min)
-
-    def take_max(self, count: int) -> "FusePlan":
-        return self._take_with_options(count, TakeType.Max)
-
-    def with_path(self, path: Path) -> "FusePlan":
-        self.path = Path(path)
-        return self
+        return super().filter(score, cmp)
 
     def _k(self) -> int:
         return max(int(self.take_count), 0) if self.take_count is not None else max(len(self.vector_store), 1)
@@ -1262,12 +1195,11 @@ class FusePlan:
         self.validate()
         sets = [t if isinstance(t, np.ndarray) else np.stack(t).astype(np.float32, copy=False) for t in self.leg_sets]
         w = self._flat_weights()
-        take = self.take_type if self.take_type is not None else infer_default_take_type(self.search_metric)
-        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
+        take, k, fc, ft = self._lowered(max(len(self.vector_store), 1))  # (k: what _k() says)
         return ResolvedFuse(queries=np.ascontiguousarray(np.concatenate(sets), dtype=np.float32),
                             legs_per_request=np.array([t.shape[0] for t in sets], dtype=np.uint32), fusion=int(self.fusion), rrf_k=float(self.rrf_k),
                             weights=None if w is None else np.array(w, dtype=np.float32), fetch=self._fetch(), metric=int(self.search_metric),
-                            take=int(take), k=self._k(), filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, path=int(self.path))
+                            take=take, k=k, filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, path=int(self.path))
 
     def collect_arrays(self):
         """(hits, counts): `hits` a NumPy record array (`index` u64, `score` f32 = the fused score F, `query` = the request), every
@@ -1279,13 +1211,7 @@ class FusePlan:
 
     def collect(self):
         """One list of SearchResult(index, fused score) per request."""
-        hits, counts = self.collect_arrays()
-        idx, sc = hits["index"].tolist(), hits["score"].tolist()
-        out, o = [], 0
-        for c in counts:
-            out.append([SearchResult(i, x) for i, x in zip(idx[o:o + c], sc[o:o + c])])
-            o += c
-        return out
+        return split_results(*self.collect_arrays())
 
 
 SPARSE_MAX_VOCAB = 1 << 20      # include/otters_hip.h: OTT_SPARSE_MAX_VOCAB
@@ -1322,61 +1248,28 @@ class ResolvedSparse:
     filter_thr: float
     row_mask: Optional[np.ndarray]
     path: int
+    metric: int = int(Metric.DotProduct)  # a sparse score is a dot product
 
 
-class SparseQueryPlan:
+class SparseQueryPlan(_PathScorePlan):
     """Exact sparse dot search over the store's sparse rows (VecStore.sparse_query; ott_query_sparse): a row is a hit iff it shares
     an index with the query; its score adds value x weight over the shared indices in the row's index order, one rounded f32
     operation at a time.  Lazy like VecQueryPlan: errors surface at collect()."""
 
     def __init__(self, store: "VecStore", q):
+        super().__init__()
         self.vector_store = store
+        self.search_metric = Metric.DotProduct  # a sparse score is a dot product: it decides the default take
         single = isinstance(q, tuple) and len(q) == 2 and not (len(q[0]) and isinstance(q[0][0], (tuple, list, np.ndarray)))
         self.queries = [q] if single else list(q)
-        self.filter_criteria: Optional[tuple] = None
-        self.take_type: Optional[TakeType] = None
-        self.take_count: Optional[int] = None
-        self.row_mask: Optional[np.ndarray] = None
-        self.path = Path.Auto
-
-    def with_row_mask(self, mask) -> "SparseQueryPlan":
-        self.row_mask = np.asarray(mask, dtype=bool).ravel()
-        return self
-
-    def filter(self, score: float, cmp: Cmp) -> "SparseQueryPlan":
-        self.filter_criteria = (float(np.float32(score)), Cmp(cmp))
-        return self
-
-    def _take_with_options(self, count: int, take_type: Optional[TakeType]) -> "SparseQueryPlan":
-        self.take_count = int(count)
-        if take_type is not None:
-            self.take_type = take_type
-        elif self.take_type is None:
-            self.take_type = infer_default_take_type(Metric.DotProduct)
-        return self
-
-    def take(self, count: int) -> "SparseQueryPlan":
-        return self._take_with_options(count, None)
-
-    def take_min(self, count: int) -> "SparseQueryPlan":
-        return self._take_with_options(count, TakeType.Min)
-
-    def take_max(self, count: int) -> "SparseQueryPlan":
-        return self._take_with_options(count, TakeType.Max)
-
-    def with_path(self, path: Path) -> "SparseQueryPlan":
-        self.path = Path(path)
-        return self
 
     def resolve(self) -> ResolvedSparse:
         """Lower the plan.  Pure host logic, no GPU; the library checks the queries against the store's vocab."""
         if not self.queries:
             raise OttersError("No queries provided")
         ptr, idx, val = sparse_csr(self.queries)
-        k = self.take_count if self.take_count is not None else len(self.vector_store)
-        take = self.take_type if self.take_type is not None else infer_default_take_type(Metric.DotProduct)
-        fc, ft = (0, 0.0) if self.filter_criteria is None else (int(self.filter_criteria[1]), self.filter_criteria[0])
-        return ResolvedSparse(indptr=ptr, indices=idx, values=val, take=int(take), k=max(int(k), 0), filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask,
+        take, k, fc, ft = self._lowered(len(self.vector_store))
+        return ResolvedSparse(indptr=ptr, indices=idx, values=val, take=take, k=k, filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask,
                               path=int(self.path))
 
     def collect_arrays(self):
@@ -1389,19 +1282,38 @@ class SparseQueryPlan:
 
     def collect_per_query(self):
         """One list of SearchResult(index, score) per query."""
-        hits, counts = self.collect_arrays()
-        idx, sc = hits["index"].tolist(), hits["score"].tolist()
-        out, o = [], 0
-        for c in counts:
-            out.append([SearchResult(i, x) for i, x in zip(idx[o:o + c], sc[o:o + c])])
-            o += c
-        return out
+        return split_results(*self.collect_arrays())
 
     def collect(self):
         """The hits of ONE query as a list of SearchResult(index, score); a batch needs collect_per_query()."""
         if len(self.queries) != 1:
             raise OttersError("ott_query_sparse: a batch needs OTT_MODE_PER_QUERY (a merged list over several sparse queries is not served)")
         return self.collect_per_query()[0]
+
+
+def query_desc(r, queries: Optional[np.ndarray], nq: int, mode: int, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
+    """The ott_query_desc of a resolved record: `r` supplies metric, take, filter_cmp, filter_thr, k, row_mask and, where it has
+    one, path (else Path.Auto); `queries` is the query matrix or None.  Returns (desc, keep): the descriptor holds bare addresses
+    into the arrays of `keep`, which the caller keeps referenced until the native call has returned.  The evaluated device row
+    mask takes precedence over the record's; a row mask of size 0 is not sent."""
+    d = N.QueryDesc()
+    keep = [queries]
+    d.queries = None if queries is None else queries.ctypes.data
+    d.nq = nq
+    d.metric, d.take, d.filter_cmp, d.filter_thr = r.metric, r.take, r.filter_cmp, r.filter_thr
+    d.mode, d.k, d.path = int(mode), r.k, getattr(r, "path", int(Path.Auto))
+    if chunk_mask is not None:
+        cm = N.pack_bits(chunk_mask)
+        keep.append(cm)
+        d.chunk_mask = cm.ctypes.data
+    if use_device_row_mask:
+        d.use_device_row_mask = 1
+    elif r.row_mask is not None and r.row_mask.size:
+        rm = N.pack_bits(r.row_mask)
+        keep.append(rm)
+        d.row_mask = rm.ctypes.data
+        d.row_mask_bits = int(r.row_mask.size)
+    return d, keep
 
 
 class VecStore:
@@ -1692,26 +1604,8 @@ class VecStore:
         nq = int(rs.indptr.size - 1)
         cap = max(nq * min(rs.k, self._n), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)
-        d = N.QueryDesc()
-        d.queries = None
-        d.nq = nq
-        d.metric, d.take, d.filter_cmp, d.filter_thr = int(Metric.DotProduct), rs.take, rs.filter_cmp, rs.filter_thr
-        d.mode, d.k, d.path = int(Mode.PerQuery if nq > 1 else Mode.Merged), rs.k, rs.path
-        keep = []
-        if chunk_mask is not None:
-            cm = N.pack_bits(chunk_mask)
-            keep.append(cm)
-            d.chunk_mask = cm.ctypes.data
-        if use_device_row_mask:
-            d.use_device_row_mask = 1
-        elif rs.row_mask is not None and rs.row_mask.size:
-            rm = N.pack_bits(rs.row_mask)
-            keep.append(rm)
-            d.row_mask = rm.ctypes.data
-            d.row_mask_bits = int(rs.row_mask.size)
-        n_out = C.c_uint64(0)
-        per = (C.c_uint64 * max(nq, 1))()
-        st = N.Stats()
+        d, keep = query_desc(rs, None, nq, Mode.PerQuery if nq > 1 else Mode.Merged, chunk_mask, use_device_row_mask)
+        n_out, per, st = C.c_uint64(0), (C.c_uint64 * max(nq, 1))(), N.Stats()
         N.check(N.lib().ott_query_sparse(self._handle(), C.byref(d), N.ptr(rs.indptr), N.ptr(rs.indices) if rs.indices.size else None,
                                          N.ptr(rs.values) if rs.values.size else None, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         return out[: n_out.value].copy(), list(per)[:nq], st.as_dict()
@@ -1829,26 +1723,8 @@ class VecStore:
         if rq.group_list is not None:  # ... and per listed group
             cap = max(min(rq.k, int(np.unique(rq.group_list).size)), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)  # ott_query writes n_out entries; only those are returned
-        d = N.QueryDesc()
-        d.queries = rq.queries.ctypes.data
-        d.nq = nq
-        d.metric, d.take, d.filter_cmp, d.filter_thr = rq.metric, rq.take, rq.filter_cmp, rq.filter_thr
-        d.mode, d.k, d.path = rq.mode, rq.k, rq.path
-        keep = []
-        if chunk_mask is not None:
-            cm = N.pack_bits(chunk_mask)
-            keep.append(cm)
-            d.chunk_mask = cm.ctypes.data
-        if use_device_row_mask:
-            d.use_device_row_mask = 1
-        elif rq.row_mask is not None and rq.row_mask.size:
-            rm = N.pack_bits(rq.row_mask)
-            keep.append(rm)
-            d.row_mask = rm.ctypes.data
-            d.row_mask_bits = int(rq.row_mask.size)
-        n_out = C.c_uint64(0)
-        per = (C.c_uint64 * nq)()
-        st = N.Stats()
+        d, keep = query_desc(rq, rq.queries, nq, rq.mode, chunk_mask, use_device_row_mask)
+        n_out, per, st = C.c_uint64(0), (C.c_uint64 * nq)(), N.Stats()
         if rq.group_list is not None:
             gl = rq.group_list
             N.check(N.lib().ott_query_maxsim_groups(self._handle(), C.byref(d), N.ptr(gl) if gl.size else None, gl.size, N.ptr(out), cap, C.byref(n_out), C.byref(st)))
@@ -1898,26 +1774,8 @@ class VecStore:
         B = int(rb.tokens_per_query.size)
         cap = max(sum(min(rb.k, n) for n in rb.distinct_per_query), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)
-        d = N.QueryDesc()
-        d.queries = rb.queries.ctypes.data
-        d.nq = int(rb.queries.shape[0])
-        d.metric, d.take, d.filter_cmp, d.filter_thr = rb.metric, rb.take, rb.filter_cmp, rb.filter_thr
-        d.mode, d.k, d.path = int(Mode.Merged), rb.k, int(Path.Auto)
-        keep = []
-        if chunk_mask is not None:
-            cm = N.pack_bits(chunk_mask)
-            keep.append(cm)
-            d.chunk_mask = cm.ctypes.data
-        if use_device_row_mask:
-            d.use_device_row_mask = 1
-        elif rb.row_mask is not None and rb.row_mask.size:
-            rm = N.pack_bits(rb.row_mask)
-            keep.append(rm)
-            d.row_mask = rm.ctypes.data
-            d.row_mask_bits = int(rb.row_mask.size)
-        n_out = C.c_uint64(0)
-        per = (C.c_uint64 * B)()
-        st = N.Stats()
+        d, keep = query_desc(rb, rb.queries, int(rb.queries.shape[0]), Mode.Merged, chunk_mask, use_device_row_mask)  # (the record has no path: always Path.Auto)
+        n_out, per, st = C.c_uint64(0), (C.c_uint64 * B)(), N.Stats()
         N.check(N.lib().ott_query_maxsim_groups_batch(self._handle(), C.byref(d), N.ptr(rb.tokens_per_query), N.ptr(rb.listed_per_query), B,
                                                       N.ptr(rb.groups) if rb.groups.size else None, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         hits = out if n_out.value == cap else out[: n_out.value].copy()
@@ -1937,25 +1795,8 @@ class VecStore:
         cap = max(min(rr.k, self._n), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)
         sides = np.empty(cap, dtype=np.uint32)
-        d = N.QueryDesc()
-        d.queries = None
-        d.nq = 0
-        d.metric, d.take, d.filter_cmp, d.filter_thr = rr.metric, rr.take, rr.filter_cmp, rr.filter_thr
-        d.mode, d.k, d.path = int(Mode.Merged), rr.k, rr.path
-        keep = []
-        if chunk_mask is not None:
-            cm = N.pack_bits(chunk_mask)
-            keep.append(cm)
-            d.chunk_mask = cm.ctypes.data
-        if use_device_row_mask:
-            d.use_device_row_mask = 1
-        elif rr.row_mask is not None and rr.row_mask.size:
-            rm = N.pack_bits(rr.row_mask)
-            keep.append(rm)
-            d.row_mask = rm.ctypes.data
-            d.row_mask_bits = int(rr.row_mask.size)
-        n_out = C.c_uint64(0)
-        st = N.Stats()
+        d, keep = query_desc(rr, None, 0, Mode.Merged, chunk_mask, use_device_row_mask)
+        n_out, st = C.c_uint64(0), N.Stats()
         neg = N.ptr(rr.negative) if rr.negative.size else None
         if rr.strategy == int(RecommendStrategy.BestScore):
             N.check(N.lib().ott_query_recommend(self._handle(), C.byref(d), N.ptr(rr.positive), rr.positive.size, neg, rr.negative.size, rr.flags, N.ptr(out), cap,
@@ -1978,26 +1819,8 @@ class VecStore:
         stride = min(rf.fetch, self._n)
         cap = max(sum(min(rf.k, int(l) * stride) for l in rf.legs_per_request), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)
-        d = N.QueryDesc()
-        d.queries = rf.queries.ctypes.data
-        d.nq = int(rf.queries.shape[0])
-        d.metric, d.take, d.filter_cmp, d.filter_thr = rf.metric, rf.take, rf.filter_cmp, rf.filter_thr
-        d.mode, d.k, d.path = int(Mode.PerQuery), rf.k, rf.path
-        keep = []
-        if chunk_mask is not None:
-            cm = N.pack_bits(chunk_mask)
-            keep.append(cm)
-            d.chunk_mask = cm.ctypes.data
-        if use_device_row_mask:
-            d.use_device_row_mask = 1
-        elif rf.row_mask is not None and rf.row_mask.size:
-            rm = N.pack_bits(rf.row_mask)
-            keep.append(rm)
-            d.row_mask = rm.ctypes.data
-            d.row_mask_bits = int(rf.row_mask.size)
-        n_out = C.c_uint64(0)
-        per = (C.c_uint64 * B)()
-        st = N.Stats()
+        d, keep = query_desc(rf, rf.queries, int(rf.queries.shape[0]), Mode.PerQuery, chunk_mask, use_device_row_mask)
+        n_out, per, st = C.c_uint64(0), (C.c_uint64 * B)(), N.Stats()
         N.check(N.lib().ott_query_fuse(self._handle(), C.byref(d), N.ptr(rf.legs_per_request), B, rf.fusion, rf.rrf_k,
                                        N.ptr(rf.weights) if rf.weights is not None else None, rf.fetch, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         return out[: n_out.value].copy(), list(per), st.as_dict()
@@ -2013,30 +1836,9 @@ class VecStore:
         cap = max(min(rd.k, self._n), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)
         wins = np.empty(cap, dtype=np.uint32)
-        d = N.QueryDesc()
-        keep = []
-        if rd.target is not None:
-            keep.append(rd.target)
-            d.queries = rd.target.ctypes.data
-            d.nq = 1
-        else:
-            d.queries = None
-            d.nq = 0
-        d.metric, d.take, d.filter_cmp, d.filter_thr = rd.metric, rd.take, rd.filter_cmp, rd.filter_thr
-        d.mode, d.k, d.path = int(Mode.Merged), rd.k, rd.path
-        if chunk_mask is not None:
-            cm = N.pack_bits(chunk_mask)
-            keep.append(cm)
-            d.chunk_mask = cm.ctypes.data
-        if use_device_row_mask:
-            d.use_device_row_mask = 1
-        elif rd.row_mask is not None and rd.row_mask.size:
-            rm = N.pack_bits(rd.row_mask)
-            keep.append(rm)
-            d.row_mask = rm.ctypes.data
-            d.row_mask_bits = int(rd.row_mask.size)
-        n_out = C.c_uint64(0)
-        st = N.Stats()
+        # the target vector, when there is one, is the call's one query
+        d, keep = query_desc(rd, rd.target, 0 if rd.target is None else 1, Mode.Merged, chunk_mask, use_device_row_mask)
+        n_out, st = C.c_uint64(0), N.Stats()
         N.check(N.lib().ott_query_discover(self._handle(), C.byref(d), rd.target_row, N.ptr(rd.positive), N.ptr(rd.negative), rd.positive.size, rd.min_wins, 0,
                                            N.ptr(out), cap, C.byref(n_out), N.ptr(wins), C.byref(st)))
         return out[: n_out.value].copy(), wins[: n_out.value].copy(), st.as_dict()
