@@ -271,10 +271,15 @@ int ott_store_prepare_batch(ott_store* s);
  * 1 always) the plane is built or extended in the background right after every append, so a host that loads and then queries
  * normally finds it ready without calling ott_store_prepare_batch. */
 int ott_store_batch_ready(const ott_store* s);
+/* Rows that the pruned exact sweeps of this store (option "exact_prune") have finished in f32 after their checkpoint so far, a
+ * running total over all queries and query contexts with host output (a multi-GPU store: over its shards).  Without the int8
+ * check of the survivors (option "exact_i8_check") a query adds what it adds to ott_stats.rescored; with it, the rows that the
+ * int8 plane could not rule out, a small part of that.  A measurement aid: results never depend on it. */
+uint64_t ott_store_exact_finished(const ott_store* s);
 
 /* Behaviour switches of one store.  The library reads the environment exactly once per store, in ott_store_create
  * (OTT_<NAME>=<int> presets the option of the same name); after that only this call changes them — the query path never calls
- * getenv.  Twenty-four options (round 5 retired the rest: experiment switches whose measurements are in DESIGN.md 3.4 and profiles/dead_ends_rounds_2_4.md).
+ * getenv.  Twenty-six options (round 5 retired the rest: experiment switches whose measurements are in DESIGN.md 3.4 and profiles/dead_ends_rounds_2_4.md).
  * Behaviour a host may want:
  *   "tie_order"  0 (default): canonical total order — better score, lower row, lower query.  1: the reference's own outcome at
  *                exact score ties, ONE TopKCollector over the store (VecStore, src/vec.rs:217-310, src/vec_compute.rs:236-277).
@@ -311,6 +316,11 @@ int ott_store_batch_ready(const ott_store* s);
  *   first 32 dims again, whether the store still holds a head or not.  The head itself is dropped, or made for every row, at the
  *   next append after a switch, so switched back on the option shows from that append.  Lists of k > 256 always take the sweep
  *   without a head: the head kernel's registers leave one wave per SIMD there, and it measured slower),
+ *   "exact_i8_check" (-1, the default, and 1: in the sweep without f32 dims in front, k <= 64, a row whose four-bit bound reaches the
+ *   gate is first scored on the cascade's int8 plane — a quarter of its bytes — and its f32 dims are read only unless that score plus
+ *   the int8 level's certified error still ranks below the gate; 0 = never.  Only while that plane exists and covers every row
+ *   (ott_store_batch_ready on a store whose first plane is the int8 one): asking builds nothing.  Hits and ott_stats.rescored are
+ *   the same either way; ott_store_exact_finished counts the rows whose f32 dims were read),
  *   "id_gather" (-1 auto: lists of up to 10000 ids / 0 never / 1 wherever eligible: whether ott_query_ids scores the listed rows with the gather kernel or
  *   turns the list into a row mask and takes ott_query's paths),
  *   "group_gather" (-1 auto: lists whose groups hold up to 1000000 rows / 0 never / 1 wherever eligible: whether ott_query_maxsim_groups

@@ -7,6 +7,7 @@
 
 #include "ott_internal.h"
 #include "ott_prune.h"
+#include "ott_i8_check.h"
 
 using namespace ott;
 
@@ -212,6 +213,23 @@ struct ExactCtx {
     PruneQuant qq{0, 0.0f, 0.0f, 0.0, 0};  // four bits per dim: the quantised query (ott_prune.h)
     bool head = false;                     // ... in the head form: no f32 stage in front, the query-side values over the whole query
     bool seed_est = false;                 // the seed is an estimate pass over plA; plB is then the WHOLE plan and the final merge takes its lists alone
+    // the int8 check of the gated launch's survivors (ott_exact_plan.h: prune_plan_i8_check): the plane and its scales as they were
+    // when the call was planned, the query's scale and the certified error
+    bool i8_check = false;
+    const int8_t* chk_plane = nullptr;
+    const float* chk_scale = nullptr;
+    float chk_qscale = 0.0f, chk_eps = 0.0f;
+    // the query's reference-order inverse norm (one dependent float chain over the dims): taken once, by whoever asks first — the
+    // check's plan or the embedded call
+    bool have_q_inv = false;
+    float q_inv = 0.0f;
+    float query_inv_norm() {
+        if (!have_q_inv) {
+            q_inv = host_inv_norm_exact(queries, s->dim);
+            have_q_inv = true;
+        }
+        return q_inv;
+    }
     // the result block, as the merge kernel sees it
     ExactResult res{0, 0, 0};
     uint64_t* d_counts = nullptr;
@@ -254,6 +272,20 @@ void plan_pruned_sweep(ExactCtx& c) {
     c.preB = tile_prefix(c.plB, 64);
     c.gridA = exact_grid(s, c.preA.back());
     c.gridB = exact_grid(s, c.preB.back());
+    // (the int8 check: asked only where everything else allows it — the plane is looked at under its lock, never built; the query is
+    // quantised as run_i8_single quantises it, and the kernel makes the same operand from the scale)
+    if (head && c.x.E == 1 && s->opt.exact_i8_check != 0) {
+        I8CheckState ck{false, s->opt.exact_i8_check, false};
+        float rel = 0.0f;
+        if ((ck.plane_ready = i8_plane_peek(s, &c.chk_plane, &c.chk_scale, &rel))) {
+            const I8Query iq = i8_query_quant(c.queries, s->dim, c.d->metric == OTT_METRIC_COSINE, c.query_inv_norm(), nullptr);
+            const I8CheckEps e = i8_check_eps(s->dim, c.d->metric, s->opt.eps_scale_ppm, rel, iq, max_norm(s->min_pos_inv));
+            ck.eps_ok = e.ok;
+            c.chk_qscale = iq.s_q;
+            c.chk_eps = e.eps;
+        }
+        c.i8_check = prune_plan_i8_check(in, pp, head, ck);
+    }
 }
 
 // the inputs on the device (unless they ride in the arguments), room for the block lists, and the result block
@@ -268,7 +300,7 @@ int ensure_exact_result(ExactCtx& c) {
     c.res = exact_result_layout(c.groups, c.x.KS);
     char* res_dev = nullptr;
     if (c.fetch) {
-        if ((rc = s->h_hits.ensure(c.res.host_bytes))) return rc;  // (+ 8: the pruned sweep's tail counter)
+        if ((rc = s->h_hits.ensure(c.res.host_bytes + 8))) return rc;  // (+ 8 and 8: the pruned sweep's two counters)
         void* mapped = nullptr;
         OTT_HIP(hipHostGetDevicePointer(&mapped, s->h_hits.p, 0));
         res_dev = (char*)mapped;
@@ -288,7 +320,7 @@ void fill_exact_call(ExactCtx& c, const uint64_t* d_mask, uint64_t mask_bits) {
     c.p.perq = c.perq;
     c.p.list_stride = c.x.KS;
     c.p.small = c.x.variant;
-    if (c.x.lean) embed_exact_inputs(c.p, c.queries, (size_t)s->dim * 4, host_inv_norm_exact(c.queries, s->dim), c.pl, c.prefix);
+    if (c.x.lean) embed_exact_inputs(c.p, c.queries, (size_t)s->dim * 4, c.query_inv_norm(), c.pl, c.prefix);
 }
 
 // the call's parameters over a part of its rows (the pruned sweep's seed, or the rest), its block lists at dst
@@ -309,13 +341,15 @@ int pruned_sweep(ExactCtx& c) {
     // [count (u64, 64 B) | KS hits]: the seed's merged result, read by the second launch
     if ((rc = s->d_prune.ensure(64 + (size_t)KS * sizeof(ott_hit)))) return rc;
     uint64_t* seed_res = (uint64_t*)s->d_prune.p;
-    // the kernel's count of finished tails: a running total in device memory, read back with the result (host output only)
+    // the kernel's counts of the rows that passed the gate and of the rows it finished in f32 (one and the same count without the
+    // int8 check): running totals in device memory, read back with the result (host output only)
     unsigned long long* tails_dev = nullptr;
     if (c.fetch) {
         if (!s->d_tails.p) {
-            if ((rc = s->d_tails.ensure(8))) return rc;
-            OTT_HIP(hipMemsetAsync(s->d_tails.p, 0, 8, s->stream));
+            if ((rc = s->d_tails.ensure(16))) return rc;
+            OTT_HIP(hipMemsetAsync(s->d_tails.p, 0, 16, s->stream));
             s->tails_seen = 0;
+            s->fin_seen = 0;
         }
         tails_dev = (unsigned long long*)s->d_tails.p;
     }
@@ -353,6 +387,13 @@ int pruned_sweep(ExactCtx& c) {
     sketch_inputs(pb);
     pb.prune_seed = seed_res;
     pb.prune_tails = tails_dev;
+    if (c.i8_check) {
+        pb.chk_plane = c.chk_plane;
+        pb.i8_scale = c.chk_scale;
+        pb.flag = s->d_flag;
+        pb.i8_qscale = c.chk_qscale;
+        pb.chk_eps = c.chk_eps;
+    }
     return launch_exact(s, pb, 1, c.x.E, c.gridB);
 }
 
@@ -388,15 +429,19 @@ int fetch_exact(ExactCtx& c, std::vector<std::vector<ott_hit>>& lists, ott_stats
     ott_store* s = c.s;
     const uint32_t KS = c.x.KS;
     char* hh = (char*)s->h_hits.p;
-    if (c.prune.c) OTT_HIP(hipMemcpyAsync(hh + c.res.bytes, s->d_tails.p, 8, hipMemcpyDeviceToHost, s->stream));
+    if (c.prune.c) OTT_HIP(hipMemcpyAsync(hh + c.res.bytes, s->d_tails.p, 16, hipMemcpyDeviceToHost, s->stream));
     OTT_HIP(hipStreamSynchronize(s->stream));
     // rows whose last stages were read after the checkpoint (the seed's rows are not counted: they have no checkpoint; behind an
     // estimate pass the gated launch covers every row, the few rows that pass finished are not counted)
     if (c.prune.c) {
-        uint64_t total;
-        memcpy(&total, hh + c.res.bytes, 8);
-        st.rescored += total - s->tails_seen;
-        s->tails_seen = total;
+        uint64_t total[2];
+        memcpy(total, hh + c.res.bytes, 16);
+        const uint64_t passed = total[0] - s->tails_seen;
+        // (with the int8 check the rows finished in f32 are counted apart; without it they are the rows that passed)
+        (s->owner ? s->owner : s)->exact_finished.fetch_add(c.i8_check ? total[1] - s->fin_seen : passed, std::memory_order_relaxed);
+        st.rescored += passed;
+        s->tails_seen = total[0];
+        s->fin_seen = total[1];
     }
     const uint64_t* counts = (const uint64_t*)hh;
     const ott_hit* hits = (const ott_hit*)(hh + c.res.cnt_pad);

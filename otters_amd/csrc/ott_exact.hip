@@ -25,6 +25,7 @@
 
 #include "ott_internal.h"
 #include "ott_prune.h"
+#include "ott_i8_check.h"
 #include "ott_exact_dev.h"  // candidate order, wave list, filter, metric terms, reduce8: shared with ott_gather.hip
 
 namespace ott {
@@ -43,6 +44,10 @@ constexpr int PQ_WORDS = 10;
 // four bits per dim: the digit planes of the quantised query behind the queues — per stage three digits x four words (ott_prune.h)
 constexpr int QD_WORDS = (int)(OTT_QEMB_MAX / KC) * 12;
 constexpr int EXACT_SMEM_PRUNE = EXACT_SMEM + WAVES * PQ_CAP * PQ_WORDS * 4 + QD_WORDS * 4;  // 53.3 KB: two workgroups per CU
+// the int8 check of the head form's survivors (CHK): the query's int8 operand behind the digit planes, one word per four dims of a
+// plane row (128-B stages: dim rounded up to 128)
+constexpr int Q8_WORDS = (int)((OTT_QEMB_MAX + 127) / 128) * 32;
+constexpr int EXACT_SMEM_CHECK = EXACT_SMEM_PRUNE + Q8_WORDS * 4;  // 54.1 KB: two workgroups per CU
 // experiment builds only: -DOTT_SK4_DECODE_F32 keeps the four-bit form's former decode (an f32 chain, one fma per dim, and
 // prune_score_bound_sketchb) so that both decodes can be alternated in one job
 #ifdef OTT_SK4_DECODE_F32
@@ -133,8 +138,20 @@ __device__ __forceinline__ void exact_glds16(const char* sbase, uint32_t voff, u
 // p.seed_keep best (ott_prune.h: prune_score_est_sketchq; a NaN estimate is not offered).  Behind the wave's last tile those rows go
 // to the deferred-tail queue with zero accumulators, the list is emptied, and one pq_finish scores them in the full sweep's loads
 // and additions and offers the exact scores: the block list holds exact scores of eligible rows only.
-template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false, int SK = 0, bool SEED = false>
+// CHK (the gated launch of the head form, E = 1): survivors are checked on the store's int8 plane before their f32 finish
+// (ott_exact_plan.h: prune_plan_i8_check; ott_i8_check.h).  The workgroup quantises the query once into its int8 operand in LDS, as
+// it does for the digit planes.  When 64 rows wait in the queue, pq_refine scores them as one dense tile — the plane's 128-B stages
+// through the same eight-rows-per-instruction loads as pq_finish, lane = row, eight v_dot4 per 32 bytes into two exact i32 sums —
+// forms the approximate score with run_i8_single's operand and row factor, and drops every row whose score plus the certified
+// error ranks strictly below the gate (i8_check_drops; rows outside the plane's error model and NaNs stay).  The rows that stay
+// move to the front of the 64 and pq_finish, untouched, finishes them AT ONCE: the wave's list then sees every row that can
+// enter it at the very tile it would without the check, so the gate, and with it the rows that pass the line gate (`rescored`),
+// are the same with the check on and off.  At the headline's rates more than half of the tiles of 64 keep no row and skip the
+// finish altogether.  The launch counts the rows that passed the line gate in p.prune_tails[0] and the finished ones in [1].
+template <int MK, int NQ, int E, bool PERQ, bool DUMP = false, bool SMALL = false, bool BLK = (E > 1), bool I8 = false, bool PRUNE = false, int SK = 0, bool SEED = false,
+          bool CHK = false>
 __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) {
+    static_assert(!CHK || (SK == 5 && !SEED && E == 1), "the int8 check is the gated head launch's, one list entry per lane");
     static_assert(!I8 || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL), "the int8 sweep takes one query, cosine / dot, merged");
     static_assert(!PRUNE || (NQ == 1 && MK == MK_DOT && !PERQ && !DUMP && !SMALL && !I8), "the pruned sweep takes one query, cosine / dot, merged");
     static_assert((SK == 0 || PRUNE) && (SK == 0 || SK == 1 || SK == 3 || SK == 4 || SK == 5), "the sketch is the pruned sweep's: none, one, three or four bits per dim (5: four with a head)");
@@ -219,6 +236,22 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
     const uint32_t nstages = (p.ld + KC - 1) / KC;
     // SK = 4: the digit planes of the quantised query, [stage][digit][word]; one thread per word of eight dims (zeros past dim)
     [[maybe_unused]] uint32_t* qd = reinterpret_cast<uint32_t*>(smem + WAVES * STAGE_FLOATS + WAVES * PQ_CAP * PQ_WORDS);
+    // CHK: the query's int8 operand behind them, one thread per word of four dims (zeros past dim): i8_quant_word with the pre-scale
+    // and the scale the host measured the query's loss with (ott_i8_check.h: i8_query_quant)
+    [[maybe_unused]] uint32_t* q8w = qd + QD_WORDS;
+    [[maybe_unused]] const uint32_t ld8w = ((p.dim + 127u) & ~127u) >> 2;  // words of a plane row
+    if constexpr (CHK) {
+        const float pf8 = p.metric == OTT_METRIC_COSINE ? qinv[0] : 1.0f;
+        const float inv_sq = __fdiv_rn(1.0f, p.i8_qscale);
+        const uint32_t nw8 = ld8w < (uint32_t)Q8_WORDS ? ld8w : (uint32_t)Q8_WORDS;
+        for (uint32_t i = threadIdx.x; i < nw8; i += 64 * BW) {
+            float q4[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) q4[j] = (4 * i + j < p.dim) ? Q[4 * i + j] : 0.0f;
+            q8w[i] = i8_quant_word(q4, pf8, inv_sq);
+        }
+        // (the barrier behind the digit planes covers these words too: CHK runs in the head form only)
+    }
     if constexpr (SK4 && SK4_INT) {
         const uint32_t nqs = nstages < (uint32_t)(QD_WORDS / 12) ? nstages : (uint32_t)(QD_WORDS / 12);
         for (uint32_t i = threadIdx.x; i < nqs * 4; i += 64 * BW) {
@@ -322,6 +355,77 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
         pq_head = (pq_head + n) & (PQ_CAP - 1);
         pq_n -= n;
         tails_done += n;
+    };
+    // CHK: the first n <= 64 queued rows on the int8 plane, as one tile.  The rows that stay are moved to the front of the n (their
+    // accumulators are zero like everyone's in the head form: only the inverse norm and the row move); returns how many stay
+    [[maybe_unused]] uint32_t queued = 0;  // rows that passed the line gate (wave-uniform; added to p.prune_tails[0] at the end)
+    [[maybe_unused]] auto pq_refine = [&](uint32_t n, uint32_t gate) __attribute__((always_inline)) -> uint32_t {
+        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+        wave_sync();
+        const bool valid = (uint32_t)lane < n;
+        const uint32_t e = (pq_head + (valid ? (uint32_t)lane : 0u)) & (PQ_CAP - 1);
+        const float vinv = pq[8 * PQ_CAP + e];
+        const uint32_t my_row = pq_row[e];
+        // the row's scale and flag: scattered 4-B and 1-B reads, in flight behind the stages
+        const float sv = p.i8_scale[my_row];
+        const uint32_t fl = p.flag[my_row];
+        const uint32_t* rp[8];
+#pragma unroll
+        for (int m = 0; m < 8; m++) {  // rows past n re-read the first queued row (never judged)
+            const uint32_t i = 8 * m + lrow;
+            rp[m] = reinterpret_cast<const uint32_t*>(p.chk_plane) + (uint64_t)pq_row[(pq_head + (i < n ? i : 0u)) & (PQ_CAP - 1)] * ld8w + (uint32_t)lslot * 4;
+        }
+        v4f R[8];
+        auto load_stage = [&](uint32_t s) {  // (a plane row is whole 128-B stages: no column to clamp)
+#pragma unroll
+            for (int m = 0; m < 8; m++) R[m] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(rp[m] + s * KC));
+        };
+        const uint32_t nst8 = ld8w / KC;
+        int iacc[2] = {0, 0};  // two independent v_dot4 chains, exact
+        load_stage(0);
+        for (uint32_t s = 0; s < nst8; s++) {
+#pragma unroll
+            for (int m = 0; m < 8; m++) {
+                const int row = 8 * m + lrow;
+                const v4f v = R[m];
+                *reinterpret_cast<float4*>(st + row * KC + ((lslot ^ ((row >> 1) & 7)) << 2)) = make_float4(v.x, v.y, v.z, v.w);
+            }
+            wave_sync();
+            if (s + 1 < nst8) load_stage(s + 1);
+#pragma unroll
+            for (int j = 0; j < KC / 8; j++) {
+                const float4 a = *reinterpret_cast<const float4*>(st + lane * KC + (((2 * j) ^ sw) << 2));
+                const float4 b = *reinterpret_cast<const float4*>(st + lane * KC + (((2 * j + 1) ^ sw) << 2));
+                const int x[8] = {__float_as_int(a.x), __float_as_int(a.y), __float_as_int(a.z), __float_as_int(a.w),
+                                  __float_as_int(b.x), __float_as_int(b.y), __float_as_int(b.z), __float_as_int(b.w)};
+                // the operand's eight words of these 32 dims: two broadcast reads (a wave-uniform address)
+                const v4u* qp = reinterpret_cast<const v4u*>(q8w + s * KC + 8 * j);
+                const v4u q0 = qp[0], q1 = qp[1];
+#pragma unroll
+                for (int l = 0; l < 4; l++) {
+                    iacc[0] = __builtin_amdgcn_sdot4(x[l], (int)q0[l], iacc[0], false);
+                    iacc[1] = __builtin_amdgcn_sdot4(x[4 + l], (int)q1[l], iacc[1], false);
+                }
+            }
+            wave_sync();
+        }
+        const float approx = i8_approx_score(iacc[0] + iacc[1], i8_row_factor(p.metric == OTT_METRIC_COSINE, vinv, sv, p.i8_qscale));
+        const bool stay = valid && !i8_check_drops(approx, p.chk_eps, take_max, gate, (fl & 5u) != 0);
+        const uint64_t km = __ballot(stay);
+        if (stay) {  // (every lane holds its own entry in registers, and a row only moves towards the front)
+            const uint32_t at = (pq_head + (uint32_t)__popcll(km & ((1ull << lane) - 1ull))) & (PQ_CAP - 1);
+            pq[8 * PQ_CAP + at] = vinv;
+            pq_row[at] = my_row;
+        }
+        return (uint32_t)__popcll(km);
+    };
+    // the first n queued rows: checked, and what stays finished at once; the gate is the one the last tile was judged with (the
+    // list changes in pq_finish only).  While it is open nothing can be dropped and the rows are finished as without the check
+    [[maybe_unused]] auto pq_drain = [&](uint32_t n, uint32_t gate) __attribute__((always_inline)) {
+        const uint32_t stay = gate != 0 ? pq_refine(n, gate) : n;
+        if (stay) pq_finish(stay);
+        pq_head = (pq_head + (n - stay)) & (PQ_CAP - 1);
+        pq_n -= n - stay;
     };
 
     if constexpr (HD) {
@@ -484,10 +588,12 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                 pq_row[at] = (uint32_t)my_row;
             }
             pq_n += (uint32_t)__popcll(km);
+            if constexpr (CHK) queued += (uint32_t)__popcll(km);
             if (!SEED && pq_n >= 64) {
                 // (64 survivors: about one tile in seventy at the headline's rate.  What was asked for ahead is asked for again behind
                 // the finish instead of being kept across it: its 38 registers would sit on top of the finish's own staging registers)
-                pq_finish(64);
+                if constexpr (CHK) pq_drain(64, gate);
+                else pq_finish(64);
                 if (pf) {
                     load_line(row0n, cntn, 0);
                     load_head(row0n, cntn);
@@ -963,7 +1069,16 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
         }
     }
 
-    if constexpr (PRUNE) {
+    if constexpr (CHK) {
+        if (pq_n) {  // (< 64 left)
+            const uint32_t own = (uint32_t)(tk[0] >> 32);
+            pq_drain(pq_n, own > theta ? own : theta);
+        }
+        if (p.prune_tails != nullptr && lane == 0) {
+            if (queued != 0) atomicAdd(p.prune_tails, (unsigned long long)queued);
+            if (tails_done != 0) atomicAdd(p.prune_tails + 1, (unsigned long long)tails_done);
+        }
+    } else if constexpr (PRUNE) {
         if (pq_n) pq_finish(pq_n);  // (< 64 left)
         if (p.prune_tails != nullptr && tails_done != 0 && lane == 0) atomicAdd(p.prune_tails, (unsigned long long)tails_done);
     }
@@ -1803,15 +1918,16 @@ int exact_grid(const ott_store* s, uint32_t n_tiles) {
 }
 
 // the pruned sweep (p.prune_stage != 0): its queue takes the dynamic LDS past 48 KB
-template <int E, bool BLK, int SK, bool SEED = false>
+template <int E, bool BLK, int SK, bool SEED = false, bool CHK = false>
 static int launch_prune(ott_store* s, const ExactParams& p, int grid) {
-    auto kern = exact_kernel<MK_DOT, 1, E, false, false, false, BLK, false, true, SK, SEED>;
+    auto kern = exact_kernel<MK_DOT, 1, E, false, false, false, BLK, false, true, SK, SEED, CHK>;
+    constexpr int smem = CHK ? EXACT_SMEM_CHECK : EXACT_SMEM_PRUNE;  // (the check's int8 operand sits behind the digit planes)
     static std::atomic<uint64_t> attr_set{0};
     if (ott::attr_needed(attr_set, s->device)) {
-        OTT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, EXACT_SMEM_PRUNE));
+        OTT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         ott::attr_done(attr_set, s->device);
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), EXACT_SMEM_PRUNE, s->stream, p);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s->stream, p);
     OTT_HIP(hipGetLastError());
     return OTT_OK;
 }
@@ -1825,6 +1941,14 @@ static int launch_prune_head(ott_store* s, const ExactParams& p, int grid) {
         if (p.seed_est != 0) return launch_prune<E, BLK, 5, true>(s, p, grid);
     }
     if (p.seed_est != 0) return fail(OTT_ERR_INVALID, "launch_exact: the estimate pass needs the integer decode and a list of k <= 64");
+    // (the int8 check of the survivors, p.chk_plane != nullptr: instantiated for k <= 64, which is all prune_plan_i8_check asks for)
+    if constexpr (SK4_INT && E == 1) {
+        if (p.chk_plane != nullptr) {
+            if (p.i8_scale == nullptr || p.flag == nullptr || p.dim > OTT_QEMB_MAX) return fail(OTT_ERR_INVALID, "launch_exact: the int8 check needs the plane's scales and flags and a query of up to 896 dims");
+            return launch_prune<E, BLK, 5, false, true>(s, p, grid);
+        }
+    }
+    if (p.chk_plane != nullptr) return fail(OTT_ERR_INVALID, "launch_exact: the int8 check needs the integer decode and a list of k <= 64");
     if constexpr (SK4_INT && E <= 4) return launch_prune<E, BLK, 5>(s, p, grid);
     else return fail(OTT_ERR_INVALID, "launch_exact: the head form needs the integer decode and a list of k <= 256");
 }

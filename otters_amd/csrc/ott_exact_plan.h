@@ -191,6 +191,27 @@ struct HeadState {
 inline bool prune_plan_head(const PruneIn& in, const PrunePlan& pp, bool quant_ok, const HeadState& hd) {
     return prune_plan_needs_quant(in, pp) && quant_ok && hd.present && hd.covers && hd.option != 0 && in.E <= 4;
 }
+// The int8 check of the head form's survivors ("survivors on the int8 plane"; ott_i8_check.h).  A row that passes
+// the four-bit bound is scored on the store's int8 plane — 768 B and a scale at dim 768 — and goes on to its 3072-B f32 finish
+// only unless that approximate score plus the int8 level's certified error ranks strictly below the gate.  It runs when
+//   * the head form runs, with one list entry per lane (k <= 64: the only widths the kernel is instantiated for);
+//   * the int8 plane exists and covers every row right now (i8_plane_peek, ott_planes.hip: asking builds nothing, so a store whose background
+//     builder has not finished, or that keeps no int8 plane, takes the sweep without the check);
+//   * the query is inside the int8 level's error model and its bound is finite (ott_i8_check.h: i8_check_eps);
+//   * the option (exact_i8_check: -1 / 1 use it, 0 never) allows it.
+// Otherwise the sweep is the one without the check, to the bit and to the launch.  Hits and `rescored` are the same either way.
+// Experiment builds: -DOTT_X_I8_CHECK=0 never plans it.
+#ifndef OTT_X_I8_CHECK
+#define OTT_X_I8_CHECK 1
+#endif
+struct I8CheckState {
+    bool plane_ready;  // i8_plane_peek found the plane covering every row
+    int option;        // exact_i8_check
+    bool eps_ok;       // the query is query_regular and i8_check_eps gave a finite bound
+};
+inline bool prune_plan_i8_check(const PruneIn& in, const PrunePlan& pp, bool head, const I8CheckState& ck) {
+    return OTT_X_I8_CHECK != 0 && pp.c != 0 && head && in.E == 1 && ck.plane_ready && ck.option != 0 && ck.eps_ok;
+}
 // The seed as an estimate pass ("the seed by estimate").  The gate only needs k exactly scored rows that score
 // well, so in the head form the seed launch need not read its rows in full: it streams their lines, heads and inverse norms,
 // ranks them by the decode's estimate (ott_prune.h: prune_score_est_sketchq), and each wave finishes its `keep` best exactly.

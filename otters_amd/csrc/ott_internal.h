@@ -95,9 +95,9 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  TWENTY-FIVE of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  TWENTY-SIX of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, id_gather, group_gather, masks_sweep, fuse_device, sparse_table, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, exact_sketch_head, exact_i8_check, id_gather, group_gather, masks_sweep, fuse_device, sparse_table, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
@@ -117,6 +117,8 @@ struct Options {
     int exact_sketch_head = -1;   // the head of the four-bit lines (20 B per row: stage 0's codes and a remainder norm over every stage, made with
                                   // the lines): -1 / 1 = kept and used wherever the store keeps four-bit lines — a gated row then reads no f32
                                   // stage at all — 0 = never: the sweep reads stage 0 of every row, as it does on a store without a head
+    int exact_i8_check = -1;      // the head form's survivors are checked on the int8 plane before their f32 finish (ott_exact_plan.h:
+                                  // prune_plan_i8_check): -1 / 1 = wherever the plane is ready and the query is inside its error model, 0 = never
     int force_fallback = 0;       // TESTS: bit mask of code paths the library otherwise takes only in rare conditions, forced on so that the
                                   // suite and the option fuzz hold them to the oracle: 1 = block lists merged by insertion (merge_kernel: the
                                   // rank merge's own fallback when a plateau overflows its buffer or there are > 4096 lists), 2 = k <= 64
@@ -294,8 +296,11 @@ struct ott_store {
     // per-query scratch
     ott::DevBuf d_queries, d_qinv, d_rowmask, d_runs, d_prefix, d_lists, d_lists2, d_hits, d_count, d_cand, d_misc;  // d_lists2: first stage of the two-stage merge
     ott::DevBuf d_prune;     // pruned exact sweep: the seed's merged result (the gate of the second launch)
-    ott::DevBuf d_tails;     // pruned exact sweep: running count of the rows whose tails the kernel finished (u64)
-    uint64_t tails_seen = 0; // ... and what of it earlier queries have reported
+    ott::DevBuf d_tails;     // pruned exact sweep: two running counts (u64 each) — [0] the rows that passed the gate (without the int8 check:
+                             // the rows whose tails the kernel finished, the same rows), [1] with the int8 check the rows finished in f32
+    uint64_t tails_seen = 0; // ... and what of [0] earlier queries have reported
+    uint64_t fin_seen = 0;   // ... and of [1]
+    std::atomic<uint64_t> exact_finished{0};  // owner store: rows the pruned sweeps of all contexts finished in f32 so far (ott_store_exact_finished)
     ott::DevBuf d_minpos;    // device word behind min_pos_inv
     // MFMA path scratch
     ott::DevBuf m_Q, m_qinv, m_qnorm, m_tau, m_cntA, m_cntB, m_candA, m_candB, m_over, m_out, m_outcnt, m_uncert, m_prefix;
@@ -457,6 +462,7 @@ int multi_set_option(ott_store* ms, const char* name, int64_t value);
 int multi_prepare_batch(ott_store* ms);
 int multi_sync(ott_store* ms);
 int multi_batch_ready(ott_store* ms);
+uint64_t multi_exact_finished(ott_store* ms);
 int multi_add_column(ott_store* ms, uint32_t dtype, const void* values_host, const uint64_t* nulls, uint64_t n, uint32_t* out_column_id);
 int multi_eval_row_mask(ott_store* ms, const ott_leaf* leaves, uint32_t n_leaves, uint32_t n_clauses, uint64_t* out_host);
 int multi_zone_stats(ott_store* ms, uint32_t column, uint64_t chunk_size, void* out_min, void* out_max, uint64_t* out_non_null);
@@ -522,6 +528,7 @@ PlaneSnapshot plane_snapshot(const ott_store* s);
 // the store's int8 plane (option hi_fmt = -1 / 2), built / extended on demand; *img_out = nullptr when it is unavailable
 int ensure_i8_plane(ott_store* ctx, const int8_t** img_out, const float** scale_out, float* rel_max_out);
 bool i8_plane_ready(ott_store* ctx);
+bool i8_plane_peek(ott_store* ctx, const int8_t** img_out, const float** scale_out, float* rel_max_out);  // false unless i8_plane_ready; builds nothing
 // f32 rows -> int8 rows of pitch ld8 bytes.  common_scale > 0: every row quantised with THAT scale (the query operand block: one
 // scale per batch, so that it folds into the kernel's row factors); else per row max|x| / 127, written to scale_out[r].
 // pre[r] (optional): the row is multiplied by it first (cosine: 1 / ||q||).  rel_out[r] (optional) = ||x - s x~|| / ||x||.
@@ -642,6 +649,12 @@ struct ExactParams {
     // the seed as an estimate pass (head form, ott_exact_plan.h: prune_plan_seed_est): seed_est = 1 runs the launch without a gate —
     // rows are ranked by the decode's estimate and each wave finishes its seed_keep best exactly; no prune_seed, no prune_tails
     uint32_t seed_est, seed_keep;
+    // the int8 check of the head form's survivors (gated launch, ott_exact_plan.h: prune_plan_i8_check): chk_plane != nullptr = the
+    // store's int8 plane (rows of dim rounded up to 128 bytes), with i8_scale, flag and i8_qscale as on the int8 sweep above; chk_eps:
+    // the certified |approximate - exact-order score| of this query (ott_i8_check.h: i8_check_eps).  prune_tails then holds two
+    // counters: [0] rows that passed the line gate, [1] rows finished in f32
+    const int8_t* chk_plane;
+    float chk_eps;
     float qemb[OTT_QEMB_MAX];  // last: the embedded query (kernel arguments are limited to 4 KB)
 };
 // (OTT_QEMB_MAX and the OTT_SKETCH*_MAX_WORDS limits of the sketch forms: ott_exact_plan.h)

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "ott_internal.h"
+#include "ott_i8_check.h"
 
 namespace ott {
 
@@ -1872,35 +1873,14 @@ int run_i8_single(ott_store* s, const ott_query_desc* d, const RunPlan& pl, uint
     // ---- the query: norm, int8 operand, measured loss ---------------------------------------------------------------
     const float* q = d->queries;
     const float q_inv = host_inv_norm_exact(q, dim);
-    double n2 = 0.0;
-    float amax = 0.0f;
-    for (uint32_t i = 0; i < dim; i++) {
-        n2 += (double)q[i] * q[i];
-        amax = fmaxf(amax, fabsf(q[i]));
-    }
-    const float qnorm = (float)(sqrt(n2) * (1.0 + 1e-6));
+    int8_t q8[OTT_QEMB_MAX * 4];
+    memset(q8, 0, ld8);
+    const I8Query iq = i8_query_quant(q, dim, cosine, q_inv, q8);  // (ott_i8_check.h: shared with the pruned exact sweep's check)
+    const float qnorm = iq.qnorm, s_q = iq.s_q, qrel = iq.qrel;
     out.assign(1, {});
     uncertified.assign(1, 1u);
     st.path_used = OTT_PATH_MFMA;
-    if (!query_regular(qnorm)) return OTT_OK;  // outside the error model: the next level / the exact path answers
-    const float pf = cosine ? q_inv : 1.0f;
-    const float e_max = amax * pf;
-    const float s_q = (e_max > 0.0f && e_max < __builtin_inff()) ? e_max / 127.0f : 1.0f;
-    const float inv_sq = 1.0f / s_q;
-    int8_t q8[OTT_QEMB_MAX * 4];
-    memset(q8, 0, ld8);
-    double se = 0.0, sx = 0.0;
-    for (uint32_t i = 0; i < dim; i++) {
-        const float xe = q[i] * pf;
-        float t = rintf(xe * inv_sq);
-        t = t == t ? fminf(fmaxf(t, -127.0f), 127.0f) : 0.0f;
-        q8[i] = (int8_t)(int)t;
-        const double df = (double)xe - (double)s_q * (double)(int)t;
-        se += df * df;
-        sx += (double)xe * (double)xe;
-    }
-    float qrel = sx > 0.0 ? (float)(sqrt(se / sx) * 1.0001) : 0.0f;
-    if (!(qrel <= 1.0f)) qrel = 1.0f;
+    if (!iq.regular) return OTT_OK;  // outside the error model: the next level / the exact path answers
 
     // ---- error bound: the int8 level's, as in run_mfma (both sides of |approximate - exact-order|: see i8_c_eps_units) ----------
     const ErrorModel em = error_model(level, false, dim, d->metric, true, s->opt.eps_scale_ppm, i8_rel);

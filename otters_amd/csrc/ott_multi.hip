@@ -1125,6 +1125,13 @@ int multi_batch_ready(ott_store* ms) {
     return ms->n ? 1 : 0;
 }
 
+uint64_t multi_exact_finished(ott_store* ms) {
+    ott::host::SharedLock rd(ms->rw);
+    uint64_t total = 0;
+    for (ott_store* s : ms->multi->shards) total += ott_store_exact_finished(s);
+    return total;
+}
+
 int multi_sync(ott_store* ms) {
     for (ott_store* s : ms->multi->shards) {
         const int rc = ott_store_sync(s);

@@ -532,6 +532,19 @@ static bool plane_ready(ott_store* own, const Plane& pl) {
 }
 bool hi_plane_ready(ott_store* ctx) { return plane_ready(owner_of(ctx), owner_of(ctx)->planes.hi); }
 bool i8_plane_ready(ott_store* ctx) { return plane_ready(owner_of(ctx), owner_of(ctx)->planes.i8); }
+// ... and, where it is ready, what a reader of it needs, taken under the same lock: the plane, the rows' scales, the measured loss.
+// The caller holds the store (shared), so nothing moves the rows; a builder on another context only ever extends a plane that does
+// not cover the store yet, and this one does
+bool i8_plane_peek(ott_store* ctx, const int8_t** img_out, const float** scale_out, float* rel_max_out) {
+    ott_store* own = owner_of(ctx);
+    const PlaneSet& p = own->planes;
+    std::lock_guard<std::mutex> g(own->planes.mu);
+    if (!(p.i8.d != nullptr && !p.i8.off && !p.split.off && own->n != 0 && p.i8.rows == own->n && p.d_i8_scale != nullptr)) return false;
+    *img_out = (const int8_t*)p.i8.d;
+    *scale_out = p.d_i8_scale;
+    *rel_max_out = p.i8.rel;
+    return true;
+}
 
 bool first_plane_ready(ott_store* ctx) {
     ott_store* own = owner_of(ctx);

@@ -28,13 +28,13 @@ struct OptName {
     const char* name;
     int kind;  // 0 = bool, 1 = tri-state (-1 automatic / 0 / 1), 2 = non-negative int
 };
-// the twenty-five options of the product library (see struct Options) ...
+// the twenty-six options of the product library (see struct Options) ...
 const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"hi_prebuild", 1},          {"stage_appends", 1},       {"multi_transport", 2},
                              {"multi_rebalance", 0}, {"multi_min_shard_rows", 2}, {"exact_small", 1},     {"large_k_from", 2},        {"small_sort", 1},
                              {"mfma_f32", 0},        {"no_hi_pass", 0},      {"no_batch_image", 0},       {"force_fallback", 2},      {"eps_scale_ppm", 2},
                              {"multi_fake_distinct", 0}, {"exact_prune", 1},            {"exact_sketch", 1},
                              {"id_gather", 1},       {"exact_sketch_bits", 2},   {"group_gather", 1},         {"exact_sketch_head", 1},
-                             {"masks_sweep", 2},     {"fuse_device", 1},         {"sparse_table", 1},
+                             {"masks_sweep", 2},     {"fuse_device", 1},         {"sparse_table", 1},         {"exact_i8_check", 1},
 #ifdef OTT_MFMA_DEBUG_BUILD
                              // ... and, in the diagnostic build only, kernel tuning, timing ablations and every fallback bit by its own name
                              {"mfma_wg", 2},         {"mfma_growth", 2},     {"mfma_debug", 0},           {"mfma_abl", 2},            {"hi_tmin", 2},
@@ -42,11 +42,11 @@ const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"h
                              {"merge_rank1", 1},     {"maxsim_fold", 1},
 #endif
 };
-static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 25
+static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 26
 #ifdef OTT_MFMA_DEBUG_BUILD
                                                             + 12
 #endif
-              , "the product library's option table stays at twenty-five entries");
+              , "the product library's option table stays at twenty-six entries");
 }  // namespace
 
 int option_set(Options& o, const char* name, long long v) {
@@ -83,6 +83,7 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "exact_sketch") return tri(o.exact_sketch);
     if (n == "exact_sketch_bits") { if (v != 1 && v != 3 && v != 4) return -1; o.exact_sketch_bits = (int)v; return 0; }
     if (n == "exact_sketch_head") return tri(o.exact_sketch_head);
+    if (n == "exact_i8_check") return tri(o.exact_i8_check);
     if (n == "id_gather") return tri(o.id_gather);
     if (n == "group_gather") return tri(o.group_gather);
     if (n == "fuse_device") return tri(o.fuse_device);
@@ -1162,6 +1163,11 @@ int ott_store_write_rows(ott_store* s, uint64_t first_row, const float* rows_hos
 }
 
 uint64_t ott_store_len(const ott_store* s) { return s ? store_rows(s) : 0; }  // staged rows count: they were appended
+uint64_t ott_store_exact_finished(const ott_store* s) {
+    if (!s) return 0;
+    if (s->multi) return multi_exact_finished(const_cast<ott_store*>(s));
+    return s->exact_finished.load(std::memory_order_relaxed);
+}
 uint32_t ott_store_dim(const ott_store* s) { return s ? s->dim : 0; }
 int ott_store_device(const ott_store* s) { return s ? s->device : -1; }
 

@@ -1649,8 +1649,12 @@ class VecStore:
         """The batch path's hi plane exists and covers every row (built in the background after appends: option hi_prebuild)."""
         return bool(self._n) and bool(N.lib().ott_store_batch_ready(self._handle()))
 
+    def exact_finished(self) -> int:
+        """Rows the pruned exact sweeps of this store have finished in f32 so far (ott_store_exact_finished): a running total."""
+        return int(N.lib().ott_store_exact_finished(self._handle()))
+
     def set_option(self, name: str, value: int) -> None:
-        """Behaviour switch of this store (ott_store_set_option; the twenty-five names are listed in include/otters_hip.h:
+        """Behaviour switch of this store (ott_store_set_option; the twenty-six names are listed in include/otters_hip.h:
         "tie_order", "hi_fmt", "hi_prebuild", ..., "force_fallback").  Results never depend on any but "tie_order"."""
         self._options[name] = int(value)
         if self._h is not None:
