@@ -26,6 +26,7 @@
 #include "ott_internal.h"
 #include "ott_prune.h"
 #include "ott_i8_check.h"
+#include "ott_finish_few.h"
 #include "ott_exact_dev.h"  // candidate order, wave list, filter, metric terms, reduce8: shared with ott_gather.hip
 
 namespace ott {
@@ -73,6 +74,12 @@ constexpr int SK3_XP = ((int)OTT_SKETCH_MAX_WORDS + 2 + 3) / 4 - 8;
 #define OTT_X_BLOCKS_PER_CU 2
 #endif
 constexpr int BLOCKS_PER_CU = OTT_X_BLOCKS_PER_CU;
+// The head form's kernels with one list entry per lane finish at most sixteen queued rows as rounds of several stages (pq_finish_few,
+// ott_finish_few.h).  Experiment builds give the wide finish back: "-DOTT_X_FINISH_FEW=0".
+#ifndef OTT_X_FINISH_FEW
+#define OTT_X_FINISH_FEW 1
+#endif
+static_assert(KC == (int)FF_KC, "ott_finish_few.h walks stages of KC floats");
 // small-grid variant (a handful of tiles per CU: the launch is latency-bound, not bandwidth-bound): ONE wave per
 // workgroup with a deep LDS-DMA ring
 constexpr int SMALL_RING = 8;         // ring slots: 7 K stages in flight per wave (vmcnt counts to 63 = 7 x 8 + 7)
@@ -159,6 +166,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
     constexpr bool SK4 = SK == 4 || SK == 5;   // either four-bit form
     static_assert(!HD || SK4_INT, "the head form decodes by integer dot products only");
     static_assert(!SEED || (HD && E == 1), "the estimate pass is the head form's, one list entry per lane");
+    constexpr bool FEW = OTT_X_FINISH_FEW != 0 && HD && E == 1;  // a finish of at most FF_MAX_ROWS rows takes pq_finish_few
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -283,7 +291,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
     uint32_t* pq_row = reinterpret_cast<uint32_t*>(pq + 9 * PQ_CAP);
     uint32_t pq_head = 0, pq_n = 0;  // wave-uniform
     uint32_t tails_done = 0;         // rows this wave finished (wave-uniform; added to p.prune_tails at the end)
-    auto pq_finish = [&](uint32_t n) {  // the first n <= 64 queued rows: stages c .. n-1 as one tile, then the list
+    [[maybe_unused]] auto pq_finish = [&](uint32_t n) {  // the first n <= 64 queued rows: stages c .. n-1 as one tile, then the list
         wave_sync();
         const bool valid = (uint32_t)lane < n;
         const uint32_t e = (pq_head + (valid ? (uint32_t)lane : 0u)) & (PQ_CAP - 1);
@@ -320,41 +328,83 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             }
             wave_sync();
             if (s + 1 < nstages) load_stage(s + 1);
-#pragma unroll
-            for (int j = 0; j < KC / 8; j++) {
-                const uint32_t col = s * KC + 8 * j;
-                if (col < p.dim) {
-                    const float4 a = *reinterpret_cast<const float4*>(st + lane * KC + (((2 * j) ^ sw) << 2));
-                    const float4 b = *reinterpret_cast<const float4*>(st + lane * KC + (((2 * j + 1) ^ sw) << 2));
-                    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-                    if (col + 8 <= p.dim) {
-#pragma unroll
-                        for (int l = 0; l < 8; l++) acc[l] = __fadd_rn(acc[l], exact_term<MK>(Q[col + l], x[l]));
-                    } else {
-                        const uint32_t nt = p.dim - col;
-#pragma unroll
-                        for (int l = 0; l < 7; l++)
-                            if ((uint32_t)l < nt) tail = __fadd_rn(tail, exact_term<MK>(Q[col + l], x[l]));
-                    }
-                }
+            {  // the lane's row of this stage into its chains
+                const uint32_t cs_stage = s;
+                const float* cs_row = st + lane * KC;
+                const int cs_swz = sw;
+#include "ott_exact_finish_stage.inc"
             }
             wave_sync();
         }
-        float sc = __fadd_rn(reduce8(acc, p.reduce), tail);
-        if (p.metric == OTT_METRIC_COSINE) sc = __fmul_rn(__fmul_rn(sc, qinv[0]), vinv);
-        const bool pass = valid && !(sc != sc) && cmp_holds(sc, p.cmp, p.thr);
-        const uint64_t key = ((uint64_t)ord_of(sc, take_max) << 32) | (uint32_t)(~(my_row + p.tie_off));
-        if (fresh[0]) {
-            wl_fill_sorted(L[0], tk[0], tq[0], p.k, pass, key, p.q0, lane, p.tie_sh);
-            fresh[0] = false;
-        } else if constexpr (!BLK) {
-            wl_offer(L[0], tk[0], tq[0], p.k, pass, key, p.q0, lane, p.tie_sh);
-        } else {
-            wl_offer_block(L[0], tk[0], tq[0], p.k, pass, key, p.q0, lane, p.tie_sh);
+#include "ott_exact_finish_offer.inc"
+    };
+    // FEW: the first n <= FF_MAX_ROWS queued rows as rounds (ott_finish_few.h): the eight instructions of a round ask for S = 8 / G
+    // stages of the n rows (G = 1 row group of eight, or 2), so a row of 24 stages is 3 or 6 round trips instead of 24.  The same
+    // bytes by the same clamps — a slot past a short row, a piece past ld, a row past n re-reading the first — and one more: a stage
+    // past the last reads the last one and is not consumed.  The round lands where pq_finish puts its eight instructions, which
+    // makes the stage buffer S slabs of 8 G rows; a lane walks its row's slabs in stage order through the same stage code
+    // (ott_exact_finish_stage.inc), so every chain sees the same terms in the same order
+    [[maybe_unused]] auto pq_finish_few = [&](uint32_t n) __attribute__((always_inline)) {
+        wave_sync();
+        const bool valid = (uint32_t)lane < n;
+        const uint32_t e = (pq_head + (valid ? (uint32_t)lane : 0u)) & (PQ_CAP - 1);
+        float acc[8];
+#pragma unroll
+        for (int l = 0; l < 8; l++) acc[l] = pq[l * PQ_CAP + e];
+        const float vinv = pq[8 * PQ_CAP + e];
+        const uint32_t my_row = pq_row[e];
+        float tail = 0.0f;
+        const uint32_t S = ff_stages(n);
+        const float* rp[2];
+        bool rok[2];
+#pragma unroll
+        for (int g = 0; g < 2; g++) {  // rows past n re-read the first queued row (never offered)
+            const uint32_t i = 8 * g + lrow;
+            rok[g] = i < n;
+            rp[g] = p.rows + (uint64_t)pq_row[(pq_head + (rok[g] ? i : 0u)) & (PQ_CAP - 1)] * p.ld + ff_slot_off((uint32_t)lslot, p.ld);
         }
-        pq_head = (pq_head + n) & (PQ_CAP - 1);
-        pq_n -= n;
-        tails_done += n;
+        v4f R[8];
+        auto load_round = [&](uint32_t s0) __attribute__((always_inline)) {
+#pragma unroll
+            for (int m = 0; m < 8; m++) {
+                const uint32_t sc = ff_stage_clamp(s0 + ff_load_slab(m, n), nstages);
+                R[m] = __builtin_nontemporal_load(reinterpret_cast<const v4f*>((ff_load_group(m, n) ? rp[1] : rp[0]) + ff_col_off(sc, (uint32_t)lslot, p.ld)));
+            }
+        };
+        load_round(pstage);
+        const uint32_t li = (uint32_t)lane & (8u * ff_groups(n) - 1u);  // (a lane past the slab's rows walks one of them: never offered)
+        for (uint32_t s0 = pstage; s0 < nstages; s0 += S) {
+#pragma unroll
+            for (int m = 0; m < 8; m++) {
+                const bool cok = ff_col_ok(s0 + ff_load_slab(m, n), (uint32_t)lslot, p.ld);
+                const bool ok = (ff_load_group(m, n) ? rok[1] : rok[0]) & cok;
+                const v4f v = R[m];
+                *reinterpret_cast<float4*>(st + ff_store_off(m, (uint32_t)lrow, (uint32_t)lslot)) =
+                    make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
+            }
+            wave_sync();
+            if (s0 + S < nstages) load_round(s0 + S);
+            for (uint32_t sl = 0; sl < S && s0 + sl < nstages; sl++) {  // slab sl: stage s0 + sl
+                const uint32_t brow = ff_read_off(li, n, sl, 0u) / KC;  // (slot 0 of a row: the row's base, its swizzle from the row)
+                const uint32_t cs_stage = s0 + sl;
+                const float* cs_row = st + brow * KC;
+                const int cs_swz = (int)((brow >> 1) & 7u);
+#include "ott_exact_finish_stage.inc"
+            }
+            wave_sync();
+        }
+#include "ott_exact_finish_offer.inc"
+    };
+    // n queued rows by the finish that fits them; the estimate pass queues at most p.seed_keep <= FF_MAX_ROWS and has no other
+    [[maybe_unused]] auto pq_finish_any = [&](uint32_t n) __attribute__((always_inline)) {
+        if constexpr (FEW && SEED) {
+            pq_finish_few(n);
+        } else if constexpr (FEW) {
+            if (n <= FF_MAX_ROWS) pq_finish_few(n);
+            else pq_finish(n);
+        } else {
+            pq_finish(n);
+        }
     };
     // CHK: the first n <= 64 queued rows on the int8 plane, as one tile.  The rows that stay are moved to the front of the n (their
     // accumulators are zero like everyone's in the head form: only the inverse norm and the row move); returns how many stay
@@ -423,7 +473,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
     // list changes in pq_finish only).  While it is open nothing can be dropped and the rows are finished as without the check
     [[maybe_unused]] auto pq_drain = [&](uint32_t n, uint32_t gate) __attribute__((always_inline)) {
         const uint32_t stay = gate != 0 ? pq_refine(n, gate) : n;
-        if (stay) pq_finish(stay);
+        if (stay) pq_finish_any(stay);
         pq_head = (pq_head + (n - stay)) & (PQ_CAP - 1);
         pq_n -= n - stay;
     };
@@ -593,7 +643,7 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
                 // (64 survivors: about one tile in seventy at the headline's rate.  What was asked for ahead is asked for again behind
                 // the finish instead of being kept across it: its 38 registers would sit on top of the finish's own staging registers)
                 if constexpr (CHK) pq_drain(64, gate);
-                else pq_finish(64);
+                else if constexpr (!SEED) pq_finish(64);
                 if (pf) {
                     load_line(row0n, cntn, 0);
                     load_head(row0n, cntn);
@@ -1079,7 +1129,11 @@ __global__ __launch_bounds__(SMALL ? 64 : 256) void exact_kernel(ExactParams p) 
             if (tails_done != 0) atomicAdd(p.prune_tails + 1, (unsigned long long)tails_done);
         }
     } else if constexpr (PRUNE) {
-        if (pq_n) pq_finish(pq_n);  // (< 64 left)
+        if (pq_n) {  // (< 64 left; without the narrow finish the wide one is called directly, not through pq_finish_any: the wrapper
+                     // moved a few registers in the head form's E = 2 and E = 4 kernels, this way they compile to the code they had)
+            if constexpr (FEW) pq_finish_any(pq_n);
+            else pq_finish(pq_n);
+        }
         if (p.prune_tails != nullptr && tails_done != 0 && lane == 0) atomicAdd(p.prune_tails, (unsigned long long)tails_done);
     }
     if (DUMP) {

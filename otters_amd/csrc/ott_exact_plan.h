@@ -234,6 +234,8 @@ inline bool prune_plan_i8_check(const PruneIn& in, const PrunePlan& pp, bool hea
 #endif
 constexpr uint64_t SEED_EST_MIN_ROWS = 131072;
 constexpr uint32_t SEED_EST_KEEP_MAX = 16;
+// (the estimate pass has the narrow finish only, which takes at most sixteen rows: ott_exact.hip pq_finish_few, ott_finish_few.h FF_MAX_ROWS)
+static_assert(OTT_X_SEED_KEEP <= 16, "the estimate pass finishes at most sixteen rows per wave");
 inline uint64_t prune_plan_seed_est(const PruneIn& in, const PrunePlan& pp, bool head, bool filtered) {
     // (the seed before prune_plan rounds it up to whole tiles: a tenth of 1 310 656 rows is not yet 131 072)
     if (!OTT_X_SEED_EST || !head || in.E != 1 || filtered || pp.c == 0 || in.rows_scored / 10 < SEED_EST_MIN_ROWS) return 0;
