@@ -332,6 +332,8 @@ uint64_t ott_store_exact_finished(const ott_store* s);
  *   in HBM for the fuse kernel or returns them to the host first; environment preset OTT_FUSE_DEVICE),
  *   "sparse_table" (-1 auto, the default / 0 the LDS form wherever eligible / 1 always the device table: where ott_query_sparse's
  *   kernel looks the query's weights up; environment preset OTT_SPARSE_TABLE),
+ *   "sparse_df_lds" (-1 auto, the default / 0 global atomic adds / 1 a histogram in LDS wherever the vocab fits: how
+ *   ott_store_sparse_df's kernel counts; environment preset OTT_SPARSE_DF_LDS),
  *   "large_k_from" (k above which host-output queries take the sort path; 0 = default: 512 for one query or a small store,
  *   128 for several queries on a large one), "small_sort" (0: results of up to 16384 (row, query) pairs with k > 512 through
  *   the radix sort instead of the rank sort), "mfma_f32" (batch path: one candidate pass on the f32 matrix pipe),
@@ -538,7 +540,8 @@ int ott_query_boost(ott_store* s, const ott_query_desc* d, uint32_t combine, flo
  * stages.  Stats: the first stage's (path_used, passes, bytes_scanned, ...); merge_ns carries the fuse kernel's event time on top;
  * total_ns is the whole call.
  * OUT OF SCOPE: a mask, filter or metric per leg (legs with their own filters are ott_query_masks' business; combining the two is a
- * later change); multi-GPU stores; nested prefetches; legs that are stored rows. */
+ * later change); multi-GPU stores; nested prefetches; legs that are stored rows.  (Sparse legs beside the dense ones:
+ * ott_query_hybrid, below the sparse vectors.) */
 typedef enum { OTT_FUSE_RRF = 0, OTT_FUSE_DBSF = 1, OTT_FUSE_MINMAX = 2 } ott_fusion;
 #define OTT_FUSE_MAX_LEGS 16
 #define OTT_FUSE_MAX_FETCH 512
@@ -951,7 +954,8 @@ int ott_query_sharded(ott_store* s, ott_comm* c, const ott_query_desc* d, ott_hi
  * allows (<= 32768; one query per pass), 1 always a device table (four queries per pass).  Both give the same bits.
  * stats: path_used = OTT_PATH_EXACT, passes, vectors_compared = the rows the chunk mask leaves per query, bytes_scanned = the
  * layout bytes of the slices those rows lie in, per pass.
- * Out of scope: dense and sparse legs in one ott_query_fuse call, IDF / BM25 weighting on the device, vocabularies above 2^20 or
+ * Out of scope: BM25's term-frequency saturation and length normalisation (the caller stores those values; the collection statistic
+ * is ott_store_sparse_df, dense and sparse legs in one fusion are ott_query_hybrid, both below), vocabularies above 2^20 or
  * hashed 32-bit token ids (the caller remaps), multi-GPU stores, reordering rows to cut padding, compaction with sparse rows. */
 #define OTT_SPARSE_MAX_VOCAB 1048576 /* 2^20 */
 #define OTT_SPARSE_MAX_QUERIES 1024
@@ -964,6 +968,68 @@ int ott_store_read_sparse(const ott_store* s, uint64_t first_row, uint64_t n_row
 int ott_query_sparse(ott_store* s, const ott_query_desc* d, const uint64_t* q_indptr /* [d->nq + 1] */,
                      const void* q_indices /* uint32_t[] */, const float* q_values,
                      ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats);
+
+/* ---- document frequencies and IDF query weights (Qdrant's sparse vector `modifier: idf`) -------------------
+ * ott_store_sparse_df: df_out[i] (uint32_t[vocab], may be NULL) = the LIVE rows (not deleted) whose sparse row stores index i (a
+ * stored value of 0.0 counts); *n_docs_out (may be NULL) = the live rows, rows without entries included.  A collection statistic:
+ * chunk masks and row masks play no part.  One kernel pass over the index array of the sliced-ELL layout (wave per slice, lane =
+ * row, a slice without a live row is not read), integer adds: in a histogram private to the workgroup in LDS where the vocab fits
+ * (<= 32768), flushed with one atomic add per non-zero bin, or with global atomic adds for any vocab; both give the same words.
+ * Store option "sparse_df_lds": -1 automatic (the LDS form where it fits), 0 never, 1 wherever it fits.  The counts are CACHED on
+ * the device and on the host and rebuilt by the first call that needs them after ott_store_set_sparse, ott_store_clear_sparse,
+ * ott_store_delete_rows, ott_store_restore_rows or ott_store_compact; concurrent callers see one build.
+ * ott_store_sparse_df_builds: how many times they were built.  OTT_ERR_INVALID: no sparse rows are set, or rows were appended
+ * since; OTT_ERR_UNSUPPORTED: a multi-GPU store.
+ * IDF: idf(i) = (float) log(1.0 + (n_docs - df[i] + 0.5) / (df[i] + 0.5)), f64 with the C library's log, every operation rounded,
+ * rounded once to f32.  ott_query_sparse_idf takes ott_query_sparse's arguments and returns exactly ott_query_sparse's hits for
+ * the weights fl32(weight * idf(index)) (one f32 multiplication, on the host); its messages name ott_query_sparse_idf.  A scaled
+ * weight that is not finite is refused like a weight that is not — the one refusal behind device work: the counts are built
+ * first where they are stale.  tests/hybrid_ref.py is the normative model, ott_sparse_plan.h states the formula in C. */
+int ott_store_sparse_df(ott_store* s, void* df_out /* uint32_t[vocab] or NULL */, uint64_t* n_docs_out);
+uint64_t ott_store_sparse_df_builds(const ott_store* s);
+int ott_query_sparse_idf(ott_store* s, const ott_query_desc* d, const uint64_t* q_indptr /* [d->nq + 1] */,
+                         const void* q_indices /* uint32_t[] */, const float* q_values,
+                         ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats);
+
+/* ---- hybrid search: dense and sparse legs fused per request ------------------------------------------------
+ * ott_query_fuse with sparse legs beside the dense ones (Qdrant's prefetch + fusion, Elasticsearch's rrf retriever over kNN and
+ * sparse_vector, Weaviate's hybrid).  The normative statement is the numpy model tests/hybrid_ref.py.
+ * d is the dense side exactly as in ott_query_fuse: d->queries holds the dense legs of request 0, then of request 1, ...; d->nq
+ * their total (0: no dense stage runs and d->queries is not read); metric, take, filter, chunk mask, row mask or evaluated mask,
+ * path; d->mode OTT_MODE_PER_QUERY; d->k = fused hits per request.  dense_per_request[b] and sparse_per_request[b] (uint32_t
+ * [n_requests], either may hold zeros; NULL where the side has no leg at all) say how many legs of each kind request b has; the
+ * sparse queries are CSR as ott_query_sparse takes them, request 0's first.
+ * LEGS of request b: its dense legs in the caller's order, then its sparse legs in the caller's order; 1 to OTT_FUSE_MAX_LEGS in
+ * all, legs x min(fetch, rows) at most OTT_FUSE_MAX_ENTRIES.  leg_weights ([d->nq + n_sparse] or NULL = all 1) follows that order,
+ * request by request.
+ * A DENSE LEG'S LIST is ott_query_fuse's: ott_query's hits for that vector with k = min(fetch, rows), on every path.
+ * A SPARSE LEG'S LIST is ott_query_sparse's hits for that query with k = min(fetch, rows), take Max, the filter sparse_cmp /
+ * sparse_thr (an ott_cmp; OTT_CMP_NONE = no filter: the filter in d acts on the dense legs only), the same chunk mask, row mask
+ * and live mask as the dense legs, and — with OTT_HYBRID_IDF in sparse_flags — the weights scaled as ott_query_sparse_idf does.
+ * The sparse stage is the sweep whatever d->path says.  A list may be shorter than fetch, or empty.
+ * CONTRIBUTION, FUSED SCORE and RANKING are ott_query_fuse's, word for word, with one difference: MINMAX and DBSF normalise a leg
+ * under THAT LEG'S take — d->take for a dense leg, Max for a sparse leg (a squared-L2 leg beside a sparse dot leg is the ordinary
+ * case).  A call without sparse legs returns exactly ott_query_fuse's hits.
+ * Both stages run on one query context under one shared lock; both kinds of list go up in one copy as the blocks the fuse kernel
+ * reads, with one take byte per leg.  Stats: path_used is the dense stage's (OTT_PATH_EXACT without one); passes, bytes_scanned and
+ * vectors_compared are the sums of both stages; merge_ns carries the fuse kernel's event time on top; total_ns is the whole call.
+ * Refused on the host before any device work, with nothing written, each with its own message (ott_hybrid_plan.h): what
+ * ott_query_fuse refuses, the leg count being dense plus sparse; per-request counts that do not add up to d->nq or n_sparse; an
+ * unknown sparse_cmp or flag; and what ott_query_sparse refuses for the sparse side — no sparse rows set, rows appended since, an
+ * index at or above the vocab or twice in a query, a weight that is not finite, more than OTT_SPARSE_MAX_QUERIES sparse legs,
+ * a multi-GPU store, and tie orders 1 and 2 (for the whole call, whether or not a sparse leg exists).  An empty store is a valid
+ * call with no hits.  One refusal comes behind device work: with OTT_HYBRID_IDF the document frequencies are built where they are
+ * stale (ott_store_sparse_df's kernel) before a scaled weight that is not finite is refused; nothing is written then either.
+ * OUT OF SCOPE: a metric, mask or fetch per leg; nested prefetches; legs that are stored rows; multi-GPU stores; a device route
+ * for the lists; IDF restricted to a filtered subset. */
+#define OTT_HYBRID_IDF 1u
+int ott_query_hybrid(ott_store* s, const ott_query_desc* d, const void* dense_per_request /* uint32_t[n_requests] */,
+                     const uint64_t* sq_indptr /* [n_sparse + 1] */, const void* sq_indices /* uint32_t[] */, const float* sq_values,
+                     uint32_t n_sparse, const void* sparse_per_request /* uint32_t[n_requests] */,
+                     uint32_t sparse_cmp /* ott_cmp */, float sparse_thr, uint32_t sparse_flags,
+                     uint32_t n_requests, uint32_t fusion /* ott_fusion */, float rrf_k,
+                     const float* leg_weights /* [d->nq + n_sparse] or NULL = all 1 */, uint64_t fetch,
+                     ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_request, ott_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,7 @@ FUSE_MAX_REQUESTS = 1024      # OTT_FUSE_MAX_REQUESTS
 FUSE_RRF, FUSE_DBSF, FUSE_MINMAX = 0, 1, 2           # ott_fusion
 SPARSE_MAX_VOCAB = 1 << 20    # OTT_SPARSE_MAX_VOCAB
 SPARSE_MAX_QUERIES = 1024     # OTT_SPARSE_MAX_QUERIES
+HYBRID_IDF = 1                # OTT_HYBRID_IDF (ott_query_hybrid's sparse_flags)
 
 _lib = None
 
@@ -216,6 +217,10 @@ def lib() -> C.CDLL:
         "ott_store_sparse_info": (i32, [vp, vp, vp, vp, vp]),
         "ott_store_read_sparse": (i32, [vp, u64, u64, vp, vp, vp, u64]),
         "ott_query_sparse": (i32, [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
+        "ott_store_sparse_df": (i32, [vp, vp, vp]),
+        "ott_store_sparse_df_builds": (u64, [vp]),
+        "ott_query_sparse_idf": (i32, [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
+        "ott_query_hybrid": (i32, [vp, vp, vp, vp, vp, vp, u32, vp, u32, C.c_float, u32, u32, u32, C.c_float, vp, u64, vp, u64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

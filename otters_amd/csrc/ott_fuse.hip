@@ -9,6 +9,12 @@
 // every run of equal rows in leg order, a second bitonic sort by the fused score, the best min(k, rows) written out.
 // Host decisions (refusals, capacity, layout, key packing, padded counts, route) and the host statement of the formulas:
 // ott_fuse_plan.h.
+//
+// ott_query_hybrid is the same second stage over two kinds of first stage on one context: the dense legs through
+// query_on, the sparse legs through ott_sparse.hip's sweep, both kinds of list laid out as the one block the kernel reads (a
+// request's dense legs, then its sparse legs) and uploaded in one copy.  The kernel normalises every leg under that leg's own take
+// (FuseParams::leg_take_max: a byte per leg behind the weights; nullptr = the call's take, which is what ott_query_fuse passes).
+// Host decisions: ott_hybrid_plan.h.
 #include <string.h>
 
 #include <algorithm>
@@ -17,6 +23,7 @@
 
 #include "ott_internal.h"
 #include "ott_fuse_plan.h"
+#include "ott_hybrid_plan.h"
 
 namespace ott {
 
@@ -30,6 +37,7 @@ struct FuseParams {
     uint64_t base_offset, n_rows;
     uint32_t stride, kout, fusion, take_max;
     float rrf_k;
+    const uint8_t* leg_take_max;  // [nq] 1 = the leg's list is best first under take Max; nullptr = take_max for every leg (ott_query_fuse)
 };
 
 // Bitonic network over key[0 .. P) (P a power of two >= 64), ascending or descending; PAYLOAD: con[] moves with its key.  Thread t of
@@ -75,6 +83,7 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_kernel(FuseParams p) {
     if (p.fusion != FUSE_RRF) {
         for (uint32_t l = wave; l < legs; l += n_waves) {
             const ott_hit* list = p.blocks + (size_t)(first + l) * p.stride;
+            const bool lmax = p.leg_take_max ? p.leg_take_max[first + l] != 0 : tmax;  // the leg's own take (ott_query_hybrid)
             uint32_t n = 0;
             for (uint32_t i = lane; i < p.stride; i += 64) n += list[i].index != ~0ull ? 1u : 0u;
 #pragma unroll
@@ -83,7 +92,7 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_kernel(FuseParams p) {
             if (n != 0 && p.fusion == FUSE_MINMAX) {
                 const double best = (double)list[0].score;
                 worst = (double)list[n - 1].score;
-                span = tmax ? __dsub_rn(best, worst) : __dsub_rn(worst, best);
+                span = lmax ? __dsub_rn(best, worst) : __dsub_rn(worst, best);
             } else if (n != 0) {
                 const double dn = (double)n;
                 double a = 0.0;
@@ -101,7 +110,7 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_kernel(FuseParams p) {
                 const double var = __ddiv_rn(__shfl(a, 0), dn);
                 const double sd3 = __dmul_rn(3.0, __dsqrt_rn(var));
                 const double lo = __dsub_rn(mean, sd3), hi = __dadd_rn(mean, sd3);
-                worst = tmax ? lo : hi;
+                worst = lmax ? lo : hi;
                 span = __dsub_rn(hi, lo);
             }
             if (lane == 0) {
@@ -129,7 +138,8 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_kernel(FuseParams p) {
                     const double span = sSpan[l];
                     if (span > 0.0) {
                         const double s = (double)h.score, worst = sWorst[l];
-                        nrm = __double2float_rn(__ddiv_rn(tmax ? __dsub_rn(s, worst) : __dsub_rn(worst, s), span));
+                        const bool lmax = p.leg_take_max ? p.leg_take_max[first + l] != 0 : tmax;
+                        nrm = __double2float_rn(__ddiv_rn(lmax ? __dsub_rn(s, worst) : __dsub_rn(worst, s), span));
                     }
                     c = __fmul_rn(w, nrm);
                 }
@@ -215,7 +225,8 @@ void fill_meta(const FuseCall& c, const FuseLayout& L, char* base) {
     for (uint32_t l = 0; l < c.d->nq; l++) w[l] = c.weights ? c.weights[l] : 1.0f;
 }
 
-int launch_fuse(ott_store* s, const FuseCall& c, const FuseLayout& L) {
+// off_take: where the legs' take bytes lie in the scratch (ott_query_hybrid), 0 = every leg ranks under the call's take
+int launch_fuse(ott_store* s, const FuseCall& c, const FuseLayout& L, size_t off_take = 0) {
     char* dm = (char*)s->d_fuse.p;
     FuseParams p;
     memset(&p, 0, sizeof(p));
@@ -232,6 +243,7 @@ int launch_fuse(ott_store* s, const FuseCall& c, const FuseLayout& L) {
     p.fusion = c.fusion;
     p.take_max = c.d->take == OTT_TAKE_MAX;
     p.rrf_k = c.rrf_k;
+    p.leg_take_max = off_take ? (const uint8_t*)(dm + off_take) : nullptr;
     const uint32_t padded = fuse_padded(c.max_legs * (uint32_t)c.stride);  // the network of the call's largest request
     const size_t smem = fuse_lds_bytes(padded);
     if (smem > 48 * 1024) {  // more dynamic LDS than the default limit: the opt-in, once per device
@@ -245,6 +257,9 @@ int launch_fuse(ott_store* s, const FuseCall& c, const FuseLayout& L) {
     OTT_HIP(hipGetLastError());
     return OTT_OK;
 }
+
+int fuse_second_stage(ott_store* s, const FuseCall& c, const FuseLayout& L, size_t off_take, bool events_pending, ott_hit* out, uint64_t* n_out,
+                      uint64_t* n_per_request, ott_stats* st, bool timing, const char* who);
 
 // Both stages on a context the caller holds.
 int run_fuse(ott_store* s, const FuseCall& c, ott_hit* out, uint64_t* n_out, uint64_t* n_per_request, ott_stats* st, bool timing) {
@@ -284,8 +299,17 @@ int run_fuse(ott_store* s, const FuseCall& c, ott_hit* out, uint64_t* n_out, uin
         fill_meta(c, L, hs);
         OTT_HIP(hipMemcpyAsync(dm, hs, L.upload_bytes, hipMemcpyHostToDevice, s->stream));
     }
+    return fuse_second_stage(s, c, L, 0, events_pending, out, n_out, n_per_request, st, timing, "ott_query_fuse");
+}
+
+// The second stage behind the upload: the kernel, the fused hits back, the one host wait.  c.legs: every request's legs.
+int fuse_second_stage(ott_store* s, const FuseCall& c, const FuseLayout& L, size_t off_take, bool events_pending, ott_hit* out, uint64_t* n_out,
+                      uint64_t* n_per_request, ott_stats* st, bool timing, const char* who) {
+    int rc;
+    const ott_query_desc* d = c.d;
+    char* dm = (char*)s->d_fuse.p;
     if (timing) OTT_HIP(hipEventRecord(s->ev[0], s->stream));
-    if ((rc = launch_fuse(s, c, L))) return rc;
+    if ((rc = launch_fuse(s, c, L, off_take))) return rc;
     if (timing) OTT_HIP(hipEventRecord(s->ev[1], s->stream));
     if ((rc = s->h_hits.ensure(L.result_bytes))) return rc;
     OTT_HIP(hipMemcpyAsync(s->h_hits.p, dm + L.off_counts, L.result_bytes, hipMemcpyDeviceToHost, s->stream));
@@ -300,13 +324,121 @@ int run_fuse(ott_store* s, const FuseCall& c, ott_hit* out, uint64_t* n_out, uin
     uint64_t total = 0;
     for (uint32_t b = 0; b < c.n_requests; b++) {
         const uint32_t nb = counts[b];
-        if (nb > fuse_request_cap(d->k, c.legs[b], c.stride)) return fail(OTT_ERR_HIP, "ott_query_fuse: the kernel returned more hits than a request can have");
+        if (nb > fuse_request_cap(d->k, c.legs[b], c.stride)) return fail(OTT_ERR_HIP, std::string(who) + ": the kernel returned more hits than a request can have");
         if (nb) memcpy(out + total, hits + (size_t)b * L.kout, (size_t)nb * sizeof(ott_hit));
         if (n_per_request) n_per_request[b] = nb;
         total += nb;
     }
     if (n_out) *n_out = total;
     return OTT_OK;
+}
+
+int hybrid_fail(HybridRefusal r, uint64_t bad, uint64_t v) { return fail(hybrid_refusal_status(r), hybrid_refusal_text(r, bad, v)); }
+
+// ott_query_hybrid's arguments past the checks
+struct HybridCall {
+    const ott_query_desc* d;  // the dense side; d->k = fused hits per request
+    const uint32_t *dense_per, *sparse_per;
+    const uint64_t* sq_indptr;
+    const uint32_t* sq_idx;
+    const float* sq_val;  // (already scaled where OTT_HYBRID_IDF is set)
+    uint32_t n_sparse, sparse_cmp;
+    float sparse_thr;
+    uint32_t n_requests, fusion;
+    float rrf_k;
+    const float* weights;
+    uint64_t stride;
+};
+
+// a stage's lists (`per[i]` hits of query i back to back in `cand`) into the blocks of the legs `leg_at` names
+int hybrid_place(const ott_store* s, const HybridCall& h, char* blocks, const std::vector<ott_hit>& cand, const std::vector<uint64_t>& per, const uint32_t* leg_at) {
+    size_t at = 0;
+    for (size_t i = 0; i < per.size(); i++) {
+        if (per[i] > h.stride) return fail(OTT_ERR_HIP, "ott_query_hybrid: a leg returned more hits than fetch");
+        for (uint64_t j = 0; j < per[i]; j++)
+            if (cand[at + j].index - s->base_offset >= s->n) return fail(OTT_ERR_HIP, "ott_query_hybrid: a leg returned a row outside the store");
+        if (per[i]) memcpy(blocks + ((size_t)leg_at[i] * h.stride) * sizeof(ott_hit), &cand[at], (size_t)per[i] * sizeof(ott_hit));
+        at += per[i];
+    }
+    return OTT_OK;
+}
+
+// The dense stage (query_on), the sparse stage (run_sparse_sweep) and the fuse kernel on one context the caller holds: the host route.
+int run_hybrid(ott_store* s, const HybridCall& h, ott_hit* out, uint64_t* n_out, uint64_t* n_per_request, ott_stats* st, bool timing) {
+    int rc;
+    OTT_HIP(use_device(s));
+    const ott_query_desc* d = h.d;
+    const uint32_t nd = d->nq, ns = h.n_sparse, legs = nd + ns;
+    std::vector<uint32_t> first(h.n_requests), total(h.n_requests), dense_at(nd), sparse_at(ns);
+    const uint32_t max_legs = hybrid_leg_order(h.dense_per, h.sparse_per, h.n_requests, first.data(), total.data(), dense_at.data(), sparse_at.data());
+    const HybridLayout L = hybrid_layout(legs, h.n_requests, h.stride, d->k, max_legs);
+    if ((rc = s->d_fuse.ensure(L.f.total))) return rc;
+    if ((rc = s->h_fuse.ensure(L.f.upload_bytes))) return rc;
+    char* hs = (char*)s->h_fuse.p;  // (no stage touches h_fuse: the lists are placed as they arrive)
+    memset(hs, 0xFF, L.f.block_bytes);
+    ott_stats* st1 = timing ? st : nullptr;
+    st->path_used = OTT_PATH_EXACT;  // (what a call without a dense stage reports)
+    if (nd) {
+        ott_query_desc d1 = *d;
+        d1.k = h.stride;  // a dense leg's list: ott_query's hits with k = min(fetch, rows)
+        std::vector<ott_hit> cand((size_t)nd * h.stride);
+        std::vector<uint64_t> per(nd, 0);
+        uint64_t n_cand = 0;
+        if ((rc = query_on(s, &d1, cand.data(), nullptr, cand.size(), &n_cand, per.data(), nullptr, st1))) return rc;
+        if ((rc = hybrid_place(s, h, hs, cand, per, dense_at.data()))) return rc;
+    }
+    if (ns) {
+        ott_query_desc d2 = *d;  // the same chunk mask, row mask or evaluated mask; the live mask is the store's
+        d2.queries = nullptr;
+        d2.nq = ns;
+        d2.metric = OTT_METRIC_DOT;
+        d2.take = OTT_TAKE_MAX;
+        d2.filter_cmp = h.sparse_cmp;
+        d2.filter_thr = h.sparse_thr;
+        d2.mode = OTT_MODE_PER_QUERY;
+        d2.path = OTT_PATH_EXACT;
+        RunPlan rp;
+        make_run_plan(s, d->chunk_mask, rp);
+        const uint64_t k_eff = h.stride < rp.rows_scored ? h.stride : rp.rows_scored;  // a list never outgrows the pool
+        d2.k = k_eff;
+        if (k_eff) {
+            std::vector<ott_hit> cand((size_t)ns * k_eff);
+            std::vector<uint64_t> per(ns, 0);
+            uint64_t n_cand = 0;
+            ott_stats st2;
+            memset(&st2, 0, sizeof(st2));
+            rc = run_sparse_sweep(s, &d2, h.sq_indptr, h.sq_idx, h.sq_val, k_eff, cand.data(), &n_cand, per.data(), timing ? &st2 : nullptr);
+            if (rc) {
+                (void)hipStreamSynchronize(s->stream);  // nothing of this call is in flight when the context is given back
+                return rc;
+            }
+            if ((rc = hybrid_place(s, h, hs, cand, per, sparse_at.data()))) return rc;
+            if (timing) {  // the sums of both stages
+                st->passes += st2.passes;
+                st->bytes_scanned += st2.bytes_scanned;
+                st->vectors_compared += st2.vectors_compared;
+                st->score_ns += st2.score_ns;
+                st->merge_ns += st2.merge_ns;
+                if (!nd) {
+                    st->total_chunks = st2.total_chunks;
+                    st->evaluated_chunks = st2.evaluated_chunks;
+                    st->pruned_chunks = st2.pruned_chunks;
+                }
+            }
+        }
+    }
+    // the one upload: [blocks | first | legs | weights | take]
+    memcpy(hs + L.f.off_first, first.data(), (size_t)h.n_requests * 4);
+    memcpy(hs + L.f.off_legs, total.data(), (size_t)h.n_requests * 4);
+    float* w = (float*)(hs + L.f.off_weights);
+    for (uint32_t l = 0; l < legs; l++) w[l] = h.weights ? h.weights[l] : 1.0f;
+    uint8_t* tk = (uint8_t*)(hs + L.off_take);
+    memset(tk, 0, L.f.upload_bytes - L.off_take);
+    for (uint32_t i = 0; i < nd; i++) tk[dense_at[i]] = d->take == OTT_TAKE_MAX;  // a dense leg is best first under d->take
+    for (uint32_t j = 0; j < ns; j++) tk[sparse_at[j]] = 1;                       // a sparse leg under take Max
+    OTT_HIP(hipMemcpyAsync((char*)s->d_fuse.p, hs, L.f.upload_bytes, hipMemcpyHostToDevice, s->stream));
+    const FuseCall c{d, total.data(), h.n_requests, h.fusion, h.rrf_k, h.weights, h.stride, max_legs};
+    return fuse_second_stage(s, c, L.f, L.off_take, false, out, n_out, n_per_request, st, timing, "ott_query_hybrid");
 }
 
 }  // namespace
@@ -344,6 +476,78 @@ int ott_query_fuse(ott_store* s, const ott_query_desc* d, const void* legs_per_r
     ott_stats st;
     memset(&st, 0, sizeof(st));
     if ((rc = run_fuse(ctx.c, c, out, n_out, n_per_request, &st, stats != nullptr))) return rc;
+    st.total_ns = now_ns() - t0;
+    if (stats) *stats = st;
+    return OTT_OK;
+}
+
+int ott_query_hybrid(ott_store* s, const ott_query_desc* d, const void* dense_per_request, const uint64_t* sq_indptr, const void* sq_indices, const float* sq_values,
+                     uint32_t n_sparse, const void* sparse_per_request, uint32_t sparse_cmp, float sparse_thr, uint32_t sparse_flags, uint32_t n_requests,
+                     uint32_t fusion, float rrf_k, const float* leg_weights, uint64_t fetch, ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_request,
+                     ott_stats* stats) {
+    if (!d) return fail(OTT_ERR_INVALID, "ott_query_hybrid: desc is NULL");
+    const uint32_t* dense_per = (const uint32_t*)dense_per_request;
+    const uint32_t* sparse_per = (const uint32_t*)sparse_per_request;
+    const uint32_t* sq_idx = (const uint32_t*)sq_indices;
+    uint64_t bad = 0, v = 0;
+    HybridRefusal why = hybrid_check_args(d->mode == OTT_MODE_PER_QUERY, dense_per, sparse_per, n_requests, d->nq, n_sparse, fetch, fusion, rrf_k, leg_weights, d->k,
+                                          sparse_cmp, OTT_CMP_EQ, sparse_flags, sq_indptr, sq_idx, sq_values, &bad, &v);  // before the store is looked at
+    if (why != HYBRID_OK) return hybrid_fail(why, bad, v);
+    int rc;
+    if (d->nq) {
+        if ((rc = validate_query(s, d))) return rc;  // what ott_query refuses
+    } else {  // no dense leg: d->queries is not read
+        if (!s) return fail(OTT_ERR_INVALID, "ott_query_hybrid: store is NULL");
+        if ((rc = check_desc_enums("ott_query_hybrid", d))) return rc;
+        if ((rc = check_device_row_mask("ott_query_hybrid", s, d))) return rc;
+    }
+    if (s->multi) return hybrid_fail(HYBRID_MULTI_GPU, 0, 0);  // (the front of a multi-GPU store holds no rows)
+    const uint64_t len = ott_store_len(s);
+    const auto zero_outputs = [&] {
+        if (n_out) *n_out = 0;
+        if (n_per_request)
+            for (uint32_t b = 0; b < n_requests; b++) n_per_request[b] = 0;
+        if (stats) memset(stats, 0, sizeof(*stats));
+    };
+    const uint64_t t0 = now_ns();
+    if (len == 0) {  // an empty store: a valid call with no hits
+        if (!out && cap) return hybrid_fail(HYBRID_NULL_OUT, 0, 0);
+        zero_outputs();
+        return OTT_OK;
+    }
+
+    ott::host::SharedLock rd;  // the corpus, the sparse rows and the live mask cannot change between the stages
+    if ((rc = lock_store_shared(s, rd))) return rc;
+    if ((why = hybrid_check_store(false, len, s->opt.tie_order)) != HYBRID_OK) return hybrid_fail(why, 0, 0);
+    if (n_sparse) {  // ott_query_sparse's own checks, under this entry point's name
+        uint64_t a = 0, b = 0;
+        SparseRefusal r = sparse_check_store(false, s->d_sparse != nullptr, s->sparse_n, s->n, s->opt.tie_order, &a, &b);
+        if (r == SPARSE_OK) r = sparse_check_query(n_sparse, sq_indptr, sq_idx, sq_values, s->sparse_vocab, &a, &b);
+        if (r != SPARSE_OK) return hybrid_fail(hybrid_from_sparse(r), a, b);
+    }
+    const uint64_t stride = fuse_stride(fetch, len);
+    uint64_t need = 0;
+    for (uint32_t b = 0; b < n_requests; b++) need += fuse_request_cap(d->k, (dense_per ? dense_per[b] : 0) + (sparse_per ? sparse_per[b] : 0), stride);
+    if (cap < need) return hybrid_fail(HYBRID_CAP, 0, 0);
+    if (!out && cap) return hybrid_fail(HYBRID_NULL_OUT, 0, 0);
+
+    CtxLease ctx(s);  // one query context for every stage
+    std::vector<float> scaled;
+    if ((sparse_flags & HYBRID_IDF) && n_sparse && sq_indptr[n_sparse] != 0) {
+        // the query weights times idf on the host (the document frequencies are built where they are stale)
+        if ((rc = sparse_df_ensure(ctx.c))) return rc;
+        scaled.resize(sq_indptr[n_sparse]);
+        sparse_idf_scale(s, sq_idx, sq_values, sq_indptr[n_sparse], scaled.data());
+        uint64_t a = 0, b = 0;
+        const SparseRefusal r = sparse_check_query(n_sparse, sq_indptr, sq_idx, scaled.data(), s->sparse_vocab, &a, &b);
+        if (r != SPARSE_OK) return hybrid_fail(hybrid_from_sparse(r), a, b);
+        sq_values = scaled.data();
+    }
+    zero_outputs();
+    const HybridCall h{d, dense_per, sparse_per, sq_indptr, sq_idx, sq_values, n_sparse, sparse_cmp, sparse_thr, n_requests, fusion, rrf_k, leg_weights, stride};
+    ott_stats st;
+    memset(&st, 0, sizeof(st));
+    if ((rc = run_hybrid(ctx.c, h, out, n_out, n_per_request, &st, stats != nullptr))) return rc;
     st.total_ns = now_ns() - t0;
     if (stats) *stats = st;
     return OTT_OK;

@@ -95,9 +95,9 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  TWENTY-SIX of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  TWENTY-SEVEN of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, exact_sketch_head, exact_i8_check, id_gather, group_gather, masks_sweep, fuse_device, sparse_table, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, exact_sketch_head, exact_i8_check, id_gather, group_gather, masks_sweep, fuse_device, sparse_table, sparse_df_lds, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
@@ -179,6 +179,7 @@ struct Options {
                                   // more than a small store's whole query); 0 = always split evenly over all shards
     int fuse_device = -1;         // rank fusion (ott_query_fuse): -1 = automatic (ott_fuse_plan.h: the host route), 0 = always the host route (the legs'
                                   // lists come back to the host and go up in one copy), 1 = the device route wherever it is eligible
+    int sparse_df_lds = -1;       // document frequencies (ott_store_sparse_df): -1 = automatic (ott_sparse_plan.h: sparse_df_take_lds), 0 = global atomics always, 1 = a histogram in LDS wherever the vocab fits
     int sparse_table = -1;        // sparse queries (ott_query_sparse): where the weight lookup reads from: -1 = automatic (ott_sparse_plan.h),
                                   // 0 = the LDS form wherever it is eligible (vocab <= 32768), 1 = always the device table form
 };
@@ -432,6 +433,18 @@ struct ott_store {
     ott::DevBuf d_spq, d_sptable;
     ott::PinBuf h_spq;
     bool sptable_clean = false;
+    // Document frequencies of the sparse rows (ott_sparse.hip: sparse_df_ensure), owner store only.  sparse_gen
+    // counts what moves them — the sparse rows set or dropped, rows deleted or restored, the live mask replaced — and changes only
+    // under `rw` exclusive.  df_gen: the sparse_gen the cache below was built for (0 = never); d_df [vocab] words on the device,
+    // df_host the same words on the host, df_ndocs the live rows.  The first call that needs them and finds df_gen != sparse_gen
+    // rebuilds them on ITS context's stream under df_mu (the caller holds `rw` shared), so concurrent queries see one build.
+    uint64_t sparse_gen = 1;
+    std::mutex df_mu;
+    uint64_t df_gen = 0;
+    uint32_t* d_df = nullptr;
+    std::vector<uint32_t> df_host;
+    uint64_t df_ndocs = 0;
+    std::atomic<uint64_t> df_builds{0};
 };
 
 namespace ott {
@@ -827,6 +840,15 @@ int group_grow(ott_store* s, uint64_t ncap);
 int group_ids_of_hits(ott_store* s, const ott_hit* hits, uint64_t n, uint32_t* out);  // the groups of hits of this store: a gather from the resident ids
 void group_drop(ott_store* s);
 void sparse_drop(ott_store* s);  // ott_sparse.hip: the sparse rows go (the caller holds the store exclusively, on its device)
+// ott_sparse.hip, for ott_query_hybrid (ott_fuse.hip).  run_sparse_sweep: the sparse sweep on a context whose `mu` the caller holds
+// (and the owner's `rw`, shared); k_eff = min(k, rows the chunk mask leaves) >= 1, the queries checked against the store's vocab.
+// sparse_df_ensure: the owner's document frequencies are those of the sparse rows and the live mask as they are now (built on
+// ctx's stream when they are not).  sparse_idf_scale: out[e] = fl32(q_val[e] * idf(q_idx[e])) from the cache sparse_df_ensure left.
+int run_sparse_sweep(ott_store* s, const ott_query_desc* d, const uint64_t* q_indptr, const uint32_t* q_idx, const float* q_val, uint64_t k_eff, ott_hit* out,
+                     uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats_out);
+int sparse_df_ensure(ott_store* ctx);
+void sparse_idf_scale(const ott_store* own, const uint32_t* q_idx, const float* q_val, uint64_t q_nnz, float* out);
+inline void sparse_df_stale(ott_store* s) { s->sparse_gen++; }  // the caller holds the store exclusively
 void make_run_plan(const ott_store* s, const uint64_t* chunk_mask, RunPlan& pl);
 // id_span: the low key words are ~id with id < id_span (0 = the store's rows, what a grouped query's keys hold; a late-interaction
 // query's hold group ids)

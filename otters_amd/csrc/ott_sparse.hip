@@ -21,9 +21,15 @@
 //                         NaN drop and the filter: a (query, row) pair has one writer, a plain store.  The table is d_gtable.
 //   GroupTopK             grouped search's top-k with one "group" per row: pass() after every sweep, finish() once — one host wait.
 //
-// Out of scope: dense and sparse legs fused in one ott_query_fuse call (the shared row ids make it a follow-up), IDF / BM25
-// weighting on the device, vocabularies above 2^20 or hashed 32-bit token ids (the caller remaps), multi-GPU stores, reordering
-// rows to cut padding, compaction with sparse rows resident.
+//   sparse_df_kernel      document frequencies: one pass over the index array alone, the same geometry, integer adds into
+//                         a histogram in LDS (vocab <= 32768) or straight into HBM; cached per store, rebuilt by whoever needs the
+//                         counts first after the sparse rows or the live mask changed (sparse_df_ensure).  IDF query weights are
+//                         made from them on the host (ott_query_sparse_idf), and the scaled query runs through the unchanged sweep.
+//
+// Dense and sparse legs fused per request: ott_query_hybrid (ott_fuse.hip), which calls run_sparse_sweep.
+// Out of scope: BM25's term-frequency saturation and length normalisation (the caller stores those values), vocabularies above 2^20
+// or hashed 32-bit token ids (the caller remaps), multi-GPU stores, reordering rows to cut padding, compaction with sparse rows
+// resident.
 #include <string.h>
 
 #include <algorithm>
@@ -186,7 +192,67 @@ __global__ __launch_bounds__(256) void sparse_scatter_kernel(const uint64_t* __r
     }
 }
 
+// Document frequencies: one pass over the index array with sparse_walk's geometry — wave per slice, lane = row, the
+// entry loads guarded by the row's length, a slice without a live row not read.  df[i] += 1 for every stored index i of a live row:
+// integer adds, so the words do not depend on the order of arrival.  LDS: the workgroup counts in a histogram of its own
+// ([vocab_pad] words of dynamic LDS) and adds every non-zero bin to df once at the end; otherwise every entry is a global atomic.
+struct SparseDfParams {
+    const uint32_t* idx;   // [padded]
+    const uint64_t* base;  // [n_slices + 1]
+    const uint32_t* len;   // [n_slices * 64]
+    const uint64_t* live;  // the live mask, word t = the rows of slice t; nullptr = every row is live
+    uint32_t n_slices;
+    uint64_t n_rows;
+    uint32_t* df;          // [vocab], zero when the kernel starts
+    uint32_t vocab, vocab_pad;
+};
+
+constexpr int SP_DF_WAVES = 16;
+constexpr int SP_DF_U = 8;  // index loads a lane has in flight
+
+template <bool LDS>
+__global__ __launch_bounds__(64 * SP_DF_WAVES) void sparse_df_kernel(SparseDfParams p) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t df_lds[];
+    if (LDS) {
+        for (uint32_t i = threadIdx.x; i < p.vocab_pad; i += blockDim.x) df_lds[i] = 0u;
+        __syncthreads();
+    }
+    uint32_t* bins = LDS ? df_lds : p.df;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t nw = gridDim.x * SP_DF_WAVES;
+    for (uint32_t t = blockIdx.x * SP_DF_WAVES + wave; t < p.n_slices; t += nw) {
+        const uint64_t row = (uint64_t)t * 64 + lane;
+        bool valid = row < p.n_rows;
+        if (p.live != nullptr && valid) valid = (p.live[t] >> lane) & 1;  // (word t exists: t < ceil(n_rows / 64) <= the mask's words)
+        if (__ballot(valid) == 0) continue;  // no live row: the slice is not read
+        const uint32_t len = valid ? p.len[row] : 0u;
+        const uint32_t* ip = p.idx + p.base[t] + lane;  // entry e of this lane's row: + 64 e, below base[t + 1] while e < len <= L_t
+        for (uint32_t e0 = 0; e0 < len; e0 += SP_DF_U) {
+            uint32_t ci[SP_DF_U];
+#pragma unroll
+            for (int u = 0; u < SP_DF_U; u++) ci[u] = e0 + u < len ? __builtin_nontemporal_load(ip + (uint64_t)(e0 + u) * 64) : 0u;
+#pragma unroll
+            for (int u = 0; u < SP_DF_U; u++)
+                if (e0 + u < len && ci[u] < p.vocab) atomicAdd(&bins[ci[u]], 1u);  // (every stored index is below vocab: set_sparse checked it)
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < p.vocab; i += blockDim.x) {
+            const uint32_t c = df_lds[i];
+            if (c) atomicAdd(&p.df[i], c);
+        }
+    }
+}
+
 void sparse_drop(ott_store* s) {
+    if (s->d_df) (void)hipFree(s->d_df);
+    s->d_df = nullptr;
+    s->df_host.clear();
+    s->df_host.shrink_to_fit();
+    s->df_gen = 0;
+    s->df_ndocs = 0;
+    sparse_df_stale(s);
     if (s->d_sparse) (void)hipFree(s->d_sparse);
     s->d_sparse = nullptr;
     s->sparse_n = 0;
@@ -280,6 +346,8 @@ int launch_sparse_lds(ott_store* s, const SparseParams& p, uint32_t vocab) {
     OTT_HIP(hipGetLastError());
     return OTT_OK;
 }
+
+}  // namespace
 
 // The sparse sweep on a context whose `mu` the caller holds (and the owner's `rw`, shared).  k_eff = min(k, rows the chunk mask
 // leaves) >= 1.  The layout is the owner's; the queries were checked against its vocab.
@@ -390,7 +458,59 @@ int run_sparse_sweep(ott_store* s, const ott_query_desc* d, const uint64_t* q_in
     return OTT_OK;
 }
 
-}  // namespace
+// The owner's document frequencies are those of the sparse rows and the live mask as they are now.  The caller holds the owner's
+// `rw` shared (sparse_gen cannot move) and ctx's `mu`; the build runs on ctx's stream under the owner's df_mu and is waited for,
+// so whoever finds df_gen == sparse_gen afterwards reads finished words.
+int sparse_df_ensure(ott_store* ctx) {
+    ott_store* own = ctx->owner ? ctx->owner : ctx;
+    std::lock_guard<std::mutex> g(own->df_mu);
+    if (own->df_gen == own->sparse_gen) return OTT_OK;
+    OTT_HIP(use_device(ctx));
+    const uint32_t vocab = own->sparse_vocab;
+    const SparseLayout& lay = own->sparse_lay;
+    if (!own->d_df) OTT_HIP(hipMalloc((void**)&own->d_df, (size_t)vocab * 4));
+    OTT_HIP(hipMemsetAsync(own->d_df, 0, (size_t)vocab * 4, ctx->stream));
+    if (lay.n_slices && lay.padded_entries) {
+        SparseDfParams p{};
+        p.idx = (const uint32_t*)own->d_sparse;
+        p.base = (const uint64_t*)(own->d_sparse + lay.off_bases);
+        p.len = (const uint32_t*)(own->d_sparse + lay.off_lengths);
+        p.live = own->d_live;
+        p.n_slices = (uint32_t)lay.n_slices;
+        p.n_rows = own->sparse_n;
+        p.df = own->d_df;
+        p.vocab = vocab;
+        p.vocab_pad = sparse_vocab_pad(vocab);
+        if (sparse_df_take_lds(own->opt.sparse_df_lds, vocab)) {
+            const size_t smem = sparse_df_lds_bytes(vocab);
+            if (smem > 48 * 1024) {  // more dynamic LDS than the default limit: the opt-in, once per device
+                static std::atomic<uint64_t> attr_set{0};
+                if (attr_needed(attr_set, ctx->device)) {
+                    OTT_HIP(hipFuncSetAttribute((const void*)sparse_df_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)sparse_df_lds_bytes(SPARSE_LDS_MAX_VOCAB)));
+                    attr_done(attr_set, ctx->device);
+                }
+            }
+            const uint32_t grid = grid_blocks(p.n_slices, SP_DF_WAVES, ctx->n_cu, 1);
+            hipLaunchKernelGGL(sparse_df_kernel<true>, dim3(grid), dim3(64 * SP_DF_WAVES), smem, ctx->stream, p);
+        } else {
+            const uint32_t grid = grid_blocks(p.n_slices, SP_DF_WAVES, ctx->n_cu, 2);
+            hipLaunchKernelGGL(sparse_df_kernel<false>, dim3(grid), dim3(64 * SP_DF_WAVES), 0, ctx->stream, p);
+        }
+        OTT_HIP(hipGetLastError());
+    }
+    own->df_host.assign(vocab, 0u);
+    OTT_HIP(hipMemcpyAsync(own->df_host.data(), own->d_df, (size_t)vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
+    OTT_HIP(hipStreamSynchronize(ctx->stream));
+    own->df_ndocs = own->sparse_n - own->n_dead;
+    own->df_gen = own->sparse_gen;
+    own->df_builds.fetch_add(1, std::memory_order_relaxed);
+    return OTT_OK;
+}
+
+void sparse_idf_scale(const ott_store* own, const uint32_t* q_idx, const float* q_val, uint64_t q_nnz, float* out) {
+    for (uint64_t e = 0; e < q_nnz; e++) out[e] = sparse_idf_weight(q_val[e], sparse_idf(own->df_ndocs, own->df_host[q_idx[e]]));
+}
 
 }  // namespace ott
 
@@ -486,18 +606,21 @@ int ott_store_read_sparse(const ott_store* cs, uint64_t first_row, uint64_t n_ro
     return OTT_OK;
 }
 
-int ott_query_sparse(ott_store* s, const ott_query_desc* d, const uint64_t* q_indptr, const void* q_indices_void, const float* q_values, ott_hit* out, uint64_t cap,
-                     uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats) {
-    const uint32_t* q_indices = (const uint32_t*)q_indices_void;
-    if (!d) return fail(OTT_ERR_INVALID, "ott_query_sparse: desc is NULL");
+// ott_query_sparse (idf = false) and ott_query_sparse_idf: the same checks, the same sweep; with idf the weights are scaled on the
+// host first (the document frequencies are built where they are stale: the one piece of device work in front of the last refusal)
+static int query_sparse(ott_store* s, const ott_query_desc* d, const uint64_t* q_indptr, const uint32_t* q_indices, const float* q_values, bool idf, ott_hit* out,
+                        uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats) {
+    const char* who = idf ? "ott_query_sparse_idf" : "ott_query_sparse";  // the entry point the messages name
+    const auto refuse = [who](SparseRefusal r, uint64_t a, uint64_t b) { return fail(sparse_refusal_status(r), sparse_refusal_text(r, a, b, who)); };
+    if (!d) return fail(OTT_ERR_INVALID, std::string(who) + ": desc is NULL");
     int rc;
-    if (d->nq != 0 && (rc = check_desc_enums("ott_query_sparse", d))) return rc;
+    if (d->nq != 0 && (rc = check_desc_enums(who, d))) return rc;
     // what the arguments alone decide comes first: these refusals need no store
     uint64_t a = 0, b = 0;
     SparseRefusal r = sparse_check_query_args(d->nq, d->mode, d->metric, d->path, q_indptr, q_indices, q_values, &a);
     if (r != SPARSE_OK) return refuse(r, a, 0);
-    if (!s) return fail(OTT_ERR_INVALID, "ott_query_sparse: store is NULL");
-    if ((rc = check_device_row_mask("ott_query_sparse", s, d))) return rc;
+    if (!s) return fail(OTT_ERR_INVALID, std::string(who) + ": store is NULL");
+    if ((rc = check_device_row_mask(who, s, d))) return rc;
     const uint32_t nq = d->nq;
     if (s->multi) return refuse(SPARSE_Q_MULTI_GPU, 0, 0);  // (the front of a multi-GPU store holds no rows)
 
@@ -509,7 +632,18 @@ int ott_query_sparse(ott_store* s, const ott_query_desc* d, const uint64_t* q_in
     make_run_plan(s, d->chunk_mask, rp);
     const uint64_t k_eff = d->k < rp.rows_scored ? d->k : rp.rows_scored;  // a list never outgrows the pool
     if ((r = sparse_check_cap(cap, nq, k_eff, s->n)) != SPARSE_OK) return refuse(r, 0, 0);
-    if (!out && cap) return fail(OTT_ERR_INVALID, "ott_query_sparse: out is NULL");
+    if (!out && cap) return fail(OTT_ERR_INVALID, std::string(who) + ": out is NULL");
+    std::vector<float> scaled;
+    if (idf && q_indptr[nq] != 0) {
+        scaled.resize(q_indptr[nq]);
+        {
+            CtxLease lease(s);
+            if ((rc = sparse_df_ensure(lease.c))) return rc;
+        }
+        sparse_idf_scale(s, q_indices, q_values, q_indptr[nq], scaled.data());
+        if ((r = sparse_check_query(nq, q_indptr, q_indices, scaled.data(), s->sparse_vocab, &a, &b)) != SPARSE_OK) return refuse(r, a, b);
+        q_values = scaled.data();
+    }
     if (n_out) *n_out = 0;
     if (n_per_query) memset(n_per_query, 0, (size_t)nq * sizeof(uint64_t));
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -523,5 +657,36 @@ int ott_query_sparse(ott_store* s, const ott_query_desc* d, const uint64_t* q_in
     }
     return rc;
 }
+
+int ott_query_sparse(ott_store* s, const ott_query_desc* d, const uint64_t* q_indptr, const void* q_indices, const float* q_values, ott_hit* out, uint64_t cap,
+                     uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats) {
+    return query_sparse(s, d, q_indptr, (const uint32_t*)q_indices, q_values, false, out, cap, n_out, n_per_query, stats);
+}
+
+int ott_query_sparse_idf(ott_store* s, const ott_query_desc* d, const uint64_t* q_indptr, const void* q_indices, const float* q_values, ott_hit* out, uint64_t cap,
+                         uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats) {
+    return query_sparse(s, d, q_indptr, (const uint32_t*)q_indices, q_values, true, out, cap, n_out, n_per_query, stats);
+}
+
+int ott_store_sparse_df(ott_store* s, void* df_out, uint64_t* n_docs_out) {
+    if (!s) return fail(OTT_ERR_INVALID, "ott_store_sparse_df: store is NULL");
+    if (s->multi) return fail(OTT_ERR_UNSUPPORTED, "ott_store_sparse_df: a multi-GPU store is not served (sparse rows live on one GPU)");
+    int rc;
+    ott::host::SharedLock rd;  // the sparse rows and the live mask cannot change while the call runs
+    if ((rc = lock_store_shared(s, rd))) return rc;
+    if (!s->d_sparse) return fail(OTT_ERR_INVALID, "ott_store_sparse_df: no sparse rows are set (ott_store_set_sparse)");
+    if (s->sparse_n != s->n)
+        return fail(OTT_ERR_INVALID, "ott_store_sparse_df: the sparse rows cover " + std::to_string(s->sparse_n) + " rows, the store holds " + std::to_string(s->n) +
+                                         " (rows were appended since ott_store_set_sparse: set them again)");
+    {
+        CtxLease lease(s);
+        if ((rc = sparse_df_ensure(lease.c))) return rc;
+    }
+    if (df_out) memcpy(df_out, s->df_host.data(), (size_t)s->sparse_vocab * 4);
+    if (n_docs_out) *n_docs_out = s->df_ndocs;
+    return OTT_OK;
+}
+
+uint64_t ott_store_sparse_df_builds(const ott_store* s) { return s ? s->df_builds.load(std::memory_order_relaxed) : 0ull; }
 
 }  // extern "C"

@@ -72,9 +72,10 @@ inline int sparse_refusal_status(SparseRefusal r) {
     }
 }
 
-// the message of a refusal; a and b are what the refusal names (a row or query and an entry or index, or two counts)
-inline std::string sparse_refusal_text(SparseRefusal r, uint64_t a, uint64_t b) {
-    const std::string set = "ott_store_set_sparse: ", q = "ott_query_sparse: ", rd = "ott_store_read_sparse: ";
+// the message of a refusal; a and b are what the refusal names (a row or query and an entry or index, or two counts); query_fn: the
+// entry point a query's refusal names (ott_query_sparse_idf makes the same checks under its own name)
+inline std::string sparse_refusal_text(SparseRefusal r, uint64_t a, uint64_t b, const char* query_fn = "ott_query_sparse") {
+    const std::string set = "ott_store_set_sparse: ", q = std::string(query_fn) + ": ", rd = "ott_store_read_sparse: ";
     const std::string A = std::to_string(a), B = std::to_string(b);
     switch (r) {
         case SPARSE_OK: return std::string();
@@ -291,5 +292,30 @@ inline float sparse_score_dense(const uint32_t* idx, const float* val, uint64_t 
     *overlap = any;
     return S;
 }
+
+// ---- document frequencies and IDF weights -----------------------------------------------------------------------------------
+// df[i] = the LIVE rows whose sparse row stores index i (a stored 0.0 counts), n_docs = the live rows.  The kernel counts with integer
+// adds, in a histogram private to the workgroup in LDS (vocab <= 32768: the budget of the sweep's LDS form) or with global atomics
+// (any vocab); both give the same words.  option: the store's sparse_df_lds (-1 automatic, 0 never, 1 wherever it fits).
+// AUTOMATIC is the LDS form wherever it fits, as measured on the MI355X (benchmarks/hybrid.py, profiles/hybrid/README.md: 250k and 1M
+// Zipfian rows of 64 entries, vocab 30522, per build end to end): about 80 us against 19 ms of the global form on 250k rows, about
+// 125 us against 74 ms on 1M rows — ten indices are stored by more than half of those rows, so the global form's adds meet on a few
+// words.  Above 32768 there is no choice.
+inline size_t sparse_df_lds_bytes(uint32_t vocab) { return (size_t)sparse_vocab_pad(vocab) * 4; }
+inline bool sparse_df_take_lds(int option, uint32_t vocab) {
+    if (!sparse_lds_eligible(vocab)) return false;
+    return option != 0;
+}
+// idf(i) = (float) log(1 + (n_docs - df + 0.5) / (df + 0.5)): f64, every operation rounded, the C library's log, one rounding to f32
+inline float sparse_idf(uint64_t n_docs, uint32_t df) {
+    volatile double a = (double)(n_docs - df);  // (df <= n_docs: both count live rows)
+    a = a + 0.5;
+    volatile double b = (double)df + 0.5;
+    volatile double c = a / b;
+    c = 1.0 + c;
+    return (float)log(c);
+}
+// the weight a query entry gets under OTT_HYBRID_IDF: one f32 multiplication
+inline float sparse_idf_weight(float w, float idf) { return sparse_fl(w * idf); }
 
 }  // namespace ott

@@ -28,13 +28,14 @@ struct OptName {
     const char* name;
     int kind;  // 0 = bool, 1 = tri-state (-1 automatic / 0 / 1), 2 = non-negative int
 };
-// the twenty-six options of the product library (see struct Options) ...
+// the twenty-seven options of the product library (see struct Options) ...
 const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"hi_prebuild", 1},          {"stage_appends", 1},       {"multi_transport", 2},
                              {"multi_rebalance", 0}, {"multi_min_shard_rows", 2}, {"exact_small", 1},     {"large_k_from", 2},        {"small_sort", 1},
                              {"mfma_f32", 0},        {"no_hi_pass", 0},      {"no_batch_image", 0},       {"force_fallback", 2},      {"eps_scale_ppm", 2},
                              {"multi_fake_distinct", 0}, {"exact_prune", 1},            {"exact_sketch", 1},
                              {"id_gather", 1},       {"exact_sketch_bits", 2},   {"group_gather", 1},         {"exact_sketch_head", 1},
                              {"masks_sweep", 2},     {"fuse_device", 1},         {"sparse_table", 1},         {"exact_i8_check", 1},
+                             {"sparse_df_lds", 1},
 #ifdef OTT_MFMA_DEBUG_BUILD
                              // ... and, in the diagnostic build only, kernel tuning, timing ablations and every fallback bit by its own name
                              {"mfma_wg", 2},         {"mfma_growth", 2},     {"mfma_debug", 0},           {"mfma_abl", 2},            {"hi_tmin", 2},
@@ -42,11 +43,11 @@ const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"h
                              {"merge_rank1", 1},     {"maxsim_fold", 1},
 #endif
 };
-static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 26
+static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 27
 #ifdef OTT_MFMA_DEBUG_BUILD
                                                             + 12
 #endif
-              , "the product library's option table stays at twenty-six entries");
+              , "the product library's option table stays at twenty-seven entries");
 }  // namespace
 
 int option_set(Options& o, const char* name, long long v) {
@@ -88,6 +89,7 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "group_gather") return tri(o.group_gather);
     if (n == "fuse_device") return tri(o.fuse_device);
     if (n == "sparse_table") return tri(o.sparse_table);
+    if (n == "sparse_df_lds") return tri(o.sparse_df_lds);
     if (n == "masks_sweep") { if (v < 0 || v > 2) return -1; o.masks_sweep = (int)v; return 0; }
 #ifdef OTT_MFMA_DEBUG_BUILD
     if (n == "maxsim_fold") return tri(o.maxsim_fold);
@@ -942,6 +944,7 @@ int ott_store_destroy(ott_store* s) {
         s->d_gix = nullptr;
         s->d_sparse = nullptr;
     }
+    if (s->d_df) (void)hipFree(s->d_df);  // (the owner's alone: a worker builds into the owner's and never holds one)
     if (s->d_sparse) (void)hipFree(s->d_sparse);
     if (s->d_gix) (void)hipFree(s->d_gix);
     if (s->d_live) (void)hipFree(s->d_live);

@@ -162,6 +162,7 @@ int set_live(ott_store* s, bool make_live, const uint64_t* rows_host, uint64_t n
     OTT_HIP(hipStreamSynchronize(s->stream));
     if (make_live) s->n_dead -= changed;
     else s->n_dead += changed;
+    if (changed) sparse_df_stale(s);  // the document frequencies count live rows
     if (n_changed) *n_changed = changed;
     return OTT_OK;
 }
@@ -188,6 +189,7 @@ void live_drop(ott_store* s) {
     if (s->d_live) (void)hipFree(s->d_live);
     s->d_live = nullptr;
     s->n_dead = 0;
+    sparse_df_stale(s);
 }
 
 int live_load(ott_store* s, const uint64_t* words_host) {

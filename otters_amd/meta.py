@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime, parse_datetime_millis
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import GROUP_SIZE_MAX, BoostCombine, BoostTerm, Cmp, DiscoverPlan, FusePlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, SparseQueryPlan, TakeType, VecStore, as_row_ids, boost_args, infer_default_take_type, mmr_args
+from .vec import GROUP_SIZE_MAX, BoostCombine, BoostTerm, Cmp, DiscoverPlan, FusePlan, HybridPlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, SparseQueryPlan, TakeType, VecStore, as_row_ids, boost_args, infer_default_take_type, mmr_args
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -494,6 +494,11 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
         """Rank fusion (VecStore.fuse; ott_query_fuse) with a meta_filter: `leg_sets` is a sequence of [legs, dim] matrices, one per
         request; every leg is ranked under the same filter, then the legs of a request are fused."""
         return MetaFusePlan(self, leg_sets, metric)
+
+    def hybrid(self, dense_sets, sparse_sets, metric: Metric = Metric.Cosine) -> "MetaHybridPlan":
+        """Hybrid search (VecStore.hybrid; ott_query_hybrid) with a meta_filter: one mask for the dense and the sparse legs of every
+        request; .meta_filter(expr).idf().sparse_filter(...).take(k).collect()."""
+        return MetaHybridPlan(self, dense_sets, sparse_sets, metric)
 
     def sparse_query(self, q) -> "MetaSparsePlan":
         """Exact sparse dot search (VecStore.sparse_query; ott_query_sparse) with a meta_filter: `q` is one (indices, values) pair or
@@ -1262,6 +1267,8 @@ class MetaFusePlan(_MetaWrapper):
     masks rows on the device, as for MetaRecommendPlan; it and vec_filter act on every leg before the fusion.  Errors surface at
     collect()."""
 
+    kind = "fuse"  # the word the refusals name, and the VecStore._run_* underneath
+
     def __init__(self, store: MetaStore, leg_sets, metric: Metric):
         super().__init__(store, FusePlan(store._store, leg_sets, metric))
         self.metric = Metric(metric)
@@ -1285,20 +1292,38 @@ class MetaFusePlan(_MetaWrapper):
         if self.meta_error is not None:
             raise OttersError(self.meta_error)
         if self.store._store is None:
-            raise OttersError("fuse: the store holds no vectors")
+            raise OttersError(self.kind + ": the store holds no vectors")
         self._plan.validate()
 
     def collect_arrays(self):
-        """(hits, counts), as FusePlan.collect_arrays returns them."""
+        """(hits, counts), as FusePlan.collect_arrays (HybridPlan.collect_arrays) returns them."""
         self.validate()
         st = self.store
         rf = self._plan.resolve()
-        got = _run_filtered(st, self._meta_filter, rf, "fuse", st._store._run_fuse)
-        return got if got is not None else (np.zeros(0, dtype=N.HIT_DTYPE), [0] * int(rf.legs_per_request.size))
+        got = _run_filtered(st, self._meta_filter, rf, self.kind, getattr(st._store, "_run_" + self.kind))
+        return got if got is not None else (np.zeros(0, dtype=N.HIT_DTYPE), [0] * self._plan.n_requests())
 
     def collect(self):
         """One MetaQueryResults per request: the hits' rows materialised as MetaQueryPlan.collect does, scores = the fused scores."""
         return _materialise(self.store, *self.collect_arrays())
+
+
+class MetaHybridPlan(MetaFusePlan):
+    """Hybrid search over a MetaStore (MetaStore.hybrid; VecStore.hybrid's contract): meta_filter prunes chunks by their zone maps
+    and masks rows on the device, as for MetaFusePlan — ONE mask for both kinds of leg, so the same rows vanish from the dense and
+    the sparse lists; vec_filter acts on the dense legs, sparse_filter on the sparse ones.  Errors surface at collect()."""
+
+    kind = "hybrid"
+
+    def __init__(self, store: MetaStore, dense_sets, sparse_sets, metric: Metric):
+        _MetaWrapper.__init__(self, store, HybridPlan(store._store, dense_sets, sparse_sets, metric))
+        self.metric = Metric(metric)
+
+    def idf(self, on: bool = True) -> "MetaHybridPlan":
+        return self._forward("idf", on)
+
+    def sparse_filter(self, score: float, cmp: Cmp) -> "MetaHybridPlan":
+        return self._forward("sparse_filter", score, cmp)
 
 
 class MetaSparsePlan(_MetaWrapper):
@@ -1307,6 +1332,10 @@ class MetaSparsePlan(_MetaWrapper):
 
     def __init__(self, store: MetaStore, q):
         super().__init__(store, SparseQueryPlan(store._store, q))
+
+    def idf(self, on: bool = True) -> "MetaSparsePlan":
+        """The query weights times idf(index) (SparseQueryPlan.idf): the collection's statistic, whatever the meta_filter keeps."""
+        return self._forward("idf", on)
 
     def collect_arrays(self):
         """(hits, counts), as SparseQueryPlan.collect_arrays returns them."""

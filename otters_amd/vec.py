@@ -1117,7 +1117,62 @@ class ResolvedFuse:
     path: int
 
 
-class FusePlan(_PathScorePlan):
+class _FusionPlan(_PathScorePlan):
+    """What the fusion plans (FusePlan, HybridPlan) share: the fusion and its parameter, the weights, the fetch, the default take."""
+
+    def __init__(self, store: "VecStore", metric: Metric):
+        super().__init__()
+        self.vector_store = store
+        self.search_metric = Metric(metric)
+        self.fusion = Fusion.Rrf
+        self.rrf_k = 60.0
+        self.leg_weights = None
+        self.fetch_count: Optional[int] = None
+
+    def rrf(self, k: float = 60.0):
+        """Reciprocal rank fusion: the entry at position r (0 based) of a leg with weight w contributes w / (k + (r + 1))."""
+        self.fusion, self.rrf_k = Fusion.Rrf, float(k)
+        return self
+
+    def dbsf(self):
+        """Distribution-based score fusion: a leg's scores are normalised by mean -+ 3 sigma of its list (no clamp), times its weight."""
+        self.fusion = Fusion.Dbsf
+        return self
+
+    def min_max(self):
+        """Min-max fusion: a leg's scores are normalised to [0, 1] by its list's worst and best score, times its weight."""
+        self.fusion = Fusion.MinMax
+        return self
+
+    def weights(self, list_of_lists):
+        """One list of weights per request, one weight per leg in the request's leg order (default: all 1)."""
+        self.leg_weights = [list(w) for w in list_of_lists]
+        return self
+
+    def fetch(self, n: int):
+        """Hits every leg contributes (default: max(4 x take, 32), at most 512)."""
+        self.fetch_count = int(n)
+        return self
+
+    def _k(self) -> int:
+        return max(int(self.take_count), 0) if self.take_count is not None else max(len(self.vector_store), 1)
+
+    def _fetch(self) -> int:
+        return self.fetch_count if self.fetch_count is not None else fuse_default_fetch(self._k())
+
+    def _flat_weights_for(self, legs_per_request, what: str):
+        if self.leg_weights is None:
+            return None
+        if len(self.leg_weights) != len(legs_per_request) or any(len(w) != n for w, n in zip(self.leg_weights, legs_per_request)):
+            raise OttersError(what)
+        return [float(x) for w in self.leg_weights for x in w]
+
+    def collect(self):
+        """One list of SearchResult(index, fused score) per request."""
+        return split_results(*self.collect_arrays())
+
+
+class FusePlan(_FusionPlan):
     """Rank fusion (VecStore.fuse; ott_query_fuse): every request brings several query vectors ("legs"); each leg's best `fetch` hits
     — exactly what store.query(leg, metric).per_query().take(fetch) returns under the same filter, masks and path — are merged into
     one ranking per request by reciprocal rank fusion (.rrf(k), the default), distribution-based score fusion (.dbsf()) or min-max
@@ -1126,56 +1181,18 @@ class FusePlan(_PathScorePlan):
     VecQueryPlan: errors surface at validate() / collect()."""
 
     def __init__(self, store: "VecStore", leg_sets, metric: Metric):
-        super().__init__()
-        self.vector_store = store
+        super().__init__(store, metric)
         self.leg_sets = [QueryBatch(t).queries for t in leg_sets]
-        self.search_metric = Metric(metric)
-        self.fusion = Fusion.Rrf
-        self.rrf_k = 60.0
-        self.leg_weights = None
-        self.fetch_count: Optional[int] = None
-
-    def rrf(self, k: float = 60.0) -> "FusePlan":
-        """Reciprocal rank fusion: the entry at position r (0 based) of a leg with weight w contributes w / (k + (r + 1))."""
-        self.fusion, self.rrf_k = Fusion.Rrf, float(k)
-        return self
-
-    def dbsf(self) -> "FusePlan":
-        """Distribution-based score fusion: a leg's scores are normalised by mean -+ 3 sigma of its list (no clamp), times its weight."""
-        self.fusion = Fusion.Dbsf
-        return self
-
-    def min_max(self) -> "FusePlan":
-        """Min-max fusion: a leg's scores are normalised to [0, 1] by its list's worst and best score, times its weight."""
-        self.fusion = Fusion.MinMax
-        return self
-
-    def weights(self, list_of_lists) -> "FusePlan":
-        """One list of weights per request, one weight per leg (default: all 1)."""
-        self.leg_weights = [list(w) for w in list_of_lists]
-        return self
-
-    def fetch(self, n: int) -> "FusePlan":
-        """Hits every leg contributes (default: max(4 x take, 32), at most 512)."""
-        self.fetch_count = int(n)
-        return self
 
     def filter(self, score: float, cmp: Cmp) -> "FusePlan":
         """The score filter acts on a leg's own score: it is part of the leg, as VecQueryPlan.filter."""
         return super().filter(score, cmp)
 
-    def _k(self) -> int:
-        return max(int(self.take_count), 0) if self.take_count is not None else max(len(self.vector_store), 1)
-
-    def _fetch(self) -> int:
-        return self.fetch_count if self.fetch_count is not None else fuse_default_fetch(self._k())
+    def n_requests(self) -> int:
+        return len(self.leg_sets)
 
     def _flat_weights(self):
-        if self.leg_weights is None:
-            return None
-        if len(self.leg_weights) != len(self.leg_sets) or any(len(w) != len(t) for w, t in zip(self.leg_weights, self.leg_sets)):
-            raise OttersError("fuse: weights takes one list per request with one weight per leg")
-        return [float(x) for w in self.leg_weights for x in w]
+        return self._flat_weights_for([len(t) for t in self.leg_sets], "fuse: weights takes one list per request with one weight per leg")
 
     def validate(self) -> None:
         st = self.vector_store
@@ -1209,10 +1226,6 @@ class FusePlan(_PathScorePlan):
         store.last_stats = stats
         return hits, counts
 
-    def collect(self):
-        """One list of SearchResult(index, fused score) per request."""
-        return split_results(*self.collect_arrays())
-
 
 SPARSE_MAX_VOCAB = 1 << 20      # include/otters_hip.h: OTT_SPARSE_MAX_VOCAB
 SPARSE_MAX_QUERIES = 1024       # include/otters_hip.h: OTT_SPARSE_MAX_QUERIES
@@ -1236,6 +1249,11 @@ def sparse_csr(rows):
             np.concatenate(val) if val else np.zeros(0, np.float32))
 
 
+def is_one_sparse_query(q) -> bool:
+    """whether `q` is ONE (indices, values) pair, not a sequence of them"""
+    return isinstance(q, tuple) and len(q) == 2 and not (len(q[0]) and isinstance(q[0][0], (tuple, list, np.ndarray)))
+
+
 @dataclass
 class ResolvedSparse:
     """What SparseQueryPlan hands to ott_query_sparse once it is validated."""
@@ -1249,6 +1267,7 @@ class ResolvedSparse:
     row_mask: Optional[np.ndarray]
     path: int
     metric: int = int(Metric.DotProduct)  # a sparse score is a dot product
+    idf: bool = False                     # ott_query_sparse_idf: the weights times idf(index)
 
 
 class SparseQueryPlan(_PathScorePlan):
@@ -1260,8 +1279,14 @@ class SparseQueryPlan(_PathScorePlan):
         super().__init__()
         self.vector_store = store
         self.search_metric = Metric.DotProduct  # a sparse score is a dot product: it decides the default take
-        single = isinstance(q, tuple) and len(q) == 2 and not (len(q[0]) and isinstance(q[0][0], (tuple, list, np.ndarray)))
-        self.queries = [q] if single else list(q)
+        self.queries = [q] if is_one_sparse_query(q) else list(q)
+        self.use_idf = False
+
+    def idf(self, on: bool = True) -> "SparseQueryPlan":
+        """Scale every query weight by idf(index) = log(1 + (n_docs - df + 0.5) / (df + 0.5)) over the store's live rows
+        (ott_query_sparse_idf; VecStore.sparse_df returns df and n_docs)."""
+        self.use_idf = bool(on)
+        return self
 
     def resolve(self) -> ResolvedSparse:
         """Lower the plan.  Pure host logic, no GPU; the library checks the queries against the store's vocab."""
@@ -1270,7 +1295,7 @@ class SparseQueryPlan(_PathScorePlan):
         ptr, idx, val = sparse_csr(self.queries)
         take, k, fc, ft = self._lowered(len(self.vector_store))
         return ResolvedSparse(indptr=ptr, indices=idx, values=val, take=take, k=k, filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask,
-                              path=int(self.path))
+                              path=int(self.path), idf=self.use_idf)
 
     def collect_arrays(self):
         """(hits, counts): `hits` a NumPy record array (`index` u64, `score` f32 = S, `query`), every query's list best first, back
@@ -1289,6 +1314,141 @@ class SparseQueryPlan(_PathScorePlan):
         if len(self.queries) != 1:
             raise OttersError("ott_query_sparse: a batch needs OTT_MODE_PER_QUERY (a merged list over several sparse queries is not served)")
         return self.collect_per_query()[0]
+
+
+def hybrid_args(dense_per, sparse_per, fetch: int, fusion: int, rrf_k: float, weights, k: int) -> None:
+    """ott_query_hybrid's argument refusals that the plan can raise (ott_hybrid_plan.h: hybrid_check_args), in its order and with
+    its texts, before any native call."""
+    who = "ott_query_hybrid: "
+    n = len(dense_per)
+    if n == 0:
+        raise OttersError(who + "n_requests must be at least 1")
+    if n > N.FUSE_MAX_REQUESTS:
+        raise OttersError(who + f"{n} requests are above OTT_FUSE_MAX_REQUESTS ({N.FUSE_MAX_REQUESTS})")
+    if not 1 <= fetch <= N.FUSE_MAX_FETCH:
+        raise OttersError(who + f"fetch must lie between 1 and OTT_FUSE_MAX_FETCH ({N.FUSE_MAX_FETCH})")
+    for b, (nd, ns) in enumerate(zip(dense_per, sparse_per)):
+        l = nd + ns
+        if not 1 <= l <= N.FUSE_MAX_LEGS:
+            raise OttersError(who + f"request {b} has {l} legs (dense plus sparse); a request takes 1 to OTT_FUSE_MAX_LEGS ({N.FUSE_MAX_LEGS})")
+        if l * fetch > N.FUSE_MAX_ENTRIES:
+            raise OttersError(who + f"request {b} has {l * fetch} entries (legs x fetch), above OTT_FUSE_MAX_ENTRIES ({N.FUSE_MAX_ENTRIES})")
+    if fusion not in (0, 1, 2):
+        raise OttersError(who + "unknown fusion (OTT_FUSE_RRF, OTT_FUSE_DBSF or OTT_FUSE_MINMAX)")
+    if fusion == int(Fusion.Rrf) and not (np.isfinite(np.float32(rrf_k)) and rrf_k >= 0):
+        raise OttersError(who + "rrf_k must be finite and at least 0")
+    if weights is not None:
+        for l, w in enumerate(weights):
+            if not np.isfinite(np.float32(w)):
+                raise OttersError(who + f"the weight of leg {l} is not finite")
+    if k == 0:
+        raise OttersError(who + "k must be at least 1")
+    if sum(sparse_per) > N.SPARSE_MAX_QUERIES:
+        raise OttersError(who + f"{sum(sparse_per)} sparse legs are above OTT_SPARSE_MAX_QUERIES ({N.SPARSE_MAX_QUERIES})")
+
+
+@dataclass
+class ResolvedHybrid:
+    """What HybridPlan hands to ott_query_hybrid once it is validated."""
+    queries: Optional[np.ndarray]    # [sum of dense legs, dim] f32, or None when no request has one
+    dense_per_request: np.ndarray    # uint32[B]
+    sparse_per_request: np.ndarray   # uint32[B]
+    sq_indptr: np.ndarray            # uint64[n_sparse + 1]
+    sq_indices: np.ndarray           # uint32[]
+    sq_values: np.ndarray            # float32[]
+    sparse_cmp: int
+    sparse_thr: float
+    sparse_flags: int
+    fusion: int
+    rrf_k: float
+    weights: Optional[np.ndarray]    # f32[legs] in a request's own leg order (dense, then sparse), or None = all 1
+    fetch: int
+    metric: int
+    take: int
+    k: int
+    filter_cmp: int
+    filter_thr: float
+    row_mask: Optional[np.ndarray]
+    path: int
+
+
+class HybridPlan(_FusionPlan):
+    """Hybrid search (VecStore.hybrid; ott_query_hybrid): every request brings dense query vectors and sparse queries; each dense
+    leg's best `fetch` hits are what store.query(leg, metric).take(fetch) returns, each sparse leg's what
+    store.sparse_query(q).take(fetch) returns (take Max, under .sparse_filter, with .idf() the weights times idf), all under the
+    same masks; a request's lists — its dense legs first, then its sparse legs — are merged as FusePlan merges them, except that
+    min-max and DBSF normalise every leg under its own take: the metric's take for a dense leg, Max for a sparse one.  filter()
+    acts on the dense legs only.  Lazy like VecQueryPlan: errors surface at validate() / collect()."""
+
+    def __init__(self, store: "VecStore", dense_sets, sparse_sets, metric: Metric):
+        super().__init__(store, metric)
+        dense_sets = [] if dense_sets is None else list(dense_sets)
+        sparse_sets = [] if sparse_sets is None else list(sparse_sets)
+        n = max(len(dense_sets), len(sparse_sets))
+        dense_sets += [None] * (n - len(dense_sets))    # a side that is shorter has no leg in the requests it does not name
+        sparse_sets += [None] * (n - len(sparse_sets))
+        self.dense_sets = [[] if t is None or len(t) == 0 else QueryBatch(t).queries for t in dense_sets]
+        self.sparse_sets = [[] if t is None else [t] if is_one_sparse_query(t) else list(t) for t in sparse_sets]
+        self.use_idf = False
+        self.sparse_filter_criteria: Optional[tuple] = None
+
+    def idf(self, on: bool = True) -> "HybridPlan":
+        """The sparse queries' weights times idf(index) over the store's live rows (OTT_HYBRID_IDF)."""
+        self.use_idf = bool(on)
+        return self
+
+    def sparse_filter(self, score: float, cmp: Cmp) -> "HybridPlan":
+        """The filter on a sparse leg's score; filter() acts on the dense legs only."""
+        self.sparse_filter_criteria = (float(np.float32(score)), Cmp(cmp))
+        return self
+
+    def n_requests(self) -> int:
+        return len(self.dense_sets)
+
+    def _legs(self):
+        return [len(t) for t in self.dense_sets], [len(t) for t in self.sparse_sets]
+
+    def _flat_weights(self):
+        nd, ns = self._legs()
+        return self._flat_weights_for([a + b for a, b in zip(nd, ns)],
+                                      "hybrid: weights takes one list per request with one weight per leg (its dense legs, then its sparse legs)")
+
+    def validate(self) -> None:
+        st = self.vector_store
+        nd, ns = self._legs()
+        hybrid_args(nd, ns, self._fetch(), int(self.fusion), self.rrf_k, self._flat_weights(), self._k())
+        for t in self.dense_sets:
+            for q in ([t[0]] if isinstance(t, np.ndarray) else t):
+                if len(q) != st.dim:
+                    raise OttersError(f"Query vector length {len(q)} does not match expected dimension {st.dim}")
+        if self.path == Path.Mfma and self.search_metric == Metric.Manhattan and sum(nd):
+            raise OttersError("ott_query: the MFMA path does not score the Manhattan metric; use path AUTO or EXACT")
+        if st.devices is not None:
+            raise OttersError("ott_query_hybrid: a multi-GPU store is not served (the legs' lists lie on different GPUs, sparse rows on one)")
+
+    def resolve(self) -> ResolvedHybrid:
+        """Validate and lower the plan.  Pure host logic, no GPU."""
+        self.validate()
+        sets = [t if isinstance(t, np.ndarray) else np.stack(t).astype(np.float32, copy=False) for t in self.dense_sets if len(t)]
+        nd, ns = self._legs()
+        ptr, idx, val = sparse_csr([q for t in self.sparse_sets for q in t])
+        w = self._flat_weights()
+        take, k, fc, ft = self._lowered(max(len(self.vector_store), 1))
+        sc, sthr = (0, 0.0) if self.sparse_filter_criteria is None else (int(self.sparse_filter_criteria[1]), self.sparse_filter_criteria[0])
+        return ResolvedHybrid(queries=np.ascontiguousarray(np.concatenate(sets), dtype=np.float32) if sets else None,
+                              dense_per_request=np.array(nd, dtype=np.uint32), sparse_per_request=np.array(ns, dtype=np.uint32),
+                              sq_indptr=ptr, sq_indices=idx, sq_values=val, sparse_cmp=sc, sparse_thr=sthr,
+                              sparse_flags=N.HYBRID_IDF if self.use_idf else 0, fusion=int(self.fusion), rrf_k=float(self.rrf_k),
+                              weights=None if w is None else np.array(w, dtype=np.float32), fetch=self._fetch(), metric=int(self.search_metric),
+                              take=take, k=k, filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, path=int(self.path))
+
+    def collect_arrays(self):
+        """(hits, counts): `hits` a NumPy record array (`index` u64, `score` f32 = the fused score F, `query` = the request), every
+        request's list best first, back to back in request order; counts[b] = the hits of request b."""
+        store = self.vector_store
+        hits, counts, stats = store._run_hybrid(self.resolve())
+        store.last_stats = stats
+        return hits, counts
 
 
 def query_desc(r, queries: Optional[np.ndarray], nq: int, mode: int, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
@@ -1600,15 +1760,55 @@ class VecStore:
         return SparseQueryPlan(self, q)
 
     def _run_sparse(self, rs: ResolvedSparse, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
-        """ott_query_sparse.  Returns (hits HIT_DTYPE array, per-query counts, stats dict)."""
+        """ott_query_sparse (ott_query_sparse_idf where the plan asked for idf).  Returns (hits HIT_DTYPE array, per-query counts, stats dict)."""
         nq = int(rs.indptr.size - 1)
         cap = max(nq * min(rs.k, self._n), 1)
         out = np.empty(cap, dtype=N.HIT_DTYPE)
         d, keep = query_desc(rs, None, nq, Mode.PerQuery if nq > 1 else Mode.Merged, chunk_mask, use_device_row_mask)
         n_out, per, st = C.c_uint64(0), (C.c_uint64 * max(nq, 1))(), N.Stats()
-        N.check(N.lib().ott_query_sparse(self._handle(), C.byref(d), N.ptr(rs.indptr), N.ptr(rs.indices) if rs.indices.size else None,
-                                         N.ptr(rs.values) if rs.values.size else None, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        fn = N.lib().ott_query_sparse_idf if rs.idf else N.lib().ott_query_sparse
+        N.check(fn(self._handle(), C.byref(d), N.ptr(rs.indptr), N.ptr(rs.indices) if rs.indices.size else None,
+                   N.ptr(rs.values) if rs.values.size else None, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
         return out[: n_out.value].copy(), list(per)[:nq], st.as_dict()
+
+    def sparse_df(self):
+        """(df, n_docs): df[i] (uint32[vocab]) = the live rows whose sparse row stores index i, n_docs = the live rows
+        (ott_store_sparse_df).  Cached on the device; rebuilt after set_sparse, delete_rows, restore_rows."""
+        info = self.sparse_info()
+        if info is None:
+            raise OttersError("ott_store_sparse_df: no sparse rows are set (ott_store_set_sparse)")
+        df, n_docs = np.zeros(info["vocab"], dtype=np.uint32), C.c_uint64(0)
+        N.check(N.lib().ott_store_sparse_df(self._h, N.ptr(df), C.byref(n_docs)))
+        return df, int(n_docs.value)
+
+    def sparse_df_builds(self) -> int:
+        """How many times the document frequencies were built (ott_store_sparse_df_builds)."""
+        return 0 if self._h is None else int(N.lib().ott_store_sparse_df_builds(self._h))
+
+    def hybrid(self, dense_sets, sparse_sets, metric: Metric) -> HybridPlan:
+        """Hybrid search (ott_query_hybrid): `dense_sets` a sequence of [legs, dim] matrices and `sparse_sets` a sequence of lists of
+        (indices, values) pairs, one of each per request (None or empty = no leg of that kind);
+        .rrf() / .dbsf() / .min_max(), .idf(), .sparse_filter(thr, cmp), .fetch(n), .take(k).collect() returns one fused ranking per
+        request."""
+        return HybridPlan(self, dense_sets, sparse_sets, metric)
+
+    def _run_hybrid(self, rh: ResolvedHybrid, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
+        """ott_query_hybrid.  Returns (hits HIT_DTYPE array, per-request counts, stats dict)."""
+        B = int(rh.dense_per_request.size)
+        if self._n == 0:  # an empty store: a valid call with no hits (no native store exists yet)
+            return np.zeros(0, dtype=N.HIT_DTYPE), [0] * B, N.Stats().as_dict()
+        stride = min(rh.fetch, self._n)
+        cap = max(sum(min(rh.k, (int(a) + int(b)) * stride) for a, b in zip(rh.dense_per_request, rh.sparse_per_request)), 1)
+        out = np.empty(cap, dtype=N.HIT_DTYPE)
+        nq = 0 if rh.queries is None else int(rh.queries.shape[0])
+        d, keep = query_desc(rh, rh.queries, nq, Mode.PerQuery, chunk_mask, use_device_row_mask)
+        n_out, per, st = C.c_uint64(0), (C.c_uint64 * B)(), N.Stats()
+        n_sparse = int(rh.sq_indptr.size - 1)
+        N.check(N.lib().ott_query_hybrid(self._handle(), C.byref(d), N.ptr(rh.dense_per_request), N.ptr(rh.sq_indptr),
+                                         N.ptr(rh.sq_indices) if rh.sq_indices.size else None, N.ptr(rh.sq_values) if rh.sq_values.size else None,
+                                         n_sparse, N.ptr(rh.sparse_per_request), rh.sparse_cmp, rh.sparse_thr, rh.sparse_flags, B, rh.fusion, rh.rrf_k,
+                                         N.ptr(rh.weights) if rh.weights is not None else None, rh.fetch, N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        return out[: n_out.value].copy(), list(per), st.as_dict()
 
     def shards(self):
         """[(device, first_row, n_rows)] of the store's shards (one entry for a single-GPU store)."""
@@ -1654,7 +1854,7 @@ class VecStore:
         return int(N.lib().ott_store_exact_finished(self._handle()))
 
     def set_option(self, name: str, value: int) -> None:
-        """Behaviour switch of this store (ott_store_set_option; the twenty-six names are listed in include/otters_hip.h:
+        """Behaviour switch of this store (ott_store_set_option; the twenty-seven names are listed in include/otters_hip.h:
         "tie_order", "hi_fmt", "hi_prebuild", ..., "force_fallback").  Results never depend on any but "tie_order"."""
         self._options[name] = int(value)
         if self._h is not None:
