@@ -3,7 +3,8 @@ MetaStore.sparse_query).  Bar: query b's hits — index, S's f32
 numpy model's (tests/sparse_ref.py: a serial f32 sum in the row's index order, the overlap rule, masks, NaN drop, filter, canonical
 order).  Bit for bit, no tolerances.  Every case that is eligible for both forms of the weight lookup (vocab <= 32768) runs under
 store option sparse_table 0 (a table in LDS) and 1 (a device table), which must agree with the model and so with each other.
-Values and weights are multiples of 1/4, so exact ties and sums that cancel to +0.0 are frequent."""
+Values and weights are multiples of 1/4, so exact ties and sums that cancel to +0.0 are frequent — and every sum is exact, whatever
+its order: the order and the rounding of the sum are held to the model in tests/test_gpu_sparse_rounding.py."""
 import ctypes as C
 import threading
 
