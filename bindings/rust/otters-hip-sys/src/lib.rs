@@ -36,6 +36,8 @@ pub const OTT_FUSE_DBSF: u32 = 1; // scores normalised by mean -+ 3 sigma of the
 pub const OTT_FUSE_MINMAX: u32 = 2; // scores normalised by the leg's worst and best
 pub const OTT_SPARSE_MAX_VOCAB: u32 = 1048576; // ott_store_set_sparse: indices stay below vocab <= 2^20
 pub const OTT_SPARSE_MAX_QUERIES: u32 = 1024; // ott_query_sparse: the most queries of one call
+pub const OTT_BINARY_MAX_BITS: u32 = 16384; // ott_store_set_binary: the most bits of a bit row
+pub const OTT_BINARY_MAX_QUERIES: u32 = 1024; // ott_query_binary: the most queries of one call
 pub const OTT_HYBRID_IDF: u32 = 1; // ott_query_hybrid sparse_flags bit 0: the sparse queries' weights times idf(index)
 pub const OTT_BOOST_SUM: u32 = 0; // ott_boost_combine: F = Sw + B
 pub const OTT_BOOST_MULT: u32 = 1; // F = Sw * (1 + B)
@@ -241,6 +243,13 @@ extern "C" {
     pub fn ott_store_sparse_df_builds(s: *const ott_store) -> u64;
     pub fn ott_query_sparse_idf(s: *mut ott_store, d: *const ott_query_desc, q_indptr: *const u64, q_indices: *const c_void, q_values: *const f32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int; // ott_query_sparse with the weights times idf(index)
     pub fn ott_query_hybrid(s: *mut ott_store, d: *const ott_query_desc, dense_per_request: *const c_void, sq_indptr: *const u64, sq_indices: *const c_void, sq_values: *const f32, n_sparse: u32, sparse_per_request: *const c_void, sparse_cmp: u32, sparse_thr: f32, sparse_flags: u32, n_requests: u32, fusion: u32, rrf_k: f32, leg_weights: *const f32, fetch: u64, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_request: *mut u64, stats: *mut ott_stats) -> c_int; // dense_per_request, sparse_per_request: n_requests u32; a request's dense legs come before its sparse legs
+    pub fn ott_store_set_binary(s: *mut ott_store, words: *const c_void, n: u64, n_bits: u32) -> c_int; // words: n * ceil(n_bits / 64) u64, row-major; bit j of a row = bit j % 64 of word j / 64
+    pub fn ott_store_set_binary_sign(s: *mut ott_store) -> c_int; // bit j of row r = row[j] > 0.0, made on the device
+    pub fn ott_store_clear_binary(s: *mut ott_store) -> c_int;
+    pub fn ott_store_binary_info(s: *const ott_store, n_bits: *mut u32, bytes: *mut u64) -> c_int; // *n_bits 0 = no bit rows
+    pub fn ott_store_read_binary(s: *const ott_store, first_row: u64, n_rows: u64, words_out: *mut c_void) -> c_int; // words_out: n_rows * ceil(n_bits / 64) u64
+    pub fn ott_query_binary(s: *mut ott_store, d: *const ott_query_desc, q_words: *const c_void, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, stats: *mut ott_stats) -> c_int; // d.queries is not read, d.metric = OTT_METRIC_MANHATTAN; q_words: d.nq * ceil(n_bits / 64) u64
+    pub fn ott_store_binary_counters(s: *const ott_store, out: *mut u64) -> c_int; // out: 4 u64: gated calls, pairs emitted, overflows, table-route calls
     pub fn ott_query_mmr(s: *mut ott_store, d: *const ott_query_desc, ids: *const u64, n_ids: u64, fetch_k: u64, lambda: f32, out: *mut ott_hit, cap: u64, n_out: *mut u64, n_per_query: *mut u64, out_values: *mut f32, stats: *mut ott_stats) -> c_int; // ids: null, 0 = no id list; out_values: null or cap floats
     pub fn ott_query_recommend(s: *mut ott_store, d: *const ott_query_desc, positive: *const u64, n_positive: u64, negative: *const u64, n_negative: u64, flags: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, side_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // d.queries null, d.nq 0; side_of_hit: null or cap entries
     pub fn ott_query_recommend_strategy(s: *mut ott_store, d: *const ott_query_desc, strategy: u32, positive: *const u64, n_positive: u64, negative: *const u64, n_negative: u64, flags: u32, out: *mut ott_hit, cap: u64, n_out: *mut u64, side_of_hit: *mut u32, stats: *mut ott_stats) -> c_int; // strategy 0 = ott_query_recommend; 1 / 2: flags 0, side_of_hit all 1

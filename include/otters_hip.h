@@ -334,6 +334,9 @@ uint64_t ott_store_exact_finished(const ott_store* s);
  *   kernel looks the query's weights up; environment preset OTT_SPARSE_TABLE),
  *   "sparse_df_lds" (-1 auto, the default / 0 global atomic adds / 1 a histogram in LDS wherever the vocab fits: how
  *   ott_store_sparse_df's kernel counts; environment preset OTT_SPARSE_DF_LDS),
+ *   "binary_gate" (-1 auto, the default / 0 always the key table / 1 the gated sweep wherever eligible: which route answers
+ *   ott_query_binary; environment preset OTT_BINARY_GATE), "binary_gate_cap" (0, the default: the plan's pair capacity; otherwise
+ *   the gated sweep's capacity in pairs: tests reach the overflow branch with it),
  *   "large_k_from" (k above which host-output queries take the sort path; 0 = default: 512 for one query or a small store,
  *   128 for several queries on a large one), "small_sort" (0: results of up to 16384 (row, query) pairs with k > 512 through
  *   the radix sort instead of the rank sort), "mfma_f32" (batch path: one candidate pass on the f32 matrix pipe),
@@ -1030,6 +1033,56 @@ int ott_query_hybrid(ott_store* s, const ott_query_desc* d, const void* dense_pe
                      uint32_t n_requests, uint32_t fusion /* ott_fusion */, float rrf_k,
                      const float* leg_weights /* [d->nq + n_sparse] or NULL = all 1 */, uint64_t fetch,
                      ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_request, ott_stats* stats);
+
+/* ---- binary vectors: a bit row per stored row, exact Hamming search -----------------------------------------
+ * Row r of a store may carry a bit row of n_bits bits beside its dense one (Milvus' BINARY_VECTOR with HAMMING, the first stage of
+ * Qdrant's and Elasticsearch's binary quantisation, embedders that emit bits).  The rows are attached to the store the way sparse
+ * rows are, so row ids, chunk masks, row masks, the evaluated mask, mask slots and deleted rows mean the same for a dense and a
+ * binary query.  A collection that has only bit rows is a store of dim 1.
+ *
+ * BITS: bit j of a row lies in bit j % 64 of 64-bit word j / 64 (the mask convention of this header); a row is ceil(n_bits / 64)
+ * words, 1 <= n_bits <= OTT_BINARY_MAX_BITS, and the bits at and above n_bits in its last word are zero, in rows and in queries (a
+ * set padding bit is OTT_ERR_INVALID).
+ * ott_store_set_binary: `words` row-major, n == ott_store_len.  Checked on the host before any device work; a refused call changes
+ * nothing.  ott_store_set_binary_sign: n_bits = dim and bit j of row r = (row[j] > 0.0f) in f32 — NaN, -0.0 and +0.0 give 0,
+ * +denormals give 1: Qdrant's binary quantisation — made by a kernel from the dense rows, no host copy; refused where dim >
+ * OTT_BINARY_MAX_BITS.  A second set replaces the first; ott_store_clear_binary drops the rows.  All three take the store
+ * exclusively and flush staged appends first.  While bit rows are set they count as a resident metadata column (ott_store_compact
+ * is refused).  Rows appended afterwards leave the bit rows in place, and a binary query then fails with OTT_ERR_INVALID ("set them
+ * again").  OTT_ERR_UNSUPPORTED on a multi-GPU store.
+ * In HBM the rows lie in slices of 64 rows, transposed: 16-byte unit p of the slice's 64 rows in 64 consecutive units, rows padded
+ * to whole units.  ott_store_binary_info reports n_bits (0 = no bit rows) and the bytes of the layout; ott_store_read_binary
+ * returns the words of a row range from that layout, row-major again, bit for bit.
+ *
+ * ott_query_binary: d->nq queries as q_words (uint64_t[nq * ceil(n_bits / 64)]); d->queries is not read, d->metric must be
+ * OTT_METRIC_MANHATTAN (the Hamming distance is the L1 distance of the bit vectors); take (the default of that metric is Min; Max is
+ * served), filter, k, chunk mask, row mask or evaluated mask mean what they mean in ott_query_sparse.  PER_QUERY, or MERGED with nq
+ * == 1; at most OTT_BINARY_MAX_QUERIES queries; cap >= nq * min(k, rows).
+ * The score (tests/binary_ref.py is the normative model, ott_binary_plan.h states it in C): S = (float) popcount(q XOR v), exact.
+ * Every row the masks leave is a candidate; the filter acts on S; the order is S under `take` with equal S going to the lower row;
+ * hit.score = S, hit.query = b.
+ * OTT_ERR_UNSUPPORTED: OTT_PATH_MFMA (AUTO takes the sweep), tie orders 1 and 2, a multi-GPU store, a store of 2^32 - 16 rows or
+ * more, k_eff > 512 with more than 2^26 (query, row) pairs.
+ * TWO ROUTES, the same bits: the TABLE route writes a key per (query, row) and the shared top-k reads it back; the GATED route
+ * fuses the selection into the sweep (a histogram of distances and a gate per workgroup and query, candidates appended to a pair
+ * list, one sort) and is eligible for k_eff <= 512.  Store option "binary_gate": -1 automatic (ott_binary_plan.h), 0 always the
+ * table, 1 the gated sweep wherever eligible.  The gated sweep's pair list has a capacity ("binary_gate_cap": 0 = the plan's); a
+ * call that emits more is answered by the table route (a second sweep, a second host wait) and counted.
+ * ott_store_binary_counters: out[0] gated calls, out[1] candidate pairs they emitted, out[2] overflows, out[3] table-route calls.
+ * stats: path_used = OTT_PATH_EXACT, passes, vectors_compared = the rows the chunk mask leaves per query, bytes_scanned = the
+ * layout bytes of the slices those rows lie in, per pass (an overflowed call counts both sweeps).
+ * Out of scope: Jaccard / Tanimoto, binary legs in ott_query_fuse or ott_query_hybrid, multi-GPU stores, extending bit rows on
+ * append, compaction with bit rows resident, asymmetric scoring of an f32 query against bit rows. */
+#define OTT_BINARY_MAX_BITS 16384
+#define OTT_BINARY_MAX_QUERIES 1024
+int ott_store_set_binary(ott_store* s, const void* words /* uint64_t[n * ceil(n_bits / 64)] row-major */, uint64_t n, uint32_t n_bits);
+int ott_store_set_binary_sign(ott_store* s);
+int ott_store_clear_binary(ott_store* s);
+int ott_store_binary_info(const ott_store* s, uint32_t* n_bits, uint64_t* bytes);
+int ott_store_read_binary(const ott_store* s, uint64_t first_row, uint64_t n_rows, void* words_out);
+int ott_query_binary(ott_store* s, const ott_query_desc* d, const void* q_words /* uint64_t[d->nq * ceil(n_bits / 64)] */,
+                     ott_hit* out, uint64_t cap, uint64_t* n_out, uint64_t* n_per_query, ott_stats* stats);
+int ott_store_binary_counters(const ott_store* s, uint64_t* out /* [4] */);
 
 #ifdef __cplusplus
 }

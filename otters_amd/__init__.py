@@ -5,7 +5,7 @@ and error strings) over libotters_hip.so: the corpus lives row-major in HBM, sco
 score filtering and top-k run as hand-written HIP kernels.  No CPU fallback.
 """
 from ._native import OttersError  # noqa: F401
-from .vec import (BoostCombine, BoostTerm, Cmp, DiscoverPlan, DiscoverResult, FusePlan, Fusion, HybridPlan, MaxSimBatchPlan, Metric, Mode, Path, QueryBatch, RecommendPlan, RecommendStrategy, SearchResult,  # noqa: F401
+from .vec import (BinaryQueryPlan, BoostCombine, BoostTerm, Cmp, DiscoverPlan, DiscoverResult, FusePlan, Fusion, HybridPlan, MaxSimBatchPlan, Metric, Mode, Path, QueryBatch, RecommendPlan, RecommendStrategy, SearchResult,  # noqa: F401
                   SparseQueryPlan, TakeType, VecQueryPlan, VecStore)
 
 from .col import Column, ColumnError, DataType  # noqa: F401,E402
@@ -15,5 +15,5 @@ from .meta import (MetaBuildStats, MetaQueryPlan, MetaQueryResults, MetaQuerySta
 
 __all__ = ["Column", "ColumnError", "DataType", "CmpOp", "CompiledFilter", "Expr", "ExprError", "col", "lit",
            "MetaBuildStats", "MetaQueryPlan", "MetaQueryResults", "MetaQueryStats", "MetaStore", "MetaStoreBuilder",
-           "OttersError", "BoostCombine", "BoostTerm", "Cmp", "DiscoverPlan", "DiscoverResult", "FusePlan", "Fusion", "HybridPlan", "MaxSimBatchPlan", "Metric", "Mode", "Path", "QueryBatch", "RecommendPlan", "RecommendStrategy", "SearchResult", "SparseQueryPlan", "TakeType",
+           "OttersError", "BinaryQueryPlan", "BoostCombine", "BoostTerm", "Cmp", "DiscoverPlan", "DiscoverResult", "FusePlan", "Fusion", "HybridPlan", "MaxSimBatchPlan", "Metric", "Mode", "Path", "QueryBatch", "RecommendPlan", "RecommendStrategy", "SearchResult", "SparseQueryPlan", "TakeType",
            "VecQueryPlan", "VecStore"]

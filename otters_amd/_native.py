@@ -81,6 +81,8 @@ FUSE_RRF, FUSE_DBSF, FUSE_MINMAX = 0, 1, 2           # ott_fusion
 SPARSE_MAX_VOCAB = 1 << 20    # OTT_SPARSE_MAX_VOCAB
 SPARSE_MAX_QUERIES = 1024     # OTT_SPARSE_MAX_QUERIES
 HYBRID_IDF = 1                # OTT_HYBRID_IDF (ott_query_hybrid's sparse_flags)
+BINARY_MAX_BITS = 16384       # OTT_BINARY_MAX_BITS
+BINARY_MAX_QUERIES = 1024     # OTT_BINARY_MAX_QUERIES
 
 _lib = None
 
@@ -220,6 +222,13 @@ def lib() -> C.CDLL:
         "ott_store_sparse_df": (i32, [vp, vp, vp]),
         "ott_store_sparse_df_builds": (u64, [vp]),
         "ott_query_sparse_idf": (i32, [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp]),
+        "ott_store_set_binary": (i32, [vp, vp, u64, u32]),
+        "ott_store_set_binary_sign": (i32, [vp]),
+        "ott_store_clear_binary": (i32, [vp]),
+        "ott_store_binary_info": (i32, [vp, vp, vp]),
+        "ott_store_read_binary": (i32, [vp, u64, u64, vp]),
+        "ott_query_binary": (i32, [vp, vp, vp, vp, u64, vp, vp, vp]),
+        "ott_store_binary_counters": (i32, [vp, vp]),
         "ott_query_hybrid": (i32, [vp, vp, vp, vp, vp, vp, u32, vp, u32, C.c_float, u32, u32, u32, C.c_float, vp, u64, vp, u64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -24,6 +24,7 @@
 #include "ott_recommend_plan.h"  // recommend-by-example's host-side plan (refusals, example layout, passes, k_eff, the second round, scratch bytes): HIP-free, CPU-tested
 #include "ott_mmr_plan.h"  // MMR re-ranking's host-side plan (refusals, scratch layout, the pair grid, the greedy launch): HIP-free, CPU-tested
 #include "ott_masks_plan.h"  // ott_query_masks' host-side plan (refusals, the queries' order by mask id, the route and its auto rule): HIP-free, CPU-tested
+#include "ott_binary_plan.h"  // bit rows and ott_query_binary's host-side plan (refusals, the transposed slice layout, the route, the gate's LDS and capacity, Hamming in C): HIP-free, CPU-tested
 #include "ott_sparse_plan.h"  // sparse rows and ott_query_sparse's host-side plan (refusals, the sliced-ELL layout, the lookup's form and passes, the score in C): HIP-free, CPU-tested
 #include "ott_sort_plan.h"  // the sort path's host-side plan (pass plans, sweep shape, rank or radix, prefix, slices, group extents, copy pieces): HIP-free, CPU-tested
 #ifdef OTT_DEVICE_AUDIT
@@ -95,9 +96,9 @@ struct PinBuf {
 
 // Behaviour switches of one store.  Read ONCE from the environment (OTT_* variables of the same names, upper case) when
 // the store is created, changed afterwards only through ott_store_set_option: the query path never looks at the
-// environment.  TWENTY-SEVEN of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
+// environment.  TWENTY-NINE of them have a name in the product library (ott_store.hip: kOptNames; round 5 retired the rest):
 // tie_order, hi_fmt, hi_prebuild, stage_appends, multi_transport, multi_rebalance, multi_min_shard_rows — behaviour a host may
-// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, exact_sketch_head, exact_i8_check, id_gather, group_gather, masks_sweep, fuse_device, sparse_table, sparse_df_lds, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
+// want; exact_small, exact_prune, exact_sketch, exact_sketch_bits, exact_sketch_head, exact_i8_check, id_gather, group_gather, masks_sweep, fuse_device, sparse_table, sparse_df_lds, binary_gate, binary_gate_cap, large_k_from, small_sort, mfma_f32, no_hi_pass, no_batch_image — which of several equivalent paths
 // runs (tests hold each to the oracle); force_fallback, eps_scale_ppm, multi_fake_distinct — tests only.  The fields marked
 // [debug build] can be set by name only in a library built with -DOTT_MFMA_DEBUG_BUILD (kernel tuning / timing ablations);
 // the fields marked [fallback] are set through the bits of force_fallback.
@@ -182,6 +183,10 @@ struct Options {
     int sparse_df_lds = -1;       // document frequencies (ott_store_sparse_df): -1 = automatic (ott_sparse_plan.h: sparse_df_take_lds), 0 = global atomics always, 1 = a histogram in LDS wherever the vocab fits
     int sparse_table = -1;        // sparse queries (ott_query_sparse): where the weight lookup reads from: -1 = automatic (ott_sparse_plan.h),
                                   // 0 = the LDS form wherever it is eligible (vocab <= 32768), 1 = always the device table form
+    int binary_gate = -1;         // binary queries (ott_query_binary): which route answers: -1 = automatic (ott_binary_plan.h: binary_take_gate),
+                                  // 0 = always the key table, 1 = the gated sweep wherever it is eligible
+    int binary_gate_cap = 0;      // the gated sweep's pair capacity: 0 = the plan's (binary_gate_capacity), otherwise this many pairs (tests reach the overflow
+                                  // branch with it at a small shape)
 };
 void options_from_env(Options& o);                                   // ott_store.hip; called by ott_store_create only
 int option_set(Options& o, const char* name, long long value);       // 0, or -1 for an unknown name / bad value
@@ -445,6 +450,17 @@ struct ott_store {
     std::vector<uint32_t> df_host;
     uint64_t df_ndocs = 0;
     std::atomic<uint64_t> df_builds{0};
+    // Bit rows (ott_binary.hip).  d_binary: the transposed slice layout in one allocation (ott_binary_plan.h), made by
+    // ott_store_set_binary / ott_store_set_binary_sign and freed by ott_store_clear_binary; nullptr = no bit rows.  binary_n: the rows
+    // they cover (a query needs binary_n == n).  Owned by the store (workers alias d_binary), changed only under `rw` exclusive.
+    // d_bq / h_bq: THIS context's block of a call: chunk runs, query words, gate words and the pair cursor.  bin_ctr (owner only):
+    // gated calls, candidate pairs emitted, overflows, table-route calls (ott_store_binary_counters).
+    char* d_binary = nullptr;
+    uint64_t binary_n = 0;
+    uint32_t binary_bits = 0;
+    ott::DevBuf d_bq;
+    ott::PinBuf h_bq;
+    std::atomic<uint64_t> bin_ctr[4] = {};
 };
 
 namespace ott {
@@ -839,6 +855,7 @@ int check_ids(const char* who, const uint64_t* ids, uint64_t n_ids, uint64_t len
 int group_grow(ott_store* s, uint64_t ncap);
 int group_ids_of_hits(ott_store* s, const ott_hit* hits, uint64_t n, uint32_t* out);  // the groups of hits of this store: a gather from the resident ids
 void group_drop(ott_store* s);
+void binary_drop(ott_store* s);  // ott_binary.hip: the bit rows go (the caller holds the store exclusively, on its device)
 void sparse_drop(ott_store* s);  // ott_sparse.hip: the sparse rows go (the caller holds the store exclusively, on its device)
 // ott_sparse.hip, for ott_query_hybrid (ott_fuse.hip).  run_sparse_sweep: the sparse sweep on a context whose `mu` the caller holds
 // (and the owner's `rw`, shared); k_eff = min(k, rows the chunk mask leaves) >= 1, the queries checked against the store's vocab.

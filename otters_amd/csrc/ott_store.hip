@@ -28,14 +28,14 @@ struct OptName {
     const char* name;
     int kind;  // 0 = bool, 1 = tri-state (-1 automatic / 0 / 1), 2 = non-negative int
 };
-// the twenty-seven options of the product library (see struct Options) ...
+// the twenty-nine options of the product library (see struct Options) ...
 const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"hi_prebuild", 1},          {"stage_appends", 1},       {"multi_transport", 2},
                              {"multi_rebalance", 0}, {"multi_min_shard_rows", 2}, {"exact_small", 1},     {"large_k_from", 2},        {"small_sort", 1},
                              {"mfma_f32", 0},        {"no_hi_pass", 0},      {"no_batch_image", 0},       {"force_fallback", 2},      {"eps_scale_ppm", 2},
                              {"multi_fake_distinct", 0}, {"exact_prune", 1},            {"exact_sketch", 1},
                              {"id_gather", 1},       {"exact_sketch_bits", 2},   {"group_gather", 1},         {"exact_sketch_head", 1},
                              {"masks_sweep", 2},     {"fuse_device", 1},         {"sparse_table", 1},         {"exact_i8_check", 1},
-                             {"sparse_df_lds", 1},
+                             {"sparse_df_lds", 1},    {"binary_gate", 1},         {"binary_gate_cap", 2},
 #ifdef OTT_MFMA_DEBUG_BUILD
                              // ... and, in the diagnostic build only, kernel tuning, timing ablations and every fallback bit by its own name
                              {"mfma_wg", 2},         {"mfma_growth", 2},     {"mfma_debug", 0},           {"mfma_abl", 2},            {"hi_tmin", 2},
@@ -43,11 +43,11 @@ const OptName kOptNames[] = {{"tie_order", 2},       {"hi_fmt", 1},          {"h
                              {"merge_rank1", 1},     {"maxsim_fold", 1},
 #endif
 };
-static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 27
+static_assert(sizeof(kOptNames) / sizeof(kOptNames[0]) <= 29
 #ifdef OTT_MFMA_DEBUG_BUILD
                                                             + 12
 #endif
-              , "the product library's option table stays at twenty-seven entries");
+              , "the product library's option table stays at twenty-nine entries");
 }  // namespace
 
 int option_set(Options& o, const char* name, long long v) {
@@ -90,6 +90,8 @@ int option_set(Options& o, const char* name, long long v) {
     if (n == "fuse_device") return tri(o.fuse_device);
     if (n == "sparse_table") return tri(o.sparse_table);
     if (n == "sparse_df_lds") return tri(o.sparse_df_lds);
+    if (n == "binary_gate") return tri(o.binary_gate);
+    if (n == "binary_gate_cap") { if (v < 0 || v > 0x7FFFFFFF) return -1; o.binary_gate_cap = (int)v; return 0; }
     if (n == "masks_sweep") { if (v < 0 || v > 2) return -1; o.masks_sweep = (int)v; return 0; }
 #ifdef OTT_MFMA_DEBUG_BUILD
     if (n == "maxsim_fold") return tri(o.maxsim_fold);
@@ -692,6 +694,7 @@ int store_adopt(ott_store* s, float* rows, float* inv, uint8_t* flag, uint32_t* 
     live_drop(s);  // (the rows are other rows now: whoever moved them loads their live bits afterwards, live_load)
     group_drop(s); // (a store with group ids moves no rows: nothing to drop unless a caller forced the move)
     sparse_drop(s);  // (sparse rows are set on single-GPU stores only)
+    binary_drop(s);  // (... and so are bit rows)
     s->d_rows = rows;
     s->d_inv = inv;
     s->d_flag = flag;
@@ -847,6 +850,9 @@ static void alias_corpus(ott_store* w, const ott_store* s) {
     w->sparse_nnz = s->sparse_nnz;
     w->sparse_vocab = s->sparse_vocab;
     w->sparse_lay = s->sparse_lay;
+    w->d_binary = s->d_binary;
+    w->binary_n = s->binary_n;
+    w->binary_bits = s->binary_bits;
 }
 
 // the store's own context when it is free, else a worker context that aliases the corpus (ott::host::ContextPool)
@@ -943,9 +949,11 @@ int ott_store_destroy(ott_store* s) {
         s->d_gid = nullptr;
         s->d_gix = nullptr;
         s->d_sparse = nullptr;
+        s->d_binary = nullptr;
     }
     if (s->d_df) (void)hipFree(s->d_df);  // (the owner's alone: a worker builds into the owner's and never holds one)
     if (s->d_sparse) (void)hipFree(s->d_sparse);
+    if (s->d_binary) (void)hipFree(s->d_binary);
     if (s->d_gix) (void)hipFree(s->d_gix);
     if (s->d_live) (void)hipFree(s->d_live);
     if (s->d_gid) (void)hipFree(s->d_gid);
@@ -957,7 +965,7 @@ int ott_store_destroy(ott_store* s) {
     planes_release(s);  // (a worker has none of its own)
     mask_slots_drop(s); // (nor any mask slot)
     for (ott::DevBuf* b : {&s->d_queries, &s->d_qinv, &s->d_rowmask, &s->d_runs, &s->d_prefix, &s->d_lists, &s->d_lists2, &s->d_hits,
-                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_qmasks, &s->d_gather, &s->d_mmr, &s->d_fuse, &s->d_spq, &s->d_sptable, &s->d_rectable, &s->d_disc, &s->d_gtable, &s->d_gctl, &s->d_mstable, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
+                           &s->d_count, &s->d_cand, &s->d_misc, &s->d_prune, &s->d_tails, &s->d_evalmask, &s->d_livefx, &s->d_idmask, &s->d_qmasks, &s->d_gather, &s->d_mmr, &s->d_fuse, &s->d_spq, &s->d_sptable, &s->d_bq, &s->d_rectable, &s->d_disc, &s->d_gtable, &s->d_gctl, &s->d_mstable, &s->d_minpos, &s->m_Q, &s->m_qinv, &s->m_qnorm,
                            &s->m_tau, &s->m_cntA, &s->m_cntB, &s->m_candA, &s->m_candB, &s->m_over, &s->m_out, &s->m_outcnt,
                            &s->m_uncert, &s->m_prefix, &s->x_send, &s->x_recv, &s->l_keysA, &s->l_keysB, &s->l_qA, &s->l_qB, &s->l_tmp, &s->l_cursor, &s->l_hist, &s->l_gate, &s->l_ctl})
         b->release();
@@ -965,6 +973,7 @@ int ott_store_destroy(ott_store* s) {
     s->h_hits.release();
     s->h_fuse.release();
     s->h_spq.release();
+    s->h_bq.release();
     s->h_disc.release();
     s->h_hdr.release();
     s->h_pend.release();

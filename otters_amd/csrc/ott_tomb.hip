@@ -283,6 +283,8 @@ int ott_store_compact(ott_store* s, uint64_t* out_new_index) {
         return fail(OTT_ERR_UNSUPPORTED, "ott_store_compact: rows cannot move while group ids are set (ott_store_clear_groups first, set them again afterwards)");
     if (s->d_sparse)  // ... and so do sparse rows (ott_sparse.hip)
         return fail(OTT_ERR_UNSUPPORTED, "ott_store_compact: rows cannot move while sparse rows are set (ott_store_clear_sparse first, set them again afterwards)");
+    if (s->d_binary)  // ... and bit rows (ott_binary.hip)
+        return fail(OTT_ERR_UNSUPPORTED, "ott_store_compact: rows cannot move while bit rows are set (ott_store_clear_binary first, set them again afterwards)");
     int rc = store_flush_locked(s);
     if (rc) return rc;
     const uint64_t n = s->n;

@@ -25,7 +25,7 @@ from . import _native as N
 from ._native import OttersError
 from .col import Column, DataType, format_datetime, parse_datetime_millis
 from .expr import CmpOp, ColumnFilter, CompiledFilter, Expr, ExprError
-from .vec import GROUP_SIZE_MAX, BoostCombine, BoostTerm, Cmp, DiscoverPlan, FusePlan, HybridPlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, SparseQueryPlan, TakeType, VecStore, as_row_ids, boost_args, infer_default_take_type, mmr_args
+from .vec import GROUP_SIZE_MAX, BinaryQueryPlan, BoostCombine, BoostTerm, Cmp, DiscoverPlan, FusePlan, HybridPlan, Metric, Mode, Path, RecommendPlan, RecommendStrategy, ResolvedQuery, SparseQueryPlan, TakeType, VecStore, as_row_ids, boost_args, infer_default_take_type, mmr_args
 
 I32_MIN, I32_MAX = -(2 ** 31), 2 ** 31 - 1
 I64_MIN, I64_MAX = -(2 ** 63), 2 ** 63 - 1
@@ -273,6 +273,7 @@ class MetaStoreBuilder:  # src/meta.rs:62-306
         self.device = device
         self.devices = devices  # several GPUs of this process: one store over all of them (VecStore(devices=...))
         self.sparse = None      # with_sparse: (indptr, indices, values, vocab)
+        self.binary = None      # with_binary: (bits, n_bits); with_binary_sign: "sign"
 
     def with_vectors(self, vectors) -> "MetaStoreBuilder":
         self.vectors = vectors
@@ -308,6 +309,17 @@ class MetaStoreBuilder:  # src/meta.rs:62-306
         """extension: a sparse row per row, as CSR (VecStore.set_sparse), for MetaStore.sparse_query.  A sparse-only collection gives
         with_vectors a matrix of dim 1."""
         self.sparse = (indptr, indices, values, int(vocab))
+        return self
+
+    def with_binary(self, bits, n_bits: Optional[int] = None) -> "MetaStoreBuilder":
+        """extension: a bit row per row (VecStore.set_binary), for MetaStore.binary_query.  A binary-only collection gives
+        with_vectors a matrix of dim 1."""
+        self.binary = (bits, n_bits)
+        return self
+
+    def with_binary_sign(self) -> "MetaStoreBuilder":
+        """extension: bit rows made from the vectors' signs on the device (VecStore.set_binary_sign)."""
+        self.binary = "sign"
         return self
 
     def with_random_vectors(self, n_rows: int, dim: int, seed: int) -> "MetaStoreBuilder":
@@ -360,6 +372,10 @@ class MetaStoreBuilder:  # src/meta.rs:62-306
                 store.add_vectors(mat)
             if self.sparse is not None:
                 store.set_sparse(*self.sparse)
+            if self.binary == "sign":
+                store.set_binary_sign()
+            elif self.binary is not None:
+                store.set_binary(*self.binary)
         elif self.sparse is not None and len(self.sparse[0]) != n_rows + 1:
             raise OttersError(f"with_sparse: indptr has {len(self.sparse[0])} entries for {n_rows} rows")
         ingest = time.perf_counter() - t_ing
@@ -499,6 +515,11 @@ class MetaStore:  # src/meta.rs:48-60, 308-577
         """Hybrid search (VecStore.hybrid; ott_query_hybrid) with a meta_filter: one mask for the dense and the sparse legs of every
         request; .meta_filter(expr).idf().sparse_filter(...).take(k).collect()."""
         return MetaHybridPlan(self, dense_sets, sparse_sets, metric)
+
+    def binary_query(self, q_bits, n_bits: Optional[int] = None) -> "MetaBinaryPlan":
+        """Exact Hamming search (VecStore.binary_query; ott_query_binary) with a meta_filter: `q_bits` is one bit vector or a matrix
+        of them; .meta_filter(expr).take(k).collect() for one query, .collect_per_query() for a batch."""
+        return MetaBinaryPlan(self, q_bits, n_bits)
 
     def sparse_query(self, q) -> "MetaSparsePlan":
         """Exact sparse dot search (VecStore.sparse_query; ott_query_sparse) with a meta_filter: `q` is one (indices, values) pair or
@@ -1358,6 +1379,37 @@ class MetaSparsePlan(_MetaWrapper):
         if len(self._plan.queries) != 1:
             raise OttersError("ott_query_sparse: a batch needs OTT_MODE_PER_QUERY (a merged list over several sparse queries is not served)")
         return self.collect_per_query()[0]
+
+
+class MetaBinaryPlan(_MetaWrapper):
+    """Hamming search over a MetaStore (MetaStore.binary_query; VecStore.binary_query's contract): meta_filter prunes chunks by their
+    zone maps and masks rows on the device, exactly as the dense meta query does.  Errors surface at collect()."""
+
+    def __init__(self, store: MetaStore, q_bits, n_bits=None):
+        super().__init__(store, BinaryQueryPlan(store._store, q_bits, n_bits))
+
+    def collect_arrays(self):
+        """(hits, counts), as BinaryQueryPlan.collect_arrays returns them."""
+        if self.meta_error is not None:
+            raise OttersError(self.meta_error)
+        st = self.store
+        if st._store is None:
+            raise OttersError("binary_query: the store holds no vectors")
+        self._plan.vector_store = st._store
+        rb = self._plan.resolve()
+        got = _run_filtered(st, self._meta_filter, rb, "binary_query", st._store._run_binary)
+        return got if got is not None else (np.zeros(0, dtype=N.HIT_DTYPE), [0] * int(rb.words.shape[0]))
+
+    def collect_per_query(self):
+        """One MetaQueryResults per query: the hits' rows materialised as MetaQueryPlan.collect does, scores = the distances."""
+        return _materialise(self.store, *self.collect_arrays())
+
+    def collect(self):
+        """The MetaQueryResults of ONE query; a batch needs collect_per_query()."""
+        res = self.collect_per_query()
+        if len(res) != 1:
+            raise OttersError("ott_query_binary: a batch needs OTT_MODE_PER_QUERY (a merged list over several binary queries is not served)")
+        return res[0]
 
 
 class MetaDiscoverPlan(_MetaWrapper):

@@ -1316,6 +1316,115 @@ class SparseQueryPlan(_PathScorePlan):
         return self.collect_per_query()[0]
 
 
+BINARY_MAX_BITS = 16384         # include/otters_hip.h: OTT_BINARY_MAX_BITS
+BINARY_MAX_QUERIES = 1024       # include/otters_hip.h: OTT_BINARY_MAX_QUERIES
+
+
+def binary_words(bits, n_bits: Optional[int] = None, who: str = "set_binary"):
+    """Bit rows as the library takes them: (words uint64[n, ceil(n_bits / 64)], n_bits).  `bits` is a bool / 0-1 matrix [n, n_bits]
+    (bit j of a row goes to bit j % 64 of word j // 64) or packed uint64 words [n, W] with `n_bits` named (W == ceil(n_bits / 64);
+    without n_bits: 64 W).  One row may be given as a vector.  Padding bits are not touched: the library refuses a set one."""
+    a = np.asarray(bits)
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim != 2:
+        raise OttersError(f"{who}: bits must be a matrix (rows x bits, or rows x uint64 words)")
+    if a.dtype == np.uint64:
+        nb = 64 * a.shape[1] if n_bits is None else int(n_bits)
+        if a.shape[1] != (nb + 63) // 64:
+            raise OttersError(f"{who}: {a.shape[1]} words per row for n_bits = {nb}")
+        return np.ascontiguousarray(a), nb
+    if a.dtype != np.bool_:
+        if a.size and not np.isin(a, (0, 1)).all():
+            raise OttersError(f"{who}: a bit matrix holds only 0 and 1 (packed words are uint64)")
+        a = a.astype(bool)
+    nb = a.shape[1] if n_bits is None else int(n_bits)
+    if nb != a.shape[1]:
+        raise OttersError(f"{who}: {a.shape[1]} bits per row for n_bits = {nb}")
+    W = (nb + 63) // 64
+    packed = np.zeros((a.shape[0], W * 8), dtype=np.uint8)
+    if nb:
+        packed[:, : (nb + 7) // 8] = np.packbits(a, axis=1, bitorder="little")
+    return np.ascontiguousarray(packed).view("<u8").reshape(a.shape[0], W), nb
+
+
+def sign_bits(x) -> np.ndarray:
+    """ott_store_set_binary_sign's rule on the host: bit j = x[j] > 0.0 in f32 (NaN, -0.0 and +0.0 give 0; +denormals give 1)."""
+    with np.errstate(invalid="ignore"):
+        return np.asarray(x, dtype=np.float32) > np.float32(0.0)
+
+
+@dataclass
+class ResolvedBinary:
+    """What BinaryQueryPlan hands to ott_query_binary once it is validated."""
+    words: np.ndarray    # uint64[nq, ceil(n_bits / 64)]
+    n_bits: int
+    take: int
+    k: int
+    filter_cmp: int
+    filter_thr: float
+    row_mask: Optional[np.ndarray]
+    path: int
+    metric: int = int(Metric.Manhattan)  # the Hamming distance is the L1 distance of the bit vectors
+
+
+class BinaryQueryPlan(_PathScorePlan):
+    """Exact Hamming search over the store's bit rows (VecStore.binary_query; ott_query_binary): every row the masks leave is a
+    candidate, its score is popcount(q XOR v) as a float, the default take is Min.  Lazy like VecQueryPlan: errors surface at
+    collect()."""
+
+    def __init__(self, store: "VecStore", q_bits, n_bits: Optional[int] = None):
+        super().__init__()
+        self.vector_store = store
+        self.search_metric = Metric.Manhattan  # decides the default take: Min
+        self.q_bits = q_bits
+        self.n_bits = n_bits
+
+    def resolve(self) -> ResolvedBinary:
+        """Lower the plan.  Pure host logic, no GPU; the library checks the queries against the store's n_bits."""
+        words, nb = binary_words(self.q_bits, self.n_bits, "binary_query")
+        if words.shape[0] == 0:
+            raise OttersError("No queries provided")
+        take, k, fc, ft = self._lowered(len(self.vector_store))
+        return ResolvedBinary(words=words, n_bits=nb, take=take, k=k, filter_cmp=fc, filter_thr=ft, row_mask=self.row_mask, path=int(self.path))
+
+    def collect_arrays(self):
+        """(hits, counts): `hits` a NumPy record array (`index` u64, `score` f32 = the distance, `query`), every query's list best
+        first, back to back in query order; counts[b] = the hits of query b."""
+        store = self.vector_store
+        hits, counts, stats = store._run_binary(self.resolve())
+        store.last_stats = stats
+        return hits, counts
+
+    def collect_per_query(self):
+        """One list of SearchResult(index, score) per query."""
+        return split_results(*self.collect_arrays())
+
+    def collect(self):
+        """The hits of ONE query as a list of SearchResult(index, score); a batch needs collect_per_query()."""
+        hits, counts = self.collect_arrays()
+        if len(counts) != 1:
+            raise OttersError("ott_query_binary: a batch needs OTT_MODE_PER_QUERY (a merged list over several binary queries is not served)")
+        return split_results(hits, counts)[0]
+
+    def rescore(self, q_dense, metric: Metric, k: int):
+        """The binary-quantisation pipeline: this plan's take(fetch) is the oversampled first stage; for each query its ids are
+        re-scored by store.query(q_dense[b], metric).with_row_ids(ids).take(k) — the hits are by definition those of that call.
+        Runs on the host, ONE second-stage call per query.  Returns one list of SearchResult per query."""
+        q = np.asarray(q_dense, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        hits, counts = self.collect_arrays()
+        if q.shape[0] != len(counts):
+            raise OttersError(f"rescore: {q.shape[0]} dense queries for {len(counts)} binary queries")
+        store, out, o = self.vector_store, [], 0
+        for b, c in enumerate(counts):
+            ids = hits["index"][o:o + c]
+            o += c
+            out.append(store.query(q[b:b + 1], metric).with_row_ids(ids).take(k).collect() if c else [])
+        return out
+
+
 def hybrid_args(dense_per, sparse_per, fetch: int, fusion: int, rrf_k: float, weights, k: int) -> None:
     """ott_query_hybrid's argument refusals that the plan can raise (ott_hybrid_plan.h: hybrid_check_args), in its order and with
     its texts, before any native call."""
@@ -1785,6 +1894,72 @@ class VecStore:
         """How many times the document frequencies were built (ott_store_sparse_df_builds)."""
         return 0 if self._h is None else int(N.lib().ott_store_sparse_df_builds(self._h))
 
+    # -- bit rows (include/otters_hip.h: ott_store_set_binary, ott_query_binary) ------------------------------------------------
+    def set_binary(self, bits, n_bits: Optional[int] = None) -> None:
+        """A bit row per stored row: a bool / 0-1 matrix [len(), n_bits], or packed uint64 words [len(), ceil(n_bits / 64)] (bit j in
+        bit j % 64 of word j // 64, padding bits zero).  The store keeps them in HBM in slices of 64 transposed rows.  A second call
+        replaces the first; rows appended afterwards need a new call.  While bit rows are set, compact() is refused.  Not on a
+        multi-GPU store."""
+        words, nb = binary_words(bits, n_bits, "ott_store_set_binary")
+        if not 0 <= nb <= 0xFFFFFFFF:
+            raise OttersError(f"ott_store_set_binary: n_bits {nb} is not in 1 .. OTT_BINARY_MAX_BITS ({BINARY_MAX_BITS})")
+        N.check(N.lib().ott_store_set_binary(self._handle(), N.ptr(words) if words.size else None, int(words.shape[0]), nb))
+
+    def set_binary_sign(self) -> None:
+        """Bit rows from the dense rows, on the device: n_bits = dim, bit j of row r = (row[j] > 0.0) in f32 (NaN and both zeros
+        give 0): binary quantisation (ott_store_set_binary_sign).  Refused where dim > 16384."""
+        N.check(N.lib().ott_store_set_binary_sign(self._handle()))
+
+    def clear_binary(self) -> None:
+        if self._h is not None:
+            N.check(N.lib().ott_store_clear_binary(self._h))
+
+    def binary_info(self) -> Optional[dict]:
+        """{n_bits, bytes} of the bit rows in HBM, None when none are set."""
+        if self._h is None:
+            return None
+        nb, nbytes = C.c_uint32(0), C.c_uint64(0)
+        N.check(N.lib().ott_store_binary_info(self._h, C.byref(nb), C.byref(nbytes)))
+        if nb.value == 0:
+            return None
+        return {"n_bits": int(nb.value), "bytes": int(nbytes.value)}
+
+    def read_binary(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """uint64[n, ceil(n_bits / 64)]: the words of bit rows [first, first + n), read back from the device layout bit for bit."""
+        info = self.binary_info()
+        if info is None:
+            raise OttersError("ott_store_read_binary: no bit rows are set (ott_store_set_binary)")
+        n = self._n - first if n is None else n
+        out = np.zeros((max(n, 0), (info["n_bits"] + 63) // 64), dtype=np.uint64)
+        N.check(N.lib().ott_store_read_binary(self._h, int(first), int(n), N.ptr(out) if out.size else None))
+        return out
+
+    def binary_counters(self) -> dict:
+        """{gated_calls, pairs_emitted, overflows, table_calls}: running totals of this store's binary queries (ott_store_binary_counters)."""
+        out = (C.c_uint64 * 4)()
+        if self._h is not None:
+            N.check(N.lib().ott_store_binary_counters(self._h, out))
+        return dict(zip(("gated_calls", "pairs_emitted", "overflows", "table_calls"), (int(x) for x in out)))
+
+    def binary_query(self, q_bits, n_bits: Optional[int] = None) -> BinaryQueryPlan:
+        """Exact Hamming search (ott_query_binary): `q_bits` is one bit vector or a matrix of them (bool / 0-1), or packed uint64
+        words with `n_bits`.  .take(k).collect() for one query, .collect_per_query() for a batch; the default take is Min."""
+        return BinaryQueryPlan(self, q_bits, n_bits)
+
+    def binary_query_sign(self, q_dense) -> BinaryQueryPlan:
+        """binary_query for the sign bits of dense queries, packed on the host by set_binary_sign's rule."""
+        return BinaryQueryPlan(self, sign_bits(q_dense))
+
+    def _run_binary(self, rb: ResolvedBinary, chunk_mask: Optional[np.ndarray] = None, use_device_row_mask: bool = False):
+        """ott_query_binary.  Returns (hits HIT_DTYPE array, per-query counts, stats dict)."""
+        nq = int(rb.words.shape[0])
+        cap = max(nq * min(rb.k, self._n), 1)
+        out = np.empty(cap, dtype=N.HIT_DTYPE)
+        d, keep = query_desc(rb, None, nq, Mode.PerQuery if nq > 1 else Mode.Merged, chunk_mask, use_device_row_mask)
+        n_out, per, st = C.c_uint64(0), (C.c_uint64 * max(nq, 1))(), N.Stats()
+        N.check(N.lib().ott_query_binary(self._handle(), C.byref(d), N.ptr(rb.words), N.ptr(out), cap, C.byref(n_out), per, C.byref(st)))
+        return out[: n_out.value].copy(), list(per)[:nq], st.as_dict()
+
     def hybrid(self, dense_sets, sparse_sets, metric: Metric) -> HybridPlan:
         """Hybrid search (ott_query_hybrid): `dense_sets` a sequence of [legs, dim] matrices and `sparse_sets` a sequence of lists of
         (indices, values) pairs, one of each per request (None or empty = no leg of that kind);
@@ -1854,7 +2029,7 @@ class VecStore:
         return int(N.lib().ott_store_exact_finished(self._handle()))
 
     def set_option(self, name: str, value: int) -> None:
-        """Behaviour switch of this store (ott_store_set_option; the twenty-seven names are listed in include/otters_hip.h:
+        """Behaviour switch of this store (ott_store_set_option; the twenty-nine names are listed in include/otters_hip.h:
         "tie_order", "hi_fmt", "hi_prebuild", ..., "force_fallback").  Results never depend on any but "tie_order"."""
         self._options[name] = int(value)
         if self._h is not None:
