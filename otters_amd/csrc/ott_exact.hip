@@ -1590,11 +1590,10 @@ constexpr uint32_t MS_NVAL = 8192;   // ordinals the bound is selected from (n_l
 constexpr uint32_t MS_CAP = 2048;
 constexpr size_t MS_SMEM = (size_t)(MS_NVAL + 256 + 8) * 4 + (size_t)MS_CAP * sizeof(Cand);
 
+// (the merge itself: one copy of its text for the two kernels below)
 template <int E>
-__global__ __launch_bounds__(1024) void merge_rank_kernel(const Cand* lists, uint32_t n_lists, uint32_t list_stride, uint64_t group_stride, uint32_t k,
-                                                           uint32_t take_max, uint64_t base, ott_hit* out, uint64_t out_stride, uint64_t* counts,
-                                                           uint32_t tie_sh) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+__device__ __forceinline__ void merge_rank(float* smem, const Cand* lists, uint32_t n_lists, uint32_t list_stride, uint64_t group_stride, uint32_t k,
+                                           uint32_t take_max, uint64_t base, ott_hit* out, uint64_t out_stride, uint64_t* counts, uint32_t tie_sh) {
     constexpr uint32_t KS = 64 * E;
     uint32_t* s_vals = reinterpret_cast<uint32_t*>(smem);  // [MS_NVAL] the score ordinals of the lists' first j entries
     uint32_t* s_hist = s_vals + MS_NVAL;                   // [256]
@@ -1677,6 +1676,28 @@ __global__ __launch_bounds__(1024) void merge_rank_kernel(const Cand* lists, uin
         __syncthreads();  // the LDS is about to be reused
     }
     merge_walk<E, false>(smem, lists, n_lists, list_stride, group_stride, k, take_max, base, out, out_stride, counts, (Cand*)nullptr, 1u, tie_sh);
+}
+
+template <int E>
+__global__ __launch_bounds__(1024) void merge_rank_kernel(const Cand* lists, uint32_t n_lists, uint32_t list_stride, uint64_t group_stride, uint32_t k,
+                                                           uint32_t take_max, uint64_t base, ott_hit* out, uint64_t out_stride, uint64_t* counts,
+                                                           uint32_t tie_sh) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    merge_rank<E>(smem, lists, n_lists, list_stride, group_stride, k, take_max, base, out, out_stride, counts, tie_sh);
+}
+
+// The same launch for k <= 64 as the pruned sweep's final merge on host output (ott_exact_plan.h: prune_plan_ride): it also leaves
+// the sweep's two counter totals (`tails`: final when this kernel starts, it is stream-ordered behind the gated launch) at
+// `totals`, behind the result block in pinned host memory, so no copy is queued behind the merge
+__global__ __launch_bounds__(1024) void merge_rank_totals_kernel(const Cand* lists, uint32_t n_lists, uint32_t list_stride, uint64_t group_stride, uint32_t k,
+                                                                  uint32_t take_max, uint64_t base, ott_hit* out, uint64_t out_stride, uint64_t* counts,
+                                                                  uint32_t tie_sh, unsigned long long* tails, unsigned long long* totals) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        totals[0] = __hip_atomic_load(tails, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        totals[1] = __hip_atomic_load(tails + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    merge_rank<1>(smem, lists, n_lists, list_stride, group_stride, k, take_max, base, out, out_stride, counts, tie_sh);
 }
 
 // merge_small_kernel: the same merge for k <= 64 (one list entry per lane), i.e. every top-10 call.  What cost merge_kernel<1> its
@@ -2130,7 +2151,15 @@ int launch_exact(ott_store* s, const ExactParams& p, int nq_tile, int E, int gri
 
 int launch_merge(ott_store* s, const Cand* lists, uint32_t n_lists, uint32_t list_stride, uint64_t group_stride,
                  uint32_t groups, uint32_t k, int E, bool take_max, uint64_t base_offset, ott_hit* out_hits,
-                 uint64_t out_stride, uint64_t* out_counts, uint32_t tie_sh) {
+                 uint64_t out_stride, uint64_t* out_counts, uint32_t tie_sh, unsigned long long* tails, unsigned long long* totals) {
+    if (totals != nullptr) {  // (ott_exact_plan.h: prune_plan_ride — k <= 64 and the merge options at their defaults)
+        if (E != 1 || tails == nullptr || s->opt.merge_rank1 == 0 || s->opt.merge_walk || n_lists > MS_VMAX)
+            return fail(OTT_ERR_INVALID, "launch_merge: the counters ride with the rank merge of k <= 64 only");
+        hipLaunchKernelGGL(merge_rank_totals_kernel, dim3(groups), dim3(1024), MS_SMEM, s->stream, lists, n_lists, list_stride, group_stride, k, take_max ? 1u : 0u,
+                           base_offset, out_hits, out_stride, out_counts, tie_sh, tails, totals);
+        OTT_HIP(hipGetLastError());
+        return OTT_OK;
+    }
     if (E == 1 && !(s->opt.merge_rank1 != 0 && !s->opt.merge_walk && n_lists <= MS_VMAX)) {  // option merge_rank1 = 0: k <= 64 through sorted heads + tree fold (round 2's merge)
         hipLaunchKernelGGL(merge_small_kernel, dim3(groups), dim3(64 * MERGE_WAVES), 0, s->stream, lists, n_lists, list_stride, group_stride, k,
                            take_max ? 1u : 0u, base_offset, out_hits, out_stride, out_counts, tie_sh);

@@ -251,6 +251,22 @@ inline uint32_t prune_seed_keep(uint64_t k) {
     if (OTT_X_SEED_KEEP > 0) return OTT_X_SEED_KEEP < 64 ? (uint32_t)OTT_X_SEED_KEEP : 64u;
     return k < SEED_EST_KEEP_MAX ? (uint32_t)k : SEED_EST_KEEP_MAX;
 }
+// The counters ride in the result block ("the counters ride").  On host output the sweep's two counter totals
+// are wanted beside the hits.  Behind an estimate pass — head form, k <= 64, no score filter, a store from 1 310 720 rows — and with
+// the rank merge (the merge options at their defaults) the final merge launch writes the totals behind the hits it writes into the
+// pinned block: no copy is queued behind the merge, and no timing marker stands between the gated launch and its merge
+// (ott_stats.score_ns then spans the chain, the merges included, and merge_ns is 0).  Otherwise the call is the one with the copy
+// and the marker, to the launch.  Experiment builds: -DOTT_X_RIDE=0 never plans it.
+#ifndef OTT_X_RIDE
+#define OTT_X_RIDE 1
+#endif
+struct MergeOptions {
+    int merge_rank1;  // store option merge_rank1 (-1 / 1: the rank merge, 0: round 2's merge)
+    bool merge_walk;  // store option merge_walk
+};
+inline bool prune_plan_ride(uint64_t est_rows, int E, bool fetch, const MergeOptions& mo) {
+    return OTT_X_RIDE != 0 && est_rows != 0 && E == 1 && fetch && mo.merge_rank1 != 0 && !mo.merge_walk;
+}
 inline PrunePlan prune_plan_quant_refused(PruneIn in) {
     in.exact_sketch = 0;
     return prune_plan(in);

@@ -698,7 +698,8 @@ int exact_grid(const ott_store* s, uint32_t n_tiles);
 // out_hits[g*out_stride ...] and out_counts[g]
 int launch_merge(ott_store* s, const Cand* lists, uint32_t n_lists, uint32_t list_stride, uint64_t group_stride,
                  uint32_t groups, uint32_t k, int E, bool take_max, uint64_t base_offset, ott_hit* out_hits,
-                 uint64_t out_stride, uint64_t* out_counts, uint32_t tie_sh);
+                 uint64_t out_stride, uint64_t* out_counts, uint32_t tie_sh, unsigned long long* tails = nullptr, unsigned long long* totals = nullptr);
+// (totals != nullptr: the pruned sweep's final merge on host output — the launch also copies the two counters at `tails` to `totals`)
 
 // hdr_slots: ott_hit-sized header slots behind every rank's [n_groups][list_len] hits (the blocks of ott_query_sharded); they are
 // copied to hdr_out ([n_lists][hdr_slots], e.g. pinned host memory) by the same launch
