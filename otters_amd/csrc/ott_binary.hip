@@ -280,18 +280,7 @@ int binary_build(ott_store* s, const uint64_t* words, uint64_t n, uint32_t n_bit
     return OTT_OK;
 }
 
-// the layout bytes of the slices the chunk runs touch (a slice two runs share counts once)
-uint64_t binary_run_bytes(uint32_t units, const RunPlan& pl) {
-    uint64_t bytes = 0, done = 0;  // slices below `done` are counted
-    for (const ott_run& r : pl.runs) {
-        uint64_t t0 = r.start / BINARY_SLICE;
-        const uint64_t t1 = (r.start + r.count + BINARY_SLICE - 1) / BINARY_SLICE;
-        if (t0 < done) t0 = done;
-        if (t1 > t0) bytes += binary_range_bytes(t0 * BINARY_SLICE, t1 * BINARY_SLICE, units);
-        if (t1 > done) done = t1;
-    }
-    return bytes;
-}
+static_assert(sizeof(ott_run) == 16 && offsetof(ott_run, start) == 0 && offsetof(ott_run, count) == 8, "binary_run_bytes reads a run as a (start, count) pair");
 
 template <int NQ>
 int launch_table(ott_store* s, const BinaryParams& p) {
@@ -370,7 +359,7 @@ int run_binary_sweep(ott_store* s, const ott_query_desc* d, const uint64_t* q_wo
         p.cursor = (unsigned long long*)((char*)s->d_bq.p + off_cur);
         p.k = (uint32_t)std::min<uint64_t>(k_eff, BINARY_GATE_MAX_K);
         const bool timing = stats_out != nullptr;
-        const uint64_t run_bytes = binary_run_bytes(units, pl);
+        const uint64_t run_bytes = binary_run_bytes((const uint64_t*)pl.runs.data(), pl.runs.size(), units);
         bool done = false;
 
         // (a context that cannot allocate the pair arrays answers on the table route, which needs none)

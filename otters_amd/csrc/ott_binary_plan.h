@@ -190,6 +190,20 @@ inline uint64_t binary_range_bytes(uint64_t row0, uint64_t row1, uint32_t units)
     if (row1 <= row0) return 0;
     return ((row1 + BINARY_SLICE - 1) / BINARY_SLICE - row0 / BINARY_SLICE) * binary_slice_bytes(units);
 }
+// the layout bytes of the slices the chunk runs touch (a slice two runs share counts once).  runs: n_runs (start, count) pairs of
+// rows, ascending and disjoint (ott_run's two fields)
+inline uint64_t binary_run_bytes(const uint64_t* runs, size_t n_runs, uint32_t units) {
+    uint64_t bytes = 0, done = 0;  // slices below `done` are counted
+    for (size_t i = 0; i < n_runs; i++) {
+        const uint64_t start = runs[2 * i], count = runs[2 * i + 1];
+        uint64_t t0 = start / BINARY_SLICE;
+        const uint64_t t1 = (start + count + BINARY_SLICE - 1) / BINARY_SLICE;
+        if (t0 < done) t0 = done;
+        if (t1 > t0) bytes += binary_range_bytes(t0 * BINARY_SLICE, t1 * BINARY_SLICE, units);
+        if (t1 > done) done = t1;
+    }
+    return bytes;
+}
 inline uint64_t binary_bytes_scanned(uint32_t passes, uint64_t slice_bytes) { return (uint64_t)passes * slice_bytes; }
 
 // ---- the route ------------------------------------------------------------------------------------------------------------------------------

@@ -112,6 +112,18 @@ def range_bytes(row0, row1, n_units):
     return 0 if row1 <= row0 else ((row1 + SLICE - 1) // SLICE - row0 // SLICE) * n_units * SLICE * UNIT_BYTES
 
 
+def run_bytes(rows, n_units):
+    """what a pass over the kept rows reads (stats.bytes_scanned per pass): a slice is read whole when any kept row lies in it, and
+    once.  rows: the kept row indices, a bool mask over the rows, or (start, count) runs as an int array [n, 2]"""
+    rows = np.asarray(rows)
+    if rows.dtype == np.bool_:
+        rows = np.flatnonzero(rows)
+    elif rows.ndim == 2:
+        rows = np.concatenate([np.arange(s, s + c, dtype=np.int64) for s, c in rows.astype(np.int64)] + [np.zeros(0, np.int64)])
+    slices = set((rows.astype(np.int64) // SLICE).tolist())
+    return len(slices) * n_units * SLICE * UNIT_BYTES
+
+
 def layout_image(row_words, n_bits):
     """the device layout of the rows as bytes: what ott_store_set_binary uploads"""
     row_words = np.asarray(row_words, np.uint64)

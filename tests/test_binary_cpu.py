@@ -143,6 +143,22 @@ int main(int argc, char** argv) {
         for (uint32_t i = 0; i < m; i++) printf("%s%u", i ? ", " : "", binary_sign_bit(x[i]));
         printf("], \"bad_padding\": %llu", (unsigned long long)binary_first_bad_padding(rowsv.data(), n, nb));
     }
+    // binary_run_bytes on the caller's run sets: argv[3] = a file of u32 n_sets, then per set u32 units, u32 n_runs, (start, count) u64 pairs
+    if (argc > 3) {
+        FILE* f = fopen(argv[3], "rb");
+        uint32_t n_sets = 0;
+        if (!f || fread(&n_sets, 4, 1, f) != 1) return 3;
+        printf(", \"run_bytes\": [");
+        for (uint32_t i = 0; i < n_sets; i++) {
+            uint32_t units = 0, n_runs = 0;
+            if (fread(&units, 4, 1, f) != 1 || fread(&n_runs, 4, 1, f) != 1) return 3;
+            std::vector<uint64_t> runs((size_t)n_runs * 2);  // (exactly n_runs pairs: a read past them is the sanitizer's to find)
+            if (fread(runs.data(), 8, runs.size(), f) != runs.size()) return 3;
+            printf("%s%llu", i ? ", " : "", (unsigned long long)binary_run_bytes(runs.data(), n_runs, units));
+        }
+        fclose(f);
+        printf("]");
+    }
     printf("}\n");
     return 0;
 }
@@ -165,11 +181,44 @@ def probe(tmp_path_factory):
     x = np.array([np.nan, 0.0, -0.0, 1e-45, -1e-45, 2.5, -2.5, np.inf, -np.inf], np.float32)
     fin = d / "data.bin"
     fin.write_bytes(np.array([nb, n], "<u4").tobytes() + rows.tobytes() + q.tobytes() + np.array([x.size], "<u4").tobytes() + x.tobytes())
-    out = subprocess.run([str(exe), str(fin), "data"], capture_output=True, text=True)
+    sets = run_sets(np.random.default_rng(6))
+    frun = d / "runs.bin"
+    frun.write_bytes(np.array([len(sets)], "<u4").tobytes() + b"".join(np.array([u, r.shape[0]], "<u4").tobytes() + r.astype("<u8").tobytes() for u, r in sets))
+    out = subprocess.run([str(exe), str(fin), "data", str(frun)], capture_output=True, text=True)
     assert out.returncode == 0, (out.returncode, out.stdout, out.stderr)
     got = json.loads(out.stdout)
     got["_data"] = (rows, q, x, nb)
+    got["_run_sets"] = sets
     return got
+
+
+def runs_from(counts, gaps, first=0):
+    """(start, count) runs [n, 2], ascending: run i holds counts[i] rows, gaps[i] >= 1 rows lie between run i - 1 and run i"""
+    counts, gaps = np.asarray(counts, np.int64), np.asarray(gaps, np.int64)
+    assert (counts >= 1).all() and (gaps[1:] >= 1).all()
+    ends = np.cumsum(counts + gaps) + first
+    return np.stack([ends - counts, counts], axis=1)
+
+
+def run_sets(rng):
+    """[(units, runs)]: hand-made run sets that name each case, then random ones.  Runs are what make_run_plan gives: ascending,
+    disjoint, at least one row apart"""
+    sets = [(1, np.zeros((0, 2), np.int64)),                                            # no run
+            (3, np.array([[0, 1]])), (3, np.array([[63, 1]])), (3, np.array([[63, 2]])),  # single rows; a run that crosses a slice edge
+            (2, np.array([[0, 64]])), (2, np.array([[1, 64]])), (2, np.array([[64, 64], [130, 1]])),
+            (5, np.array([[0, 8], [16, 8], [32, 8], [48, 8]])),                          # four runs share slice 0
+            (5, np.array([[60, 8], [70, 1], [72, 1], [127, 2], [129, 1]])),              # every slice shared with the run before
+            (1, np.array([[10, 1], [12, 300], [313, 1], [1000, 1]])),                    # a long run between single rows of its own slices
+            (128, np.array([[0, 5000]])), (128, np.array([[2 ** 32 - 17 - 64, 64]])),    # the widest row; the last rows a store may hold
+            (7, runs_from(np.full(313, 8), np.full(313, 8))),                            # every second chunk of 8 rows: 313 runs
+            (7, runs_from(np.full(50, 100), np.full(50, 600), first=3)), (7, runs_from(np.full(5, 1021), np.full(5, 1021)))]
+    for _ in range(60):
+        n = int(rng.integers(1, 40))
+        kind = int(rng.integers(4))
+        counts = (np.ones(n, np.int64), rng.integers(1, 10, n), rng.integers(1, 200, n), rng.integers(1, 3000, n))[kind]
+        gaps = rng.integers(1, (3, 20, 200, 70)[kind], n)
+        sets.append((int(rng.integers(1, 129)), runs_from(counts, gaps, first=int(rng.integers(0, 200)) + (2 ** 32 - 2 ** 20 if kind == 3 and n % 2 else 0))))
+    return sets
 
 
 def test_plan_header_unit_counts_and_offsets(probe):
@@ -230,6 +279,25 @@ def test_plan_header_hamming_and_sign_rule(probe):
     assert probe["hamming"] == BR.distances(rows, q)[0].tolist()
     assert probe["sign"] == BR.sign_bits(x).astype(int).tolist() == [0, 0, 0, 1, 0, 1, 0, 1, 0]
     assert probe["bad_padding"] == rows.shape[0]  # none
+
+
+def test_plan_header_run_bytes_a_slice_two_runs_share_counts_once(probe):
+    """binary_run_bytes (what stats.bytes_scanned reports per pass) against the model's count of distinct slices, which knows no
+    runs: single rows, several runs in one slice, a slice shared with the run before, runs that end on a slice's edge"""
+    sets = probe["_run_sets"]
+    want = [BR.run_bytes(r, u) for u, r in sets]
+    assert probe["run_bytes"] == want
+    assert want[:8] == [0, 3072, 3072, 6144, 2048, 4096, 4096, 5120] and want[8] == 3 * 5120 and want[9] == 6 * 1024
+    shared = sum(1 for u, r in sets if r.shape[0] > 1 and ((r[1:, 0] // 64) == ((r[:-1, 0] + r[:-1, 1] - 1) // 64)).any())
+    assert shared > 30 and max(r.shape[0] for _, r in sets) == 313
+    # the model's three forms of `rows` agree
+    u, r = sets[8]
+    rows = np.concatenate([np.arange(s, s + c) for s, c in r])
+    keep = np.zeros(200, bool)
+    keep[rows] = True
+    assert BR.run_bytes(rows, u) == BR.run_bytes(keep, u) == want[8]
+    # ... and a range of whole slices is binary_range_bytes
+    assert BR.run_bytes(np.array([[64, 640]]), 9) == BR.range_bytes(64, 704, 9)
 
 
 # ---- the gated sweep, simulated ------------------------------------------------------------------------------------------------------------
